@@ -7,6 +7,7 @@ BS/util.cuh:105-130); it does not go through the reference's
 preprocessing kernels and it uses nothing but numpy.
 """
 import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -164,7 +165,8 @@ class SyntheticStack:
 
     def __init__(self, num_keyframes, width=640, height=480, cell=4, seed=0xBAD51A4,
                  fx=525.0, fy=525.0, cx=320.0, cy=240.0, raw_to_float_depth=1.0 / 5000, baseline_fx=40.0,
-                 translation_range=None, rotation_range=None, plane_count=20, surfel_noise=0.002, kind="dense"):
+                 translation_range=None, rotation_range=None, plane_count=20, surfel_noise=0.002, kind="dense", threads=1):
+        """threads > 1: each keyframe's image is rendered in that many bands of rows at once; the stack is the same."""
         rng = np.random.default_rng(seed)
         self.kind = kind
         if kind in POSE_RANGES:
@@ -188,6 +190,15 @@ class SyntheticStack:
         self.t = []
         surf = []
         cw, ch = (width - 1) // cell + 1, (height - 1) // cell + 1
+        # per-pixel products of the keyframe being rendered, filled band by band (rows [lo, hi)); the surfel noise below draws
+        # from rng in keyframe order on the calling thread, so the stack does not depend on `threads`
+        valid = np.zeros((height, width), bool)
+        z = np.zeros((height, width), np.float32)
+        bestn = np.zeros((height, width, 3), np.float64)
+        r2 = np.zeros((height, width), np.float16)
+        rows = -(-height // max(1, threads))
+        bands = [(lo, min(height, lo + rows)) for lo in range(0, height, rows)]
+        pool = ThreadPoolExecutor(len(bands)) if len(bands) > 1 else None
         for k in range(num_keyframes):
             if kind == "trajectory":
                 R, t = trajectory_pose(k, num_keyframes)
@@ -196,33 +207,12 @@ class SyntheticStack:
                 R, t = se3_exp(xi)
             self.R.append(R)
             self.t.append(t)
-            dg = dirs @ R.T
-            # nearest front-facing plane per pixel, all planes at once (first plane wins ties, as a plane-by-plane sweep would)
-            denom = dg @ plane_matrix.T                                  # [h, w, planes]
             num = -(plane_d + plane_matrix @ t)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                tt = num[None, None, :] / denom
-            tt = np.where((denom < 0) & (tt > 0.3), tt, np.inf)
-            which = np.argmin(tt, axis=2)
-            best = np.take_along_axis(tt, which[..., None], axis=2)[..., 0]
-            bestn = np.where(np.isfinite(best)[..., None], plane_matrix[which], 0.0)
-            valid = np.isfinite(best) & (best < 6.0)
-            valid[0, :] = valid[-1, :] = False
-            valid[:, 0] = valid[:, -1] = False
-            d16 = np.where(valid, best / float(raw_to_float_depth) + 0.5, 65535).astype(np.uint32)
-            valid &= d16 < 32768
-            d16 = np.where(valid, d16, 65535).astype(np.uint16)
-            self.depth[k] = d16
-            n_cam = (bestn @ R).astype(np.float32)          # R^T n, rows
-            self.normals[k] = np.where(valid, s8_pack(n_cam[..., 0], n_cam[..., 1]), 0).astype(np.uint16)
-            z = (d16.astype(np.float32) * self.raw_to_float_depth)
-            r2 = np.where(valid, (z / np.float32(fx)) ** 2, 0).astype(np.float16)
-            self.radius[k] = r2.view(np.uint16)
-            pts = t[None, None, :] + dg * np.where(valid, best, 0.0)[..., None]
-            lum = (np.sin(7.0 * pts[..., 0] + 0.37) + np.sin(9.0 * pts[..., 1] + 0.5) + np.sin(11.0 * pts[..., 2] + 0.7)
-                   + 0.5 * np.sin(23.0 * (pts[..., 0] + pts[..., 1])) + 0.5 * np.cos(17.0 * (pts[..., 1] - pts[..., 2])))
-            lum = np.clip((lum + 4.0) / 8.0 * 255.0, 0, 255).astype(np.uint8)
-            self.color[k] = np.repeat(lum[:, :, None], 4, axis=2)
+            args = (k, R, t, num, dirs, plane_matrix, raw_to_float_depth, fx, valid, z, bestn, r2)
+            if pool is None:
+                self._render_rows(*args, 0, height)
+            else:
+                list(pool.map(lambda band: self._render_rows(*args, *band), bands))
             # cell-4 surfel creation without merge: first pixel of each cell, if valid
             yy, xx = np.meshgrid(np.arange(ch) * cell + 1, np.arange(cw) * cell + 1, indexing="ij")
             yy = np.minimum(yy, height - 2)
@@ -237,9 +227,46 @@ class SyntheticStack:
             s[3] = s10_pack(bestn[yy, xx][v].astype(np.float32)).view(np.float32)
             s[4] = r2[yy, xx][v].astype(np.float32)
             surf.append(s)
+        if pool is not None:
+            pool.shutdown()
         self.surfels = np.ascontiguousarray(np.concatenate(surf, axis=1))
         self.surfels_size = self.surfels.shape[1]
         self.cfactor = np.zeros(((height - 1) // cell + 1, (width - 1) // cell + 1), np.float32)
+
+    def _render_rows(self, k, R, t, num, dirs, plane_matrix, raw_to_float_depth, fx, valid, z, bestn, r2, lo, hi):
+        """Image rows [lo, hi) of keyframe k: depth, normals, radius and colour into the stack, and the per-pixel valid / z / bestn /
+        r2 the surfel creation reads.  Every operation is per pixel or per image row, so a band gives the same bits as the whole
+        image (numpy's matmul of [rows, w, 3] stacks is one BLAS call per row)."""
+        dg = dirs[lo:hi] @ R.T
+        # nearest front-facing plane per pixel, all planes at once (first plane wins ties, as a plane-by-plane sweep would)
+        denom = dg @ plane_matrix.T                                  # [rows, w, planes]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            tt = num[None, None, :] / denom
+        tt = np.where((denom < 0) & (tt > 0.3), tt, np.inf)
+        which = np.argmin(tt, axis=2)
+        best = np.take_along_axis(tt, which[..., None], axis=2)[..., 0]
+        bn = np.where(np.isfinite(best)[..., None], plane_matrix[which], 0.0)
+        v = np.isfinite(best) & (best < 6.0)
+        if lo == 0:
+            v[0, :] = False
+        if hi == self.height:
+            v[-1, :] = False
+        v[:, 0] = v[:, -1] = False
+        d16 = np.where(v, best / float(raw_to_float_depth) + 0.5, 65535).astype(np.uint32)
+        v &= d16 < 32768
+        d16 = np.where(v, d16, 65535).astype(np.uint16)
+        self.depth[k, lo:hi] = d16
+        n_cam = (bn @ R).astype(np.float32)          # R^T n, rows
+        self.normals[k, lo:hi] = np.where(v, s8_pack(n_cam[..., 0], n_cam[..., 1]), 0).astype(np.uint16)
+        zb = (d16.astype(np.float32) * self.raw_to_float_depth)
+        r2b = np.where(v, (zb / np.float32(fx)) ** 2, 0).astype(np.float16)
+        self.radius[k, lo:hi] = r2b.view(np.uint16)
+        pts = t[None, None, :] + dg * np.where(v, best, 0.0)[..., None]
+        lum = (np.sin(7.0 * pts[..., 0] + 0.37) + np.sin(9.0 * pts[..., 1] + 0.5) + np.sin(11.0 * pts[..., 2] + 0.7)
+               + 0.5 * np.sin(23.0 * (pts[..., 0] + pts[..., 1])) + 0.5 * np.cos(17.0 * (pts[..., 1] - pts[..., 2])))
+        lum = np.clip((lum + 4.0) / 8.0 * 255.0, 0, 255).astype(np.uint8)
+        self.color[k, lo:hi] = np.repeat(lum[:, :, None], 4, axis=2)
+        valid[lo:hi], z[lo:hi], bestn[lo:hi], r2[lo:hi] = v, zb, bn, r2b
 
     def pose(self, k, xi=None):
         """(global_T_frame as SE3f, frame_T_global 3x4, global_R_frame) of keyframe k, optionally * exp(xi)."""

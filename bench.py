@@ -10,15 +10,19 @@ batched pose Gauss-Newton, every keyframe restarted from a 5 mm / 1 mrad perturb
 evaluated are counted (the activation pass stops at a surfel's first associated keyframe, the geometry passes skip
 inactive surfels, converged keyframes leave the pose loop).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 N > 1: one rank per GPU.  Started under a launcher (torch.distributed.run: WORLD_SIZE / RANK / LOCAL_RANK in the environment)
 this process IS one rank; started bare, it spawns the N ranks itself as fresh child processes -- before anything in the parent
 touches a GPU -- relays rank 0's JSON line and fails if any rank fails.  Surfels are sharded, keyframes replicated, the K x 32
 coefficient rows are all-reduced over RCCL once per batched GN iteration.  `value` is the weak-scaled configs[2] workload
-(every rank owns a full 5.76 M-surfel shard; N = 1 is the single-GPU headline); `config.strong` is the FIXED configs[4]
-problem (1000 keyframes x 19.2 M surfels, geometry only) split over the N ranks with shard_range.  On one GPU the line also
-carries `config.secondary` (configs[1]: 50 keyframes, geometry only), `config.trajectory` and `config.survey` (the other two
-stacks of SURVEY.md 8d), a `pcg` block (PCG scheme) and `cpu_baseline` (the oracle on the host cores, N threads and 1 thread).
+(every rank owns a full 5.76 M-surfel shard; N = 1 is the single-GPU headline).
+
+A plain run measures the headline block and nothing else.  `--full` adds the pair census and the `roofline` block, and
+`config.strong`, the FIXED configs[4] problem (1000 keyframes x 19.2 M surfels, geometry only) split over the N ranks with
+shard_range.  On one GPU a `--full` line also carries `config.secondary` (configs[1]: 50 keyframes, geometry only),
+`config.trajectory` and `config.survey` (the other two stacks of SURVEY.md 8d), a `pcg` block (PCG scheme) and `cpu_baseline`
+(the oracle on the host cores, N threads and 1 thread).  `--dump-outputs DIR` writes what the headline's last timed step
+computed (dump_outputs) for output-to-output comparisons of two builds; the inputs are seeded, identical from run to run.
 """
 import argparse
 import ctypes as C
@@ -53,17 +57,22 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--keyframes", type=int, default=300)
     ap.add_argument("--photometric", type=int, default=1, help="1: photometric+geometric residuals (configs[2]); 0: geometry only")
-    ap.add_argument("--secondary", type=int, default=1, help="also measure configs[1] (50 keyframes, geometry only) on one GPU")
-    ap.add_argument("--pcg", type=int, default=1, help="also measure the PCG scheme (one GPU)")
+    ap.add_argument("--secondary", type=int, default=1, help="--full: also measure configs[1] (50 keyframes, geometry only) on one GPU")
+    ap.add_argument("--pcg", type=int, default=1, help="--full: also measure the PCG scheme (one GPU)")
     ap.add_argument("--scene", default="dense", choices=["dense", "survey", "trajectory"],
                     help="synthetic stack of the headline block (badslam_amd/synthetic.py); the bench line of record uses dense")
-    ap.add_argument("--trajectory", type=int, default=1, help="also measure the smooth-trajectory stack (one GPU): config.trajectory")
-    ap.add_argument("--survey", type=int, default=1, help="also measure the dense stack with the survey's pose ranges (one GPU): config.survey")
-    ap.add_argument("--strong", type=int, default=1, help="also measure the fixed configs[4] problem split over the ranks: config.strong")
+    ap.add_argument("--trajectory", type=int, default=1, help="--full: also measure the smooth-trajectory stack (one GPU): config.trajectory")
+    ap.add_argument("--survey", type=int, default=1, help="--full: also measure the dense stack with the survey's pose ranges (one GPU): config.survey")
+    ap.add_argument("--strong", type=int, default=1, help="--full: also measure the fixed configs[4] problem split over the ranks: config.strong")
     ap.add_argument("--strong-keyframes", type=int, default=1000)
     ap.add_argument("--culling", type=int, default=1, help="block-level frustum culling in the pair kernels (0: off, A/B runs)")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: also time the oracle on the host cores (one GPU)")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="target seconds for each of the two CPU-baseline runs")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the pair census and roofline, and the blocks marked --full above "
+                         "(each still subject to its own flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float32 / float64)")
     return ap.parse_args()
 
 
@@ -91,7 +100,7 @@ def build_stack(env, K, kind, rendered_in_hbm, shard=None):
     if rendered_in_hbm:
         dev = synthetic.TorchStack(K, env.device, kind=kind)
     else:
-        host = synthetic.SyntheticStack(K, seed=0xBAD51A4, kind=kind)
+        host = synthetic.SyntheticStack(K, seed=0xBAD51A4, kind=kind, threads=min(16, host_cpu_share()))   # same stack, rows rendered in bands
         if env.world > 1 and shard is None:   # weak scaling: rank r jitters its full-size surfel shard differently
             rng = np.random.default_rng(1000 + env.rank)
             host.surfels[2] += rng.uniform(-0.001, 0.001, host.surfels_size).astype(np.float32)
@@ -105,8 +114,9 @@ def build_stack(env, K, kind, rendered_in_hbm, shard=None):
     return dev, host
 
 
-def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False, shard=None, config_index=None):
-    """Times `steps` BA iterations on a synthetic stack of K keyframes; returns the result dict of that workload."""
+def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False, shard=None, config_index=None, full=True, dump_dir=None):
+    """Times `steps` BA iterations on a synthetic stack of K keyframes; returns the result dict of that workload.
+    full = False: no pair census and no roofline (the timed steps and `value` are the same).  dump_dir: see dump_outputs."""
     import torch
     import torch.distributed as dist
     import badslam_amd
@@ -155,11 +165,12 @@ def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False
 
     for _ in range(warmup):
         step()
-    # census for the roofline accounting (untimed), on the surfels as the pose loop sees them
-    inb, assoc = C.c_uint64(), C.c_uint64()
-    badslam_amd.check(L.bslam_debug_count_pairs(ctx.handle, stream, C.byref(cam), C.byref(dp), K, kfs, S, C.byref(sb), C.byref(inb), C.byref(assoc)))
-    frac_inb = inb.value / max(1, S * K)
-    frac_assoc = assoc.value / max(1, S * K)
+    if full:
+        # census for the roofline accounting (untimed), on the surfels as the pose loop sees them
+        inb, assoc = C.c_uint64(), C.c_uint64()
+        badslam_amd.check(L.bslam_debug_count_pairs(ctx.handle, stream, C.byref(cam), C.byref(dp), K, kfs, S, C.byref(sb), C.byref(inb), C.byref(assoc)))
+        frac_inb = inb.value / max(1, S * K)
+        frac_assoc = assoc.value / max(1, S * K)
 
     badslam_amd.check(L.bslam_profile_enable(ctx.handle, 1))
     barrier()
@@ -202,40 +213,42 @@ def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False
             pairs_all = float(tot.item())
     value = pairs_all / dt
 
-    pose_launches, pose_ms = prof["pose"]
-    # dominant kernel: pose_accumulate.  A launch covers the keyframes still unconverged.
-    avg_kf_per_launch = gn_iters_total / max(1, pose_launches)
-    bytes_per_launch = S * avg_kf_per_launch * (frac_inb * B_POSE[use_desc] + (1 - frac_inb) * B_REJECTED)
-    avg_launch_s = (pose_ms / 1e3) / max(1, pose_launches)
-    achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
-    pmc = pmc_entry(use_desc, K, S, kind)
-    roof = {"bound": "valu", "kernel": "pose_accumulate_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-            "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_value(pmc, "pose_accumulate_kernel", "hbm_bytes"),
-            "convention": "achieved = ALGORITHMIC bytes per launch (SURVEY.md 8d: in-bounds pairs at the full figure, pairs rejected at "
-                          "z <= 0 / bounds at 12 B) / average launch time, priced against the HBM peak as the contract asks; the PMC "
-                          "counters say the kernel is VALU-issue bound, not HBM bound (valu_issue_frac, hbm_traffic_frac)",
-            "avg_launch_us": avg_launch_s * 1e6, "launches": pose_launches, "keyframes_per_launch": avg_kf_per_launch,
-            "algorithmic_bytes_per_launch": bytes_per_launch,
-            "pmc_source": (pmc or {}).get("source"), "pmc_csrc_hash": (pmc or {}).get("csrc_hash")}
-    valu = pmc_value(pmc, "pose_accumulate_kernel", "valu_wave_insts_per_pair")
-    if valu is not None and avg_launch_s > 0:
-        # SQ_INSTS_VALU counts wave instructions; a wave64 op occupies a SIMD32 for >= 2 cycles (packed / fp64 / DPP more)
-        roof["valu_issue_frac"] = valu * S * avg_kf_per_launch * 2 / (SIMD_COUNT * CLOCK_HZ * avg_launch_s)
-    if roof["traffic"] is not None and avg_launch_s > 0:
-        # counted per average launch of the PMC run: scale by pairs to this run's average launch
-        per_pair = roof["traffic"] / (pmc_value(pmc, "pose_accumulate_kernel", "pairs_per_launch") or (S * K))
-        roof["traffic"] = per_pair * S * avg_kf_per_launch
-        roof["traffic_raw"] = (pmc_value(pmc, "pose_accumulate_kernel", "hbm_bytes_raw") or 0) / (pmc_value(pmc, "pose_accumulate_kernel", "pairs_per_launch") or (S * K)) * S * avg_kf_per_launch
-        roof["hbm_traffic_frac"] = roof["traffic"] / avg_launch_s / 1e9 / HBM_PEAK_GBS
-    geo_launches, geo_ms = prof["geometry"]
-    roof["geometry_kernel"] = geometry_roofline(S, K, frac_inb, use_desc, steps, active_surfel_steps, geo_ms, pmc)
-    act_launches, act_ms = prof["activation"]
-    if act_launches:
-        roof["activation_kernel"] = {"avg_launch_us": act_ms * 1e3 / act_launches, "pairs_visited_per_launch": pairs_activation / act_launches,
-                                     "achieved": pairs_activation / act_launches * (frac_inb * B_ASSOC + (1 - frac_inb) * B_REJECTED) / (act_ms / 1e3 / act_launches) / 1e9}
-    red_launches, red_ms = prof["pose_reduce"]
-    if red_launches:
-        roof["pose_reduce_solve_kernel"] = {"avg_launch_us": red_ms * 1e3 / red_launches, "launches": red_launches}
+    roof = None
+    if full:
+        pose_launches, pose_ms = prof["pose"]
+        # dominant kernel: pose_accumulate.  A launch covers the keyframes still unconverged.
+        avg_kf_per_launch = gn_iters_total / max(1, pose_launches)
+        bytes_per_launch = S * avg_kf_per_launch * (frac_inb * B_POSE[use_desc] + (1 - frac_inb) * B_REJECTED)
+        avg_launch_s = (pose_ms / 1e3) / max(1, pose_launches)
+        achieved = bytes_per_launch / avg_launch_s / 1e9 if avg_launch_s > 0 else 0.0
+        pmc = pmc_entry(use_desc, K, S, kind)
+        roof = {"bound": "valu", "kernel": "pose_accumulate_kernel", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBS, "traffic": pmc_value(pmc, "pose_accumulate_kernel", "hbm_bytes"),
+                "convention": "achieved = ALGORITHMIC bytes per launch (SURVEY.md 8d: in-bounds pairs at the full figure, pairs rejected at "
+                              "z <= 0 / bounds at 12 B) / average launch time, priced against the HBM peak as the contract asks; the PMC "
+                              "counters say the kernel is VALU-issue bound, not HBM bound (valu_issue_frac, hbm_traffic_frac)",
+                "avg_launch_us": avg_launch_s * 1e6, "launches": pose_launches, "keyframes_per_launch": avg_kf_per_launch,
+                "algorithmic_bytes_per_launch": bytes_per_launch,
+                "pmc_source": (pmc or {}).get("source"), "pmc_csrc_hash": (pmc or {}).get("csrc_hash")}
+        valu = pmc_value(pmc, "pose_accumulate_kernel", "valu_wave_insts_per_pair")
+        if valu is not None and avg_launch_s > 0:
+            # SQ_INSTS_VALU counts wave instructions; a wave64 op occupies a SIMD32 for >= 2 cycles (packed / fp64 / DPP more)
+            roof["valu_issue_frac"] = valu * S * avg_kf_per_launch * 2 / (SIMD_COUNT * CLOCK_HZ * avg_launch_s)
+        if roof["traffic"] is not None and avg_launch_s > 0:
+            # counted per average launch of the PMC run: scale by pairs to this run's average launch
+            per_pair = roof["traffic"] / (pmc_value(pmc, "pose_accumulate_kernel", "pairs_per_launch") or (S * K))
+            roof["traffic"] = per_pair * S * avg_kf_per_launch
+            roof["traffic_raw"] = (pmc_value(pmc, "pose_accumulate_kernel", "hbm_bytes_raw") or 0) / (pmc_value(pmc, "pose_accumulate_kernel", "pairs_per_launch") or (S * K)) * S * avg_kf_per_launch
+            roof["hbm_traffic_frac"] = roof["traffic"] / avg_launch_s / 1e9 / HBM_PEAK_GBS
+        geo_launches, geo_ms = prof["geometry"]
+        roof["geometry_kernel"] = geometry_roofline(S, K, frac_inb, use_desc, steps, active_surfel_steps, geo_ms, pmc)
+        act_launches, act_ms = prof["activation"]
+        if act_launches:
+            roof["activation_kernel"] = {"avg_launch_us": act_ms * 1e3 / act_launches, "pairs_visited_per_launch": pairs_activation / act_launches,
+                                         "achieved": pairs_activation / act_launches * (frac_inb * B_ASSOC + (1 - frac_inb) * B_REJECTED) / (act_ms / 1e3 / act_launches) / 1e9}
+        red_launches, red_ms = prof["pose_reduce"]
+        if red_launches:
+            roof["pose_reduce_solve_kernel"] = {"avg_launch_us": red_ms * 1e3 / red_launches, "launches": red_launches}
     exchange = None
     ex_launches, ex_ms = prof["exchange"]
     if ex_launches:
@@ -248,7 +261,9 @@ def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False
     else:
         per_gpu = f"{S} surfels per GPU"
     cfg_name = f" (BASELINE.json configs[{config_index}])" if config_index is not None else ""
-    return {
+    if dump_dir is not None:
+        dump_outputs(dump_dir, dev, poses, iters, conv)
+    res = {
         "value": value, "ms_per_step": dt / steps * 1e3, "S": S, "K": K, "stack": host, "dev": dev,
         "config": {"workload": f"{label}, {K} keyframes, {per_gpu} (cell 4, no merge), "
                                f"{'photometric+geometric' if use_desc else 'geometry-residual-only'} alternating BA iteration{cfg_name}",
@@ -262,12 +277,49 @@ def measure(env, K, use_desc, steps, warmup, kind="dense", rendered_in_hbm=False
                                            "same data: tests/test_gpu_large_configs.py::test_photometric_gauss_newton_on_the_bench_stack") if use_desc else None,
                    "pairs_per_step": {"activation_visited": pairs_activation / steps, "geometry": pairs_geometry / steps, "pose": pairs_pose / steps},
                    "active_surfel_fraction": active_surfel_steps / max(1, steps * S),
-                   "in_bounds_pair_fraction": frac_inb, "associated_pair_fraction": frac_assoc,
                    "culled_pair_fraction": cull,
                    "surfels_restored_per_step": restore,
                    "parallelism": f"surfel-shard x{world}", "exchange": env.exchange, "exchange_timing": exchange},
         "roofline": roof,
     }
+    if full:
+        res["config"].update(in_bounds_pair_fraction=frac_inb, associated_pair_fraction=frac_assoc)
+    return res
+
+
+# surfel columns that --dump-outputs writes (a fixed, seeded sample; every column of a smaller stack): 24 MB in all
+DUMP_SURFEL_SAMPLE = 1 << 19
+
+
+def dump_outputs(out_dir, dev, poses, iters, conv):
+    """--dump-outputs: what the last timed step handed back to its caller, as .npy files -- the refined poses (q x y z w, t) with
+    their Gauss-Newton iteration counts and convergence flags, and on a fixed, seeded sample of surfel columns (surfel_index) the
+    surfels after the step: positions, normals (the three signed 10-bit fields of the packed row, / 511), radius squared, the two
+    descriptors and the activation flag."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    S = dev.surfels_size
+    if S <= DUMP_SURFEL_SAMPLE:
+        idx = np.arange(S)
+    else:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(S, DUMP_SURFEL_SAMPLE, replace=False))
+    cols = torch.from_numpy(idx).to(dev.surfels.device)
+    surf = dev.surfels[:8].index_select(1, cols).cpu().numpy()
+    active = dev.active[0].index_select(0, cols).cpu().numpy()
+    bits = surf[3].view(np.uint32)
+    s10 = np.stack([(bits >> (10 * i)) & 0x3FF for i in range(3)], axis=1).astype(np.int32)
+    normals = (np.where(s10 >= 512, s10 - 1024, s10) / 511.0).astype(np.float32)
+    out = {"poses": np.frombuffer(poses, np.float32).reshape(len(iters), 7),
+           "gn_iterations": np.array(iters, np.float64),
+           "converged": np.array(conv, np.float64),
+           "surfel_index": idx.astype(np.float64),
+           "surfel_positions": np.ascontiguousarray(surf[0:3].T),
+           "surfel_normals": normals,
+           "surfel_radius_squared": surf[4].copy(),
+           "surfel_descriptors": np.ascontiguousarray(surf[6:8].T),
+           "surfel_active": active.astype(np.float32)}
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cull_stats(env):
@@ -495,18 +547,22 @@ def run_rank(args, world):
     use_desc = bool(args.photometric)
     only = os.environ.get("BSLAM_BENCH_ONLY")     # profiling runs: "strong" = nothing but the strong-scaling block
     default_workload = args.keyframes == 300 and use_desc and args.scene == "dense"
+    full = args.full                              # a plain run measures the headline block and nothing else
+    dump = args.dump_outputs if rank == 0 else None
     head = measure(env, args.keyframes, use_desc, args.steps, args.warmup, kind=args.scene, rendered_in_hbm=(args.scene != "dense"),
-                   config_index=(2 if use_desc else 1) if args.scene == "dense" else None) if only != "strong" else None
+                   config_index=(2 if use_desc else 1) if args.scene == "dense" else None, full=full, dump_dir=dump) if only != "strong" else None
     out = {"metric": "surfel x keyframe residual evaluations per second, full alternating BA iteration"}
     if head is not None:
         out.update({"value": head["value"], "unit": "pairs/s", "n_gpus": joined, "steps": args.steps, "warmup": args.warmup,
                     "ms_per_step": head["ms_per_step"], "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                    "dtype": "f32", "data": "synthetic", "config": head["config"], "roofline": head["roofline"]})
+                    "dtype": "f32", "data": "synthetic", "config": head["config"]})
+        if head["roofline"] is not None:
+            out["roofline"] = head["roofline"]
         head["dev"] = None                        # the stack's HBM is released before the next block is built
     single = world == 1 and rank == 0
     small_stack = None
     headline_stack = head["stack"] if head is not None else None
-    if single and head is not None and args.secondary and not (args.keyframes == 50 and not use_desc):
+    if full and single and head is not None and args.secondary and not (args.keyframes == 50 and not use_desc):
         sec = measure(env, 50, False, 20, 3, config_index=1)
         small_stack = sec["stack"]
         out["config"]["secondary"] = {"value": sec["value"], "unit": "pairs/s", "ms_per_step": sec["ms_per_step"], "steps": 20, "warmup": 3,
@@ -514,33 +570,36 @@ def run_rank(args, world):
         del sec
     # the other two stacks of SURVEY.md 8(d): same K, same residuals, rendered in HBM
     for flag, kind in ((args.trajectory, "trajectory"), (args.survey, "survey")):
-        if single and head is not None and flag and default_workload:
+        if full and single and head is not None and flag and default_workload:
             torch.cuda.empty_cache()
             r = measure(env, 300, True, 5, 2, kind=kind, rendered_in_hbm=True)
             out["config"][kind] = {"value": r["value"], "unit": "pairs/s", "ms_per_step": r["ms_per_step"], "steps": 5, "warmup": 2,
                                    "config": r["config"], "roofline": r["roofline"]}
             del r
-    if args.strong and (default_workload or only == "strong"):
+    if args.strong and ((full and default_workload) or only == "strong"):
         # BASELINE.json configs[4]: ONE fixed problem (1000 keyframes x 19.2 M surfels, geometry only) split over the ranks
         torch.cuda.empty_cache()
-        r = measure(env, args.strong_keyframes, False, 3, 1, kind="dense", rendered_in_hbm=True, shard=(rank, world), config_index=4)
+        r = measure(env, args.strong_keyframes, False, 3, 1, kind="dense", rendered_in_hbm=True, shard=(rank, world), config_index=4,
+                    full=full, dump_dir=dump if head is None else None)
         strong = {"value": r["value"], "unit": "pairs/s", "ms_per_step": r["ms_per_step"], "steps": 3, "warmup": 1, "scaling": "strong",
                   "n_gpus": joined, "config": r["config"], "roofline": r["roofline"]}
         del r
         if head is None:
             out.update({"value": strong["value"], "unit": "pairs/s", "n_gpus": joined, "steps": 3, "warmup": 1, "ms_per_step": strong["ms_per_step"],
                         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-                        "config": strong["config"], "roofline": strong["roofline"]})
+                        "config": strong["config"]})
+            if strong["roofline"] is not None:
+                out["roofline"] = strong["roofline"]
         else:
             out["config"]["strong"] = strong
     torch.cuda.empty_cache()
-    if single and args.pcg and headline_stack is not None:
+    if full and single and args.pcg and headline_stack is not None:
         out["pcg"] = {"headline_stack": pcg_block(headline_stack, use_desc, dev_index, out["config"]["in_bounds_pair_fraction"],
                                                   pmc=pmc_entry(use_desc, head["K"], head["S"], args.scene))}
         if small_stack is not None:
             out["pcg"]["secondary_stack"] = pcg_block(small_stack, False, dev_index, out["config"]["secondary"]["config"]["in_bounds_pair_fraction"],
                                                       pmc=pmc_entry(False, 50, small_stack.surfels_size, "dense"))
-    if single and args.cpu_baseline and headline_stack is not None:
+    if full and single and args.cpu_baseline and headline_stack is not None:
         out["cpu_baseline"] = cpu_baseline(headline_stack, head["K"], use_desc, args.cpu_seconds)
     if dist.is_initialized():
         dist.barrier()

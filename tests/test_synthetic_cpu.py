@@ -17,6 +17,24 @@ def test_dense_stack_is_unchanged():
     assert h.hexdigest() == "863f896341a485192433c419fca561f7642576658ba204cd7723058dbcb16f50"
 
 
+def stack_arrays(st):
+    return (st.surfels, st.depth, st.normals, st.radius, st.color, np.array(st.R), np.array(st.t))
+
+
+def test_rows_rendered_in_bands_give_the_same_stack():
+    """bench.py renders the headline stack with threads = its CPU share: the bands (uneven ones included) change no bit."""
+    for threads in (4, 7):
+        st = synthetic.SyntheticStack(3, seed=0xBAD51A4, threads=threads)
+        h = hashlib.sha256()
+        for a in stack_arrays(st)[:5]:
+            h.update(np.ascontiguousarray(a).tobytes())
+        assert h.hexdigest() == "863f896341a485192433c419fca561f7642576658ba204cd7723058dbcb16f50"
+    for kind in ("survey", "trajectory"):
+        one, banded = synthetic.SyntheticStack(4, kind=kind), synthetic.SyntheticStack(4, kind=kind, threads=5)
+        for a, b in zip(stack_arrays(one), stack_arrays(banded)):
+            assert a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
 def in_view_fraction(st, keyframes):
     p = st.surfels[:3].astype(np.float64)
     cam = st.camera

@@ -8,9 +8,9 @@ R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out/$TAG
 mkdir -p $O
 cd $R
-ONE="--cpu-baseline 0 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0"
+ONE="--full --cpu-baseline 0 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0"
 if [ $STAGE = all ] || [ $STAGE = bench ]; then
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench done"; tail -c 300 $O/bench_default.json
 python bench.py $ONE --keyframes 200 --photometric 0 > $O/bench_k200_geo.json 2> $O/bench_k200_geo.err
 python bench.py $ONE --keyframes 1000 --photometric 0 --steps 3 --warmup 1 > $O/bench_k1000_geo.json 2> $O/bench_k1000_geo.err
@@ -26,20 +26,20 @@ echo "stats headline done"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_k300_trajectory -- python3 $R/bench.py $ONE --scene trajectory --steps 5 > $O/stats_k300_trajectory.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_k50_geo -- python3 $R/bench.py $ONE --keyframes 50 --photometric 0 > $O/stats_k50_geo.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_k50_photo -- python3 $R/bench.py $ONE --keyframes 50 --photometric 1 > $O/stats_k50_photo.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pcg -- python3 $R/bench.py --cpu-baseline 0 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 --steps 1 --warmup 1 > $O/stats_pcg.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats_pcg -- python3 $R/bench.py --full --cpu-baseline 0 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 --steps 1 --warmup 1 > $O/stats_pcg.log 2>&1
 echo "stats done"
 for d in $O/stats_*/; do n=$(basename $d); cp $(ls $d*/*kernel_stats.csv | head -1) $O/$n.kernel_stats.csv; done
 find $O -name "*kernel_trace.csv" -delete
 fi
 cd $R
 if [ $STAGE = all ] || [ $STAGE = pmc ]; then
-bash tools/pmc.sh $TAG/pmc_k300_photo --steps 1 --warmup 1 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 > $O/pmc_k300_photo.log 2>&1
+bash tools/pmc.sh $TAG/pmc_k300_photo --full --steps 1 --warmup 1 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 > $O/pmc_k300_photo.log 2>&1
 echo "pmc headline done"
 fi
 if [ $STAGE = all ] || [ $STAGE = pmc2 ]; then
-bash tools/pmc.sh $TAG/pmc_k300_trajectory --steps 2 --warmup 1 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0 --scene trajectory > $O/pmc_k300_trajectory.log 2>&1
-bash tools/pmc.sh $TAG/pmc_k50_geo --steps 2 --warmup 1 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 --keyframes 50 --photometric 0 > $O/pmc_k50_geo.log 2>&1
-bash tools/pmc.sh $TAG/pmc_k50_photo --steps 2 --warmup 1 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0 --keyframes 50 --photometric 1 > $O/pmc_k50_photo.log 2>&1
+bash tools/pmc.sh $TAG/pmc_k300_trajectory --full --steps 2 --warmup 1 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0 --scene trajectory > $O/pmc_k300_trajectory.log 2>&1
+bash tools/pmc.sh $TAG/pmc_k50_geo --full --steps 2 --warmup 1 --secondary 0 --pcg 1 --trajectory 0 --survey 0 --strong 0 --keyframes 50 --photometric 0 > $O/pmc_k50_geo.log 2>&1
+bash tools/pmc.sh $TAG/pmc_k50_photo --full --steps 2 --warmup 1 --secondary 0 --pcg 0 --trajectory 0 --survey 0 --strong 0 --keyframes 50 --photometric 1 > $O/pmc_k50_photo.log 2>&1
 echo "pmc done"
 fi
 # summaries of whatever PMC passes this call produced (kernel durations: the stats stage's summary, from this call or -- stages run

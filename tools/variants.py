@@ -35,7 +35,7 @@ def build(specs):
 def bench(args):
     for so in sorted(glob.glob(os.path.join(OUT, "*.so"))):
         env = dict(os.environ, BSLAM_HIP_LIB=so)
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-baseline", "0", "--pcg", "0", "--secondary", "0"] + args, env=env,
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-baseline", "0", "--pcg", "0", "--secondary", "0"] + args, env=env,
                            capture_output=True, text=True)
         name = os.path.basename(so)[len("libbadslam_hip_"):-3]
         try:

@@ -46,6 +46,8 @@ static CamConsts make_cam_consts(const bslam_context* ctx, const bslam_camera4f*
     c.d2c_cy = -1 * color->fy * depth->cy / depth->fy + color->cy;
     c.color_width = color->width; c.color_height = color->height;
     c.cfx = color->fx; c.cfy = color->fy; c.ccx = color->cx; c.ccy = color->cy;
+    c.desc_gx_scale = kDescScale * c.cfx;
+    c.desc_gy_scale = kDescScale * c.cfy;
   }
   c.a = dp->a;
   c.raw_to_float_depth = dp->raw_to_float_depth;

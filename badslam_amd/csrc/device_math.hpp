@@ -60,6 +60,9 @@ struct CamConsts {
   int color_width, color_height;
   // colour camera (corner convention; the centre projector only differs in cx, cy which are unused)
   float cfx, cfy, ccx, ccy;
+  // kDescScale * cfx, kDescScale * cfy (rounded once): the descriptor residual's image gradient in byte units -> its derivative
+  // by the normalised image coordinates, one multiply per component where the pair would otherwise spend two
+  float desc_gx_scale, desc_gy_scale;
   // DepthParameters scalars
   float a, raw_to_float_depth, baseline_fx, inv_baseline_fx;
   int cell;
@@ -356,6 +359,29 @@ __device__ __forceinline__ void bilinear_gradient_bytes(const LumaQuad& t, float
   *dx = __builtin_fmaf(ty, (t.br - t.bl) - (t.tr - t.tl), t.tr - t.tl);
   *dy = __builtin_fmaf(tx, (t.br - t.tr) - (t.bl - t.tl), t.bl - t.tl);
 }
+// A packed quad as the three byte differences both filters are built from, formed in integers (exact) and converted once:
+// tr - tl, bl - tl and the mixed difference (br - bl) - (tr - tl) = (br - tr) - (bl - tl), which the gradient's two components
+// share (bilinear_gradient_bytes writes it once per component, and the compiler forms it twice).
+struct QuadDiffs { float tl, dtop, dleft, dmix; };
+__device__ __forceinline__ QuadDiffs quad_diffs(uint32_t q) {
+  const int tl = (int)(q & 0xffu), tr = (int)((q >> 8) & 0xffu), bl = (int)((q >> 16) & 0xffu), br = (int)(q >> 24);
+  const int dtop = tr - tl;
+  return QuadDiffs{(float)tl, (float)dtop, (float)(bl - tl), (float)((br - bl) - dtop)};
+}
+// bilinear_gradient_bytes on the differences: the same operands, the same single rounding per component
+__device__ __forceinline__ void bilinear_gradient_diffs(const QuadDiffs& t, float tx, float ty, float* dx, float* dy) {
+  *dx = __builtin_fmaf(ty, t.dmix, t.dtop);
+  *dy = __builtin_fmaf(tx, t.dmix, t.dleft);
+}
+// bilinear_bytes for weights on the 1/256 grid (BSLAM_TEX_FIXED_POINT_1_8: a = ka / 256, b = kb / 256, ka, kb in [0, 256]), from
+// the gradient's differences.  Every intermediate of bilinear_bytes is then exact -- top = top' / 256 and bot - top =
+// (256 (bl - tl) + ka ((br - bl) - (tr - tl))) / 256 with integers |top'| < 2^16, |bot' - top'| < 2^18, and the value N / 2^16
+// with N < 2^24 -- and so is each fma here: the same value, bit for bit, in one conversion and three fmas instead of two
+// conversions, three fmas and a subtraction.  (With unquantised weights the intermediates round, and bilinear_bytes stays.)
+__device__ __forceinline__ float bilinear_diffs_fixed(const QuadDiffs& t, float a, float b) {
+  const float top = __builtin_fmaf(a, t.dtop, t.tl);
+  return __builtin_fmaf(b, __builtin_fmaf(a, t.dmix, t.dleft), top);
+}
 // bilinear luma in byte units at pixel-corner coordinates (x, y)
 __device__ __forceinline__ float tex_b(const KfDev& kf, const CamConsts& c, float x, float y) {
   const TexFootprint f = tex_footprint(c, x, y);
@@ -440,15 +466,25 @@ __device__ __forceinline__ DescSamples descriptor_samples_issue(const KfDev& kf,
   for (int k = 0; k < 3; ++k) tex_weights(c, &d.f[k]);
   return d;
 }
+// The gradients leave multiplied by (gx_scale, gy_scale): kDescScale for the gradient by pixel coordinates, or the folded
+// CamConsts::desc_gx_scale / desc_gy_scale for the kernels that go on to multiply by the colour focal lengths.
 template <class SamplePoints>
-__device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const CamConsts& c, const DescSamples& d, float d1, float d2, SamplePoints&& sample_points,
-                                                          float* r1, float* r2, float* gx1, float* gy1, float* gx2, float* gy2) {
+__device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const CamConsts& c, const DescSamples& d, float d1, float d2, float gx_scale, float gy_scale,
+                                                          SamplePoints&& sample_points, float* r1, float* r2, float* gx1, float* gy1, float* gx2, float* gy2) {
   float val[3], gx[3], gy[3];   // byte units
+  if (c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8) {
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const LumaQuad t = unpack_quad_bytes(d.q[k]);
-    val[k] = bilinear_bytes(t, d.f[k].a, d.f[k].b);
-    bilinear_gradient_bytes(t, d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
+    for (int k = 0; k < 3; ++k) {
+      const QuadDiffs t = quad_diffs(d.q[k]);
+      val[k] = bilinear_diffs_fixed(t, d.f[k].a, d.f[k].b);
+      bilinear_gradient_diffs(t, d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      val[k] = bilinear_bytes(unpack_quad_bytes(d.q[k]), d.f[k].a, d.f[k].b);
+      bilinear_gradient_diffs(quad_diffs(d.q[k]), d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
+    }
   }
   // some sample's 2x2 footprint touches the image border: a base texel outside [0, w - 2] x [0, h - 2] (-1 is the largest unsigned
   // value), decided on the maxima of the three base texels (two v_max3_u32 and two compares instead of six compares)
@@ -460,20 +496,20 @@ __device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
       const GradFootprint g = grad_footprint(c, pts[k]);
-      bilinear_gradient_bytes(unpack_quad_bytes(quad_at(kf, c, g.ix, g.iy)), g.tx, g.ty, &gx[k], &gy[k]);
+      bilinear_gradient_diffs(quad_diffs(quad_at(kf, c, g.ix, g.iy)), g.tx, g.ty, &gx[k], &gy[k]);
     }
   }
   *r1 = __builtin_fmaf(kDescScale, val[1] - val[0], -d1);
   *r2 = __builtin_fmaf(kDescScale, val[2] - val[0], -d2);
-  *gx1 = kDescScale * (gx[1] - gx[0]);
-  *gy1 = kDescScale * (gy[1] - gy[0]);
-  *gx2 = kDescScale * (gx[2] - gx[0]);
-  *gy2 = kDescScale * (gy[2] - gy[0]);
+  *gx1 = gx_scale * (gx[1] - gx[0]);
+  *gy1 = gy_scale * (gy[1] - gy[0]);
+  *gx2 = gx_scale * (gx[2] - gx[0]);
+  *gy2 = gy_scale * (gy[2] - gy[0]);
 }
 __device__ __forceinline__ void descriptor_residual_and_jacobian(const KfDev& kf, const CamConsts& c, f2 cp, f2 t1, f2 t2, float d1, float d2,
                                                                  float* r1, float* r2, float* gx1, float* gy1, float* gx2, float* gy2) {
   const DescSamples d = descriptor_samples_issue(kf, c, cp, t1, t2);
-  descriptor_samples_finish(kf, c, d, d1, d2, [&](f2 (&pts)[3]) { pts[0] = cp; pts[1] = t1; pts[2] = t2; }, r1, r2, gx1, gy1, gx2, gy2);
+  descriptor_samples_finish(kf, c, d, d1, d2, kDescScale, kDescScale, [&](f2 (&pts)[3]) { pts[0] = cp; pts[1] = t1; pts[2] = t2; }, r1, r2, gx1, gy1, gx2, gy2);
 }
 
 // BS/surfel_projection.cuh:196-207

@@ -113,7 +113,7 @@ __global__ __launch_bounds__(kIntrThreads) void intrinsics_accumulate_kernel(
       if (kColorIntr) {                                           // :120-158, 198-216
         if (has_desc) {
           float r1, rr2, gx1, gy1, gx2, gy2;
-          descriptor_samples_finish(kf, c, ds, d1[r], d2[r], [&](f2 (&pts)[3]) { pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);
+          descriptor_samples_finish(kf, c, ds, d1[r], d2[r], kDescScale, kDescScale, [&](f2 (&pts)[3]) { pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);
           float j1[4], j2[4];
           color_intrinsics_jacobian(gx1, gy1, nx, ny, j1);
           color_intrinsics_jacobian(gx2, gy2, nx, ny, j2);

@@ -168,9 +168,7 @@ constexpr int kPcgStateComps = 14;   // 0-2 normal, 3-5 / 6-8 tangent points, 9-
 template <class SamplePoints>
 __device__ __forceinline__ DescTerms descriptor_terms_finish(const CamConsts& c, const KfDev& kf, const DescSamples& ds, float d1, float d2, SamplePoints&& sample_points) {
   DescTerms t;
-  descriptor_samples_finish(kf, c, ds, d1, d2, sample_points, &t.r1, &t.r2, &t.gx1, &t.gy1, &t.gx2, &t.gy2);
-  t.gx1 *= c.cfx; t.gx2 *= c.cfx;
-  t.gy1 *= c.cfy; t.gy2 *= c.cfy;
+  descriptor_samples_finish(kf, c, ds, d1, d2, c.desc_gx_scale, c.desc_gy_scale, sample_points, &t.r1, &t.r2, &t.gx1, &t.gy1, &t.gx2, &t.gy2);
   t.w1 = desc_weight(t.r1);
   t.w2 = desc_weight(t.r2);
   return t;

@@ -268,10 +268,8 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
         if (kDesc) {                                            // BS/kernel_opt_pose.cu:320-382
           if (has_desc) {
             float r1, rr2, gx1, gy1, gx2, gy2;
-            descriptor_samples_finish(kf, c, ds, desc1[r], desc2[r], [&](f2 (&pts)[3]) { pts[0] = color_pxy; pts[1] = t1; pts[2] = t2;
-            }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);
-            gx1 *= c.cfx; gx2 *= c.cfx;
-            gy1 *= c.cfy; gy2 *= c.cfy;
+            descriptor_samples_finish(kf, c, ds, desc1[r], desc2[r], c.desc_gx_scale, c.desc_gy_scale, [&](f2 (&pts)[3]) {
+              pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);   // gradients times cfx, cfy
             descriptor_pose_jacobian(gx1, gy1, p.local, J);
             accumulate_h_b(r1, desc_weight(r1), J, acc);
             descriptor_pose_jacobian(gx2, gy2, p.local, J);

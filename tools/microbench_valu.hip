@@ -46,6 +46,20 @@ __global__ __launch_bounds__(256) void k_pkfma(float* out, float a, float b) {
   out[blockIdx.x * blockDim.x + threadIdx.x] = s.x + s.y;
 }
 
+// zeroing moves (the pose kernel's accumulators): 8 independent destinations per statement, as above
+KERNEL(k_mov32, asm volatile("v_mov_b32 %0, 0\nv_mov_b32 %1, 0\nv_mov_b32 %2, 0\nv_mov_b32 %3, 0\n"
+                             "v_mov_b32 %4, 0\nv_mov_b32 %5, 0\nv_mov_b32 %6, 0\nv_mov_b32 %7, 0\n"
+                             : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7)))
+__global__ __launch_bounds__(256) void k_mov64(float* out, float a, float b) {
+  double x0 = threadIdx.x + 1, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
+  for (int i = 0; i < kIters; ++i) {
+    asm volatile("v_mov_b64 %0, 0\nv_mov_b64 %1, 0\nv_mov_b64 %2, 0\nv_mov_b64 %3, 0\n"
+                 "v_mov_b64 %4, 0\nv_mov_b64 %5, 0\nv_mov_b64 %6, 0\nv_mov_b64 %7, 0\n"
+                 : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7));
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7);
+}
+
 template <typename K>
 static void run(const char* name, K kernel, float* d_out) {
   const int blocks = 256 * 8;   // 8 blocks of 4 waves per CU = 8 waves per SIMD
@@ -75,5 +89,7 @@ int main() {
   run("v_rcp_f32", k_rcp, d_out);
   run("v_sqrt_f32", k_sqrt, d_out);
   run("v_cvt_i32_f32", k_cvt, d_out);
+  run("v_mov_b32 0", k_mov32, d_out);
+  run("v_mov_b64 0", k_mov64, d_out);
   return 0;
 }

@@ -149,6 +149,11 @@ SIGNATURES = {
     "bslam_estimate_frame_poses_batched": (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_int, C.c_int, _CAM, _CAM, _DP, C.c_int, _KFS,
         C.c_uint32, _BUF, C.c_int, P(SE3f), P(C.c_int32), P(C.c_int32), ALLREDUCE_FN, C.c_void_p]),
+    "bslam_compute_ba_cost": (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_int, C.c_int, _CAM, _CAM, _DP, C.c_int, _KFS,
+        C.c_uint32, _BUF, _BUF, P(C.c_float), P(C.c_uint32), ALLREDUCE_FN, C.c_void_p]),
+    "bslam_debug_ba_cost_descriptor_residuals": (C.c_int, [
+        C.c_void_p, C.c_void_p, _CAM, _CAM, _DP, _KFS, C.c_uint32, _BUF, C.c_void_p]),
     "bslam_accumulate_pose_coeffs_batched": (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_int, C.c_int, _CAM, _CAM, _DP, C.c_int, _KFS,
         C.c_uint32, _BUF, P(C.c_float), P(C.c_uint32)]),

@@ -18,6 +18,7 @@
 #include "preprocess_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
+#include "cost_kernels.hpp"
 
 namespace bslam {
 
@@ -1319,3 +1320,4 @@ int bslam_debug_pose_residuals(
 #include "lifecycle_abi.inc"
 #include "preprocess_abi.inc"
 #include "odometry_abi.inc"
+#include "cost_abi.inc"

@@ -212,6 +212,13 @@ __device__ __forceinline__ float tukey_residual(float r, float k) {
   if (fabsf(r) < k) { const float q = rdiv(r, k); const float t = 1.f - q * q; return (1 / 6.f) * k * k * (1 - t * t * t); }
   return (1 / 6.f) * k * k;
 }
+// The objective's Tukey term: (k^2 / 6) q^2 (1 + t + t^2), q = r / k, t = 1 - q^2 -- algebraically tukey_residual's
+// (k^2 / 6)(1 - t^3), without its cancellation: at a converged pose most residuals are tiny, and 1 - t^3 in fp32 keeps few of their
+// digits (the pose kernels' debug cost keeps the reference's form).
+__device__ __forceinline__ float tukey_residual_accurate(float r, float k) {
+  if (fabsf(r) < k) { const float q = rdiv(r, k); const float q2 = q * q; const float t = 1.f - q2; return (1 / 6.f) * k * k * (q2 * ((1.f + t) + t * t)); }
+  return (1 / 6.f) * k * k;
+}
 __device__ __forceinline__ float huber_weight(float r, float k) { const float a = fabsf(r); return (a < k) ? 1.f : rdiv(k, a); }
 __device__ __forceinline__ float huber_residual(float r, float k) {
   const float a = fabsf(r);
@@ -233,6 +240,7 @@ __device__ __forceinline__ float depth_inv_stddev(float nx, float ny, float dept
 }
 __device__ __forceinline__ float depth_weight(float r) { return 1.f * tukey_weight(r, 1.f * kDepthTukey); }
 __device__ __forceinline__ float weighted_depth_residual(float r) { return 1.f * tukey_residual(r, 1.f * kDepthTukey); }
+__device__ __forceinline__ float objective_depth_term(float r) { return tukey_residual_accurate(r, kDepthTukey); }   // bslam_compute_ba_cost
 __device__ __forceinline__ float desc_weight(float r) { return 1.f * kDescWeight * huber_weight(r, kDescHuber); }
 __device__ __forceinline__ float weighted_desc_residual(float r) { return 1.f * kDescWeight * huber_residual(r, kDescHuber); }
 
@@ -506,6 +514,20 @@ __device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const
   *gx2 = gx_scale * (gx[2] - gx[0]);
   *gy2 = gy_scale * (gy[2] - gy[0]);
 }
+// The residuals of descriptor_samples_finish alone (the BA objective: no gradients, no border path): the same operations on the
+// same operands, so r1 and r2 are the same bits (bslam_debug_ba_cost_descriptor_residuals compares the two).
+__device__ __forceinline__ void descriptor_samples_values(const CamConsts& c, const DescSamples& d, float d1, float d2, float* r1, float* r2) {
+  float val[3];   // byte units
+  if (c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) val[k] = bilinear_diffs_fixed(quad_diffs(d.q[k]), d.f[k].a, d.f[k].b);
+  } else {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) val[k] = bilinear_bytes(unpack_quad_bytes(d.q[k]), d.f[k].a, d.f[k].b);
+  }
+  *r1 = __builtin_fmaf(kDescScale, val[1] - val[0], -d1);
+  *r2 = __builtin_fmaf(kDescScale, val[2] - val[0], -d2);
+}
 __device__ __forceinline__ void descriptor_residual_and_jacobian(const KfDev& kf, const CamConsts& c, f2 cp, f2 t1, f2 t2, float d1, float d2,
                                                                  float* r1, float* r2, float* gx1, float* gy1, float* gx2, float* gy2) {
   const DescSamples d = descriptor_samples_issue(kf, c, cp, t1, t2);
@@ -673,6 +695,11 @@ __device__ __forceinline__ f3 pixel_unprojection(const Proj& r) {   // unproject
 __device__ __forceinline__ void depth_residual_and_jacobian(const CamConsts& c, const Proj& r, float* raw, float* J) {
   const float inv_stddev = depth_inv_stddev(r.nx, r.ny, r.depth, r.n_local, c.baseline_fx);
   depth_residual_and_pose_jacobian_fused(inv_stddev, r.n_local, pixel_unprojection(r), r.local, raw, J);
+}
+// The residual of depth_residual_and_jacobian without its Jacobian (the BA objective), unfused as the reference writes it: near a
+// converged pose the dot product cancels, and the objective is compared with the oracle's value there.
+__device__ __forceinline__ float depth_residual_value(const CamConsts& c, const Proj& r) {
+  return depth_residual(depth_inv_stddev(r.nx, r.ny, r.depth, r.n_local, c.baseline_fx), r.n_local, pixel_unprojection(r), r.local);
 }
 // Depth residual wrt. a surfel move of t along its (unit) normal (BS/kernel_opt_geometry.cu:440, BS/kernel_pcg.cu:217).
 __device__ __forceinline__ float depth_position_jacobian(float inv_stddev) { return -inv_stddev; }

@@ -67,6 +67,10 @@ def host_lib():
     L.bsh_get_intrinsics.argtypes = [C.c_void_p, f32p, f32p, f32p]
     L.bsh_set_intrinsics.argtypes = [C.c_void_p, f32p, f32p, C.c_float]
     L.bsh_get_cfactor.argtypes = [C.c_void_p, C.c_void_p, f32p]
+    L.bsh_compute_cost.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_int), f32p, C.POINTER(C.c_uint32), C.POINTER(C.c_int),
+                                   C.POINTER(C.c_double)]
+    L.bsh_set_cost_tracking.argtypes = [C.c_void_p, C.c_int]
+    L.bsh_cost_history.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
     _host = L
     return L
 
@@ -404,6 +408,32 @@ class DirectBA:
                                                  max_iterations, int(use_pcg), active_keyframe_window_start, active_keyframe_window_end,
                                                  int(increase_ba_iteration_count), pcg_max_inner_iterations, C.byref(it), C.byref(conv)))
         return it.value, bool(conv.value)
+
+    def ComputeCost(self, active_surfels_only=False):
+        """The BA objective at the current poses, intrinsics and cfactors (bslam_compute_ba_cost): dict with keyframe_ids (n,),
+        cost (n, 2) float32 [Tukey depth sum, kDescWeight * Huber sum of both descriptor residuals], counts (n, 2) uint32
+        [depth-associated pairs, pairs with valid descriptor residuals], depth_total, descriptor_total and total (float64)."""
+        cap = max(1, self.keyframe_count())
+        ids, cost, counts = np.zeros(cap, np.int32), np.zeros((cap, 2), np.float32), np.zeros((cap, 2), np.uint32)
+        n, totals = C.c_int(), np.zeros(2, np.float64)
+        self._check(self.L.bsh_compute_cost(self._ba, self.stream, int(active_surfels_only), cap, ids.ctypes.data_as(C.POINTER(C.c_int)), _f(cost),
+                                            counts.ctypes.data_as(C.POINTER(C.c_uint32)), C.byref(n), totals.ctypes.data_as(C.POINTER(C.c_double))))
+        k = n.value
+        return dict(keyframe_ids=ids[:k], cost=cost[:k], counts=counts[:k], depth_total=float(totals[0]), descriptor_total=float(totals[1]),
+                    total=float(totals[0] + totals[1]))
+
+    def SetCostTracking(self, enable):
+        """BundleAdjustment records the objective before its first and after every iteration (cost_history); off by default."""
+        self._check(self.L.bsh_set_cost_tracking(self._ba, int(enable)))
+
+    @property
+    def cost_history(self):
+        """(iterations + 1, 2) float64 [depth total, descriptor total] of the last BundleAdjustment call with cost tracking on."""
+        n = C.c_int()
+        self._check(self.L.bsh_cost_history(self._ba, 0, None, C.byref(n)))
+        out = np.zeros((max(1, n.value), 2), np.float64)
+        self._check(self.L.bsh_cost_history(self._ba, n.value, out.ctypes.data_as(C.POINTER(C.c_double)), C.byref(n)))
+        return out[:n.value]
 
     def set_intrinsics(self, color4=None, depth4=None, a=0.0):
         c = None if color4 is None else _f(np.ascontiguousarray(color4, np.float32))

@@ -221,6 +221,32 @@ int bsh_bundle_adjustment(void* ba, void* stream, int optimize_depth_intrinsics,
   });
 }
 
+// DirectBA::ComputeCost: ids[n], cost[n][2], counts[n][2] for the n <= capacity non-deleted keyframes, totals[2] = (depth, descriptor).
+int bsh_compute_cost(void* ba_, void* stream, int active_surfels_only, int capacity, int* ids, float* cost, uint32_t* counts, int* n, double* totals) {
+  BSH_TRY({
+    DirectBA::CostReport r;
+    static_cast<DirectBA*>(ba_)->ComputeCost(static_cast<hipStream_t>(stream), active_surfels_only != 0, &r);
+    const int K = static_cast<int>(r.keyframe_ids.size());
+    if (K > capacity) throw std::invalid_argument("bsh_compute_cost: more keyframes than capacity");
+    for (int k = 0; k < K; ++k) {
+      ids[k] = r.keyframe_ids[k];
+      for (int j = 0; j < 2; ++j) { cost[2 * k + j] = r.cost[2 * k + j]; counts[2 * k + j] = r.counts[2 * k + j]; }
+    }
+    *n = K;
+    totals[0] = r.depth_total;
+    totals[1] = r.descriptor_total;
+  });
+}
+int bsh_set_cost_tracking(void* ba, int enable) { BSH_TRY(static_cast<DirectBA*>(ba)->SetCostTracking(enable != 0)); }
+// DirectBA::cost_history: totals[i][2] = (depth, descriptor) of entry i < min(n, capacity); n = the entries of the last BundleAdjustment
+int bsh_cost_history(void* ba, int capacity, double* totals, int* n) {
+  BSH_TRY({
+    const auto& h = static_cast<DirectBA*>(ba)->cost_history();
+    *n = static_cast<int>(h.size());
+    for (int i = 0; i < *n && i < capacity; ++i) { totals[2 * i] = h[i].depth_total; totals[2 * i + 1] = h[i].descriptor_total; }
+  });
+}
+
 int bsh_set_intrinsics(void* ba_, const float* color4, const float* depth4, float a) {
   BSH_TRY({
     DirectBA* ba = static_cast<DirectBA*>(ba_);

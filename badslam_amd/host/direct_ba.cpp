@@ -439,6 +439,32 @@ void DirectBA::ExportToPointCloud(hipStream_t stream, PointCloud* cloud) const {
   }
 }
 
+void DirectBA::ComputeCost(hipStream_t stream, bool active_surfels_only, CostReport* report) {
+  const std::vector<bslam_keyframe_view> views = KeyframeViews();
+  const int K = static_cast<int>(views.size());
+  const bslam_camera4f color_cam = color_camera_.pod(), depth_cam = depth_camera_.pod();
+  const bslam_depth_params dp = depth_params();
+  const bslam_buffer2d surfels = surfels_->ToPod(), active = active_surfels_->ToPod();
+  report->keyframe_ids.clear();
+  for (const auto& kf : keyframes_) if (kf) report->keyframe_ids.push_back(kf->id());
+  report->cost.assign(2 * static_cast<size_t>(K), 0.f);
+  report->counts.assign(2 * static_cast<size_t>(K), 0u);
+  Check(bslam_compute_ba_cost(ctx_, stream, use_depth_residuals_, use_descriptor_residuals_, &color_cam, &depth_cam, &dp, K, views.data(), surfels_size_,
+                              &surfels, active_surfels_only ? &active : nullptr, report->cost.data(), report->counts.data(), allreduce_, allreduce_user_),
+        "bslam_compute_ba_cost");
+  report->depth_total = report->descriptor_total = 0;
+  for (int k = 0; k < K; ++k) {
+    report->depth_total += report->cost[2 * static_cast<size_t>(k)];
+    report->descriptor_total += report->cost[2 * static_cast<size_t>(k) + 1];
+  }
+}
+
+void DirectBA::TrackCost(hipStream_t stream) {
+  if (!cost_tracking_) return;
+  cost_history_.emplace_back();
+  ComputeCost(stream, false, &cost_history_.back());
+}
+
 std::vector<bslam_keyframe_view> DirectBA::KeyframeViews() const {
   // Deleted keyframes (null entries) are skipped by every kernel wrapper of the reference
   // (BS/kernel_opt_geometry.cc:115); here they are simply left out of the table.
@@ -640,6 +666,8 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
   HIP_OR_THROW(hipMemsetAsync(active_surfels_->address(), 0, surfels_size_ * sizeof(u8), stream));   // :338
 
   const bslam_buffer2d surfels = surfels_->ToPod(), active = active_surfels_->ToPod();
+  cost_history_.clear();
+  TrackCost(stream);
 
   for (int iteration = 0; iteration < max_iterations; ++iteration) {
     if (progress_function && !progress_function(iteration)) break;
@@ -791,6 +819,8 @@ void DirectBA::BundleAdjustmentAlternating(hipStream_t stream, bool optimize_dep
       if (optimize_depth_intrinsics || optimize_color_intrinsics) { HIP_OR_THROW(hipEventElapsedTime(&ms, ev_[14], ev_[15])); *timings_stream_ << "BA_intrinsics_optimization " << ms << std::endl; }
     }
 
+    TrackCost(stream);
+
     // --- CONVERGENCE (:692-717) ---
     if (iteration >= min_iterations - 1 && (num_converged == keyframes_.size() || !optimize_poses)) {
       if (converged) *converged = true;
@@ -832,6 +862,8 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
   const bslam_buffer2d surfels = surfels_->ToPod(), active = active_surfels_->ToPod();
   const int K = static_cast<int>(keyframes_.size());
   std::vector<u32> keyframes_with_new_surfels;
+  cost_history_.clear();
+  TrackCost(stream);
 
   for (int iteration = 0; iteration < max_iterations; ++iteration) {
     if (progress_function && !progress_function(iteration)) break;
@@ -983,6 +1015,8 @@ void DirectBA::BundleAdjustmentPCG(hipStream_t stream, bool optimize_depth_intri
                        << " surfel_count " << surfel_count_ << std::endl;
       *timings_stream_ << "BA_PCG " << ms << std::endl;
     }
+
+    TrackCost(stream);
 
     // convergence (:745-760)
     if (iteration >= min_iterations - 1 && (num_converged == keyframes_.size() || !optimize_poses)) {

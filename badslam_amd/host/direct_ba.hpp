@@ -198,6 +198,23 @@ class DirectBA {
   };
   void ExportToPointCloud(hipStream_t stream, PointCloud* cloud) const;
 
+  // The objective the BA minimises (bslam_compute_ba_cost: Tukey depth terms and kDescWeight * Huber on both descriptor
+  // residuals) at the keyframes' current poses, intrinsics and cfactors: every non-deleted keyframe whatever its activation, every
+  // non-deleted surfel -- with active_surfels_only, only those the last geometry step flagged active.  Only reads the scene.
+  struct CostReport {
+    std::vector<int> keyframe_ids;
+    std::vector<float> cost;        // 2 per keyframe: depth, descriptor
+    std::vector<uint32_t> counts;   // 2 per keyframe: depth-associated pairs, pairs with valid descriptor residuals
+    double depth_total = 0, descriptor_total = 0;
+    double total() const { return depth_total + descriptor_total; }
+  };
+  void ComputeCost(hipStream_t stream, bool active_surfels_only, CostReport* report);
+  // Off by default.  On: BundleAdjustment (alternating and PCG) evaluates the objective before its first iteration and after
+  // every iteration into cost_history(), which each BundleAdjustment call restarts.  The poses and surfels it computes do not
+  // change (the evaluation only reads); it costs one surfel x keyframe pass and a host round trip per iteration.
+  void SetCostTracking(bool enable) { cost_tracking_ = enable; }
+  const std::vector<CostReport>& cost_history() const { return cost_history_; }
+
   // Scene state in / out.
   void SetSurfels(hipStream_t stream, const float* host_rows, size_t host_pitch_bytes, u32 count);
   void GetSurfels(hipStream_t stream, float* host_rows, size_t host_pitch_bytes, int rows) const;
@@ -307,6 +324,9 @@ class DirectBA {
   mutable std::mutex ba_thread_mutex_;
   // PCG vectors, allocated lazily (BS/direct_ba_pcg.cc:255-268)
   std::unique_ptr<DeviceBuffer<float>> pcg_r_, pcg_M_, pcg_delta_, pcg_g_, pcg_p_, pcg_scalars_;
+  bool cost_tracking_ = false;
+  std::vector<CostReport> cost_history_;
+  void TrackCost(hipStream_t stream);   // appends ComputeCost(stream, false) to cost_history_ when tracking is on
   bool batched_pose_optimization_ = true;
   bool scheme_end_tasks_ = true;
   int fixed_gauge_keyframe_ = -1;

@@ -203,7 +203,8 @@ int bslam_debug_cull_stats(bslam_context* ctx, uint64_t* tested, uint64_t* culle
 int bslam_profile_enable(bslam_context* ctx, int enable);
 enum { BSLAM_PROF_POSE_ACCUMULATE = 0, BSLAM_PROF_GEOMETRY = 1, BSLAM_PROF_PCG_INIT = 2, BSLAM_PROF_PCG_STEP1 = 3, BSLAM_PROF_ACTIVATION = 4,
        BSLAM_PROF_EXCHANGE = 5,      /* the K x 32 all-reduce of a batched Gauss-Newton iteration (surfel-sharded runs) */
-       BSLAM_PROF_POSE_REDUCE = 6 }; /* row sums + 6x6 solve of a batched Gauss-Newton iteration (single-GPU path) */
+       BSLAM_PROF_POSE_REDUCE = 6,   /* row sums + 6x6 solve of a batched Gauss-Newton iteration (single-GPU path) */
+       BSLAM_PROF_BA_COST = 7 };     /* the objective pass of bslam_compute_ba_cost and its row sums */
 int bslam_profile_read(bslam_context* ctx, int kernel, int32_t* launches, float* total_ms);
 /* Work counters accumulated since bslam_profile_enable(ctx, 1) by the counting variants of the kernels (8 values, HOST out):
  * [0] (surfel, keyframe) pairs the activation pass actually visited (it stops at a surfel's first associated active keyframe,
@@ -261,6 +262,34 @@ int bslam_estimate_frame_poses_batched(
     int max_iterations,
     bslam_se3f* poses, int32_t* iterations_done, int32_t* converged,
     bslam_allreduce_fn allreduce, void* allreduce_user);
+
+/* Objective of the surfel model: for every keyframe of the list, whatever its activation field, and every non-deleted
+ * surfel (only those with bit 0 of active_surfels set when it is non-null):
+ *   cost[k][0] = sum of Tukey depth terms        counts[k][0] = depth-associated pairs
+ *   cost[k][1] = sum of kDescWeight * (Huber(r1) + Huber(r2))   counts[k][1] = pairs with valid descriptor residuals
+ * HOST outputs, valid on return (counts may be null).  Sums over surfel shards through the call's hook, else the context's
+ * hook / RCCL communicator, as bslam_estimate_frame_poses_batched does; the counts then travel as floats and are exact while a
+ * keyframe's total stays below 2^24 -- a call in which one reaches it returns BSLAM_ERR_INVALID_ARGUMENT on every rank.
+ * keyframe_count == 0 or surfels_size == 0 is valid (zeros).  Not the reference's quirk Q1 (both descriptor residuals).
+ * The library's own extension: the reference has no such entry point. */
+int bslam_compute_ba_cost(
+    bslam_context* ctx, void* stream,
+    int use_depth_residuals, int use_descriptor_residuals,
+    const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
+    const bslam_depth_params* depth_params,
+    int keyframe_count, const bslam_keyframe_view* keyframes,
+    uint32_t surfels_size, const bslam_buffer2d* surfels, const bslam_buffer2d* active_surfels,
+    float* cost, uint32_t* counts,
+    bslam_allreduce_fn allreduce, void* allreduce_user);
+
+/* Probe of the objective's value-only descriptor path (test aid): for every surfel that associates with `keyframe` and whose
+ * pixel lies in the colour image, writes 4 floats to DEVICE out: r1, r2 as the pose kernels form them (with gradients) and
+ * r1, r2 as bslam_compute_ba_cost forms them (values only); zeros for the other surfels.  The two pairs are the same bits. */
+int bslam_debug_ba_cost_descriptor_residuals(
+    bslam_context* ctx, void* stream,
+    const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
+    const bslam_depth_params* depth_params, const bslam_keyframe_view* keyframe,
+    uint32_t surfels_size, const bslam_buffer2d* surfels, float* out);
 
 /* One batched accumulation without the solve: H/b for all K keyframes at the
  * given frame_T_global (kf.frame_T_global), written to HOST Hb[K][27] (21 H then

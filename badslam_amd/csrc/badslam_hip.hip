@@ -397,8 +397,10 @@ static SurfelRowsRW surfel_rows_rw(const SurfelWork& w, const bslam_buffer2d* su
   return o;
 }
 
-// Chooses how many keyframes one block walks: enough blocks to fill 256 CUs several times over.
-static int choose_kfs_per_block(int tiles, int kf_count) {
+// Chooses how many keyframes one block walks: enough blocks to fill 256 CUs several times over.  `multiple`: the photometric
+// kernel deals a chunk's keyframes to its four waves (pose_accumulate_desc), so its chunks are rounded up to a multiple of four
+// keyframes, else the waves of every block would end unevenly (K = 50: chunks of 10 keyframes are 3 + 3 + 2 + 2).
+static int choose_kfs_per_block(int tiles, int kf_count, int multiple = 1) {
 #ifndef BSLAM_POSE_TARGET_BLOCKS
 #define BSLAM_POSE_TARGET_BLOCKS 8192
 #endif
@@ -420,6 +422,7 @@ static int choose_kfs_per_block(int tiles, int kf_count) {
 #define BSLAM_POSE_MAX_KFS_PER_BLOCK 0   /* 0: 64 with >= 8192 work slots, else 32 */
 #endif
   const int cap = BSLAM_POSE_MAX_KFS_PER_BLOCK > 0 ? BSLAM_POSE_MAX_KFS_PER_BLOCK : (tiles >= 8192 ? 64 : 32);
+  per_block = (per_block + multiple - 1) / multiple * multiple;
   if (per_block > cap) per_block = cap;
   return per_block;
 }
@@ -458,7 +461,10 @@ static int launch_pose_accumulate(bslam_context* ctx, hipStream_t stream, int us
   if (rc) return rc;
   rc = ctx->coeffs.reserve((size_t)kf_count * kRow * sizeof(float));
   if (rc) return rc;
-  const int per_block = choose_kfs_per_block(tiles, kf_count);   // <= 64: one bit per keyframe of a chunk in a visit word
+#ifndef BSLAM_POSE_DESC_KF_MULTIPLE
+#define BSLAM_POSE_DESC_KF_MULTIPLE 4
+#endif
+  const int per_block = choose_kfs_per_block(tiles, kf_count, use_desc ? BSLAM_POSE_DESC_KF_MULTIPLE : 1);   // <= 64: one bit per keyframe of a chunk in a visit word
   const unsigned chunks = (unsigned)((kf_count + per_block - 1) / per_block);
   if (kfs_per_block_out) *kfs_per_block_out = per_block;
   if ((rc = ctx->vis.reserve((size_t)chunks * sc.slots * sizeof(VisWord)))) return rc;
@@ -488,8 +494,8 @@ static int launch_pose_accumulate(bslam_context* ctx, hipStream_t stream, int us
   }
   BSLAM_HIP_TRY(hipGetLastError());
   if (!reduce_rows) return BSLAM_OK;   // the caller's pose_reduce_solve_kernel sums the rows itself
-  // sums of counts are formed per row as floats: a (slot, wave) row holds <= 64 * kPoseR residuals, a thread's
-  // share at most rows / 32 * 256 -- exact in fp32 up to 2^24
+  // sums of counts are formed per row as floats: a (slot, keyframe) row holds <= 2 * 256 * kPoseR residuals, a thread's
+  // share at most rows / 32 * 1024 -- exact in fp32 up to 2^24
   hipLaunchKernelGGL(pose_reduce_rows_kernel, dim3((unsigned)kf_count), dim3(1024), (unsigned)visit_map_bytes(tiles), stream, (const float*)partials, rows_per_kf, kf_count,
                      (float*)ctx->coeffs.ptr, states, (const VisWord*)vis, per_block, cull_stats_ptr(ctx), kf_list ? kf_list + 1 + kf_count : nullptr);
   BSLAM_HIP_TRY(hipGetLastError());

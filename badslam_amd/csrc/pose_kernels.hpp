@@ -7,16 +7,17 @@
 // MI355X design (not the reference's one-launch-per-keyframe, 27-block-reductions-per-launch
 // shape):
 //   * one launch covers (surfel tiles) x (keyframe chunks); a thread keeps kR surfels (position +
-//     decoded normal in registers; the photometric variant's 14 per-surfel constants in LDS) and
-//     walks the keyframes of its chunk, so surfel bytes are read once per chunk instead of once
-//     per keyframe; the surfels come in the library's per-surfel Morton order (sorted copy of the
-//     rows, badslam_hip.hip: prepare_surfels), so a wave's 64 surfels are a compact blob;
+//     decoded normal in registers) and walks the keyframes of its chunk, so surfel bytes are read
+//     once per chunk instead of once per keyframe -- the photometric variant stages its slot's 14
+//     per-surfel constants in LDS instead and deals the keyframes to its waves (pose_accumulate_desc);
+//     the surfels come in the library's per-surfel Morton order (sorted copy of the rows,
+//     badslam_hip.hip: prepare_surfels), so a wave's 64 surfels are a compact blob;
 //   * the 21 + 6 (+ cost) coefficients are accumulated per thread over its kR surfels (fused
 //     multiply-adds: these sums are compared at 1e-4, only the association predicates need
 //     bit-exact arithmetic), reduced across the wave through a wave-private LDS tile (8 columns
 //     per round: ds_write / ds_read_b128 / three DPP adds, no barrier) and the four waves' rows
-//     meet in an LDS stash, so that ONE 32-float row per (work slot, keyframe) leaves the block,
-//     with one barrier per four visited keyframes; a second kernel sums the rows in a fixed
+//     meet in an LDS stash (photometric: one wave forms the whole row), so that ONE 32-float row
+//     per (work slot, keyframe) leaves the block; a second kernel sums the rows in a fixed
 //     order: deterministic, no float atomics;
 //   * a block decides up front which keyframes of its chunk its surfels can be seen from at all
 //     (block-level frustum culling, device_math.hpp) and visits only those;
@@ -88,7 +89,7 @@ __device__ __forceinline__ void accumulate_h_b(float raw, float w, const float* 
 
 // Occupancy target handed to the register allocator: without it the 32 accumulators' zero initialisation lands in a
 // second 32-register tuple (104 VGPRs, 4 waves per SIMD); with it the geometric kernel fits 76 VGPRs (6 waves).
-// The photometric variants fit 95 VGPRs (5 waves) with their per-surfel constants in LDS.
+// The photometric variants fit 96 VGPRs (5 waves) with their per-surfel constants in LDS.
 #ifndef BSLAM_POSE_WAVES_GEO
 #define BSLAM_POSE_WAVES_GEO 6
 #endif
@@ -103,20 +104,174 @@ __device__ __forceinline__ void accumulate_h_b(float raw, float w, const float* 
 #ifndef BSLAM_POSE_REDUCE_COLS_DESC
 #define BSLAM_POSE_REDUCE_COLS_DESC 4
 #endif
-#ifndef BSLAM_POSE_STASH_GROUP_DESC
-#define BSLAM_POSE_STASH_GROUP_DESC 2
-#endif
-// columns per round / stashed keyframes per barrier: 8 / 4 for the geometry-only kernels; the photometric ones, whose 24 KB of
-// per-surfel constants already sit in LDS, take 4 / 2 so that tiles (4 KB) and stash (2 KB) leave FIVE workgroups per CU
-// (30 KB; 32 KB already means four): K = 300 dense 13.47 -> 13.27 ms, trajectory stack 1252 -> 1203 us, survey 4.40 -> 4.28 ms
+// columns per round: 8 for the geometry-only kernels; the photometric ones, whose 28 KB of per-surfel constants sit in LDS, take 4
+// so that the tiles (4 KB) leave FIVE workgroups per CU
 constexpr int kRedColsGeo = 8, kRedColsDesc = BSLAM_POSE_REDUCE_COLS_DESC;
-// One partial row per (work slot, keyframe): the four waves' rows meet in an LDS stash, one barrier per kPoseStashGroup visited
-// keyframes (two stashes alternate, so a wave that runs ahead never overwrites rows that are still being added; it cannot get
-// two groups ahead: the barrier).  A quarter of the row traffic of one row per wave: the row sums of a batched Gauss-Newton
-// iteration at K = 300 go from 428 to about 110 us.
+// One partial row per (work slot, keyframe).  Geometry-only kernels: the four waves' rows meet in an LDS stash, one barrier per
+// kPoseStashGroupGeo visited keyframes (two stashes alternate, so a wave that runs ahead never overwrites rows that are still
+// being added; it cannot get two groups ahead: the barrier).  Photometric kernels: one wave forms the whole row
+// (pose_accumulate_desc).  A quarter of the row traffic of one row per wave: the row sums of a batched Gauss-Newton iteration
+// at K = 300 go from 428 to about 110 us.
 constexpr int kPoseRowsPerSlot = 1;
 typedef unsigned long long VisWord;   // visit word of a (chunk, work slot): one bit per keyframe of the chunk (<= 64)
-constexpr int kPoseStashGroupGeo = 4, kPoseStashGroupDesc = BSLAM_POSE_STASH_GROUP_DESC;
+constexpr int kPoseStashGroupGeo = 4;
+// Photometric kernels: unroll factor of a lane's loop over the kPoseR x 4 surfels of a keyframe
+#ifndef BSLAM_POSE_DESC_UNROLL
+#define BSLAM_POSE_DESC_UNROLL 1
+#endif
+// Which keyframes of the chunk [kf_begin, kf_end) (<= 64) the block visits, decided for all of them at once, one keyframe per
+// lane: not converged (late Gauss-Newton iterations: most chunks have nothing left to do) and -- block-level frustum culling --
+// the bounding box of the slot's surfels reaches into the keyframe's image.  The word goes to vis[chunk][slot]: the row sums
+// (pose_reduce_*_kernel) only read the partial rows of visited (slot, keyframe) pairs, the others are never written.
+// Decided by the first wave and handed to the others through the LDS word `shared`: for the workgroups that leave at once (nine
+// in ten on a trajectory) the three other waves' copies of the test were the larger part of their work (survey-range stack
+// -1.5 %).  Ends with a barrier; uniform result.
+__device__ __forceinline__ unsigned long long pose_chunk_todo(const CamConsts& c, const KfDev* __restrict__ kfs, int kf_begin, int kf_end,
+                                                              const Schedule& sc, uint32_t slot, int R, uint32_t chunk,
+                                                              const PoseState* __restrict__ states, VisWord* __restrict__ vis,
+                                                              const int* __restrict__ kf_list, unsigned long long* shared) {
+  const int lane = threadIdx.x & 63;
+  if (threadIdx.x < 64) {
+    const int place = kf_begin + lane;
+    const int k = (kf_list && place < kf_end) ? kf_list[1 + place] : place;
+    const bool wanted = states == nullptr || (place < kf_end && !states[k].converged);
+    const unsigned long long todo = keyframes_to_visit(c, kfs, kf_begin, kf_end, sc, slot, R, wanted, kf_list ? k : -1);
+    if (lane == 0) { *shared = todo; vis[(size_t)chunk * sc.slots + slot] = todo; }
+  }
+  __syncthreads();
+  return *shared;
+}
+
+// Photometric variants (kDesc): the block stages the 14 per-surfel constants of its slot's kPoseR x 256 surfels in LDS once
+// (position, normal, the two tangent sample points of the descriptor residual, both descriptors: 28 KB at kPoseR = 2), shared by
+// the four waves, and the WAVES split the visited keyframes of the chunk -- wave w takes visited keyframes w, w + 4, ... -- so that
+// one wave forms a whole (slot, keyframe) row: lane l handles the kPoseR x 4 surfels g 256 + j 64 + l (g granule, j step), one
+// Morton-compact group of 64 per step, and the row's 27 (28) columns are reduced once for all of them and stored straight
+// into partials.  The fixed work per (lane, keyframe) -- zeroing the accumulators, the wave reduction, the ballot counts, the
+// translation copies -- is thus shared by 8 pairs instead of 2, and the keyframe loop needs no block barrier (round 3 formed a row
+// from four waves' rows through an LDS stash, one barrier per two keyframes).  A row's bits depend only on (slot, keyframe): each
+// lane's surfels are summed in a fixed order and the reduction order is fixed, whichever wave formed the row.
+constexpr int kPoseDescState = 14;
+template <bool kDepth, int kPoseR, bool kCost>
+__device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* __restrict__ kfs, int kf_begin, int kf_end, uint32_t chunk,
+                                                     const Schedule& sc, uint32_t slot, const SurfelRows& s, float* __restrict__ partials,
+                                                     int rows_per_kf, const PoseState* __restrict__ states, VisWord* __restrict__ vis,
+                                                     const int* __restrict__ kf_list) {
+  constexpr int kSurfels = kPoseR * kPoseThreads;
+  constexpr int kSteps = kSurfels / 64;
+  constexpr int kRedCols = kRedColsDesc;
+  // [component][surfel]: a step's 64 lanes read 64 consecutive floats (conflict-free), the component is an immediate offset
+  __shared__ float state[kPoseDescState * kSurfels];
+  // the wave-private reduction tiles; the visit word passes through their first word before the staging barrier, ahead of
+  // any use of the tiles (28 + 4 KB: five workgroups per CU, as many as 160 KB of LDS hold -- one more word would mean four)
+  __shared__ union { __attribute__((aligned(16))) float tile[kPoseThreads / 64][kRedCols * 64]; unsigned long long todo; } red;
+  static_assert(sizeof(state) + sizeof(red) <= 32768, "five workgroups per CU");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const unsigned long long todo = pose_chunk_todo(c, kfs, kf_begin, kf_end, sc, slot, kPoseR, chunk, states, vis, kf_list, &red.todo);
+  if (todo == 0) return;   // leaves before touching the surfels
+
+  // staging: thread t loads surfel t of each granule (coalesced); a column past the end gets a NaN position, which
+  // project_to_pixel rejects like the deleted surfels' NaN
+#pragma unroll
+  for (int g = 0; g < kPoseR; ++g) {
+    const uint32_t i = surfel_of_slot(sc, slot, g, kPoseR);
+    const bool valid = i < s.size;
+    const uint32_t j = valid ? i : 0;
+    const f3 gp = mk3(s.x[j], s.y[j], s.z[j]);
+    const f3 gn = unpack_normal(s.normal[j]);
+    f3 tp1, tp2;
+    tangent_points(gp, gn, s.radius_squared[j], &tp1, &tp2);
+    float* d = state + g * kPoseThreads + threadIdx.x;
+    d[0 * kSurfels] = valid ? gp.x : __uint_as_float(0x7fc00000u); d[1 * kSurfels] = gp.y; d[2 * kSurfels] = gp.z;
+    d[3 * kSurfels] = gn.x; d[4 * kSurfels] = gn.y; d[5 * kSurfels] = gn.z;
+    d[6 * kSurfels] = tp1.x; d[7 * kSurfels] = tp1.y; d[8 * kSurfels] = tp1.z;
+    d[9 * kSurfels] = tp2.x; d[10 * kSurfels] = tp2.y; d[11 * kSurfels] = tp2.z;
+    d[12 * kSurfels] = s.d1[j]; d[13 * kSurfels] = s.d2[j];
+  }
+  __syncthreads();
+
+  BSLAM_HOIST_CAM_CENTRES(c);
+  // this wave's keyframes: visited keyframes wave, wave + 4, ... of the chunk; the list entry of the next one is fetched (a
+  // scalar load) one visit ahead
+  unsigned long long mine = todo;
+  for (int w = 0; w < wave; ++w) mine &= mine - 1;
+  if (mine == 0) return;
+  auto kf_of = [&](unsigned long long m) { const int place = kf_begin + __builtin_ctzll(m); return kf_list ? kf_list[1 + place] : place; };
+  int k_next = kf_of(mine);
+  int my_col;    // the column this lane ends up with in the reduction, and whether it is the lane that stores it
+  bool writer;
+  constexpr int kLive = kCost ? kRowCost + 1 : kRowCost;   // 21 H, 6 b (, cost); the count column is filled in below
+  wave_column_sums_owner<kLive, kRedCols>(&my_col, &writer);
+  while (mine != 0) {   // uniform
+    const int k = k_next;
+#pragma unroll
+    for (int w = 0; w < kPoseThreads / 64; ++w) mine &= mine - 1;
+    if (mine != 0) k_next = kf_of(mine);
+    KfDev kf = kfs[k];   // by value: the uniform fields are fetched once per keyframe, ahead of the per-surfel branches
+    BSLAM_HOIST_KF_TRANSLATION(kf);
+    float acc[kRow];
+    // every live accumulator zeroed by its own opaque instruction (BSLAM_ZERO)
+#pragma unroll
+    for (int i = 0; i < kRow; ++i) {
+      if (i < kLive) BSLAM_ZERO(acc[i]);
+      else acc[i] = 0.f;
+    }
+    // residual count of the row: formed from ballots at the points where the lanes have reconverged (s_bcnt1 on the mask: no
+    // VALU, and one column less in the reduction below); uniform, <= 2 kSurfels: exact as a float
+    uint32_t count = 0;
+#pragma unroll BSLAM_POSE_DESC_UNROLL
+    for (int step = 0; step < kSteps; ++step) {
+      const float* st = state + step * 64 + lane;
+      bool got_depth = false, got_desc = false;
+      do {
+        Proj p;
+        DescSamples ds;
+        f2 color_pxy, t1, t2;   // the three sample positions of the descriptor residual
+        // The descriptor samples depend on the surfel and the pose only, not on the pixel record: their three quad gathers are
+        // issued together with the record gather, BEFORE the association test (99.6 % of the in-bounds pairs pass it), so a
+        // pair waits for one L2 round trip instead of two and the depth residual is evaluated while the quads are in flight
+        // (551 -> 517 us at K = 50).  Issued unconditionally -- the quad table's clamp addressing makes every address valid --
+        // so that no control-flow join sits in front of the record's wait (s_waitcnt vmcnt(3), not vmcnt(0)).
+        if (!project_to_pixel(c, kf, mk3(st[0 * kSurfels], st[1 * kSurfels], st[2 * kSurfels]), &p)) break;
+        const PixelRecord rec = load_record(c, kf, p);
+        const bool has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
+        project_tangent_points(mk3(st[6 * kSurfels], st[7 * kSurfels], st[8 * kSurfels]), mk3(st[9 * kSurfels], st[10 * kSurfels], st[11 * kSurfels]),
+                               kf.frame_T_global, c, &t1, &t2);
+        ds = descriptor_samples_issue(kf, c, color_pxy, t1, t2);
+        asm volatile("" ::: "memory");   // keeps the compiler from sinking the gathers below the branches that follow
+        if (!associate_with_record(c, kf, mk3(st[3 * kSurfels], st[4 * kSurfels], st[5 * kSurfels]), rec, &p)) break;
+        float J[6];
+        float raw;
+        if (kDepth) {                                           // BS/kernel_opt_pose.cu:283-317
+          depth_residual_and_jacobian(c, p, &raw, J);
+          accumulate_h_b(raw, depth_weight(raw), J, acc);
+          if constexpr (kCost) acc[kRowCost] += weighted_depth_residual(raw);
+          got_depth = true;
+        }
+        if (has_desc) {                                         // BS/kernel_opt_pose.cu:320-382
+          float r1, rr2, gx1, gy1, gx2, gy2;
+          descriptor_samples_finish(kf, c, ds, st[12 * kSurfels], st[13 * kSurfels], c.desc_gx_scale, c.desc_gy_scale, [&](f2 (&pts)[3]) {
+            pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);   // gradients times cfx, cfy
+          descriptor_pose_jacobian(gx1, gy1, p.local, J);
+          accumulate_h_b(r1, desc_weight(r1), J, acc);
+          descriptor_pose_jacobian(gx2, gy2, p.local, J);
+          accumulate_h_b(rr2, desc_weight(rr2), J, acc);
+          if constexpr (kCost) acc[kRowCost] += weighted_desc_residual(r1);        // quirk Q1: only the first residual is counted
+          got_desc = true;
+        }
+      } while (false);
+      count += (uint32_t)__builtin_popcountll(__ballot(got_depth)) + (uint32_t)__builtin_popcountll(__ballot(got_desc));
+    }
+
+    // wave reduction (skipped when the whole wave saw nothing for this keyframe), one row per (slot, keyframe)
+    float total = 0.f;
+    if (count != 0) total = wave_column_sums_lds<kLive, kRedCols>(acc, red.tile[wave]);
+    if (my_col == kRowCount) total = (float)count;
+    if (writer) partials[((size_t)k * rows_per_kf + (size_t)slot) * kRow + my_col] = total;
+  }
+}
+
 // kCost: the robust cost (column kRowCost) is wanted -- only the per-keyframe debug entry point returns it; the batched
 // Gauss-Newton loop never does, and leaves the tukey / huber residual evaluations out.
 template <bool kDepth, bool kDesc, int kPoseR, bool kCost>
@@ -140,38 +295,22 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
   const int kf_begin = (int)chunk * kfs_per_block;
   if (kf_begin >= kf_places) return;   // the host sized the grid by an older (larger) count of unconverged keyframes
   const int kf_end = min(kf_places, kf_begin + kfs_per_block);
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  // Which keyframes of the chunk (<= 64) this block visits, decided for all of them at once, one keyframe per lane: not
-  // converged (late Gauss-Newton iterations: most chunks have nothing left to do) and -- block-level frustum culling -- the
-  // bounding box of the slot's surfels reaches into the keyframe's image.  The word goes to vis[chunk][slot]: the row sums
-  // (pose_reduce_*_kernel) only read the partial rows of visited (slot, keyframe) pairs, the others are never written.
-  unsigned long long todo;
-  // decided by the first wave and handed to the others through LDS: for the workgroups that leave here (nine in ten on a
-  // trajectory) the three other waves' copies of the test were the larger part of their work (survey-range stack -1.5 %)
-  __shared__ unsigned long long todo_shared;
-  if (wave == 0) {
-    const int place = kf_begin + lane;
-    const int k = (kf_list && place < kf_end) ? kf_list[1 + place] : place;
-    const bool wanted = states == nullptr || (place < kf_end && !states[k].converged);
-    todo = keyframes_to_visit(c, kfs, kf_begin, kf_end, sc, slot, kPoseR, wanted, kf_list ? k : -1);
-    if (lane == 0) { todo_shared = todo; vis[(size_t)chunk * sc.slots + slot] = todo; }
+  if constexpr (kDesc) {
+    pose_accumulate_desc<kDepth, kPoseR, kCost>(c, kfs, kf_begin, kf_end, chunk, sc, slot, s, partials, rows_per_kf, states, vis, kf_list);
+    return;
   }
-  __syncthreads();
-  todo = todo_shared;
+  // Geometry-only variants: a thread keeps its kPoseR surfels in registers and walks the visited keyframes of the chunk; the
+  // four waves' rows of a keyframe meet in an LDS stash.
+  const int wave = threadIdx.x >> 6;
+  __shared__ unsigned long long todo_shared;
+  unsigned long long todo = pose_chunk_todo(c, kfs, kf_begin, kf_end, sc, slot, kPoseR, chunk, states, vis, kf_list, &todo_shared);
   if (todo == 0) return;   // leaves before touching the surfels
 
   // surfels of this thread: tile * kPoseTile + r * kPoseThreads + threadIdx.x (coalesced per r)
   f3 gp[kPoseR], gn[kPoseR];
   bool valid[kPoseR];
-  // Photometric variant: 12 per-surfel constants (position, normal, the two tangent sample points of the descriptor
-  // residual) live in LDS -- [component][thread]: conflict-free, private to the thread, no barrier -- instead of 24 VGPRs, and
-  // are read back where a pair needs them (round 2: 123 -> 95 VGPRs, 518 -> 495 us at K = 50).
-  constexpr int kState = 12;
-  __shared__ float state[kDesc ? kState * kPoseR * kPoseThreads : 1];
-  float desc1[kDesc ? kPoseR : 1], desc2[kDesc ? kPoseR : 1];   // in registers: 24 + 8 + 4 KB of LDS per block leave four blocks per CU
-  constexpr int kRedCols = kDesc ? kRedColsDesc : kRedColsGeo;
-  constexpr int kPoseStashGroup = kDesc ? kPoseStashGroupDesc : kPoseStashGroupGeo;
+  constexpr int kRedCols = kRedColsGeo;
+  constexpr int kPoseStashGroup = kPoseStashGroupGeo;
   __shared__ float row_stash[2][kPoseStashGroup][kPoseThreads / 64][kRow];
   __shared__ int stash_kf[2][kPoseStashGroup];
   int stashed = 0, stash_buf = 0;   // uniform
@@ -186,7 +325,6 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
   };
   static_assert(kPoseStashGroup * kRow <= kPoseThreads && kPoseThreads / 64 == 4, "one thread per stashed column; four waves");
   __shared__ __attribute__((aligned(16))) float red_tile[kPoseThreads / 64][kRedCols * 64];   // wave-private tiles of the row reduction
-  auto st = [&](int r, int comp) -> float& { return state[(r * kState + comp) * kPoseThreads + threadIdx.x]; };
 #pragma unroll
   for (int r = 0; r < kPoseR; ++r) {
     const uint32_t i = surfel_of_slot(sc, slot, r, kPoseR);
@@ -194,19 +332,9 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
     const uint32_t j = valid[r] ? i : 0;
     gp[r] = mk3(s.x[j], s.y[j], s.z[j]);
     gn[r] = unpack_normal(s.normal[j]);
-    if constexpr (kDesc) {
-      f3 tp1, tp2;
-      tangent_points(gp[r], gn[r], s.radius_squared[j], &tp1, &tp2);
-      st(r, 0) = gp[r].x; st(r, 1) = gp[r].y; st(r, 2) = gp[r].z;
-      st(r, 3) = gn[r].x; st(r, 4) = gn[r].y; st(r, 5) = gn[r].z;
-      st(r, 6) = tp1.x; st(r, 7) = tp1.y; st(r, 8) = tp1.z;
-      st(r, 9) = tp2.x; st(r, 10) = tp2.y; st(r, 11) = tp2.z;
-      desc1[r] = s.d1[j]; desc2[r] = s.d2[j];
-    }
   }
 
-  if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
-  else if constexpr (kPoseR > 4) BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
+  if constexpr (kPoseR > 4) BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
   // the list entry of the next keyframe to visit is fetched (a scalar load) one visit ahead
   int k_next = kf_begin + __builtin_ctzll(todo);
   if (kf_list) k_next = kf_list[1 + k_next];
@@ -218,7 +346,7 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
       if (kf_list) k_next = kf_list[1 + k_next];
     }
     KfDev kf = kfs[k];   // by value: the uniform fields are fetched once per keyframe, ahead of the per-surfel branches
-    if constexpr (kDesc || kPoseR > 4) BSLAM_HOIST_KF_TRANSLATION(kf);
+    if constexpr (kPoseR > 4) BSLAM_HOIST_KF_TRANSLATION(kf);
     float acc[kRow];
     // Every live accumulator is zeroed by its own opaque instruction.  Written as acc[i] = 0.f the optimiser knows all of
     // them to be one value: it folds the first surfel's fma(wj, J, 0) into a multiply and then has to materialise the zeros a
@@ -234,29 +362,11 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
 
 #pragma unroll
     for (int r = 0; r < kPoseR; ++r) {
-      bool got_depth = false, got_desc = false;
+      bool got_depth = false;
       do {
         Proj p;
-        DescSamples ds;
-        f2 color_pxy, t1, t2;   // the three sample positions of the descriptor residual
-        bool has_desc = false;
         if (!valid[r]) break;
-        if constexpr (!kDesc) {
-          if (!project_and_associate(c, kf, gp[r], gn[r], &p)) break;
-        } else {
-          // The descriptor samples depend on the surfel and the pose only, not on the pixel record: their three quad gathers
-          // are issued together with the record gather, BEFORE the association test (99.6 % of the in-bounds pairs pass it),
-          // so a pair waits for one L2 round trip instead of two and the depth residual is evaluated while the quads are in
-          // flight (551 -> 517 us at K = 50).  Issued unconditionally -- the quad table's clamp addressing makes every address
-          // valid -- so that no control-flow join sits in front of the record's wait (s_waitcnt vmcnt(3), not vmcnt(0)).
-          if (!project_to_pixel(c, kf, mk3(st(r, 0), st(r, 1), st(r, 2)), &p)) break;
-          const PixelRecord rec = load_record(c, kf, p);
-          has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
-          project_tangent_points(mk3(st(r, 6), st(r, 7), st(r, 8)), mk3(st(r, 9), st(r, 10), st(r, 11)), kf.frame_T_global, c, &t1, &t2);
-          ds = descriptor_samples_issue(kf, c, color_pxy, t1, t2);
-          asm volatile("" ::: "memory");   // keeps the compiler from sinking the gathers below the branches that follow
-          if (!associate_with_record(c, kf, mk3(st(r, 3), st(r, 4), st(r, 5)), rec, &p)) break;
-        }
+        if (!project_and_associate(c, kf, gp[r], gn[r], &p)) break;
         float J[6];
         float raw;
         if (kDepth) {                                           // BS/kernel_opt_pose.cu:283-317
@@ -265,21 +375,8 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
           if constexpr (kCost) acc[kRowCost] += weighted_depth_residual(raw);
           got_depth = true;
         }
-        if (kDesc) {                                            // BS/kernel_opt_pose.cu:320-382
-          if (has_desc) {
-            float r1, rr2, gx1, gy1, gx2, gy2;
-            descriptor_samples_finish(kf, c, ds, desc1[r], desc2[r], c.desc_gx_scale, c.desc_gy_scale, [&](f2 (&pts)[3]) {
-              pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);   // gradients times cfx, cfy
-            descriptor_pose_jacobian(gx1, gy1, p.local, J);
-            accumulate_h_b(r1, desc_weight(r1), J, acc);
-            descriptor_pose_jacobian(gx2, gy2, p.local, J);
-            accumulate_h_b(rr2, desc_weight(rr2), J, acc);
-            if constexpr (kCost) acc[kRowCost] += weighted_desc_residual(r1);        // quirk Q1: only the first residual is counted
-            got_desc = true;
-          }
-        }
       } while (false);
-      count += (uint32_t)__builtin_popcountll(__ballot(got_depth)) + (uint32_t)__builtin_popcountll(__ballot(got_desc));
+      count += (uint32_t)__builtin_popcountll(__ballot(got_depth));
     }
 
     // wave reduction (skipped when the whole wave saw nothing for this keyframe)

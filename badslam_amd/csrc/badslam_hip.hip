@@ -432,6 +432,35 @@ static unsigned long long* cull_stats_ptr(bslam_context* ctx) {
   return ctx->profiling ? (unsigned long long*)((uint8_t*)ctx->misc.ptr + kMiscCullStats) : nullptr;
 }
 
+// Grid of a pass with the pose kernel's shape (pose_accumulate_kernel, ba_cost_kernel): 8 * slots_per_xcd * launch_chunks blocks,
+// a block walks a chunk of <= 64 keyframes of one work slot, and leaves one visit word per (chunk, slot) in ctx->vis.
+struct PoseGrid {
+  Schedule sc;             // the prepared schedule, culling decided
+  int per_block;           // keyframes per chunk
+  unsigned chunks;         // chunks of the keyframe table: the visit words reserved
+  unsigned launch_chunks;  // chunks the grid covers
+  dim3 grid;
+};
+// multiple: chunk lengths are rounded up to it (choose_kfs_per_block).  list_bound >= 0: the launch walks a device-side keyframe
+// list (the batched loop's unconverged keyframes) whose length is at most list_bound (the count of an earlier iteration, known to
+// the host), which sizes the grid -- the visit words keep room for all chunks; < 0: the launch walks the keyframe table.
+static int plan_pose_grid(bslam_context* ctx, const Schedule& prepared, int kf_count, int multiple, int list_bound, PoseGrid* g) {
+  g->sc = prepared;
+  // A block walks a chunk of <= 64 keyframes of one work slot; on short keyframe lists the chunks are so short (6 keyframes at
+  // K = 50) that the culling test at the head of every block costs more than it saves on any stack we have (K = 50 dense, 12 %
+  // of the blocks culled: 96 -> 102 us per launch).  The geometry / PCG / intrinsics kernels walk the whole list per block and
+  // keep it.
+#ifndef BSLAM_POSE_CULL_MIN_KEYFRAMES
+#define BSLAM_POSE_CULL_MIN_KEYFRAMES 64
+#endif
+  if (kf_count < BSLAM_POSE_CULL_MIN_KEYFRAMES) g->sc.bounds = nullptr;
+  g->per_block = choose_kfs_per_block((int)g->sc.slots, kf_count, multiple);   // <= 64: one bit per keyframe of a chunk in a visit word
+  g->chunks = (unsigned)((kf_count + g->per_block - 1) / g->per_block);
+  g->launch_chunks = list_bound >= 0 ? (unsigned)std::max(1, (std::min(list_bound, kf_count) + g->per_block - 1) / g->per_block) : g->chunks;
+  g->grid = dim3(8u * g->sc.slots_per_xcd * g->launch_chunks);
+  return ctx->vis.reserve((size_t)g->chunks * g->sc.slots * sizeof(VisWord));
+}
+
 // `work`: the prepared schedule + rows of this API call (prepare_surfels; the batched Gauss-Newton loop prepares them once for
 // all its iterations), or nullptr to prepare them here.
 static int launch_pose_accumulate(bslam_context* ctx, hipStream_t stream, int use_depth, int use_desc, const CamConsts& c,
@@ -444,35 +473,24 @@ static int launch_pose_accumulate(bslam_context* ctx, hipStream_t stream, int us
     if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, pose_surfels_per_thread(use_desc != 0, surfels_size), kf_count, &local, use_desc != 0))) return rc;
     work = &local;
   }
-  Schedule sc = work->sc;
-  // A block of this kernel walks a chunk of <= 32 keyframes of one work slot; on short keyframe lists the chunks are so short
-  // (6 keyframes at K = 50) that the culling test at the head of every block costs more than it saves on any stack we have
-  // (K = 50 dense, 12 % of the blocks culled: 96 -> 102 us per launch).  The geometry / PCG / intrinsics kernels walk the whole
-  // list per block and keep it.
-#ifndef BSLAM_POSE_CULL_MIN_KEYFRAMES
-#define BSLAM_POSE_CULL_MIN_KEYFRAMES 64
-#endif
-  if (kf_count < BSLAM_POSE_CULL_MIN_KEYFRAMES) sc.bounds = nullptr;
-  const int tiles = (int)sc.slots;
+  const int tiles = (int)work->sc.slots;
   *tiles_out = tiles;
-  const int rows_per_kf = tiles * kPoseRowsPerSlot;   // one partial row per (slot, wave), or per slot
-  const size_t partial_floats = (size_t)rows_per_kf * kf_count * kRow;
-  rc = ctx->partials.reserve((partial_floats + (size_t)kf_count * kReduceParts * kRow) * sizeof(float));
+  const int rows_per_kf = tiles;   // one partial row per (work slot, keyframe)
+  rc = ctx->partials.reserve((size_t)rows_per_kf * kf_count * kRow * sizeof(float));
   if (rc) return rc;
   rc = ctx->coeffs.reserve((size_t)kf_count * kRow * sizeof(float));
   if (rc) return rc;
 #ifndef BSLAM_POSE_DESC_KF_MULTIPLE
 #define BSLAM_POSE_DESC_KF_MULTIPLE 4
 #endif
-  const int per_block = choose_kfs_per_block(tiles, kf_count, use_desc ? BSLAM_POSE_DESC_KF_MULTIPLE : 1);   // <= 64: one bit per keyframe of a chunk in a visit word
-  const unsigned chunks = (unsigned)((kf_count + per_block - 1) / per_block);
+  // kf_list: the launch walks the device-side list of unconverged keyframes (batched loop), at most kf_list_bound long
+  PoseGrid g;
+  if ((rc = plan_pose_grid(ctx, work->sc, kf_count, use_desc ? BSLAM_POSE_DESC_KF_MULTIPLE : 1, kf_list ? kf_list_bound : -1, &g))) return rc;
+  const Schedule& sc = g.sc;
+  const int per_block = g.per_block;
   if (kfs_per_block_out) *kfs_per_block_out = per_block;
-  if ((rc = ctx->vis.reserve((size_t)chunks * sc.slots * sizeof(VisWord)))) return rc;
   VisWord* vis = (VisWord*)ctx->vis.ptr;
-  // kf_list: the launch walks the device-side list of unconverged keyframes (batched loop); kf_list_bound = an upper bound of its
-  // length known to the host (the count of an earlier iteration), which sizes the grid -- the visit words keep room for all chunks
-  const unsigned launch_chunks = kf_list ? (unsigned)std::max(1, (std::min(kf_list_bound, kf_count) + per_block - 1) / per_block) : chunks;
-  dim3 grid(8u * sc.slots_per_xcd * launch_chunks);
+  const dim3 grid = g.grid;
   const SurfelRows rows = work->rows;
   const KfDev* kfs = (const KfDev*)ctx->kf_table.ptr;
   float* partials = (float*)ctx->partials.ptr;
@@ -922,7 +940,7 @@ int bslam_accumulate_pose_estimation_coeffs(
   std::memcpy(b, out + 21, 6 * sizeof(float));
   if (debug) {
     if (residual_sum) *residual_sum = out[kRowCost];
-    if (residual_count) *residual_count = (uint32_t)out[kRowCount] + ((uint32_t)out[kRowCount + 1] << 16);
+    if (residual_count) *residual_count = read_row_count(out);
   }
   return BSLAM_OK;
 }
@@ -954,7 +972,7 @@ int bslam_accumulate_pose_coeffs_batched(
     const float* out = (const float*)ctx->staging2.ptr;
     for (int k = 0; k < keyframe_count; ++k) {
       if (Hb) std::memcpy(Hb + 27 * (size_t)k, out + (size_t)k * kRow, 27 * sizeof(float));
-      if (counts) counts[k] = (uint32_t)out[(size_t)k * kRow + kRowCount] + ((uint32_t)out[(size_t)k * kRow + kRowCount + 1] << 16);
+      if (counts) counts[k] = read_row_count(out + (size_t)k * kRow);
     }
   }
   return BSLAM_OK;
@@ -1044,7 +1062,7 @@ int bslam_estimate_frame_poses_batched(
       {
         ProfScope prof(ctx, stream, BSLAM_PROF_POSE_REDUCE);
         hipLaunchKernelGGL(pose_reduce_solve_kernel, dim3((unsigned)keyframe_count), dim3(kReduceSolveThreads), (unsigned)visit_map_bytes(tiles), stream, (const float*)ctx->partials.ptr,
-                           tiles * kPoseRowsPerSlot, keyframe_count, d_states, (KfDev*)ctx->kf_table.ptr, d_active + slot, d_active + ((it + 1) & 3),
+                           tiles, keyframe_count, d_states, (KfDev*)ctx->kf_table.ptr, d_active + slot, d_active + ((it + 1) & 3),
                            (const VisWord*)ctx->vis.ptr, per_block, cull_stats_ptr(ctx), d_list ? d_list + 1 + keyframe_count : nullptr);
       }
       BSLAM_HIP_TRY(hipGetLastError());

@@ -34,18 +34,17 @@ int bslam_compute_ba_cost(
     const int R = pose_surfels_per_thread(desc, surfels_size);
     SurfelWork work;
     if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, R, keyframe_count, &work, desc))) return rc;
-    Schedule sc = work.sc;
-    if (keyframe_count < BSLAM_POSE_CULL_MIN_KEYFRAMES) sc.bounds = nullptr;   // the pose kernel's rule (launch_pose_accumulate)
-    const int rows_per_kf = (int)sc.slots;   // one row per (work slot, keyframe)
+    const int rows_per_kf = (int)work.sc.slots;   // one row per (work slot, keyframe)
     if ((rc = ctx->partials.reserve((size_t)rows_per_kf * keyframe_count * kCostCols * sizeof(float)))) return rc;
-    const int per_block = choose_kfs_per_block(rows_per_kf, keyframe_count);
-    const unsigned chunks = (unsigned)((keyframe_count + per_block - 1) / per_block);
-    if ((rc = ctx->vis.reserve((size_t)chunks * sc.slots * sizeof(VisWord)))) return rc;
+    PoseGrid g;
+    if ((rc = plan_pose_grid(ctx, work.sc, keyframe_count, 1, -1, &g))) return rc;
+    const Schedule& sc = g.sc;
+    const int per_block = g.per_block;
+    const dim3 grid = g.grid;
     VisWord* vis = (VisWord*)ctx->vis.ptr;
     float* partials = (float*)ctx->partials.ptr;
     const KfDev* kfs = (const KfDev*)ctx->kf_table.ptr;
     const uint8_t* active = active_surfels ? (const uint8_t*)active_surfels->address : nullptr;
-    const dim3 grid(8u * sc.slots_per_xcd * chunks);
     {
       ProfScope prof(ctx, stream, BSLAM_PROF_BA_COST);
 #define BSLAM_LAUNCH_COST(DEPTH, DESC, RR)                                                                                                        \

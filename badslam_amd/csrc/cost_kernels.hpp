@@ -29,24 +29,16 @@ __global__ __launch_bounds__(kPoseThreads) void ba_cost_kernel(CamConsts c_in, c
                                                                const uint32_t* __restrict__ perm, float* __restrict__ partials, int rows_per_kf,
                                                                VisWord* __restrict__ vis) {
   CamConsts c = c_in;
-  const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-  const uint32_t chunk = j / sc.slots_per_xcd, local = j - chunk * sc.slots_per_xcd;
-  uint32_t slot;
-  if (!slot_of_block(sc, (local << 3) | xcd, &slot)) return;
+  uint32_t chunk, slot;
+  if (!chunk_and_slot_of_block(sc, &chunk, &slot)) return;
   const int kf_begin = (int)chunk * kfs_per_block;
   if (kf_begin >= kf_count) return;
   const int kf_end = min(kf_count, kf_begin + kfs_per_block);
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  // the keyframes of the chunk this block visits (pose_accumulate_kernel): the word goes to vis[chunk][slot] for the row sums
-  unsigned long long todo;
+  // the keyframes of the chunk this block visits, as in pose_accumulate_kernel (every keyframe is wanted, no keyframe list)
   __shared__ unsigned long long todo_shared;
-  if (wave == 0) {
-    todo = keyframes_to_visit(c, kfs, kf_begin, kf_end, sc, slot, kR, true);
-    if (lane == 0) { todo_shared = todo; vis[(size_t)chunk * sc.slots + slot] = todo; }
-  }
-  __syncthreads();
-  todo = todo_shared;
+  unsigned long long todo = pose_chunk_todo(c, kfs, kf_begin, kf_end, sc, slot, kR, chunk, nullptr, vis, nullptr, &todo_shared);
   if (todo == 0) return;
 
   // surfels of this thread, in registers: the cost path carries no accumulators to make room for
@@ -68,19 +60,8 @@ __global__ __launch_bounds__(kPoseThreads) void ba_cost_kernel(CamConsts c_in, c
     }
   }
 
-  __shared__ float row_stash[2][kCostStashGroup][kPoseThreads / 64][kCostCols];
-  __shared__ int stash_kf[2][kCostStashGroup];
-  __shared__ __attribute__((aligned(16))) float red_tile[kPoseThreads / 64][kCostRedCols * 64];
-  static_assert(kCostStashGroup * kCostCols <= kPoseThreads && kPoseThreads / 64 == 4, "one thread per stashed column; four waves");
-  int stashed = 0, stash_buf = 0;   // uniform
-  auto flush_rows = [&](int n) {
-    __syncthreads();
-    const int jr = threadIdx.x / kCostCols, col = threadIdx.x % kCostCols;
-    if (jr < n) {
-      const float (*w)[kCostCols] = row_stash[stash_buf][jr];
-      partials[((size_t)stash_kf[stash_buf][jr] * rows_per_kf + slot) * kCostCols + col] = ((w[0][col] + w[1][col]) + w[2][col]) + w[3][col];
-    }
-  };
+  __shared__ RowStash<kCostCols, kCostStashGroup, kCostRedCols> stash;
+  RowStashCursor at;
 
   if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
   while (todo != 0) {   // uniform
@@ -134,16 +115,15 @@ __global__ __launch_bounds__(kPoseThreads) void ba_cost_kernel(CamConsts c_in, c
     int my_col;
     bool writer;
     wave_column_sums_owner<2, kCostRedCols>(&my_col, &writer);
-    if (n_depth + n_desc != 0) total = wave_column_sums_lds<2, kCostRedCols>(cost, red_tile[wave]);
-    if (writer && my_col < 2) row_stash[stash_buf][stashed][wave][my_col] = total;
+    if (n_depth + n_desc != 0) total = wave_column_sums_lds<2, kCostRedCols>(cost, stash.tile[wave]);
+    if (writer && my_col < 2) stash.put(at, my_col, total);
     if (lane == 0) {
-      row_stash[stash_buf][stashed][wave][2] = (float)n_depth;   // <= 64 * kR: exact
-      row_stash[stash_buf][stashed][wave][3] = (float)n_desc;
+      stash.put(at, 2, (float)n_depth);   // <= 64 * kR: exact
+      stash.put(at, 3, (float)n_desc);
     }
-    if (threadIdx.x == 0) stash_kf[stash_buf][stashed] = k;
-    if (++stashed == kCostStashGroup) { flush_rows(stashed); stashed = 0; stash_buf ^= 1; }
+    stash.next(at, k, partials, rows_per_kf, slot);
   }
-  if (stashed) flush_rows(stashed);
+  if (at.n) stash.flush(at, partials, rows_per_kf, slot);
 }
 
 // Row sums of keyframe k = blockIdx.x: the rows of the work slots that visited it (vis: bit place % kfs_per_block of the word

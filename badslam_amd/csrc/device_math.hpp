@@ -818,6 +818,15 @@ __device__ __forceinline__ bool slot_of_block(const Schedule& sc, uint32_t b, ui
   return true;
 }
 
+// (keyframe chunk, work slot) of this block in a 1-D grid of 8 * slots_per_xcd * chunks blocks (the pose and cost passes), or
+// false: block b -> XCD lane b % 8; within an XCD the blocks run chunk-major over that XCD's share of the work slots.
+__device__ __forceinline__ bool chunk_and_slot_of_block(const Schedule& sc, uint32_t* chunk, uint32_t* slot) {
+  const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+  *chunk = j / sc.slots_per_xcd;
+  const uint32_t local = j - *chunk * sc.slots_per_xcd;
+  return slot_of_block(sc, (local << 3) | xcd, slot);
+}
+
 // Surfel column of this thread for granule r of the slot (R granules per slot); >= size if none.
 __device__ __forceinline__ uint32_t surfel_of_slot(const Schedule& sc, uint32_t slot, int r, int R) {
   const uint32_t pos = slot * (uint32_t)R + (uint32_t)r;
@@ -1067,6 +1076,37 @@ __device__ __forceinline__ float wave_column_sums_lds(const float (&v)[N], float
   if constexpr (kBatches == 2) t = (lane % (16u / kCols) == 1) ? total[1] : total[0];
   return (col < kLive) ? t : 0.f;
 }
+
+// One row of kCols floats per (keyframe, work slot) from the four waves of a 256-thread workgroup (pose, cost and PCG passes).
+// Every wave puts its wave sums for a keyframe into an entry of the stash and moves on; after kGroup entries ONE barrier lets
+// the block add the four waves' values -- ((w0 + w1) + w2) + w3 -- and store one row per entry.  Two buffers alternate, so a
+// wave that runs ahead into the next group never overwrites entries that are still being added (it cannot get two groups
+// ahead: the barrier).  The cursor (entries in the current buffer, which buffer) is uniform and stays in the caller's registers.
+struct RowStashCursor { int n = 0, buf = 0; };
+template <int kCols, int kGroup, int kRedCols>
+struct RowStash {
+  static_assert(kGroup * kCols <= 256, "one thread per stashed value");
+  float v[2][kGroup][4][kCols];
+  int kf[2][kGroup];
+  __attribute__((aligned(16))) float tile[4][kRedCols * 64];   // wave-private tiles of wave_column_sums_lds
+  // this wave's value of column `col` of the current entry
+  __device__ __forceinline__ void put(const RowStashCursor& at, int col, float x) { v[at.buf][at.n][(int)(threadIdx.x >> 6)][col] = x; }
+  // the current entry is keyframe k's; a full group is flushed
+  __device__ __forceinline__ void next(RowStashCursor& at, int k, float* __restrict__ out, size_t rows_per_kf, size_t slot) {
+    if (threadIdx.x == 0) kf[at.buf][at.n] = k;
+    if (++at.n == kGroup) { flush(at, out, rows_per_kf, slot); at.n = 0; at.buf ^= 1; }
+  }
+  // adds up the at.n entries of the current buffer and stores row (kf, slot) of each: out[(kf * rows_per_kf + slot) * kCols + col]
+  // (all threads call; holds the group's one barrier)
+  __device__ __forceinline__ void flush(const RowStashCursor& at, float* __restrict__ out, size_t rows_per_kf, size_t slot) {
+    __syncthreads();
+    const int j = threadIdx.x / kCols, col = threadIdx.x - j * kCols;
+    if (j < at.n) {
+      const float (*w)[kCols] = v[at.buf][j];
+      out[((size_t)kf[at.buf][j] * rows_per_kf + slot) * kCols + col] = ((w[0][col] + w[1][col]) + w[2][col]) + w[3][col];
+    }
+  }
+};
 
 // Generic form for N = 8 or 16 values: N - 1 exchanges down to one value per lane, then log2(64 / N)
 // butterfly steps.  Afterwards every lane holds the wave total of column (lane / (64 / N)) % N.

@@ -67,9 +67,9 @@ static int run_pair_kernel(bslam_context* ctx, hipStream_t stream, bool coeffs, 
 #undef BSLAM_PAIR_GM
   BSLAM_HIP_TRY(hipGetLastError());
   float* parts = partials + partial_floats;
-  hipLaunchKernelGGL(pose_reduce_kernel, dim3(1, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, 1, parts, (const PoseState*)nullptr);
+  hipLaunchKernelGGL(pose_reduce_kernel, dim3(1, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, parts);
   BSLAM_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)parts, 1, (float*)ctx->coeffs.ptr, (const PoseState*)nullptr);
+  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
   BSLAM_HIP_TRY(hipGetLastError());
   if ((rc = ctx->staging2.reserve(kRow * sizeof(float)))) return rc;
   BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, kRow * sizeof(float), hipMemcpyDeviceToHost, stream));
@@ -77,8 +77,6 @@ static int run_pair_kernel(bslam_context* ctx, hipStream_t stream, bool coeffs, 
   std::memcpy(row_out, ctx->staging2.ptr, kRow * sizeof(float));
   return BSLAM_OK;
 }
-
-static uint32_t row_count(const float* row) { return (uint32_t)row[kRowCount] + ((uint32_t)row[kRowCount + 1] << 16); }
 
 }  // namespace bslam
 
@@ -179,7 +177,7 @@ int bslam_accumulate_pose_coeffs_from_images(
   if (rc) return rc;
   std::memcpy(H, row, 21 * sizeof(float));
   std::memcpy(b, row + 21, 6 * sizeof(float));
-  if (visible_count) *visible_count = row_count(row);
+  if (visible_count) *visible_count = read_row_count(row);
   return BSLAM_OK;
 }
 
@@ -193,7 +191,7 @@ int bslam_compute_cost_and_residual_count_from_images(
   int rc = run_pair_kernel(ctx, (hipStream_t)stream, false, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
                            downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
   if (rc) return rc;
-  *residual_count = row_count(row);
+  *residual_count = read_row_count(row);
   *residual_sum = row[kRowCost];
   return BSLAM_OK;
 }
@@ -210,7 +208,7 @@ int bslam_accumulate_pose_coeffs_from_images_gradmag(
   if (rc) return rc;
   std::memcpy(H, row, 21 * sizeof(float));
   std::memcpy(b, row + 21, 6 * sizeof(float));
-  if (visible_count) *visible_count = row_count(row);
+  if (visible_count) *visible_count = read_row_count(row);
   return BSLAM_OK;
 }
 
@@ -224,7 +222,7 @@ int bslam_compute_cost_and_residual_count_from_images_gradmag(
   int rc = run_pair_kernel(ctx, (hipStream_t)stream, false, true, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
                            downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
   if (rc) return rc;
-  *residual_count = row_count(row);
+  *residual_count = read_row_count(row);
   *residual_sum = row[kRowCost];
   return BSLAM_OK;
 }

@@ -40,37 +40,23 @@ constexpr int kPcgR = BSLAM_PCG_R;
 // reduction (6 - 12 wave sums + a barrier) over twice as many pairs
 constexpr int pcg_surfels_per_thread(bool desc, bool intr) { return (!desc && !intr) ? BSLAM_PCG_R_GEO : kPcgR; }
 constexpr int kPcgPoseRow = 12;    // init: r[6], M[6];  step1: g[6] (+6 unused)
-// Per-keyframe pose rows of a workgroup: every wave drops its wave sums into an LDS stash and moves on; after kPcgGroup visited
-// keyframes ONE barrier lets the block add the four waves' entries -- ((w0 + w1) + w2) + w3, the order of the former
-// per-keyframe reduction: same bits -- and store one row per (keyframe, work slot).  Two stashes alternate, so a wave that runs
-// ahead into the next group never overwrites entries that are still being added (it cannot get two groups ahead: the barrier).
+// Per-keyframe pose rows of a workgroup: the four waves' wave sums meet in a RowStash, one barrier per kPcgGroup visited
+// keyframes, and leave as one row per (keyframe, work slot).  The wave sums go through the wave's LDS tile
+// (wave_column_sums_lds, 4 columns per round) instead of six-step shuffle sums of each value (measured on one box: K = 300
+// photometric pcg_step1_kernel 16.7 -> 15.7 ms, pcg_init_kernel 18.6 -> 16.7 ms, BA iteration 340 -> 321 ms; K = 50
+// geometry-only 210 -> 187 us and 270 -> 195 us).
 constexpr int kPcgGroup = 16;
-struct PcgRowStash {
-  float v[2][kPcgGroup][4][kPcgPoseRow];
-  int kf[2][kPcgGroup];
-  __attribute__((aligned(16))) float tile[4][4 * 64];   // wave-private tiles of the wave sums (wave_column_sums_lds, 4 columns per round)
-};
-// The wave sums of `pose` go into the stash entry of keyframe k, through the wave's LDS tile instead of six-step shuffle sums of
-// each value (measured on one box: K = 300 photometric pcg_step1_kernel 16.7 -> 15.7 ms, pcg_init_kernel 18.6 -> 16.7 ms, BA
-// iteration 340 -> 321 ms; K = 50 geometry-only 210 -> 187 us and 270 -> 195 us).
+// The wave sums of the first kLive entries of `pose` go into the current stash entry, which becomes keyframe k's.
 template <int kLive>
-__device__ __forceinline__ void pcg_stash_wave_sums(PcgRowStash& st, int buf, int at, int k, const float (&pose)[kPcgPoseRow]) {
-  const int wave = threadIdx.x >> 6;
+__device__ __forceinline__ void pcg_stash_pose(RowStash<kPcgPoseRow, kPcgGroup, 4>& st, RowStashCursor& at, int k, const float (&pose)[kPcgPoseRow],
+                                               float* __restrict__ partial_pose, uint32_t slots, int tile) {
   int col;
   bool writer;
   wave_column_sums_owner<kLive, 4>(&col, &writer);   // column lane / 4, stored by every fourth lane
-  const float total = wave_column_sums_lds<kLive, 4>(pose, st.tile[wave]);
-  if (writer && col < kPcgPoseRow) st.v[buf][at][wave][col] = total;
-  if (threadIdx.x == 0) st.kf[buf][at] = k;
+  const float total = wave_column_sums_lds<kLive, 4>(pose, st.tile[threadIdx.x >> 6]);
+  if (writer && col < kPcgPoseRow) st.put(at, col, total);
+  st.next(at, k, partial_pose, slots, tile);
 }
-// Adds up and stores the `n` stashed keyframes of buffer `buf` (all threads call; contains the group's one barrier).
-__device__ __forceinline__ void pcg_flush_rows(PcgRowStash& st, int buf, int n, float* __restrict__ partial_pose, uint32_t slots, int tile) {
-  __syncthreads();
-  const int j = threadIdx.x / kPcgPoseRow, col = threadIdx.x - j * kPcgPoseRow;
-  if (j < n)
-    partial_pose[((size_t)st.kf[buf][j] * slots + tile) * kPcgPoseRow + col] = ((st.v[buf][j][0][col] + st.v[buf][j][1][col]) + st.v[buf][j][2][col]) + st.v[buf][j][3][col];
-}
-static_assert(kPcgGroup * kPcgPoseRow <= kPcgThreads, "one thread per stashed value");
 // Zero rows for the keyframes of the batch [k0, k0 + 64) that the workgroup does not visit (frustum culling): the row sums read
 // every (keyframe, work slot) row.
 __device__ __forceinline__ void pcg_zero_rows(unsigned long long visited, int k0, int k_end, float* __restrict__ partial_pose, uint32_t slots, int tile) {
@@ -186,7 +172,7 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
   uint32_t slot;
   if (!slot_of_block(sc, blockIdx.x, &slot)) return;
   const int tile = (int)slot;
-  __shared__ PcgRowStash stash;
+  __shared__ RowStash<kPcgPoseRow, kPcgGroup, 4> stash;
   __shared__ float redg[4][32];
 
   f3 gp[R], gn[R];
@@ -219,8 +205,7 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
   if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
   else BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
   BSLAM_HOIST_UNPROJECTION_CENTRE(c);
-  int stashed = 0;   // keyframes in the current stash (uniform)
-  int buf = 0;
+  RowStashCursor at;
   for (int k0 = 0; k0 < kf_count; k0 += 64) {
   unsigned long long todo = keyframes_to_visit(c, kfs, k0, kf_count, sc, slot, R, true);
   if (P.optimize_poses && sc.bounds != nullptr) pcg_zero_rows(todo, k0, kf_count, partial_pose, sc.slots, tile);
@@ -336,12 +321,11 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
     }
 
     if (opt_pose) {   // uniform
-      pcg_stash_wave_sums<kPcgPoseRow>(stash, buf, stashed, k, pose);
-      if (++stashed == kPcgGroup) { pcg_flush_rows(stash, buf, stashed, partial_pose, sc.slots, tile); stashed = 0; buf ^= 1; }
+      pcg_stash_pose<kPcgPoseRow>(stash, at, k, pose, partial_pose, sc.slots, tile);
     }
   }
   }
-  if (stashed) pcg_flush_rows(stash, buf, stashed, partial_pose, sc.slots, tile);
+  if (at.n) stash.flush(at, partial_pose, sc.slots, tile);
 
   if (P.optimize_geometry) {
 #pragma unroll
@@ -449,7 +433,7 @@ __global__ __launch_bounds__(kPcgThreads) __attribute__((amdgpu_waves_per_eu(kDe
   uint32_t slot;
   if (!slot_of_block(sc, blockIdx.x, &slot)) return;
   const int tile = (int)slot;
-  __shared__ PcgRowStash stash;
+  __shared__ RowStash<kPcgPoseRow, kPcgGroup, 4> stash;
   __shared__ float redg[4][32];
 
   f3 gp[R], gn[R];
@@ -491,8 +475,7 @@ __global__ __launch_bounds__(kPcgThreads) __attribute__((amdgpu_waves_per_eu(kDe
   if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
   else BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
   BSLAM_HOIST_UNPROJECTION_CENTRE(c);
-  int stashed = 0;   // keyframes in the current stash (uniform)
-  int buf = 0;
+  RowStashCursor at;
   for (int k0 = 0; k0 < kf_count; k0 += 64) {
   unsigned long long todo = keyframes_to_visit(c, kfs, k0, kf_count, sc, slot, R, true);
   if (P.optimize_poses && sc.bounds != nullptr) pcg_zero_rows(todo, k0, kf_count, partial_pose, sc.slots, tile);
@@ -623,12 +606,11 @@ __global__ __launch_bounds__(kPcgThreads) __attribute__((amdgpu_waves_per_eu(kDe
     }
 
     if (opt_pose) {   // uniform
-      pcg_stash_wave_sums<6>(stash, buf, stashed, k, pose);
-      if (++stashed == kPcgGroup) { pcg_flush_rows(stash, buf, stashed, partial_pose, sc.slots, tile); stashed = 0; buf ^= 1; }
+      pcg_stash_pose<6>(stash, at, k, pose, partial_pose, sc.slots, tile);
     }
   }
   }
-  if (stashed) pcg_flush_rows(stash, buf, stashed, partial_pose, sc.slots, tile);
+  if (at.n) stash.flush(at, partial_pose, sc.slots, tile);
 
   if (P.optimize_geometry) {
 #pragma unroll

@@ -53,6 +53,13 @@ inline int pose_surfels_per_thread(bool use_desc, uint32_t surfels_size) {
 constexpr int kRow = 32;                       // floats per partial row: 21 H, 6 b, cost, count bits, pad
 constexpr int kRowCost = 27;
 constexpr int kRowCount = 28;
+// A summed row's residual count travels as two exactly representable floats, its low and high 16 bits (columns kRowCount and
+// kRowCount + 1), so that the row can go through a float all-reduce across GPUs unchanged in meaning.
+__host__ __device__ __forceinline__ void write_row_count(float* row, uint32_t n) {
+  row[kRowCount] = (float)(n & 0xffffu);
+  row[kRowCount + 1] = (float)(n >> 16);
+}
+__host__ __device__ __forceinline__ uint32_t read_row_count(const float* row) { return (uint32_t)row[kRowCount] + ((uint32_t)row[kRowCount + 1] << 16); }
 
 struct SurfelRows {
   const float* x; const float* y; const float* z;
@@ -107,12 +114,10 @@ __device__ __forceinline__ void accumulate_h_b(float raw, float w, const float* 
 // columns per round: 8 for the geometry-only kernels; the photometric ones, whose 28 KB of per-surfel constants sit in LDS, take 4
 // so that the tiles (4 KB) leave FIVE workgroups per CU
 constexpr int kRedColsGeo = 8, kRedColsDesc = BSLAM_POSE_REDUCE_COLS_DESC;
-// One partial row per (work slot, keyframe).  Geometry-only kernels: the four waves' rows meet in an LDS stash, one barrier per
-// kPoseStashGroupGeo visited keyframes (two stashes alternate, so a wave that runs ahead never overwrites rows that are still
-// being added; it cannot get two groups ahead: the barrier).  Photometric kernels: one wave forms the whole row
-// (pose_accumulate_desc).  A quarter of the row traffic of one row per wave: the row sums of a batched Gauss-Newton iteration
-// at K = 300 go from 428 to about 110 us.
-constexpr int kPoseRowsPerSlot = 1;
+// One partial row per (work slot, keyframe).  Geometry-only kernels: the four waves' rows meet in an LDS stash (RowStash), one
+// barrier per kPoseStashGroupGeo visited keyframes.  Photometric kernels: one wave forms the whole row (pose_accumulate_desc).
+// A quarter of the row traffic of one row per wave: the row sums of a batched Gauss-Newton iteration at K = 300 go from 428 to
+// about 110 us.
 typedef unsigned long long VisWord;   // visit word of a (chunk, work slot): one bit per keyframe of the chunk (<= 64)
 constexpr int kPoseStashGroupGeo = 4;
 // Photometric kernels: unroll factor of a lane's loop over the kPoseR x 4 surfels of a keyframe
@@ -285,13 +290,8 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
   // iteration with a handful of stragglers runs one chunk's worth of workgroups instead of every chunk's, each of which would only
   // start, find its keyframes converged and leave.  nullptr: the chunks cut the table itself.
   const int kf_places = kf_list ? kf_list[0] : kf_count;
-  // 1-D grid of 8 * slots_per_xcd * chunks blocks: block b -> XCD lane x = b % 8; within an XCD the
-  // blocks run chunk-major over that XCD's range of surfel slots.
-  const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-  const uint32_t chunk = j / sc.slots_per_xcd, local = j - chunk * sc.slots_per_xcd;
-  uint32_t slot;
-  if (!slot_of_block(sc, (local << 3) | xcd, &slot)) return;
-  const int tile = (int)slot;
+  uint32_t chunk, slot;
+  if (!chunk_and_slot_of_block(sc, &chunk, &slot)) return;
   const int kf_begin = (int)chunk * kfs_per_block;
   if (kf_begin >= kf_places) return;   // the host sized the grid by an older (larger) count of unconverged keyframes
   const int kf_end = min(kf_places, kf_begin + kfs_per_block);
@@ -306,25 +306,13 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
   unsigned long long todo = pose_chunk_todo(c, kfs, kf_begin, kf_end, sc, slot, kPoseR, chunk, states, vis, kf_list, &todo_shared);
   if (todo == 0) return;   // leaves before touching the surfels
 
-  // surfels of this thread: tile * kPoseTile + r * kPoseThreads + threadIdx.x (coalesced per r)
+  // surfels of this thread: granule r of the slot, column threadIdx.x (coalesced per r)
   f3 gp[kPoseR], gn[kPoseR];
   bool valid[kPoseR];
   constexpr int kRedCols = kRedColsGeo;
-  constexpr int kPoseStashGroup = kPoseStashGroupGeo;
-  __shared__ float row_stash[2][kPoseStashGroup][kPoseThreads / 64][kRow];
-  __shared__ int stash_kf[2][kPoseStashGroup];
-  int stashed = 0, stash_buf = 0;   // uniform
-  // adds up the four waves' rows of the `n` stashed keyframes -- ((w0 + w1) + w2) + w3 -- and stores one row per keyframe
-  auto flush_rows = [&](int n) {
-    __syncthreads();
-    const int j = threadIdx.x / kRow, col = threadIdx.x % kRow;
-    if (j < n) {
-      const float (*w)[kRow] = row_stash[stash_buf][j];
-      partials[((size_t)stash_kf[stash_buf][j] * rows_per_kf + (size_t)tile) * kRow + col] = ((w[0][col] + w[1][col]) + w[2][col]) + w[3][col];
-    }
-  };
-  static_assert(kPoseStashGroup * kRow <= kPoseThreads && kPoseThreads / 64 == 4, "one thread per stashed column; four waves");
-  __shared__ __attribute__((aligned(16))) float red_tile[kPoseThreads / 64][kRedCols * 64];   // wave-private tiles of the row reduction
+  static_assert(kPoseThreads == 256, "four waves");
+  __shared__ RowStash<kRow, kPoseStashGroupGeo, kRedCols> stash;
+  RowStashCursor at;
 #pragma unroll
   for (int r = 0; r < kPoseR; ++r) {
     const uint32_t i = surfel_of_slot(sc, slot, r, kPoseR);
@@ -386,13 +374,12 @@ __global__ __launch_bounds__(kPoseThreads) BSLAM_POSE_WAVES_ATTR void pose_accum
     int my_col;    // the column this lane ends up with, and whether it is the lane that stores it
     bool writer;
     wave_column_sums_owner<kLive, kRedCols>(&my_col, &writer);
-    if (any) total = wave_column_sums_lds<kLive, kRedCols>(acc, red_tile[wave]);
+    if (any) total = wave_column_sums_lds<kLive, kRedCols>(acc, stash.tile[wave]);
     if (my_col == kRowCount) total = (float)count;   // <= 64 * kPoseR: exact
-    if (writer) row_stash[stash_buf][stashed][wave][my_col] = total;
-    if (threadIdx.x == 0) stash_kf[stash_buf][stashed] = k;
-    if (++stashed == kPoseStashGroup) { flush_rows(stashed); stashed = 0; stash_buf ^= 1; }
+    if (writer) stash.put(at, my_col, total);
+    stash.next(at, k, partials, rows_per_kf, slot);
   }
-  if (stashed) flush_rows(stashed);
+  if (at.n) stash.flush(at, partials, rows_per_kf, slot);
 }
 
 // bslam_debug_wave_column_sums: wave_column_sums_lds on given values -- one wave, lane l holds in[l][0 .. 32), out[c] = the total
@@ -410,15 +397,13 @@ __global__ __launch_bounds__(64) void wave_column_sums_probe_kernel(const float*
   if (writer) out[col] = total;
 }
 
-// Sums the partial rows [k][row][32] of one keyframe in a fixed order, in two stages so that the
-// sum is spread over K x kReduceParts workgroups.  Stage A: block (k, part) sums its contiguous
-// range of rows (thread t owns column t % 32 and row residue t / 32); stage B adds the parts.
+// Sums the partial rows [row][32] of one image pair (odometry_abi.inc) in a fixed order, in two stages so that the sum is
+// spread over kReduceParts workgroups.  Stage A: block `part` sums its contiguous range of rows (thread t owns column t % 32
+// and row residue t / 32); stage B adds the parts.
 constexpr int kReduceParts = 8;
 
-__global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restrict__ partials, int rows_per_kf, int kf_count,
-                                                           float* __restrict__ parts, const PoseState* __restrict__ states) {
+__global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restrict__ partials, int rows_per_kf, float* __restrict__ parts) {
   const int k = blockIdx.x, part = blockIdx.y;
-  if (states != nullptr && states[k].converged) return;
   const int col = threadIdx.x & 31;
   const int sub = threadIdx.x >> 5;   // 0..7
   const int per_part = (rows_per_kf + kReduceParts - 1) / kReduceParts;
@@ -436,20 +421,16 @@ __global__ __launch_bounds__(256) void pose_reduce_kernel(const float* __restric
   }
 }
 
-// Stage B: coeffs[k][col] = sum over parts; the residual count (per-row counts are small exact
-// floats, their sum is formed in integers) leaves as two exactly representable floats (low / high
-// 16 bits) so that the row can go through a float all-reduce across GPUs unchanged in meaning.
-__global__ __launch_bounds__(64) void pose_reduce_final_kernel(const float* __restrict__ parts, int kf_count, float* __restrict__ coeffs,
-                                                              const PoseState* __restrict__ states) {
+// Stage B: coeffs[col] = sum over parts; the residual count (per-row counts are small exact floats, their sum is formed in
+// integers) leaves in the two-float format of write_row_count.
+__global__ __launch_bounds__(64) void pose_reduce_final_kernel(const float* __restrict__ parts, float* __restrict__ coeffs) {
   const int k = blockIdx.x;
-  if (states != nullptr && states[k].converged) return;
   const int col = threadIdx.x;
   if (col >= kRow) return;
   if (col == kRowCount) {
     uint32_t total = 0;
     for (int p = 0; p < kReduceParts; ++p) total += (uint32_t)parts[((size_t)k * kReduceParts + p) * kRow + col];
-    coeffs[(size_t)k * kRow + kRowCount] = (float)(total & 0xffffu);
-    coeffs[(size_t)k * kRow + kRowCount + 1] = (float)(total >> 16);
+    write_row_count(coeffs + (size_t)k * kRow, total);
   } else if (col != kRowCount + 1) {
     float total = 0.f;
     for (int p = 0; p < kReduceParts; ++p) total += parts[((size_t)k * kReduceParts + p) * kRow + col];
@@ -458,7 +439,7 @@ __global__ __launch_bounds__(64) void pose_reduce_final_kernel(const float* __re
 }
 
 // Row sums of one keyframe by a 1024-thread block.  Only the rows of work slots that visited the keyframe exist (vis: one word
-// per slot, bit = the keyframe's place in its chunk; a slot owns kPoseThreads / 64 consecutive rows).  The block first turns
+// per slot, bit = the keyframe's place in its chunk; a slot owns one row).  The block first turns
 // the keyframe's bit of every slot's word into a bitmap in LDS (one bit per slot); whole groups of 64 slots (256 rows) that
 // did not visit are then skipped with one uniform test -- in Morton order the visiting slots of a keyframe form a few runs.
 // Thread (sub, col) adds column `col` of the rows sub, sub + 32, sub + 64, ...: row r always goes to thread r % 32 and to its
@@ -466,9 +447,8 @@ __global__ __launch_bounds__(64) void pose_reduce_final_kernel(const float* __re
 // same bits with and without culling.  Eight independent partial sums keep eight loads in flight; a row that is skipped
 // loads a zero from a fixed address instead of branching around the load.
 __device__ const float kZeroFloat = 0.f;
-constexpr int kRowsPerSlot = kPoseRowsPerSlot;
-constexpr int kSlotsPerPass = 256 / kRowsPerSlot;        // a pass of the 32 x 8 partial sums covers 256 rows
-constexpr int kWordsPerPass = (kSlotsPerPass + 63) / 64;   // 1 (four rows per slot) or 4 (one)
+constexpr int kSlotsPerPass = 256;   // a pass of the 32 x 8 partial sums covers 256 rows: 256 slots
+constexpr int kWordsPerPass = 4;     // visit-map words of a pass
 __host__ __device__ __forceinline__ size_t visit_map_bytes(int slots) {
   return (size_t)(((slots + kSlotsPerPass - 1) / kSlotsPerPass) * kWordsPerPass) * sizeof(unsigned long long);
 }
@@ -502,7 +482,7 @@ __device__ __forceinline__ float column_share_of_rows(const float* __restrict__ 
     for (int u = 0; u < 8; ++u) {
       const int in_pass = sub + 32 * u;
       const int r = pass * 256 + in_pass;
-      const int sl = in_pass / kRowsPerSlot;
+      const int sl = in_pass;
       const bool take = r < rows && ((w[sl >> 6] >> (sl & 63)) & 1ull);
       const float* p = take ? base + (size_t)r * kRow : zero;
       v[u] += *p;
@@ -511,10 +491,25 @@ __device__ __forceinline__ float column_share_of_rows(const float* __restrict__ 
   return ((v[0] + v[1]) + (v[2] + v[3])) + ((v[4] + v[5]) + (v[6] + v[7]));
 }
 
+// Keyframe k's visited rows (one per work slot) summed by a 1024-thread block: thread (sub, col) = (t / 32, t % 32) leaves its
+// share of column col in sm[sub][col] (the count column: <= 256 per row, exact in fp32 up to 65k rows); ends with a barrier.
+// vis, kfs_per_block, kf_pos: as the accumulation wrote them; stats: the cull statistics, or nullptr.
+__device__ __forceinline__ void pose_sum_rows(const float* __restrict__ partials, int rows_per_kf, int k, const VisWord* __restrict__ vis, int kfs_per_block,
+                                              unsigned long long* __restrict__ stats, const int* __restrict__ kf_pos, float (*sm)[kRow]) {
+  extern __shared__ unsigned long long vmap[];   // visit_map_bytes(slots)
+  const int col = threadIdx.x & 31, sub = threadIdx.x >> 5;
+  const int slots = rows_per_kf;
+  const int place = kf_pos ? kf_pos[k] : k;   // the keyframe's place in the list the accumulation walked (its chunk and bit)
+  const uint32_t visiting = build_visit_map(vis + (size_t)(place / kfs_per_block) * slots, (uint32_t)(place % kfs_per_block), slots, vmap);
+  if (stats != nullptr && threadIdx.x == 0) { atomicAdd(&stats[0], (unsigned long long)slots); atomicAdd(&stats[1], (unsigned long long)visiting); }
+  sm[sub][col] = column_share_of_rows(partials + (size_t)k * rows_per_kf * kRow + col, sub, rows_per_kf, vmap);
+  __syncthreads();
+}
+
 // Both stages in one launch for the batched loop with an all-reduce hook: block k (1024 threads) sums keyframe k's
 // rows coalesced in the same fixed order as pose_reduce_solve_kernel and writes the coefficient row that goes through
-// the exchange (count as two exact 16-bit halves, as above).  Rows of converged keyframes are written as zeros, so
-// that repeated in-place all-reduces never grow stale values.
+// the exchange (count: write_row_count).  Rows of converged keyframes are written as zeros, so that repeated in-place
+// all-reduces never grow stale values.
 __global__ __launch_bounds__(1024) void pose_reduce_rows_kernel(const float* __restrict__ partials, int rows_per_kf, int kf_count,
                                                                float* __restrict__ coeffs, const PoseState* __restrict__ states,
                                                                const VisWord* __restrict__ vis, int kfs_per_block, unsigned long long* __restrict__ stats,
@@ -525,20 +520,13 @@ __global__ __launch_bounds__(1024) void pose_reduce_rows_kernel(const float* __r
     return;
   }
   __shared__ float sm[32][kRow];
-  extern __shared__ unsigned long long vmap[];   // visit_map_bytes(slots)
-  const int col = threadIdx.x & 31, sub = threadIdx.x >> 5;
-  const int slots = rows_per_kf / kRowsPerSlot;
-  const int place = kf_pos ? kf_pos[k] : k;   // the keyframe's place in the list the accumulation walked (its chunk and bit)
-  const uint32_t visiting = build_visit_map(vis + (size_t)(place / kfs_per_block) * slots, (uint32_t)(place % kfs_per_block), slots, vmap);
-  if (stats != nullptr && threadIdx.x == 0) { atomicAdd(&stats[0], (unsigned long long)slots); atomicAdd(&stats[1], (unsigned long long)visiting); }
-  sm[sub][col] = column_share_of_rows(partials + (size_t)k * rows_per_kf * kRow + col, sub, rows_per_kf, vmap);   // the count column: <= 256 per row, exact in fp32 up to 65k rows
-  __syncthreads();
+  pose_sum_rows(partials, rows_per_kf, k, vis, kfs_per_block, stats, kf_pos, sm);
   if (threadIdx.x >= kRow) return;
+  const int col = threadIdx.x;
   if (col == kRowCount) {
     uint32_t total = 0;
     for (int i = 0; i < 32; ++i) total += (uint32_t)sm[i][col];
-    coeffs[(size_t)k * kRow + kRowCount] = (float)(total & 0xffffu);
-    coeffs[(size_t)k * kRow + kRowCount + 1] = (float)(total >> 16);
+    write_row_count(coeffs + (size_t)k * kRow, total);
   } else if (col != kRowCount + 1) {
     float total = 0.f;
     for (int i = 0; i < 32; ++i) total += sm[i][col];
@@ -764,17 +752,12 @@ __global__ __launch_bounds__(kActiveListThreads) void pose_active_list_kernel(in
   if (threadIdx.x == 0) out[0] = base;
 }
 
-// One Gauss-Newton update per keyframe (BS/direct_ba_alternating.cc:206-233).
-__global__ void pose_solve_kernel(const float* __restrict__ coeffs, int kf_count, PoseState* __restrict__ states,
-                                  KfDev* __restrict__ kfs, int* __restrict__ active_count, int* __restrict__ next_active_count) {
-  const int k = blockIdx.x * blockDim.x + threadIdx.x;
-  if (k == 0 && next_active_count != nullptr) *next_active_count = 0;   // last read four iterations ago
-  if (k >= kf_count) return;
-  PoseState st = states[k];
-  if (st.converged) return;
-  float H[21], b[6], x[6];
-  for (int i = 0; i < 21; ++i) H[i] = coeffs[(size_t)k * kRow + i];
-  for (int i = 0; i < 6; ++i) b[i] = coeffs[(size_t)k * kRow + 21 + i];
+// One Gauss-Newton update of keyframe k from H (upper triangle, 21) and b (6) (BS/direct_ba_alternating.cc:206-233): the
+// solve, T <- T * exp(-x), the convergence test, the state and the keyframe's frame_T_global.  st: the keyframe's state as the
+// caller has loaded it.
+__device__ __forceinline__ void pose_update(int k, PoseState st, const float* H, const float* b, PoseState* __restrict__ states,
+                                            KfDev* __restrict__ kfs, int* __restrict__ active_count) {
+  float x[6];
   solve_ldlt6(H, b, x);
   float neg[6];
   for (int i = 0; i < 6; ++i) neg[i] = -1.f * x[i];
@@ -796,11 +779,23 @@ __global__ void pose_solve_kernel(const float* __restrict__ coeffs, int kf_count
   if (!st.converged) atomicAdd(active_count, 1);
 }
 
-// pose_reduce_kernel + pose_reduce_final_kernel + pose_solve_kernel in one launch (single-GPU path: no exchange in
-// between).  Block k sums the per-wave rows [rows][32] of keyframe k -- thread (sub, col) owns the rows r = sub mod 32 of
-// column col and keeps four independent partial sums for memory-level parallelism; the 32 per-thread sums of a column
-// are then added in a fixed order (deterministic) -- and thread 0 does the fp64 pivoted LDL^T, the SE3 update and the
-// convergence test (LDL^T unrolled in registers).
+// One Gauss-Newton update per keyframe from its summed coefficient row.
+__global__ void pose_solve_kernel(const float* __restrict__ coeffs, int kf_count, PoseState* __restrict__ states,
+                                  KfDev* __restrict__ kfs, int* __restrict__ active_count, int* __restrict__ next_active_count) {
+  const int k = blockIdx.x * blockDim.x + threadIdx.x;
+  if (k == 0 && next_active_count != nullptr) *next_active_count = 0;   // last read four iterations ago
+  if (k >= kf_count) return;
+  const PoseState st = states[k];
+  if (st.converged) return;
+  float H[21], b[6];
+  for (int i = 0; i < 21; ++i) H[i] = coeffs[(size_t)k * kRow + i];
+  for (int i = 0; i < 6; ++i) b[i] = coeffs[(size_t)k * kRow + 21 + i];
+  pose_update(k, st, H, b, states, kfs, active_count);
+}
+
+// pose_reduce_rows_kernel + pose_solve_kernel in one launch (single-GPU path: no exchange in between).  Block k sums the
+// rows of keyframe k (pose_sum_rows), the 32 per-thread sums of a column are then added in a fixed order (deterministic),
+// and thread 0 does the fp64 pivoted LDL^T, the SE3 update and the convergence test (pose_update).
 constexpr int kReduceSolveThreads = 1024;
 __global__ __launch_bounds__(kReduceSolveThreads) void pose_reduce_solve_kernel(const float* __restrict__ partials, int rows_per_kf, int kf_count,
                                                                                PoseState* __restrict__ states, KfDev* __restrict__ kfs,
@@ -812,14 +807,7 @@ __global__ __launch_bounds__(kReduceSolveThreads) void pose_reduce_solve_kernel(
   if (states[k].converged) return;   // uniform
   __shared__ float sm[32][kRow];
   __shared__ float row[kRow];
-  extern __shared__ unsigned long long vmap[];   // visit_map_bytes(slots)
-  const int col = threadIdx.x & 31, sub = threadIdx.x >> 5;
-  const int slots = rows_per_kf / kRowsPerSlot;
-  const int place = kf_pos ? kf_pos[k] : k;   // the keyframe's place in the list the accumulation walked (its chunk and bit)
-  const uint32_t visiting = build_visit_map(vis + (size_t)(place / kfs_per_block) * slots, (uint32_t)(place % kfs_per_block), slots, vmap);
-  if (stats != nullptr && threadIdx.x == 0) { atomicAdd(&stats[0], (unsigned long long)slots); atomicAdd(&stats[1], (unsigned long long)visiting); }
-  sm[sub][col] = column_share_of_rows(partials + (size_t)k * rows_per_kf * kRow + col, sub, rows_per_kf, vmap);
-  __syncthreads();
+  pose_sum_rows(partials, rows_per_kf, k, vis, kfs_per_block, stats, kf_pos, sm);
   if (threadIdx.x < 27) {
     float total = 0.f;
     for (int i = 0; i < 32; ++i) total += sm[i][threadIdx.x];
@@ -827,28 +815,10 @@ __global__ __launch_bounds__(kReduceSolveThreads) void pose_reduce_solve_kernel(
   }
   __syncthreads();
   if (threadIdx.x != 0) return;
-  PoseState st = states[k];
-  float H[21], b[6], x[6];
+  float H[21], b[6];
   for (int i = 0; i < 21; ++i) H[i] = row[i];
   for (int i = 0; i < 6; ++i) b[i] = row[21 + i];
-  solve_ldlt6(H, b, x);
-  float neg[6];
-  for (int i = 0; i < 6; ++i) neg[i] = -1.f * x[i];
-  Quat dq; f3 dt;
-  se3_exp(neg, &dq, &dt);
-  Quat q{st.q[0], st.q[1], st.q[2], st.q[3]};
-  f3 t = mk3(st.t[0], st.t[1], st.t[2]);
-  se3_mul_inplace(&q, &t, dq, dt);
-  const float sc = 1e-06f / 1e-07f;   // IsScale1PoseEstimationConverged BS/convergence_analysis.h:45-52
-  float nrm = 0.f;
-  for (int i = 0; i < 6; ++i) { const float v = (i < 3) ? x[i] : x[i] * sc; nrm += v * v; }
-  st.q[0] = q.x; st.q[1] = q.y; st.q[2] = q.z; st.q[3] = q.w;
-  st.t[0] = t.x; st.t[1] = t.y; st.t[2] = t.z;
-  st.iterations += 1;
-  st.converged = (nrm < 1e-06f) ? 1 : 0;
-  states[k] = st;
-  se3_inverse_matrix(q, t, kfs[k].frame_T_global.m);
-  if (!st.converged) atomicAdd(active_count, 1);
+  pose_update(k, states[k], H, b, states, kfs, active_count);
 }
 
 }  // namespace bslam

@@ -44,6 +44,7 @@ class BadSlam:
         self.direct_ba.stream = C.c_void_p(None)
         self.direct_ba.close = lambda: None             # instance attribute: shadows DirectBA.close for this view only
         self._ba_ptr = L.bsh_slam_direct_ba(self._slam)
+        self._num_scales = num_scales
 
     def ba(self):
         """The DirectBA of this BadSlam (valid while the BadSlam object lives)."""
@@ -88,6 +89,29 @@ class BadSlam:
         out = np.zeros((max(1, n), 7), np.float32)
         self._check(self.L.bsh_slam_get_frame_poses(self._slam, dba._f(out), n))
         return out[:n]
+
+    def CloseLoop(self, matched_id, old_T_cur_initial):
+        """Loop closure of the newest keyframe against keyframe matched_id (DirectBA.CloseLoop's dict); when the loop is
+        closed, the non-keyframe poses follow their keyframes."""
+        L = dba._loop_lib()
+        ints, floats, chi2 = dba._loop_buffers(self._num_scales)
+        self._check(L.bsh_slam_close_loop(self._slam, matched_id, dba._f(dba.pose7(old_T_cur_initial)), dba._i(ints), dba._f(floats), dba._d(chi2)))
+        return dba._loop_result(ints, floats, chi2, self._num_scales)
+
+    def set_loop_candidate_search(self, enable, min_keyframe_gap=10):
+        """Opt-in geometric loop candidates (off by default): on every new keyframe, the nearest older keyframe (id <= new id -
+        min_keyframe_gap) whose frustum intersects the new one is tried with CloseLoop.  Not place recognition: it closes
+        only drift the pairwise tracker can still converge over."""
+        self._check(dba._loop_lib().bsh_slam_set_loop_candidate_search(self._slam, int(enable), int(min_keyframe_gap)))
+
+    def loop_closure_log(self):
+        """[{keyframe, candidate, status, mean_pixel_distance}] of the candidate search, oldest first."""
+        L = dba._loop_lib()
+        n = L.bsh_slam_loop_log_size(self._slam)
+        e, d = np.zeros(3 * max(1, n), np.int32), np.zeros(max(1, n), np.float32)
+        self._check(L.bsh_slam_loop_log(self._slam, dba._i(e), dba._f(d), n))
+        return [{"keyframe": int(e[3 * i]), "candidate": int(e[3 * i + 1]), "status": dba.LOOP_STATUS_NAMES[int(e[3 * i + 2])],
+                 "mean_pixel_distance": float(d[i])} for i in range(n)]
 
     def state(self):
         s = (C.c_int * 5)()

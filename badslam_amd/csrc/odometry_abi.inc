@@ -227,6 +227,71 @@ int bslam_compute_cost_and_residual_count_from_images_gradmag(
   return BSLAM_OK;
 }
 
+int bslam_accumulate_pose_coeffs_from_images_batched(
+    bslam_context* ctx, void* stream_, int use_depth_residuals, int use_descriptor_residuals, const bslam_camera4f* color_camera,
+    const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor, int pair_count, const bslam_buffer2d* tracked_depth,
+    const bslam_buffer2d* tracked_normals, const bslam_buffer2d* tracked_color, const bslam_mat3x4* estimates_frame_T_surfel_frame,
+    const bslam_buffer2d* base_depth, const bslam_buffer2d* base_normals, const bslam_buffer2d* base_color, uint32_t* visible_counts, float* H, float* b) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx || !color_camera || !depth_camera || !estimates_frame_T_surfel_frame || !tracked_depth || !tracked_normals || !tracked_color)
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  if (!H || !b) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
+  if (pair_count < 1 || pair_count > kMaxPairBatch) return fail(BSLAM_ERR_INVALID_ARGUMENT, "pair_count %d outside [1, %d]", pair_count, kMaxPairBatch);
+  if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
+  PairBatch batch;
+  std::memset(&batch, 0, sizeof(batch));
+  int rc;
+  for (int p = 0; p < pair_count; ++p) {
+    Img frame_color_img;
+    if ((rc = pair_images(&tracked_depth[p], &tracked_normals[p], &tracked_color[p], base_depth, base_normals, base_color, depth_camera, color_camera,
+                          &batch.im[p], &frame_color_img)))
+      return rc;
+    batch.im[p].frame_color = frame_color_img;
+    std::memcpy(batch.T[p].m, estimates_frame_T_surfel_frame[p].m, sizeof(float) * 12);
+  }
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  bslam_depth_params dp;
+  std::memset(&dp, 0, sizeof(dp));
+  dp.sparse_surfel_cell_size = 1;
+  dp.baseline_fx = baseline_fx;
+  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, &dp);
+  // every pair's tracked colour as luma quads, one launch (pair_images checked that all have the colour camera's size)
+  const int cw = color_camera->width, ch = color_camera->height;
+  const size_t quad_count = (size_t)(cw + 1) * (ch + 1);
+  if ((rc = ctx->quads_aux.reserve((size_t)pair_count * quad_count * sizeof(uint32_t)))) return rc;
+  for (int p = 0; p < pair_count; ++p) batch.im[p].frame_quads = (const uint32_t*)ctx->quads_aux.ptr + (size_t)p * quad_count;
+  hipLaunchKernelGGL(build_quads_u8_batched_kernel, dim3((unsigned)((cw + 1 + 255) / 256), (unsigned)(ch + 1), (unsigned)pair_count), dim3(256), 0, stream,
+                     batch, (uint32_t*)ctx->quads_aux.ptr, quad_count);
+  BSLAM_HIP_TRY(hipGetLastError());
+  const int pixels = depth_camera->width * depth_camera->height;
+  const int blocks = (pixels + 255) / 256;
+  const int rows = blocks * 4;
+  const size_t partial_floats = (size_t)pair_count * rows * kRow;
+  if ((rc = ctx->partials.reserve((partial_floats + (size_t)pair_count * kReduceParts * kRow) * sizeof(float)))) return rc;
+  if ((rc = ctx->coeffs.reserve((size_t)pair_count * kRow * sizeof(float)))) return rc;
+  float* partials = (float*)ctx->partials.ptr;
+  const dim3 grid((unsigned)blocks, (unsigned)pair_count), block(256);
+  if (use_depth_residuals && use_descriptor_residuals) hipLaunchKernelGGL((pair_accumulate_batched_kernel<true, true>), grid, block, 0, stream, c, threshold_factor, batch, partials);
+  else if (use_depth_residuals) hipLaunchKernelGGL((pair_accumulate_batched_kernel<true, false>), grid, block, 0, stream, c, threshold_factor, batch, partials);
+  else hipLaunchKernelGGL((pair_accumulate_batched_kernel<false, true>), grid, block, 0, stream, c, threshold_factor, batch, partials);
+  BSLAM_HIP_TRY(hipGetLastError());
+  float* parts = partials + partial_floats;
+  hipLaunchKernelGGL(pose_reduce_kernel, dim3((unsigned)pair_count, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, parts);
+  BSLAM_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3((unsigned)pair_count), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
+  BSLAM_HIP_TRY(hipGetLastError());
+  if ((rc = ctx->staging2.reserve((size_t)pair_count * kRow * sizeof(float)))) return rc;
+  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, (size_t)pair_count * kRow * sizeof(float), hipMemcpyDeviceToHost, stream));
+  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+  const float* rows_out = (const float*)ctx->staging2.ptr;
+  for (int p = 0; p < pair_count; ++p) {
+    std::memcpy(H + 21 * p, rows_out + (size_t)p * kRow, 21 * sizeof(float));
+    std::memcpy(b + 6 * p, rows_out + (size_t)p * kRow + 21, 6 * sizeof(float));
+    if (visible_counts) visible_counts[p] = read_row_count(rows_out + (size_t)p * kRow);
+  }
+  return BSLAM_OK;
+}
+
 int bslam_compute_sobel_gradient_magnitude(bslam_context* ctx, void* stream_, const bslam_buffer2d* color_buffer, const bslam_buffer2d* gradmag_buffer) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");

@@ -172,8 +172,9 @@ struct PairImages {
 // ComputeCostAndResidualCountFromImagesCUDAKernel_GradientXY.
 // kGradMag: ONE colour residual on gradient-magnitude images (ComputeRawColorResidualAndJacobian BS/kernel_opt_pose.cu:192-222,
 // kernels :713-937 and :1173-1338) instead of the two descriptor residuals.
-template <bool kDepth, bool kDesc, bool kCoeffs, bool kGradMag = false>
-__global__ __launch_bounds__(256) void pair_accumulate_kernel(CamConsts c, M34 T, float threshold_factor, PairImages im, float* __restrict__ partials) {
+// The body is shared with pair_accumulate_batched_kernel: `partials` is the first row of the pair's own blocks.
+template <bool kDepth, bool kDesc, bool kCoeffs, bool kGradMag>
+__device__ __forceinline__ void pair_accumulate_body(const CamConsts& c, const M34& T, float threshold_factor, const PairImages& im, float* __restrict__ partials) {
   const int pixel = blockIdx.x * blockDim.x + threadIdx.x;
   const int w = im.surfel_depth.width, h = im.surfel_depth.height;
   float acc[kRow];
@@ -297,6 +298,38 @@ __global__ __launch_bounds__(256) void pair_accumulate_kernel(CamConsts c, M34 T
   const float total = wave_transpose_sum32(acc);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if ((lane & 1) == 0) partials[((size_t)blockIdx.x * (blockDim.x / 64) + wave) * kRow + (lane >> 1)] = total;
+}
+
+template <bool kDepth, bool kDesc, bool kCoeffs, bool kGradMag = false>
+__global__ __launch_bounds__(256) void pair_accumulate_kernel(CamConsts c, M34 T, float threshold_factor, PairImages im, float* __restrict__ partials) {
+  pair_accumulate_body<kDepth, kDesc, kCoeffs, kGradMag>(c, T, threshold_factor, im, partials);
+}
+
+// Loop verification (BS/loop_detector.cc:440-712) tracks one base frame against up to kMaxPairBatch tracked frames at
+// once: blockIdx.y = pair, each pair writes its own gridDim.x * 4 rows, which pose_reduce_kernel then sums per pair in
+// the single-pair order (so row p is bit-identical to a single-pair call).  The per-pair images travel in the kernel
+// arguments; the base images are the same in every entry.
+constexpr int kMaxPairBatch = BSLAM_MAX_PAIR_BATCH;
+struct PairBatch {
+  PairImages im[kMaxPairBatch];
+  M34 T[kMaxPairBatch];
+};
+
+__global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(PairBatch batch, uint32_t* __restrict__ quads, size_t quads_per_pair) {
+  const int p = blockIdx.z;
+  const Img img = batch.im[p].frame_color;
+  const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
+  const int w = img.width, h = img.height;
+  if (qx > w) return;
+  const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
+  const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
+  quads[(size_t)p * quads_per_pair + (size_t)qy * (size_t)(w + 1) + qx] = tl | (tr << 8) | (bl << 16) | (br << 24);
+}
+
+template <bool kDepth, bool kDesc>
+__global__ __launch_bounds__(256) void pair_accumulate_batched_kernel(CamConsts c, float threshold_factor, PairBatch batch, float* __restrict__ partials) {
+  const int p = blockIdx.y;
+  pair_accumulate_body<kDepth, kDesc, true, false>(c, batch.T[p], threshold_factor, batch.im[p], partials + (size_t)p * gridDim.x * (blockDim.x / 64) * kRow);
 }
 
 }  // namespace bslam

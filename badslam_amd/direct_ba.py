@@ -92,6 +92,93 @@ def se3f_from7(p):
     return T
 
 
+# ---- loop closure (badslam_amd/host/pose_graph.hpp, loop_closure.hpp) ------------------------------------------
+LOOP_CLOSED, LOOP_IGNORED_SMALL, LOOP_REJECTED_NO_NEIGHBOURS, LOOP_REJECTED_INCONSISTENT = 0, 1, 2, 3
+LOOP_STATUS_NAMES = {0: "closed", 1: "ignored_small", 2: "rejected_no_neighbours", 3: "rejected_inconsistent"}
+LOOP_POSE_GRAPH_ITERATIONS = 20
+
+
+def _loop_lib():
+    L = host_lib()
+    if getattr(L, "_loop_ready", False):
+        return L
+    dp, ip, fp = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float)
+    L.bsh_optimize_pose_graph.argtypes = [C.c_int, dp, C.c_int, ip, dp, C.c_int, C.c_int, dp, dp, C.POINTER(C.c_longlong)]
+    L.bsh_optimize_keyframe_pose_graph.argtypes = [C.c_int, ip, dp, C.c_int, ip, dp, C.c_int, dp, dp, C.POINTER(C.c_longlong)]
+    L.bsh_average_pose.argtypes = [C.c_int, dp, dp]
+    L.bsh_track_keyframes_batched.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, ip, fp, C.c_int, fp, ip]
+    L.bsh_close_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, fp, C.c_int, ip, fp, dp]
+    L.bsh_slam_close_loop.argtypes = [C.c_void_p, C.c_int, fp, ip, fp, dp]
+    L.bsh_slam_set_loop_candidate_search.argtypes = [C.c_void_p, C.c_int, C.c_int]
+    L.bsh_slam_loop_log_size.argtypes = [C.c_void_p]
+    L.bsh_slam_loop_log.argtypes = [C.c_void_p, ip, fp, C.c_int]
+    L._loop_ready = True
+    return L
+
+
+def _d(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _i(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def optimize_pose_graph(poses7, edges, measurements7, fixed_id, iterations=LOOP_POSE_GRAPH_ITERATIONS):
+    """Keyframe pose graph (BS/pose_graph_optimizer.cc semantics, g2o EdgeSE3 / VertexSE3, plain Gauss-Newton) on the host,
+    in double.  poses7: (V, 7) [qx qy qz qw tx ty tz] global_T_frame; edges: (E, 2) vertex pairs (from, to);
+    measurements7: (E, 7) from_T_to.  Vertex fixed_id is held.  Returns (poses7 (V, 7), chi2 after each iteration,
+    info dict with initial_chi2 and factor_blocks)."""
+    L = _loop_lib()
+    poses = np.array(poses7, np.float64).reshape(-1, 7).copy()
+    e = np.ascontiguousarray(np.asarray(edges, np.int32).reshape(-1, 2))
+    m = np.ascontiguousarray(np.asarray(measurements7, np.float64).reshape(-1, 7))
+    if len(e) != len(m):
+        raise ValueError("one measurement per edge")
+    chi2, init, blocks = np.zeros(max(1, iterations)), C.c_double(), C.c_longlong()
+    if L.bsh_optimize_pose_graph(len(poses), _d(poses), len(e), _i(e), _d(m), int(fixed_id), int(iterations), _d(chi2), C.byref(init), C.byref(blocks)) < 0:
+        raise DirectBAError(L.bsh_last_error().decode())
+    return poses, chi2[:iterations].copy(), {"initial_chi2": init.value, "factor_blocks": blocks.value}
+
+
+def optimize_keyframe_pose_graph(poses7, exists, loop_edges, loop_measurements7, iterations=LOOP_POSE_GRAPH_ITERATIONS):
+    """The graph loop closure builds over a keyframe list: a vertex per existing keyframe, odometry edges between
+    consecutive existing keyframes from the current poses, the given loop edges (keyframe ids); the lowest-id existing
+    keyframe is the gauge.  Returns (poses7, chi2 per iteration, info dict with gauge, initial_chi2, factor_blocks)."""
+    L = _loop_lib()
+    poses = np.array(poses7, np.float64).reshape(-1, 7).copy()
+    ex = np.ascontiguousarray(np.asarray(exists, np.int32).reshape(-1))
+    e = np.ascontiguousarray(np.asarray(loop_edges, np.int32).reshape(-1, 2))
+    m = np.ascontiguousarray(np.asarray(loop_measurements7, np.float64).reshape(-1, 7))
+    chi2, init, blocks = np.zeros(max(1, iterations)), C.c_double(), C.c_longlong()
+    gauge = L.bsh_optimize_keyframe_pose_graph(len(poses), _i(ex), _d(poses), len(e), _i(e), _d(m), int(iterations), _d(chi2), C.byref(init), C.byref(blocks))
+    if gauge < 0:
+        raise DirectBAError(L.bsh_last_error().decode())
+    return poses, chi2[:iterations].copy(), {"gauge": gauge, "initial_chi2": init.value, "factor_blocks": blocks.value}
+
+
+def average_pose(poses7):
+    """AveragePose (BS/util.cc:110-129) in double: SVD projection of the summed rotations, mean translation."""
+    L = _loop_lib()
+    p = np.ascontiguousarray(np.asarray(poses7, np.float64).reshape(-1, 7))
+    out = np.zeros(7)
+    if L.bsh_average_pose(len(p), _d(p), _d(out)) < 0:
+        raise DirectBAError(L.bsh_last_error().decode())
+    return out
+
+
+def _loop_result(ints, floats, chi2, num_scales):
+    n_chi2 = int(ints[5])
+    return {"status": LOOP_STATUS_NAMES[int(ints[0])], "status_code": int(ints[0]), "old_keyframe_ids": [int(v) for v in ints[1:4]],
+            "cur_T_old_refined": [se3f_from7(floats[7 * i:7 * i + 7]) for i in range(3)], "cur_T_old_averaged": se3f_from7(floats[21:28]),
+            "mean_pixel_distance": float(floats[28]), "pixel_count": int(ints[4]), "chi2": [float(v) for v in chi2[:n_chi2]],
+            "tracking_iterations": [[int(v) for v in ints[6 + num_scales * i:6 + num_scales * (i + 1)]] for i in range(3)]}
+
+
+def _loop_buffers(num_scales):
+    return np.zeros(6 + 3 * num_scales, np.int32), np.zeros(29, np.float32), np.zeros(LOOP_POSE_GRAPH_ITERATIONS)
+
+
 # ---- file formats (badslam_amd/host/io.hpp) -----------------------------------------------------------------
 def _io_lib():
     L = host_lib()
@@ -274,6 +361,29 @@ class DirectBA:
         self._check(self.L.bsh_track_keyframe_pair_ex(self._ba, self.stream, tracked_id, base_id, num_scales, int(test_different_initial_estimates), _f(p1),
                                                       _f(p2), _f(out), its, int(use_pyramid_level_0), int(use_gradmag)))
         return se3f_from7(out), list(its)
+
+    def TrackKeyframesBatched(self, base_id, tracked_ids, inits, num_scales=5):
+        """TrackFramesPairwiseBatched: keyframes `tracked_ids` (up to 8) against keyframe `base_id` in lockstep, as loop
+        verification runs it (use_pyramid_level_0, no gradmag, one initial estimate).  Returns ([base_T_tracked], [iterations
+        per scale]); each entry is bit-identical to TrackKeyframePair(tracked_id, base_id, init, num_scales=num_scales)."""
+        L = _loop_lib()
+        n = len(tracked_ids)
+        ids = np.asarray(tracked_ids, np.int32)
+        p = np.concatenate([pose7(T) for T in inits]).astype(np.float32)
+        out = np.zeros(7 * n, np.float32)
+        its = np.zeros(num_scales * n, np.int32)
+        self._check(L.bsh_track_keyframes_batched(self._ba, self.stream, base_id, n, _i(ids), _f(p), num_scales, _f(out), _i(its)))
+        return [se3f_from7(out[7 * i:7 * i + 7]) for i in range(n)], [list(its[num_scales * i:num_scales * (i + 1)]) for i in range(n)]
+
+    def CloseLoop(self, current_id, matched_id, old_T_cur_initial, num_scales=5):
+        """Loop closure (BS/loop_detector.cc:440-712 after RANSAC) from keyframe current_id to matched_id: verification by
+        three trackings, averaging, the BA-can-handle-it test and the pose graph.  Returns a dict: status ("closed",
+        "ignored_small", "rejected_no_neighbours", "rejected_inconsistent"), old_keyframe_ids, cur_T_old_refined (3),
+        cur_T_old_averaged, mean_pixel_distance, pixel_count, chi2, tracking_iterations."""
+        L = _loop_lib()
+        ints, floats, chi2 = _loop_buffers(num_scales)
+        self._check(L.bsh_close_loop(self._ba, self.stream, current_id, matched_id, _f(pose7(old_T_cur_initial)), num_scales, _i(ints), _f(floats), _d(chi2)))
+        return _loop_result(ints, floats, chi2, num_scales)
 
     def SaveState(self, path, frame_count):
         """The DirectBA part of SaveState (BS/io.cc:38-178) as a version-1 state file."""

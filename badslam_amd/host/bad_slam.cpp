@@ -205,6 +205,7 @@ std::shared_ptr<Keyframe> BadSlam::CreateKeyframe(int frame_index) {
     for (SE3f& pose : base_kf_tr_frame_) pose = new_base_T_old_base * pose;
     base_kf_tr_frame_.back() = SE3f();   // exactly the identity, not a product that rounds to it
   }
+  if (loop_candidate_search_) SearchLoopCandidate(frame_index, *new_keyframe);   // before the keyframe's BA iterations (:1120-1158)
   if (!config_.estimate_poses) return new_keyframe;
 
   if (keyframes_added >= 2) {   // :1074-1094
@@ -215,6 +216,53 @@ std::shared_ptr<Keyframe> BadSlam::CreateKeyframe(int frame_index) {
     CheckHip(hipStreamSynchronize(stream_), "hipStreamSynchronize");
   }
   return new_keyframe;
+}
+
+void BadSlam::CloseLoopUpTo(int frame_index, int matched_id, const SE3f& old_T_cur_initial, LoopClosureResult* result) {
+  int current_id = -1;
+  for (int i = static_cast<int>(direct_ba_->keyframes().size()) - 1; i >= 0 && current_id < 0; --i)
+    if (direct_ba_->keyframes()[i]) current_id = i;
+  if (current_id < 0) throw std::logic_error("BadSlam::CloseLoop without keyframes");
+  std::vector<SE3f> original_keyframe_T_global;
+  RememberKeyframePoses(*direct_ba_, &original_keyframe_T_global);
+  bslam_host::CloseLoop(*direct_ba_, stream_, current_id, matched_id, old_T_cur_initial, config_.num_scales, result);
+  if (result->status != kLoopClosed) return;
+  ExtrapolateAndInterpolateKeyframePoseChanges(static_cast<u32>(config_.start_frame), static_cast<u32>(frame_index), *direct_ba_,
+                                               original_keyframe_T_global, &frame_global_T_frame_);
+  if (base_kf_) base_kf_global_T_frame_ = base_kf_->global_T_frame();
+}
+
+void BadSlam::CloseLoop(int matched_id, const SE3f& old_T_cur_initial, LoopClosureResult* result) {
+  if (last_frame_index_ < 0) throw std::logic_error("BadSlam::CloseLoop before the first frame");
+  CloseLoopUpTo(last_frame_index_, matched_id, old_T_cur_initial, result);
+}
+
+void BadSlam::SetLoopCandidateSearch(bool enable, int min_keyframe_gap) {
+  if (min_keyframe_gap < 1) throw std::invalid_argument("SetLoopCandidateSearch: min_keyframe_gap must be >= 1");
+  loop_candidate_search_ = enable;
+  loop_min_keyframe_gap_ = min_keyframe_gap;
+}
+
+void BadSlam::SearchLoopCandidate(int frame_index, const Keyframe& new_keyframe) {
+  const auto& kfs = direct_ba_->keyframes();
+  const PinholeCamera4f& cam = direct_ba_->depth_camera();
+  CameraFrustum new_frustum(cam, new_keyframe.min_depth(), new_keyframe.max_depth(), new_keyframe.global_T_frame());
+  const SE3f& g = new_keyframe.global_T_frame();
+  int best = -1;
+  float best_d2 = 0.f;
+  for (int i = 0; i <= new_keyframe.id() - loop_min_keyframe_gap_ && i < static_cast<int>(kfs.size()); ++i) {
+    if (!kfs[i]) continue;
+    CameraFrustum frustum(cam, kfs[i]->min_depth(), kfs[i]->max_depth(), kfs[i]->global_T_frame());
+    if (!new_frustum.Intersects(&frustum)) continue;
+    const SE3f& o = kfs[i]->global_T_frame();
+    const float dx = o.tx - g.tx, dy = o.ty - g.ty, dz = o.tz - g.tz;
+    const float d2 = dx * dx + dy * dy + dz * dz;
+    if (best < 0 || d2 < best_d2) { best = i; best_d2 = d2; }   // strict: ties keep the lower id
+  }
+  if (best < 0) return;
+  LoopClosureResult result;
+  CloseLoopUpTo(frame_index, best, kfs[best]->frame_T_global() * g, &result);
+  loop_log_.push_back(LoopLogEntry{new_keyframe.id(), best, result.status, result.mean_pixel_distance});
 }
 
 void BadSlam::RunBundleAdjustment(u32 frame_index, bool optimize_depth_intrinsics, bool optimize_color_intrinsics, bool optimize_poses,

@@ -4,8 +4,11 @@
 // (:953-1097) and the planned bundle-adjustment iterations (:212-282, :481-536), after which the poses of the
 // non-keyframes follow their neighbouring keyframes (BS/trajectory_deformation.cc:45-146).
 //
-// Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), loop detection / pose-graph
-// optimisation (DBoW2, opengv, g2o are not in this image), median_filter_and_densify_iterations > 0,
+// Loop closure: CloseLoop (host/loop_closure.hpp) for a caller-supplied candidate, and an opt-in geometric candidate
+// search (SetLoopCandidateSearch) that closes drift within the tracker's basin; it is not place recognition.
+//
+// Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), loop detection (DBoW2 place recognition,
+// opengv RANSAC; enable_loop_detection stays off), median_filter_and_densify_iterations > 0,
 // pyramid_level_for_depth / _color > 0, keyframe merging on low memory.  Those switches must keep their "off" values.
 #pragma once
 
@@ -14,6 +17,7 @@
 
 #include "direct_ba.hpp"
 #include "io.hpp"
+#include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
 
 namespace bslam_host {
@@ -35,6 +39,23 @@ class BadSlam {
                            int min_iterations, int max_iterations, int active_keyframe_window_start, int active_keyframe_window_end,
                            bool increase_ba_iteration_count, int* iterations_done, bool* converged);
 
+  // The closure half of LoopDetector::AddImage (BS/loop_detector.cc:440-712) for the newest keyframe against keyframe
+  // matched_id; old_T_cur_initial = the newest keyframe's pose in matched_id's frame.  With status kLoopClosed, the
+  // non-keyframe poses follow their keyframes (:685-708).
+  void CloseLoop(int matched_id, const SE3f& old_T_cur_initial, LoopClosureResult* result);
+
+  // Opt-in geometric loop candidates (off by default): when a keyframe is added, before its BA iterations, the
+  // existing keyframe with id <= new id - min_keyframe_gap whose frustum intersects the new one and whose camera centre
+  // is nearest (ties: lower id) is tried with CloseLoop, initial estimate from the current poses.  Closes drift the
+  // pairwise tracker can still converge over; it does not recognise places.
+  struct LoopLogEntry {
+    int keyframe_id, candidate_id;
+    LoopClosureStatus status;
+    float mean_pixel_distance;
+  };
+  void SetLoopCandidateSearch(bool enable, int min_keyframe_gap);
+  const std::vector<LoopLogEntry>& loop_closure_log() const { return loop_log_; }
+
   DirectBA& direct_ba() { return *direct_ba_; }
   const BadSlamConfigV1& config() const { return config_; }
   // global_T_frame of every processed frame (index = frame_index - config.start_frame)
@@ -51,6 +72,8 @@ class BadSlam {
   void PredictFramePose(SE3f* estimate_1, SE3f* estimate_2) const;                          // :763-825
   void RunOdometry(int frame_index);                                                        // :827-950
   std::shared_ptr<Keyframe> CreateKeyframe(int frame_index);                                // :953-1097
+  void CloseLoopUpTo(int frame_index, int matched_id, const SE3f& old_T_cur_initial, LoopClosureResult* result);
+  void SearchLoopCandidate(int frame_index, const Keyframe& new_keyframe);
   SE3f& FramePose(int frame_index) { return frame_global_T_frame_.at(static_cast<size_t>(frame_index - config_.start_frame)); }
 
   BadSlamConfigV1 config_;
@@ -71,6 +94,9 @@ class BadSlam {
   int num_planned_ba_iterations_ = 0;
   int bundle_adjustment_counter_ = 0;
   bool pose_estimated_ = false, keyframe_created_ = false;
+  bool loop_candidate_search_ = false;
+  int loop_min_keyframe_gap_ = 0;
+  std::vector<LoopLogEntry> loop_log_;
 };
 
 // BS/trajectory_deformation.cc:33-43 / :45-146 on a plain pose vector (frame_poses[i] = pose of frame start_frame + i)

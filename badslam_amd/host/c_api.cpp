@@ -10,7 +10,9 @@
 #include "bad_slam.hpp"
 #include "direct_ba.hpp"
 #include "io.hpp"
+#include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
+#include "pose_graph.hpp"
 
 using namespace bslam_host;
 
@@ -499,6 +501,123 @@ int bsh_track_keyframe_pair(void* ba_, void* stream, int tracked_id, int base_id
   });
 }
 
+// TrackFramesPairwiseBatched of keyframes tracked_ids[0..n) against keyframe base_id: out_pose7[7 * p] = base_T_tracked[p],
+// iterations[num_scales * p + s].
+int bsh_track_keyframes_batched(void* ba_, void* stream, int base_id, int n, const int* tracked_ids, const float* inits_pose7, int num_scales,
+                                float* out_pose7, int* iterations) {
+  BSH_TRY({
+    DirectBA* ba = static_cast<DirectBA*>(ba_);
+    const auto& base = ba->keyframes().at(base_id);
+    if (!base) throw std::invalid_argument("base keyframe is deleted");
+    std::vector<TrackedFrameImages> tracked;
+    std::vector<SE3f> inits;
+    for (int p = 0; p < n; ++p) {
+      const auto& kf = ba->keyframes().at(tracked_ids[p]);
+      if (!kf) throw std::invalid_argument("tracked keyframe is deleted");
+      tracked.push_back(TrackedFrameImages{&kf->depth_buffer(), &kf->normals_buffer(), &kf->color_buffer()});
+      inits.push_back(pose_from7(inits_pose7 + 7 * p));
+    }
+    std::vector<std::unique_ptr<PairwiseFrameTrackingBuffers>> buffers;
+    std::vector<SE3f> out;
+    std::vector<std::vector<int>> its;
+    TrackFramesPairwiseBatched(ba->context(), static_cast<hipStream_t>(stream), &buffers, num_scales, ba->color_camera(), ba->depth_camera(), ba->depth_params(),
+                               ba->use_depth_residuals(), ba->use_descriptor_residuals(), tracked, base->depth_buffer(), base->normals_buffer(),
+                               base->color_buffer(), inits, &out, &its);
+    for (int p = 0; p < n; ++p) {
+      pose_to7(out[p], out_pose7 + 7 * p);
+      for (int s = 0; s < num_scales; ++s) iterations[num_scales * p + s] = its[p][s];
+    }
+  });
+}
+
+// LoopClosureResult as flat arrays.  ints: [status, old ids (3), pixel_count, chi2 count, iterations (3 x num_scales)];
+// floats: [refined pose7 x 3, averaged pose7, mean pixel distance]; chi2: up to kLoopPoseGraphIterations doubles.
+static void loop_result_out(const LoopClosureResult& r, int num_scales, int* ints, float* floats, double* chi2) {
+  ints[0] = static_cast<int>(r.status);
+  for (int i = 0; i < 3; ++i) ints[1 + i] = r.old_keyframe_ids[i];
+  ints[4] = r.pixel_count;
+  ints[5] = static_cast<int>(r.chi2.size());
+  for (int i = 0; i < 3; ++i)
+    for (int s = 0; s < num_scales; ++s) ints[6 + num_scales * i + s] = (i < static_cast<int>(r.tracking_iterations.size())) ? r.tracking_iterations[i][s] : 0;
+  for (int i = 0; i < 3; ++i) pose_to7(r.cur_T_old_refined[i], floats + 7 * i);
+  pose_to7(r.cur_T_old_averaged, floats + 21);
+  floats[28] = r.mean_pixel_distance;
+  for (size_t i = 0; i < r.chi2.size() && i < static_cast<size_t>(kLoopPoseGraphIterations); ++i) chi2[i] = r.chi2[i];
+}
+
+int bsh_close_loop(void* ba_, void* stream, int current_id, int matched_id, const float* old_T_cur_initial_pose7, int num_scales, int* ints, float* floats,
+                   double* chi2) {
+  BSH_TRY({
+    LoopClosureResult r;
+    CloseLoop(*static_cast<DirectBA*>(ba_), static_cast<hipStream_t>(stream), current_id, matched_id, pose_from7(old_T_cur_initial_pose7), num_scales, &r);
+    loop_result_out(r, num_scales, ints, floats, chi2);
+  });
+}
+
+// ---- pose graph (host/pose_graph.hpp); poses as double pose7 [qx qy qz qw tx ty tz] ----
+static Pose3d pose3d_from7(const double* p) { return Pose3d::FromQuaternion(p[0], p[1], p[2], p[3], p[4], p[5], p[6]); }
+static void pose3d_to7(const Pose3d& T, double* p) {
+  T.ToQuaternion(p, p + 1, p + 2, p + 3);
+  p[4] = T.t[0]; p[5] = T.t[1]; p[6] = T.t[2];
+}
+static void report_pose_graph(const PoseGraphResult& res, double* chi2, double* initial_chi2, long long* factor_blocks) {
+  if (chi2) for (size_t i = 0; i < res.chi2.size(); ++i) chi2[i] = res.chi2[i];
+  if (initial_chi2) *initial_chi2 = res.initial_chi2;
+  if (factor_blocks) *factor_blocks = static_cast<long long>(res.factor_blocks);
+}
+
+// OptimizePoseGraph on an explicit graph.  poses7: vertex_count x 7 (in / out); edges: edge_count x (from, to);
+// measurements7: edge_count x 7 (from_T_to).  chi2: `iterations` values (may be null).
+int bsh_optimize_pose_graph(int vertex_count, double* poses7, int edge_count, const int* edges, const double* measurements7, int fixed_vertex, int iterations,
+                            double* chi2, double* initial_chi2, long long* factor_blocks) {
+  BSH_TRY({
+    std::vector<Pose3d> poses(static_cast<size_t>(vertex_count));
+    for (int v = 0; v < vertex_count; ++v) poses[v] = pose3d_from7(poses7 + 7 * v);
+    std::vector<PoseGraphEdge> e(static_cast<size_t>(edge_count));
+    for (int i = 0; i < edge_count; ++i) e[i] = PoseGraphEdge{edges[2 * i], edges[2 * i + 1], pose3d_from7(measurements7 + 7 * i)};
+    PoseGraphResult res;
+    OptimizePoseGraph(&poses, e, fixed_vertex, iterations, &res);
+    for (int v = 0; v < vertex_count; ++v)
+      if (v != fixed_vertex) pose3d_to7(poses[v], poses7 + 7 * v);   // the gauge is returned untouched
+    report_pose_graph(res, chi2, initial_chi2, factor_blocks);
+  });
+}
+
+// OptimizeKeyframePoseGraph: exists[i] = 0 for a deleted keyframe; loop_edges: loop_count x (from_id, to_id).
+// Returns the gauge keyframe id (>= 0) or -1 on error.
+int bsh_optimize_keyframe_pose_graph(int keyframe_count, const int* exists, double* poses7, int loop_count, const int* loop_edges,
+                                     const double* loop_measurements7, int iterations, double* chi2, double* initial_chi2, long long* factor_blocks) {
+  int gauge = -1;
+  int rc = [&]() -> int {
+    BSH_TRY({
+      std::vector<Pose3d> poses(static_cast<size_t>(keyframe_count));
+      std::vector<bool> ex(static_cast<size_t>(keyframe_count));
+      for (int i = 0; i < keyframe_count; ++i) {
+        ex[i] = exists[i] != 0;
+        if (ex[i]) poses[i] = pose3d_from7(poses7 + 7 * i);
+      }
+      std::vector<KeyframeLoopEdge> loops(static_cast<size_t>(loop_count));
+      for (int i = 0; i < loop_count; ++i) loops[i] = KeyframeLoopEdge{loop_edges[2 * i], loop_edges[2 * i + 1], pose3d_from7(loop_measurements7 + 7 * i)};
+      PoseGraphResult res;
+      gauge = OptimizeKeyframePoseGraph(&poses, ex, loops, iterations, &res);
+      if (gauge < 0) throw std::invalid_argument("no keyframe exists");
+      for (int i = 0; i < keyframe_count; ++i)
+        if (ex[i] && i != gauge) pose3d_to7(poses[i], poses7 + 7 * i);
+      report_pose_graph(res, chi2, initial_chi2, factor_blocks);
+    });
+  }();
+  return rc < 0 ? rc : gauge;
+}
+
+// AveragePose (BS/util.cc:110-129) of count double pose7s.
+int bsh_average_pose(int count, const double* poses7, double* out7) {
+  BSH_TRY({
+    std::vector<Pose3d> poses;
+    for (int i = 0; i < count; ++i) poses.push_back(pose3d_from7(poses7 + 7 * i));
+    pose3d_to7(AveragePose(poses), out7);
+  });
+}
+
 // ---- BadSlam front end (host/bad_slam.hpp) ----
 // cfg: [keyframe_interval, max_num_ba_iterations_per_keyframe, num_scales, max_surfel_count, sparse_surfel_cell_size, use_motion_model,
 //       use_geometric_residuals, use_photometric_residuals, do_surfel_updates, use_pcg, optimize_intrinsics, disable_deactivation, start_frame]
@@ -534,6 +653,30 @@ int bsh_slam_run_bundle_adjustment(void* slam, int frame_index, int optimize_dep
                                                      increase_ba_iteration_count != 0, &done, &conv);
     if (iterations_done) *iterations_done = done;
     if (converged) *converged = conv ? 1 : 0;
+  });
+}
+int bsh_slam_close_loop(void* slam, int matched_id, const float* old_T_cur_initial_pose7, int* ints, float* floats, double* chi2) {
+  BSH_TRY({
+    BadSlam* s = static_cast<BadSlam*>(slam);
+    LoopClosureResult r;
+    s->CloseLoop(matched_id, pose_from7(old_T_cur_initial_pose7), &r);
+    loop_result_out(r, s->config().num_scales, ints, floats, chi2);
+  });
+}
+int bsh_slam_set_loop_candidate_search(void* slam, int enable, int min_keyframe_gap) {
+  BSH_TRY(static_cast<BadSlam*>(slam)->SetLoopCandidateSearch(enable != 0, min_keyframe_gap));
+}
+int bsh_slam_loop_log_size(void* slam) { return static_cast<int>(static_cast<BadSlam*>(slam)->loop_closure_log().size()); }
+// entries x [keyframe id, candidate id, status]; distances: entries floats
+int bsh_slam_loop_log(void* slam, int* entries3, float* distances, int capacity) {
+  BSH_TRY({
+    const auto& log = static_cast<BadSlam*>(slam)->loop_closure_log();
+    for (size_t i = 0; i < log.size() && static_cast<int>(i) < capacity; ++i) {
+      entries3[3 * i] = log[i].keyframe_id;
+      entries3[3 * i + 1] = log[i].candidate_id;
+      entries3[3 * i + 2] = static_cast<int>(log[i].status);
+      distances[i] = log[i].mean_pixel_distance;
+    }
   });
 }
 int bsh_slam_frame_count(void* slam) { return static_cast<int>(static_cast<BadSlam*>(slam)->frame_poses().size()); }

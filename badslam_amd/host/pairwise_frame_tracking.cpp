@@ -146,4 +146,114 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
   *out_base_T_frame = estimate;
 }
 
+void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vector<std::unique_ptr<PairwiseFrameTrackingBuffers>>* buffers, int num_scales,
+                                const PinholeCamera4f& color_camera, const PinholeCamera4f& depth_camera, const bslam_depth_params& dp,
+                                bool use_depth_residuals, bool use_descriptor_residuals, const std::vector<TrackedFrameImages>& tracked,
+                                const DeviceBuffer<u16>& base_depth_u16, const DeviceBuffer<u16>& base_normals_l0, const DeviceBuffer<uchar4_t>& base_color_rgba,
+                                const std::vector<SE3f>& inits, std::vector<SE3f>* out_base_T_frame, std::vector<std::vector<int>>* iterations_per_scale) {
+  if (depth_camera.width() != color_camera.width()) throw std::invalid_argument("TrackFramesPairwiseBatched: depth and colour images must have the same size here");
+  const int pairs = static_cast<int>(tracked.size());
+  if (pairs < 1 || pairs > BSLAM_MAX_PAIR_BATCH) throw std::invalid_argument("TrackFramesPairwiseBatched: 1 to BSLAM_MAX_PAIR_BATCH tracked frames");
+  if (static_cast<int>(inits.size()) != pairs) throw std::invalid_argument("TrackFramesPairwiseBatched: one initial estimate per tracked frame");
+  while (static_cast<int>(buffers->size()) < pairs)
+    buffers->emplace_back(new PairwiseFrameTrackingBuffers(depth_camera.width(), depth_camera.height(), color_camera.width(), color_camera.height(), num_scales));
+  for (int p = 0; p < pairs; ++p)
+    if ((*buffers)[p]->num_scales != num_scales) throw std::invalid_argument("TrackFramesPairwiseBatched: buffers built for another scale count");
+  const bslam_camera4f color_cam = color_camera.pod(), depth_cam = depth_camera.pod();
+  PairwiseFrameTrackingBuffers& b0 = *(*buffers)[0];
+  // per scale: the base level (shared) and every pair's tracked level
+  std::vector<bslam_buffer2d> base_depth(num_scales), base_normals(num_scales), base_color(num_scales);
+  std::vector<std::vector<bslam_buffer2d>> tracked_depth(num_scales, std::vector<bslam_buffer2d>(pairs)), tracked_normals = tracked_depth,
+                                           tracked_color = tracked_depth;
+  for (int s = 0; s < num_scales; ++s) {
+    base_depth[s] = b0.base_depth[s]->ToPod();
+    base_color[s] = b0.base_color[s]->ToPod();
+    base_normals[s] = s ? b0.base_normals[s]->ToPod() : base_normals_l0.ToPod();
+    for (int p = 0; p < pairs; ++p) {
+      PairwiseFrameTrackingBuffers& bp = *(*buffers)[p];
+      tracked_depth[s][p] = bp.tracked_depth[s]->ToPod();
+      tracked_color[s][p] = bp.tracked_color[s]->ToPod();
+      tracked_normals[s][p] = s ? bp.tracked_normals[s]->ToPod() : tracked[p].normals->ToPod();
+    }
+  }
+  // --- input preparation and pyramids, as TrackFramePairwise does them (base once, each tracked frame once)
+  const bslam_buffer2d base_rgba = base_color_rgba.ToPod(), base_gm = b0.base_gradmag->ToPod(), base_d16 = base_depth_u16.ToPod();
+  Check(bslam_compute_brightness_from_color(ctx, stream, &base_rgba, &base_gm), "bslam_compute_brightness_from_color");
+  Check(bslam_calibrate_depth_and_transform_color_to_depth(ctx, stream, &color_cam, &depth_cam, &dp, &base_d16, &base_gm, &base_depth[0], &base_color[0]),
+        "bslam_calibrate_depth_and_transform_color_to_depth");
+  for (int s = 1; s < num_scales; ++s)
+    Check(bslam_downsample_images(ctx, stream, &base_depth[s - 1], &base_normals[s - 1], &base_color[s - 1], &base_depth[s], &base_normals[s], &base_color[s]),
+          "bslam_downsample_images");
+  for (int p = 0; p < pairs; ++p) {
+    const bslam_buffer2d rgba = tracked[p].color->ToPod(), gm = (*buffers)[p]->tracked_gradmag->ToPod(), d16 = tracked[p].depth->ToPod();
+    Check(bslam_compute_brightness_from_color(ctx, stream, &rgba, &gm), "bslam_compute_brightness_from_color");
+    Check(bslam_calibrate_depth(ctx, stream, &dp, &d16, &tracked_depth[0][p]), "bslam_calibrate_depth");
+    Check(bslam_set_to_read_mode_normalized(ctx, stream, &gm, &tracked_color[0][p]), "bslam_set_to_read_mode_normalized");
+    for (int s = 1; s < num_scales; ++s)
+      Check(bslam_downsample_images(ctx, stream, &tracked_depth[s - 1][p], &tracked_normals[s - 1][p], &tracked_color[s - 1][p], &tracked_depth[s][p],
+                                    &tracked_normals[s][p], &tracked_color[s][p]),
+            "bslam_downsample_images");
+  }
+  // --- coarse to fine in lockstep (TrackFramePairwise's loop per pair)
+  constexpr int kMaxIterationsPerScale = 30;
+  std::vector<SE3f> estimate = inits;
+  iterations_per_scale->assign(pairs, std::vector<int>(num_scales, 0));
+  for (int scale = num_scales - 1; scale >= 0; --scale) {
+    const float scaling_factor = static_cast<float>(std::pow(2, scale));
+    const bslam_camera4f tcc = Scaled(color_camera, 1.f / scaling_factor), tdc = Scaled(depth_camera, 1.f / scaling_factor);
+    const float threshold_factor = scaling_factor;
+    if (scale != num_scales - 1) {   // last estimate vs the initial one (test_different_initial_estimates = false: chosen_initial = init)
+      for (int p = 0; p < pairs; ++p) {
+        u32 count[2] = {0, 0};
+        float cost[2] = {0, 0};
+        const SE3f cand[2] = {estimate[p], inits[p]};
+        for (int i = 0; i < 2; ++i) {
+          const bslam_mat3x4 M = cand[i].Inverse().Matrix3x4();
+          Check(bslam_compute_cost_and_residual_count_from_images(ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx,
+                                                                  threshold_factor, &tracked_depth[scale][p], &tracked_normals[scale][p],
+                                                                  &tracked_color[scale][p], &M, &base_depth[scale], &base_normals[scale], &base_color[scale],
+                                                                  &count[i], &cost[i]),
+                "bslam_compute_cost_and_residual_count_from_images");
+        }
+        if (count[0] > 2 * count[1]) estimate[p] = cand[0];
+        else if (count[1] > 2 * count[0]) estimate[p] = cand[1];
+        else if (cost[0] < cost[1]) estimate[p] = cand[0];
+        else estimate[p] = cand[1];
+      }
+    }
+    float damping = 1.f;   // :573-579
+    if (scale == num_scales - 2) damping = 0.5f;
+    else if (scale == num_scales - 1) damping = 0.25f;
+    std::vector<int> active(pairs);
+    for (int p = 0; p < pairs; ++p) active[p] = p;
+    while (!active.empty()) {
+      const int n = static_cast<int>(active.size());
+      std::vector<bslam_buffer2d> td(n), tn(n), tc(n);
+      std::vector<bslam_mat3x4> M(n);
+      for (int i = 0; i < n; ++i) {
+        const int p = active[i];
+        td[i] = tracked_depth[scale][p]; tn[i] = tracked_normals[scale][p]; tc[i] = tracked_color[scale][p];
+        M[i] = estimate[p].Inverse().Matrix3x4();
+      }
+      std::vector<float> H(21 * static_cast<size_t>(n)), b(6 * static_cast<size_t>(n));
+      Check(bslam_accumulate_pose_coeffs_from_images_batched(ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx,
+                                                              threshold_factor, n, td.data(), tn.data(), tc.data(), M.data(), &base_depth[scale],
+                                                              &base_normals[scale], &base_color[scale], nullptr, H.data(), b.data()),
+            "bslam_accumulate_pose_coeffs_from_images_batched");
+      std::vector<int> still;
+      for (int i = 0; i < n; ++i) {
+        const int p = active[i];
+        float x[6], step[6];
+        SolveLDLTUpper(6, &H[21 * static_cast<size_t>(i)], &b[6 * static_cast<size_t>(i)], x);
+        for (int k = 0; k < 6; ++k) step[k] = -damping * x[k];
+        estimate[p] = estimate[p] * SE3f::Exp(step);
+        const int done = ++(*iterations_per_scale)[p][scale];
+        if (!IsScaleNPoseEstimationConverged(x, scaling_factor) && done < kMaxIterationsPerScale) still.push_back(p);
+      }
+      active.swap(still);
+    }
+  }
+  *out_base_T_frame = estimate;
+}
+
 }  // namespace bslam_host

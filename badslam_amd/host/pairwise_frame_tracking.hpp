@@ -31,4 +31,24 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
                         const SE3f& base_T_frame_initial_estimate_2, SE3f* out_base_T_frame, int* iterations_per_scale,
                         bool use_pyramid_level_0 = true, bool use_gradmag = false);
 
+// Keyframe-format device images of one tracked frame.
+struct TrackedFrameImages {
+  const DeviceBuffer<u16>* depth;
+  const DeviceBuffer<u16>* normals;
+  const DeviceBuffer<uchar4_t>* color;
+};
+
+// Loop verification (BS/loop_detector.cc:495-546): tracks tracked.size() (1..BSLAM_MAX_PAIR_BATCH) frames against ONE base
+// frame in lockstep, with test_different_initial_estimates = false, use_pyramid_level_0 = true, use_gradmag = false.
+// The base pyramid is built once.  Each Gauss-Newton iteration makes one bslam_accumulate_pose_coeffs_from_images_batched
+// call over the pairs still iterating at that scale; each pair keeps its own damping, solve, convergence test and
+// iteration count, so out_base_T_frame[p] and iterations_per_scale[p] are bit-identical to a TrackFramePairwise call of
+// pair p alone.  buffers: grown to tracked.size() entries if shorter (entry 0 also holds the base pyramid).
+void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vector<std::unique_ptr<PairwiseFrameTrackingBuffers>>* buffers, int num_scales,
+                                const PinholeCamera4f& color_camera, const PinholeCamera4f& depth_camera, const bslam_depth_params& depth_params,
+                                bool use_depth_residuals, bool use_descriptor_residuals, const std::vector<TrackedFrameImages>& tracked,
+                                const DeviceBuffer<u16>& base_depth, const DeviceBuffer<u16>& base_normals, const DeviceBuffer<uchar4_t>& base_color,
+                                const std::vector<SE3f>& base_T_frame_initial_estimates, std::vector<SE3f>* out_base_T_frame,
+                                std::vector<std::vector<int>>* iterations_per_scale);
+
 }  // namespace bslam_host

@@ -571,6 +571,21 @@ int bslam_compute_cost_and_residual_count_from_images_gradmag(
     const bslam_mat3x4* estimate_frame_T_surfel_frame,
     const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color,
     uint32_t* residual_count, float* residual_sum);
+/* Batched form of bslam_accumulate_pose_coeffs_from_images for loop verification (BS/loop_detector.cc:440-712), which
+ * tracks ONE base frame against several tracked frames (non-gradmag path only, BS/loop_detector.cc:228).  Pair p uses
+ * tracked_depth[p] / tracked_normals[p] / tracked_color[p] and estimates_frame_T_surfel_frame[p]; the base ("surfel")
+ * images and the cameras are shared.  1 <= pair_count <= BSLAM_MAX_PAIR_BATCH.  Outputs: H[21 * p .. 21 * p + 20],
+ * b[6 * p .. 6 * p + 5], visible_counts[p] (may be NULL), valid on return; row p is bit-identical to the single-pair call
+ * with pair p's arguments.  One launch per stage for all pairs, one copy, one stream synchronisation. */
+#define BSLAM_MAX_PAIR_BATCH 8
+int bslam_accumulate_pose_coeffs_from_images_batched(
+    bslam_context* ctx, void* stream, int use_depth_residuals, int use_descriptor_residuals,
+    const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor,
+    int pair_count,
+    const bslam_buffer2d* tracked_depth, const bslam_buffer2d* tracked_normals, const bslam_buffer2d* tracked_color,
+    const bslam_mat3x4* estimates_frame_T_surfel_frame,
+    const bslam_buffer2d* base_depth, const bslam_buffer2d* base_normals, const bslam_buffer2d* base_color,
+    uint32_t* visible_counts, float* H, float* b);
 /* Replaces ComputeSobelGradientMagnitudeCUDA(stream, rgbi_texture, gradmag_buffer) (BS/cuda_image_processing.cu:104-167): Sobel
  * gradient magnitude of the luma channel of a uchar4 colour image, 0..255. */
 int bslam_compute_sobel_gradient_magnitude(bslam_context* ctx, void* stream, const bslam_buffer2d* color_buffer, const bslam_buffer2d* gradmag_buffer);

@@ -63,22 +63,17 @@ static CamConsts make_cam_consts(const bslam_context* ctx, const bslam_camera4f*
   return c;
 }
 
-static void fill_kf(KfDev* d, const bslam_buffer2d* depth, const bslam_buffer2d* normals, const bslam_buffer2d* color,
-                    const bslam_mat3x4* frame_T_global, const bslam_mat3x3* global_R_frame, int activation, int id,
-                    const bslam_buffer2d* radius = nullptr) {
-  std::memset(d, 0, sizeof(*d));
-  d->depth = (const uint8_t*)depth->address;     d->depth_pitch = (uint32_t)depth->pitch;
-  d->normals = (const uint8_t*)normals->address; d->normals_pitch = (uint32_t)normals->pitch;
-  if (color) { d->color = (const uint8_t*)color->address; d->color_pitch = (uint32_t)color->pitch; }
-  if (radius) { d->radius = (const uint8_t*)radius->address; d->radius_pitch = (uint32_t)radius->pitch; }
-  std::memcpy(d->frame_T_global.m, frame_T_global->m, sizeof(float) * 12);
-  if (global_R_frame) std::memcpy(d->global_R_frame, global_R_frame->m, sizeof(float) * 9);
-  d->activation = activation;
-  d->id = id;
+// surfels_size against the width of the surfel buffer and, when given, of the active-surfel buffer.
+static int check_surfels_size(const bslam_buffer2d* surfels, uint32_t surfels_size, const bslam_buffer2d* active = nullptr) {
+  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
+  if (active && (!active->address || surfels_size > (uint32_t)active->width))
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null or narrower than surfels_size %u", surfels_size);
+  return BSLAM_OK;
 }
 
-static int check_common(const bslam_context* ctx, const bslam_camera4f* depth_camera, const bslam_depth_params* dp,
-                        const bslam_buffer2d* surfels) {
+// The arguments every surfel call validates: depth camera, depth parameters, surfel buffer and check_surfels_size.
+static int check_surfel_call(const bslam_context* ctx, const bslam_camera4f* depth_camera, const bslam_depth_params* dp,
+                             const bslam_buffer2d* surfels, uint32_t surfels_size, const bslam_buffer2d* active = nullptr) {
   if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
   if (!depth_camera || !dp || !surfels) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (dp->sparse_surfel_cell_size < 1) return fail(BSLAM_ERR_INVALID_ARGUMENT, "sparse_surfel_cell_size must be >= 1");
@@ -90,7 +85,7 @@ static int check_common(const bslam_context* ctx, const bslam_camera4f* depth_ca
                 dp->cfactor_buffer.width, dp->cfactor_buffer.height, depth_camera->width, depth_camera->height,
                 dp->sparse_surfel_cell_size, need_w, need_h);
   if (surfels->height < BSLAM_SURFEL_DATA_ATTRIBUTE_COUNT) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfel buffer has %d rows, need >= %d", surfels->height, BSLAM_SURFEL_DATA_ATTRIBUTE_COUNT);
-  return BSLAM_OK;
+  return check_surfels_size(surfels, surfels_size, active);
 }
 
 static int check_image(const bslam_buffer2d* b, const bslam_camera4f* cam, size_t elem, const char* name) {
@@ -101,29 +96,53 @@ static int check_image(const bslam_buffer2d* b, const bslam_camera4f* cam, size_
   return BSLAM_OK;
 }
 
+// The images of a keyframe view a call reads, checked against the cameras.
+static int check_keyframe_images(const bslam_keyframe_view& v, const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera,
+                                 bool need_color, bool need_radius) {
+  int rc = check_image(&v.depth, depth_camera, 2, "keyframe depth");
+  if (rc) return rc;
+  if ((rc = check_image(&v.normals, depth_camera, 2, "keyframe normals"))) return rc;
+  if (need_color && (rc = check_image(&v.color, color_camera, 4, "keyframe color"))) return rc;
+  if (need_radius && (rc = check_image(&v.radius, depth_camera, 2, "keyframe radius"))) return rc;
+  return BSLAM_OK;
+}
+
+// Row r of a surfel buffer.
+static float* surfel_row(const bslam_buffer2d* s, int r) { return (float*)((uint8_t*)s->address + (size_t)r * s->pitch); }
+
 static SurfelRows surfel_rows(const bslam_buffer2d* s, uint32_t size) {
-  auto row = [&](int r) { return (const float*)((const uint8_t*)s->address + (size_t)r * s->pitch); };
   SurfelRows o;
-  o.x = row(BSLAM_SURFEL_X); o.y = row(BSLAM_SURFEL_Y); o.z = row(BSLAM_SURFEL_Z);
-  o.normal = (const uint32_t*)row(BSLAM_SURFEL_NORMAL);
-  o.radius_squared = row(BSLAM_SURFEL_RADIUS_SQUARED);
-  o.d1 = row(BSLAM_SURFEL_DESCRIPTOR1); o.d2 = row(BSLAM_SURFEL_DESCRIPTOR2);
+  o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
+  o.normal = (const uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
+  o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
+  o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
   o.size = size;
   return o;
 }
 
 static SurfelRowsRW surfel_rows_rw(const bslam_buffer2d* s, const bslam_buffer2d* active, uint32_t size) {
-  auto row = [&](int r) { return (float*)((uint8_t*)s->address + (size_t)r * s->pitch); };
   SurfelRowsRW o;
-  o.x = row(BSLAM_SURFEL_X); o.y = row(BSLAM_SURFEL_Y); o.z = row(BSLAM_SURFEL_Z);
-  o.normal = (uint32_t*)row(BSLAM_SURFEL_NORMAL);
-  o.radius_squared = row(BSLAM_SURFEL_RADIUS_SQUARED);
-  o.d1 = row(BSLAM_SURFEL_DESCRIPTOR1); o.d2 = row(BSLAM_SURFEL_DESCRIPTOR2);
+  o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
+  o.normal = (uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
+  o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
+  o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
   o.active = active ? (uint8_t*)active->address : nullptr;
   o.size = size;
   o.perm = nullptr;
   o.ox = o.x; o.oy = o.y; o.oz = o.z; o.onormal = o.normal; o.od1 = o.d1; o.od2 = o.d2;
   return o;
+}
+
+// Copies `count` values from the device into the context's pinned staging and waits for the stream: a result the call returns
+// on the host.  *host stays valid until the next call on the context.
+template <typename T>
+static int read_back(bslam_context* ctx, hipStream_t stream, const T* dev, size_t count, const T** host) {
+  int rc = ctx->staging2.reserve(count * sizeof(T));
+  if (rc) return rc;
+  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, dev, count * sizeof(T), hipMemcpyDeviceToHost, stream));
+  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+  *host = (const T*)ctx->staging2.ptr;
+  return BSLAM_OK;
 }
 
 // Uploads a keyframe table through pinned staging.  The staging buffer is only rewritten after
@@ -193,27 +212,36 @@ static int upload_kf_table(bslam_context* ctx, hipStream_t stream, std::vector<K
   return BSLAM_OK;
 }
 
-static int build_kf_table(const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, bool need_color,
-                          int keyframe_count, const bslam_keyframe_view* keyframes, std::vector<KfDev>* table, bool need_radius = false) {
-  table->resize((size_t)keyframe_count);
+// The setup of every call that walks a keyframe table: validates the arguments (check_surfel_call), sets the device, builds the
+// table from the keyframe views with their colour / radius images as requested, forms the camera constants into *c and uploads
+// the table.  An empty list becomes one zeroed entry, which keeps the table pointer valid (the calls that refuse an empty list,
+// or return early on one, do so before).  Calls that return early once their arguments are valid run check_surfel_call first
+// themselves.
+static int setup_keyframe_table(bslam_context* ctx, hipStream_t stream, const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
+                                const bslam_depth_params* dp, int keyframe_count, const bslam_keyframe_view* keyframes, bool need_color,
+                                uint32_t surfels_size, const bslam_buffer2d* surfels, CamConsts* c,
+                                const bslam_buffer2d* active = nullptr, bool need_radius = false) {
+  int rc = check_surfel_call(ctx, depth_camera, dp, surfels, surfels_size, active);
+  if (rc) return rc;
+  if (keyframe_count < 0 || (keyframe_count > 0 && !keyframes)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad keyframe list");
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  std::vector<KfDev> table((size_t)std::max(keyframe_count, 1));
+  std::memset(table.data(), 0, table.size() * sizeof(KfDev));
   for (int k = 0; k < keyframe_count; ++k) {
     const bslam_keyframe_view& v = keyframes[k];
-    int rc = check_image(&v.depth, depth_camera, 2, "keyframe depth");
-    if (rc) return rc;
-    rc = check_image(&v.normals, depth_camera, 2, "keyframe normals");
-    if (rc) return rc;
-    if (need_color) {
-      rc = check_image(&v.color, color_camera, 4, "keyframe color");
-      if (rc) return rc;
-    }
-    if (need_radius) {
-      rc = check_image(&v.radius, depth_camera, 2, "keyframe radius");
-      if (rc) return rc;
-    }
-    fill_kf(&(*table)[k], &v.depth, &v.normals, need_color ? &v.color : nullptr, &v.frame_T_global, &v.global_R_frame, v.activation, v.id,
-            need_radius ? &v.radius : nullptr);
+    if ((rc = check_keyframe_images(v, depth_camera, color_camera, need_color, need_radius))) return rc;
+    KfDev& d = table[(size_t)k];
+    d.depth = (const uint8_t*)v.depth.address;     d.depth_pitch = (uint32_t)v.depth.pitch;
+    d.normals = (const uint8_t*)v.normals.address; d.normals_pitch = (uint32_t)v.normals.pitch;
+    if (need_color) { d.color = (const uint8_t*)v.color.address; d.color_pitch = (uint32_t)v.color.pitch; }
+    if (need_radius) { d.radius = (const uint8_t*)v.radius.address; d.radius_pitch = (uint32_t)v.radius.pitch; }
+    std::memcpy(d.frame_T_global.m, v.frame_T_global.m, sizeof(float) * 12);
+    std::memcpy(d.global_R_frame, v.global_R_frame.m, sizeof(float) * 9);
+    d.activation = v.activation;
+    d.id = v.id;
   }
-  return BSLAM_OK;
+  *c = make_cam_consts(ctx, color_camera, depth_camera, dp);
+  return upload_kf_table(ctx, stream, table, *c);
 }
 
 // Builds (or re-uses) the XCD-aware granule order for a surfel buffer: centroid per granule on the
@@ -251,13 +279,13 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
   if (perm_out) *perm_out = nullptr;
   if (!ctx->use_schedule || G < 64) return BSLAM_OK;   // tiny problems: identity order
   const bool want_perm = perm_out != nullptr && keyframe_count >= kPermMinKeyframes;
-  if (want_perm && ctx->perm_key_ptr == surfels->address && ctx->perm_key_size == surfels_size && ctx->perm_key_pitch == surfels->pitch) {
+  if (want_perm && ctx->perm_key.matches(surfels, surfels_size)) {
     // the permutation was sorted asynchronously on the stream of the call that built it: a call on another stream waits for it
     if (stream != ctx->perm_stream && ctx->perm_ready) BSLAM_HIP_TRY(hipStreamWaitEvent(stream, ctx->perm_ready, 0));
     *perm_out = (const uint32_t*)ctx->perm.ptr;
     return BSLAM_OK;
   }
-  if (!want_perm && ctx->order_key_ptr == surfels->address && ctx->order_key_size == surfels_size && ctx->order_key_pitch == surfels->pitch) {
+  if (!want_perm && ctx->order_key.matches(surfels, surfels_size)) {
     out->order = (const uint32_t*)ctx->order.ptr;
     return BSLAM_OK;
   }
@@ -266,8 +294,10 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
   int rc = ctx->centroids.reserve((size_t)G * sizeof(float4));
   if (rc) return rc;
   float4* d_cent = (float4*)ctx->centroids.ptr;
-  auto row = [&](int r) { return (const float*)((const uint8_t*)surfels->address + (size_t)r * surfels->pitch); };
-  hipLaunchKernelGGL(granule_centroid_kernel, dim3(G), dim3(kGranule), 0, stream, row(BSLAM_SURFEL_X), row(BSLAM_SURFEL_Y), row(BSLAM_SURFEL_Z), surfels_size, d_cent);
+  const float* x = surfel_row(surfels, BSLAM_SURFEL_X);
+  const float* y = surfel_row(surfels, BSLAM_SURFEL_Y);
+  const float* z = surfel_row(surfels, BSLAM_SURFEL_Z);
+  hipLaunchKernelGGL(granule_centroid_kernel, dim3(G), dim3(kGranule), 0, stream, x, y, z, surfels_size, d_cent);
   BSLAM_HIP_TRY(hipGetLastError());
   std::vector<float4> cent(G);
   BSLAM_HIP_TRY(hipMemcpyAsync(cent.data(), d_cent, (size_t)G * sizeof(float4), hipMemcpyDeviceToHost, stream));
@@ -282,7 +312,7 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
     // keys + identity -> radix sort by key -> perm.  Layout of ctx->perm: perm[S] | keys[S] | keys_sorted[S] | ids[S] | sort scratch
     const size_t n = surfels_size, words = (n + 63) & ~(size_t)63;
     size_t temp_bytes = 0;
-    ctx->perm_key_ptr = nullptr;   // as above
+    ctx->perm_key.clear();   // as above
     BSLAM_HIP_TRY(rocprim::radix_sort_pairs(nullptr, temp_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, 30, stream));
     if ((rc = ctx->perm.reserve(4 * words * sizeof(uint32_t) + temp_bytes + 256))) return rc;
     uint32_t* d_perm = (uint32_t*)ctx->perm.ptr;
@@ -294,21 +324,18 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
     inv3.x = hi[0] > lo[0] ? 1.f / (hi[0] - lo[0]) : 0.f;
     inv3.y = hi[1] > lo[1] ? 1.f / (hi[1] - lo[1]) : 0.f;
     inv3.z = hi[2] > lo[2] ? 1.f / (hi[2] - lo[2]) : 0.f;
-    hipLaunchKernelGGL(surfel_morton_key_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, row(BSLAM_SURFEL_X), row(BSLAM_SURFEL_Y), row(BSLAM_SURFEL_Z),
-                       surfels_size, lo3, inv3, d_keys, d_ids);
+    hipLaunchKernelGGL(surfel_morton_key_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, x, y, z, surfels_size, lo3, inv3, d_keys, d_ids);
     BSLAM_HIP_TRY(hipGetLastError());
     BSLAM_HIP_TRY(rocprim::radix_sort_pairs(d_temp, temp_bytes, (const uint32_t*)d_keys, d_keys_sorted, (const uint32_t*)d_ids, d_perm, n, 0, 30, stream));
     if (!ctx->perm_ready) BSLAM_HIP_TRY(hipEventCreateWithFlags(&ctx->perm_ready, hipEventDisableTiming));
     BSLAM_HIP_TRY(hipEventRecord(ctx->perm_ready, stream));
     ctx->perm_stream = stream;
     ++ctx->perm_serial;
-    ctx->perm_key_ptr = surfels->address;
-    ctx->perm_key_size = surfels_size;
-    ctx->perm_key_pitch = surfels->pitch;
+    ctx->perm_key.set(surfels, surfels_size);
     *perm_out = d_perm;
     return BSLAM_OK;
   }
-  ctx->order_key_ptr = nullptr;   // the slab may move and is rewritten below: no stale key survives an early return
+  ctx->order_key.clear();   // the slab may move and is rewritten below: no stale key survives an early return
   if ((rc = ctx->order.reserve((size_t)G * sizeof(uint32_t)))) return rc;
   uint32_t* d_order = (uint32_t*)ctx->order.ptr;
   std::vector<std::pair<uint32_t, uint32_t>> keyed(G);
@@ -331,9 +358,7 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
   for (uint32_t g = 0; g < G; ++g) order[g] = keyed[g].second;
   BSLAM_HIP_TRY(hipMemcpyAsync(d_order, order.data(), (size_t)G * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // `order` is a stack-local vector
-  ctx->order_key_ptr = surfels->address;
-  ctx->order_key_size = surfels_size;
-  ctx->order_key_pitch = surfels->pitch;
+  ctx->order_key.set(surfels, surfels_size);
   out->order = d_order;
   return BSLAM_OK;
 }
@@ -350,7 +375,7 @@ static int prepare_surfels(bslam_context* ctx, hipStream_t stream, const bslam_b
   int rc = make_schedule(ctx, stream, surfels, surfels_size, R, &w->sc, keyframe_count, &w->perm);
   if (rc) return rc;
   w->rows = surfel_rows(surfels, surfels_size);
-  if (!w->perm) { ctx->sorted_key_ptr = nullptr; return BSLAM_OK; }
+  if (!w->perm) { ctx->sorted_key.clear(); return BSLAM_OK; }
   const size_t pitch = ((size_t)surfels_size + 63) & ~(size_t)63;
   if ((rc = ctx->sorted_rows.reserve(7 * pitch * sizeof(float)))) return rc;
   float* out = (float*)ctx->sorted_rows.ptr;
@@ -363,9 +388,8 @@ static int prepare_surfels(bslam_context* ctx, hipStream_t stream, const bslam_b
   // the copy costs a scattered 4-byte read per row and surfel: rows the call's kernels never read (radius, descriptors in a
   // geometry-only call) are left out
   const int copy_rows = need_descriptor_rows ? 7 : 4;
-  const bool reuse = same_surfels_as_last_call && ctx->sorted_key_ptr == surfels->address && ctx->sorted_key_size == surfels_size &&
-                     ctx->sorted_key_pitch == surfels->pitch && ctx->sorted_key_rows >= copy_rows && ctx->sorted_key_bounds == (bounds != nullptr) &&
-                     ctx->sorted_key_perm_serial == ctx->perm_serial;
+  const bool reuse = same_surfels_as_last_call && ctx->sorted_key.matches(surfels, surfels_size) && ctx->sorted_key_rows >= copy_rows &&
+                     ctx->sorted_key_bounds == (bounds != nullptr) && ctx->sorted_key_perm_serial == ctx->perm_serial;
   if (reuse) {
     // K = 300 photometric PCG: 0.47 ms per PCGStep1 call, 8.5 of the 325 ms of a BA iteration
   } else if (need_descriptor_rows)
@@ -375,7 +399,7 @@ static int prepare_surfels(bslam_context* ctx, hipStream_t stream, const bslam_b
     hipLaunchKernelGGL(permute_surfel_rows_kernel<4>, dim3(w->sc.granules), dim3(256), 0, stream, w->perm, surfels_size, (const float*)surfels->address,
                        surfels->pitch / sizeof(float), out, pitch, bounds);
   BSLAM_HIP_TRY(hipGetLastError());
-  ctx->sorted_key_ptr = surfels->address; ctx->sorted_key_size = surfels_size; ctx->sorted_key_pitch = surfels->pitch;
+  ctx->sorted_key.set(surfels, surfels_size);
   if (!reuse) { ctx->sorted_key_rows = copy_rows; ctx->sorted_key_bounds = bounds != nullptr; ctx->sorted_key_perm_serial = ctx->perm_serial; }
   w->sc.bounds = bounds;
   w->rows.x = out; w->rows.y = out + pitch; w->rows.z = out + 2 * pitch;
@@ -604,9 +628,9 @@ int bslam_create(int device, bslam_context** out_ctx) {
   ctx->device = device;
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, device) == hipSuccess) ctx->cu_count = prop.multiProcessorCount;
-  int rc = ctx->misc.reserve(256);
+  int rc = ctx->misc.reserve(kMiscBytes);
   if (rc) { delete ctx; return rc; }
-  if (hipMemset(ctx->misc.ptr, 0, 256) != hipSuccess) { delete ctx; return fail(BSLAM_ERR_HIP, "hipMemset failed"); }
+  if (hipMemset(ctx->misc.ptr, 0, kMiscBytes) != hipSuccess) { delete ctx; return fail(BSLAM_ERR_HIP, "hipMemset failed"); }
   if (const char* e = getenv("BSLAM_CULLING")) ctx->culling = atoi(e) != 0;   // A/B runs of whole programs (bslam_set_culling otherwise)
   *out_ctx = ctx;
   return BSLAM_OK;
@@ -614,16 +638,8 @@ int bslam_create(int device, bslam_context** out_ctx) {
 
 int bslam_destroy(bslam_context* ctx) {
   if (!ctx) return BSLAM_OK;
-  hipError_t e = hipSetDevice(ctx->device); (void)e;
+  hipError_t e = hipSetDevice(ctx->device); (void)e;   // the context frees its memory, events and streams on its own device
   bslam_comm_destroy(ctx);
-  ctx->kf_table.release(); ctx->partials.release(); ctx->coeffs.release(); ctx->pose_state.release(); ctx->misc.release(); ctx->records.release(); ctx->quads.release(); ctx->exchange.release(); ctx->lifecycle.release(); ctx->quads_aux.release(); ctx->order.release(); ctx->centroids.release(); ctx->perm.release(); ctx->sorted_rows.release(); ctx->bounds.release(); ctx->vis.release(); ctx->intr_cells.release(); ctx->prof_counters.release();
-  ctx->staging.release(); ctx->staging2.release(); ctx->upload_ring.release();
-  for (hipEvent_t& e : ctx->iter_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; e = nullptr; }
-  for (hipEvent_t& e : ctx->solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; e = nullptr; }
-  if (ctx->copy_stream) { hipError_t err = hipStreamDestroy(ctx->copy_stream); (void)err; ctx->copy_stream = nullptr; }
-  if (ctx->perm_ready) { hipError_t err = hipEventDestroy(ctx->perm_ready); (void)err; ctx->perm_ready = nullptr; }
-  for (auto& ev : ctx->prof_pending) ctx->prof_pool.push_back(std::make_pair(ev.start, ev.stop));
-  for (auto& ev : ctx->prof_pool) { hipError_t e1 = hipEventDestroy(ev.first); e1 = hipEventDestroy(ev.second); (void)e1; }
   delete ctx;
   return BSLAM_OK;
 }
@@ -714,8 +730,8 @@ int bslam_invalidate_keyframe_cache(bslam_context* ctx) {
 int bslam_set_xcd_schedule(bslam_context* ctx, int enable) {
   if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
   ctx->use_schedule = enable != 0;
-  ctx->order_key_ptr = nullptr;
-  ctx->perm_key_ptr = nullptr;
+  ctx->order_key.clear();
+  ctx->perm_key.clear();
   return BSLAM_OK;
 }
 
@@ -802,21 +818,14 @@ int bslam_assign_colors(
     const bslam_buffer2d* surfels) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;   // BS/kernel_assign_colors.cc:49-51
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "color_camera is null");
-  if (keyframe_count < 0 || (keyframe_count > 0 && !keyframes)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad keyframe list");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  if (surfels->height <= BSLAM_SURFEL_COLOR) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the surfel buffer has no colour row");
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
+  if (rc) return rc;
   if (keyframe_count == 0) return BSLAM_OK;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, true, keyframe_count, keyframes, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
-  uint32_t* color_row = (uint32_t*)((uint8_t*)surfels->address + (size_t)BSLAM_SURFEL_COLOR * surfels->pitch);
+  CamConsts c;
+  if ((rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, true, surfels_size, surfels, &c))) return rc;
   hipLaunchKernelGGL(assign_colors_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, keyframe_count,
-                     surfel_rows_rw(surfels, nullptr, surfels_size), color_row);
+                     surfel_rows_rw(surfels, nullptr, surfels_size), (uint32_t*)surfel_row(surfels, BSLAM_SURFEL_COLOR));
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }
@@ -884,24 +893,18 @@ int bslam_debug_count_pairs(
     int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t surfels_size, const bslam_buffer2d* surfels,
     uint64_t* in_bounds_pairs, uint64_t* associated_pairs) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (keyframe_count <= 0 || !keyframes) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need at least one keyframe");
-  if (surfels_size == 0 || surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad surfels_size %u", surfels_size);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, nullptr, false, keyframe_count, keyframes, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
-  unsigned long long* d_out = (unsigned long long*)((uint8_t*)ctx->misc.ptr + 64);
+  if (surfels_size == 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size must be > 0");
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, nullptr, depth_camera, depth_params, keyframe_count, keyframes, false, surfels_size, surfels, &c);
+  if (rc) return rc;
+  unsigned long long* d_out = (unsigned long long*)((uint8_t*)ctx->misc.ptr + kMiscPairCensus);
   BSLAM_HIP_TRY(hipMemsetAsync(d_out, 0, 2 * sizeof(unsigned long long), stream));
   hipLaunchKernelGGL(count_pairs_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, keyframe_count,
                      surfel_rows_rw(surfels, nullptr, surfels_size), d_out);
   BSLAM_HIP_TRY(hipGetLastError());
-  if ((rc = ctx->staging2.reserve(64))) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, d_out, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-  const unsigned long long* o = (const unsigned long long*)ctx->staging2.ptr;
+  const unsigned long long* o = nullptr;
+  if ((rc = read_back(ctx, stream, (const unsigned long long*)d_out, 2, &o))) return rc;
   if (in_bounds_pairs) *in_bounds_pairs = o[0];
   if (associated_pairs) *associated_pairs = o[1];
   return BSLAM_OK;
@@ -914,28 +917,26 @@ int bslam_accumulate_pose_estimation_coeffs(
     const bslam_mat3x4* frame_T_global_estimate, uint32_t surfels_size, const bslam_buffer2d* surfels,
     int debug, uint32_t* residual_count, float* residual_sum, float* H, float* b) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   // CHECK(use_depth_residuals || use_descriptor_residuals); CHECK_GT(surfels_size, 0)  (BS/kernel_opt_pose.cc:58-61)
   if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
   if (surfels_size == 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size must be > 0");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  if (!H || !b || !frame_T_global_estimate || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if ((rc = check_image(depth_buffer, depth_camera, 2, "depth"))) return rc;
-  if ((rc = check_image(normals_buffer, depth_camera, 2, "normals"))) return rc;
-  if (use_descriptor_residuals && (rc = check_image(color_buffer, color_camera, 4, "color"))) return rc;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-
-  std::vector<KfDev> table(1);
-  fill_kf(&table[0], depth_buffer, normals_buffer, use_descriptor_residuals ? color_buffer : nullptr, frame_T_global_estimate, nullptr, BSLAM_KF_ACTIVE, 0);
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  if (!H || !b || !frame_T_global_estimate || !color_camera || !depth_buffer || !normals_buffer || (use_descriptor_residuals && !color_buffer))
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  // the one keyframe of the table: the caller's images at the pose estimate
+  bslam_keyframe_view v;
+  std::memset(&v, 0, sizeof(v));
+  v.depth = *depth_buffer;
+  v.normals = *normals_buffer;
+  if (use_descriptor_residuals) v.color = *color_buffer;
+  v.frame_T_global = *frame_T_global_estimate;
+  v.activation = BSLAM_KF_ACTIVE;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, 1, &v, use_descriptor_residuals != 0, surfels_size, surfels, &c);
+  if (rc) return rc;
   int tiles = 0;
   if ((rc = launch_pose_accumulate(ctx, stream, use_depth_residuals, use_descriptor_residuals, c, 1, surfels_size, surfels, nullptr, &tiles, true, nullptr, nullptr, debug != 0))) return rc;
-  if ((rc = ctx->staging2.reserve(kRow * sizeof(float)))) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, kRow * sizeof(float), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // results valid on return, BS/kernel_opt_pose.cc:96
-  const float* out = (const float*)ctx->staging2.ptr;
+  const float* out = nullptr;
+  if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, kRow, &out))) return rc;   // results valid on return, BS/kernel_opt_pose.cc:96
   std::memcpy(H, out, 21 * sizeof(float));
   std::memcpy(b, out + 21, 6 * sizeof(float));
   if (debug) {
@@ -951,25 +952,18 @@ int bslam_accumulate_pose_coeffs_batched(
     int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t surfels_size, const bslam_buffer2d* surfels,
     float* Hb, uint32_t* counts) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
   if (keyframe_count <= 0 || !keyframes || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need at least one keyframe");
   if (surfels_size == 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size must be > 0");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, use_descriptor_residuals != 0, keyframe_count, keyframes, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, use_descriptor_residuals != 0,
+                                surfels_size, surfels, &c);
+  if (rc) return rc;
   int tiles = 0;
   if ((rc = launch_pose_accumulate(ctx, stream, use_depth_residuals, use_descriptor_residuals, c, keyframe_count, surfels_size, surfels, nullptr, &tiles))) return rc;
   if (Hb || counts) {
-    const size_t bytes = (size_t)keyframe_count * kRow * sizeof(float);
-    if ((rc = ctx->staging2.reserve(bytes))) return rc;
-    BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, bytes, hipMemcpyDeviceToHost, stream));
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-    const float* out = (const float*)ctx->staging2.ptr;
+    const float* out = nullptr;
+    if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, (size_t)keyframe_count * kRow, &out))) return rc;
     for (int k = 0; k < keyframe_count; ++k) {
       if (Hb) std::memcpy(Hb + 27 * (size_t)k, out + (size_t)k * kRow, 27 * sizeof(float));
       if (counts) counts[k] = read_row_count(out + (size_t)k * kRow);
@@ -985,15 +979,12 @@ int bslam_estimate_frame_poses_batched(
     int max_iterations, bslam_se3f* poses, int32_t* iterations_done, int32_t* converged,
     bslam_allreduce_fn allreduce, void* allreduce_user) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
   if (keyframe_count <= 0 || !keyframes || !poses || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need at least one keyframe and its pose");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, use_descriptor_residuals != 0, keyframe_count, keyframes, &table))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, use_descriptor_residuals != 0,
+                                surfels_size, surfels, &c);
+  if (rc) return rc;
   // pose state: keyframes that are INACTIVE are not optimised (BS/direct_ba_alternating.cc:549-552)
   std::vector<PoseState> states((size_t)keyframe_count);
   for (int k = 0; k < keyframe_count; ++k) {
@@ -1003,8 +994,6 @@ int bslam_estimate_frame_poses_batched(
     std::memcpy(st.t, poses[k].t, sizeof(float) * 3);
     st.converged = (keyframes[k].activation == BSLAM_KF_INACTIVE) ? 1 : 0;
   }
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
   const size_t state_bytes = states.size() * sizeof(PoseState);
   if ((rc = ctx->pose_state.reserve(state_bytes))) return rc;
   if ((rc = ctx->staging2.reserve(state_bytes + 64))) return rc;
@@ -1017,7 +1006,7 @@ int bslam_estimate_frame_poses_batched(
   }
 
   PoseState* d_states = (PoseState*)ctx->pose_state.ptr;
-  int* d_active = (int*)ctx->misc.ptr;                                     // [4]: one counter per in-flight iteration
+  int* d_active = (int*)((uint8_t*)ctx->misc.ptr + kMiscActive);          // [4]: one counter per in-flight iteration
   int* h_active = (int*)((uint8_t*)ctx->staging2.ptr + state_bytes);       // [4]
   for (hipEvent_t& e : ctx->iter_done)
     if (!e) BSLAM_HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -1131,31 +1120,16 @@ int bslam_estimate_frame_poses_batched(
 
 // ---- activation / geometry ------------------------------------------------------------------
 
-static int geometry_common(bslam_context* ctx, hipStream_t stream, const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
-                           const bslam_depth_params* dp, bool need_color, int keyframe_count, const bslam_keyframe_view* keyframes,
-                           uint32_t surfels_size, const bslam_buffer2d* surfels, const bslam_buffer2d* active) {
-  int rc = check_common(ctx, depth_camera, dp, surfels);
-  if (rc) return rc;
-  if (keyframe_count < 0 || (keyframe_count > 0 && !keyframes)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad keyframe list");
-  if (!active || !active->address) return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null");
-  if (surfels_size > (uint32_t)surfels->width || surfels_size > (uint32_t)active->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds a buffer width", surfels_size);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, need_color, keyframe_count, keyframes, &table))) return rc;
-  if (table.empty()) { table.resize(1); std::memset(&table[0], 0, sizeof(KfDev)); }   // keep the table pointer valid; kf_count = 0 makes every loop empty
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, dp);
-  return upload_kf_table(ctx, stream, table, c);
-}
-
 int bslam_update_surfel_activation(
     bslam_context* ctx, void* stream_, const bslam_camera4f* depth_camera, const bslam_depth_params* depth_params,
     int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t surfels_size, const bslam_buffer2d* surfels,
     const bslam_buffer2d* active_surfels) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;   // BS/kernel_surfel_activation.cc:48-50
-  int rc = geometry_common(ctx, stream, nullptr, depth_camera, depth_params, false, keyframe_count, keyframes, surfels_size, surfels, active_surfels);
+  if (!active_surfels) return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null");
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, nullptr, depth_camera, depth_params, keyframe_count, keyframes, false, surfels_size, surfels, &c, active_surfels);
   if (rc) return rc;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
   // A surfel stops at its first associated keyframe.  On a stack where every keyframe sees everything that is about 3 of K
   // visits, which does not pay for a sorted copy of the rows: granule order.  On a trajectory the first keyframes of the list
   // do not see the surfel at all and the walk is long; from kActivationPermMinKeyframes keyframes on the pass therefore runs
@@ -1196,9 +1170,10 @@ int bslam_update_surfel_normals(
     const bslam_buffer2d* active_surfels) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;   // BS/kernel_opt_geometry.cc:48-50
-  int rc = geometry_common(ctx, stream, nullptr, depth_camera, depth_params, false, keyframe_count, keyframes, surfels_size, surfels, active_surfels);
+  if (!active_surfels) return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null");
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, nullptr, depth_camera, depth_params, keyframe_count, keyframes, false, surfels_size, surfels, &c, active_surfels);
   if (rc) return rc;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
   SurfelWork work;
   if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, 1, keyframe_count, &work, false))) return rc;
   const Schedule sc = work.sc;
@@ -1226,9 +1201,11 @@ int bslam_optimize_geometry_iteration(
   if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");   // BS/kernel_opt_geometry.cc:91
   if (surfels_size == 0) return BSLAM_OK;   // BS/kernel_opt_geometry.cc:93-95
   if (!color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "color_camera is null");
-  int rc = geometry_common(ctx, stream, color_camera, depth_camera, depth_params, use_descriptor_residuals != 0, keyframe_count, keyframes, surfels_size, surfels, active_surfels);
+  if (!active_surfels) return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null");
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, use_descriptor_residuals != 0,
+                                surfels_size, surfels, &c, active_surfels);
   if (rc) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
 #ifndef BSLAM_GEOM_R
 #define BSLAM_GEOM_R 3
 #endif
@@ -1297,15 +1274,10 @@ int bslam_debug_association(
     const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* out_pixel) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!keyframe || !out_pixel) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, nullptr, false, 1, keyframe, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, nullptr, depth_camera, depth_params, 1, keyframe, false, surfels_size, surfels, &c);
+  if (rc) return rc;
   hipLaunchKernelGGL(association_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr,
                      surfel_rows_rw(surfels, nullptr, surfels_size), out_pixel);
   BSLAM_HIP_TRY(hipGetLastError());
@@ -1318,15 +1290,10 @@ int bslam_debug_pose_residuals(
     const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, float* out) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!keyframe || !out || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, use_descriptor_residuals != 0, 1, keyframe, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, 1, keyframe, use_descriptor_residuals != 0, surfels_size, surfels, &c);
+  if (rc) return rc;
   const dim3 grid((surfels_size + 255) / 256), block(256);
   const KfDev* kfs = (const KfDev*)ctx->kf_table.ptr;
   const SurfelRowsRW rows = surfel_rows_rw(surfels, nullptr, surfels_size);

@@ -33,39 +33,54 @@ inline int fail(int code, const char* fmt, ...) {
     if (e_ != hipSuccess) return ::bslam::fail(BSLAM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
-// Byte offsets of the small device scalars in bslam_context::misc (256 bytes, zeroed at creation): [0, 16) active-keyframe
-// counters of the batched pose loop, [64, 80) pair census, [128, 192) PCG scalars, [192, 224) lifecycle / preprocessing counters.
-constexpr size_t kMiscCullStats = 224;   // unsigned long long[2]: (work slot, keyframe) pairs tested / visited by the pose kernel
+// Byte offsets of the small device scalars in bslam_context::misc (kMiscBytes, zeroed at creation).
+constexpr size_t kMiscActive = 0;           // int[4]: active-keyframe counters of the batched pose loop, one per in-flight iteration
+constexpr size_t kMiscPairCensus = 64;      // unsigned long long[2]: in-bounds / associated pairs (bslam_debug_count_pairs)
+constexpr size_t kMiscPcgScratch = 128;     // float[3]: PCGStep1's epsilon term {shared, sharded} and this rank's pair sum of alpha_d
+constexpr size_t kMiscPcgPair = 160;        // float[2]: {shared, sharded} of a multi-rank PCG dot product (pcg_final_sum)
+constexpr size_t kMiscDeleted = 192;        // uint32_t: surfels deleted by bslam_delete_surfels_and_update_radii
+constexpr size_t kMiscMinMaxDepth = 208;    // uint32_t[2]: bits of the min / max depth of bslam_compute_min_max_depth
+constexpr size_t kMiscCullStats = 224;      // unsigned long long[2]: (work slot, keyframe) pairs tested / visited by the pose kernel
+constexpr size_t kMiscBytes = 256;
 
-// A device slab that only ever grows.
-struct Slab {
+// A slab that only ever grows: device memory, or pinned host memory when kPinned.  Freed with its owner.
+template <bool kPinned>
+struct GrowingSlab {
   void* ptr = nullptr;
   size_t bytes = 0;
+  GrowingSlab() = default;
+  GrowingSlab(const GrowingSlab&) = delete;
+  GrowingSlab& operator=(const GrowingSlab&) = delete;
+  ~GrowingSlab() { release(); }
   int reserve(size_t need) {
     if (need <= bytes) return BSLAM_OK;
-    if (ptr) { hipError_t e = hipFree(ptr); (void)e; ptr = nullptr; bytes = 0; }
-    size_t want = need + need / 4 + 256;
-    hipError_t e = hipMalloc(&ptr, want);
-    if (e != hipSuccess) return fail(BSLAM_ERR_OUT_OF_MEMORY, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+    release();
+    const size_t want = need + need / 4 + 256;
+    const hipError_t e = kPinned ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : hipMalloc(&ptr, want);
+    if (e != hipSuccess) {
+      ptr = nullptr;
+      return fail(BSLAM_ERR_OUT_OF_MEMORY, "%s(%zu) failed: %s", kPinned ? "hipHostMalloc" : "hipMalloc", want, hipGetErrorString(e));
+    }
     bytes = want;
     return BSLAM_OK;
   }
-  void release() { if (ptr) { hipError_t e = hipFree(ptr); (void)e; } ptr = nullptr; bytes = 0; }
+  void release() {
+    if (ptr) { hipError_t e = kPinned ? hipHostFree(ptr) : hipFree(ptr); (void)e; }
+    ptr = nullptr;
+    bytes = 0;
+  }
 };
+using Slab = GrowingSlab<false>;
+using PinnedSlab = GrowingSlab<true>;
 
-struct PinnedSlab {
-  void* ptr = nullptr;
-  size_t bytes = 0;
-  int reserve(size_t need) {
-    if (need <= bytes) return BSLAM_OK;
-    if (ptr) { hipError_t e = hipHostFree(ptr); (void)e; ptr = nullptr; bytes = 0; }
-    size_t want = need + need / 4 + 256;
-    hipError_t e = hipHostMalloc(&ptr, want, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(BSLAM_ERR_OUT_OF_MEMORY, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e));
-    bytes = want;
-    return BSLAM_OK;
-  }
-  void release() { if (ptr) { hipError_t e = hipHostFree(ptr); (void)e; } ptr = nullptr; bytes = 0; }
+// What a cache built from a caller's surfel buffer was built from: its address, the surfel count and the pitch.
+struct SurfelKey {
+  const void* ptr = nullptr;
+  uint32_t size = 0;
+  size_t pitch = 0;
+  bool matches(const bslam_buffer2d* s, uint32_t n) const { return ptr == s->address && size == n && pitch == s->pitch; }
+  void set(const bslam_buffer2d* s, uint32_t n) { ptr = s->address; size = n; pitch = s->pitch; }
+  void clear() { ptr = nullptr; }
 };
 
 // Ring of pinned upload buffers: an API call takes the next slot for its small host->device uploads and
@@ -101,12 +116,9 @@ struct StagingRing {
     pending[cur] = true;
     return BSLAM_OK;
   }
-  void release() {
-    for (int i = 0; i < kSlots; ++i) {
-      if (done[i]) { hipError_t e = hipEventDestroy(done[i]); (void)e; done[i] = nullptr; }
-      slot[i].release();
-      pending[i] = false;
-    }
+  ~StagingRing() {
+    for (hipEvent_t e : done)
+      if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
   }
 };
 
@@ -127,8 +139,7 @@ struct bslam_context {
   int geom_kf_chunk = -1;    // geometry iteration: keyframes per launch (0: one launch for the whole list; -1: default = one launch)
   int intr_cells_owner = 0;  // 0: intrinsics step (zeroes per call), 1: PCG (kept zero between calls)
   size_t intr_cells_cells = 0;
-  bslam::PinnedSlab staging; // pinned host staging for tiny up/downloads
-  bslam::PinnedSlab staging2;
+  bslam::PinnedSlab staging2;       // pinned host memory of the results a call reads back (read_back)
   bslam::StagingRing upload_ring;   // keyframe table / pose state uploads
   hipEvent_t iter_done[4] = {};     // batched pose loop: one event per in-flight iteration (recorded behind its flag copy)
   hipEvent_t solve_done[4] = {};    // ... recorded on the BA stream behind the iteration's solve kernel
@@ -156,9 +167,7 @@ struct bslam_context {
   bslam::Slab bounds;        // float4[2 * granules]: bounding box of every granule of the sorted copy, rebuilt with it
   // what the sorted copy holds (prepare_surfels): PCGStep1 re-uses the copy PCGInit / the previous PCGStep1 of the same solve
   // made -- the surfels do not change inside a solve (BS/direct_ba_pcg.cc:339-425) -- every other call rebuilds it
-  const void* sorted_key_ptr = nullptr;
-  uint32_t sorted_key_size = 0;
-  size_t sorted_key_pitch = 0;
+  bslam::SurfelKey sorted_key;
   int sorted_key_rows = 0;
   bool sorted_key_bounds = false;
   uint64_t sorted_key_perm_serial = 0;   // the permutation the copy was made with
@@ -167,15 +176,11 @@ struct bslam_context {
   bslam::Slab vis;           // uint64[chunks][slots]: keyframes of a chunk (<= 64) a work slot visited in the last pose_accumulate launch
   bool culling = true;       // block-level frustum culling in the pair kernels (bslam_set_culling)
   int pose_list_min_keyframes = 64;   // batched pose loop: walk the list of unconverged keyframes from this many keyframes on (bslam_set_pose_keyframe_list; 0: never)
-  const void* perm_key_ptr = nullptr;
-  uint32_t perm_key_size = 0;
-  size_t perm_key_pitch = 0;
+  bslam::SurfelKey perm_key;
   hipEvent_t perm_ready = nullptr;   // recorded behind the sort that produced `perm`
   hipStream_t perm_stream = nullptr; // ... on this stream
   bool use_schedule = true;
-  const void* order_key_ptr = nullptr;
-  uint32_t order_key_size = 0;
-  size_t order_key_pitch = 0;
+  bslam::SurfelKey order_key;
   // kernel timing (bslam_profile_*)
   bool profiling = false;
   struct ProfEntry { hipEvent_t start, stop; int tag; };
@@ -186,6 +191,15 @@ struct bslam_context {
   bslam::Slab prof_counters; // unsigned long long[blocks][2]: work counters filled by the counting kernel variants while profiling
   size_t prof_counter_slots = 0;
   uint64_t prof_counter_base[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // counts carried over a resize of the per-block array
+  // The slabs free themselves; the device must be the context's (bslam_destroy).
+  ~bslam_context() {
+    for (hipEvent_t e : iter_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+    for (hipEvent_t e : solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+    if (perm_ready) { hipError_t err = hipEventDestroy(perm_ready); (void)err; }
+    if (copy_stream) { hipError_t err = hipStreamDestroy(copy_stream); (void)err; }
+    for (const ProfEntry& p : prof_pending) { hipError_t err = hipEventDestroy(p.start); err = hipEventDestroy(p.stop); (void)err; }
+    for (const auto& p : prof_pool) { hipError_t err = hipEventDestroy(p.first); err = hipEventDestroy(p.second); (void)err; }
+  }
 };
 
 namespace bslam {

@@ -8,21 +8,15 @@ int bslam_compute_ba_cost(
     int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t surfels_size, const bslam_buffer2d* surfels,
     const bslam_buffer2d* active_surfels, float* cost, uint32_t* counts, bslam_allreduce_fn allreduce, void* allreduce_user) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
-  if (keyframe_count < 0 || (keyframe_count > 0 && !keyframes) || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad keyframe list");
+  if (!color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "color_camera is null");
   if (!cost) return fail(BSLAM_ERR_INVALID_ARGUMENT, "cost is null");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  if (active_surfels && (!active_surfels->address || surfels_size > (uint32_t)active_surfels->width))
-    return fail(BSLAM_ERR_INVALID_ARGUMENT, "active_surfels is null or narrower than surfels_size %u", surfels_size);
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size, active_surfels);
+  if (rc) return rc;
   if (keyframe_count == 0) return BSLAM_OK;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, use_descriptor_residuals != 0, keyframe_count, keyframes, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  if ((rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, use_descriptor_residuals != 0,
+                                 surfels_size, surfels, &c, active_surfels))) return rc;
   const size_t row_floats = (size_t)keyframe_count * kCostCols;
   const size_t out_bytes = row_floats * sizeof(float) + (size_t)keyframe_count * 2 * sizeof(uint32_t);
   if ((rc = ctx->coeffs.reserve(out_bytes))) return rc;
@@ -73,10 +67,8 @@ int bslam_compute_ba_cost(
   } else if (exchange) {
     if ((rc = exchange_sum(ctx, stream, d_rows, row_floats))) return rc;
   }
-  if ((rc = ctx->staging2.reserve(out_bytes))) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, d_rows, out_bytes, hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-  const float* rows = (const float*)ctx->staging2.ptr;
+  const float* rows = nullptr;
+  if ((rc = read_back(ctx, stream, (const float*)d_rows, out_bytes / sizeof(float), &rows))) return rc;
   const uint32_t* exact = (const uint32_t*)(rows + row_floats);
   for (int k = 0; k < keyframe_count; ++k) {
     const float* row = rows + (size_t)k * kCostCols;
@@ -97,15 +89,10 @@ int bslam_debug_ba_cost_descriptor_residuals(
     const bslam_depth_params* depth_params, const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, float* out) {
   hipStream_t stream = (hipStream_t)stream_;
   if (surfels_size == 0) return BSLAM_OK;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!keyframe || !out || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, true, 1, keyframe, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, 1, keyframe, true, surfels_size, surfels, &c);
+  if (rc) return rc;
   hipLaunchKernelGGL(ba_cost_descriptor_probe_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr,
                      surfel_rows(surfels, surfels_size), out);
   BSLAM_HIP_TRY(hipGetLastError());

@@ -54,20 +54,19 @@ int bslam_optimize_intrinsics(
     bslam_camera4f* out_color_camera, bslam_camera4f* out_depth_camera, float* a) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!optimize_depth_intrinsics && !optimize_color_intrinsics) return fail(BSLAM_ERR_INVALID_ARGUMENT, "nothing to optimise");   // BS/kernel_opt_intrinsics.cc:53
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
   if (rc) return rc;
   if (surfels_size == 0 && !has_exchange(ctx)) return BSLAM_OK;                                                                       // :55-57 (an empty shard still takes part in the exchange)
   if (keyframe_count <= 0 || !keyframes || !color_camera || !a) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument / no keyframes");
   if (optimize_depth_intrinsics && !out_depth_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_depth_camera is null");
   if (optimize_color_intrinsics && !out_color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_color_camera is null");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, optimize_color_intrinsics != 0, keyframe_count, keyframes, &table))) return rc;
-  CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  c.a = *a;   // the caller's current value (DirectBA passes depth_params_.a by pointer, BS/direct_ba_alternating.cc:591)
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  // the caller's current a (DirectBA passes depth_params_.a by pointer, BS/direct_ba_alternating.cc:591), in place before the
+  // upload: the derived pixel records are built from it
+  bslam_depth_params dp = *depth_params;
+  dp.a = *a;
+  CamConsts c;
+  if ((rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, &dp, keyframe_count, keyframes, optimize_color_intrinsics != 0,
+                                 surfels_size, surfels, &c))) return rc;
 
   const int cw = depth_params->cfactor_buffer.width;
   const int ncells = ((depth_camera->width - 1) / depth_params->sparse_surfel_cell_size + 1) *
@@ -123,9 +122,6 @@ int bslam_optimize_intrinsics(
     }
   }
 
-  if ((rc = ctx->staging2.reserve(kIntrRow * sizeof(float)))) return rc;
-  float* h = (float*)ctx->staging2.ptr;
-
   if (optimize_depth_intrinsics) {
     // Schur complement: A -= B D^-1 B^T, b1 -= B D^-1 b2 (:110-118)
     hipLaunchKernelGGL(intrinsics_intermediate_kernel, dim3((unsigned)cell_blocks), dim3(256), 0, stream, cells, partial);
@@ -133,8 +129,8 @@ int bslam_optimize_intrinsics(
     hipLaunchKernelGGL(intrinsics_sum_rows_kernel, dim3(1), dim3(64), 0, stream, (const float*)partial, cell_blocks, sums, -1.f, 1);
     BSLAM_HIP_TRY(hipGetLastError());
   }
-  BSLAM_HIP_TRY(hipMemcpyAsync(h, sums, kIntrRow * sizeof(float), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+  const float* h = nullptr;
+  if ((rc = read_back(ctx, stream, (const float*)sums, kIntrRow, &h))) return rc;
 
   if (optimize_depth_intrinsics) {
     float A[15], b1[5], x1[5];
@@ -150,17 +146,17 @@ int bslam_optimize_intrinsics(
     const float new_cy = -(new_fy * (c.cy_inv - x1[3])) + 0.5f;
     *out_depth_camera = bslam_camera4f{new_fx, new_fy, new_cx, new_cy, depth_camera->width, depth_camera->height};
     *a -= x1[4];
-    std::memcpy(h, x1, sizeof(x1));
-    BSLAM_HIP_TRY(hipMemcpyAsync(x1_dev, h, sizeof(x1), hipMemcpyHostToDevice, stream));
+    float* x1_stage = (float*)ctx->staging2.ptr;
+    std::memcpy(x1_stage, x1, sizeof(x1));
+    BSLAM_HIP_TRY(hipMemcpyAsync(x1_dev, x1_stage, sizeof(x1), hipMemcpyHostToDevice, stream));
     hipLaunchKernelGGL(intrinsics_pixel_update_kernel, dim3((unsigned)cell_blocks), dim3(256), 0, stream, cells, (const float*)x1_dev,
                        (uint8_t*)depth_params->cfactor_buffer.address, (uint32_t)depth_params->cfactor_buffer.pitch, cw);
     BSLAM_HIP_TRY(hipGetLastError());
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));              // h is re-used below / by the next call
+    BSLAM_HIP_TRY(hipStreamSynchronize(stream));              // the staging is re-used below / by the next call
     ctx->records_signature.clear();                           // cfactor content changed
   }
   if (optimize_color_intrinsics) {
-    BSLAM_HIP_TRY(hipMemcpyAsync(h, sums, kIntrRow * sizeof(float), hipMemcpyDeviceToHost, stream));
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+    if ((rc = read_back(ctx, stream, (const float*)sums, kIntrRow, &h))) return rc;
     float H[10], b[4], x[4];
     std::memcpy(H, h + 20, sizeof(H));
     std::memcpy(b, h + 30, sizeof(b));

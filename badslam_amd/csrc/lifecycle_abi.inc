@@ -3,23 +3,19 @@
 namespace bslam {
 
 static SurfelRowsAll surfel_rows_all(const bslam_buffer2d* s) {
-  auto row = [&](int r) { return (float*)((uint8_t*)s->address + (size_t)r * s->pitch); };
   SurfelRowsAll o;
-  o.x = row(BSLAM_SURFEL_X); o.y = row(BSLAM_SURFEL_Y); o.z = row(BSLAM_SURFEL_Z);
-  o.normal = (uint32_t*)row(BSLAM_SURFEL_NORMAL);
-  o.radius_squared = row(BSLAM_SURFEL_RADIUS_SQUARED);
-  o.color = (uint32_t*)row(BSLAM_SURFEL_COLOR);
-  o.d1 = row(BSLAM_SURFEL_DESCRIPTOR1); o.d2 = row(BSLAM_SURFEL_DESCRIPTOR2);
+  o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
+  o.normal = (uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
+  o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
+  o.color = (uint32_t*)surfel_row(s, BSLAM_SURFEL_COLOR);
+  o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
   return o;
 }
 
 static int make_kf_images(const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, const bslam_keyframe_view* v,
                           bool need_radius, bool need_color, KfImages* out) {
-  int rc = check_image(&v->depth, depth_camera, 2, "keyframe depth");
+  int rc = check_keyframe_images(*v, depth_camera, color_camera, need_color, need_radius);
   if (rc) return rc;
-  if ((rc = check_image(&v->normals, depth_camera, 2, "keyframe normals"))) return rc;
-  if (need_radius && (rc = check_image(&v->radius, depth_camera, 2, "keyframe radius"))) return rc;
-  if (need_color && (rc = check_image(&v->color, color_camera, 4, "keyframe color"))) return rc;
   std::memset(out, 0, sizeof(*out));
   out->depth = (const uint8_t*)v->depth.address;     out->depth_pitch = (uint32_t)v->depth.pitch;
   out->normals = (const uint8_t*)v->normals.address; out->normals_pitch = (uint32_t)v->normals.pitch;
@@ -74,11 +70,10 @@ static int device_scan(hipStream_t stream, int kind, const void* in, uint32_t n,
 }
 
 static int read_u32(bslam_context* ctx, hipStream_t stream, const uint32_t* dev, uint32_t* host_out) {
-  int rc = ctx->staging2.reserve(64);
+  const uint32_t* h = nullptr;
+  int rc = read_back(ctx, stream, dev, 1, &h);
   if (rc) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, dev, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-  *host_out = *(const uint32_t*)ctx->staging2.ptr;
+  *host_out = *h;
   return BSLAM_OK;
 }
 
@@ -120,10 +115,9 @@ int bslam_determine_supporting_surfels_and_merge(
     bslam_context* ctx, void* stream_, float merge_dist_factor, const bslam_camera4f* depth_camera, const bslam_depth_params* depth_params,
     const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* surfel_count) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!keyframe || !surfel_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
+  if (rc) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   KfImages kf;
   if ((rc = make_kf_images(depth_camera, nullptr, keyframe, false, false, &kf))) return rc;
@@ -144,11 +138,10 @@ int bslam_create_surfels_for_keyframe(
     int covis_count, const bslam_keyframe_view* covis_keyframes, const bslam_mat3x4* covis_T_frame,
     uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* new_surfel_count) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
-  if (rc) return rc;
   if (!keyframe || !color_camera || !global_T_frame || !new_surfel_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (covis_count < 0 || (covis_count > 0 && filter_new_surfels && (!covis_keyframes || !covis_T_frame))) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad co-visibility list");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
+  if (rc) return rc;
   *new_surfel_count = 0;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   KfImages kf;
@@ -207,19 +200,15 @@ int bslam_delete_surfels_and_update_radii(
     bslam_context* ctx, void* stream_, int min_observation_count, const bslam_camera4f* depth_camera, const bslam_depth_params* depth_params,
     int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t* surfel_count, uint32_t surfels_size, const bslam_buffer2d* surfels) {
   hipStream_t stream = (hipStream_t)stream_;
-  int rc = check_common(ctx, depth_camera, depth_params, surfels);
+  if (!surfel_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
   if (rc) return rc;
-  if (!surfel_count || keyframe_count < 0 || (keyframe_count > 0 && !keyframes)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
+  if (keyframe_count < 0 || (keyframe_count > 0 && !keyframes)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad keyframe list");
   if (surfels_size == 0) return BSLAM_OK;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, nullptr, false, keyframe_count, keyframes, &table, true))) return rc;
-  if (table.empty()) { table.resize(1); std::memset(&table[0], 0, sizeof(KfDev)); }
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
-  if ((rc = ctx->misc.reserve(256))) return rc;
-  uint32_t* counter = (uint32_t*)((uint8_t*)ctx->misc.ptr + 192);
+  CamConsts c;
+  if ((rc = setup_keyframe_table(ctx, stream, nullptr, depth_camera, depth_params, keyframe_count, keyframes, false, surfels_size, surfels, &c,
+                                 nullptr, true))) return rc;
+  uint32_t* counter = (uint32_t*)((uint8_t*)ctx->misc.ptr + kMiscDeleted);
   BSLAM_HIP_TRY(hipMemsetAsync(counter, 0, sizeof(uint32_t), stream));
   SurfelWork work;   // per-surfel order for >= 4 keyframes: sorted copy of position + normal, granule boxes for the culling
   if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, 1, keyframe_count, &work, false))) return rc;
@@ -246,7 +235,7 @@ int bslam_compact_surfels(bslam_context* ctx, void* stream_, uint32_t surfel_cou
   if (rc) return rc;
   const uint32_t free_spot_count = n - surfel_count;
   const dim3 grid((n + 255) / 256), block(256);
-  const float* x = (const float*)((const uint8_t*)surfels->address + (size_t)BSLAM_SURFEL_X * surfels->pitch);
+  const float* x = surfel_row(surfels, BSLAM_SURFEL_X);
   uint32_t* invalid = sc.cell_of;   // [n]
   hipLaunchKernelGGL(compact_flag_kernel, grid, block, 0, stream, n, x, invalid);
   BSLAM_HIP_TRY(hipGetLastError());

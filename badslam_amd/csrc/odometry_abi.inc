@@ -71,10 +71,9 @@ static int run_pair_kernel(bslam_context* ctx, hipStream_t stream, bool coeffs, 
   BSLAM_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(pose_reduce_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
   BSLAM_HIP_TRY(hipGetLastError());
-  if ((rc = ctx->staging2.reserve(kRow * sizeof(float)))) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, kRow * sizeof(float), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // results valid on return (BS/kernel_opt_pose.cc:189-191)
-  std::memcpy(row_out, ctx->staging2.ptr, kRow * sizeof(float));
+  const float* h = nullptr;
+  if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, kRow, &h))) return rc;   // results valid on return (BS/kernel_opt_pose.cc:189-191)
+  std::memcpy(row_out, h, kRow * sizeof(float));
   return BSLAM_OK;
 }
 
@@ -280,10 +279,8 @@ int bslam_accumulate_pose_coeffs_from_images_batched(
   BSLAM_HIP_TRY(hipGetLastError());
   hipLaunchKernelGGL(pose_reduce_final_kernel, dim3((unsigned)pair_count), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
   BSLAM_HIP_TRY(hipGetLastError());
-  if ((rc = ctx->staging2.reserve((size_t)pair_count * kRow * sizeof(float)))) return rc;
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, ctx->coeffs.ptr, (size_t)pair_count * kRow * sizeof(float), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-  const float* rows_out = (const float*)ctx->staging2.ptr;
+  const float* rows_out = nullptr;
+  if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, (size_t)pair_count * kRow, &rows_out))) return rc;
   for (int p = 0; p < pair_count; ++p) {
     std::memcpy(H + 21 * p, rows_out + (size_t)p * kRow, 21 * sizeof(float));
     std::memcpy(b + 6 * p, rows_out + (size_t)p * kRow + 21, 6 * sizeof(float));

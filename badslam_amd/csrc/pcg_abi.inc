@@ -46,10 +46,6 @@ static void launch_pcg_surfel_kernel(Kernel kernel_tt, Kernel kernel_tf, Kernel 
   hipLaunchKernelGGL(k, grid, dim3(kPcgThreads), 0, stream, c, kfs, kf_count, sc, rows, P, pp, pg);
 }
 
-static int call_allreduce(bslam_context* ctx, hipStream_t stream, float* device_buffer, size_t count) {
-  return exchange_sum(ctx, stream, device_buffer, count);
-}
-
 // Deterministic dot product tail: the two runs of block partials (shared | sharded) -> *out = shared + sum over
 // ranks of sharded.  `pair` (2 floats of device scratch) receives {shared, sharded} when a hook is set.
 static int pcg_final_sum(bslam_context* ctx, hipStream_t stream, const float* partial, int sb, int lb, float* out, float* pair) {
@@ -60,7 +56,7 @@ static int pcg_final_sum(bslam_context* ctx, hipStream_t stream, const float* pa
   }
   hipLaunchKernelGGL(pcg_final_sum_kernel, dim3(1), dim3(256), 0, stream, partial, sb, lb, pair, 0);
   BSLAM_HIP_TRY(hipGetLastError());
-  int rc = call_allreduce(ctx, stream, pair + 1, 1);
+  int rc = exchange_sum(ctx, stream, pair + 1, 1);
   if (rc) return rc;
   hipLaunchKernelGGL(pcg_add2_kernel, dim3(1), dim3(1), 0, stream, (const float*)pair, out);
   BSLAM_HIP_TRY(hipGetLastError());
@@ -82,7 +78,7 @@ static int pcg_exchange_shared(bslam_context* ctx, hipStream_t stream, const Pcg
   }
   float* tail = stage + (size_t)shared * (v1 ? 2 : 1);
   if (extra_count) BSLAM_HIP_TRY(hipMemcpyAsync(tail, extra, sizeof(float) * extra_count, hipMemcpyDeviceToDevice, stream));
-  if ((rc = call_allreduce(ctx, stream, stage, count))) return rc;
+  if ((rc = exchange_sum(ctx, stream, stage, count))) return rc;
   if (shared) {
     hipLaunchKernelGGL(pcg_unpack_shared_kernel, dim3(blocks), dim3(256), 0, stream, v0, v1, P.unknown_count, P.shard_begin, P.shard_end, (const float*)stage);
     BSLAM_HIP_TRY(hipGetLastError());
@@ -95,10 +91,7 @@ static int pcg_surfel_pass(bslam_context* ctx, hipStream_t stream, bool step1, c
                            const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera, const bslam_depth_params* dp,
                            int keyframe_count, const bslam_keyframe_view* keyframes, uint32_t surfels_size, const bslam_buffer2d* surfels,
                            const bslam_pcg_vectors* v) {
-  int rc = check_common(ctx, depth_camera, dp, surfels);
-  if (rc) return rc;
   if (keyframe_count <= 0 || !keyframes || !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need at least one keyframe");
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
   const uint32_t per = layout->use_descriptor_residuals ? 3u : 1u;
   if (layout->optimize_geometry && (uint64_t)layout->surfel_unknown_start_index + (uint64_t)per * surfels_size > layout->unknown_count)
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "unknown layout too small for %u surfels", surfels_size);
@@ -106,11 +99,10 @@ static int pcg_surfel_pass(bslam_context* ctx, hipStream_t stream, bool step1, c
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "gauge keyframe %d out of range", layout->gauge_keyframe_id);
   for (int k = 0; k < keyframe_count; ++k)
     if (keyframes[k].id != k) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the PCG path needs keyframe ids 0..K-1 in list order (BS/direct_ba_pcg.cc:138-143)");
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  std::vector<KfDev> table;
-  if ((rc = build_kf_table(depth_camera, color_camera, layout->use_descriptor_residuals != 0, keyframe_count, keyframes, &table))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, dp);
-  if ((rc = upload_kf_table(ctx, stream, table, c))) return rc;
+  CamConsts c;
+  int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, dp, keyframe_count, keyframes, layout->use_descriptor_residuals != 0,
+                                surfels_size, surfels, &c);
+  if (rc) return rc;
   PcgParams P = make_pcg_params(layout, v);
   if (layout->optimize_depth_intrinsics) {
     // fp64 scratch for the per-cell sums; zeroed on first use and left zero by pcg_cf_flush_kernel
@@ -168,7 +160,7 @@ static int pcg_surfel_pass(bslam_context* ctx, hipStream_t stream, bool step1, c
     BSLAM_HIP_TRY(hipGetLastError());
   }
   // device scratch: [0..1] eps {shared, sharded}, [2] this rank's pair sum of alpha_d
-  float* scratch = (float*)((uint8_t*)ctx->misc.ptr + 128);
+  float* scratch = (float*)((uint8_t*)ctx->misc.ptr + kMiscPcgScratch);
   if (step1) {
     // epsilon term (added once per keyframe, quirk Q7, BS/kernel_pcg.cu:1102-1113)
     const int sb = (int)vec_shared_blocks(P), lb = (int)vec_local_blocks(P);
@@ -224,11 +216,10 @@ int bslam_pcg_init2(bslam_context* ctx, void* stream_, const bslam_pcg_layout* l
   const PcgParams P = make_pcg_params(layout, v);
   const int sb = (int)vec_shared_blocks(P), lb = (int)vec_local_blocks(P);
   if ((rc = ctx->coeffs.reserve(((size_t)sb + lb + 8) * sizeof(float)))) return rc;
-  if ((rc = ctx->misc.reserve(256))) return rc;
   float* vpart = (float*)ctx->coeffs.ptr;
   hipLaunchKernelGGL(pcg_init2_kernel, dim3((unsigned)(sb + lb)), dim3(kVecThreads), 0, stream, P, a, vpart);
   BSLAM_HIP_TRY(hipGetLastError());
-  return pcg_final_sum(ctx, stream, vpart, sb, lb, v->alpha_n, (float*)((uint8_t*)ctx->misc.ptr + 160));
+  return pcg_final_sum(ctx, stream, vpart, sb, lb, v->alpha_n, (float*)((uint8_t*)ctx->misc.ptr + kMiscPcgPair));
 }
 
 int bslam_pcg_step1(bslam_context* ctx, void* stream_, const bslam_pcg_layout* layout,
@@ -254,16 +245,14 @@ int bslam_pcg_step2(bslam_context* ctx, void* stream_, const bslam_pcg_layout* l
   const PcgParams P = make_pcg_params(layout, v);
   const int sb = (int)vec_shared_blocks(P), lb = (int)vec_local_blocks(P);
   if ((rc = ctx->coeffs.reserve(((size_t)sb + lb + 8) * sizeof(float)))) return rc;
-  if ((rc = ctx->misc.reserve(256))) return rc;
   float* vpart = (float*)ctx->coeffs.ptr;
   hipLaunchKernelGGL(pcg_step2_kernel, dim3((unsigned)(sb + lb)), dim3(kVecThreads), 0, stream, P, vpart);
   BSLAM_HIP_TRY(hipGetLastError());
-  if ((rc = pcg_final_sum(ctx, stream, vpart, sb, lb, v->beta_n, (float*)((uint8_t*)ctx->misc.ptr + 160)))) return rc;
+  if ((rc = pcg_final_sum(ctx, stream, vpart, sb, lb, v->beta_n, (float*)((uint8_t*)ctx->misc.ptr + kMiscPcgPair)))) return rc;
   if (beta_n_host) {
-    if ((rc = ctx->staging2.reserve(64))) return rc;
-    BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, v->beta_n, sizeof(float), hipMemcpyDeviceToHost, stream));
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // BS/direct_ba_pcg.cc:441-443
-    *beta_n_host = *(const float*)ctx->staging2.ptr;
+    const float* h = nullptr;
+    if ((rc = read_back(ctx, stream, (const float*)v->beta_n, 1, &h))) return rc;   // BS/direct_ba_pcg.cc:441-443
+    *beta_n_host = *h;
   }
   return BSLAM_OK;
 }
@@ -286,7 +275,8 @@ int bslam_update_surfels_from_pcg_delta(bslam_context* ctx, void* stream_, uint3
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !surfels || !pcg_delta) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (surfels_size == 0) return BSLAM_OK;   // BS/kernel_pcg.cu:1343-1345
-  if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
+  int rc = check_surfels_size(surfels, surfels_size);
+  if (rc) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   SurfelRowsRW s = surfel_rows_rw(surfels, nullptr, surfels_size);
   const dim3 grid((surfels_size + 255) / 256), block(256);

@@ -94,18 +94,17 @@ int bslam_compute_min_max_depth(bslam_context* ctx, void* stream_, const bslam_b
   int rc = make_img(depth_buffer, 2, "depth", &in);
   if (rc) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  if ((rc = ctx->misc.reserve(256))) return rc;
   if ((rc = ctx->staging2.reserve(64))) return rc;
-  uint32_t* result = (uint32_t*)((uint8_t*)ctx->misc.ptr + 208);
+  uint32_t* result = (uint32_t*)((uint8_t*)ctx->misc.ptr + kMiscMinMaxDepth);
   const uint32_t init[2] = {0x7f800000u, 0u};   // +inf, 0 (ComputeMinMaxDepthCUDA_InitializeBuffers)
   std::memcpy(ctx->staging2.ptr, init, sizeof(init));
   BSLAM_HIP_TRY(hipMemcpyAsync(result, ctx->staging2.ptr, sizeof(init), hipMemcpyHostToDevice, stream));
   hipLaunchKernelGGL(min_max_depth_kernel, image_grid(in), dim3(256), 0, stream, raw_to_float_depth, in, result);
   BSLAM_HIP_TRY(hipGetLastError());
-  BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, result, sizeof(init), hipMemcpyDeviceToHost, stream));
-  BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // results valid on return (BS/cuda_depth_processing.cu:455-464)
-  std::memcpy(min_depth, ctx->staging2.ptr, 4);
-  std::memcpy(max_depth, (const uint8_t*)ctx->staging2.ptr + 4, 4);
+  const uint32_t* h = nullptr;
+  if ((rc = read_back(ctx, stream, (const uint32_t*)result, 2, &h))) return rc;   // results valid on return (BS/cuda_depth_processing.cu:455-464)
+  std::memcpy(min_depth, h, 4);
+  std::memcpy(max_depth, h + 1, 4);
   return BSLAM_OK;
 }
 

@@ -14,6 +14,10 @@
  *   - all image / surfel memory is owned by the caller and lives in device memory;
  *   - small results written through host pointers are valid on return (the function
  *     synchronises the stream, as BS/kernel_opt_pose.cc:96 does);
+ *   - the calls on one context are issued on one stream, or the caller orders them
+ *     (events, synchronisation): a context keeps device state between calls (keyframe
+ *     table, derived images, surfel work orders, scratch) that a later call re-uses on
+ *     the strength of stream order alone;
  *   - return value: 0 on success, negative bslam_status on error.  The reference
  *     aborts via CHECK()/LOG(FATAL) (BS/kernel_opt_pose.cc:58-61); we return the
  *     code and keep the message in bslam_last_error().

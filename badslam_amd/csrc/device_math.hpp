@@ -242,6 +242,18 @@ __device__ __forceinline__ float depth_weight(float r) { return 1.f * tukey_weig
 __device__ __forceinline__ float weighted_depth_residual(float r) { return 1.f * tukey_residual(r, 1.f * kDepthTukey); }
 __device__ __forceinline__ float objective_depth_term(float r) { return tukey_residual_accurate(r, kDepthTukey); }   // bslam_compute_ba_cost
 __device__ __forceinline__ float desc_weight(float r) { return 1.f * kDescWeight * huber_weight(r, kDescHuber); }
+// desc_weight of both residuals of a pair, same bits.  Near convergence |r| < kDescHuber for almost every pair, where the weight
+// is the constant kDescWeight: the reciprocal, its two multiplies and the select are taken only when some lane of the wave needs
+// them (a wave-uniform branch; call it where the wave's lanes have a common exec mask or not, the ballot covers the active ones).
+__device__ __forceinline__ void desc_weights_pair(float r1, float r2, float* w1, float* w2) {
+  float a = 1.f * kDescWeight * 1.f, b = a;
+  if (__ballot(!(fabsf(r1) < kDescHuber) || !(fabsf(r2) < kDescHuber)) != 0) {
+    a = desc_weight(r1);
+    b = desc_weight(r2);
+  }
+  *w1 = a;
+  *w2 = b;
+}
 __device__ __forceinline__ float weighted_desc_residual(float r) { return 1.f * kDescWeight * huber_residual(r, kDescHuber); }
 
 // float -> int, truncating and saturating (v_cvt_i32_f32; CUDA's cvt.rzi.s32.f32 behaves the same)
@@ -732,6 +744,53 @@ __device__ __forceinline__ void descriptor_pose_jacobian(float gx, float gy, f3 
     J[4] = -((ls.x * ls.x + ls_z_sq) * gx + ls_x_y * gy) * inv_ls_z_sq;
     J[5] = -(ls.x * gy - ls.y * gx) * inv_ls_z;
   }
+}
+// Normal equations of the TWO descriptor residuals of a pair in one rank-two update (the pose kernel's form).  Both rows of
+// descriptor_pose_jacobian are built from the same point ls; with u = ls.x / ls.z, v = ls.y / ls.z, iz = 1 / ls.z its six
+// formulas are J_r = gx_r a0 + gy_r a1,
+//   a0 = [-iz,   0, u iz, u v,     -(1 + u^2),  v],
+//   a1 = [  0, -iz, v iz, 1 + v^2, -u v,       -u],
+// so  sum_r w_r J_r^T J_r = A^T G A  and  sum_r w_r r_r J_r = A^T h  with A = [a0; a1] (2 x 6),
+// G = sum_r w_r g_r g_r^T (2 x 2 symmetric), h = sum_r w_r r_r g_r.  79 instructions against the 96 of two Jacobians and two
+// accumulate_h_b (the zeros of A's first two columns are spelled out: columns 0, 1 of B = G A and rows 0, 1 of A^T B take
+// one factor each).  acc: 21 upper-triangle H entries, row-major, then 6 b entries, as accumulate_h_b.
+__device__ __forceinline__ void accumulate_h_b_desc_pair(float u, float v, float iz, float gx1, float gy1, float r1, float w1,
+                                                         float gx2, float gy2, float r2, float w2, float* acc) {
+#pragma clang fp contract(fast)
+  const float uv = u * v;
+  const float a0[4] = {u * iz, uv, -(1.f + u * u), v};   // columns 2 .. 5
+  const float a1[4] = {v * iz, 1.f + v * v, -uv, -u};
+  const float wx1 = w1 * gx1, wy1 = w1 * gy1, wx2 = w2 * gx2, wy2 = w2 * gy2;
+  const float gxx = wx1 * gx1 + wx2 * gx2, gxy = wx1 * gy1 + wx2 * gy2, gyy = wy1 * gy1 + wy2 * gy2;
+  const float h0 = wx1 * r1 + wx2 * r2, h1 = wy1 * r1 + wy2 * r2;
+  const float niz = -iz;
+  float b0[6], b1[6];   // B = G A
+  b0[0] = niz * gxx; b0[1] = niz * gxy;
+  b1[0] = b0[1];     b1[1] = niz * gyy;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    b0[2 + c] = gxx * a0[c] + gxy * a1[c];
+    b1[2 + c] = gxy * a0[c] + gyy * a1[c];
+  }
+  // H += A^T B (upper triangle)
+#pragma unroll
+  for (int c = 0; c < 6; ++c) acc[c] = __builtin_fmaf(niz, b0[c], acc[c]);
+#pragma unroll
+  for (int c = 1; c < 6; ++c) acc[5 + c] = __builtin_fmaf(niz, b1[c], acc[5 + c]);
+  int idx = 11;
+#pragma unroll
+  for (int r = 2; r < 6; ++r) {
+#pragma unroll
+    for (int c = r; c < 6; ++c) {
+      acc[idx] = __builtin_fmaf(a0[r - 2], b0[c], __builtin_fmaf(a1[r - 2], b1[c], acc[idx]));
+      ++idx;
+    }
+  }
+  // b += A^T h
+  acc[21] = __builtin_fmaf(niz, h0, acc[21]);
+  acc[22] = __builtin_fmaf(niz, h1, acc[22]);
+#pragma unroll
+  for (int r = 2; r < 6; ++r) acc[21 + r] = __builtin_fmaf(a0[r - 2], h0, __builtin_fmaf(a1[r - 2], h1, acc[21 + r]));
 }
 // Descriptor residual wrt. a surfel move along its normal (BS/kernel_opt_geometry.cu:175-189, BS/kernel_pcg.cu:364-372):
 // rn = normal in the frame, ls = position in the frame; the gradient (gx, gy) is multiplied by (fx, fy) here (the PCG kernels

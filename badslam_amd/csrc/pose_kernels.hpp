@@ -258,10 +258,12 @@ __device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* 
           float r1, rr2, gx1, gy1, gx2, gy2;
           descriptor_samples_finish(kf, c, ds, st[12 * kSurfels], st[13 * kSurfels], c.desc_gx_scale, c.desc_gy_scale, [&](f2 (&pts)[3]) {
             pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; }, &r1, &rr2, &gx1, &gy1, &gx2, &gy2);   // gradients times cfx, cfy
-          descriptor_pose_jacobian(gx1, gy1, p.local, J);
-          accumulate_h_b(r1, desc_weight(r1), J, acc);
-          descriptor_pose_jacobian(gx2, gy2, p.local, J);
-          accumulate_h_b(rr2, desc_weight(rr2), J, acc);
+          // both rows in one rank-two update (accumulate_h_b_desc_pair); u, v, iz from the 1-ulp reciprocal the projection
+          // starts from (the same v_rcp_f32: no second one, and nothing more to carry across the gathers than p.local)
+          float w1, w2;
+          desc_weights_pair(r1, rr2, &w1, &w2);
+          const float iz = rrcp(p.local.z);
+          accumulate_h_b_desc_pair(p.local.x * iz, p.local.y * iz, iz, gx1, gy1, r1, w1, gx2, gy2, rr2, w2, acc);
           if constexpr (kCost) acc[kRowCost] += weighted_desc_residual(r1);        // quirk Q1: only the first residual is counted
           got_desc = true;
         }
@@ -395,6 +397,33 @@ __global__ __launch_bounds__(64) void wave_column_sums_probe_kernel(const float*
   wave_column_sums_owner<kLive, kCols>(&col, &writer);
   const float total = wave_column_sums_lds<kLive, kCols>(v, tile);
   if (writer) out[col] = total;
+}
+
+// bslam_debug_desc_pair: the descriptor normal equations of one pair, per point [ls(3), gx1, gy1, r1, gx2, gy2, r2] ->
+// [27 columns through accumulate_h_b_desc_pair with desc_weights_pair, 27 columns through two descriptor_pose_jacobian +
+// accumulate_h_b with desc_weight, w1, w2 of desc_weights_pair, w1, w2 of desc_weight]; a wave holds 64 consecutive points.
+constexpr int kDescPairProbeIn = 9, kDescPairProbeOut = 2 * 27 + 4;
+__global__ __launch_bounds__(256) void desc_pair_probe_kernel(int count, const float* __restrict__ in, float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const float* a = in + (size_t)i * kDescPairProbeIn;
+  float* o = out + (size_t)i * kDescPairProbeOut;
+  const f3 ls = mk3(a[0], a[1], a[2]);
+  const float gx1 = a[3], gy1 = a[4], r1 = a[5], gx2 = a[6], gy2 = a[7], r2 = a[8];
+  float pair[kRow], rows[kRow], J[6];
+#pragma unroll
+  for (int k = 0; k < kRow; ++k) pair[k] = rows[k] = 0.f;
+  float w1, w2;
+  desc_weights_pair(r1, r2, &w1, &w2);
+  const float iz = rrcp(ls.z);
+  accumulate_h_b_desc_pair(ls.x * iz, ls.y * iz, iz, gx1, gy1, r1, w1, gx2, gy2, r2, w2, pair);
+  descriptor_pose_jacobian(gx1, gy1, ls, J);
+  accumulate_h_b(r1, desc_weight(r1), J, rows);
+  descriptor_pose_jacobian(gx2, gy2, ls, J);
+  accumulate_h_b(r2, desc_weight(r2), J, rows);
+#pragma unroll
+  for (int k = 0; k < 27; ++k) { o[k] = pair[k]; o[27 + k] = rows[k]; }
+  o[54] = w1; o[55] = w2; o[56] = desc_weight(r1); o[57] = desc_weight(r2);
 }
 
 // Sums the partial rows [row][32] of one image pair (odometry_abi.inc) in a fixed order, in two stages so that the sum is

@@ -431,6 +431,13 @@ int bslam_debug_jacobians(bslam_context* ctx, void* stream, int kind, int count,
  * configuration keep the value they had.  (live_columns, columns_per_round) must be one of the kernels' configurations:
  * (27 | 28, 4 | 8), (6, 4), (12, 4). */
 int bslam_debug_wave_column_sums(bslam_context* ctx, void* stream, int live_columns, int columns_per_round, const float* in, float* out);
+/* Test probe of the photometric pose kernel's descriptor normal equations: for `count` points (HOST in / out, valid on return)
+ *   [ls(3), gx1, gy1, r1, gx2, gy2, r2]  (9 floats: surfel position in the frame, the two residuals with their gradients times fx, fy)
+ *   -> [H upper triangle (21) and b (6) of the pair through the rank-two form (accumulate_h_b_desc_pair, weights from the
+ *       wave-uniform Huber path), the same 27 numbers through two descriptor Jacobian rows and two rank-one updates,
+ *       w1, w2 of the wave-uniform Huber path, w1, w2 of the per-lane form]  (58 floats).
+ * A wave evaluates 64 consecutive points, so the Huber path taken depends on the residuals of a point's group of 64. */
+int bslam_debug_desc_pair(bslam_context* ctx, void* stream, int count, const float* in, float* out);
 
 /* ------------------------------------------------------------------------- */
 /* Surfel lifecycle                                          */

@@ -38,12 +38,14 @@ static PcgParams make_pcg_params(const bslam_pcg_layout* l, const bslam_pcg_vect
   return P;
 }
 
-template <typename Kernel>
-static void launch_pcg_surfel_kernel(Kernel kernel_tt, Kernel kernel_tf, Kernel kernel_ft, Kernel kernel_tt_i, Kernel kernel_tf_i, Kernel kernel_ft_i,
-                                     bool depth, bool desc, bool intr, dim3 grid, hipStream_t stream, const CamConsts& c, const KfDev* kfs,
-                                     int kf_count, const Schedule& sc, const SurfelRows& rows, const PcgParams& P, float* pp, float* pg) {
-  Kernel k = intr ? (depth && desc ? kernel_tt_i : (depth ? kernel_tf_i : kernel_ft_i)) : (depth && desc ? kernel_tt : (depth ? kernel_tf : kernel_ft));
-  hipLaunchKernelGGL(k, grid, dim3(kPcgThreads), 0, stream, c, kfs, kf_count, sc, rows, P, pp, pg);
+// The instantiation of the surfel kernels for a pass (init / step 1), its residuals (depth and descriptors, depth only,
+// descriptors only) and whether any intrinsics are unknowns.
+typedef void (*PcgSurfelKernel)(CamConsts, const KfDev*, int, Schedule, SurfelRows, PcgParams, float*, float*);
+template <bool kDepth, bool kDesc, bool kIntr>
+static PcgSurfelKernel pcg_surfel_kernel_of(bool step1) { return step1 ? pcg_step1_kernel<kDepth, kDesc, kIntr> : pcg_init_kernel<kDepth, kDesc, kIntr>; }
+template <bool kIntr>
+static PcgSurfelKernel pcg_surfel_kernel_of(bool step1, bool depth, bool desc) {
+  return depth && desc ? pcg_surfel_kernel_of<true, true, kIntr>(step1) : depth ? pcg_surfel_kernel_of<true, false, kIntr>(step1) : pcg_surfel_kernel_of<false, true, kIntr>(step1);
 }
 
 // Deterministic dot product tail: the two runs of block partials (shared | sharded) -> *out = shared + sum over
@@ -138,17 +140,10 @@ static int pcg_surfel_pass(bslam_context* ctx, hipStream_t stream, bool step1, c
   const KfDev* kfs = (const KfDev*)ctx->kf_table.ptr;
   const SurfelRows rows = work.rows;
   const dim3 grid(8u * sc.slots_per_xcd);
-  typedef void (*K)(CamConsts, const KfDev*, int, Schedule, SurfelRows, PcgParams, float*, float*);
   if (tiles > 0) {   // an empty shard of a multi-rank run only takes part in the reductions below
     ProfScope prof(ctx, stream, step1 ? 3 : 2);
-    if (!step1)
-      launch_pcg_surfel_kernel<K>(pcg_init_kernel<true, true, false>, pcg_init_kernel<true, false, false>, pcg_init_kernel<false, true, false>,
-                                  pcg_init_kernel<true, true, true>, pcg_init_kernel<true, false, true>, pcg_init_kernel<false, true, true>,
-                                  depth, desc, intr, grid, stream, c, kfs, keyframe_count, sc, rows, P, pp, pg);
-    else
-      launch_pcg_surfel_kernel<K>(pcg_step1_kernel<true, true, false>, pcg_step1_kernel<true, false, false>, pcg_step1_kernel<false, true, false>,
-                                  pcg_step1_kernel<true, true, true>, pcg_step1_kernel<true, false, true>, pcg_step1_kernel<false, true, true>,
-                                  depth, desc, intr, grid, stream, c, kfs, keyframe_count, sc, rows, P, pp, pg);
+    const PcgSurfelKernel kernel = intr ? pcg_surfel_kernel_of<true>(step1, depth, desc) : pcg_surfel_kernel_of<false>(step1, depth, desc);
+    hipLaunchKernelGGL(kernel, grid, dim3(kPcgThreads), 0, stream, c, kfs, keyframe_count, sc, rows, P, pp, pg);
   }
   BSLAM_HIP_TRY(hipGetLastError());
   if (P.cf_cells) {

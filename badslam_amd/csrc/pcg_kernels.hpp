@@ -22,20 +22,20 @@ constexpr float kDiagEpsilon = 1e-8f;   // BS/kernel_pcg.cu:44
 constexpr float kAPriorWeight = 10.f;   // BS/kernel_pcg.cu:48
 constexpr uint32_t kInvalidUnknown = 0xffffffffu;
 
-constexpr int kPcgThreads = 256;
+// Tuning knobs (-D; tools/variants.py, tools/pcg_ab.sh): surfels per thread of the photometric / intrinsics kernels and of the
+// geometry-only kernels, and the waves per SIMD asked of the photometric step-1 kernels.
 #ifndef BSLAM_PCG_R
 #define BSLAM_PCG_R 2
 #endif
-// ---------------------------------------------------------------------------------------------
-// PCGStep1 for all keyframes (BS/kernel_pcg.cu:645-1025)
-// ---------------------------------------------------------------------------------------------
-#ifndef BSLAM_PCG_STEP1_WAVES_DESC
-#define BSLAM_PCG_STEP1_WAVES_DESC 3
-#endif
-constexpr int kPcgR = BSLAM_PCG_R;
 #ifndef BSLAM_PCG_R_GEO
 #define BSLAM_PCG_R_GEO 3
 #endif
+#ifndef BSLAM_PCG_STEP1_WAVES_DESC
+#define BSLAM_PCG_STEP1_WAVES_DESC 3
+#endif
+
+constexpr int kPcgThreads = 256;
+constexpr int kPcgR = BSLAM_PCG_R;
 // surfels per thread: the geometry-only kernels without intrinsics are light on registers and amortise the per-keyframe
 // reduction (6 - 12 wave sums + a barrier) over twice as many pairs
 constexpr int pcg_surfels_per_thread(bool desc, bool intr) { return (!desc && !intr) ? BSLAM_PCG_R_GEO : kPcgR; }
@@ -133,24 +133,34 @@ __device__ __forceinline__ DepthIntrinsicsTerms depth_intrinsics_terms(const Cam
   return t;
 }
 
-struct DescTerms {
-  float r1, r2, w1, w2;
-  float gx1, gy1, gx2, gy2;   // image gradients already multiplied by the colour focal lengths
-};
-
-// In two steps around the association test: the sample positions depend on the surfel and the pose only, so their three quad
-// gathers are issued together with the record gather (see pose_accumulate_kernel); the filters run after the test.
-__device__ __forceinline__ DescSamples descriptor_terms_issue(const CamConsts& c, const KfDev& kf, f3 tp1, f3 tp2, f2 color_pxy, f2* t1, f2* t2) {
-  project_tangent_points(tp1, tp2, kf.frame_T_global, c, t1, t2);
-  return descriptor_samples_issue(kf, c, color_pxy, *t1, *t2);
-}
-
 // Photometric variants: per-surfel constants that a pair only reads (normal, the two tangent sample points, descriptors, and
 // in step 1 the surfel's entries of p) live in LDS -- [component][thread], conflict-free, private to the thread, no barrier --
 // instead of VGPRs: registers for one more wave per SIMD, and the tangent points are formed once per surfel instead of once
 // per pair.
 constexpr int kPcgStateComps = 14;   // 0-2 normal, 3-5 / 6-8 tangent points, 9-10 descriptor, 11-13 p entries (step 1)
 #define BSLAM_PCG_ST(r, comp) state[((r) * kPcgStateComps + (comp)) * kPcgThreads + threadIdx.x]
+#define BSLAM_PCG_ST3(r, comp) mk3(BSLAM_PCG_ST(r, comp), BSLAM_PCG_ST(r, (comp) + 1), BSLAM_PCG_ST(r, (comp) + 2))
+
+// What PCGInit and PCGStep1 evaluate alike for an associated pair, ahead of the Jacobians each forms where it uses them.
+// Contraction is lexical: the evaluators carry the pragma of the blocks they were lifted from, so every product keeps the fusing
+// it had there.
+struct DepthTerms {
+  float inv_stddev, raw, weight;
+  f3 lu;   // the pixel, unprojected
+};
+__device__ __forceinline__ DepthTerms depth_terms(const CamConsts& c, const Proj& p) {
+#pragma clang fp contract(fast)
+  DepthTerms t;
+  t.inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, p.n_local, c.baseline_fx);
+  t.lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
+  t.raw = depth_residual(t.inv_stddev, p.n_local, t.lu, p.local);
+  t.weight = depth_weight(t.raw);
+  return t;
+}
+struct DescTerms {
+  float r1, r2, w1, w2;
+  float gx1, gy1, gx2, gy2;   // image gradients already multiplied by the colour focal lengths
+};
 template <class SamplePoints>
 __device__ __forceinline__ DescTerms descriptor_terms_finish(const CamConsts& c, const KfDev& kf, const DescSamples& ds, float d1, float d2, SamplePoints&& sample_points) {
   DescTerms t;
@@ -159,16 +169,34 @@ __device__ __forceinline__ DescTerms descriptor_terms_finish(const CamConsts& c,
   t.w2 = desc_weight(t.r2);
   return t;
 }
+// Both descriptor residuals wrt. the colour intrinsics (BS/kernel_pcg.cu:462-509)
+__device__ __forceinline__ void descriptor_color_intrinsics_jacobians(const CamConsts& c, const Proj& p, const DescTerms& t, float* Jc1, float* Jc2) {
+#pragma clang fp contract(fast)
+  const float gx_1 = t.gx1 / c.cfx, gy_1 = t.gy1 / c.cfy, gx_2 = t.gx2 / c.cfx, gy_2 = t.gy2 / c.cfy;
+  const float nx = nx_of(c, (float)p.px), ny = ny_of(c, (float)p.py);
+  color_intrinsics_jacobian(gx_1, gy_1, nx, ny, Jc1);
+  color_intrinsics_jacobian(gx_2, gy_2, nx, ny, Jc2);
+}
 
 // ---------------------------------------------------------------------------------------------
-// PCGInit for all keyframes (BS/kernel_pcg.cu:179-513, BS/direct_ba_pcg.cc:339-365)
+// PCGInit (BS/kernel_pcg.cu:179-513, BS/direct_ba_pcg.cc:339-365) and PCGStep1 (BS/kernel_pcg.cu:645-1025) for all keyframes:
+// one skeleton -- surfel prologue, keyframe walk, association and term evaluation per pair, row stash, per-surfel store, block
+// sums -- around the two accumulations.  Init sums r = -J w res and the diagonal M = J w J; step 1 forms sum = J p per residual,
+// then g += J w sum and alpha_d += sum w sum.
+//   acc[r][0..2]   the surfel's entries of r (init) or g (step 1)
+//   accM / ps      its entries of M (init); its entries of p, read once (step 1; in LDS with descriptors)
+//   pose[12]       the keyframe's r[6], M[6] (init) or g[6] (step 1: 6 live columns)
+//   glob[20]       init: depth intrinsics r[5], M[5], colour r[4], M[4] (rows 18, 19 are never written; nor are the rows of a
+//                  residual that the variant lacks); step 1: alpha_d, g depth[5], g colour[4]
 // ---------------------------------------------------------------------------------------------
-template <bool kDepth, bool kDesc, bool kIntr>
-__global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
-    CamConsts c_in, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRows s, PcgParams P,
-    float* __restrict__ partial_pose, float* __restrict__ partial_glob) {
+// first unknown of the surfel at position i of the library's sorted rows
+__device__ __forceinline__ uint32_t pcg_surfel_unknown(const PcgParams& P, uint32_t i) { return P.surfel_start + (uint32_t)P.per_surfel * (P.perm ? P.perm[i] : i); }
+template <bool kStep1, bool kDepth, bool kDesc, bool kIntr>
+__device__ __forceinline__ void pcg_surfel_body(const CamConsts& c_in, const KfDev* __restrict__ kfs, int kf_count, const Schedule& sc, const SurfelRows& s,
+                                                const PcgParams& P, float* __restrict__ partial_pose, float* __restrict__ partial_glob) {
   CamConsts c = c_in;
   constexpr int R = pcg_surfels_per_thread(kDesc, kIntr);
+  constexpr int kLive = kStep1 ? 6 : kPcgPoseRow;
   uint32_t slot;
   if (!slot_of_block(sc, blockIdx.x, &slot)) return;
   const int tile = (int)slot;
@@ -179,7 +207,7 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
   bool valid[R];
   uint32_t idx[R];
   __shared__ float state[kDesc ? kPcgStateComps * R * kPcgThreads : 1];
-  float ar[R][3], aM[R][3];
+  float acc[R][3], accM[R][3], ps[R][3];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
     const uint32_t i = surfel_of_slot(sc, slot, r, R);
@@ -187,6 +215,13 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
     idx[r] = valid[r] ? i : 0;
     gp[r] = mk3(s.x[idx[r]], s.y[idx[r]], s.z[idx[r]]);
     gn[r] = unpack_normal(s.normal[idx[r]]);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) { acc[r][j] = 0.f; accM[r][j] = 0.f; ps[r][j] = 0.f; }
+    if constexpr (kStep1) if (P.optimize_geometry) {
+      const uint32_t base = pcg_surfel_unknown(P, idx[r]);
+      ps[r][0] = P.p[base];
+      if (kDesc) { ps[r][1] = P.p[base + 1]; ps[r][2] = P.p[base + 2]; }
+    }
     if constexpr (kDesc) {
       f3 tp1, tp2;
       tangent_points(gp[r], gn[r], s.radius_squared[idx[r]], &tp1, &tp2);
@@ -194,13 +229,17 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
       BSLAM_PCG_ST(r, 3) = tp1.x; BSLAM_PCG_ST(r, 4) = tp1.y; BSLAM_PCG_ST(r, 5) = tp1.z;
       BSLAM_PCG_ST(r, 6) = tp2.x; BSLAM_PCG_ST(r, 7) = tp2.y; BSLAM_PCG_ST(r, 8) = tp2.z;
       BSLAM_PCG_ST(r, 9) = s.d1[idx[r]]; BSLAM_PCG_ST(r, 10) = s.d2[idx[r]];
+      if constexpr (kStep1) { BSLAM_PCG_ST(r, 11) = ps[r][0]; BSLAM_PCG_ST(r, 12) = ps[r][1]; BSLAM_PCG_ST(r, 13) = ps[r][2]; }
     }
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { ar[r][j] = 0.f; aM[r][j] = 0.f; }
   }
   float glob[kPcgGlobRow];
 #pragma unroll
   for (int i = 0; i < kPcgGlobRow; ++i) glob[i] = 0.f;
+  float pdi[5] = {0, 0, 0, 0, 0}, pci[4] = {0, 0, 0, 0};   // the intrinsics entries of p: read by step 1 only (as accM is init's, ps and pp step 1's)
+  if constexpr (kStep1 && kIntr) {
+    if (P.optimize_depth_intr) for (int j = 0; j < 5; ++j) pdi[j] = P.p[P.depth_intr_start + j];
+    if (P.optimize_color_intr) for (int j = 0; j < 4; ++j) pci[j] = P.p[P.color_intr_start + j];
+  }
 
   if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
   else BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
@@ -215,9 +254,14 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
     BSLAM_HOIST_KF_TRANSLATION(kf);
     const uint32_t kf_idx = kf_pose_unknown_index(P.gauge_kf, kf.id);
     const bool opt_pose = P.optimize_poses && kf_idx != kInvalidUnknown;
+    float pp[6] = {0, 0, 0, 0, 0, 0};   // step 1: the keyframe's entries of p
+    if constexpr (kStep1) if (opt_pose) for (int j = 0; j < 6; ++j) pp[j] = P.p[kf_idx + j];
     float pose[kPcgPoseRow];
 #pragma unroll
-    for (int i = 0; i < kPcgPoseRow; ++i) BSLAM_ZERO(pose[i]);   // independent zeros: see pose_accumulate_kernel
+    for (int i = 0; i < kPcgPoseRow; ++i) {
+      if (i < kLive) BSLAM_ZERO(pose[i]);   // independent zeros: see pose_accumulate_kernel
+      else pose[i] = 0.f;
+    }
 
 #pragma unroll
     for (int r = 0; r < R; ++r) {
@@ -226,13 +270,14 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
       f2 color_pxy, t1, t2;   // the three sample positions of the descriptor residual
       bool has_desc = false;
       if constexpr (kDesc) {
+        // the quad gathers go ahead of the association test: see pose_accumulate_kernel
         if (!valid[r] || !project_to_pixel(c, kf, gp[r], &p)) continue;
         const PixelRecord rec = load_record(c, kf, p);
         has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
-        ds = descriptor_terms_issue(c, kf, mk3(BSLAM_PCG_ST(r, 3), BSLAM_PCG_ST(r, 4), BSLAM_PCG_ST(r, 5)),
-                                    mk3(BSLAM_PCG_ST(r, 6), BSLAM_PCG_ST(r, 7), BSLAM_PCG_ST(r, 8)), color_pxy, &t1, &t2);
-        asm volatile("" ::: "memory");   // the gathers stay in front of the branches of the association test
-        if (!associate_with_record(c, kf, mk3(BSLAM_PCG_ST(r, 0), BSLAM_PCG_ST(r, 1), BSLAM_PCG_ST(r, 2)), rec, &p)) continue;
+        project_tangent_points(BSLAM_PCG_ST3(r, 3), BSLAM_PCG_ST3(r, 6), kf.frame_T_global, c, &t1, &t2);
+        ds = descriptor_samples_issue(kf, c, color_pxy, t1, t2);
+        asm volatile("" ::: "memory");
+        if (!associate_with_record(c, kf, BSLAM_PCG_ST3(r, 0), rec, &p)) continue;
       } else {
         if (!valid[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
       }
@@ -240,88 +285,163 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
       const f3 rn = p.n_local;
       if (kDepth) {
 #pragma clang fp contract(fast)   // past the association test nothing feeds an integer output: products with p and the sums fuse (as nvcc's default does)
-        const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, rn, c.baseline_fx);
-        const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
-        const float raw = depth_residual(inv_stddev, rn, lu, p.local);
-        const float weight = depth_weight(raw);
-        if (P.optimize_geometry) {                               // :217-221
-          const float jp = depth_position_jacobian(inv_stddev);
-          ar[r][0] -= jp * weight * raw;
-          aM[r][0] += jp * weight * jp;
-        }
-        if (opt_pose) {                                          // :224-255
-          float J[6];
-          depth_pose_jacobian(inv_stddev, rn, lu, J);
-#pragma unroll
-          for (int j = 0; j < 6; ++j) {
-            const float wj = weight * J[j];
-            pose[j] += -1 * wj * raw;
-            pose[6 + j] += J[j] * wj;
+        const DepthTerms t = depth_terms(c, p);
+        const auto intrinsics_terms = [&] { return depth_intrinsics_terms(c, kf, p, kDesc ? BSLAM_PCG_ST3(r, 0) : gn[r], t.inv_stddev, P.depth_intr_start); };
+        if constexpr (!kStep1) {
+          if (P.optimize_geometry) {                               // BS/kernel_pcg.cu:217-221
+            const float jp = depth_position_jacobian(t.inv_stddev);
+            acc[r][0] -= jp * t.weight * t.raw;
+            accM[r][0] += jp * t.weight * jp;
           }
-        }
-        if (kIntr && P.optimize_depth_intr) {                    // :258-322
-          const DepthIntrinsicsTerms t = depth_intrinsics_terms(c, kf, p, kDesc ? mk3(BSLAM_PCG_ST(r, 0), BSLAM_PCG_ST(r, 1), BSLAM_PCG_ST(r, 2)) : gn[r], inv_stddev, P.depth_intr_start);
-          if (t.valid) {
+          if (opt_pose) {                                          // :224-255
+            float J[6];
+            depth_pose_jacobian(t.inv_stddev, rn, t.lu, J);
 #pragma unroll
-            for (int j = 0; j < 5; ++j) {
-              const float wj = weight * t.d[j];
-              glob[j] += -1 * wj * raw;
-              glob[5 + j] += t.d[j] * wj;
+            for (int j = 0; j < 6; ++j) {
+              const float wj = t.weight * J[j];
+              pose[j] += -1 * wj * t.raw;
+              pose[6 + j] += J[j] * wj;
             }
-            const float wj = weight * t.cf_jac;
-            const uint32_t cell = t.cf_index - (P.depth_intr_start + 5);
-            atomicAdd(&P.cf_acc0[cell], (double)(-1 * wj * raw));
-            atomicAdd(&P.cf_acc1[cell], (double)(t.cf_jac * wj));
-          } else {
-            visible = false;                                      // :272 (also disables the descriptor part)
+          }
+          if (kIntr && P.optimize_depth_intr) {                    // :258-322
+            const DepthIntrinsicsTerms it = intrinsics_terms();
+            if (it.valid) {
+#pragma unroll
+              for (int j = 0; j < 5; ++j) {
+                const float wj = t.weight * it.d[j];
+                glob[j] += -1 * wj * t.raw;
+                glob[5 + j] += it.d[j] * wj;
+              }
+              const float wj = t.weight * it.cf_jac;
+              const uint32_t cell = it.cf_index - (P.depth_intr_start + 5);
+              atomicAdd(&P.cf_acc0[cell], (double)(-1 * wj * t.raw));
+              atomicAdd(&P.cf_acc1[cell], (double)(it.cf_jac * wj));
+            } else {
+              visible = false;                                      // :272 (also disables the descriptor part; init only)
+            }
+          }
+        } else {
+          float sum = 0;
+          float gj = 0;
+          float J[6] = {0, 0, 0, 0, 0, 0};
+          if (P.optimize_geometry) { gj = depth_position_jacobian(t.inv_stddev); sum += gj * (kDesc ? BSLAM_PCG_ST(r, 11) : ps[r][0]); }
+          if (opt_pose) {
+            depth_pose_jacobian(t.inv_stddev, rn, t.lu, J);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) sum += J[j] * pp[j];
+          }
+          DepthIntrinsicsTerms it;
+          it.valid = false;
+          if (kIntr && P.optimize_depth_intr) {
+            it = intrinsics_terms();
+            if (it.valid) {
+              sum += it.d[2] * pdi[2];
+              sum += it.d[3] * pdi[3];
+              sum += it.d[0] * pdi[0];
+              sum += it.d[1] * pdi[1];
+              sum += it.d[4] * pdi[4];
+              sum += it.cf_jac * P.p[it.cf_index];
+            }
+          }
+          glob[0] += sum * t.weight * sum;
+          sum *= t.weight;
+          if (P.optimize_geometry) acc[r][0] += gj * sum;
+          if (opt_pose) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) pose[j] += J[j] * sum;
+          }
+          if (kIntr && P.optimize_depth_intr && it.valid) {
+#pragma unroll
+            for (int j = 0; j < 5; ++j) glob[1 + j] += it.d[j] * sum;
+            atomicAdd(&P.cf_acc0[it.cf_index - (P.depth_intr_start + 5)], (double)(it.cf_jac * sum));
           }
         }
       }
-      if (kDesc) {                                               // :330-511
+      if (kDesc) {                                               // BS/kernel_pcg.cu:330-511
 #pragma clang fp contract(fast)
         visible = visible && has_desc;
         if (!visible) continue;
         const DescTerms t = descriptor_terms_finish(c, kf, ds, BSLAM_PCG_ST(r, 9), BSLAM_PCG_ST(r, 10), [&](f2 (&pts)[3]) { pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; });
         const f3 ls = p.local;
-        if (P.optimize_geometry) {                               // :364-399
-          const float jp1 = descriptor_position_jacobian(t.gx1, t.gy1, 1.f, 1.f, rn, ls);   // gx, gy already carry fx, fy
-          const float jp2 = descriptor_position_jacobian(t.gx2, t.gy2, 1.f, 1.f, rn, ls);
-          ar[r][0] -= jp1 * t.w1 * t.r1 + jp2 * t.w2 * t.r2;
-          aM[r][0] += jp1 * t.w1 * jp1 + jp2 * t.w2 * jp2;
-          const float j11 = -1, j12 = 0, j21 = 0, j22 = -1;
-          ar[r][1] -= j11 * t.w1 * t.r1 + j12 * t.w2 * t.r2;
-          aM[r][1] += j11 * t.w1 * j11 + j12 * t.w2 * j12;
-          ar[r][2] -= j21 * t.w1 * t.r1 + j22 * t.w2 * t.r2;
-          aM[r][2] += j21 * t.w1 * j21 + j22 * t.w2 * j22;
-        }
-        if (opt_pose) {                                          // :402-459
-          float J1[6], J2[6];
-          descriptor_pose_jacobian(t.gx1, t.gy1, ls, J1);
-          descriptor_pose_jacobian(t.gx2, t.gy2, ls, J2);
-#pragma unroll
-          for (int j = 0; j < 6; ++j) {
-            const float wj1 = t.w1 * J1[j], wj2 = t.w2 * J2[j];
-            pose[j] += -1 * wj1 * t.r1 + -1 * wj2 * t.r2;
-            pose[6 + j] += J1[j] * wj1 + J2[j] * wj2;
+        if constexpr (!kStep1) {
+          if (P.optimize_geometry) {                               // :364-399
+            const float jp1 = descriptor_position_jacobian(t.gx1, t.gy1, 1.f, 1.f, rn, ls);   // gx, gy already carry fx, fy
+            const float jp2 = descriptor_position_jacobian(t.gx2, t.gy2, 1.f, 1.f, rn, ls);
+            acc[r][0] -= jp1 * t.w1 * t.r1 + jp2 * t.w2 * t.r2;
+            accM[r][0] += jp1 * t.w1 * jp1 + jp2 * t.w2 * jp2;
+            const float j11 = -1, j12 = 0, j21 = 0, j22 = -1;
+            acc[r][1] -= j11 * t.w1 * t.r1 + j12 * t.w2 * t.r2;
+            accM[r][1] += j11 * t.w1 * j11 + j12 * t.w2 * j12;
+            acc[r][2] -= j21 * t.w1 * t.r1 + j22 * t.w2 * t.r2;
+            accM[r][2] += j21 * t.w1 * j21 + j22 * t.w2 * j22;
           }
-        }
-        if (kIntr && P.optimize_color_intr) {                    // :462-509
-          const float gx_1 = t.gx1 / c.cfx, gy_1 = t.gy1 / c.cfy, gx_2 = t.gx2 / c.cfx, gy_2 = t.gy2 / c.cfy;
-          const float nx = nx_of(c, (float)p.px), ny = ny_of(c, (float)p.py);
-          const float Jc1[4] = {gx_1 * nx, gy_1 * ny, gx_1, gy_1};
-          const float Jc2[4] = {gx_2 * nx, gy_2 * ny, gx_2, gy_2};
+          if (opt_pose) {                                          // :402-459
+            float J1[6], J2[6];
+            descriptor_pose_jacobian(t.gx1, t.gy1, ls, J1);
+            descriptor_pose_jacobian(t.gx2, t.gy2, ls, J2);
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const float wj1 = t.w1 * Jc1[j], wj2 = t.w2 * Jc2[j];
-            glob[10 + j] += -1 * wj1 * t.r1 + -1 * wj2 * t.r2;
-            glob[14 + j] += Jc1[j] * wj1 + Jc2[j] * wj2;
+            for (int j = 0; j < 6; ++j) {
+              const float wj1 = t.w1 * J1[j], wj2 = t.w2 * J2[j];
+              pose[j] += -1 * wj1 * t.r1 + -1 * wj2 * t.r2;
+              pose[6 + j] += J1[j] * wj1 + J2[j] * wj2;
+            }
+          }
+          if (kIntr && P.optimize_color_intr) {                    // :462-509
+            float Jc1[4], Jc2[4];
+            descriptor_color_intrinsics_jacobians(c, p, t, Jc1, Jc2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              const float wj1 = t.w1 * Jc1[j], wj2 = t.w2 * Jc2[j];
+              glob[10 + j] += -1 * wj1 * t.r1 + -1 * wj2 * t.r2;
+              glob[14 + j] += Jc1[j] * wj1 + Jc2[j] * wj2;
+            }
+          }
+        } else {
+          float sum_1 = 0, sum_2 = 0, gj1 = 0, gj2 = 0;
+          float J1[6] = {0, 0, 0, 0, 0, 0}, J2[6] = {0, 0, 0, 0, 0, 0};
+          float Jc1[4] = {0, 0, 0, 0}, Jc2[4] = {0, 0, 0, 0};
+          if (P.optimize_geometry) {
+            gj1 = descriptor_position_jacobian(t.gx1, t.gy1, 1.f, 1.f, rn, ls);
+            gj2 = descriptor_position_jacobian(t.gx2, t.gy2, 1.f, 1.f, rn, ls);
+            const float ps0 = BSLAM_PCG_ST(r, 11);
+            sum_1 += gj1 * ps0;
+            sum_2 += gj2 * ps0;
+            sum_1 += -1.f * BSLAM_PCG_ST(r, 12);
+            sum_2 += -1.f * BSLAM_PCG_ST(r, 13);
+          }
+          if (opt_pose) {
+            descriptor_pose_jacobian(t.gx1, t.gy1, ls, J1);
+            descriptor_pose_jacobian(t.gx2, t.gy2, ls, J2);
+#pragma unroll
+            for (int j = 0; j < 6; ++j) { sum_1 += J1[j] * pp[j]; sum_2 += J2[j] * pp[j]; }
+          }
+          if (kIntr && P.optimize_color_intr) {
+            descriptor_color_intrinsics_jacobians(c, p, t, Jc1, Jc2);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sum_1 += Jc1[j] * pci[j]; sum_2 += Jc2[j] * pci[j]; }
+          }
+          glob[0] += sum_1 * t.w1 * sum_1 + sum_2 * t.w2 * sum_2;
+          sum_1 *= t.w1;
+          sum_2 *= t.w2;
+          if (P.optimize_geometry) {
+            acc[r][0] += gj1 * sum_1 + gj2 * sum_2;
+            acc[r][1] += -1.f * sum_1 + 0.f * sum_2;
+            acc[r][2] += 0.f * sum_1 + -1.f * sum_2;
+          }
+          if (opt_pose) {
+#pragma unroll
+            for (int j = 0; j < 6; ++j) pose[j] += J1[j] * sum_1 + J2[j] * sum_2;
+          }
+          if (kIntr && P.optimize_color_intr) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) glob[6 + j] += Jc1[j] * sum_1 + Jc2[j] * sum_2;
           }
         }
       }
     }
 
     if (opt_pose) {   // uniform
-      pcg_stash_pose<kPcgPoseRow>(stash, at, k, pose, partial_pose, sc.slots, tile);
+      pcg_stash_pose<kLive>(stash, at, k, pose, partial_pose, sc.slots, tile);
     }
   }
   }
@@ -331,16 +451,31 @@ __global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       if (!valid[r]) continue;
-      const uint32_t base = P.surfel_start + (uint32_t)P.per_surfel * (P.perm ? P.perm[idx[r]] : idx[r]);
-      P.r[base] = ar[r][0];
-      P.M[base] = aM[r][0];
-      if (kDesc) {
-        P.r[base + 1] = ar[r][1]; P.M[base + 1] = aM[r][1];
-        P.r[base + 2] = ar[r][2]; P.M[base + 2] = aM[r][2];
+      const uint32_t base = pcg_surfel_unknown(P, idx[r]);
+      float* out = kStep1 ? P.g : P.r;
+#pragma unroll
+      for (int j = 0; j < (kDesc ? 3 : 1); ++j) {
+        out[base + j] = acc[r][j];
+        if constexpr (!kStep1) P.M[base + j] = accM[r][j];
       }
     }
   }
-  if (kIntr) block_reduce_rows<kPcgGlobRow>(glob, redg, partial_glob + (size_t)tile * kPcgGlobRow);
+  if constexpr (kStep1) block_reduce_rows<10>(glob, redg, partial_glob + (size_t)tile * kPcgGlobRow);
+  else if constexpr (kIntr) block_reduce_rows<kPcgGlobRow>(glob, redg, partial_glob + (size_t)tile * kPcgGlobRow);
+}
+
+// The two kernels differ in the occupancy they ask for.
+template <bool kDepth, bool kDesc, bool kIntr>
+__global__ __launch_bounds__(kPcgThreads) void pcg_init_kernel(
+    CamConsts c, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRows s, PcgParams P,
+    float* __restrict__ partial_pose, float* __restrict__ partial_glob) {
+  pcg_surfel_body<false, kDepth, kDesc, kIntr>(c, kfs, kf_count, sc, s, P, partial_pose, partial_glob);
+}
+template <bool kDepth, bool kDesc, bool kIntr>
+__global__ __launch_bounds__(kPcgThreads) __attribute__((amdgpu_waves_per_eu(kDesc ? BSLAM_PCG_STEP1_WAVES_DESC : 4))) void pcg_step1_kernel(
+    CamConsts c, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRows s, PcgParams P,
+    float* __restrict__ partial_pose, float* __restrict__ partial_glob) {
+  pcg_surfel_body<true, kDepth, kDesc, kIntr>(c, kfs, kf_count, sc, s, P, partial_pose, partial_glob);
 }
 
 // Sums the per-tile pose rows of one keyframe ([k][tile][12], contiguous per keyframe) and stores them at
@@ -422,206 +557,6 @@ __global__ __launch_bounds__(kPcgGlobReduceThreads) void pcg_glob_reduce_kernel(
       if (P.optimize_color_intr) P.g[P.color_intr_start + col - 6] += v;
     }
   }
-}
-
-template <bool kDepth, bool kDesc, bool kIntr>
-__global__ __launch_bounds__(kPcgThreads) __attribute__((amdgpu_waves_per_eu(kDesc ? BSLAM_PCG_STEP1_WAVES_DESC : 4))) void pcg_step1_kernel(
-    CamConsts c_in, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRows s, PcgParams P,
-    float* __restrict__ partial_pose, float* __restrict__ partial_glob) {
-  CamConsts c = c_in;
-  constexpr int R = pcg_surfels_per_thread(kDesc, kIntr);
-  uint32_t slot;
-  if (!slot_of_block(sc, blockIdx.x, &slot)) return;
-  const int tile = (int)slot;
-  __shared__ RowStash<kPcgPoseRow, kPcgGroup, 4> stash;
-  __shared__ float redg[4][32];
-
-  f3 gp[R], gn[R];
-  bool valid[R];
-  uint32_t idx[R];
-  __shared__ float state[kDesc ? kPcgStateComps * R * kPcgThreads : 1];
-  float ps[R][3], ag[R][3];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    const uint32_t i = surfel_of_slot(sc, slot, r, R);
-    valid[r] = i < s.size;
-    idx[r] = valid[r] ? i : 0;
-    gp[r] = mk3(s.x[idx[r]], s.y[idx[r]], s.z[idx[r]]);
-    gn[r] = unpack_normal(s.normal[idx[r]]);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) { ps[r][j] = 0.f; ag[r][j] = 0.f; }
-    if (P.optimize_geometry) {
-      const uint32_t base = P.surfel_start + (uint32_t)P.per_surfel * (P.perm ? P.perm[idx[r]] : idx[r]);
-      ps[r][0] = P.p[base];
-      if (kDesc) { ps[r][1] = P.p[base + 1]; ps[r][2] = P.p[base + 2]; }
-    }
-    if constexpr (kDesc) {
-      f3 tp1, tp2;
-      tangent_points(gp[r], gn[r], s.radius_squared[idx[r]], &tp1, &tp2);
-      BSLAM_PCG_ST(r, 0) = gn[r].x; BSLAM_PCG_ST(r, 1) = gn[r].y; BSLAM_PCG_ST(r, 2) = gn[r].z;
-      BSLAM_PCG_ST(r, 3) = tp1.x; BSLAM_PCG_ST(r, 4) = tp1.y; BSLAM_PCG_ST(r, 5) = tp1.z;
-      BSLAM_PCG_ST(r, 6) = tp2.x; BSLAM_PCG_ST(r, 7) = tp2.y; BSLAM_PCG_ST(r, 8) = tp2.z;
-      BSLAM_PCG_ST(r, 9) = s.d1[idx[r]]; BSLAM_PCG_ST(r, 10) = s.d2[idx[r]];
-      BSLAM_PCG_ST(r, 11) = ps[r][0]; BSLAM_PCG_ST(r, 12) = ps[r][1]; BSLAM_PCG_ST(r, 13) = ps[r][2];
-    }
-  }
-  float glob[kPcgGlobRow];
-#pragma unroll
-  for (int i = 0; i < kPcgGlobRow; ++i) glob[i] = 0.f;
-  float pdi[5] = {0, 0, 0, 0, 0}, pci[4] = {0, 0, 0, 0};
-  if (kIntr && P.optimize_depth_intr) for (int j = 0; j < 5; ++j) pdi[j] = P.p[P.depth_intr_start + j];
-  if (kIntr && P.optimize_color_intr) for (int j = 0; j < 4; ++j) pci[j] = P.p[P.color_intr_start + j];
-
-  if constexpr (kDesc) BSLAM_HOIST_CAM_CENTRES(c);
-  else BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
-  BSLAM_HOIST_UNPROJECTION_CENTRE(c);
-  RowStashCursor at;
-  for (int k0 = 0; k0 < kf_count; k0 += 64) {
-  unsigned long long todo = keyframes_to_visit(c, kfs, k0, kf_count, sc, slot, R, true);
-  if (P.optimize_poses && sc.bounds != nullptr) pcg_zero_rows(todo, k0, kf_count, partial_pose, sc.slots, tile);
-  for (; todo != 0; todo &= todo - 1) {
-    const int k = k0 + __builtin_ctzll(todo);
-    KfDev kf = kfs[k];
-    BSLAM_HOIST_KF_TRANSLATION(kf);
-    const uint32_t kf_idx = kf_pose_unknown_index(P.gauge_kf, kf.id);
-    const bool opt_pose = P.optimize_poses && kf_idx != kInvalidUnknown;
-    float pp[6] = {0, 0, 0, 0, 0, 0};
-    if (opt_pose) for (int j = 0; j < 6; ++j) pp[j] = P.p[kf_idx + j];
-    float pose[kPcgPoseRow];   // 6 live columns
-#pragma unroll
-    for (int i = 0; i < kPcgPoseRow; ++i) {
-      if (i < 6) BSLAM_ZERO(pose[i]);   // independent zeros: see pose_accumulate_kernel
-      else pose[i] = 0.f;
-    }
-
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      Proj p;
-      DescSamples ds;
-      f2 color_pxy, t1, t2;   // the three sample positions of the descriptor residual
-      bool has_desc = false;
-      if constexpr (kDesc) {
-        if (!valid[r] || !project_to_pixel(c, kf, gp[r], &p)) continue;
-        const PixelRecord rec = load_record(c, kf, p);
-        has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
-        ds = descriptor_terms_issue(c, kf, mk3(BSLAM_PCG_ST(r, 3), BSLAM_PCG_ST(r, 4), BSLAM_PCG_ST(r, 5)),
-                                    mk3(BSLAM_PCG_ST(r, 6), BSLAM_PCG_ST(r, 7), BSLAM_PCG_ST(r, 8)), color_pxy, &t1, &t2);
-        asm volatile("" ::: "memory");   // the gathers stay in front of the branches of the association test
-        if (!associate_with_record(c, kf, mk3(BSLAM_PCG_ST(r, 0), BSLAM_PCG_ST(r, 1), BSLAM_PCG_ST(r, 2)), rec, &p)) continue;
-      } else {
-        if (!valid[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
-      }
-      bool visible = true;
-      const f3 rn = p.n_local;
-      if (kDepth) {
-#pragma clang fp contract(fast)   // past the association test nothing feeds an integer output: products with p and the sums fuse (as nvcc's default does)
-        const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, rn, c.baseline_fx);
-        const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
-        const float raw = depth_residual(inv_stddev, rn, lu, p.local);
-        const float weight = depth_weight(raw);
-        float sum = 0;
-        float gj = 0;
-        float J[6] = {0, 0, 0, 0, 0, 0};
-        if (P.optimize_geometry) { gj = depth_position_jacobian(inv_stddev); sum += gj * (kDesc ? BSLAM_PCG_ST(r, 11) : ps[r][0]); }
-        if (opt_pose) {
-          depth_pose_jacobian(inv_stddev, rn, lu, J);
-#pragma unroll
-          for (int j = 0; j < 6; ++j) sum += J[j] * pp[j];
-        }
-        DepthIntrinsicsTerms t;
-        t.valid = false;
-        if (kIntr && P.optimize_depth_intr) {
-          t = depth_intrinsics_terms(c, kf, p, kDesc ? mk3(BSLAM_PCG_ST(r, 0), BSLAM_PCG_ST(r, 1), BSLAM_PCG_ST(r, 2)) : gn[r], inv_stddev, P.depth_intr_start);
-          if (t.valid) {
-            sum += t.d[2] * pdi[2];
-            sum += t.d[3] * pdi[3];
-            sum += t.d[0] * pdi[0];
-            sum += t.d[1] * pdi[1];
-            sum += t.d[4] * pdi[4];
-            sum += t.cf_jac * P.p[t.cf_index];
-          }
-        }
-        glob[0] += sum * weight * sum;
-        sum *= weight;
-        if (P.optimize_geometry) ag[r][0] += gj * sum;
-        if (opt_pose) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) pose[j] += J[j] * sum;
-        }
-        if (kIntr && P.optimize_depth_intr && t.valid) {
-#pragma unroll
-          for (int j = 0; j < 5; ++j) glob[1 + j] += t.d[j] * sum;
-          atomicAdd(&P.cf_acc0[t.cf_index - (P.depth_intr_start + 5)], (double)(t.cf_jac * sum));
-        }
-      }
-      if (kDesc) {
-#pragma clang fp contract(fast)
-        visible = visible && has_desc;
-        if (!visible) continue;
-        const DescTerms t = descriptor_terms_finish(c, kf, ds, BSLAM_PCG_ST(r, 9), BSLAM_PCG_ST(r, 10), [&](f2 (&pts)[3]) { pts[0] = color_pxy; pts[1] = t1; pts[2] = t2; });
-        const f3 ls = p.local;
-        float sum_1 = 0, sum_2 = 0, gj1 = 0, gj2 = 0;
-        float J1[6] = {0, 0, 0, 0, 0, 0}, J2[6] = {0, 0, 0, 0, 0, 0};
-        float Jc1[4] = {0, 0, 0, 0}, Jc2[4] = {0, 0, 0, 0};
-        if (P.optimize_geometry) {
-          gj1 = descriptor_position_jacobian(t.gx1, t.gy1, 1.f, 1.f, rn, ls);
-          gj2 = descriptor_position_jacobian(t.gx2, t.gy2, 1.f, 1.f, rn, ls);
-          const float ps0 = BSLAM_PCG_ST(r, 11);
-          sum_1 += gj1 * ps0;
-          sum_2 += gj2 * ps0;
-          sum_1 += -1.f * BSLAM_PCG_ST(r, 12);
-          sum_2 += -1.f * BSLAM_PCG_ST(r, 13);
-        }
-        if (opt_pose) {
-          descriptor_pose_jacobian(t.gx1, t.gy1, ls, J1);
-          descriptor_pose_jacobian(t.gx2, t.gy2, ls, J2);
-#pragma unroll
-          for (int j = 0; j < 6; ++j) { sum_1 += J1[j] * pp[j]; sum_2 += J2[j] * pp[j]; }
-        }
-        if (kIntr && P.optimize_color_intr) {
-          const float gx_1 = t.gx1 / c.cfx, gy_1 = t.gy1 / c.cfy, gx_2 = t.gx2 / c.cfx, gy_2 = t.gy2 / c.cfy;
-          const float nx = nx_of(c, (float)p.px), ny = ny_of(c, (float)p.py);
-          color_intrinsics_jacobian(gx_1, gy_1, nx, ny, Jc1);
-          color_intrinsics_jacobian(gx_2, gy_2, nx, ny, Jc2);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) { sum_1 += Jc1[j] * pci[j]; sum_2 += Jc2[j] * pci[j]; }
-        }
-        glob[0] += sum_1 * t.w1 * sum_1 + sum_2 * t.w2 * sum_2;
-        sum_1 *= t.w1;
-        sum_2 *= t.w2;
-        if (P.optimize_geometry) {
-          ag[r][0] += gj1 * sum_1 + gj2 * sum_2;
-          ag[r][1] += -1.f * sum_1 + 0.f * sum_2;
-          ag[r][2] += 0.f * sum_1 + -1.f * sum_2;
-        }
-        if (opt_pose) {
-#pragma unroll
-          for (int j = 0; j < 6; ++j) pose[j] += J1[j] * sum_1 + J2[j] * sum_2;
-        }
-        if (kIntr && P.optimize_color_intr) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) glob[6 + j] += Jc1[j] * sum_1 + Jc2[j] * sum_2;
-        }
-      }
-    }
-
-    if (opt_pose) {   // uniform
-      pcg_stash_pose<6>(stash, at, k, pose, partial_pose, sc.slots, tile);
-    }
-  }
-  }
-  if (at.n) stash.flush(at, partial_pose, sc.slots, tile);
-
-  if (P.optimize_geometry) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (!valid[r]) continue;
-      const uint32_t base = P.surfel_start + (uint32_t)P.per_surfel * (P.perm ? P.perm[idx[r]] : idx[r]);
-      P.g[base] = ag[r][0];
-      if (kDesc) { P.g[base + 1] = ag[r][1]; P.g[base + 2] = ag[r][2]; }
-    }
-  }
-  block_reduce_rows<10>(glob, redg, partial_glob + (size_t)tile * kPcgGlobRow);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -96,6 +96,9 @@ SIGNATURES = {
                                                    P(C.c_uint32)]),
     "bslam_delete_surfels_and_update_radii": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, P(Camera4f), P(DepthParams), C.c_int, P(KeyframeView),
                                                        P(C.c_uint32), C.c_uint32, P(Buffer2D)]),
+    "bslam_median_filter_and_densify_depth": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
+    "bslam_downscale_depth_median": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
+    "bslam_downscale_rgb": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_compute_brightness": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_bilateral_filter_and_depth_cutoff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint16, C.c_float,
                                                          P(Buffer2D), P(Buffer2D)]),

@@ -12,8 +12,10 @@ class BadSlam:
     def __init__(self, color_camera, depth_camera, keyframe_interval=10, max_num_ba_iterations_per_keyframe=10, num_scales=5,
                  max_surfel_count=25 * 1000 * 1000, sparse_surfel_cell_size=4, use_motion_model=True, use_geometric_residuals=True,
                  use_photometric_residuals=True, do_surfel_updates=True, use_pcg=False, optimize_intrinsics=False, disable_deactivation=False,
-                 start_frame=0, raw_to_float_depth=1.0 / 5000, max_depth=3.0, baseline_fx=40.0, device=0):
-        """Keyword defaults = BS/bad_slam_config.h."""
+                 start_frame=0, raw_to_float_depth=1.0 / 5000, max_depth=3.0, baseline_fx=40.0, device=0, pyramid_level_for_depth=0,
+                 pyramid_level_for_color=0, median_filter_and_densify_iterations=0):
+        """Keyword defaults = BS/bad_slam_config.h.  The cameras are those of the pyramid levels in use (already scaled);
+        ProcessFrame takes the full-resolution images, (width << level, height << level) per stream."""
         self.L = dba.host_lib()
         L = self.L
         f32p = C.POINTER(C.c_float)
@@ -23,13 +25,15 @@ class BadSlam:
         L.bsh_slam_direct_ba.restype = C.c_void_p
         L.bsh_slam_direct_ba.argtypes = [C.c_void_p]
         L.bsh_slam_process_frame.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), C.c_int]
+        L.bsh_slam_preprocess_frame.argtypes = [C.c_void_p, C.POINTER(C.c_uint16), C.POINTER(C.c_uint8)]
         L.bsh_slam_run_bundle_adjustment.argtypes = [C.c_void_p] + [C.c_int] * 10 + [C.POINTER(C.c_int), C.POINTER(C.c_int)]
         L.bsh_slam_frame_count.argtypes = [C.c_void_p]
         L.bsh_slam_get_frame_poses.argtypes = [C.c_void_p, f32p, C.c_int]
         L.bsh_slam_state.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        cfg = (C.c_int * 13)(keyframe_interval, max_num_ba_iterations_per_keyframe, num_scales, max_surfel_count, sparse_surfel_cell_size,
+        cfg = (C.c_int * 16)(keyframe_interval, max_num_ba_iterations_per_keyframe, num_scales, max_surfel_count, sparse_surfel_cell_size,
                              int(use_motion_model), int(use_geometric_residuals), int(use_photometric_residuals), int(do_surfel_updates), int(use_pcg),
-                             int(optimize_intrinsics), int(disable_deactivation), start_frame)
+                             int(optimize_intrinsics), int(disable_deactivation), start_frame, pyramid_level_for_depth, pyramid_level_for_color,
+                             median_filter_and_densify_iterations)
         fcfg = (C.c_float * 3)(raw_to_float_depth, max_depth, baseline_fx)
         cc = np.array([color_camera.fx, color_camera.fy, color_camera.cx, color_camera.cy], np.float32)
         dc = np.array([depth_camera.fx, depth_camera.fy, depth_camera.cx, depth_camera.cy], np.float32)
@@ -44,6 +48,9 @@ class BadSlam:
         self.direct_ba.stream = C.c_void_p(None)
         self.direct_ba.close = lambda: None             # instance attribute: shadows DirectBA.close for this view only
         self._ba_ptr = L.bsh_slam_direct_ba(self._slam)
+        # what ProcessFrame reads from the host: the full-resolution frame of each stream
+        self._depth_shape = (depth_camera.height << pyramid_level_for_depth, depth_camera.width << pyramid_level_for_depth)
+        self._rgb_shape = (color_camera.height << pyramid_level_for_color, color_camera.width << pyramid_level_for_color, 3)
         self._num_scales = num_scales
 
     def ba(self):
@@ -69,11 +76,23 @@ class BadSlam:
         except Exception:
             pass
 
-    def ProcessFrame(self, frame_index, depth_u16, rgb_u8, force_keyframe=False):
+    def _frame(self, depth_u16, rgb_u8):
+        """The two host images, contiguous and of the sizes the native side reads (camera size << pyramid level)."""
         d = np.ascontiguousarray(depth_u16, np.uint16)
         rgb = np.ascontiguousarray(rgb_u8, np.uint8)
+        if d.shape != self._depth_shape or rgb.size != int(np.prod(self._rgb_shape)) or rgb.shape[0] != self._rgb_shape[0]:
+            raise ValueError(f"frame of depth {d.shape} / rgb {rgb.shape}: expected the full-resolution images {self._depth_shape} / {self._rgb_shape}")
+        return d, rgb
+
+    def ProcessFrame(self, frame_index, depth_u16, rgb_u8, force_keyframe=False):
+        d, rgb = self._frame(depth_u16, rgb_u8)
         self._check(self.L.bsh_slam_process_frame(self._slam, frame_index, d.ctypes.data_as(C.POINTER(C.c_uint16)),
                                                   rgb.ctypes.data_as(C.POINTER(C.c_uint8)), int(force_keyframe)))
+
+    def PreprocessFrame(self, depth_u16, rgb_u8):
+        """The first stage of ProcessFrame alone (upload, input conditioning, preprocessing kernels), finished on return."""
+        d, rgb = self._frame(depth_u16, rgb_u8)
+        self._check(self.L.bsh_slam_preprocess_frame(self._slam, d.ctypes.data_as(C.POINTER(C.c_uint16)), rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
 
     def RunBundleAdjustment(self, frame_index, optimize_depth_intrinsics, optimize_color_intrinsics, optimize_poses, optimize_geometry,
                             min_iterations, max_iterations, window_start=-1, window_end=-1, increase_ba_iteration_count=True):

@@ -156,10 +156,13 @@ int bslam_downsample_images(bslam_context* ctx, void* stream_, const bslam_buffe
       (rc = make_img(downsampled_depth, 4, "downsampled depth", &od)) || (rc = make_img(downsampled_normals, 2, "downsampled normals", &on)) ||
       (rc = make_img(downsampled_color, 1, "downsampled color", &oc)))
     return rc;
-  if (!same_shape(d, n) || !same_shape(od, on) || !same_shape(od, oc) || 2 * od.width > d.width || 2 * od.height > d.height)
+  if (!same_shape(d, n) || !same_shape(od, on) || 2 * od.width > d.width || 2 * od.height > d.height)
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "pyramid level sizes do not fit");
+  // a colour pyramid of its own size (colour camera of another pyramid level than the depth camera) halves like the depth one
+  if (!same_shape(od, oc) && (2 * oc.width > col.width || 2 * oc.height > col.height)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour pyramid level sizes do not fit");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(downsample_kernel, image_grid(od), dim3(256), 0, stream, d, n, col, ctx->tex_mode, od, on, oc);
+  const dim3 grid((unsigned)((std::max(od.width, oc.width) + 255) / 256), (unsigned)std::max(od.height, oc.height));
+  hipLaunchKernelGGL(downsample_kernel, grid, dim3(256), 0, stream, d, n, col, ctx->tex_mode, od, on, oc);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }

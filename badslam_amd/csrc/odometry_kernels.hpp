@@ -67,9 +67,11 @@ __global__ __launch_bounds__(256) void calibrate_depth_kernel(CamConsts c, Img d
     out_depth.at<float>(y, x) = depth;
   }
 }
-// DownsampleImagesCUDAKernel BS/kernel_downsample.cu:105-152
+// DownsampleImagesCUDAKernel BS/kernel_downsample.cu:105-152.  The colour pyramid may have another size than the depth
+// pyramid (a colour camera of another pyramid level): the grid covers the larger of the two outputs.
 __global__ __launch_bounds__(256) void downsample_kernel(Img depth, Img normals, Img color, int tex_mode, Img out_depth, Img out_normals, Img out_color) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x < out_color.width && y < out_color.height) out_color.at<uint8_t>(y, x) = sat_u8(255.f * tex_u8_direct(color, 2 * x + 1.0f, 2 * y + 1.0f, tex_mode) + 0.5f);
   if (x >= out_depth.width || y >= out_depth.height) return;
   float depths[4], depth_sum = 0.f;
   int depth_count = 0;
@@ -93,7 +95,6 @@ __global__ __launch_bounds__(256) void downsample_kernel(Img depth, Img normals,
     out_depth.at<float>(y, x) = depths[closest_index];
     out_normals.at<uint16_t>(y, x) = normals.at<uint16_t>(2 * y + (closest_index >> 1), 2 * x + (closest_index & 1));
   }
-  out_color.at<uint8_t>(y, x) = sat_u8(255.f * tex_u8_direct(color, 2 * x + 1.0f, 2 * y + 1.0f, tex_mode) + 0.5f);
 }
 // ComputeSobelGradientMagnitudeKernel(texture, gradmag) BS/cuda_image_processing.cu:104-143: Sobel magnitude of the luma channel
 // (.w of the uchar4 image, clamp addressing), normalised to 0..255 and truncated

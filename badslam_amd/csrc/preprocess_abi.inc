@@ -10,10 +10,76 @@ static int make_img(const bslam_buffer2d* b, size_t elem, const char* name, Img*
 }
 static bool same_shape(const Img& a, const Img& b) { return a.width == b.width && a.height == b.height; }
 static dim3 image_grid(const Img& i) { return dim3((unsigned)((i.width + 255) / 256), (unsigned)i.height); }
+static dim3 flat_grid(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+// do the byte ranges [base, base + height * pitch) of two images share a byte?
+static bool overlap(const Img& a, const Img& b) {
+  const uintptr_t a0 = (uintptr_t)a.base, a1 = a0 + (size_t)a.height * a.pitch, b0 = (uintptr_t)b.base, b1 = b0 + (size_t)b.height * b.pitch;
+  return a0 < b1 && b0 < a1;
+}
+static bool rows_aligned(const Img& i, size_t bytes) { return ((uintptr_t)i.base | (uintptr_t)i.pitch) % bytes == 0; }
+
+// The pyramid level L (1 ... 3) with in = out * 2^L in both dimensions; 0 if there is none.
+static int pyramid_level(const Img& in, const Img& out) {
+  for (int level = 1; level <= 3; ++level)
+    if (in.width == (int64_t)out.width << level && in.height == (int64_t)out.height << level) return level;
+  return 0;
+}
 
 }  // namespace bslam
 
 extern "C" {
+
+int bslam_median_filter_and_densify_depth(bslam_context* ctx, void* stream_, const bslam_buffer2d* input_depth, const bslam_buffer2d* output_depth) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
+  Img in, out;
+  int rc = make_img(input_depth, 2, "input depth", &in);
+  if (rc) return rc;
+  if ((rc = make_img(output_depth, 2, "output depth", &out))) return rc;
+  if (!same_shape(in, out) || overlap(in, out)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "input and output depth must be buffers of one size that do not overlap");
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  const int quads_per_row = (in.width + 3) / 4;
+  hipLaunchKernelGGL(median_densify_kernel, flat_grid((size_t)quads_per_row * in.height), dim3(256), 0, stream, in, out, quads_per_row,
+                     rows_aligned(in, 8) && rows_aligned(out, 8));
+  BSLAM_HIP_TRY(hipGetLastError());
+  return BSLAM_OK;
+}
+
+int bslam_downscale_depth_median(bslam_context* ctx, void* stream_, const bslam_buffer2d* input_depth, const bslam_buffer2d* output_depth) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
+  Img in, out;
+  int rc = make_img(input_depth, 2, "input depth", &in);
+  if (rc) return rc;
+  if ((rc = make_img(output_depth, 2, "output depth", &out))) return rc;
+  const int level = pyramid_level(in, out);
+  if (!level || overlap(in, out)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "input depth must have 2^L times the output size, L = 1 ... 3, and not overlap the output");
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  const dim3 grid = flat_grid((size_t)out.width * out.height);
+  if (level == 1) hipLaunchKernelGGL(downscale_depth_median_kernel<1>, grid, dim3(256), 0, stream, in, out, rows_aligned(in, 4));
+  else if (level == 2) hipLaunchKernelGGL(downscale_depth_median_kernel<2>, grid, dim3(256), 0, stream, in, out, rows_aligned(in, 8));
+  else hipLaunchKernelGGL(downscale_depth_median_kernel<3>, grid, dim3(256), 0, stream, in, out, rows_aligned(in, 16));
+  BSLAM_HIP_TRY(hipGetLastError());
+  return BSLAM_OK;
+}
+
+int bslam_downscale_rgb(bslam_context* ctx, void* stream_, const bslam_buffer2d* input_rgb, const bslam_buffer2d* output_rgb) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
+  Img in, out;
+  int rc = make_img(input_rgb, 3, "input rgb", &in);
+  if (rc) return rc;
+  if ((rc = make_img(output_rgb, 3, "output rgb", &out))) return rc;
+  const int level = pyramid_level(in, out);
+  if (!level || overlap(in, out)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "input rgb must have 2^L times the output size, L = 1 ... 3, and not overlap the output");
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  const dim3 grid = flat_grid((size_t)out.width * 3 * out.height);
+  if (level == 1) hipLaunchKernelGGL(downscale_rgb_kernel<1>, grid, dim3(256), 0, stream, in, out);
+  else if (level == 2) hipLaunchKernelGGL(downscale_rgb_kernel<2>, grid, dim3(256), 0, stream, in, out);
+  else hipLaunchKernelGGL(downscale_rgb_kernel<3>, grid, dim3(256), 0, stream, in, out);
+  BSLAM_HIP_TRY(hipGetLastError());
+  return BSLAM_OK;
+}
 
 int bslam_compute_brightness(bslam_context* ctx, void* stream_, const bslam_buffer2d* rgb_buffer, const bslam_buffer2d* color_buffer) {
   hipStream_t stream = (hipStream_t)stream_;

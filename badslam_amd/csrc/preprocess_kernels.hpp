@@ -1,5 +1,6 @@
 // preprocess_kernels.hpp -- keyframe preprocessing producers for gfx950: brightness,
-// bilateral depth filter + cutoff, pixel normals, point radii + isolated-pixel removal, min / max depth.
+// bilateral depth filter + cutoff, pixel normals, point radii + isolated-pixel removal, min / max depth; before them
+// the input conditioning of the raw frame (depth median + densify, depth / rgb pyramid level).
 // Replaces BS/cuda_image_processing.cu:165-194 and BS/cuda_depth_processing.cu:42-465.  These define the
 // u16 / half / uchar4 image formats the bundle-adjustment kernels read.  All outputs are
 // integers (u8 / u16 / half bits): they are compared bit for bit with the oracle.
@@ -15,6 +16,152 @@ struct Img {   // pitched 2-D image
   uint8_t* base; uint32_t pitch; int width, height;
   template <class T> __device__ __forceinline__ T& at(int y, int x) const { return *((T*)(base + (size_t)y * pitch) + x); }
 };
+
+// ------------------------------------------------------------------------------------------------
+// Input conditioning of BadSlam::PreprocessFrame (BS/bad_slam.cc:645-685), which the reference runs on the host with a
+// sort per pixel: 3x3 median + densify, median downscale of the raw depth, half-size steps of the rgb image.
+// ------------------------------------------------------------------------------------------------
+
+// The median of the non-zero values of v[0..N) (0 = no measurement); *count = how many there are.  An odd count gives
+// the middle value.  An even count gives the lower middle value if it is strictly nearer to the fp32 mean than the upper
+// one, else the upper one (BS/preprocessing.cc:66-76, LV/image.h:1033-1047): the sum (<= 64 * 65535) is exact in fp32,
+// the division is correctly rounded and the differences are fp32 subtractions.  The middle value is found by a binary
+// search on its 16 bits, counting the values below each candidate, so v is only ever indexed by unrolled loops and
+// stays in registers for N = 4 ... 64 alike.  Undefined for a count of 0.
+template <int N>
+__device__ __forceinline__ uint32_t nonzero_median(const uint32_t (&v)[N], uint32_t* count) {
+  constexpr uint32_t kAbsent = 0x10000u;   // above every u16: never below a candidate
+  uint32_t key[N], n = 0, sum = 0;
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    n += (v[i] != 0) ? 1u : 0u;
+    sum += v[i];
+    key[i] = v[i] ? v[i] : kAbsent;
+  }
+  *count = n;
+  const uint32_t k = (n - 1) >> 1;   // 0-based rank of the (lower) middle value
+  uint32_t low = 0;                  // the largest x with #{key < x} <= k
+  for (int bit = 15; bit >= 0; --bit) {
+    const uint32_t candidate = low | (1u << bit);
+    uint32_t below = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) below += (key[i] < candidate) ? 1u : 0u;
+    if (below <= k) low = candidate;
+  }
+  if (n & 1u) return low;
+  uint32_t at_most = 0, next = kAbsent;   // the upper middle value: `low` again if it occurs often enough, else the next larger value
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    at_most += (key[i] <= low) ? 1u : 0u;
+    next = min(next, (key[i] > low) ? key[i] : kAbsent);
+  }
+  const uint32_t high = (at_most > (n >> 1)) ? low : next;
+  const float average = (float)sum / (float)n;
+  return (fabsf((float)low - average) < fabsf((float)high - average)) ? low : high;
+}
+
+// R consecutive u16 of one row -> v[0..R); wide: one R * 2 byte load (p must be aligned to it)
+template <int R>
+__device__ __forceinline__ void load_depth_run(const uint16_t* p, bool wide, uint32_t* v) {
+  struct alignas(2 * R) Packed { uint32_t d[R / 2]; };
+  if (wide) {
+    const Packed packed = *(const Packed*)p;
+#pragma unroll
+    for (int i = 0; i < R / 2; ++i) { v[2 * i] = packed.d[i] & 0xffffu; v[2 * i + 1] = packed.d[i] >> 16; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < R; ++i) v[i] = p[i];
+  }
+}
+
+// MedianFilterAndDensifyDepthMap BS/preprocessing.cc:40-85, one iteration.  A thread makes 4 adjacent pixels from the
+// 3 x 6 values around them.  Clipping the window at the border = padding with 0, because zeros are not collected.
+// rows_aligned: every row of both images starts on an 8 byte boundary.
+__global__ __launch_bounds__(256) void median_densify_kernel(Img in, Img out, int quads_per_row, bool rows_aligned) {
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = q / quads_per_row, x0 = 4 * (q - y * quads_per_row);
+  if (y >= in.height) return;
+  const bool wide = rows_aligned && x0 + 3 < in.width;
+  uint32_t v[3][6];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) v[r][i] = 0;
+    const int sy = y + r - 1;
+    if (sy < 0 || sy >= in.height) continue;
+    const uint16_t* row = (const uint16_t*)(in.base + (size_t)sy * in.pitch);
+    if (wide) {
+      load_depth_run<4>(row + x0, true, &v[r][1]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+        if (x0 + i < in.width) v[r][1 + i] = row[x0 + i];
+    }
+    if (x0 > 0) v[r][0] = row[x0 - 1];
+    if (x0 + 4 < in.width) v[r][5] = row[x0 + 4];
+  }
+  uint32_t result[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    const uint32_t window[9] = {v[0][p], v[0][p + 1], v[0][p + 2], v[1][p], v[1][p + 1], v[1][p + 2], v[2][p], v[2][p + 1], v[2][p + 2]};
+    uint32_t count;
+    const uint32_t median = nonzero_median<9>(window, &count);
+    result[p] = (count >= 2) ? median : v[1][p + 1];   // kMinNeighbors = 2: otherwise the pixel stays what it is
+  }
+  uint16_t* out_row = (uint16_t*)(out.base + (size_t)y * out.pitch);
+  if (wide) {
+    *(uint2*)(out_row + x0) = make_uint2(result[0] | (result[1] << 16), result[2] | (result[3] << 16));
+  } else {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+      if (x0 + p < out.width) out_row[x0 + p] = (uint16_t)result[p];
+  }
+}
+
+// Image<u16>::DownscaleUsingMedianWhileExcluding(0, ...) LV/image.h:1003-1053 for in = out * 2^L: one output pixel per
+// thread from its 2^L x 2^L block.  rows_aligned: every input row starts on a 2 * 2^L byte boundary.
+template <int L>
+__global__ __launch_bounds__(256) void downscale_depth_median_kernel(Img in, Img out, bool rows_aligned) {
+  constexpr int S = 1 << L;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int y = q / out.width, x = q - y * out.width;
+  if (y >= out.height) return;
+  uint32_t v[S * S];
+#pragma unroll
+  for (int i = 0; i < S; ++i)
+    load_depth_run<S>((const uint16_t*)(in.base + (size_t)(y * S + i) * in.pitch) + (size_t)x * S, rows_aligned, &v[i * S]);
+  uint32_t count;
+  const uint32_t median = nonzero_median<S * S>(v, &count);
+  out.at<uint16_t>(y, x) = (uint16_t)(count ? median : 0u);
+}
+
+// L times Image<Vec3u8>::DownscaleToHalfSize (LV/image.h:929-948, LV/image_cache.h:212-231) in one pass: one output
+// byte (pixel, channel) per thread from its 2^L x 2^L block.  One step is a / 4 + b / 4 + c / 4 + d / 4 with each
+// quotient truncated, so the steps do not collapse into one box mean.
+template <int L>
+__global__ __launch_bounds__(256) void downscale_rgb_kernel(Img in, Img out) {
+  constexpr int S = 1 << L;
+  const int q = blockIdx.x * blockDim.x + threadIdx.x;
+  const int row_bytes = 3 * out.width;
+  const int y = q / row_bytes, b = q - y * row_bytes;
+  if (y >= out.height) return;
+  const int x = b / 3, channel = b - 3 * x;
+  const uint8_t* block = in.base + (size_t)(y * S) * in.pitch + 3 * (size_t)(x * S) + channel;
+  uint32_t v[S][S];
+#pragma unroll
+  for (int i = 0; i < S; ++i)
+#pragma unroll
+    for (int j = 0; j < S; ++j) v[i][j] = block[(size_t)i * in.pitch + 3 * j];
+  // in place: step l leaves its (S >> l + 1)^2 results in the top left corner; v[i][j] is written after its last read
+#pragma unroll
+  for (int l = 0; l < L; ++l)
+#pragma unroll
+    for (int i = 0; i < S / 2; ++i)
+#pragma unroll
+      for (int j = 0; j < S / 2; ++j)
+        if (i < (S >> (l + 1)) && j < (S >> (l + 1))) v[i][j] = v[2 * i][2 * j] / 4 + v[2 * i][2 * j + 1] / 4 + v[2 * i + 1][2 * j] / 4 + v[2 * i + 1][2 * j + 1] / 4;
+  out.base[(size_t)y * out.pitch + b] = (uint8_t)v[0][0];
+}
 
 // ComputeBrightnessKernel BS/cuda_image_processing.cu:165-176: rgb (3 B / pixel) -> rgb + luma
 __global__ __launch_bounds__(256) void brightness_kernel(Img rgb, Img color) {

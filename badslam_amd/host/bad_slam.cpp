@@ -97,8 +97,12 @@ BadSlam::BadSlam(const BadSlamConfigV1& config, const PinholeCamera4f& color_cam
   if (config_.parallel_ba) config_.parallel_ba = false;   // sequential only (see the header)
   if (config_.enable_loop_detection) config_.enable_loop_detection = false;
   if (config_.target_frame_rate != 0) throw std::invalid_argument("BadSlam: real-time pacing (target_frame_rate) is not built");
-  if (config_.median_filter_and_densify_iterations != 0) throw std::invalid_argument("BadSlam: median_filter_and_densify_iterations must be 0");
-  if (config_.pyramid_level_for_depth != 0 || config_.pyramid_level_for_color != 0) throw std::invalid_argument("BadSlam: pyramid levels for depth / colour must be 0");
+  const int depth_level = config_.pyramid_level_for_depth, color_level = config_.pyramid_level_for_color;
+  const int median_iterations = config_.median_filter_and_densify_iterations;
+  if (median_iterations < 0) throw std::invalid_argument("BadSlam: median_filter_and_densify_iterations must be >= 0");
+  if (depth_level < 0 || depth_level > 3 || color_level < 0 || color_level > 3) throw std::invalid_argument("BadSlam: pyramid levels for depth / colour must be 0 ... 3");
+  if (median_iterations > 0 && depth_level > 0)   // BS/bad_slam.cc:667-669
+    throw std::invalid_argument("BadSlam: downscaling and median filtering of the depth maps at once is not built");
   if (config_.keyframe_interval < 1) throw std::invalid_argument("BadSlam: keyframe_interval must be >= 1");
   // BS/bad_slam.cc:121-138
   direct_ba_.reset(new DirectBA(config_.max_surfel_count, config_.raw_to_float_depth, config_.baseline_fx, config_.sparse_surfel_cell_size,
@@ -115,6 +119,10 @@ BadSlam::BadSlam(const BadSlamConfigV1& config, const PinholeCamera4f& color_cam
   normals_buffer_.reset(new DeviceBuffer<u16>(dh, dw));
   radius_buffer_.reset(new DeviceBuffer<u16>(dh, dw));
   pairwise_tracking_buffers_.reset(new PairwiseFrameTrackingBuffers(dw, dh, cw, ch, config_.num_scales));
+  // full-resolution staging of the frame as it arrives, only where the input conditioning is on
+  if (depth_level > 0 || median_iterations > 0) raw_depth_buffer_.reset(new DeviceBuffer<u16>(dh << depth_level, dw << depth_level));
+  if (median_iterations > 1) median_depth_buffer_.reset(new DeviceBuffer<u16>(dh, dw));
+  if (color_level > 0) raw_rgb_buffer_.reset(new DeviceBuffer<u8>(ch << color_level, (cw << color_level) * 3));
 }
 
 BadSlam::~BadSlam() = default;
@@ -123,10 +131,36 @@ void BadSlam::PreprocessFrame(const u16* depth_image, const u8* rgb_image) {
   bslam_context* ctx = direct_ba_->context();
   const PinholeCamera4f& depth_camera = direct_ba_->depth_camera();
   const int dw = depth_camera.width(), cw = direct_ba_->color_camera().width();
-  depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(dw) * sizeof(u16));
-  rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(cw) * 3);
   bslam_buffer2d rgb_pod = rgb_buffer_->ToPod();
   rgb_pod.width = cw;   // 3 bytes per pixel
+  // Input conditioning (:645-685): the frame arrives at full resolution and reaches depth_buffer_ / rgb_buffer_ at the
+  // cameras' sizes.  With the three switches off this is the plain upload.
+  if (raw_depth_buffer_) {
+    raw_depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(raw_depth_buffer_->width()) * sizeof(u16));
+    const bslam_buffer2d raw_pod = raw_depth_buffer_->ToPod(), final_pod = depth_buffer_->ToPod();
+    if (config_.pyramid_level_for_depth > 0) {
+      CheckRc(bslam_downscale_depth_median(ctx, stream_, &raw_pod, &final_pod), "bslam_downscale_depth_median");
+    } else {   // the iterations alternate between the two staging buffers; the last one writes depth_buffer_
+      const int iterations = config_.median_filter_and_densify_iterations;
+      bslam_buffer2d source = raw_pod, spare = median_depth_buffer_ ? median_depth_buffer_->ToPod() : raw_pod;
+      for (int iteration = 0; iteration < iterations; ++iteration) {
+        const bslam_buffer2d target = (iteration == iterations - 1) ? final_pod : spare;
+        CheckRc(bslam_median_filter_and_densify_depth(ctx, stream_, &source, &target), "bslam_median_filter_and_densify_depth");
+        spare = source;
+        source = target;
+      }
+    }
+  } else {
+    depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(dw) * sizeof(u16));
+  }
+  if (raw_rgb_buffer_) {
+    raw_rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(raw_rgb_buffer_->width()));
+    bslam_buffer2d raw_pod = raw_rgb_buffer_->ToPod();
+    raw_pod.width /= 3;
+    CheckRc(bslam_downscale_rgb(ctx, stream_, &raw_pod, &rgb_pod), "bslam_downscale_rgb");
+  } else {
+    rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(cw) * 3);
+  }
   const bslam_buffer2d color_pod = color_buffer_->ToPod(), depth_pod = depth_buffer_->ToPod(), a_pod = filtered_depth_buffer_A_->ToPod(),
                        b_pod = filtered_depth_buffer_B_->ToPod(), normals_pod = normals_buffer_->ToPod(), radius_pod = radius_buffer_->ToPod();
   CheckRc(bslam_compute_brightness(ctx, stream_, &rgb_pod, &color_pod), "bslam_compute_brightness");

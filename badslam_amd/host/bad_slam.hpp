@@ -7,9 +7,14 @@
 // Loop closure: CloseLoop (host/loop_closure.hpp) for a caller-supplied candidate, and an opt-in geometric candidate
 // search (SetLoopCandidateSearch) that closes drift within the tracker's basin; it is not place recognition.
 //
+// Input conditioning (BS/bad_slam.cc:645-685): median_filter_and_densify_iterations, pyramid_level_for_depth and
+// pyramid_level_for_color (each level 0 ... 3) run as kernels on the uploaded full-resolution frame, where the
+// reference works on the host.  As there, median iterations and a depth level exclude each other.  The two streams may
+// use different levels (cameras of different sizes).
+//
 // Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), loop detection (DBoW2 place recognition,
-// opengv RANSAC; enable_loop_detection stays off), median_filter_and_densify_iterations > 0,
-// pyramid_level_for_depth / _color > 0, keyframe merging on low memory.  Those switches must keep their "off" values.
+// opengv RANSAC; enable_loop_detection stays off), keyframe merging on low memory.  Those switches must keep their
+// "off" values.
 #pragma once
 
 #include <memory>
@@ -25,14 +30,22 @@ namespace bslam_host {
 class BadSlam {
  public:
   // config: BS/bad_slam_config.h (defaults of BadSlamConfigV1).  Cameras in the pixel-corner convention of
-  // PinholeCamera4f, already scaled to the pyramid levels in use (level 0 only).
+  // PinholeCamera4f, already scaled to the pyramid levels in use (config.pyramid_level_for_color / _depth).
   BadSlam(const BadSlamConfigV1& config, const PinholeCamera4f& color_camera, const PinholeCamera4f& depth_camera, int device = 0);
   ~BadSlam();
 
   // vis::BadSlam::ProcessFrame (BS/bad_slam.cc:170-282).  depth_image: raw u16 depth (0 = no measurement, as in the
-  // dataset PNGs), rgb_image: 3 bytes per pixel; both HOST arrays of the cameras' sizes.  Frames must arrive with
-  // consecutive indices starting at config.start_frame.
+  // dataset PNGs), rgb_image: 3 bytes per pixel; both HOST arrays at full resolution, i.e. of the cameras' sizes
+  // times 2^level of their stream (width << level, height << level).  Frames must arrive with consecutive indices
+  // starting at config.start_frame.
   void ProcessFrame(int frame_index, const u16* depth_image, const u8* rgb_image, bool force_keyframe = false);
+
+  // The first stage of ProcessFrame on its own (BS/bad_slam.cc:639-760): upload, input conditioning and the preprocessing
+  // kernels, enqueued on the stream.  The images as for ProcessFrame.  It overwrites the buffers of the frame being
+  // processed (depth, normals, radius, colour) and nothing else, so a call between two ProcessFrame calls is harmless
+  // only because the next ProcessFrame uploads its own frame first.  Public for timing the stage.
+  void PreprocessFrame(const u16* depth_image, const u8* rgb_image);
+  hipStream_t stream() const { return stream_; }
 
   // vis::BadSlam::RunBundleAdjustment (BS/bad_slam.cc:481-536)
   void RunBundleAdjustment(u32 frame_index, bool optimize_depth_intrinsics, bool optimize_color_intrinsics, bool optimize_poses, bool optimize_geometry,
@@ -68,7 +81,6 @@ class BadSlam {
   const std::vector<SE3f>& motion_model_base_kf_tr_frame() const { return base_kf_tr_frame_; }
 
  private:
-  void PreprocessFrame(const u16* depth_image, const u8* rgb_image);                       // :639-760
   void PredictFramePose(SE3f* estimate_1, SE3f* estimate_2) const;                          // :763-825
   void RunOdometry(int frame_index);                                                        // :827-950
   std::shared_ptr<Keyframe> CreateKeyframe(int frame_index);                                // :953-1097
@@ -84,6 +96,9 @@ class BadSlam {
   std::unique_ptr<DeviceBuffer<u8>> rgb_buffer_;
   std::unique_ptr<DeviceBuffer<uchar4_t>> color_buffer_;
   std::unique_ptr<DeviceBuffer<u16>> depth_buffer_, filtered_depth_buffer_A_, filtered_depth_buffer_B_, normals_buffer_, radius_buffer_;
+  // full-resolution staging for the input conditioning; null while the switch that needs it is off
+  std::unique_ptr<DeviceBuffer<u8>> raw_rgb_buffer_;
+  std::unique_ptr<DeviceBuffer<u16>> raw_depth_buffer_, median_depth_buffer_;
   std::unique_ptr<PairwiseFrameTrackingBuffers> pairwise_tracking_buffers_;
 
   Keyframe* base_kf_ = nullptr;

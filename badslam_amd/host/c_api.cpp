@@ -620,7 +620,8 @@ int bsh_average_pose(int count, const double* poses7, double* out7) {
 
 // ---- BadSlam front end (host/bad_slam.hpp) ----
 // cfg: [keyframe_interval, max_num_ba_iterations_per_keyframe, num_scales, max_surfel_count, sparse_surfel_cell_size, use_motion_model,
-//       use_geometric_residuals, use_photometric_residuals, do_surfel_updates, use_pcg, optimize_intrinsics, disable_deactivation, start_frame]
+//       use_geometric_residuals, use_photometric_residuals, do_surfel_updates, use_pcg, optimize_intrinsics, disable_deactivation, start_frame,
+//       pyramid_level_for_depth, pyramid_level_for_color, median_filter_and_densify_iterations]
 // fcfg: [raw_to_float_depth, max_depth, baseline_fx]
 void* bsh_slam_create(const int* cfg, const float* fcfg, int color_width, int color_height, const float* color_params, int depth_width, int depth_height,
                       const float* depth_params, int device) {
@@ -630,6 +631,7 @@ void* bsh_slam_create(const int* cfg, const float* fcfg, int color_width, int co
     c.sparse_surfel_cell_size = cfg[4]; c.use_motion_model = cfg[5] != 0; c.use_geometric_residuals = cfg[6] != 0;
     c.use_photometric_residuals = cfg[7] != 0; c.do_surfel_updates = cfg[8] != 0; c.use_pcg = cfg[9] != 0; c.optimize_intrinsics = cfg[10] != 0;
     c.disable_deactivation = cfg[11] != 0; c.start_frame = cfg[12];
+    c.pyramid_level_for_depth = cfg[13]; c.pyramid_level_for_color = cfg[14]; c.median_filter_and_densify_iterations = cfg[15];
     c.raw_to_float_depth = fcfg[0]; c.max_depth = fcfg[1]; c.baseline_fx = fcfg[2];
     return new BadSlam(c, PinholeCamera4f(color_width, color_height, color_params), PinholeCamera4f(depth_width, depth_height, depth_params), device);
   } catch (const std::exception& e) {
@@ -641,6 +643,14 @@ void bsh_slam_destroy(void* slam) { delete static_cast<BadSlam*>(slam); }
 void* bsh_slam_direct_ba(void* slam) { return &static_cast<BadSlam*>(slam)->direct_ba(); }
 int bsh_slam_process_frame(void* slam, int frame_index, const uint16_t* depth, const uint8_t* rgb, int force_keyframe) {
   BSH_TRY(static_cast<BadSlam*>(slam)->ProcessFrame(frame_index, depth, rgb, force_keyframe != 0));
+}
+// BadSlam::PreprocessFrame alone, finished on return (for timing the stage)
+int bsh_slam_preprocess_frame(void* slam, const uint16_t* depth, const uint8_t* rgb) {
+  BSH_TRY({
+    BadSlam* s = static_cast<BadSlam*>(slam);
+    s->PreprocessFrame(depth, rgb);
+    if (hipStreamSynchronize(s->stream()) != hipSuccess) throw std::runtime_error("hipStreamSynchronize failed");
+  });
 }
 int bsh_slam_run_bundle_adjustment(void* slam, int frame_index, int optimize_depth_intrinsics, int optimize_color_intrinsics, int optimize_poses,
                                    int optimize_geometry, int min_iterations, int max_iterations, int window_start, int window_end,

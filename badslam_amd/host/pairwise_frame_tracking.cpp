@@ -36,8 +36,10 @@ PairwiseFrameTrackingBuffers::PairwiseFrameTrackingBuffers(int depth_width, int 
     const int w = static_cast<int>(depth_width / std::pow(2, scale)), h = static_cast<int>(depth_height / std::pow(2, scale));
     base_depth[scale].reset(new DeviceBuffer<float>(h, w));
     tracked_depth[scale].reset(new DeviceBuffer<float>(h, w));
-    base_color[scale].reset(new DeviceBuffer<u8>(h, w));
-    tracked_color[scale].reset(new DeviceBuffer<u8>(h, w));
+    base_color[scale].reset(new DeviceBuffer<u8>(h, w));   // the base colour is transformed into the depth image's geometry
+    // The tracked colour keeps the colour camera's geometry, which the pose kernels sample with the scaled colour camera (the
+    // reference sizes these by the depth image and leaves the other case as a TODO, BS/pairwise_frame_tracking.cc:301-302).
+    tracked_color[scale].reset(new DeviceBuffer<u8>(static_cast<int>(color_height / std::pow(2, scale)), static_cast<int>(color_width / std::pow(2, scale))));
     if (scale >= 1) {
       base_normals[scale].reset(new DeviceBuffer<u16>(h, w));
       tracked_normals[scale].reset(new DeviceBuffer<u16>(h, w));
@@ -53,7 +55,8 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
                         const DeviceBuffer<u16>& base_depth_u16, const DeviceBuffer<u16>& base_normals_l0, const DeviceBuffer<uchar4_t>& base_color_rgba,
                         bool test_different_initial_estimates, const SE3f& init1, const SE3f& init2, SE3f* out_base_T_frame, int* iterations_per_scale,
                         bool use_pyramid_level_0, bool use_gradmag) {
-  if (depth_camera.width() != color_camera.width()) throw std::invalid_argument("TrackFramePairwise: depth and colour images must have the same size here");
+  if (!use_pyramid_level_0 && (depth_camera.width() != color_camera.width() || depth_camera.height() != color_camera.height()))
+    throw std::invalid_argument("TrackFramePairwise: without pyramid level 0, depth and colour images must have the same size");   // :303-323 builds level 1 of both at once
   const int num_scales = buffers->num_scales;
   const bslam_camera4f color_cam = color_camera.pod(), depth_cam = depth_camera.pod();
   std::vector<bslam_buffer2d> base_depth(num_scales), base_normals(num_scales), base_color(num_scales), tracked_depth(num_scales),
@@ -151,7 +154,6 @@ void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vec
                                 bool use_depth_residuals, bool use_descriptor_residuals, const std::vector<TrackedFrameImages>& tracked,
                                 const DeviceBuffer<u16>& base_depth_u16, const DeviceBuffer<u16>& base_normals_l0, const DeviceBuffer<uchar4_t>& base_color_rgba,
                                 const std::vector<SE3f>& inits, std::vector<SE3f>* out_base_T_frame, std::vector<std::vector<int>>* iterations_per_scale) {
-  if (depth_camera.width() != color_camera.width()) throw std::invalid_argument("TrackFramesPairwiseBatched: depth and colour images must have the same size here");
   const int pairs = static_cast<int>(tracked.size());
   if (pairs < 1 || pairs > BSLAM_MAX_PAIR_BATCH) throw std::invalid_argument("TrackFramesPairwiseBatched: 1 to BSLAM_MAX_PAIR_BATCH tracked frames");
   if (static_cast<int>(inits.size()) != pairs) throw std::invalid_argument("TrackFramesPairwiseBatched: one initial estimate per tracked frame");

@@ -11,7 +11,8 @@
 
 namespace bslam_host {
 
-// vis::PairwiseFrameTrackingBuffers (BS/pairwise_frame_tracking.h): per-scale images of both frames
+// vis::PairwiseFrameTrackingBuffers (BS/pairwise_frame_tracking.h): per-scale images of both frames.  Everything has the
+// depth image's size halved per scale, except tracked_color, which has the colour image's (the two cameras may differ).
 struct PairwiseFrameTrackingBuffers {
   PairwiseFrameTrackingBuffers(int depth_width, int depth_height, int color_width, int color_height, int num_scales);
   int num_scales;

@@ -489,6 +489,29 @@ int bslam_compact_surfels(
 /* These write the u16 / half / uchar4 keyframe images the bundle adjuster reads.  Buffers are device
  * memory; input and output of one call must not alias. */
 
+/* Input conditioning of the raw frame (BadSlam::PreprocessFrame, BS/bad_slam.cc:645-685; host code in the
+ * reference).  Like the other producers: launched on `stream` without synchronisation, results ordered on it.
+ * Input and output must not share a byte ([address, address + height * pitch) of each): invalid argument. */
+
+/* One iteration of MedianFilterAndDensifyDepthMap (BS/preprocessing.cc:40-85): per pixel the median of the
+ * non-zero values of its 3x3 window, clipped at the border; a window with fewer than 2 of them leaves the pixel
+ * as it is.  With an even count: the lower middle value if it is strictly nearer to the fp32 mean than the
+ * upper one, else the upper one.  u16 images of one size. */
+int bslam_median_filter_and_densify_depth(bslam_context* ctx, void* stream,
+                                          const bslam_buffer2d* input_depth, const bslam_buffer2d* output_depth);
+
+/* Image<u16>::DownscaleUsingMedianWhileExcluding(0, ...) (LV/image.h:1003-1053) by a pyramid level L = 1 ... 3,
+ * inferred from the shapes (input = output * 2^L in both dimensions): per 2^L x 2^L block the median of its
+ * non-zero values by the rule above, 0 for a block of zeros. */
+int bslam_downscale_depth_median(bslam_context* ctx, void* stream,
+                                 const bslam_buffer2d* input_depth, const bslam_buffer2d* output_depth);
+
+/* L = 1 ... 3 (inferred as above) successive Image<Vec3u8>::DownscaleToHalfSize steps (LV/image.h:929-948,
+ * ImagePyramid LV/image_cache.h:212-231) in one launch; a step is a/4 + b/4 + c/4 + d/4 per channel, each
+ * quotient truncated.  Both images have 3 bytes per pixel (width = pixels, as in bslam_compute_brightness). */
+int bslam_downscale_rgb(bslam_context* ctx, void* stream,
+                        const bslam_buffer2d* input_rgb, const bslam_buffer2d* output_rgb);
+
 /* Replaces ComputeBrightnessCUDA (BS/cuda_image_processing.cuh, kernel BS/cuda_image_processing.cu:165-194):
  * rgb_buffer has 3 bytes per pixel, color_buffer 4 (r, g, b, luma). */
 int bslam_compute_brightness(bslam_context* ctx, void* stream,
@@ -541,7 +564,8 @@ int bslam_calibrate_depth_and_transform_color_to_depth(
     bslam_context* ctx, void* stream, const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
     const bslam_depth_params* depth_params, const bslam_buffer2d* depth_buffer, const bslam_buffer2d* color_u8,
     const bslam_buffer2d* out_depth, const bslam_buffer2d* out_color);
-/* Replaces DownsampleImagesCUDA (BS/kernel_downsample.cu:105-234). */
+/* Replaces DownsampleImagesCUDA (BS/kernel_downsample.cu:105-234).  downsampled_color may have another size than
+ * downsampled_depth (the colour camera of another pyramid level): it then halves color_u8 on its own. */
 int bslam_downsample_images(
     bslam_context* ctx, void* stream, const bslam_buffer2d* depth_buffer, const bslam_buffer2d* normals_buffer,
     const bslam_buffer2d* color_u8, const bslam_buffer2d* downsampled_depth,

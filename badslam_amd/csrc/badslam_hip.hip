@@ -20,6 +20,14 @@
 #include "pose_kernels.hpp"
 #include "cost_kernels.hpp"
 
+// surfels per thread of the geometry iteration: geometry-only / photometric (tuning builds override them)
+#ifndef BSLAM_GEOM_R
+#define BSLAM_GEOM_R 3
+#endif
+#ifndef BSLAM_GEOM_R_DESC
+#define BSLAM_GEOM_R_DESC 2
+#endif
+
 namespace bslam {
 
 thread_local std::string g_last_error;
@@ -1196,7 +1204,7 @@ int bslam_update_surfel_normals(
   if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, 1, keyframe_count, &work, false))) return rc;
   const Schedule sc = work.sc;
   // the normals pass of the geometry iteration on its own: one launch over the whole keyframe list (first and last chunk)
-  hipLaunchKernelGGL((geometry_chunk_kernel<1, 0>), dim3(8u * sc.slots_per_xcd), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, 0, keyframe_count, 1, 1, sc, 0u,
+  hipLaunchKernelGGL((geometry_normals_kernel<1>), dim3(8u * sc.slots_per_xcd), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, 0, keyframe_count, 1, 1, sc,
                      surfel_rows_rw(work, surfels, active_surfels, surfels_size), (float*)nullptr, 0u);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
@@ -1224,64 +1232,46 @@ int bslam_optimize_geometry_iteration(
   int rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, use_descriptor_residuals != 0,
                                 surfels_size, surfels, &c, active_surfels);
   if (rc) return rc;
-#ifndef BSLAM_GEOM_R
-#define BSLAM_GEOM_R 3
-#endif
-#ifndef BSLAM_GEOM_R_DESC
-#define BSLAM_GEOM_R_DESC 2
-#endif
   SurfelWork work;
   if ((rc = prepare_surfels(ctx, stream, surfels, surfels_size, use_descriptor_residuals ? BSLAM_GEOM_R_DESC : BSLAM_GEOM_R, keyframe_count, &work, use_descriptor_residuals != 0))) return rc;
   const Schedule sc = work.sc;
   const dim3 grid(8u * sc.slots_per_xcd), block(256);
   const KfDev* kfs = (const KfDev*)ctx->kf_table.ptr;
   const SurfelRowsRW rows = surfel_rows_rw(work, surfels, active_surfels, surfels_size);
+  // One launch per pass over all surfels and keyframes: the geometry-only iteration is a single fused launch, the photometric
+  // one a normals launch and a joint position + descriptor launch.  (Round 1 split the work into resident grids and keyframe
+  // chunks of 128 to keep the workgroups in lockstep on the keyframe table; with the per-surfel work order that costs 24 % at
+  // K = 200 geometry-only, 22.0 against 16.5 ms per K = 300 photometric iteration, and nothing is gained by chunks, K = 1000
+  // included.)  bslam_set_geometry_keyframe_chunk still selects chunked launches, one pass after the other, with the
+  // per-surfel sums carried in library scratch: bit-identical results.
+  const int kf_chunk_set = equal_keyframe_chunks(keyframe_count, ctx->geom_kf_chunk < 0 ? 0 : ctx->geom_kf_chunk);
+  const int kf_chunk = kf_chunk_set > 0 ? kf_chunk_set : keyframe_count;
+  const bool chunked = keyframe_count > kf_chunk;
+  float* acc = nullptr;
+  uint32_t acc_pitch = 0;
+  if (chunked) {
+    acc_pitch = (surfels_size + 63u) & ~63u;
+    if ((rc = ctx->exchange.reserve((size_t)acc_pitch * (use_descriptor_residuals ? 8 : 4) * sizeof(float)))) return rc;
+    acc = (float*)ctx->exchange.ptr;
+  }
   {
-  ProfScope prof(ctx, stream, 1);
-  if (!use_descriptor_residuals) {
-    // One launch over all surfels and keyframes.  (Round 1 split the work into resident grids and keyframe chunks of 128 to keep
-    // the workgroups in lockstep on the keyframe table; with the per-surfel work order that costs 24 % at K = 200 and nothing is
-    // gained by chunks, K = 1000 included.  bslam_set_geometry_keyframe_chunk still selects chunked launches, per-surfel sums
-    // carried in library scratch, bit-identical results.)
-    const int kf_chunk = equal_keyframe_chunks(keyframe_count, ctx->geom_kf_chunk < 0 ? 0 : ctx->geom_kf_chunk);
-    if (kf_chunk <= 0 || keyframe_count <= kf_chunk) {
-      hipLaunchKernelGGL((geometry_position_kernel<BSLAM_GEOM_R>), grid, block, 0, stream, c, kfs, keyframe_count, sc, 0u, rows);
+    ProfScope prof(ctx, stream, 1);
+    if (!use_descriptor_residuals && !chunked) {
+      hipLaunchKernelGGL((geometry_position_kernel<BSLAM_GEOM_R>), grid, block, 0, stream, c, kfs, keyframe_count, sc, rows);
     } else {
-      const uint32_t acc_pitch = (surfels_size + 63u) & ~63u;
-      if ((rc = ctx->exchange.reserve((size_t)acc_pitch * 4 * sizeof(float)))) return rc;
-      float* acc = (float*)ctx->exchange.ptr;
+      void (*passes[2])(CamConsts, const KfDev*, int, int, int, int, Schedule, SurfelRowsRW, float*, uint32_t) = {
+          geometry_normals_kernel<BSLAM_GEOM_R>, geometry_position_chunk_kernel<BSLAM_GEOM_R>};
+      if (use_descriptor_residuals) {
+        passes[0] = geometry_normals_kernel<BSLAM_GEOM_R_DESC>;
+        passes[1] = use_depth_residuals ? geometry_desc_chunk_kernel<BSLAM_GEOM_R_DESC, true> : geometry_desc_chunk_kernel<BSLAM_GEOM_R_DESC, false>;
+      }
       for (int pass = 0; pass < 2; ++pass) {
         for (int k0 = 0; k0 < keyframe_count; k0 += kf_chunk) {
           const int k1 = std::min(keyframe_count, k0 + kf_chunk);
-          if (pass == 0) hipLaunchKernelGGL((geometry_chunk_kernel<BSLAM_GEOM_R, 0>), grid, block, 0, stream, c, kfs, k0, k1, k0 == 0, k1 == keyframe_count, sc, 0u, rows, acc, acc_pitch);
-          else hipLaunchKernelGGL((geometry_chunk_kernel<BSLAM_GEOM_R, 1>), grid, block, 0, stream, c, kfs, k0, k1, k0 == 0, k1 == keyframe_count, sc, 0u, rows, acc, acc_pitch);
+          hipLaunchKernelGGL(passes[pass], grid, block, 0, stream, c, kfs, k0, k1, k0 == 0, k1 == keyframe_count, sc, rows, acc, acc_pitch);
         }
       }
     }
-  }
-  else {
-    // photometric iteration: BSLAM_GEOM_R_DESC surfels per thread, one launch per pass over all surfels and keyframes (K = 300:
-    // 22.0 ms per iteration with resident-grid launches, 16.5 ms with one); optional keyframe chunks with the per-surfel sums
-    // carried in scratch (4 floats for the normals pass, 8 for the joint position + descriptor pass)
-    const int kf_chunk_set = equal_keyframe_chunks(keyframe_count, ctx->geom_kf_chunk < 0 ? 0 : ctx->geom_kf_chunk);
-    const int kf_chunk = kf_chunk_set > 0 ? kf_chunk_set : keyframe_count;
-    float* acc = nullptr;
-    uint32_t acc_pitch = 0;
-    if (keyframe_count > kf_chunk) {
-      acc_pitch = (surfels_size + 63u) & ~63u;
-      if ((rc = ctx->exchange.reserve((size_t)acc_pitch * 8 * sizeof(float)))) return rc;
-      acc = (float*)ctx->exchange.ptr;
-    }
-    for (int pass = 0; pass < 2; ++pass) {
-      for (int k0 = 0; k0 < keyframe_count; k0 += kf_chunk) {
-        const int k1 = std::min(keyframe_count, k0 + kf_chunk);
-        const int fc = k0 == 0, lc = k1 == keyframe_count;
-        if (pass == 0) hipLaunchKernelGGL((geometry_desc_chunk_kernel<BSLAM_GEOM_R_DESC, 0, true>), grid, block, 0, stream, c, kfs, k0, k1, fc, lc, sc, 0u, rows, acc, acc_pitch);
-        else if (use_depth_residuals) hipLaunchKernelGGL((geometry_desc_chunk_kernel<BSLAM_GEOM_R_DESC, 1, true>), grid, block, 0, stream, c, kfs, k0, k1, fc, lc, sc, 0u, rows, acc, acc_pitch);
-        else hipLaunchKernelGGL((geometry_desc_chunk_kernel<BSLAM_GEOM_R_DESC, 1, false>), grid, block, 0, stream, c, kfs, k0, k1, fc, lc, sc, 0u, rows, acc, acc_pitch);
-      }
-    }
-  }
   }
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;

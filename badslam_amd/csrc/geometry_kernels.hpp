@@ -291,17 +291,10 @@ __global__ __launch_bounds__(256) void count_pairs_kernel(CamConsts c, const KfD
     const f3 gn = unpack_normal(s.normal[i]);
     for (int k = 0; k < kf_count; ++k) {
       const KfDev kf = kfs[k];
-      const M34& T = kf.frame_T_global;
-      f3 l;
-      l.z = tr_row(T.m[8], T.m[9], T.m[10], T.m[11], gp);
-      if (l.z <= 0.f) continue;
-      l.x = tr_row(T.m[0], T.m[1], T.m[2], T.m[3], gp);
-      l.y = tr_row(T.m[4], T.m[5], T.m[6], T.m[7], gp);
-      const f2 pxy = project(c.fx, c.fy, c.cx, c.cy, l);
-      if (pxy.x < 0 || pxy.y < 0 || f2i(pxy.x) >= c.width || f2i(pxy.y) >= c.height) continue;
-      inb += 1;
       Proj p;
-      if (project_and_associate(c, kf, gp, gn, &p)) assoc += 1;
+      if (!project_to_pixel(c, kf, gp, &p)) continue;
+      inb += 1;
+      if (associate_with_record(c, kf, gn, load_record(c, kf, p), &p)) assoc += 1;
     }
   }
   inb = wave_sum_u32(inb);
@@ -348,235 +341,224 @@ __global__ __launch_bounds__(256) void residual_probe_kernel(CamConsts c, const 
   for (int k = 0; k < 8; ++k) out[(size_t)i * 8 + k] = o[k];
 }
 
-// Geometry-only iteration (normals, then position along the normal: UpdateSurfelNormalsCUDA + OptimizeGeometryIterationCUDA,
-// BS/kernel_opt_geometry.cc:39-78, 137-169; kernels BS/kernel_opt_geometry.cu:417-459, 487-507, 527-597) with R surfels per thread,
-// interleaved keyframe by keyframe: R independent gather chains per thread, per-surfel sums formed in keyframe order -- the order in
-// which the reference's serialised per-keyframe launches add their terms.  One launch covers all surfels (first_i = 0); round 1 launched it
-// one resident grid at a time to keep the workgroups in lockstep on the keyframe table, which the per-surfel work order made
-// unnecessary (first_i = first slot of every XCD's range handled by a launch is kept for that use).
+// ---------------------------------------------------------------------------------------------
+// Geometry iteration (UpdateSurfelNormalsCUDA + OptimizeGeometryIterationCUDA, BS/kernel_opt_geometry.cc:39-78, 137-169; kernels
+// BS/kernel_opt_geometry.cu:118-231, 273-361, 417-459, 487-507, 527-597): a thread owns R surfels, one of each of the R granules
+// of its work slot, and walks the keyframes with them interleaved -- R independent gather chains per thread, per-surfel sums
+// formed in keyframe order, the order in which the reference's serialised per-keyframe launches add their terms.  One launch
+// covers all surfels.  The pieces below are shared by every geometry kernel; a kernel that can be launched once per chunk of
+// keyframes carries its per-surfel sums from launch to launch in library scratch (acc), which does not change the order of the
+// additions: same bits as one launch over the whole list.
+// ---------------------------------------------------------------------------------------------
+// The R surfels of a thread: column, "exists and is active", position and decoded normal (of column 0 where !on).
 template <int R>
-__global__ __launch_bounds__(256) void geometry_position_kernel(CamConsts c_in, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, uint32_t first_i,
-                                                               SurfelRowsRW s) {
-  CamConsts c = c_in;
-  uint32_t slot;
-  if (!slot_of_block(sc, blockIdx.x + (first_i << 3), &slot)) return;
+struct SurfelSet {
   uint32_t idx[R];
   bool on[R];
   f3 gp[R], gn[R];
+};
+template <int R>
+__device__ __forceinline__ void load_surfel_set(const Schedule& sc, uint32_t slot, const SurfelRowsRW& s, SurfelSet<R>* t) {
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    idx[r] = surfel_of_slot(sc, slot, r, R);
-    on[r] = idx[r] < s.size;
-    if (on[r]) on[r] = (s.active[column_of(s, idx[r])] & BSLAM_SURFEL_ACTIVE_FLAG) != 0;
-    const uint32_t j = on[r] ? idx[r] : 0;
-    gp[r] = mk3(s.x[j], s.y[j], s.z[j]);
-    gn[r] = unpack_normal(s.normal[j]);
+    t->idx[r] = surfel_of_slot(sc, slot, r, R);
+    t->on[r] = t->idx[r] < s.size;
+    if (t->on[r]) t->on[r] = (s.active[column_of(s, t->idx[r])] & BSLAM_SURFEL_ACTIVE_FLAG) != 0;
+    const uint32_t j = t->on[r] ? t->idx[r] : 0;
+    t->gp[r] = mk3(s.x[j], s.y[j], s.z[j]);
+    t->gn[r] = unpack_normal(s.normal[j]);
   }
+}
+
+// kAcc per-surfel sums between the launches of a chunked pass: row q of acc, column = the surfel's.
+template <int kAcc, int R>
+__device__ __forceinline__ void carry_load(const SurfelSet<R>& t, int first_chunk, const float* __restrict__ acc, uint32_t acc_pitch, float (&a)[R][kAcc]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+#pragma unroll
+    for (int q = 0; q < kAcc; ++q) a[r][q] = (!first_chunk && t.on[r]) ? acc[(size_t)q * acc_pitch + t.idx[r]] : 0.f;
+  }
+}
+template <int kAcc, int R>
+__device__ __forceinline__ void carry_store(const SurfelSet<R>& t, const float (&a)[R][kAcc], float* __restrict__ acc, uint32_t acc_pitch) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (!t.on[r]) continue;
+#pragma unroll
+    for (int q = 0; q < kAcc; ++q) acc[(size_t)q * acc_pitch + t.idx[r]] = a[r][q];
+  }
+}
+
+// Normals: a[r] += (global_R_frame * normal of the associated pixel, 1) over the keyframes of [k_begin, k_end) ...
+template <int R>
+__device__ __forceinline__ void normals_walk(const CamConsts& c, const KfDev* __restrict__ kfs, int k_begin, int k_end, const Schedule& sc, uint32_t slot,
+                                             const SurfelSet<R>& t, float (&a)[R][4]) {
+  BSLAM_FOR_VISITED_KEYFRAMES(k, k_begin, k_end, R) {
+    KfDev kf = kfs[k];
+    BSLAM_HOIST_KF_TRANSLATION(kf);
+    const float* Rm = kf.global_R_frame;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      Proj p;
+      if (!t.on[r] || !project_and_associate(c, kf, t.gp[r], t.gn[r], &p)) continue;
+      const f3 ln = p.pixel_normal;
+      a[r][0] += rot_row(Rm[0], Rm[1], Rm[2], ln);
+      a[r][1] += rot_row(Rm[3], Rm[4], Rm[5], ln);
+      a[r][2] += rot_row(Rm[6], Rm[7], Rm[8], ln);
+      a[r][3] += 1.f;
+    }
+  }
+}
+// ... and the mean of the sums, packed, as the surfel's new normal; t->gn becomes what a reader of the stored normal decodes.
+template <int R>
+__device__ __forceinline__ void normals_finish(const SurfelRowsRW& s, const float (&a)[R][4], SurfelSet<R>* t) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (t->on[r] && a[r][3] >= 1) {
+      const float inv = 1.f / a[r][3];
+      const uint32_t packed = pack_normal(mk3(inv * a[r][0], inv * a[r][1], inv * a[r][2]));
+      store_normal(s, t->idx[r], packed);
+      t->gn[r] = unpack_normal(packed);
+    }
+  }
+}
+
+// Position along the normal from the depth residuals alone: one associated pair's term of H = sum w J^2, b = sum w J r ...
+__device__ __forceinline__ void depth_position_term(const CamConsts& c, const Proj& p, float* H, float* b) {
+  const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, p.n_local, c.baseline_fx);
+  const float dj = depth_position_jacobian(inv_stddev);
+  const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
+  const float raw = depth_residual(inv_stddev, p.n_local, lu, p.local);
+  const float w = depth_weight(raw);
+  const float wj = w * dj;
+  *H += wj * dj;
+  *b += wj * raw;
+}
+// ... and the step t = -b / H along the normal (a[r] = H, b).
+template <int R>
+__device__ __forceinline__ void position_step(const SurfelRowsRW& s, const SurfelSet<R>& t, const float (&a)[R][2]) {
+#pragma unroll
+  for (int r = 0; r < R; ++r) {
+    if (t.on[r] && a[r][0] > 1e-6f) {
+      const float step = -1.f * a[r][1] / a[r][0];
+      store_position(s, t.idx[r], add3(t.gp[r], scale3(step, t.gn[r])));
+    }
+  }
+}
+
+// The normals pass: bslam_update_surfel_normals (R = 1), pass 0 of the photometric iteration and of the chunked geometry-only
+// iteration.  Chunkable: acc = 4 floats per surfel.
+template <int R>
+__global__ __launch_bounds__(256) void geometry_normals_kernel(CamConsts c, const KfDev* __restrict__ kfs, int k_begin, int k_end, int first_chunk, int last_chunk,
+                                                              Schedule sc, SurfelRowsRW s, float* __restrict__ acc, uint32_t acc_pitch) {
+  uint32_t slot;
+  if (!slot_of_block(sc, blockIdx.x, &slot)) return;
+  SurfelSet<R> t;
+  load_surfel_set(sc, slot, s, &t);
+  float a[R][4];
+  carry_load(t, first_chunk, acc, acc_pitch, a);
+  normals_walk(c, kfs, k_begin, k_end, sc, slot, t, a);
+  if (last_chunk) normals_finish(s, a, &t);
+  else carry_store(t, a, acc, acc_pitch);
+}
+
+// The geometry-only iteration in one launch, normals then position with the new normals: the default.
+template <int R>
+__global__ __launch_bounds__(256) void geometry_position_kernel(CamConsts c_in, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRowsRW s) {
+  CamConsts c = c_in;
+  uint32_t slot;
+  if (!slot_of_block(sc, blockIdx.x, &slot)) return;
+  SurfelSet<R> t;
+  load_surfel_set(sc, slot, s, &t);
   BSLAM_HOIST_DEPTH_CAM_CENTRE(c);
   BSLAM_HOIST_UNPROJECTION_CENTRE(c);
   {
-    float sx[R], sy[R], sz[R], cnt[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) sx[r] = sy[r] = sz[r] = cnt[r] = 0.f;
-    BSLAM_FOR_VISITED_KEYFRAMES(k, 0, kf_count, R) {
-      KfDev kf = kfs[k];
-      BSLAM_HOIST_KF_TRANSLATION(kf);
-      const float* Rm = kf.global_R_frame;
-#pragma unroll
-      for (int r = 0; r < R; ++r) {
-        Proj p;
-        if (!on[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
-        const f3 ln = p.pixel_normal;
-        sx[r] += rot_row(Rm[0], Rm[1], Rm[2], ln);
-        sy[r] += rot_row(Rm[3], Rm[4], Rm[5], ln);
-        sz[r] += rot_row(Rm[6], Rm[7], Rm[8], ln);
-        cnt[r] += 1.f;
-      }
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      if (on[r] && cnt[r] >= 1) {
-        const float inv = 1.f / cnt[r];
-        const uint32_t packed = pack_normal(mk3(inv * sx[r], inv * sy[r], inv * sz[r]));
-        store_normal(s, idx[r], packed);
-        gn[r] = unpack_normal(packed);
-      }
-    }
+    float n[R][4] = {};
+    normals_walk(c, kfs, 0, kf_count, sc, slot, t, n);
+    normals_finish(s, n, &t);
   }
-  float H[R], b[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) H[r] = b[r] = 0.f;
+  float a[R][2] = {};
   BSLAM_FOR_VISITED_KEYFRAMES(k, 0, kf_count, R) {
     KfDev kf = kfs[k];
     BSLAM_HOIST_KF_TRANSLATION(kf);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       Proj p;
-      if (!on[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
-      const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, p.n_local, c.baseline_fx);
-      const float dj = depth_position_jacobian(inv_stddev);
-      const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
-      const float raw = depth_residual(inv_stddev, p.n_local, lu, p.local);
-      const float w = depth_weight(raw);
-      const float wj = w * dj;
-      H[r] += wj * dj;
-      b[r] += wj * raw;
+      if (t.on[r] && project_and_associate(c, kf, t.gp[r], t.gn[r], &p)) depth_position_term(c, p, &a[r][0], &a[r][1]);
     }
   }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (on[r] && H[r] > 1e-6f) {
-      const float t = -1.f * b[r] / H[r];
-      const f3 np = add3(gp[r], scale3(t, gn[r]));
-      store_position(s, idx[r], np);
-    }
-  }
+  position_step(s, t, a);
 }
 
-// The same two passes for long keyframe lists, one launch per chunk of keyframes: the per-surfel sums travel between the
-// launches in library scratch (acc: 4 floats per surfel).  Sums are still formed in keyframe order: same bits as the
-// single-launch kernel.  (Selected by bslam_set_geometry_keyframe_chunk; the default since the per-surfel work order is one
-// launch over the whole list.)  pass 0: normals (acc = sx, sy, sz, count), pass 1: position (acc = H, b).
-template <int R, int kPass>
-__global__ __launch_bounds__(256) void geometry_chunk_kernel(CamConsts c, const KfDev* __restrict__ kfs, int k_begin, int k_end, int first_chunk, int last_chunk,
-                                                            Schedule sc, uint32_t first_i, SurfelRowsRW s, float* __restrict__ acc, uint32_t acc_pitch) {
+// Its position pass on its own, chunkable (acc = 2 floats per surfel): pass 1 of the chunked geometry-only iteration
+// (bslam_set_geometry_keyframe_chunk), after geometry_normals_kernel has run over the whole list.
+template <int R>
+__global__ __launch_bounds__(256) void geometry_position_chunk_kernel(CamConsts c, const KfDev* __restrict__ kfs, int k_begin, int k_end, int first_chunk, int last_chunk,
+                                                                     Schedule sc, SurfelRowsRW s, float* __restrict__ acc, uint32_t acc_pitch) {
   uint32_t slot;
-  if (!slot_of_block(sc, blockIdx.x + (first_i << 3), &slot)) return;
-  uint32_t idx[R];
-  bool on[R];
-  f3 gp[R], gn[R];
-  float a0[R], a1[R], a2[R], a3[R];
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    idx[r] = surfel_of_slot(sc, slot, r, R);
-    on[r] = idx[r] < s.size;
-    if (on[r]) on[r] = (s.active[column_of(s, idx[r])] & BSLAM_SURFEL_ACTIVE_FLAG) != 0;
-    const uint32_t j = on[r] ? idx[r] : 0;
-    gp[r] = mk3(s.x[j], s.y[j], s.z[j]);
-    gn[r] = unpack_normal(s.normal[j]);
-    a0[r] = a1[r] = a2[r] = a3[r] = 0.f;
-    if (!first_chunk && on[r]) {
-      a0[r] = acc[j]; a1[r] = acc[(size_t)acc_pitch + j];
-      if (kPass == 0) { a2[r] = acc[(size_t)2 * acc_pitch + j]; a3[r] = acc[(size_t)3 * acc_pitch + j]; }
-    }
-  }
+  if (!slot_of_block(sc, blockIdx.x, &slot)) return;
+  SurfelSet<R> t;
+  load_surfel_set(sc, slot, s, &t);
+  float a[R][2];
+  carry_load(t, first_chunk, acc, acc_pitch, a);
   BSLAM_FOR_VISITED_KEYFRAMES(k, k_begin, k_end, R) {
     const KfDev kf = kfs[k];
-    const float* Rm = kf.global_R_frame;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       Proj p;
-      if (!on[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
-      if (kPass == 0) {
-        const f3 ln = p.pixel_normal;
-        a0[r] += rot_row(Rm[0], Rm[1], Rm[2], ln);
-        a1[r] += rot_row(Rm[3], Rm[4], Rm[5], ln);
-        a2[r] += rot_row(Rm[6], Rm[7], Rm[8], ln);
-        a3[r] += 1.f;
-      } else {
-        const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, p.n_local, c.baseline_fx);
-        const float dj = depth_position_jacobian(inv_stddev);
-        const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);
-        const float raw = depth_residual(inv_stddev, p.n_local, lu, p.local);
-        const float w = depth_weight(raw);
-        const float wj = w * dj;
-        a0[r] += wj * dj;
-        a1[r] += wj * raw;
-      }
+      if (t.on[r] && project_and_associate(c, kf, t.gp[r], t.gn[r], &p)) depth_position_term(c, p, &a[r][0], &a[r][1]);
     }
   }
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    if (!on[r]) continue;
-    const uint32_t j = idx[r];
-    if (!last_chunk) {
-      acc[j] = a0[r]; acc[(size_t)acc_pitch + j] = a1[r];
-      if (kPass == 0) { acc[(size_t)2 * acc_pitch + j] = a2[r]; acc[(size_t)3 * acc_pitch + j] = a3[r]; }
-    } else if (kPass == 0) {
-      if (a3[r] >= 1) {
-        const float inv = 1.f / a3[r];
-        store_normal(s, j, pack_normal(mk3(inv * a0[r], inv * a1[r], inv * a2[r])));
-      }
-    } else if (a0[r] > 1e-6f) {
-      const float t = -1.f * a1[r] / a0[r];
-      const f3 np = add3(gp[r], scale3(t, gn[r]));
-      store_position(s, j, np);
-    }
-  }
+  if (last_chunk) position_step(s, t, a);
+  else carry_store(t, a, acc, acc_pitch);
 }
 
-// The joint position + descriptor iteration (kMode 2 of geometry_kernel) in the same launch shape as geometry_chunk_kernel: R surfels
-// per thread walked keyframe by keyframe, the keyframe list optionally cut into chunks whose per-surfel sums
-// travel in library scratch (acc: 4 floats per surfel for the normals pass, 8 for the joint pass).  Sums are formed in keyframe
-// order: same bits as geometry_kernel<2, kDepth>.  kPass 0: normals (= geometry_chunk_kernel's pass 0, repeated here so that a
-// photometric iteration needs no geometry-only instantiation of a different R); kPass 1: position + descriptors
-// (BS/kernel_opt_geometry.cu:118-231, 273-361).
+// Pass 1 of the photometric iteration: position + descriptors jointly (BS/kernel_opt_geometry.cu:118-231, 273-361), after
+// geometry_normals_kernel.  Chunkable: acc = 8 floats per surfel.
 #ifndef BSLAM_GEOM_DESC_WAVES
 #define BSLAM_GEOM_DESC_WAVES 4
 #endif
-template <int R, int kPass, bool kDepth>
+template <int R, bool kDepth>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BSLAM_GEOM_DESC_WAVES))) void geometry_desc_chunk_kernel(CamConsts c_in, const KfDev* __restrict__ kfs, int k_begin, int k_end, int first_chunk, int last_chunk,
-                                                                 Schedule sc, uint32_t first_i, SurfelRowsRW s, float* __restrict__ acc, uint32_t acc_pitch) {
+                                                                 Schedule sc, SurfelRowsRW s, float* __restrict__ acc, uint32_t acc_pitch) {
   CamConsts c = c_in;
   uint32_t slot;
-  if (!slot_of_block(sc, blockIdx.x + (first_i << 3), &slot)) return;
-  constexpr int kAcc = kPass == 0 ? 4 : 8;
-  uint32_t idx[R];
-  bool on[R];
-  f3 gp[R], gn[R], tp1[R], tp2[R];
+  if (!slot_of_block(sc, blockIdx.x, &slot)) return;
+  SurfelSet<R> t;
+  load_surfel_set(sc, slot, s, &t);
+  f3 tp1[R], tp2[R];
   float desc1[R], desc2[R];
-  float a[R][kAcc];
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    idx[r] = surfel_of_slot(sc, slot, r, R);
-    on[r] = idx[r] < s.size;
-    if (on[r]) on[r] = (s.active[column_of(s, idx[r])] & BSLAM_SURFEL_ACTIVE_FLAG) != 0;
-    const uint32_t j = on[r] ? idx[r] : 0;
-    gp[r] = mk3(s.x[j], s.y[j], s.z[j]);
-    gn[r] = unpack_normal(s.normal[j]);
-    if constexpr (kPass == 1) {
-      desc1[r] = s.d1[j]; desc2[r] = s.d2[j];
-      tangent_points(gp[r], gn[r], s.radius_squared[j], &tp1[r], &tp2[r]);
-    }
-#pragma unroll
-    for (int q = 0; q < kAcc; ++q) a[r][q] = (!first_chunk && on[r]) ? acc[(size_t)q * acc_pitch + j] : 0.f;
+    const uint32_t j = t.on[r] ? t.idx[r] : 0;
+    desc1[r] = s.d1[j]; desc2[r] = s.d2[j];
+    tangent_points(t.gp[r], t.gn[r], s.radius_squared[j], &tp1[r], &tp2[r]);
   }
-  if constexpr (kPass == 1) BSLAM_HOIST_CAM_CENTRES(c);
-  if constexpr (kPass == 1) BSLAM_HOIST_UNPROJECTION_CENTRE(c);
+  float a[R][8];   // [0] H00, [1] H01, [2] H02, [3] H11, [4] H22, [5] b0, [6] b1, [7] b2   (H12 is never accumulated: quirk Q2)
+  carry_load(t, first_chunk, acc, acc_pitch, a);
+  BSLAM_HOIST_CAM_CENTRES(c);
+  BSLAM_HOIST_UNPROJECTION_CENTRE(c);
   BSLAM_FOR_VISITED_KEYFRAMES(k, k_begin, k_end, R) {
     KfDev kf = kfs[k];
-    if constexpr (kPass == 1) BSLAM_HOIST_KF_TRANSLATION(kf);
-    const float* Rm = kf.global_R_frame;
+    BSLAM_HOIST_KF_TRANSLATION(kf);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
+      // the three quad gathers of the descriptor samples do not depend on the pixel record: issued with the record gather,
+      // before the association test (see pose_accumulate_kernel)
       Proj p;
-      DescSamples ds;
+      if (!t.on[r] || !project_to_pixel(c, kf, t.gp[r], &p)) continue;
+      const PixelRecord rec = load_record(c, kf, p);
       f2 color_pxy, t1, t2;   // the three sample positions of the descriptor residual
-      bool has_desc = false;
-      if constexpr (kPass == 1) {
-        // the three quad gathers of the descriptor samples do not depend on the pixel record: issued with the record gather,
-        // before the association test (see pose_accumulate_kernel)
-        if (!on[r] || !project_to_pixel(c, kf, gp[r], &p)) continue;
-        const PixelRecord rec = load_record(c, kf, p);
-        has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
-        project_tangent_points(tp1[r], tp2[r], kf.frame_T_global, c, &t1, &t2);
-        ds = descriptor_samples_issue(kf, c, color_pxy, t1, t2);
-        asm volatile("" ::: "memory");
-        if (!associate_with_record(c, kf, gn[r], rec, &p)) continue;
-      } else {
-        if (!on[r] || !project_and_associate(c, kf, gp[r], gn[r], &p)) continue;
-      }
-      if constexpr (kPass == 0) {
-        const f3 ln = p.pixel_normal;
-        a[r][0] += rot_row(Rm[0], Rm[1], Rm[2], ln);
-        a[r][1] += rot_row(Rm[3], Rm[4], Rm[5], ln);
-        a[r][2] += rot_row(Rm[6], Rm[7], Rm[8], ln);
-        a[r][3] += 1.f;
-      } else {
-        // accumulators: [0] H00, [1] H01, [2] H02, [3] H11, [4] H22, [5] b0, [6] b1, [7] b2   (H12 is never accumulated: quirk Q2)
-#pragma clang fp contract(fast)   // the position / descriptor sums (compared at 1e-4); the normals pass above feeds packed normals and stays unfused
+      const bool has_desc = depth_to_color_pxy_in_bounds(c, p.pxy, &color_pxy);
+      project_tangent_points(tp1[r], tp2[r], kf.frame_T_global, c, &t1, &t2);
+      const DescSamples ds = descriptor_samples_issue(kf, c, color_pxy, t1, t2);
+      asm volatile("" ::: "memory");
+      if (!associate_with_record(c, kf, t.gn[r], rec, &p)) continue;
+      {
+#pragma clang fp contract(fast)   // the position / descriptor sums (compared at 1e-4)
         const f3 rn = p.n_local;
         if (kDepth) {
+          // not depth_position_term: that one rounds w * dj first and is compiled unfused, this sum is w * dj * dj, fused
           const float inv_stddev = depth_inv_stddev(p.nx, p.ny, p.depth, rn, c.baseline_fx);
           const float dj = depth_position_jacobian(inv_stddev);
           const f3 lu = mk3(p.depth * p.nx, p.depth * p.ny, p.depth);   // unproject(c, p.px, p.py, p.depth)
@@ -607,40 +589,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(BSLAM_GEOM_
       }
     }
   }
+  if (!last_chunk) { carry_store(t, a, acc, acc_pitch); return; }
 #pragma unroll
   for (int r = 0; r < R; ++r) {
-    if (!on[r]) continue;
-    const uint32_t j = idx[r];
-    if (!last_chunk) {
-#pragma unroll
-      for (int q = 0; q < kAcc; ++q) acc[(size_t)q * acc_pitch + j] = a[r][q];
-    } else if constexpr (kPass == 0) {
-      if (a[r][3] >= 1) {
-        const float inv = 1.f / a[r][3];
-        store_normal(s, j, pack_normal(mk3(inv * a[r][0], inv * a[r][1], inv * a[r][2])));
-      }
-    } else {
-      float H00 = a[r][0], H01 = a[r][1], H02 = a[r][2], H11 = a[r][3], H12 = 0.f, H22 = a[r][4];
-      H00 += 1e-6f; H11 += 1e-6f; H22 += 1e-6f;
-      H00 = sqrtf(H00);
-      H01 = H01 / H00;
-      H11 = sqrtf(H11 - H01 * H01);
-      H02 = H02 / H00;
-      H12 = (H12 - H02 * H01) / H11;
-      H22 = sqrtf(H22 - H02 * H02 - H12 * H12);
-      const float y0 = a[r][5] / H00;
-      const float y1 = (a[r][6] - H01 * y0) / H11;
-      const float y2 = (a[r][7] - H02 * y0 - H12 * y1) / H22;
-      const float x2 = y2 / H22;
-      const float x1 = (y1 - H12 * x2) / H11;
-      const float x0 = (y0 - H02 * x2 - H01 * x1) / H00;
-      if (x0 != 0) {
-        const f3 np = sub3(gp[r], scale3(x0, gn[r]));
-        store_position(s, j, np);
-      }
-      if (x1 != 0) store_descriptor1(s, j, fmaxf(-180.f, fminf(180.f, desc1[r] - x1)));
-      if (x2 != 0) store_descriptor2(s, j, fmaxf(-180.f, fminf(180.f, desc2[r] - x2)));
-    }
+    if (!t.on[r]) continue;
+    const uint32_t j = t.idx[r];
+    float H00 = a[r][0], H01 = a[r][1], H02 = a[r][2], H11 = a[r][3], H12 = 0.f, H22 = a[r][4];
+    H00 += 1e-6f; H11 += 1e-6f; H22 += 1e-6f;
+    H00 = sqrtf(H00);
+    H01 = H01 / H00;
+    H11 = sqrtf(H11 - H01 * H01);
+    H02 = H02 / H00;
+    H12 = (H12 - H02 * H01) / H11;
+    H22 = sqrtf(H22 - H02 * H02 - H12 * H12);
+    const float y0 = a[r][5] / H00;
+    const float y1 = (a[r][6] - H01 * y0) / H11;
+    const float y2 = (a[r][7] - H02 * y0 - H12 * y1) / H22;
+    const float x2 = y2 / H22;
+    const float x1 = (y1 - H12 * x2) / H11;
+    const float x0 = (y0 - H02 * x2 - H01 * x1) / H00;
+    if (x0 != 0) store_position(s, j, sub3(t.gp[r], scale3(x0, t.gn[r])));
+    if (x1 != 0) store_descriptor1(s, j, fmaxf(-180.f, fminf(180.f, desc1[r] - x1)));
+    if (x2 != 0) store_descriptor2(s, j, fmaxf(-180.f, fminf(180.f, desc2[r] - x2)));
   }
 }
 

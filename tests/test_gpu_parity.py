@@ -502,6 +502,38 @@ def test_photometric_geometry_chunked_equals_single_launch(oracle):
     assert np.abs(got[6:8] - scene.surfels[6:8, :n]).max() < 2e-3    # descriptors (range +-180)
 
 
+def test_normals_pass_is_one_pass_from_every_entry_point(oracle):
+    """The normals pass is the same pass whichever entry point runs it: bslam_update_surfel_normals (one surfel per thread),
+    the fused geometry-only kernel, the chunked geometry-only iteration, and the photometric iteration in one launch per pass
+    and in keyframe chunks (three and two surfels per thread) all store the same packed normals, bit for bit, from the same
+    start state.  Surfel count with a ragged last granule, K = 37 in chunks of 5 (eight launches of 5, 5, 5, 5, 5, 5, 5, 2)."""
+    from tests import gpu_util
+    cam = bso.make_camera(131.25, 131.25, 80.0, 60.0, 160, 120)
+    scene = scenes.synthetic_scene(37, seed=17, width=160, height=120, camera=cam, use_depth_residuals=True, use_descriptor_residuals=True)
+    hip = gpu_util.Hip(scene.to_device("cuda:0"))
+    if hip.d.surfels_size % 256 == 0:
+        hip.d.surfels_size -= 1                                      # the last work slot must be ragged for every R
+    n = hip.d.surfels_size
+    hip.update_activation()
+    start = hip.d.surfels.clone()
+    L, h = hip.L, hip.ctx.handle
+    hip.update_normals()
+    normals = hip.d.surfels_np()[3, :n].view(np.uint32).copy()
+    assert (normals != start.cpu().numpy()[3, :n].view(np.uint32)).any()   # at least one normal changed
+    try:
+        for use_desc in (False, True):
+            hip.h.use_descriptor_residuals = use_desc
+            for chunk in (0, 5):
+                hip.d.surfels.copy_(start)
+                badslam_amd.check(L.bslam_set_geometry_keyframe_chunk(h, chunk))
+                hip.optimize_geometry_iteration()
+                got = hip.d.surfels_np()[3, :n].view(np.uint32)
+                assert np.array_equal(got, normals), (use_desc, chunk)
+    finally:
+        hip.h.use_descriptor_residuals = True
+        badslam_amd.check(L.bslam_set_geometry_keyframe_chunk(h, -1))
+
+
 def test_per_surfel_work_order_is_transparent(multi):
     """Calls with >= 4 keyframes walk the surfels in the library's own order (Morton order of the positions, on a sorted copy of
     the rows, include/badslam_hip.h: bslam_set_xcd_schedule).  What is computed per surfel must not depend on it at all --

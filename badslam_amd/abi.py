@@ -41,6 +41,12 @@ class Camera4f(C.Structure):
                 ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class RadtanCamera(C.Structure):
+    """bslam_radtan_camera: pixel-CENTRE convention (Camera4f is pixel-corner)."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("k1", C.c_float), ("k2", C.c_float), ("k3", C.c_float), ("p1", C.c_float), ("p2", C.c_float)]
+
+
 class DepthParams(C.Structure):
     _fields_ = [("cfactor_buffer", Buffer2D), ("a", C.c_float), ("raw_to_float_depth", C.c_float),
                 ("baseline_fx", C.c_float), ("sparse_surfel_cell_size", C.c_int32)]
@@ -99,6 +105,10 @@ SIGNATURES = {
     "bslam_median_filter_and_densify_depth": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_downscale_depth_median": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_downscale_rgb": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
+    "bslam_build_undistortion_map": (C.c_int, [C.c_void_p, C.c_void_p, P(RadtanCamera), P(Camera4f), P(Buffer2D)]),
+    "bslam_undistort_rgb": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
+    "bslam_reproject_depth": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), C.c_float, P(Buffer2D), P(Mat3x4), P(Camera4f), C.c_float, C.c_float,
+                                        P(Buffer2D)]),
     "bslam_compute_brightness": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_bilateral_filter_and_depth_cutoff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint16, C.c_float,
                                                          P(Buffer2D), P(Buffer2D)]),

@@ -51,6 +51,7 @@ class BadSlam:
         # what ProcessFrame reads from the host: the full-resolution frame of each stream
         self._depth_shape = (depth_camera.height << pyramid_level_for_depth, depth_camera.width << pyramid_level_for_depth)
         self._rgb_shape = (color_camera.height << pyramid_level_for_color, color_camera.width << pyramid_level_for_color, 3)
+        self._plain_shapes = (self._depth_shape, self._rgb_shape)
         self._num_scales = num_scales
 
     def ba(self):
@@ -93,6 +94,29 @@ class BadSlam:
         """The first stage of ProcessFrame alone (upload, input conditioning, preprocessing kernels), finished on return."""
         d, rgb = self._frame(depth_u16, rgb_u8)
         self._check(self.L.bsh_slam_preprocess_frame(self._slam, d.ctypes.data_as(C.POINTER(C.c_uint16)), rgb.ctypes.data_as(C.POINTER(C.c_uint8))))
+
+    def set_sensor_rectification(self, color_camera=None, depth_camera=None, color_T_depth=None, depth_difference_threshold=0.05,
+                                 raw_depth_to_metres=0.001):
+        """BadSlam::SetSensorRectification: from now on ProcessFrame / PreprocessFrame take the RAW frames of a sensor with the two
+        radtan cameras (abi.RadtanCamera, pixel-centre convention; rectification.radtan_camera builds one): u16 depth of the depth
+        camera's size in units of raw_depth_to_metres, rgb of the colour camera's size.  color_T_depth: 3x4 (or 12 values, row-major)
+        pose of the depth camera in the colour camera's frame, identity if None.  This object must have been constructed with
+        rectification.decide_undistorted_camera(color_camera, True), scaled by the pyramid levels, for both streams.  Without
+        cameras: off again."""
+        from . import abi
+        L = self.L
+        L.bsh_slam_set_sensor_rectification.argtypes = [C.c_void_p, C.c_int, C.POINTER(abi.RadtanCamera), C.POINTER(C.c_float), C.c_float, C.c_float]
+        if color_camera is None and depth_camera is None:
+            self._check(L.bsh_slam_set_sensor_rectification(self._slam, 0, None, None, 0.0, 0.0))
+            self._depth_shape, self._rgb_shape = self._plain_shapes
+            return
+        if color_camera is None or depth_camera is None:
+            raise ValueError("set_sensor_rectification needs both raw cameras (or neither, to switch it off)")
+        cameras = (abi.RadtanCamera * 2)(color_camera, depth_camera)
+        T = np.ascontiguousarray(np.eye(4)[:3] if color_T_depth is None else color_T_depth, np.float32).reshape(12)
+        self._check(L.bsh_slam_set_sensor_rectification(self._slam, 1, cameras, dba._f(T), depth_difference_threshold, raw_depth_to_metres))
+        self._depth_shape = (depth_camera.height, depth_camera.width)
+        self._rgb_shape = (color_camera.height, color_camera.width, 3)
 
     def RunBundleAdjustment(self, frame_index, optimize_depth_intrinsics, optimize_color_intrinsics, optimize_poses, optimize_geometry,
                             min_iterations, max_iterations, window_start=-1, window_end=-1, increase_ba_iteration_count=True):

@@ -16,6 +16,7 @@
 #include "pcg_kernels.hpp"
 #include "lifecycle_kernels.hpp"
 #include "preprocess_kernels.hpp"
+#include "rectify_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
 #include "cost_kernels.hpp"
@@ -1318,5 +1319,6 @@ int bslam_debug_pose_residuals(
 #include "pcg_abi.inc"
 #include "lifecycle_abi.inc"
 #include "preprocess_abi.inc"
+#include "rectify_abi.inc"
 #include "odometry_abi.inc"
 #include "cost_abi.inc"

@@ -127,16 +127,73 @@ BadSlam::BadSlam(const BadSlamConfigV1& config, const PinholeCamera4f& color_cam
 
 BadSlam::~BadSlam() = default;
 
+void BadSlam::SetSensorRectification(const SensorRectification* rectification) {
+  CheckHip(hipStreamSynchronize(stream_), "hipStreamSynchronize");   // no frame in flight reads the buffers replaced below
+  rectify_ = false;
+  sensor_rgb_buffer_.reset();
+  sensor_depth_buffer_.reset();
+  undistortion_map_.reset();
+  unprojection_map_.reset();
+  if (!rectification) return;
+  if (!(rectification->depth_difference_threshold > 0) || !(rectification->raw_depth_to_metres > 0))
+    throw std::invalid_argument("SetSensorRectification: depth_difference_threshold and raw_depth_to_metres must be > 0");
+  const PinholeCamera4f target = DecideUndistortedCamera(rectification->color_camera, /*avoid_invalid_pixels*/ true);
+  const std::vector<float> unprojection_host = MakeUnprojectionMap(rectification->depth_camera);   // validates the depth camera
+  const PinholeCamera4f& color_camera = direct_ba_->color_camera();
+  const PinholeCamera4f& depth_camera = direct_ba_->depth_camera();
+  const int color_level = config_.pyramid_level_for_color, depth_level = config_.pyramid_level_for_depth;
+  if (target.width() != color_camera.width() << color_level || target.height() != color_camera.height() << color_level ||
+      target.width() != depth_camera.width() << depth_level || target.height() != depth_camera.height() << depth_level)
+    throw std::invalid_argument("SetSensorRectification: the undistorted camera is " + std::to_string(target.width()) + " x " +
+                                std::to_string(target.height()) + ", which is not the cameras' size times 2^level of both streams");
+  rectification_ = *rectification;
+  rectified_camera_ = target.pod();
+  const bslam_radtan_camera& raw_color = rectification->color_camera;
+  const bslam_radtan_camera& raw_depth = rectification->depth_camera;
+  sensor_rgb_buffer_.reset(new DeviceBuffer<u8>(raw_color.height, raw_color.width * 3));
+  sensor_depth_buffer_.reset(new DeviceBuffer<u16>(raw_depth.height, raw_depth.width));
+  undistortion_map_.reset(new DeviceBuffer<float>(target.height(), target.width() * 2));
+  unprojection_map_.reset(new DeviceBuffer<float>(raw_depth.height, raw_depth.width * 2));
+  unprojection_map_->Upload(stream_, unprojection_host.data(), static_cast<size_t>(raw_depth.width) * 2 * sizeof(float));
+  bslam_buffer2d map_pod = undistortion_map_->ToPod();
+  map_pod.width /= 2;
+  CheckRc(bslam_build_undistortion_map(direct_ba_->context(), stream_, &raw_color, &rectified_camera_, &map_pod), "bslam_build_undistortion_map");
+  CheckHip(hipStreamSynchronize(stream_), "hipStreamSynchronize");   // the upload has read unprojection_host
+  rectify_ = true;
+}
+
 void BadSlam::PreprocessFrame(const u16* depth_image, const u8* rgb_image) {
   bslam_context* ctx = direct_ba_->context();
   const PinholeCamera4f& depth_camera = direct_ba_->depth_camera();
-  const int dw = depth_camera.width(), cw = direct_ba_->color_camera().width();
+  const int cw = direct_ba_->color_camera().width();
   bslam_buffer2d rgb_pod = rgb_buffer_->ToPod();
   rgb_pod.width = cw;   // 3 bytes per pixel
   // Input conditioning (:645-685): the frame arrives at full resolution and reaches depth_buffer_ / rgb_buffer_ at the
   // cameras' sizes.  With the three switches off this is the plain upload.
+  // The frame lands where the input conditioning reads it: the full-resolution staging buffer of a stream whose
+  // switches are on, else depth_buffer_ / rgb_buffer_ themselves.  With the sensor rectification on it gets there through
+  // the rectification kernels (BS/input_structure.cc:137-172), else by the plain upload.
+  DeviceBuffer<u16>& arriving_depth = raw_depth_buffer_ ? *raw_depth_buffer_ : *depth_buffer_;
+  DeviceBuffer<u8>& arriving_rgb = raw_rgb_buffer_ ? *raw_rgb_buffer_ : *rgb_buffer_;
+  if (rectify_) {
+    sensor_depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(sensor_depth_buffer_->width()) * sizeof(u16));
+    sensor_rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(sensor_rgb_buffer_->width()));
+    const bslam_buffer2d sensor_depth_pod = sensor_depth_buffer_->ToPod(), depth_target_pod = arriving_depth.ToPod();
+    bslam_buffer2d sensor_rgb_pod = sensor_rgb_buffer_->ToPod(), rgb_target_pod = arriving_rgb.ToPod(), unprojection_pod = unprojection_map_->ToPod(),
+                   undistortion_pod = undistortion_map_->ToPod();
+    sensor_rgb_pod.width /= 3;   // 3 bytes per pixel
+    rgb_target_pod.width /= 3;
+    unprojection_pod.width /= 2;   // 2 floats per pixel
+    undistortion_pod.width /= 2;
+    CheckRc(bslam_reproject_depth(ctx, stream_, &sensor_depth_pod, rectification_.raw_depth_to_metres, &unprojection_pod, &rectification_.color_T_depth,
+                                  &rectified_camera_, rectification_.depth_difference_threshold, 1.0f / config_.raw_to_float_depth, &depth_target_pod),
+            "bslam_reproject_depth");
+    CheckRc(bslam_undistort_rgb(ctx, stream_, &sensor_rgb_pod, &undistortion_pod, &rgb_target_pod), "bslam_undistort_rgb");
+  } else {
+    arriving_depth.Upload(stream_, depth_image, static_cast<size_t>(arriving_depth.width()) * sizeof(u16));
+    arriving_rgb.Upload(stream_, rgb_image, static_cast<size_t>(arriving_rgb.width()));
+  }
   if (raw_depth_buffer_) {
-    raw_depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(raw_depth_buffer_->width()) * sizeof(u16));
     const bslam_buffer2d raw_pod = raw_depth_buffer_->ToPod(), final_pod = depth_buffer_->ToPod();
     if (config_.pyramid_level_for_depth > 0) {
       CheckRc(bslam_downscale_depth_median(ctx, stream_, &raw_pod, &final_pod), "bslam_downscale_depth_median");
@@ -150,16 +207,11 @@ void BadSlam::PreprocessFrame(const u16* depth_image, const u8* rgb_image) {
         source = target;
       }
     }
-  } else {
-    depth_buffer_->Upload(stream_, depth_image, static_cast<size_t>(dw) * sizeof(u16));
   }
   if (raw_rgb_buffer_) {
-    raw_rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(raw_rgb_buffer_->width()));
     bslam_buffer2d raw_pod = raw_rgb_buffer_->ToPod();
     raw_pod.width /= 3;
     CheckRc(bslam_downscale_rgb(ctx, stream_, &raw_pod, &rgb_pod), "bslam_downscale_rgb");
-  } else {
-    rgb_buffer_->Upload(stream_, rgb_image, static_cast<size_t>(cw) * 3);
   }
   const bslam_buffer2d color_pod = color_buffer_->ToPod(), depth_pod = depth_buffer_->ToPod(), a_pod = filtered_depth_buffer_A_->ToPod(),
                        b_pod = filtered_depth_buffer_B_->ToPod(), normals_pod = normals_buffer_->ToPod(), radius_pod = radius_buffer_->ToPod();

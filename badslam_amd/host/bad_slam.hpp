@@ -12,6 +12,11 @@
 // reference works on the host.  As there, median iterations and a depth level exclude each other.  The two streams may
 // use different levels (cameras of different sizes).
 //
+// Sensor rectification (SetSensorRectification, off by default): the frames arrive as a raw sensor streams them, from a
+// distorted colour camera and a distorted depth camera beside it, and are undistorted / reprojected into the cameras
+// of this object on the stream, in front of the input conditioning (the reference: host code in its input threads,
+// BS/undistortion.cc and BS/input_structure.cc:196-298).
+//
 // Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), loop detection (DBoW2 place recognition,
 // opengv RANSAC; enable_loop_detection stays off), keyframe merging on low memory.  Those switches must keep their
 // "off" values.
@@ -24,6 +29,7 @@
 #include "io.hpp"
 #include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
+#include "rectification.hpp"
 
 namespace bslam_host {
 
@@ -46,6 +52,17 @@ class BadSlam {
   // only because the next ProcessFrame uploads its own frame first.  Public for timing the stage.
   void PreprocessFrame(const u16* depth_image, const u8* rgb_image);
   hipStream_t stream() const { return stream_; }
+
+  // Switches the sensor rectification on (null: off again, the staging buffers are released).  While it is on,
+  // ProcessFrame / PreprocessFrame take the RAW frames: depth of rectification->depth_camera's size in units of
+  // raw_depth_to_metres, rgb of rectification->color_camera's size.  The depth mesh is reprojected into, and the
+  // colour image undistorted into, the camera DecideUndistortedCamera(color_camera, avoid_invalid_pixels = true), as
+  // the reference does (BS/input_structure.cc:418-422); the depth comes out in units of config.raw_to_float_depth.
+  // That camera, scaled by the pyramid level of each stream, is what this object must have been constructed with: its
+  // size must equal the cameras' sizes times 2^level (std::invalid_argument otherwise).  The undistortion map and the
+  // unprojection map are built and uploaded here, once.
+  void SetSensorRectification(const SensorRectification* rectification);
+  bool sensor_rectification() const { return rectify_; }
 
   // vis::BadSlam::RunBundleAdjustment (BS/bad_slam.cc:481-536)
   void RunBundleAdjustment(u32 frame_index, bool optimize_depth_intrinsics, bool optimize_color_intrinsics, bool optimize_poses, bool optimize_geometry,
@@ -99,6 +116,13 @@ class BadSlam {
   // full-resolution staging for the input conditioning; null while the switch that needs it is off
   std::unique_ptr<DeviceBuffer<u8>> raw_rgb_buffer_;
   std::unique_ptr<DeviceBuffer<u16>> raw_depth_buffer_, median_depth_buffer_;
+  // sensor rectification; the buffers exist only while it is on
+  bool rectify_ = false;
+  SensorRectification rectification_;
+  bslam_camera4f rectified_camera_ = {};   // the full-resolution target of both streams
+  std::unique_ptr<DeviceBuffer<u8>> sensor_rgb_buffer_;
+  std::unique_ptr<DeviceBuffer<u16>> sensor_depth_buffer_;
+  std::unique_ptr<DeviceBuffer<float>> undistortion_map_, unprojection_map_;   // 2 floats per pixel
   std::unique_ptr<PairwiseFrameTrackingBuffers> pairwise_tracking_buffers_;
 
   Keyframe* base_kf_ = nullptr;

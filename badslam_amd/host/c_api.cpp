@@ -13,6 +13,7 @@
 #include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
 #include "pose_graph.hpp"
+#include "rectification.hpp"
 
 using namespace bslam_host;
 
@@ -650,6 +651,47 @@ int bsh_slam_preprocess_frame(void* slam, const uint16_t* depth, const uint8_t* 
     BadSlam* s = static_cast<BadSlam*>(slam);
     s->PreprocessFrame(depth, rgb);
     if (hipStreamSynchronize(s->stream()) != hipSuccess) throw std::runtime_error("hipStreamSynchronize failed");
+  });
+}
+// Sensor rectification (host/rectification.hpp).  cameras: [colour, depth]; color_T_depth: 12 floats, row-major 3x4; enable = 0 switches it off
+// and reads nothing else.
+int bsh_slam_set_sensor_rectification(void* slam, int enable, const bslam_radtan_camera* cameras, const float* color_T_depth,
+                                      float depth_difference_threshold, float raw_depth_to_metres) {
+  BSH_TRY({
+    BadSlam* s = static_cast<BadSlam*>(slam);
+    if (!enable) { s->SetSensorRectification(nullptr); return 0; }
+    SensorRectification r;
+    r.color_camera = cameras[0];
+    r.depth_camera = cameras[1];
+    std::memcpy(r.color_T_depth.m, color_T_depth, sizeof(r.color_T_depth.m));
+    r.depth_difference_threshold = depth_difference_threshold;
+    r.raw_depth_to_metres = raw_depth_to_metres;
+    s->SetSensorRectification(&r);
+  });
+}
+// params4: fx, fy, cx, cy (pixel-corner); size2: width, height
+int bsh_decide_undistorted_camera(const bslam_radtan_camera* camera, int avoid_invalid_pixels, float* params4, int* size2) {
+  BSH_TRY({
+    const PinholeCamera4f c = DecideUndistortedCamera(*camera, avoid_invalid_pixels != 0);
+    std::memcpy(params4, c.parameters(), 4 * sizeof(float));
+    size2[0] = c.width();
+    size2[1] = c.height();
+  });
+}
+// map: height x width x 2 floats
+int bsh_make_unprojection_map(const bslam_radtan_camera* camera, float* map) {
+  BSH_TRY({
+    const std::vector<float> m = MakeUnprojectionMap(*camera);
+    std::memcpy(map, m.data(), m.size() * sizeof(float));
+  });
+}
+// count normalised points (x, y) through the distortion (inverse = 0) or its inverse (inverse = 1), in double
+int bsh_radtan_points(const bslam_radtan_camera* camera, int inverse, int count, const double* in_xy, double* out_xy) {
+  BSH_TRY({
+    for (int i = 0; i < count; ++i) {
+      if (inverse) RadtanUndistort(*camera, in_xy[2 * i], in_xy[2 * i + 1], &out_xy[2 * i], &out_xy[2 * i + 1]);
+      else RadtanDistort(*camera, in_xy[2 * i], in_xy[2 * i + 1], &out_xy[2 * i], &out_xy[2 * i + 1]);
+    }
   });
 }
 int bsh_slam_run_bundle_adjustment(void* slam, int frame_index, int optimize_depth_intrinsics, int optimize_color_intrinsics, int optimize_poses,

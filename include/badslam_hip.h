@@ -100,6 +100,21 @@ typedef struct bslam_camera4f {
   int32_t width, height;
 } bslam_camera4f;
 
+/* A raw sensor camera with radial-tangential distortion (the reference's RadtanCamera9d as
+ * BS/input_structure.cc:391-403 fills it; forward model RadtanDistortion5::Project, LV/camera.h:615-631).
+ * fx, fy, cx, cy in the pixel-CENTRE convention, as sensor SDKs report them: the centre of pixel (x, y) has the
+ * coordinates (x, y), and a normalised distorted point (dx, dy) lands on (fx * dx + cx, fy * dy + cy).
+ * bslam_camera4f stays pixel-CORNER (centre of pixel (x, y) at (x + 0.5, y + 0.5)); the half pixel is added where a
+ * radtan camera becomes a bslam_camera4f (DecideUndistortedCamera, host/rectification.hpp: cx_corner = cx_centre +
+ * 0.5 - first column) and nowhere else: the rectification kernels take target pixel centres at (x + 0.5, y + 0.5) of
+ * the bslam_camera4f and source positions in the radtan camera's own pixel-centre coordinates. */
+typedef struct bslam_radtan_camera {
+  int32_t width, height;
+  float fx, fy, cx, cy;
+  float k1, k2, k3; /* radial */
+  float p1, p2;     /* tangential (r1, r2 of RadtanDistortion5) */
+} bslam_radtan_camera;
+
 /* = vis::DepthParameters (BS/surfel_projection.cuh:129-149). */
 typedef struct bslam_depth_params {
   bslam_buffer2d cfactor_buffer; /* float image, ceil(h/cell) x ceil(w/cell) */
@@ -511,6 +526,39 @@ int bslam_downscale_depth_median(bslam_context* ctx, void* stream,
  * quotient truncated.  Both images have 3 bytes per pixel (width = pixels, as in bslam_compute_brightness). */
 int bslam_downscale_rgb(bslam_context* ctx, void* stream,
                         const bslam_buffer2d* input_rgb, const bslam_buffer2d* output_rgb);
+
+/* Sensor rectification (host code in the reference: BS/undistortion.cc, BS/input_structure.cc:196-298): a raw frame
+ * of a distorted colour camera and a distorted depth camera beside it becomes the ideal pinhole frame of one
+ * viewpoint that everything above expects.  Launched on `stream` without synchronisation, like the calls above. */
+
+/* CreateUndistortionMap (BS/undistortion.cc:122-140) in fp32: for every pixel of `target`, the position in the
+ * `source` image (its pixel-centre coordinates) that the ray through the target pixel's centre lands on, clamped to
+ * [0, width - 1 - FLT_EPSILON] x [0, height - 1 - FLT_EPSILON] (in fp32 that is width - 1, height - 1).  `map` has the
+ * size of `target` and 8 bytes per pixel (float x, float y).  The source must be at least 2 x 2. */
+int bslam_build_undistortion_map(bslam_context* ctx, void* stream, const bslam_radtan_camera* source,
+                                 const bslam_camera4f* target, const bslam_buffer2d* map);
+
+/* UndistortImage (BS/undistortion.cc:142-156): output pixel = bilinear interpolation of input_rgb at the map position,
+ * each channel (u8)(value + 0.5f).  3 bytes per pixel; map and output have one size; the input is at least 2 x 2 and
+ * must not overlap the output.  Map positions are taken as clamped by bslam_build_undistortion_map; the texel index is
+ * limited to width - 2 / height - 2, so a position on the last column / row reads inside the image. */
+int bslam_undistort_rgb(bslam_context* ctx, void* stream, const bslam_buffer2d* input_rgb, const bslam_buffer2d* map,
+                        const bslam_buffer2d* output_rgb);
+
+/* ReprojectDepthImage (BS/input_structure.cc:196-298) as a rasteriser: the raw u16 depth image (0 = no measurement)
+ * becomes a triangle mesh -- vertex of raw pixel (x, y) = depth * input_depth_to_metres * (ux, uy, 1) with (ux, uy)
+ * from unprojection_map (8 bytes per pixel, size of input_depth; MakeUnprojectionMap of host/rectification.hpp), two
+ * triangles per 2 x 2 pixel block, none where one of the four depths is 0 or two of them differ by
+ * depth_difference_threshold (metres, > 0) or more -- which is transformed by target_T_depth (null = identity),
+ * projected with `target` and drawn into output_depth (u16, size of `target`) with a z-buffer that keeps the nearest
+ * surface: (u16)(output_metres_to_depth * z + 0.5f), 0 where nothing was drawn or the value exceeds 65535.
+ * Deviations from the GL path: a triangle with a vertex at z < 0.05 or z > 50 is dropped, not clipped; a pixel is
+ * covered when its centre lies in the closed triangle (no top-left rule); z is interpolated perspective-correctly.
+ * The result does not depend on the order in which triangles arrive.  Input, map and output must not overlap. */
+int bslam_reproject_depth(bslam_context* ctx, void* stream, const bslam_buffer2d* input_depth, float input_depth_to_metres,
+                          const bslam_buffer2d* unprojection_map, const bslam_mat3x4* target_T_depth,
+                          const bslam_camera4f* target, float depth_difference_threshold, float output_metres_to_depth,
+                          const bslam_buffer2d* output_depth);
 
 /* Replaces ComputeBrightnessCUDA (BS/cuda_image_processing.cuh, kernel BS/cuda_image_processing.cu:165-194):
  * rgb_buffer has 3 bytes per pixel, color_buffer 4 (r, g, b, luma). */

@@ -123,6 +123,11 @@ void bso_pcg_step1(const bslam_pcg_layout* layout,
                    uint32_t surfels_size, const bslam_buffer2d* surfels,
                    const bslam_pcg_vectors* v, int clear_g, int tex_mode);
 double bso_pcg_last_alpha_d64(void);  /* float64 sum of the alpha_d terms of the last bso_pcg_step1 */
+/* float64 shadow of the SHARED entries (poses, depth intrinsics, cfactor cells, colour intrinsics) of the last bso_pcg_init
+ * (which = 0: r, 1: M) or bso_pcg_step1 (which = 2: g): per entry the float64 sum of the oracle's own fp32 terms, the float64
+ * sum of their absolute values and their number.  Copies min(count, unknown_count) entries into each non-null array (per-surfel
+ * entries are not shadowed) and returns the unknown count of that call. */
+uint32_t bso_pcg_last_shared_sums(int which, uint32_t count, double* sum64, double* abs64, uint32_t* terms);
 void bso_pcg_step2(const bslam_pcg_layout* layout, const bslam_pcg_vectors* v, float* beta_n_host);
 void bso_pcg_step3(const bslam_pcg_layout* layout, const bslam_pcg_vectors* v);
 void bso_update_surfels_from_pcg_delta(uint32_t surfels_size, const bslam_buffer2d* surfels,

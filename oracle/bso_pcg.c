@@ -6,6 +6,8 @@
  * (keyframe, surfel-index) order; per-surfel entries are written in place.
  */
 #include <math.h>
+#include <stdlib.h>
+#include <string.h>
 
 #include "bslam_oracle.h"
 #include "bso_math.h"
@@ -20,6 +22,51 @@
 static double g_alpha_d64;
 double bso_pcg_last_alpha_d64(void) { return g_alpha_d64; }
 
+/* float64 shadow of every SHARED entry (pose entries, the five depth-intrinsics entries, each cfactor cell, the four
+ * colour-intrinsics entries) of r and M of the last bso_pcg_init call and of g of the last bso_pcg_step1 call.  Those entries
+ * are fp32 serial sums over every (keyframe, surfel) pair, as long as alpha_d's; a device that sums the same terms in another
+ * order is judged against
+ *   sum64[i] = float64 sum of the oracle's own fp32 terms of entry i,
+ *   abs64[i] = float64 sum of their absolute values (the scale that the rounding of any summation order is relative to),
+ *   terms[i] = how many there were.
+ * A term is one fp32 product "J w res" / "J w J" / "J sum": where the reference adds the two descriptor residuals' products
+ * with one atomic, both products count.  Per-surfel entries are formed in the reference's order and are not shadowed. */
+typedef struct {
+  double* sum64;
+  double* abs64;
+  uint32_t* terms;
+  uint32_t n;
+} pcg_shadow;
+enum { SHADOW_R = 0, SHADOW_M = 1, SHADOW_G = 2 };
+static pcg_shadow g_shadow[3];
+
+/* start[i] (if given and nonzero) is what the fp32 entry holds before the pass: it is the sum's first term */
+static void shadow_reset(pcg_shadow* s, uint32_t n, const float* start) {
+  free(s->sum64); free(s->abs64); free(s->terms);
+  const size_t m = n ? n : 1;
+  s->sum64 = (double*)calloc(m, sizeof(double));
+  s->abs64 = (double*)calloc(m, sizeof(double));
+  s->terms = (uint32_t*)calloc(m, sizeof(uint32_t));
+  s->n = (s->sum64 && s->abs64 && s->terms) ? n : 0;
+  if (start) for (uint32_t i = 0; i < s->n; ++i) if (start[i] != 0.f) { s->sum64[i] = (double)start[i]; s->abs64[i] = fabs((double)start[i]); s->terms[i] = 1; }
+}
+static inline void shadow_add(int which, uint32_t idx, float term) {
+  pcg_shadow* s = &g_shadow[which];
+  if (idx >= s->n) return;
+  s->sum64[idx] += (double)term;
+  s->abs64[idx] += fabs((double)term);
+  s->terms[idx] += 1;
+}
+uint32_t bso_pcg_last_shared_sums(int which, uint32_t count, double* sum64, double* abs64, uint32_t* terms) {
+  if (which < 0 || which > 2) return 0;
+  const pcg_shadow* s = &g_shadow[which];
+  const uint32_t m = count < s->n ? count : s->n;
+  if (sum64) memcpy(sum64, s->sum64, m * sizeof(double));
+  if (abs64) memcpy(abs64, s->abs64, m * sizeof(double));
+  if (terms) memcpy(terms, s->terms, m * sizeof(uint32_t));
+  return s->n;
+}
+
 /* get_kf_pose_unknown_index BS/direct_ba_pcg.cc:329-337 */
 static uint32_t kf_pose_unknown_index(const bslam_pcg_layout* l, int keyframe_id) {
   if (keyframe_id == l->gauge_keyframe_id) return INVALID_INDEX;
@@ -30,15 +77,34 @@ static uint32_t kf_pose_unknown_index(const bslam_pcg_layout* l, int keyframe_id
 static void sum_r_and_m(const bslam_pcg_vectors* v, uint32_t idx, float jacobian, float weight, float raw_residual) {
   /* BlockedAtomicSumRAndM / AtomicSumRAndM BS/kernel_pcg.cu:100-177 */
   const float weighted_jacobian = weight * jacobian;
-  v->r[idx] += -1 * weighted_jacobian * raw_residual;
-  v->M[idx] += jacobian * weighted_jacobian;
+  const float tr = -1 * weighted_jacobian * raw_residual;
+  const float tm = jacobian * weighted_jacobian;
+  v->r[idx] += tr;
+  v->M[idx] += tm;
+  shadow_add(SHADOW_R, idx, tr);
+  shadow_add(SHADOW_M, idx, tm);
 }
 static void sum_r_and_m2(const bslam_pcg_vectors* v, uint32_t idx, float j1, float w1, float r1, float j2, float w2, float r2) {
   /* BlockedAtomicSumRAndM2 BS/kernel_pcg.cu:127-155 */
   const float wj1 = w1 * j1;
   const float wj2 = w2 * j2;
-  v->r[idx] += -1 * wj1 * r1 + -1 * wj2 * r2;
-  v->M[idx] += j1 * wj1 + j2 * wj2;
+  const float tr1 = -1 * wj1 * r1, tr2 = -1 * wj2 * r2;
+  const float tm1 = j1 * wj1, tm2 = j2 * wj2;
+  v->r[idx] += tr1 + tr2;
+  v->M[idx] += tm1 + tm2;
+  shadow_add(SHADOW_R, idx, tr1); shadow_add(SHADOW_R, idx, tr2);
+  shadow_add(SHADOW_M, idx, tm1); shadow_add(SHADOW_M, idx, tm2);
+}
+/* g[idx] += j * sum and g[idx] += j1 * sum_1 + j2 * sum_2 of a shared entry (BS/kernel_pcg.cu:940-1023) */
+static void sum_g(const bslam_pcg_vectors* v, uint32_t idx, float j, float sum) {
+  const float t = j * sum;
+  v->g[idx] += t;
+  shadow_add(SHADOW_G, idx, t);
+}
+static void sum_g2(const bslam_pcg_vectors* v, uint32_t idx, float j1, float sum_1, float j2, float sum_2) {
+  const float t1 = j1 * sum_1, t2 = j2 * sum_2;
+  v->g[idx] += t1 + t2;
+  shadow_add(SHADOW_G, idx, t1); shadow_add(SHADOW_G, idx, t2);
 }
 
 typedef struct {
@@ -150,6 +216,8 @@ void bso_pcg_init(const bslam_pcg_layout* layout,
                   uint32_t surfels_size, const bslam_buffer2d* surfels,
                   const bslam_pcg_vectors* v, int tex_mode) {
   for (uint32_t i = 0; i < layout->unknown_count; ++i) { v->r[i] = 0.f; v->M[i] = 0.f; }   /* BS/direct_ba_pcg.cc:315-316 */
+  shadow_reset(&g_shadow[SHADOW_R], layout->unknown_count, NULL);
+  shadow_reset(&g_shadow[SHADOW_M], layout->unknown_count, NULL);
   if (surfels_size == 0) return;
   pcg_cams c;
   c.unproj = bso_make_unprojector(depth_camera);
@@ -231,10 +299,10 @@ static void pcg_step1_keyframe(const bslam_pcg_layout* l, const bslam_camera4f* 
       g_alpha_d64 += (double)(sum * weight * sum);
       sum *= weight;
       if (l->optimize_geometry) v->g[l->surfel_unknown_start_index + per_surfel * i + 0] += geometry_jacobian * sum;
-      if (optimize_poses) for (int k = 0; k < 6; ++k) v->g[kf_idx + k] += pose_jacobian[k] * sum;
+      if (optimize_poses) for (int k = 0; k < 6; ++k) sum_g(v, kf_idx + k, pose_jacobian[k], sum);
       if (l->optimize_depth_intrinsics && djv) {
-        for (int k = 0; k < 5; ++k) v->g[l->depth_intrinsics_unknown_start_index + k] += dgi[k] * sum;
-        v->g[cfactor_entry_index] += cfactor_entry_jacobian * sum;
+        for (int k = 0; k < 5; ++k) sum_g(v, l->depth_intrinsics_unknown_start_index + k, dgi[k], sum);
+        sum_g(v, cfactor_entry_index, cfactor_entry_jacobian, sum);
       }
     }
     if (l->use_descriptor_residuals) {
@@ -299,8 +367,8 @@ static void pcg_step1_keyframe(const bslam_pcg_layout* l, const bslam_camera4f* 
         v->g[s0 + 1] += -1.f * sum_1 + 0.f * sum_2;
         v->g[s0 + 2] += 0.f * sum_1 + -1.f * sum_2;
       }
-      if (optimize_poses) for (int k = 0; k < 6; ++k) v->g[kf_idx + k] += pj1[k] * sum_1 + pj2[k] * sum_2;
-      if (l->optimize_color_intrinsics) for (int k = 0; k < 4; ++k) v->g[l->color_intrinsics_unknown_start_index + k] += cj1[k] * sum_1 + cj2[k] * sum_2;
+      if (optimize_poses) for (int k = 0; k < 6; ++k) sum_g2(v, kf_idx + k, pj1[k], sum_1, pj2[k], sum_2);
+      if (l->optimize_color_intrinsics) for (int k = 0; k < 4; ++k) sum_g2(v, l->color_intrinsics_unknown_start_index + k, cj1[k], sum_1, cj2[k], sum_2);
     }
   }
 }
@@ -314,6 +382,7 @@ void bso_pcg_step1(const bslam_pcg_layout* layout,
   *v->alpha_d = 0.f;                                               /* BS/direct_ba_pcg.cc:383 */
   g_alpha_d64 = 0.0;
   if (clear_g) for (uint32_t i = 0; i < layout->unknown_count; ++i) v->g[i] = 0.f;   /* :393 */
+  shadow_reset(&g_shadow[SHADOW_G], layout->unknown_count, v->g);
   if (surfels_size == 0) return;
   pcg_cams c;
   c.unproj = bso_make_unprojector(depth_camera);

@@ -64,6 +64,7 @@ def lib():
         "bso_pcg_init2": (None, [P(abi.PCGLayout), C.c_float, P(abi.PCGVectors)]),
         "bso_pcg_step1": (None, [P(abi.PCGLayout), _CAM, _CAM, _DP, C.c_int, _KFS, C.c_uint32, _BUF, P(abi.PCGVectors), C.c_int, C.c_int]),
         "bso_pcg_last_alpha_d64": (C.c_double, []),
+        "bso_pcg_last_shared_sums": (C.c_uint32, [C.c_int, C.c_uint32, f64p, f64p, u32p]),
         "bso_pcg_step2": (None, [P(abi.PCGLayout), P(abi.PCGVectors), f32p]),
         "bso_pcg_step3": (None, [P(abi.PCGLayout), P(abi.PCGVectors)]),
         "bso_update_surfels_from_pcg_delta": (None, [C.c_uint32, _BUF, C.c_int, C.c_uint32, f32p]),
@@ -553,6 +554,16 @@ class HostPCG:
         dp, sb, kfs, v = s.depth_params(), s.surfel_buf(), s.keyframe_views(), self.vectors()
         lib().bso_pcg_step1(*self._args(), C.byref(dp), len(s.keyframes), kfs, s.surfels_size, C.byref(sb), C.byref(v), int(clear_g), s.tex_mode)
 
+    def shared_sums(self, name):
+        """(sum64, abs64, terms) of the shared entries of `name` ("r", "M": the last init; "g": the last step1) of the
+        oracle's last call: the float64 sum of its own fp32 terms, of their absolute values, and their number."""
+        n = max(1, self.layout.unknown_count)
+        s64, a64, cnt = np.zeros(n, np.float64), np.zeros(n, np.float64), np.zeros(n, np.uint32)
+        got = lib().bso_pcg_last_shared_sums({"r": 0, "M": 1, "g": 2}[name], self.layout.unknown_count, s64.ctypes.data_as(P(C.c_double)),
+                                             a64.ctypes.data_as(P(C.c_double)), cnt.ctypes.data_as(P(C.c_uint32)))
+        assert got == self.layout.unknown_count, "the oracle's last call had another layout"
+        return s64, a64, cnt
+
     def step2(self):
         v = self.vectors()
         out = C.c_float()
@@ -568,3 +579,9 @@ class HostPCG:
         sb = s.surfel_buf()
         lib().bso_update_surfels_from_pcg_delta(s.surfels_size, C.byref(sb), int(s.use_descriptor_residuals),
                                                 self.layout.surfel_unknown_start_index, fptr(self.delta))
+
+    def apply_delta_to_cfactors(self, start=None, delta=None):
+        """cfactor += delta[start + cell] (start: the first cfactor unknown, depth intrinsics start + 5)."""
+        start = self.layout.depth_intrinsics_unknown_start_index + 5 if start is None else start
+        cb = np_buffer2d(self.scene.cfactor)
+        lib().bso_update_cfactors_from_pcg_delta(C.byref(cb), start, fptr(self.delta if delta is None else delta))

@@ -266,3 +266,13 @@ class HipPCG:
             self.hip.ctx.handle, stream_ptr(), self.hip.d.surfels_size, C.byref(sb), int(self.hip.h.use_descriptor_residuals),
             self.layout.surfel_unknown_start_index, C.c_void_p(self.delta.data_ptr())))
         self.hip.torch.cuda.synchronize()
+
+    def apply_delta_to_cfactors(self, start=None, cfactor_buf=None, delta=None):
+        """bslam_update_cfactors_from_pcg_delta on the device scene's cfactor buffer (or `cfactor_buf`, a Buffer2D of device
+        memory) with this PCG's delta (or `delta`, a device tensor); start: the first cfactor unknown."""
+        start = self.layout.depth_intrinsics_unknown_start_index + 5 if start is None else start
+        cb = self.hip.d.tbuf(self.hip.d.cfactor) if cfactor_buf is None else cfactor_buf
+        d = self.delta if delta is None else delta
+        badslam_amd.check(self.hip.L.bslam_update_cfactors_from_pcg_delta(self.hip.ctx.handle, stream_ptr(), C.byref(cb), start,
+                                                                          C.c_void_p(d.data_ptr())))
+        self.hip.torch.cuda.synchronize()

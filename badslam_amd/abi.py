@@ -109,6 +109,8 @@ SIGNATURES = {
     "bslam_undistort_rgb": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
     "bslam_reproject_depth": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), C.c_float, P(Buffer2D), P(Mat3x4), P(Camera4f), C.c_float, C.c_float,
                                         P(Buffer2D)]),
+    "bslam_render_surfels": (C.c_int, [C.c_void_p, C.c_void_p, P(Mat3x4), P(Camera4f), C.c_uint32, P(Buffer2D), C.c_float, C.c_float, C.c_float, C.c_float,
+                                       P(Buffer2D), P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
     "bslam_compute_brightness": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_bilateral_filter_and_depth_cutoff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint16, C.c_float,
                                                          P(Buffer2D), P(Buffer2D)]),

@@ -17,6 +17,7 @@
 #include "lifecycle_kernels.hpp"
 #include "preprocess_kernels.hpp"
 #include "rectify_kernels.hpp"
+#include "render_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
 #include "cost_kernels.hpp"
@@ -1320,5 +1321,6 @@ int bslam_debug_pose_residuals(
 #include "lifecycle_abi.inc"
 #include "preprocess_abi.inc"
 #include "rectify_abi.inc"
+#include "render_abi.inc"
 #include "odometry_abi.inc"
 #include "cost_abi.inc"

@@ -155,7 +155,8 @@ struct bslam_context {
   // XCD-aware schedule: granule order (short keyframe lists) and per-surfel order, each cached per surfel buffer
   bslam::Slab quads_aux;     // luma quads of the tracked frame's colour pyramid level (odometry)
   bslam::Slab lifecycle;     // supporting-surfel cell images, scan buffers, flags of the surfel lifecycle calls
-  bslam::Slab zbuffer;       // uint32[h][w]: float bits of the nearest surface per target pixel (bslam_reproject_depth)
+  bslam::Slab zbuffer;       // uint32[h][w]: float bits of the nearest surface per target pixel (bslam_reproject_depth); or
+                             // uint64[h][w]: (float bits of the depth << 32) | surfel index (bslam_render_surfels)
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

@@ -59,6 +59,8 @@ def host_lib():
     L.bsh_assign_colors.argtypes = [C.c_void_p, C.c_void_p]
     L.bsh_export_point_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, u8p, f32p, C.POINTER(C.c_uint64)]
     L.bsh_create_surfels_for_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+    L.bsh_depth_camera_size.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+    L.bsh_render_model.argtypes = [C.c_void_p, C.c_void_p, f32p, f32p, C.c_int, C.c_int, f32p, u16p, C.POINTER(C.c_uint32), u8p, f32p, f32p]
     L.bsh_set_allreduce.argtypes = [C.c_void_p, abi.ALLREDUCE_FN, C.c_void_p]
     L.bsh_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.bsh_comm_destroy.argtypes = [C.c_void_p]
@@ -473,6 +475,40 @@ class DirectBA:
         n = C.c_uint64()
         self._check(self.L.bsh_export_point_cloud(self._ba, self.stream, cap, _f(pos), col.ctypes.data_as(C.POINTER(C.c_uint8)), _f(nrm), C.byref(n)))
         return pos[:n.value], col[:n.value], nrm[:n.value]
+
+    def RenderModel(self, global_T_camera, camera=None, min_depth=0.05, max_depth=50.0, radius_scale=1.0, views=("depth", "color")):
+        """Views of the surfel model from the pose global_T_camera (abi.SE3f) with `camera` (abi.Camera4f, pixel-corner; default:
+        the depth camera): every surfel an oriented disc of radius_scale times its radius, the nearest one per pixel.  Returns a
+        dict of NumPy arrays of the camera's size with the entries named in `views` -- "depth" (h, w) uint16 in the units of a
+        keyframe depth image (0: nothing drawn), "index" (h, w) uint32 surfel columns (0xFFFFFFFF: nothing drawn), "color"
+        (h, w, 4) uint8, "normal" (h, w, 3) float32 in the camera frame -- and "camera_T_global" (3, 4) float32, the matrix
+        the kernels took.  Surfels whose ball leaves [min_depth, max_depth] metres are dropped.  A sharded (multi-GPU) object
+        renders its local shard only."""
+        unknown = set(views) - {"depth", "index", "color", "normal"}
+        if unknown or not views:
+            raise ValueError(f"views must name some of depth, index, color, normal (got {sorted(views)})")
+        if camera is None:
+            size = (C.c_int * 2)()
+            self._check(self.L.bsh_depth_camera_size(self._ba, size))
+            params, w, h = self.intrinsics()[1], size[0], size[1]
+        else:
+            params, w, h = np.array([camera.fx, camera.fy, camera.cx, camera.cy], np.float32), int(camera.width), int(camera.height)
+        out = {}
+        if "depth" in views:
+            out["depth"] = np.zeros((h, w), np.uint16)
+        if "index" in views:
+            out["index"] = np.zeros((h, w), np.uint32)
+        if "color" in views:
+            out["color"] = np.zeros((h, w, 4), np.uint8)
+        if "normal" in views:
+            out["normal"] = np.zeros((h, w, 3), np.float32)
+        out["camera_T_global"] = np.zeros((3, 4), np.float32)
+        ptr = lambda name, ctype: out[name].ctypes.data_as(C.POINTER(ctype)) if name in out else None
+        options = np.array([min_depth, max_depth, radius_scale], np.float32)
+        self._check(self.L.bsh_render_model(self._ba, self.stream, _f(pose7(global_T_camera)), _f(np.ascontiguousarray(params, np.float32)), w, h, _f(options),
+                                            ptr("depth", C.c_uint16), ptr("index", C.c_uint32), ptr("color", C.c_uint8), ptr("normal", C.c_float),
+                                            _f(out["camera_T_global"])))
+        return out
 
     def upload_keyframe_depth(self, kf_id, depth):
         d = np.ascontiguousarray(depth, np.uint16)

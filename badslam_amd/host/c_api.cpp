@@ -163,6 +163,31 @@ int bsh_export_point_cloud(void* ba, void* stream, uint64_t capacity, float* pos
     *count = cloud.size();
   });
 }
+// size2: width, height of the depth camera
+int bsh_depth_camera_size(void* ba, int* size2) {
+  BSH_TRY({
+    size2[0] = static_cast<DirectBA*>(ba)->depth_camera().width();
+    size2[1] = static_cast<DirectBA*>(ba)->depth_camera().height();
+  });
+}
+// DirectBA::RenderModel.  camera: fx, fy, cx, cy (pixel-corner) + size; options: min_depth, max_depth, radius_scale.  Each output is a
+// row-major host image of the camera's size, or null for a view that is not wanted; camera_T_global (12 floats, may be null)
+// receives the matrix the kernels took.
+int bsh_render_model(void* ba, void* stream, const float* global_T_camera_pose7, const float* camera_params4, int width, int height, const float* options3,
+                     uint16_t* depth, uint32_t* index, uint8_t* color, float* normal, float* camera_T_global) {
+  BSH_TRY({
+    DirectBA::RenderOptions o;
+    o.min_depth = options3[0]; o.max_depth = options3[1]; o.radius_scale = options3[2];
+    o.depth = depth != nullptr; o.index = index != nullptr; o.color = color != nullptr; o.normal = normal != nullptr;
+    DirectBA::ModelViews v;
+    static_cast<DirectBA*>(ba)->RenderModel(static_cast<hipStream_t>(stream), pose_from7(global_T_camera_pose7), PinholeCamera4f(width, height, camera_params4), o, &v);
+    if (depth) std::memcpy(depth, v.depth.data(), v.depth.size() * sizeof(uint16_t));
+    if (index) std::memcpy(index, v.index.data(), v.index.size() * sizeof(uint32_t));
+    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
+    if (normal) std::memcpy(normal, v.normal.data(), v.normal.size() * sizeof(float));
+    if (camera_T_global) std::memcpy(camera_T_global, v.camera_T_global.m, sizeof(v.camera_T_global.m));
+  });
+}
 int bsh_set_scheme_end_tasks(void* ba, int enable) { BSH_TRY(static_cast<DirectBA*>(ba)->SetSchemeEndTasks(enable != 0)); }
 int bsh_create_surfels_for_keyframe(void* ba, void* stream, int filter_new_surfels, int keyframe_id) {
   BSH_TRY({

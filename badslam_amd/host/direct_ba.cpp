@@ -46,6 +46,7 @@ void DeviceBuffer<T>::Clear(int byte_value, hipStream_t stream) {
 template class DeviceBuffer<float>;
 template class DeviceBuffer<u8>;
 template class DeviceBuffer<u16>;
+template class DeviceBuffer<u32>;
 template class DeviceBuffer<uchar4_t>;
 
 // ------------------------------------------------------------------------------------------------
@@ -437,6 +438,37 @@ void DirectBA::ExportToPointCloud(hipStream_t stream, PointCloud* cloud) const {
     const float factor = 1.0f / std::sqrt(nx * nx + ny * ny + nz * nz);
     cloud->normals.insert(cloud->normals.end(), {factor * nx, factor * ny, factor * nz});
   }
+}
+
+void DirectBA::RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views) {
+  const int w = camera.width(), h = camera.height();
+  if (w <= 0 || h <= 0) throw std::invalid_argument("RenderModel: the camera has no pixels");
+  if (!options.depth && !options.index && !options.color && !options.normal) throw std::invalid_argument("RenderModel: no view was asked for");
+  const auto fits = [w, h](int bw, int bh, int elems) { return bw == w * elems && bh == h; };
+  if (options.depth && !(render_depth_ && fits(render_depth_->width(), render_depth_->height(), 1))) render_depth_.reset(new DeviceBuffer<u16>(h, w));
+  if (options.index && !(render_index_ && fits(render_index_->width(), render_index_->height(), 1))) render_index_.reset(new DeviceBuffer<u32>(h, w));
+  if (options.color && !(render_color_ && fits(render_color_->width(), render_color_->height(), 1))) render_color_.reset(new DeviceBuffer<uchar4_t>(h, w));
+  if (options.normal && !(render_normal_ && fits(render_normal_->width(), render_normal_->height(), 3))) render_normal_.reset(new DeviceBuffer<float>(h, 3 * w));
+  bslam_buffer2d depth, index, color, normal;
+  if (options.depth) depth = render_depth_->ToPod();
+  if (options.index) index = render_index_->ToPod();
+  if (options.color) color = render_color_->ToPod();
+  if (options.normal) { normal = render_normal_->ToPod(); normal.width = w; }   // 12 bytes per pixel
+  const bslam_camera4f cam = camera.pod();
+  const bslam_buffer2d surfels = surfels_->ToPod();
+  views->width = w;
+  views->height = h;
+  views->camera_T_global = global_T_camera.Inverse().Matrix3x4();
+  Check(bslam_render_surfels(ctx_, stream, &views->camera_T_global, &cam, surfels_size_, &surfels, options.min_depth, options.max_depth, options.radius_scale,
+                             1.0f / raw_to_float_depth_, options.depth ? &depth : nullptr, options.index ? &index : nullptr,
+                             options.color ? &color : nullptr, options.normal ? &normal : nullptr),
+        "bslam_render_surfels");
+  const size_t pixels = static_cast<size_t>(w) * h;
+  views->depth.clear(); views->index.clear(); views->color.clear(); views->normal.clear();
+  if (options.depth) { views->depth.resize(pixels); render_depth_->Download(stream, views->depth.data(), static_cast<size_t>(w) * sizeof(u16)); }
+  if (options.index) { views->index.resize(pixels); render_index_->Download(stream, views->index.data(), static_cast<size_t>(w) * sizeof(u32)); }
+  if (options.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), static_cast<size_t>(w) * sizeof(uchar4_t)); }
+  if (options.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), static_cast<size_t>(w) * 3 * sizeof(float)); }
 }
 
 void DirectBA::ComputeCost(hipStream_t stream, bool active_surfels_only, CostReport* report) {

@@ -9,7 +9,8 @@
 //
 // Not on the hot path and therefore absent ("out of scope" / "next" rows): surfel
 // creation / merge / deletion / compaction (do_surfel_updates must be false, surfels are
-// uploaded with SetSurfels), keyframe merging, visualisation.
+// uploaded with SetSurfels), keyframe merging, the on-screen visualisation (off-screen views of the
+// model: RenderModel).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -198,6 +199,25 @@ class DirectBA {
   };
   void ExportToPointCloud(hipStream_t stream, PointCloud* cloud) const;
 
+  // Views of the surfel model from a pose (bslam_render_surfels; in place of the reference's render window): oriented
+  // discs, nearest surface per pixel, identical bits from call to call.  metres_to_depth is 1 / raw_to_float_depth, so
+  // the depth view has the units of a keyframe's depth image.  The device images are kept and re-used between calls.
+  // On a surfel-sharded (multi-GPU) object this renders the local shard only.
+  struct RenderOptions {
+    float min_depth = 0.05f, max_depth = 50.f;   // metres; a surfel whose ball leaves the range is dropped
+    float radius_scale = 1.f;
+    bool depth = true, index = false, color = true, normal = false;   // the views wanted, at least one
+  };
+  struct ModelViews {   // row-major host images of the camera's size; a view not asked for is empty
+    int width = 0, height = 0;
+    bslam_mat3x4 camera_T_global;   // global_T_camera.Inverse() as the kernels took it
+    std::vector<u16> depth;
+    std::vector<u32> index;       // 0xFFFFFFFF: nothing drawn
+    std::vector<uchar4_t> color;
+    std::vector<float> normal;    // 3 per pixel, camera frame
+  };
+  void RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views);
+
   // The objective the BA minimises (bslam_compute_ba_cost: Tukey depth terms and kDescWeight * Huber on both descriptor
   // residuals) at the keyframes' current poses, intrinsics and cfactors: every non-deleted keyframe whatever its activation, every
   // non-deleted surfel -- with active_surfels_only, only those the last geometry step flagged active.  Only reads the scene.
@@ -331,6 +351,11 @@ class DirectBA {
   bool scheme_end_tasks_ = true;
   int fixed_gauge_keyframe_ = -1;
   std::ostream* timings_stream_ = nullptr;
+  // device images of RenderModel, re-allocated when the camera's size changes
+  std::unique_ptr<DeviceBuffer<u16>> render_depth_;
+  std::unique_ptr<DeviceBuffer<u32>> render_index_;
+  std::unique_ptr<DeviceBuffer<uchar4_t>> render_color_;
+  std::unique_ptr<DeviceBuffer<float>> render_normal_;   // 3 floats per pixel
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

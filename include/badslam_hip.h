@@ -560,6 +560,32 @@ int bslam_reproject_depth(bslam_context* ctx, void* stream, const bslam_buffer2d
                           const bslam_camera4f* target, float depth_difference_threshold, float output_metres_to_depth,
                           const bslam_buffer2d* output_depth);
 
+/* Views of the surfel model from a pose (in place of the reference's on-screen view, BS/render_window.cc and
+ * BS/kernel_update_visualization.cu, which draws screen-aligned splats of a fixed pixel size): every surfel is an
+ * oriented disc of radius radius_scale * sqrt(radius_squared) around its position, perpendicular to its normal.  A
+ * pixel shows the disc that the ray through its centre hits nearest to the camera; among discs hit at bit-equal depths,
+ * the one with the lower surfel index.  The result does not depend on the order in which surfels arrive: two calls give
+ * identical bits.  All arithmetic is fp32 in a fixed expression order (csrc/render_kernels.hpp, DESIGN.md 8 "Model
+ * views").  Not drawn: surfels with NaN x, with a scaled squared radius that is not > 0, whose bounding ball does not lie
+ * in [min_depth, max_depth] (centre z - radius >= min_depth and centre z <= max_depth: dropped, not clipped), and those
+ * seen from behind or with a zero normal.
+ *   camera_T_global  pose of the view; camera: pixel-corner pinhole camera, 1 ... 2^31 - 1 pixels, fx, fy > 0
+ *   surfels          the surfel rows up to BSLAM_SURFEL_COLOR at least; surfels_size = 0 gives empty views
+ *   0 < min_depth <= max_depth (metres);  radius_scale > 0;  metres_to_depth > 0
+ * Outputs, each of the camera's size and optional (null = not written), at least one given; they must not overlap each
+ * other or the surfel rows, and their rows must be aligned to their element (2 / 4 / 4 / 4 bytes):
+ *   out_depth   u16     (u16)(metres_to_depth * z + 0.5f), 0 where nothing was drawn or the value exceeds 65535 -- with
+ *                       metres_to_depth = 1 / raw_to_float_depth the units of a keyframe's depth image
+ *   out_index   u32     the surfel's column, 0xFFFFFFFF where nothing was drawn
+ *   out_color   uchar4  the surfel's BSLAM_SURFEL_COLOR entry, 0 where nothing was drawn
+ *   out_normal  12 B    three floats: the surfel's unit normal in the camera frame, 0 where nothing was drawn
+ * Launched on `stream` without synchronisation.  In a surfel-sharded run a rank renders the surfels it was given, i.e.
+ * its own shard; nothing is exchanged (merging shards would be a minimum of the keys across the ranks). */
+int bslam_render_surfels(bslam_context* ctx, void* stream, const bslam_mat3x4* camera_T_global, const bslam_camera4f* camera,
+                         uint32_t surfels_size, const bslam_buffer2d* surfels, float min_depth, float max_depth,
+                         float radius_scale, float metres_to_depth, const bslam_buffer2d* out_depth,
+                         const bslam_buffer2d* out_index, const bslam_buffer2d* out_color, const bslam_buffer2d* out_normal);
+
 /* Replaces ComputeBrightnessCUDA (BS/cuda_image_processing.cuh, kernel BS/cuda_image_processing.cu:165-194):
  * rgb_buffer has 3 bytes per pixel, color_buffer 4 (r, g, b, luma). */
 int bslam_compute_brightness(bslam_context* ctx, void* stream,

@@ -6,7 +6,7 @@ has a ground truth, prints the ATE RMSE.
     python tools/run_tum.py <dataset_dir> [--trajectory groundtruth.txt] [--out poses.txt] [--keyframe-interval 10]
                             [--ba-iterations 10] [--max-depth 3.0] [--end-frame N] [--ba-cost]
                             [--pyramid-level-for-depth L] [--pyramid-level-for-color L]
-                            [--median-filter-and-densify-iterations N]
+                            [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -14,6 +14,13 @@ sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320
 
 --ba-cost: after the last frame, one more BA over the whole window (poses + geometry), with the BA objective printed before and
 after it (DirectBA.ComputeCost: Tukey depth terms + weighted Huber descriptor terms over all surfel / keyframe pairs).
+
+--render-dir DIR: after the run, the reconstructed surfel model is rendered from the pose of every keyframe (--render-every N:
+of every N-th) with the depth camera as the run left it (DirectBA.RenderModel) and written to DIR as a TUM-style directory that
+the dataset reader loads back: depth/<timestamp>.png (16-bit, the units of the input depth), rgb/<timestamp>.png, associated.txt,
+calibration.txt and groundtruth.txt (the keyframe poses the views were rendered from).  --render-radius-scale S: the discs are
+drawn with S times the surfels' radii; the default is the sparse surfel cell size of the run (4), because a surfel stands for a
+cell of that many pixels a side while its radius is that of one pixel, so that scale closes the gaps between neighbours.
 """
 import argparse
 import os
@@ -22,7 +29,7 @@ import sys
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from badslam_amd import abi, ate, bad_slam          # noqa: E402
+from badslam_amd import abi, ate, bad_slam, png     # noqa: E402
 from badslam_amd import direct_ba as dba            # noqa: E402
 
 
@@ -47,21 +54,55 @@ def check_level_fits(width, height, level):
         raise ValueError(f"pyramid level {level} does not fit a {width}x{height} dataset: levels are 0 ... 3 and the size must be divisible by 2^level")
 
 
+def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0):
+    """Writes the model views from the poses of keyframes[::every] -- (keyframe id, timestamp string) pairs -- as a TUM-style
+    directory; deleted keyframes are left out.  Returns the (keyframe id, timestamp) pairs written."""
+    if every < 1:
+        raise ValueError("--render-every must be at least 1")
+    os.makedirs(os.path.join(str(render_dir), "depth"), exist_ok=True)
+    os.makedirs(os.path.join(str(render_dir), "rgb"), exist_ok=True)
+    _, depth4, _ = ba.intrinsics()
+    written, associated, trajectory = [], [], ["# timestamp tx ty tz qx qy qz qw"]
+    for kf_id, ts in keyframes[::every]:
+        if ba.keyframe_is_deleted(kf_id):
+            continue
+        pose = ba.keyframe_pose(kf_id)
+        views = ba.RenderModel(pose, radius_scale=radius_scale, views=("depth", "color"))
+        png.write_png(os.path.join(str(render_dir), "depth", f"{ts}.png"), views["depth"])
+        png.write_png(os.path.join(str(render_dir), "rgb", f"{ts}.png"), np.ascontiguousarray(views["color"][:, :, :3]))
+        associated.append(f"{ts} rgb/{ts}.png {ts} depth/{ts}.png")
+        q = dba.pose7(pose)
+        trajectory.append(f"{ts} {q[4]:.9g} {q[5]:.9g} {q[6]:.9g} {q[0]:.9g} {q[1]:.9g} {q[2]:.9g} {q[3]:.9g}")
+        written.append((kf_id, ts))
+    with open(os.path.join(str(render_dir), "associated.txt"), "w") as f:
+        f.write("\n".join(associated) + "\n")
+    with open(os.path.join(str(render_dir), "calibration.txt"), "w") as f:    # pixel-centre convention on disk
+        f.write(f"{depth4[0]:.9g} {depth4[1]:.9g} {depth4[2] - 0.5:.9g} {depth4[3] - 0.5:.9g}\n")
+    with open(os.path.join(str(render_dir), "groundtruth.txt"), "w") as f:
+        f.write("\n".join(trajectory) + "\n")
+    return written
+
+
 def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterations=10, max_depth=3.0, end_frame=None, raw_to_float_depth=1.0 / 5000,
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
-        median_filter_and_densify_iterations=0):
+        median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None):
+    """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_depth)
     color_cam = scaled_camera(ds["camera"], ds["width"], ds["height"], pyramid_level_for_color)
     depth_cam = scaled_camera(ds["camera"], ds["width"], ds["height"], pyramid_level_for_depth)
-    slam = bad_slam.BadSlam(color_cam, depth_cam, keyframe_interval=keyframe_interval, max_num_ba_iterations_per_keyframe=ba_iterations,
+    cell = 4                # sparse surfel cell size of the front end
+    slam = bad_slam.BadSlam(color_cam, depth_cam, sparse_surfel_cell_size=cell, keyframe_interval=keyframe_interval, max_num_ba_iterations_per_keyframe=ba_iterations,
                             num_scales=num_scales, max_surfel_count=max_surfel_count, raw_to_float_depth=raw_to_float_depth, max_depth=max_depth,
                             pyramid_level_for_depth=pyramid_level_for_depth, pyramid_level_for_color=pyramid_level_for_color,
                             median_filter_and_densify_iterations=median_filter_and_densify_iterations)
+    keyframes = []          # (keyframe id, timestamp string) in the order of creation
     for k, fr in enumerate(frames):
         slam.ProcessFrame(k, dba.read_png(fr["depth_path"]), dba.read_png(fr["rgb_path"]))
+        if render_dir and slam.state()["keyframe_created"]:
+            keyframes.append((slam.state()["base_kf_id"], fr["depth_timestamp"]))
     result = {}
     if ba_cost:
         before = slam.ba().ComputeCost()
@@ -73,6 +114,11 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     out = out or os.path.join(str(dataset_dir), "poses_badslam_amd.txt")
     dba.save_poses([f["depth_timestamp"] for f in frames], poses, 0, out)
     result.update({"frames": len(frames), "keyframes": slam.ba().keyframe_count(), "surfels": slam.ba().surfels_size(), "poses_file": out})
+    if render_dir:
+        result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, float(render_radius_scale or cell))
+        result["render_dir"] = str(render_dir)
+    if inspect:
+        inspect(slam, result)
     if trajectory:
         result["ate"] = ate.ate_files(os.path.join(str(dataset_dir), trajectory), out)
     return result
@@ -91,6 +137,9 @@ def arg_parser():
     ap.add_argument("--pyramid-level-for-depth", type=int, default=0)
     ap.add_argument("--pyramid-level-for-color", type=int, default=0)
     ap.add_argument("--median-filter-and-densify-iterations", type=int, default=0)
+    ap.add_argument("--render-dir", default=None)
+    ap.add_argument("--render-every", type=int, default=1)
+    ap.add_argument("--render-radius-scale", type=float, default=None)
     return ap
 
 
@@ -98,10 +147,13 @@ def main():
     a = arg_parser().parse_args()
     r = run(a.dataset_dir, a.trajectory, a.out, a.keyframe_interval, a.ba_iterations, a.max_depth, a.end_frame, ba_cost=a.ba_cost,
             pyramid_level_for_depth=a.pyramid_level_for_depth, pyramid_level_for_color=a.pyramid_level_for_color,
-            median_filter_and_densify_iterations=a.median_filter_and_densify_iterations)
+            median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
+            render_radius_scale=a.render_radius_scale)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
+    if "rendered" in r:
+        print(f"{len(r['rendered'])} model views -> {r['render_dir']}")
     if "ate" in r:
         print(f"ATE RMSE {r['ate']['rmse']:.6f} m over {r['ate']['pairs']} poses")
 

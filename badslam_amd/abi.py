@@ -111,6 +111,9 @@ SIGNATURES = {
                                         P(Buffer2D)]),
     "bslam_render_surfels": (C.c_int, [C.c_void_p, C.c_void_p, P(Mat3x4), P(Camera4f), C.c_uint32, P(Buffer2D), C.c_float, C.c_float, C.c_float, C.c_float,
                                        P(Buffer2D), P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
+    "bslam_extract_keyframe_features": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D), C.c_int64, C.c_void_p, C.c_void_p]),
+    "bslam_place_pattern": (C.c_int, [P(C.c_int8)]),
+    "bslam_match_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bslam_compute_brightness": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D)]),
     "bslam_bilateral_filter_and_depth_cutoff": (C.c_int, [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_uint16, C.c_float,
                                                          P(Buffer2D), P(Buffer2D)]),

@@ -156,6 +156,26 @@ class BadSlam:
         return [{"keyframe": int(e[3 * i]), "candidate": int(e[3 * i + 1]), "status": dba.LOOP_STATUS_NAMES[int(e[3 * i + 2])],
                  "mean_pixel_distance": float(d[i])} for i in range(n)]
 
+    def set_place_recognition(self, enable, **options):
+        """Opt-in place recognition (off by default): every new keyframe's features enter a device database, and before its BA
+        iterations the keyframe is matched against the keyframes at least min_keyframe_gap ids older; a recognised place gets
+        a RANSAC start pose and CloseLoop.  options: see direct_ba.place_recognition_options.  Excludes
+        set_loop_candidate_search."""
+        L = dba._place_lib()
+        o, thr = dba._place_options_arrays(dba.place_recognition_options(**options))
+        self._check(L.bsh_slam_set_place_recognition(self._slam, int(enable), o.ctypes.data_as(C.POINTER(C.c_int64)), thr))
+
+    def place_recognition_log(self):
+        """[{keyframe, candidate (-1: none), match_count, inlier_count, pose_found, old_T_cur, loop_attempted, status,
+        mean_pixel_distance}] of place recognition, one entry per keyframe added while it was on, oldest first."""
+        L = dba._place_lib()
+        n = L.bsh_slam_place_log_size(self._slam)
+        e, d, p = np.zeros(7 * max(1, n), np.int32), np.zeros(max(1, n), np.float32), np.zeros(7 * max(1, n))
+        self._check(L.bsh_slam_place_log(self._slam, dba._i(e), dba._f(d), dba._d(p), n))
+        return [{"keyframe": int(e[7 * i]), "candidate": int(e[7 * i + 1]), "match_count": int(e[7 * i + 2]), "inlier_count": int(e[7 * i + 3]),
+                 "pose_found": bool(e[7 * i + 4]), "old_T_cur": p[7 * i:7 * i + 7].copy(), "loop_attempted": bool(e[7 * i + 5]),
+                 "status": dba.LOOP_STATUS_NAMES[int(e[7 * i + 6])] if e[7 * i + 5] else None, "mean_pixel_distance": float(d[i])} for i in range(n)]
+
     def state(self):
         s = (C.c_int * 5)()
         self._check(self.L.bsh_slam_state(self._slam, s))

@@ -18,6 +18,7 @@
 #include "preprocess_kernels.hpp"
 #include "rectify_kernels.hpp"
 #include "render_kernels.hpp"
+#include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
 #include "cost_kernels.hpp"
@@ -1322,5 +1323,6 @@ int bslam_debug_pose_residuals(
 #include "preprocess_abi.inc"
 #include "rectify_abi.inc"
 #include "render_abi.inc"
+#include "place_abi.inc"
 #include "odometry_abi.inc"
 #include "cost_abi.inc"

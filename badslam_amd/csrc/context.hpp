@@ -157,6 +157,8 @@ struct bslam_context {
   bslam::Slab lifecycle;     // supporting-surfel cell images, scan buffers, flags of the surfel lifecycle calls
   bslam::Slab zbuffer;       // uint32[h][w]: float bits of the nearest surface per target pixel (bslam_reproject_depth); or
                              // uint64[h][w]: (float bits of the depth << 32) | surfel index (bslam_render_surfels)
+  bslam::Slab place_pattern; // uint32[256]: the BRIEF point pairs of bslam_extract_keyframe_features, uploaded by its first call
+  bool place_pattern_ready = false;
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

@@ -181,6 +181,65 @@ def _loop_buffers(num_scales):
     return np.zeros(6 + 3 * num_scales, np.int32), np.zeros(29, np.float32), np.zeros(LOOP_POSE_GRAPH_ITERATIONS)
 
 
+# ---- place recognition (badslam_amd/host/place_recognition.hpp) -----------------------------------------------
+def _place_lib():
+    L = _loop_lib()
+    if getattr(L, "_place_ready", False):
+        return L
+    dp, ip, fp, i64p, u32p = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_int64), C.POINTER(C.c_uint32)
+    L.bsh_place_default_options.argtypes = [i64p, dp]
+    L.bsh_estimate_relative_pose.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp, C.c_int, C.c_double, C.c_int, dp, ip, C.POINTER(C.c_uint8)]
+    L.bsh_place_ransac_seed.restype = C.c_uint32
+    L.bsh_place_ransac_seed.argtypes = [C.c_int, C.c_int]
+    L.bsh_place_cells.argtypes = [C.c_void_p]
+    L.bsh_extract_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, u32p, u32p]
+    L.bsh_match_keyframe_features.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, ip, C.c_int, C.POINTER(C.c_int32), u32p]
+    L.bsh_recognize_place.argtypes = [C.c_void_p, C.c_void_p, C.c_int, i64p, C.c_double, C.c_int, ip, dp, ip, fp, dp]
+    L.bsh_slam_set_place_recognition.argtypes = [C.c_void_p, C.c_int, i64p, C.c_double]
+    L.bsh_slam_place_log_size.argtypes = [C.c_void_p]
+    L.bsh_slam_place_log.argtypes = [C.c_void_p, ip, fp, dp, C.c_int]
+    L._place_ready = True
+    return L
+
+
+def place_recognition_options(**overrides):
+    """PlaceRecognitionOptions as a dict: min_keyframe_gap, score_threshold, max_distance, min_matches, ransac_iterations,
+    ransac_min_inliers, ransac_inlier_threshold (metres) -- the native defaults with `overrides` applied."""
+    L = _place_lib()
+    o, thr = np.zeros(6, np.int64), C.c_double()
+    L.bsh_place_default_options(o.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(thr))
+    names = ("min_keyframe_gap", "score_threshold", "max_distance", "min_matches", "ransac_iterations", "ransac_min_inliers")
+    opts = {n: int(v) for n, v in zip(names, o)}
+    opts["ransac_inlier_threshold"] = thr.value
+    unknown = set(overrides) - set(opts)
+    if unknown:
+        raise ValueError(f"unknown place recognition options {sorted(unknown)}")
+    opts.update(overrides)
+    return opts
+
+
+def _place_options_arrays(opts):
+    o = np.array([opts[n] for n in ("min_keyframe_gap", "score_threshold", "max_distance", "min_matches", "ransac_iterations", "ransac_min_inliers")], np.int64)
+    return o, float(opts["ransac_inlier_threshold"])
+
+
+def estimate_relative_pose(current_id, matched_id, p_cur, p_old, iterations=500, inlier_threshold=0.06, min_inliers=10):
+    """3D-3D RANSAC of place recognition on the host, in double (no GPU): p_cur, p_old (n, 3) corresponding points in the
+    frames of the current and the matched keyframe.  Returns a dict: found, old_T_cur (7,) float64 [qx qy qz qw tx ty tz],
+    inlier_count, inliers (n,) bool."""
+    L = _place_lib()
+    a = np.ascontiguousarray(np.asarray(p_cur, np.float64).reshape(-1, 3))
+    b = np.ascontiguousarray(np.asarray(p_old, np.float64).reshape(-1, 3))
+    if len(a) != len(b):
+        raise ValueError("one point of each frame per correspondence")
+    pose, count, mask = np.zeros(7), C.c_int(), np.zeros(max(1, len(a)), np.uint8)
+    rc = L.bsh_estimate_relative_pose(int(current_id), int(matched_id), len(a), _d(a), _d(b), int(iterations), float(inlier_threshold), int(min_inliers),
+                                      _d(pose), C.byref(count), mask.ctypes.data_as(C.POINTER(C.c_uint8)))
+    if rc < 0:
+        raise DirectBAError(L.bsh_last_error().decode())
+    return {"found": bool(rc), "old_T_cur": pose, "inlier_count": count.value, "inliers": mask[:len(a)].astype(bool)}
+
+
 # ---- file formats (badslam_amd/host/io.hpp) -----------------------------------------------------------------
 def _io_lib():
     L = host_lib()
@@ -386,6 +445,44 @@ class DirectBA:
         ints, floats, chi2 = _loop_buffers(num_scales)
         self._check(L.bsh_close_loop(self._ba, self.stream, current_id, matched_id, _f(pose7(old_T_cur_initial)), num_scales, _i(ints), _f(floats), _d(chi2)))
         return _loop_result(ints, floats, chi2, num_scales)
+
+    def ExtractKeyframeFeatures(self, kf_id, score_threshold=None):
+        """Extracts keyframe kf_id's place-recognition features into the device database (bslam_extract_keyframe_features) and
+        returns them: xy (cells,) uint32 = x | y << 16 or 0xFFFFFFFF, desc (cells, 8) uint32; one slot per 16 x 16 cell."""
+        L = _place_lib()
+        if score_threshold is None:
+            score_threshold = place_recognition_options()["score_threshold"]
+        cells = self._check(L.bsh_place_cells(self._ba))
+        xy, desc = np.zeros(cells, np.uint32), np.zeros((cells, 8), np.uint32)
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._check(L.bsh_extract_keyframe_features(self._ba, self.stream, int(kf_id), int(score_threshold), u32(xy), u32(desc)))
+        return xy, desc
+
+    def MatchKeyframeFeatures(self, query_id, ids, max_distance=None):
+        """One bslam_match_features launch of keyframe query_id against the keyframes `ids` (all extracted before): returns
+        match (len(ids), cells) int32 (the matched slot or -1) and count (len(ids),) uint32."""
+        L = _place_lib()
+        if max_distance is None:
+            max_distance = place_recognition_options()["max_distance"]
+        cells = self._check(L.bsh_place_cells(self._ba))
+        idv = np.ascontiguousarray(ids, np.int32)
+        match, count = np.zeros((max(1, len(idv)), cells), np.int32), np.zeros(max(1, len(idv)), np.uint32)
+        self._check(L.bsh_match_keyframe_features(self._ba, self.stream, int(query_id), len(idv), _i(idv), int(max_distance),
+                                                  match.ctypes.data_as(C.POINTER(C.c_int32)), count.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return match[:len(idv)], count[:len(idv)]
+
+    def RecognizePlace(self, current_id, num_scales=5, **options):
+        """Place recognition for keyframe current_id: candidate by feature matching, start pose by 3D-3D RANSAC, then CloseLoop.
+        options: see place_recognition_options.  Returns a dict: candidate (-1: none), match_count, inlier_count, pose_found,
+        old_T_cur (7,) float64 [qx qy qz qw tx ty tz] of the RANSAC estimate, loop_attempted and loop (CloseLoop's dict, or None)."""
+        L = _place_lib()
+        o, thr = _place_options_arrays(place_recognition_options(**options))
+        out5, pose = np.zeros(5, np.int32), np.zeros(7)
+        ints, floats, chi2 = _loop_buffers(num_scales)
+        self._check(L.bsh_recognize_place(self._ba, self.stream, int(current_id), o.ctypes.data_as(C.POINTER(C.c_int64)), thr, num_scales, _i(out5), _d(pose),
+                                          _i(ints), _f(floats), _d(chi2)))
+        return {"candidate": int(out5[0]), "match_count": int(out5[1]), "inlier_count": int(out5[2]), "pose_found": bool(out5[3]), "old_T_cur": pose,
+                "loop_attempted": bool(out5[4]), "loop": _loop_result(ints, floats, chi2, num_scales) if out5[4] else None}
 
     def SaveState(self, path, frame_count):
         """The DirectBA part of SaveState (BS/io.cc:38-178) as a version-1 state file."""

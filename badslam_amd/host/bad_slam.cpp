@@ -292,6 +292,7 @@ std::shared_ptr<Keyframe> BadSlam::CreateKeyframe(int frame_index) {
     base_kf_tr_frame_.back() = SE3f();   // exactly the identity, not a product that rounds to it
   }
   if (loop_candidate_search_) SearchLoopCandidate(frame_index, *new_keyframe);   // before the keyframe's BA iterations (:1120-1158)
+  if (place_recognition_) RunPlaceRecognition(frame_index, *new_keyframe);
   if (!config_.estimate_poses) return new_keyframe;
 
   if (keyframes_added >= 2) {   // :1074-1094
@@ -325,6 +326,7 @@ void BadSlam::CloseLoop(int matched_id, const SE3f& old_T_cur_initial, LoopClosu
 
 void BadSlam::SetLoopCandidateSearch(bool enable, int min_keyframe_gap) {
   if (min_keyframe_gap < 1) throw std::invalid_argument("SetLoopCandidateSearch: min_keyframe_gap must be >= 1");
+  if (enable && place_recognition_) throw std::invalid_argument("SetLoopCandidateSearch: place recognition is on; the two searches exclude each other");
   loop_candidate_search_ = enable;
   loop_min_keyframe_gap_ = min_keyframe_gap;
 }
@@ -349,6 +351,32 @@ void BadSlam::SearchLoopCandidate(int frame_index, const Keyframe& new_keyframe)
   LoopClosureResult result;
   CloseLoopUpTo(frame_index, best, kfs[best]->frame_T_global() * g, &result);
   loop_log_.push_back(LoopLogEntry{new_keyframe.id(), best, result.status, result.mean_pixel_distance});
+}
+
+void BadSlam::SetPlaceRecognition(bool enable, const PlaceRecognitionOptions& options) {
+  if (enable && loop_candidate_search_) throw std::invalid_argument("SetPlaceRecognition: the loop candidate search is on; the two searches exclude each other");
+  if (enable && options.min_keyframe_gap < 1) throw std::invalid_argument("SetPlaceRecognition: min_keyframe_gap must be >= 1");
+  if (enable && (options.max_distance < 0 || options.max_distance > 256)) throw std::invalid_argument("SetPlaceRecognition: max_distance must lie in 0 ... 256");
+  place_recognition_ = enable;
+  place_options_ = options;
+  if (!enable) direct_ba_->ResetPlaceRecognizer();
+}
+
+void BadSlam::RunPlaceRecognition(int frame_index, const Keyframe& new_keyframe) {
+  std::vector<SE3f> original_keyframe_T_global;
+  RememberKeyframePoses(*direct_ba_, &original_keyframe_T_global);
+  PlaceRecognitionResult r;
+  direct_ba_->RecognizePlace(stream_, new_keyframe.id(), place_options_, config_.num_scales, &r);
+  PlaceLogEntry e;
+  e.keyframe_id = r.keyframe_id; e.candidate_id = r.candidate_id; e.match_count = r.match_count; e.inlier_count = r.pose.inlier_count;
+  e.pose_found = r.pose.found; e.loop_attempted = r.loop_attempted; e.status = r.loop.status; e.mean_pixel_distance = r.loop.mean_pixel_distance;
+  for (int i = 0; i < 4; ++i) e.old_T_cur[i] = r.pose.q[i];
+  for (int i = 0; i < 3; ++i) e.old_T_cur[4 + i] = r.pose.t[i];
+  place_log_.push_back(e);
+  if (!r.loop_attempted || r.loop.status != kLoopClosed) return;
+  ExtrapolateAndInterpolateKeyframePoseChanges(static_cast<u32>(config_.start_frame), static_cast<u32>(frame_index), *direct_ba_,
+                                               original_keyframe_T_global, &frame_global_T_frame_);
+  if (base_kf_) base_kf_global_T_frame_ = base_kf_->global_T_frame();
 }
 
 void BadSlam::RunBundleAdjustment(u32 frame_index, bool optimize_depth_intrinsics, bool optimize_color_intrinsics, bool optimize_poses,

@@ -4,8 +4,10 @@
 // (:953-1097) and the planned bundle-adjustment iterations (:212-282, :481-536), after which the poses of the
 // non-keyframes follow their neighbouring keyframes (BS/trajectory_deformation.cc:45-146).
 //
-// Loop closure: CloseLoop (host/loop_closure.hpp) for a caller-supplied candidate, and an opt-in geometric candidate
-// search (SetLoopCandidateSearch) that closes drift within the tracker's basin; it is not place recognition.
+// Loop closure: CloseLoop (host/loop_closure.hpp) for a caller-supplied candidate; an opt-in geometric candidate
+// search (SetLoopCandidateSearch) that closes drift within the tracker's basin; and opt-in place recognition
+// (SetPlaceRecognition, host/place_recognition.hpp), which finds the candidate and the start pose from the images alone
+// and so closes drift of any size.
 //
 // Input conditioning (BS/bad_slam.cc:645-685): median_filter_and_densify_iterations, pyramid_level_for_depth and
 // pyramid_level_for_color (each level 0 ... 3) run as kernels on the uploaded full-resolution frame, where the
@@ -17,9 +19,9 @@
 // of this object on the stream, in front of the input conditioning (the reference: host code in its input threads,
 // BS/undistortion.cc and BS/input_structure.cc:196-298).
 //
-// Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), loop detection (DBoW2 place recognition,
-// opengv RANSAC; enable_loop_detection stays off), keyframe merging on low memory.  Those switches must keep their
-// "off" values.
+// Not built: parallel_ba (BA thread), real-time pacing (target_frame_rate), the reference's own loop detector (DBoW2
+// vocabulary, opengv RANSAC; enable_loop_detection stays off -- SetPlaceRecognition is this project's stand-in), keyframe
+// merging on low memory.  Those switches must keep their "off" values.
 #pragma once
 
 #include <memory>
@@ -29,6 +31,7 @@
 #include "io.hpp"
 #include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
+#include "place_recognition.hpp"
 #include "rectification.hpp"
 
 namespace bslam_host {
@@ -86,6 +89,22 @@ class BadSlam {
   void SetLoopCandidateSearch(bool enable, int min_keyframe_gap);
   const std::vector<LoopLogEntry>& loop_closure_log() const { return loop_log_; }
 
+  // Opt-in place recognition (off by default; while it is off nothing is allocated or launched for it): every new
+  // keyframe's features enter the database, and before its BA iterations DirectBA::RecognizePlace looks for an older
+  // keyframe showing the same place, estimates the start pose and tries CloseLoop.  With status kLoopClosed the
+  // non-keyframe poses follow their keyframes.  Switching it off releases the database.  It excludes
+  // SetLoopCandidateSearch: enabling one while the other is on throws std::invalid_argument.
+  struct PlaceLogEntry {
+    int keyframe_id, candidate_id;   // candidate_id = -1: no place recognised
+    int match_count, inlier_count;
+    bool pose_found, loop_attempted;
+    LoopClosureStatus status;        // meaningful with loop_attempted
+    float mean_pixel_distance;
+    double old_T_cur[7];             // qx qy qz qw tx ty tz of the RANSAC start pose (with pose_found)
+  };
+  void SetPlaceRecognition(bool enable, const PlaceRecognitionOptions& options);
+  const std::vector<PlaceLogEntry>& place_recognition_log() const { return place_log_; }
+
   DirectBA& direct_ba() { return *direct_ba_; }
   const BadSlamConfigV1& config() const { return config_; }
   // global_T_frame of every processed frame (index = frame_index - config.start_frame)
@@ -103,6 +122,7 @@ class BadSlam {
   std::shared_ptr<Keyframe> CreateKeyframe(int frame_index);                                // :953-1097
   void CloseLoopUpTo(int frame_index, int matched_id, const SE3f& old_T_cur_initial, LoopClosureResult* result);
   void SearchLoopCandidate(int frame_index, const Keyframe& new_keyframe);
+  void RunPlaceRecognition(int frame_index, const Keyframe& new_keyframe);
   SE3f& FramePose(int frame_index) { return frame_global_T_frame_.at(static_cast<size_t>(frame_index - config_.start_frame)); }
 
   BadSlamConfigV1 config_;
@@ -136,6 +156,9 @@ class BadSlam {
   bool loop_candidate_search_ = false;
   int loop_min_keyframe_gap_ = 0;
   std::vector<LoopLogEntry> loop_log_;
+  bool place_recognition_ = false;
+  PlaceRecognitionOptions place_options_;
+  std::vector<PlaceLogEntry> place_log_;
 };
 
 // BS/trajectory_deformation.cc:33-43 / :45-146 on a plain pose vector (frame_poses[i] = pose of frame start_frame + i)

@@ -12,6 +12,7 @@
 #include "io.hpp"
 #include "loop_closure.hpp"
 #include "pairwise_frame_tracking.hpp"
+#include "place_recognition.hpp"
 #include "pose_graph.hpp"
 #include "rectification.hpp"
 
@@ -580,6 +581,80 @@ int bsh_close_loop(void* ba_, void* stream, int current_id, int matched_id, cons
   });
 }
 
+// ---- place recognition (host/place_recognition.hpp) ----
+// options: [min_keyframe_gap, score_threshold, max_distance, min_matches, ransac_iterations, ransac_min_inliers]
+static PlaceRecognitionOptions place_options_in(const int64_t* options6, double ransac_inlier_threshold) {
+  PlaceRecognitionOptions o;
+  o.min_keyframe_gap = static_cast<int>(options6[0]); o.score_threshold = options6[1]; o.max_distance = static_cast<int>(options6[2]);
+  o.min_matches = static_cast<int>(options6[3]); o.ransac_iterations = static_cast<int>(options6[4]); o.ransac_min_inliers = static_cast<int>(options6[5]);
+  o.ransac_inlier_threshold = ransac_inlier_threshold;
+  return o;
+}
+// the defaults of PlaceRecognitionOptions in the layout above
+int bsh_place_default_options(int64_t* options6, double* ransac_inlier_threshold) {
+  const PlaceRecognitionOptions o;
+  options6[0] = o.min_keyframe_gap; options6[1] = o.score_threshold; options6[2] = o.max_distance; options6[3] = o.min_matches;
+  options6[4] = o.ransac_iterations; options6[5] = o.ransac_min_inliers;
+  *ransac_inlier_threshold = o.ransac_inlier_threshold;
+  return 0;
+}
+// EstimateRelativePose (no GPU): points as n x 3 doubles; pose7 = old_T_cur [qx qy qz qw tx ty tz]; inliers: n bytes (may be null).
+// Returns 1 when an estimate was found, 0 when it was rejected, -1 on error.
+int bsh_estimate_relative_pose(int current_id, int matched_id, int n, const double* p_cur, const double* p_old, int iterations, double inlier_threshold,
+                               int min_inliers, double* pose7, int* inlier_count, uint8_t* inliers) {
+  int found = 0;
+  const int rc = [&]() -> int {
+    BSH_TRY({
+      RelativePoseEstimate e;
+      EstimateRelativePose(current_id, matched_id, n, p_cur, p_old, iterations, inlier_threshold, min_inliers, &e);
+      for (int i = 0; i < 4; ++i) pose7[i] = e.q[i];
+      for (int i = 0; i < 3; ++i) pose7[4 + i] = e.t[i];
+      *inlier_count = e.inlier_count;
+      if (inliers) std::memcpy(inliers, e.inliers.data(), e.inliers.size());
+      found = e.found ? 1 : 0;
+    });
+  }();
+  return rc < 0 ? rc : found;
+}
+uint32_t bsh_place_ransac_seed(int current_id, int matched_id) { return PlaceRansacSeed(current_id, matched_id); }
+int bsh_place_cells(void* ba) {
+  int cells = 0;
+  const int rc = [&]() -> int { BSH_TRY(cells = static_cast<DirectBA*>(ba)->place_recognizer().cells()); }();
+  return rc < 0 ? rc : cells;
+}
+// xy: cells words, desc: cells x 8 words (bsh_place_cells)
+int bsh_extract_keyframe_features(void* ba, void* stream, int keyframe_id, int64_t score_threshold, uint32_t* xy, uint32_t* desc) {
+  BSH_TRY({
+    std::vector<u32> x, d;
+    static_cast<DirectBA*>(ba)->ExtractKeyframeFeatures(static_cast<hipStream_t>(stream), keyframe_id, score_threshold, &x, &d);
+    std::memcpy(xy, x.data(), x.size() * sizeof(u32));
+    std::memcpy(desc, d.data(), d.size() * sizeof(u32));
+  });
+}
+// match: n x cells, count: n
+int bsh_match_keyframe_features(void* ba, void* stream, int query_id, int n, const int* ids, int max_distance, int32_t* match, uint32_t* count) {
+  BSH_TRY({
+    std::vector<int32_t> m;
+    std::vector<u32> c;
+    static_cast<DirectBA*>(ba)->MatchKeyframeFeatures(static_cast<hipStream_t>(stream), query_id, std::vector<int>(ids, ids + n), max_distance, &m, &c);
+    std::memcpy(match, m.data(), m.size() * sizeof(int32_t));
+    std::memcpy(count, c.data(), c.size() * sizeof(u32));
+  });
+}
+// out5: [candidate id, match count, inlier count, pose found, loop attempted]; pose7: the RANSAC old_T_cur in double;
+// ints / floats / chi2: the LoopClosureResult as bsh_close_loop reports it (meaningful with loop attempted).
+int bsh_recognize_place(void* ba, void* stream, int current_id, const int64_t* options6, double ransac_inlier_threshold, int num_scales, int* out5, double* pose7,
+                        int* ints, float* floats, double* chi2) {
+  BSH_TRY({
+    PlaceRecognitionResult r;
+    static_cast<DirectBA*>(ba)->RecognizePlace(static_cast<hipStream_t>(stream), current_id, place_options_in(options6, ransac_inlier_threshold), num_scales, &r);
+    out5[0] = r.candidate_id; out5[1] = r.match_count; out5[2] = r.pose.inlier_count; out5[3] = r.pose.found ? 1 : 0; out5[4] = r.loop_attempted ? 1 : 0;
+    for (int i = 0; i < 4; ++i) pose7[i] = r.pose.q[i];
+    for (int i = 0; i < 3; ++i) pose7[4 + i] = r.pose.t[i];
+    loop_result_out(r.loop, num_scales, ints, floats, chi2);
+  });
+}
+
 // ---- pose graph (host/pose_graph.hpp); poses as double pose7 [qx qy qz qw tx ty tz] ----
 static Pose3d pose3d_from7(const double* p) { return Pose3d::FromQuaternion(p[0], p[1], p[2], p[3], p[4], p[5], p[6]); }
 static void pose3d_to7(const Pose3d& T, double* p) {
@@ -753,6 +828,23 @@ int bsh_slam_loop_log(void* slam, int* entries3, float* distances, int capacity)
       entries3[3 * i + 1] = log[i].candidate_id;
       entries3[3 * i + 2] = static_cast<int>(log[i].status);
       distances[i] = log[i].mean_pixel_distance;
+    }
+  });
+}
+int bsh_slam_set_place_recognition(void* slam, int enable, const int64_t* options6, double ransac_inlier_threshold) {
+  BSH_TRY(static_cast<BadSlam*>(slam)->SetPlaceRecognition(enable != 0, enable ? place_options_in(options6, ransac_inlier_threshold) : PlaceRecognitionOptions()));
+}
+int bsh_slam_place_log_size(void* slam) { return static_cast<int>(static_cast<BadSlam*>(slam)->place_recognition_log().size()); }
+// entries x [keyframe id, candidate id, match count, inlier count, pose found, loop attempted, status]; distances: entries floats; poses7: entries x 7 doubles
+int bsh_slam_place_log(void* slam, int* entries7, float* distances, double* poses7, int capacity) {
+  BSH_TRY({
+    const auto& log = static_cast<BadSlam*>(slam)->place_recognition_log();
+    for (size_t i = 0; i < log.size() && static_cast<int>(i) < capacity; ++i) {
+      int* e = entries7 + 7 * i;
+      e[0] = log[i].keyframe_id; e[1] = log[i].candidate_id; e[2] = log[i].match_count; e[3] = log[i].inlier_count; e[4] = log[i].pose_found ? 1 : 0;
+      e[5] = log[i].loop_attempted ? 1 : 0; e[6] = static_cast<int>(log[i].status);
+      distances[i] = log[i].mean_pixel_distance;
+      for (int j = 0; j < 7; ++j) poses7[7 * i + j] = log[i].old_T_cur[j];
     }
   });
 }

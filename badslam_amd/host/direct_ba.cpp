@@ -2,6 +2,8 @@
 // the C ABI of include/badslam_hip.h (BS = applications/badslam/src/badslam of pangfumin/badslam).
 #include "direct_ba.hpp"
 
+#include "place_recognition.hpp"   // ~DirectBA destroys the PlaceRecognizer
+
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
@@ -243,6 +245,7 @@ DirectBA::DirectBA(int max_surfel_count, float raw_to_float_depth, float baselin
 DirectBA::~DirectBA() {
   for (auto& e : ev_) { hipError_t r = hipEventDestroy(e); (void)r; }
   keyframes_.clear();
+  place_recognizer_.reset();
   if (ctx_) bslam_destroy(ctx_);
 }
 

@@ -152,6 +152,10 @@ class CameraFrustum {
   float bb_min_[3], bb_max_[3];
 };
 
+class PlaceRecognizer;            // host/place_recognition.hpp
+struct PlaceRecognitionOptions;
+struct PlaceRecognitionResult;
+
 class Timer;   // reference API placeholder (BS/direct_ba.h:158); only a null pointer is accepted
 
 class DirectBA {
@@ -217,6 +221,21 @@ class DirectBA {
     std::vector<float> normal;    // 3 per pixel, camera frame
   };
   void RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views);
+
+  // Place recognition (host/place_recognition.hpp; the methods are defined in place_recognition.cpp).  The database of
+  // keyframe features is created by the first of these calls; an object that never calls them allocates and launches
+  // nothing for it.
+  // Extracts keyframe_id's features into its database slot and, with xy and desc given, downloads them: xy[cells],
+  // desc[cells][8] as bslam_extract_keyframe_features writes them.
+  void ExtractKeyframeFeatures(hipStream_t stream, int keyframe_id, int64_t score_threshold, std::vector<u32>* xy, std::vector<u32>* desc);
+  // One match launch of keyframe query_id against the extracted keyframes `ids`: match[ids.size()][cells], count[ids.size()].
+  void MatchKeyframeFeatures(hipStream_t stream, int query_id, const std::vector<int>& ids, int max_distance, std::vector<int32_t>* match, std::vector<u32>* count);
+  // Adds every keyframe up to current_id that the database lacks, picks the candidate (PlaceRecognizer::Query), estimates
+  // old_T_cur from the matched pixels' depths (EstimateRelativePose) and hands it to CloseLoop.  Keyframe poses change
+  // only when result->loop.status is kLoopClosed.
+  void RecognizePlace(hipStream_t stream, int current_id, const PlaceRecognitionOptions& options, int num_scales, PlaceRecognitionResult* result);
+  PlaceRecognizer& place_recognizer();
+  void ResetPlaceRecognizer();   // releases the database
 
   // The objective the BA minimises (bslam_compute_ba_cost: Tukey depth terms and kDescWeight * Huber on both descriptor
   // residuals) at the keyframes' current poses, intrinsics and cfactors: every non-deleted keyframe whatever its activation, every
@@ -356,6 +375,7 @@ class DirectBA {
   std::unique_ptr<DeviceBuffer<u32>> render_index_;
   std::unique_ptr<DeviceBuffer<uchar4_t>> render_color_;
   std::unique_ptr<DeviceBuffer<float>> render_normal_;   // 3 floats per pixel
+  std::unique_ptr<PlaceRecognizer> place_recognizer_;   // null until place recognition is used
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

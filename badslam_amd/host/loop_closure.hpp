@@ -1,7 +1,8 @@
 // loop_closure.hpp -- the closure half of vis::LoopDetector::AddImage (BS/loop_detector.cc:440-712, after the RANSAC
 // step): verify a loop candidate with three direct pairwise trackings, average them, decide whether bundle adjustment
-// could close the loop by itself, and otherwise close it with a keyframe pose graph (host/pose_graph.hpp).  Place
-// recognition (DBoW2 on BRIEF features) and the RANSAC initial pose (opengv) stay with the caller.
+// could close the loop by itself, and otherwise close it with a keyframe pose graph (host/pose_graph.hpp).  The
+// candidate and the initial pose come from the caller: host/place_recognition.hpp finds both from the images (in place of
+// the reference's DBoW2 query and opengv RANSAC).
 #pragma once
 
 #include <vector>

@@ -586,6 +586,43 @@ int bslam_render_surfels(bslam_context* ctx, void* stream, const bslam_mat3x4* c
                          float radius_scale, float metres_to_depth, const bslam_buffer2d* out_depth,
                          const bslam_buffer2d* out_index, const bslam_buffer2d* out_color, const bslam_buffer2d* out_normal);
 
+/* Place recognition (in place of the FAST + BRIEF + DBoW2 half of vis::LoopDetector::AddImage, BS/loop_detector.cc:98-127,
+ * 160-167): one Harris corner with an unoriented 256-bit BRIEF descriptor per cell of 16 x 16 pixels of a keyframe.  All
+ * arithmetic is integer (csrc/place_kernels.hpp, DESIGN.md 8 "Place recognition"); two calls give identical bits.
+ *   color   uchar4 image; byte 3 is the intensity L that bslam_compute_brightness writes.  Rows 4 byte aligned.
+ *   depth   u16 image of the same size (at most 65535 x 65535).  Rows 2 byte aligned.
+ *   cells = (height / 16) * (width / 16), row-major; partial cells at the right and bottom are ignored
+ *   score = 16 (A B - C C) - (A + B)^2 in int64 with A, B, C the 5 x 5 sums of gx^2, gy^2, gx gy of the Sobel gradients
+ *   A pixel is eligible iff it lies 16 pixels inside the image, its depth is neither 0 nor has bit 15 set, and
+ *   score > score_threshold.  The feature of a cell is its eligible pixel of highest score (ties: lowest y, then x).
+ *   out_xy[cells]       x | y << 16, or 0xFFFFFFFF for a cell without a feature
+ *   out_desc[cells][8]  bit i (word i / 32, bit i % 32) = S(p + a_i) < S(p + b_i), S the 5 x 5 box sum of L and (a_i, b_i)
+ *                       pair i of bslam_place_pattern; all zero for a cell without a feature
+ * The outputs are device arrays, 4 byte aligned, that overlap neither each other nor the images.  Launched on `stream`
+ * without synchronisation (the first call of a context uploads the point pairs synchronously). */
+int bslam_extract_keyframe_features(bslam_context* ctx, void* stream, const bslam_buffer2d* color, const bslam_buffer2d* depth,
+                                    int64_t score_threshold, uint32_t* out_xy, uint32_t* out_desc);
+
+/* The 256 point pairs of the descriptor as pairs[256][4] = (ax, ay, bx, by), each in -13 ... 13 (HOST array, no GPU
+ * needed).  Generator: s = 0x0BAD51A4; a draw is s = s * 1664525 + 1013904223 mod 2^32 -> ((s >> 16) % 27) - 13; four
+ * draws per pair; a pair with a == b is drawn again. */
+int bslam_place_pattern(int8_t* pairs);
+
+/* Matches the features of one keyframe against n_db database keyframes by Hamming distance with a ratio test.
+ *   query_xy[cells], query_desc[cells][8]   as bslam_extract_keyframe_features writes them
+ *   database   n_db keyframes of 9 * cells words each: xy[cells] followed by desc[cells][8] (so a keyframe's slot is
+ *              what the extraction writes with out_xy = slot, out_desc = slot + cells)
+ *   For a non-empty query slot q and database keyframe k: best = the smallest distance over k's non-empty slots (ties:
+ *   the lowest slot), second = the smallest over the remaining slots (257 if none; a duplicate of the best descriptor
+ *   gives second == best).  Accepted iff best <= max_distance and 4 best < 3 second.
+ *   out_match[n_db][cells]  int32: the matched slot, or -1 (empty query slot, k without features, rejected)
+ *   out_count[n_db]         uint32: accepted matches of keyframe k
+ * cells in 1 ... 2^24, n_db in 0 ... 65535 (0: nothing is launched, nothing is read), max_distance in 0 ... 256.  All
+ * arrays are device memory, 4 byte aligned; the outputs overlap neither each other nor the inputs.  Launched on `stream`
+ * without synchronisation. */
+int bslam_match_features(bslam_context* ctx, void* stream, const uint32_t* query_xy, const uint32_t* query_desc, int cells,
+                         const uint32_t* database, int n_db, int max_distance, int32_t* out_match, uint32_t* out_count);
+
 /* Replaces ComputeBrightnessCUDA (BS/cuda_image_processing.cuh, kernel BS/cuda_image_processing.cu:165-194):
  * rgb_buffer has 3 bytes per pixel, color_buffer 4 (r, g, b, luma). */
 int bslam_compute_brightness(bslam_context* ctx, void* stream,

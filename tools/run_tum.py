@@ -7,6 +7,7 @@ has a ground truth, prints the ATE RMSE.
                             [--ba-iterations 10] [--max-depth 3.0] [--end-frame N] [--ba-cost]
                             [--pyramid-level-for-depth L] [--pyramid-level-for-color L]
                             [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
+                            [--place-recognition] [--place-min-gap N]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -14,6 +15,10 @@ sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320
 
 --ba-cost: after the last frame, one more BA over the whole window (poses + geometry), with the BA objective printed before and
 after it (DirectBA.ComputeCost: Tukey depth terms + weighted Huber descriptor terms over all surfel / keyframe pairs).
+
+--place-recognition: every new keyframe is matched against the keyframes at least --place-min-gap (default 10) ids older
+(BadSlam.set_place_recognition: one Harris / BRIEF feature per 16 x 16 cell, brute-force matching, 3D-3D RANSAC start pose,
+CloseLoop); the recognised places and what became of them are printed after the run.  Both streams must use the same level.
 
 --render-dir DIR: after the run, the reconstructed surfel model is rendered from the pose of every keyframe (--render-every N:
 of every N-th) with the depth camera as the run left it (DirectBA.RenderModel) and written to DIR as a TUM-style directory that
@@ -85,7 +90,8 @@ def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0):
 
 def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterations=10, max_depth=3.0, end_frame=None, raw_to_float_depth=1.0 / 5000,
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
-        median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None):
+        median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
+        place_recognition=False, place_min_gap=10):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -98,6 +104,10 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
                             num_scales=num_scales, max_surfel_count=max_surfel_count, raw_to_float_depth=raw_to_float_depth, max_depth=max_depth,
                             pyramid_level_for_depth=pyramid_level_for_depth, pyramid_level_for_color=pyramid_level_for_color,
                             median_filter_and_densify_iterations=median_filter_and_densify_iterations)
+    if place_recognition:
+        if pyramid_level_for_depth != pyramid_level_for_color:
+            raise ValueError("--place-recognition needs colour and depth images of one size: use the same pyramid level for both streams")
+        slam.set_place_recognition(True, min_keyframe_gap=place_min_gap)
     keyframes = []          # (keyframe id, timestamp string) in the order of creation
     for k, fr in enumerate(frames):
         slam.ProcessFrame(k, dba.read_png(fr["depth_path"]), dba.read_png(fr["rgb_path"]))
@@ -114,6 +124,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     out = out or os.path.join(str(dataset_dir), "poses_badslam_amd.txt")
     dba.save_poses([f["depth_timestamp"] for f in frames], poses, 0, out)
     result.update({"frames": len(frames), "keyframes": slam.ba().keyframe_count(), "surfels": slam.ba().surfels_size(), "poses_file": out})
+    if place_recognition:
+        result["place_recognition"] = slam.place_recognition_log()
     if render_dir:
         result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, float(render_radius_scale or cell))
         result["render_dir"] = str(render_dir)
@@ -140,6 +152,8 @@ def arg_parser():
     ap.add_argument("--render-dir", default=None)
     ap.add_argument("--render-every", type=int, default=1)
     ap.add_argument("--render-radius-scale", type=float, default=None)
+    ap.add_argument("--place-recognition", action="store_true")
+    ap.add_argument("--place-min-gap", type=int, default=10)
     return ap
 
 
@@ -148,10 +162,14 @@ def main():
     r = run(a.dataset_dir, a.trajectory, a.out, a.keyframe_interval, a.ba_iterations, a.max_depth, a.end_frame, ba_cost=a.ba_cost,
             pyramid_level_for_depth=a.pyramid_level_for_depth, pyramid_level_for_color=a.pyramid_level_for_color,
             median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
-            render_radius_scale=a.render_radius_scale)
+            render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
+    for e in r.get("place_recognition", []):
+        if e["candidate"] >= 0:
+            print(f"keyframe {e['keyframe']}: place of keyframe {e['candidate']} ({e['match_count']} matches, {e['inlier_count']} inliers) -> "
+                  f"{e['status'] if e['loop_attempted'] else 'no start pose'}")
     if "rendered" in r:
         print(f"{len(r['rendered'])} model views -> {r['render_dir']}")
     if "ate" in r:

@@ -169,8 +169,10 @@ static int upload_kf_table(bslam_context* ctx, hipStream_t stream, std::vector<K
   const bool with_color = !table.empty() && table[0].color != nullptr;
   const size_t quads_per_kf = (size_t)(c.color_width + 1) * (size_t)(c.color_height + 1);
   if (with_color) {
-    if ((rc = ctx->quads.reserve(table.size() * quads_per_kf * sizeof(uint32_t)))) return rc;
-    for (size_t k = 0; k < table.size(); ++k) table[k].quads = (const uint32_t*)ctx->quads.ptr + k * quads_per_kf;
+    if (!quad_table_addressable(c.color_width, c.color_height))
+      return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", c.color_width, c.color_height);
+    if ((rc = ctx->quads.reserve(table.size() * quads_per_kf * sizeof(QuadEntry)))) return rc;
+    for (size_t k = 0; k < table.size(); ++k) table[k].quads = (const QuadEntry*)ctx->quads.ptr + k * quads_per_kf;
   } else {
     for (size_t k = 0; k < table.size(); ++k) table[k].quads = nullptr;
   }
@@ -217,7 +219,7 @@ static int upload_kf_table(bslam_context* ctx, hipStream_t stream, std::vector<K
   }
   if (rebuild_quads) {
     hipLaunchKernelGGL(build_quads_kernel, dim3((unsigned)((c.color_width + 1 + 255) / 256), (unsigned)(c.color_height + 1), (unsigned)table.size()), dim3(256), 0, stream,
-                       c, (const KfDev*)ctx->kf_table.ptr, (uint32_t*)ctx->quads.ptr);
+                       c, (const KfDev*)ctx->kf_table.ptr, (QuadEntry*)ctx->quads.ptr);
     BSLAM_HIP_TRY(hipGetLastError());
   }
   return BSLAM_OK;
@@ -913,6 +915,65 @@ int bslam_debug_desc_pair(bslam_context* ctx, void* stream_, int count, const fl
   hipLaunchKernelGGL(desc_pair_probe_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, count, (const float*)d_in, d_out);
   BSLAM_HIP_TRY(hipGetLastError());
   BSLAM_HIP_TRY(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, stream));
+  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+  return BSLAM_OK;
+}
+
+int bslam_debug_quad_samples(bslam_context* ctx, void* stream_, int image_count, int width, int height, int channels, const uint8_t* images,
+                             int count, const float* positions, int tex_mode, float* out, uint16_t* entries) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx || !images || !entries || (count > 0 && (!positions || !out))) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  if (channels != 1 && channels != 4) return fail(BSLAM_ERR_INVALID_ARGUMENT, "channels must be 4 (keyframe colour) or 1 (u8 image), not %d", channels);
+  if (image_count < 1 || image_count > kMaxPairBatch) return fail(BSLAM_ERR_INVALID_ARGUMENT, "image_count must be 1 .. %d", kMaxPairBatch);
+  if (!quad_table_addressable(width, height)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "image %dx%d is beyond the luma quad table's 32-bit addressing", width, height);
+  if (tex_mode != BSLAM_TEX_FIXED_POINT_1_8 && tex_mode != BSLAM_TEX_EXACT_FLOAT) return fail(BSLAM_ERR_INVALID_ARGUMENT, "unknown texture mode %d", tex_mode);
+  for (int t = 0; t < count; ++t)
+    if (!(positions[3 * t] >= 0.f && positions[3 * t] < (float)image_count) || !std::isfinite(positions[3 * t + 1]) || !std::isfinite(positions[3 * t + 2]))
+      return fail(BSLAM_ERR_INVALID_ARGUMENT, "position %d names no image or is not finite", t);
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t pitch = (size_t)width * channels, image_bytes = pitch * height, quads_per_image = (size_t)(width + 1) * (height + 1);
+  const size_t o_pos = up(image_bytes * image_count), o_out = o_pos + up((size_t)count * 3 * sizeof(float)), o_tab = o_out + up((size_t)count * 6 * sizeof(float));
+  const size_t o_kfs = o_tab + up(quads_per_image * image_count * sizeof(QuadEntry));
+  int rc = ctx->coeffs.reserve(o_kfs + up(image_count * sizeof(KfDev)));
+  if (rc) return rc;
+  uint8_t* base = (uint8_t*)ctx->coeffs.ptr;
+  QuadEntry* table = (QuadEntry*)(base + o_tab);
+  std::vector<KfDev> kfs(image_count);
+  std::memset((void*)kfs.data(), 0, image_count * sizeof(KfDev));
+  for (int k = 0; k < image_count; ++k) {
+    kfs[k].color = base + k * image_bytes;
+    kfs[k].color_pitch = (uint32_t)pitch;
+    kfs[k].quads = table + k * quads_per_image;
+  }
+  CamConsts c;
+  std::memset((void*)&c, 0, sizeof(c));
+  c.color_width = width; c.color_height = height; c.tex_mode = tex_mode;
+  BSLAM_HIP_TRY(hipMemcpyAsync(base, images, image_bytes * image_count, hipMemcpyHostToDevice, stream));
+  BSLAM_HIP_TRY(hipMemcpyAsync(base + o_kfs, kfs.data(), image_count * sizeof(KfDev), hipMemcpyHostToDevice, stream));
+  if (count > 0) BSLAM_HIP_TRY(hipMemcpyAsync(base + o_pos, positions, (size_t)count * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+  BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // `kfs` is a local vector
+  // the table through the kernel that builds it in production: keyframe colour (build_quads_kernel), one u8 image
+  // (build_quads_u8_kernel), several u8 images (build_quads_u8_batched_kernel)
+  const dim3 grid((unsigned)((width + 1 + 255) / 256), (unsigned)(height + 1), (unsigned)image_count);
+  if (channels == 4) {
+    hipLaunchKernelGGL(build_quads_kernel, grid, dim3(256), 0, stream, c, (const KfDev*)(base + o_kfs), table);
+  } else if (image_count == 1) {
+    hipLaunchKernelGGL(build_quads_u8_kernel, grid, dim3(256), 0, stream, Img{base, (uint32_t)pitch, width, height}, table);
+  } else {
+    PairBatch batch;
+    std::memset((void*)&batch, 0, sizeof(batch));
+    for (int k = 0; k < image_count; ++k) batch.im[k].frame_color = Img{base + k * image_bytes, (uint32_t)pitch, width, height};
+    hipLaunchKernelGGL(build_quads_u8_batched_kernel, grid, dim3(256), 0, stream, batch, table, quads_per_image);
+  }
+  BSLAM_HIP_TRY(hipGetLastError());
+  if (count > 0) {
+    hipLaunchKernelGGL(quad_samples_probe_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, stream, c, (const KfDev*)(base + o_kfs), channels,
+                       channels == 4 ? 3 : 0, count, (const float*)(base + o_pos), (float*)(base + o_out));
+    BSLAM_HIP_TRY(hipGetLastError());
+    BSLAM_HIP_TRY(hipMemcpyAsync(out, base + o_out, (size_t)count * 6 * sizeof(float), hipMemcpyDeviceToHost, stream));
+  }
+  BSLAM_HIP_TRY(hipMemcpyAsync(entries, table, quads_per_image * image_count * sizeof(QuadEntry), hipMemcpyDeviceToHost, stream));
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));
   return BSLAM_OK;
 }

@@ -130,7 +130,7 @@ struct bslam_context {
   int cu_count = 256;
   bslam::Slab kf_table;      // KfDev[K]
   bslam::Slab records;       // PixelRecord[K][h][w] derived pixel records (16 B)
-  bslam::Slab quads;         // uint32[K][ch+1][cw+1] derived luma quads (only when colour images are given)
+  bslam::Slab quads;         // QuadEntry[K][ch+1][cw+1] derived luma quads, 8 bytes each (only when colour images are given)
   bslam::Slab partials;      // float[tiles][K][32]
   bslam::Slab coeffs;        // float[K][32]
   bslam::Slab pose_state;    // PoseState[K]

@@ -75,6 +75,20 @@ struct CamConsts {
 
 struct __attribute__((aligned(16))) PixelRecord { float depth, nx, ny, nz; };
 
+// One entry of a luma quad table (KfDev::quads): {tl, dtop, dleft, dmix} as IEEE halves, 8 bytes.
+typedef _Float16 QuadEntry __attribute__((ext_vector_type(4)));
+// The entry of the byte quad {tl, tr, bl, br}: the three differences formed in integers (|.| <= 510 < 2048, so each is exact in
+// fp16's 11-bit significand), each converted once.
+__host__ __device__ __forceinline__ QuadEntry pack_quad(uint32_t tl, uint32_t tr, uint32_t bl, uint32_t br) {
+  const int dtop = (int)tr - (int)tl;
+  QuadEntry e;
+  e.x = (_Float16)(int)tl;
+  e.y = (_Float16)dtop;
+  e.z = (_Float16)((int)bl - (int)tl);
+  e.w = (_Float16)(((int)br - (int)bl) - dtop);
+  return e;
+}
+
 // Device view of one keyframe (pointers + pose), kept in a device array and read with scalar loads.
 struct KfDev {
   const uint8_t* depth;    uint32_t depth_pitch;
@@ -84,10 +98,11 @@ struct KfDev {
   // derived per-pixel records {f32 calibrated depth (0: no measurement), decoded pixel normal x, y, z}, row pitch in
   // records = image width (library-owned, rebuilt by build_records_kernel)
   const PixelRecord* records;
-  // derived luma quads: quads[(j + 1) * (color_width + 1) + (i + 1)] packs the 2x2 texel footprint
-  // {L(i,j), L(i+1,j), L(i,j+1), L(i+1,j+1)} (clamp addressing, i in [-1, w-1], j in [-1, h-1]) so that a
-  // bilinear sample is ONE 4-byte gather instead of four byte gathers (library-owned, build_quads_kernel)
-  const uint32_t* quads;
+  // derived luma quads: quads[(j + 1) * (color_width + 1) + (i + 1)] holds the 2x2 texel footprint
+  // {L(i,j), L(i+1,j), L(i,j+1), L(i+1,j+1)} (clamp addressing, i in [-1, w-1], j in [-1, h-1]) as the four numbers the
+  // sample filters are built from, {tl, tr - tl, bl - tl, (br - bl) - (tr - tl)} in fp16 (pack_quad), so that a bilinear sample
+  // is ONE 8-byte gather instead of four byte gathers and no unpacking (library-owned, build_quads_kernel)
+  const QuadEntry* quads;
   M34 frame_T_global;
   float global_R_frame[9];
   int activation;
@@ -290,24 +305,21 @@ __device__ __forceinline__ PixelRecord gload_record(const PixelRecord* p) {   //
 
 struct LumaQuad { float tl, tr, bl, br; };   // texels (i,j), (i+1,j), (i,j+1), (i+1,j+1) in [0,1]
 
-__device__ __forceinline__ LumaQuad unpack_quad(uint32_t q) {
-  LumaQuad r;
-  r.tl = (float)(q & 0xffu) * (1.0f / 255.0f);
-  r.tr = (float)((q >> 8) & 0xffu) * (1.0f / 255.0f);
-  r.bl = (float)((q >> 16) & 0xffu) * (1.0f / 255.0f);
-  r.br = (float)(q >> 24) * (1.0f / 255.0f);
-  return r;
+// Largest colour image a quad table addresses with quad_at's 32-bit offset: the row pitch 8 (w + 1) and the row j are the 24-bit
+// signed factors of v_mad_i32_i24, and the byte offset inside one keyframe's table stays below 2^31.
+__host__ __device__ __forceinline__ bool quad_table_addressable(int w, int h) {
+  return w >= 1 && h >= 1 && (long long)w + 1 < (1ll << 20) && (long long)h + 1 < (1ll << 23) &&
+         8ll * ((long long)w + 1) * ((long long)h + 1) < (1ll << 31);
 }
-
 // i in [-1, w-1], j in [-1, h-1]
-__device__ __forceinline__ uint32_t quad_at(const KfDev& kf, const CamConsts& c, int i, int j) {
-  // byte offset inside one keyframe's table: < 2^26, 32-bit arithmetic (v_mul_u32_u24, v_lshl_add_u32) on top of the uniform base
-  // (j + 1) * pitch + (i + 1) * 4 as  j * pitch + (4 i + (pitch + 4)):  v_lshl_add_u32 + v_mad_i32_i24 (j and i may be -1; the sum is not)
-  const int pitch = 4 * (c.color_width + 1);
-  const uint32_t t = ((uint32_t)i << 2) + (uint32_t)(pitch + 4);
+__device__ __forceinline__ QuadEntry quad_at(const KfDev& kf, const CamConsts& c, int i, int j) {
+  // byte offset inside one keyframe's table (quad_table_addressable, checked on the host): 32-bit arithmetic on top of the uniform base
+  // (j + 1) * pitch + (i + 1) * 8 as  j * pitch + (8 i + (pitch + 8)):  v_lshl_add_u32 + v_mad_i32_i24 (j and i may be -1; the sum is not)
+  const int pitch = 8 * (c.color_width + 1);
+  const uint32_t t = ((uint32_t)i << 3) + (uint32_t)(pitch + 8);
   uint32_t off;   // written out: the compiler splits the constant off again and spends a third instruction on it
   asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(off) : "v"(j), "s"(pitch), "v"(t));
-  return gload_at(kf.quads, off);
+  return gload_at(kf.quads, off);   // one global_load_dwordx2
 }
 
 // Bilinear footprint of a sample at pixel-corner coordinates (x, y): base texel (clamped to the quad
@@ -362,13 +374,30 @@ __device__ __forceinline__ float tex_filter(const LumaQuad& t, float a, float b)
 // The CPU checker evaluates the same sequences, so the two agree to the bit; the reference's formula as written is its
 // "literal" mode.
 constexpr float kDescScale = 180.f / 255.f;
-__device__ __forceinline__ LumaQuad unpack_quad_bytes(uint32_t q) {
+// The four texels of an entry in byte units: tr = tl + dtop, bl = tl + dleft, br = bl + (dmix + dtop) -- float adds of small
+// integers, exact, so these are the bytes the table was built from.
+__device__ __forceinline__ LumaQuad unpack_quad_bytes(QuadEntry e) {
+  const float tl = (float)e.x, dtop = (float)e.y, dleft = (float)e.z, dmix = (float)e.w;
   LumaQuad r;
-  r.tl = (float)(q & 0xffu);
-  r.tr = (float)((q >> 8) & 0xffu);
-  r.bl = (float)((q >> 16) & 0xffu);
-  r.br = (float)(q >> 24);
+  r.tl = tl;
+  r.tr = tl + dtop;
+  r.bl = tl + dleft;
+  r.br = r.bl + (dmix + dtop);
   return r;
+}
+// the same in [0, 1] (tex_filter's unit)
+__device__ __forceinline__ LumaQuad unpack_quad(QuadEntry e) {
+  LumaQuad r = unpack_quad_bytes(e);
+  r.tl *= 1.0f / 255.0f; r.tr *= 1.0f / 255.0f; r.bl *= 1.0f / 255.0f; r.br *= 1.0f / 255.0f;
+  return r;
+}
+// bilinear_bytes on an entry: tr - tl IS dtop, br - bl is dmix + dtop and bl is tl + dleft (exact), so the three fmas see the
+// operands they saw on the unpacked bytes
+__device__ __forceinline__ float bilinear_bytes_entry(QuadEntry e, float a, float b) {
+  const float tl = (float)e.x, dtop = (float)e.y, dleft = (float)e.z, dmix = (float)e.w;
+  const float top = __builtin_fmaf(a, dtop, tl);
+  const float bot = __builtin_fmaf(a, dmix + dtop, tl + dleft);
+  return __builtin_fmaf(b, bot - top, top);
 }
 __device__ __forceinline__ float bilinear_bytes(const LumaQuad& t, float a, float b) {
   const float top = __builtin_fmaf(a, t.tr - t.tl, t.tl);
@@ -379,11 +408,15 @@ __device__ __forceinline__ void bilinear_gradient_bytes(const LumaQuad& t, float
   *dx = __builtin_fmaf(ty, (t.br - t.bl) - (t.tr - t.tl), t.tr - t.tl);
   *dy = __builtin_fmaf(tx, (t.br - t.tr) - (t.bl - t.tl), t.bl - t.tl);
 }
-// A packed quad as the three byte differences both filters are built from, formed in integers (exact) and converted once:
-// tr - tl, bl - tl and the mixed difference (br - bl) - (tr - tl) = (br - tr) - (bl - tl), which the gradient's two components
-// share (bilinear_gradient_bytes writes it once per component, and the compiler forms it twice).
+// A quad as the three byte differences both filters are built from: tr - tl, bl - tl and the mixed difference
+// (br - bl) - (tr - tl) = (br - tr) - (bl - tl), which the gradient's two components share (bilinear_gradient_bytes writes it once
+// per component, and the compiler forms it twice).  The table stores exactly these (pack_quad), so this is conversion only, and
+// the compiler folds each conversion into the fma that reads it (v_fma_mix_f32 with op_sel): a sample is its five fmas.
 struct QuadDiffs { float tl, dtop, dleft, dmix; };
-__device__ __forceinline__ QuadDiffs quad_diffs(uint32_t q) {
+__device__ __forceinline__ QuadDiffs quad_diffs(QuadEntry e) { return QuadDiffs{(float)e.x, (float)e.y, (float)e.z, (float)e.w}; }
+// The same from four packed bytes tl | tr << 8 | bl << 16 | br << 24, formed in integers and converted once: what the kernels
+// did per sample before the table held the differences.  Reference of bslam_debug_quad_samples only.
+__device__ __forceinline__ QuadDiffs quad_diffs_from_bytes(uint32_t q) {
   const int tl = (int)(q & 0xffu), tr = (int)((q >> 8) & 0xffu), bl = (int)((q >> 16) & 0xffu), br = (int)(q >> 24);
   const int dtop = tr - tl;
   return QuadDiffs{(float)tl, (float)dtop, (float)(bl - tl), (float)((br - bl) - dtop)};
@@ -405,7 +438,7 @@ __device__ __forceinline__ float bilinear_diffs_fixed(const QuadDiffs& t, float 
 // bilinear luma in byte units at pixel-corner coordinates (x, y)
 __device__ __forceinline__ float tex_b(const KfDev& kf, const CamConsts& c, float x, float y) {
   const TexFootprint f = tex_footprint(c, x, y);
-  return bilinear_bytes(unpack_quad_bytes(quad_at(kf, c, f.i, f.j)), f.a, f.b);
+  return bilinear_bytes_entry(quad_at(kf, c, f.i, f.j), f.a, f.b);
 }
 
 // BS/cost_function.cuh:115-136
@@ -470,7 +503,7 @@ __device__ __forceinline__ void grad_filter(const LumaQuad& t, const GradFootpri
 // from what the kernel holds anyway) instead of carrying a second set of footprints through every pair.
 struct DescSamples {
   TexFootprint f[3];
-  uint32_t q[3];
+  QuadEntry q[3];
 };
 __device__ __forceinline__ DescSamples descriptor_samples_issue(const KfDev& kf, const CamConsts& c, f2 cp, f2 t1, f2 t2) {
   DescSamples d;
@@ -502,7 +535,7 @@ __device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const
   } else {
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      val[k] = bilinear_bytes(unpack_quad_bytes(d.q[k]), d.f[k].a, d.f[k].b);
+      val[k] = bilinear_bytes_entry(d.q[k], d.f[k].a, d.f[k].b);
       bilinear_gradient_diffs(quad_diffs(d.q[k]), d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
     }
   }
@@ -535,7 +568,7 @@ __device__ __forceinline__ void descriptor_samples_values(const CamConsts& c, co
     for (int k = 0; k < 3; ++k) val[k] = bilinear_diffs_fixed(quad_diffs(d.q[k]), d.f[k].a, d.f[k].b);
   } else {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) val[k] = bilinear_bytes(unpack_quad_bytes(d.q[k]), d.f[k].a, d.f[k].b);
+    for (int k = 0; k < 3; ++k) val[k] = bilinear_bytes_entry(d.q[k], d.f[k].a, d.f[k].b);
   }
   *r1 = __builtin_fmaf(kDescScale, val[1] - val[0], -d1);
   *r2 = __builtin_fmaf(kDescScale, val[2] - val[0], -d2);
@@ -597,7 +630,7 @@ __global__ __launch_bounds__(256) void build_records_kernel(CamConsts c, const K
 }
 
 // Luma quads of every keyframe's colour image (see KfDev::quads); grid (ceil((w+1)/256), h+1, K).
-__global__ __launch_bounds__(256) void build_quads_kernel(CamConsts c, const KfDev* __restrict__ kfs, uint32_t* __restrict__ quads) {
+__global__ __launch_bounds__(256) void build_quads_kernel(CamConsts c, const KfDev* __restrict__ kfs, QuadEntry* __restrict__ quads) {
   const int qx = blockIdx.x * blockDim.x + threadIdx.x;   // = i + 1
   const int qy = blockIdx.y;                              // = j + 1
   const int k = blockIdx.z;
@@ -610,7 +643,49 @@ __global__ __launch_bounds__(256) void build_quads_kernel(CamConsts c, const KfD
   const uint8_t* r1 = kf.color + (size_t)j1 * kf.color_pitch;
   const uint32_t tl = r0[4 * (size_t)i0 + 3], tr = r0[4 * (size_t)i1 + 3];
   const uint32_t bl = r1[4 * (size_t)i0 + 3], br = r1[4 * (size_t)i1 + 3];
-  quads[((size_t)k * (h + 1) + qy) * (size_t)(w + 1) + qx] = tl | (tr << 8) | (bl << 16) | (br << 24);
+  quads[((size_t)k * (h + 1) + qy) * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
+}
+
+// bslam_debug_quad_samples: one bilinear sample {val, gx, gy} (byte units) per position [image, x, y] (pixel-corner coordinates),
+// twice: out[0..3) through the quad table as the kernels read it (tex_footprint, quad_at, quad_diffs, bilinear_diffs_fixed or
+// bilinear_bytes_entry, bilinear_gradient_diffs, and the border strip's second footprint as in descriptor_samples_finish),
+// out[3..6) from four byte loads of the image with clamp addressing, differences formed per sample in integers
+// (quad_diffs_from_bytes), then the same filters.  The luma of pixel (x, y) is byte color[y * pitch + x * pixel_stride + luma_offset].
+__global__ __launch_bounds__(256) void quad_samples_probe_kernel(CamConsts c, const KfDev* __restrict__ kfs, int pixel_stride, int luma_offset, int count,
+                                                                 const float* __restrict__ positions, float* __restrict__ out) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= count) return;
+  const KfDev& kf = kfs[(int)positions[3 * t]];
+  const f2 p{positions[3 * t + 1], positions[3 * t + 2]};
+  const bool fixed = c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8;
+  TexFootprint f = tex_footprint<false>(c, p.x, p.y);
+  const QuadEntry e = quad_at(kf, c, f.i, f.j);
+  tex_weights(c, &f);
+  const GradFootprint g = grad_footprint(c, p);
+  const bool border = ((uint32_t)f.i >= (uint32_t)(c.color_width - 1)) | ((uint32_t)f.j >= (uint32_t)(c.color_height - 1));
+  float val, gx, gy;
+  {
+    const QuadDiffs d = quad_diffs(e);
+    val = fixed ? bilinear_diffs_fixed(d, f.a, f.b) : bilinear_bytes_entry(e, f.a, f.b);
+    bilinear_gradient_diffs(d, f.ua, f.ub, &gx, &gy);
+    if (border) bilinear_gradient_diffs(quad_diffs(quad_at(kf, c, g.ix, g.iy)), g.tx, g.ty, &gx, &gy);
+  }
+  out[6 * t] = val; out[6 * t + 1] = gx; out[6 * t + 2] = gy;
+  auto texel = [&](int ix, int iy) -> uint32_t {
+    ix = max(0, min(ix, c.color_width - 1));
+    iy = max(0, min(iy, c.color_height - 1));
+    return gload(kf.color + (size_t)iy * kf.color_pitch + (size_t)ix * pixel_stride + luma_offset);
+  };
+  auto bytes_at = [&](int ix, int iy) { return texel(ix, iy) | (texel(ix + 1, iy) << 8) | (texel(ix, iy + 1) << 16) | (texel(ix + 1, iy + 1) << 24); };
+  {
+    const uint32_t q = bytes_at(f.i, f.j);
+    const QuadDiffs d = quad_diffs_from_bytes(q);
+    const LumaQuad b{(float)(q & 0xffu), (float)((q >> 8) & 0xffu), (float)((q >> 16) & 0xffu), (float)(q >> 24)};
+    val = fixed ? bilinear_diffs_fixed(d, f.a, f.b) : bilinear_bytes(b, f.a, f.b);
+    bilinear_gradient_diffs(d, f.ua, f.ub, &gx, &gy);
+    if (border) bilinear_gradient_diffs(quad_diffs_from_bytes(bytes_at(g.ix, g.iy)), g.tx, g.ty, &gx, &gy);
+  }
+  out[6 * t + 3] = val; out[6 * t + 4] = gx; out[6 * t + 5] = gy;
 }
 
 // Projection + association in three stages, so that a kernel can put the record gathers of several surfels in flight before
@@ -1074,23 +1149,30 @@ __device__ __forceinline__ float wave_transpose_sum32(float (&v)[32]) {
 // rounds (<= 4 kCols columns) 16 / kCols lanes share a column; with two batches the first lane of a group holds the column of
 // the first batch and the second lane that of the second.
 template <int kLive, int kCols>
-__device__ __forceinline__ void wave_column_sums_owner(int* col, bool* writer) {
+__device__ __forceinline__ void wave_column_sums_owner(uint32_t lane, int* col, bool* writer) {
   constexpr int kBatches = ((kLive + kCols - 1) / kCols + 3) / 4;
   constexpr uint32_t kShare = 16u / kCols;   // lanes per column after the second stage
   static_assert(kBatches == 1 || (kBatches == 2 && kShare >= 2), "two batches need two lanes per column");
-  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t sub = lane % kShare;
   *col = (int)(lane / kShare) + ((kBatches == 2 && sub == 1) ? 4 * kCols : 0);
   *writer = sub < (uint32_t)kBatches && *col < 32;
 }
+template <int kLive, int kCols>
+__device__ __forceinline__ void wave_column_sums_owner(int* col, bool* writer) { wave_column_sums_owner<kLive, kCols>(threadIdx.x & 63u, col, writer); }
+// `lane`: the lane number; a caller short of registers hands in one it has just counted (lane_counted), so that the tile
+// addresses are formed where they are used instead of being carried through the caller's loop.
+__device__ __forceinline__ uint32_t lane_counted() {
+  uint32_t zero = 0;
+  asm volatile("" : "+v"(zero));   // opaque: not hoisted out of a loop
+  return __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, zero));
+}
 template <int kLive, int kCols, int N>
-__device__ __forceinline__ float wave_column_sums_lds(const float (&v)[N], float* __restrict__ tile) {
+__device__ __forceinline__ float wave_column_sums_lds(const float (&v)[N], float* __restrict__ tile, uint32_t lane) {
   static_assert(kLive >= 1 && kLive <= N && N <= 32, "at most 32 columns");
   static_assert(kCols == 4 || kCols == 8, "4 or 8 columns per round");
   constexpr uint32_t L = 64 / kCols;
   constexpr int kRounds = (kLive + kCols - 1) / kCols;
   constexpr int kBatches = (kRounds + 3) / 4;
-  const uint32_t lane = threadIdx.x & 63u;
   const uint32_t g = lane / L, i = lane % L;
   typedef float v4f __attribute__((ext_vector_type(4)));
   float total[kBatches];
@@ -1130,10 +1212,14 @@ __device__ __forceinline__ float wave_column_sums_lds(const float (&v)[N], float
   }
   int col;
   bool writer;
-  wave_column_sums_owner<kLive, kCols>(&col, &writer);
+  wave_column_sums_owner<kLive, kCols>(lane, &col, &writer);
   float t = total[0];
   if constexpr (kBatches == 2) t = (lane % (16u / kCols) == 1) ? total[1] : total[0];
   return (col < kLive) ? t : 0.f;
+}
+template <int kLive, int kCols, int N>
+__device__ __forceinline__ float wave_column_sums_lds(const float (&v)[N], float* __restrict__ tile) {
+  return wave_column_sums_lds<kLive, kCols>(v, tile, threadIdx.x & 63u);
 }
 
 // One row of kCols floats per (keyframe, work slot) from the four waves of a 256-thread workgroup (pose, cost and PCG passes).

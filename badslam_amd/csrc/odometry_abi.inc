@@ -37,13 +37,15 @@ static int run_pair_kernel(bslam_context* ctx, hipStream_t stream, bool coeffs, 
   dp.sparse_surfel_cell_size = 1;
   dp.baseline_fx = baseline_fx;
   const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, &dp);
-  // tracked-frame colour as luma quads (one 4-byte gather per bilinear sample)
+  // tracked-frame colour as luma quads (one 8-byte gather per bilinear sample)
+  if (!quad_table_addressable(frame_color_img.width, frame_color_img.height))
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", frame_color_img.width, frame_color_img.height);
   const size_t quad_count = (size_t)(frame_color_img.width + 1) * (frame_color_img.height + 1);
-  if ((rc = ctx->quads_aux.reserve(quad_count * sizeof(uint32_t)))) return rc;
+  if ((rc = ctx->quads_aux.reserve(quad_count * sizeof(QuadEntry)))) return rc;
   hipLaunchKernelGGL(build_quads_u8_kernel, dim3((unsigned)((frame_color_img.width + 1 + 255) / 256), (unsigned)(frame_color_img.height + 1)), dim3(256), 0, stream,
-                     frame_color_img, (uint32_t*)ctx->quads_aux.ptr);
+                     frame_color_img, (QuadEntry*)ctx->quads_aux.ptr);
   BSLAM_HIP_TRY(hipGetLastError());
-  im.frame_quads = (const uint32_t*)ctx->quads_aux.ptr;
+  im.frame_quads = (const QuadEntry*)ctx->quads_aux.ptr;
   im.frame_color = frame_color_img;
   const int pixels = im.surfel_depth.width * im.surfel_depth.height;
   const int blocks = (pixels + 255) / 256;
@@ -260,10 +262,11 @@ int bslam_accumulate_pose_coeffs_from_images_batched(
   // every pair's tracked colour as luma quads, one launch (pair_images checked that all have the colour camera's size)
   const int cw = color_camera->width, ch = color_camera->height;
   const size_t quad_count = (size_t)(cw + 1) * (ch + 1);
-  if ((rc = ctx->quads_aux.reserve((size_t)pair_count * quad_count * sizeof(uint32_t)))) return rc;
-  for (int p = 0; p < pair_count; ++p) batch.im[p].frame_quads = (const uint32_t*)ctx->quads_aux.ptr + (size_t)p * quad_count;
+  if (!quad_table_addressable(cw, ch)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", cw, ch);
+  if ((rc = ctx->quads_aux.reserve((size_t)pair_count * quad_count * sizeof(QuadEntry)))) return rc;
+  for (int p = 0; p < pair_count; ++p) batch.im[p].frame_quads = (const QuadEntry*)ctx->quads_aux.ptr + (size_t)p * quad_count;
   hipLaunchKernelGGL(build_quads_u8_batched_kernel, dim3((unsigned)((cw + 1 + 255) / 256), (unsigned)(ch + 1), (unsigned)pair_count), dim3(256), 0, stream,
-                     batch, (uint32_t*)ctx->quads_aux.ptr, quad_count);
+                     batch, (QuadEntry*)ctx->quads_aux.ptr, quad_count);
   BSLAM_HIP_TRY(hipGetLastError());
   const int pixels = depth_camera->width * depth_camera->height;
   const int blocks = (pixels + 255) / 256;

@@ -152,19 +152,19 @@ __global__ __launch_bounds__(256) void calibrate_and_downsample_kernel(CamConsts
   out_color.at<uint8_t>(y, x) = sat_u8(255.f * col + 0.5f);
 }
 // luma quads of a u8 image (see KfDev::quads)
-__global__ __launch_bounds__(256) void build_quads_u8_kernel(Img img, uint32_t* __restrict__ quads) {
+__global__ __launch_bounds__(256) void build_quads_u8_kernel(Img img, QuadEntry* __restrict__ quads) {
   const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
   const int w = img.width, h = img.height;
   if (qx > w) return;
   const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
   const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
-  quads[(size_t)qy * (size_t)(w + 1) + qx] = tl | (tr << 8) | (bl << 16) | (br << 24);
+  quads[(size_t)qy * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
 }
 
 struct PairImages {
   Img surfel_depth, surfel_normals, surfel_color;   // base frame: f32 depth, u16 normals, u8 colour (depth intrinsics)
   Img frame_depth, frame_normals;                   // tracked frame: f32 depth, u16 normals
-  const uint32_t* frame_quads;                      // tracked frame colour as luma quads (colour intrinsics)
+  const QuadEntry* frame_quads;                     // tracked frame colour as luma quads (colour intrinsics)
   Img frame_color;                                  // the same image, direct (the gradient-magnitude variant reads it as the reference does)
 };
 
@@ -316,7 +316,7 @@ struct PairBatch {
   M34 T[kMaxPairBatch];
 };
 
-__global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(PairBatch batch, uint32_t* __restrict__ quads, size_t quads_per_pair) {
+__global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(PairBatch batch, QuadEntry* __restrict__ quads, size_t quads_per_pair) {
   const int p = blockIdx.z;
   const Img img = batch.im[p].frame_color;
   const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
@@ -324,7 +324,7 @@ __global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(PairBatch b
   if (qx > w) return;
   const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
   const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
-  quads[(size_t)p * quads_per_pair + (size_t)qy * (size_t)(w + 1) + qx] = tl | (tr << 8) | (bl << 16) | (br << 24);
+  quads[(size_t)p * quads_per_pair + (size_t)qy * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
 }
 
 template <bool kDepth, bool kDesc>

@@ -204,10 +204,7 @@ __device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* 
   if (mine == 0) return;
   auto kf_of = [&](unsigned long long m) { const int place = kf_begin + __builtin_ctzll(m); return kf_list ? kf_list[1 + place] : place; };
   int k_next = kf_of(mine);
-  int my_col;    // the column this lane ends up with in the reduction, and whether it is the lane that stores it
-  bool writer;
   constexpr int kLive = kCost ? kRowCost + 1 : kRowCost;   // 21 H, 6 b (, cost); the count column is filled in below
-  wave_column_sums_owner<kLive, kRedCols>(&my_col, &writer);
   while (mine != 0) {   // uniform
     const int k = k_next;
 #pragma unroll
@@ -272,8 +269,15 @@ __device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* 
     }
 
     // wave reduction (skipped when the whole wave saw nothing for this keyframe), one row per (slot, keyframe)
+    // The tile addresses, the column this lane ends up with in the reduction and whether it is the lane that stores it are formed
+    // here, per row, from the lane number counted afresh (three instructions per eight pairs).  Formed once ahead of the keyframe
+    // loop, the store address and the tile addresses held registers across every pair, which the loop does not have to spare.
+    const uint32_t row_lane = lane_counted();
     float total = 0.f;
-    if (count != 0) total = wave_column_sums_lds<kLive, kRedCols>(acc, red.tile[wave]);
+    if (count != 0) total = wave_column_sums_lds<kLive, kRedCols>(acc, red.tile[wave], row_lane);
+    int my_col;
+    bool writer;
+    wave_column_sums_owner<kLive, kRedCols>(row_lane, &my_col, &writer);
     if (my_col == kRowCount) total = (float)count;
     if (writer) partials[((size_t)k * rows_per_kf + (size_t)slot) * kRow + my_col] = total;
   }

@@ -453,6 +453,17 @@ int bslam_debug_wave_column_sums(bslam_context* ctx, void* stream, int live_colu
  *       w1, w2 of the wave-uniform Huber path, w1, w2 of the per-lane form]  (58 floats).
  * A wave evaluates 64 consecutive points, so the Huber path taken depends on the residuals of a point's group of 64. */
 int bslam_debug_desc_pair(bslam_context* ctx, void* stream, int count, const float* in, float* out);
+/* Test probe of the luma quad table (csrc/device_math.hpp: KfDev::quads).  `images` (HOST) holds image_count tightly packed images
+ * of width x height pixels with `channels` bytes each: 4 = keyframe colour (luma in byte 3, table built by the kernel of the
+ * keyframe calls), 1 = u8 image (table built by the kernels of the odometry calls: the single-pair one for image_count = 1, the
+ * batched one otherwise; image_count <= BSLAM_MAX_PAIR_BATCH).  For each of `count` positions [image index, x, y] (HOST,
+ * pixel-corner coordinates, any finite value) out (HOST, 6 floats per position, valid on return) receives the bilinear sample
+ * and its gradient in byte units, [val, gx, gy], twice: through the table as the kernels sample it, and from four byte loads of
+ * the image with clamp addressing and the differences formed per sample in integers.  `entries` (HOST, image_count x (height + 1)
+ * x (width + 1) x 4 uint16, valid on return) receives the raw table: fp16 bit patterns {tl, tr - tl, bl - tl,
+ * (br - bl) - (tr - tl)} of base texel (i, j) at [image][j + 1][i + 1]. */
+int bslam_debug_quad_samples(bslam_context* ctx, void* stream, int image_count, int width, int height, int channels, const uint8_t* images,
+                             int count, const float* positions, int tex_mode, float* out, uint16_t* entries);
 
 /* ------------------------------------------------------------------------- */
 /* Surfel lifecycle                                          */

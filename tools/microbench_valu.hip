@@ -33,6 +33,23 @@ KERNEL(k_rcp, CHAIN8_1("v_rcp_f32"))
 KERNEL(k_sqrt, CHAIN8_1("v_sqrt_f32"))
 KERNEL(k_cvt, CHAIN8_1("v_cvt_i32_f32"))
 
+// fp16 operands converted on the way in: x = fma(a, (float)half(b), x) with the half taken from either 16 bits of b (op_sel), and
+// the explicit conversions (low half plain, high half through SDWA) -- the luma quad table's sample arithmetic
+#define CHAIN8_MIX(SEL)                                                                                                      \
+  asm volatile("v_fma_mix_f32 %0, %8, %9, %0 " SEL "\nv_fma_mix_f32 %1, %8, %9, %1 " SEL "\nv_fma_mix_f32 %2, %8, %9, %2 " SEL "\n" \
+               "v_fma_mix_f32 %3, %8, %9, %3 " SEL "\nv_fma_mix_f32 %4, %8, %9, %4 " SEL "\nv_fma_mix_f32 %5, %8, %9, %5 " SEL "\n" \
+               "v_fma_mix_f32 %6, %8, %9, %6 " SEL "\nv_fma_mix_f32 %7, %8, %9, %7 " SEL "\n"                                     \
+               : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7) : "v"(a), "v"(b))
+#define CHAIN8_1S(OP, SUFFIX)                                                                              \
+  asm volatile(OP " %0, %0 " SUFFIX "\n" OP " %1, %1 " SUFFIX "\n" OP " %2, %2 " SUFFIX "\n" OP " %3, %3 " SUFFIX "\n" \
+               OP " %4, %4 " SUFFIX "\n" OP " %5, %5 " SUFFIX "\n" OP " %6, %6 " SUFFIX "\n" OP " %7, %7 " SUFFIX "\n" \
+               : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7))
+KERNEL(k_fma_mix_lo, CHAIN8_MIX("op_sel:[0,0,0] op_sel_hi:[0,1,0]"))
+KERNEL(k_fma_mix_hi, CHAIN8_MIX("op_sel:[0,1,0] op_sel_hi:[0,1,0]"))
+KERNEL(k_fma_mix_2h, CHAIN8_MIX("op_sel:[0,1,0] op_sel_hi:[1,1,0]"))   // both multiplicands fp16 (low half of a, high half of b)
+KERNEL(k_cvt_f16, CHAIN8_1("v_cvt_f32_f16"))
+KERNEL(k_cvt_f16_hi, CHAIN8_1S("v_cvt_f32_f16_sdwa", "dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1"))
+
 typedef float float2_t __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_pkfma(float* out, float a, float b) {
   float2_t x0 = {(float)threadIdx.x, 1.f}, x1 = x0 + 1.f, x2 = x0 + 2.f, x3 = x0 + 3.f, x4 = x0 + 4.f, x5 = x0 + 5.f, x6 = x0 + 6.f, x7 = x0 + 7.f;
@@ -89,6 +106,11 @@ int main() {
   run("v_rcp_f32", k_rcp, d_out);
   run("v_sqrt_f32", k_sqrt, d_out);
   run("v_cvt_i32_f32", k_cvt, d_out);
+  run("v_fma_mix lo", k_fma_mix_lo, d_out);
+  run("v_fma_mix hi", k_fma_mix_hi, d_out);
+  run("v_fma_mix 2xh", k_fma_mix_2h, d_out);
+  run("v_cvt_f32_f16", k_cvt_f16, d_out);
+  run("v_cvt_f32_f16 hi", k_cvt_f16_hi, d_out);
   run("v_mov_b32 0", k_mov32, d_out);
   run("v_mov_b64 0", k_mov64, d_out);
   return 0;

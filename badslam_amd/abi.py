@@ -58,6 +58,11 @@ class KeyframeView(C.Structure):
                 ("activation", C.c_int32), ("id", C.c_int32)]
 
 
+class Volume(C.Structure):
+    """bslam_volume: sample (x, y, z) lies at origin + (i + 0.5) * voxel_size per axis."""
+    _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
+
+
 class SE3f(C.Structure):
     _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3)]
 
@@ -111,6 +116,9 @@ SIGNATURES = {
                                         P(Buffer2D)]),
     "bslam_render_surfels": (C.c_int, [C.c_void_p, C.c_void_p, P(Mat3x4), P(Camera4f), C.c_uint32, P(Buffer2D), C.c_float, C.c_float, C.c_float, C.c_float,
                                        P(Buffer2D), P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
+    "bslam_fuse_keyframes": (C.c_int, [C.c_void_p, C.c_void_p, _CAM, _CAM, _DP, C.c_int, _KFS, P(Volume), C.c_float, _BUF, _BUF, _BUF]),
+    "bslam_extract_mesh": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, _BUF, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                     C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "bslam_extract_keyframe_features": (C.c_int, [C.c_void_p, C.c_void_p, P(Buffer2D), P(Buffer2D), C.c_int64, C.c_void_p, C.c_void_p]),
     "bslam_place_pattern": (C.c_int, [P(C.c_int8)]),
     "bslam_match_features": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),

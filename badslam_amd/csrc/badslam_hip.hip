@@ -18,6 +18,7 @@
 #include "preprocess_kernels.hpp"
 #include "rectify_kernels.hpp"
 #include "render_kernels.hpp"
+#include "fusion_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
@@ -1384,6 +1385,7 @@ int bslam_debug_pose_residuals(
 #include "preprocess_abi.inc"
 #include "rectify_abi.inc"
 #include "render_abi.inc"
+#include "fusion_abi.inc"
 #include "place_abi.inc"
 #include "odometry_abi.inc"
 #include "cost_abi.inc"

@@ -73,6 +73,12 @@ def host_lib():
                                    C.POINTER(C.c_double)]
     L.bsh_set_cost_tracking.argtypes = [C.c_void_p, C.c_int]
     L.bsh_cost_history.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]
+    u32p = C.POINTER(C.c_uint32)
+    L.bsh_model_bounds.argtypes = [C.c_void_p, C.c_void_p, f32p]
+    L.bsh_fuse_keyframes.argtypes = [C.c_void_p, C.c_void_p, f32p, C.c_float, C.POINTER(C.c_int), C.c_float]
+    L.bsh_extract_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
+    L.bsh_mesh_copy.argtypes = [f32p, f32p, u8p, u32p]
+    L.bsh_volume.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), f32p, f32p, u32p, u8p]
     _host = L
     return L
 
@@ -255,6 +261,8 @@ def _io_lib():
     L.bsh_tum_camera.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.bsh_tum_frame.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     L.bsh_save_poses.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int, C.c_char_p]
+    L.bsh_save_point_cloud_ply.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
+    L.bsh_save_mesh_ply.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint32)]
     L.bsh_save_calibration_arrays.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.bsh_load_calibration_arrays.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.bsh_save_calibration.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
@@ -312,6 +320,33 @@ def save_poses(timestamp_strings, poses7, start_frame, path):
     arr = (C.c_char_p * n)(*[t.encode() for t in timestamp_strings])
     p = np.ascontiguousarray(poses7, np.float32)
     _io_check(L, L.bsh_save_poses(n, arr, _f(p), start_frame, str(path).encode()))
+
+
+def SavePointCloudAsPLY(path, positions, colors=None, normals=None):
+    """Binary little-endian PLY of a point cloud (BS/io.cc:694): positions (n, 3) f32, colors (n, 3) u8, normals (n, 3) f32 -- the
+    arrays of DirectBA.ExportToPointCloud; colors / normals may be None."""
+    L = _io_lib()
+    pos = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    col = None if colors is None else np.ascontiguousarray(colors, np.uint8).reshape(-1, 3)
+    nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+    if (col is not None and len(col) != len(pos)) or (nrm is not None and len(nrm) != len(pos)):
+        raise ValueError("colors and normals need one row per point")
+    _io_check(L, L.bsh_save_point_cloud_ply(str(path).encode(), len(pos), _f(pos), None if col is None else col.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                            None if nrm is None else _f(nrm)))
+
+
+def SaveMeshAsPLY(path, mesh):
+    """Binary little-endian PLY of a triangle mesh: vertex x y z nx ny nz red green blue, face list uchar int vertex_indices.
+    mesh: the dict of DirectBA.ExtractMesh -- positions (V, 3) f32, normals (V, 3) f32, colors (V, 4) u8, triangles (T, 3) u32."""
+    L = _io_lib()
+    pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+    nrm = np.ascontiguousarray(mesh["normals"], np.float32).reshape(-1, 3)
+    col = np.ascontiguousarray(mesh["colors"], np.uint8).reshape(-1, 4)
+    tri = np.ascontiguousarray(mesh["triangles"], np.uint32).reshape(-1, 3)
+    if len(nrm) != len(pos) or len(col) != len(pos):
+        raise ValueError("normals and colors need one row per vertex")
+    _io_check(L, L.bsh_save_mesh_ply(str(path).encode(), len(pos), _f(pos), _f(nrm), col.ctypes.data_as(C.POINTER(C.c_uint8)), len(tri),
+                                     tri.ctypes.data_as(C.POINTER(C.c_uint32))))
 
 
 def save_calibration_arrays(base, depth4, color4, a, cfactor):
@@ -606,6 +641,45 @@ class DirectBA:
                                             ptr("depth", C.c_uint16), ptr("index", C.c_uint32), ptr("color", C.c_uint8), ptr("normal", C.c_float),
                                             _f(out["camera_T_global"])))
         return out
+
+    # --- volumetric fusion and meshing (bslam_fuse_keyframes, bslam_extract_mesh)
+    def ModelBounds(self):
+        """(min (3,), max (3,)) float32 of the valid surfels, or None when there is none."""
+        b = np.zeros(6, np.float32)
+        rc = self.L.bsh_model_bounds(self._ba, self.stream, _f(b))
+        self._check(min(rc, 0))
+        return (b[:3].copy(), b[3:].copy()) if rc == 1 else None
+
+    def FuseKeyframes(self, origin, voxel_size, dims, truncation):
+        """Fuses all keyframes that are not deleted, at their current poses and with the current depth calibration, into a
+        truncated signed distance volume of dims = (nx, ny, nz) samples; sample (x, y, z) lies at origin + (i + 0.5) * voxel_size.
+        A full rebuild: call it after bundle adjustment.  At most 2^30 samples."""
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        d = (C.c_int * 3)(*[int(v) for v in dims])
+        self._check(self.L.bsh_fuse_keyframes(self._ba, self.stream, _f(o), float(voxel_size), d, float(truncation)))
+
+    def ExtractMesh(self, min_count=1):
+        """Surface nets of the fused volume over the samples seen by at least min_count keyframes: dict of positions (V, 3) f32,
+        normals (V, 3) f32 (towards free space), colors (V, 4) u8, triangles (T, 3) u32 (counter-clockwise seen from free space)."""
+        counts = (C.c_uint64 * 2)()
+        self._check(self.L.bsh_extract_mesh(self._ba, self.stream, int(min_count), counts))
+        V, T = int(counts[0]), int(counts[1])
+        out = dict(positions=np.zeros((V, 3), np.float32), normals=np.zeros((V, 3), np.float32), colors=np.zeros((V, 4), np.uint8),
+                   triangles=np.zeros((T, 3), np.uint32))
+        self._check(self.L.bsh_mesh_copy(_f(out["positions"]), _f(out["normals"]), out["colors"].ctypes.data_as(C.POINTER(C.c_uint8)),
+                                         out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32))))
+        return out
+
+    def Volume(self):
+        """Download of the fused volume: dict of origin (3,), voxel_size, truncation, dims (nx, ny, nz) and the arrays tsdf f32,
+        count u32 of shape (nz, ny, nx) and color u8 (nz, ny, nx, 4)."""
+        dims, fl = (C.c_int * 3)(), np.zeros(5, np.float32)
+        self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), None, None, None))
+        nx, ny, nz = dims[0], dims[1], dims[2]
+        tsdf, count, color = np.zeros((nz, ny, nx), np.float32), np.zeros((nz, ny, nx), np.uint32), np.zeros((nz, ny, nx, 4), np.uint8)
+        self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), _f(tsdf), count.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                      color.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return dict(origin=fl[:3].copy(), voxel_size=float(fl[3]), truncation=float(fl[4]), dims=(nx, ny, nz), tsdf=tsdf, count=count, color=color)
 
     def upload_keyframe_depth(self, kf_id, depth):
         d = np.ascontiguousarray(depth, np.uint16)

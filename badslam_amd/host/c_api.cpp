@@ -189,6 +189,63 @@ int bsh_render_model(void* ba, void* stream, const float* global_T_camera_pose7,
     if (camera_T_global) std::memcpy(camera_T_global, v.camera_T_global.m, sizeof(v.camera_T_global.m));
   });
 }
+// DirectBA::ModelBounds.  bounds6: min x y z, max x y z; returns 1 when there is a valid surfel, 0 when none, -1 on error.
+int bsh_model_bounds(void* ba, void* stream, float* bounds6) {
+  try { return static_cast<DirectBA*>(ba)->ModelBounds(static_cast<hipStream_t>(stream), bounds6, bounds6 + 3) ? 1 : 0; }
+  catch (const std::exception& e) { g_err = e.what(); return -1; }
+}
+// DirectBA::FuseKeyframes.  origin3: x y z of the volume's corner; dims3: nx ny nz.
+int bsh_fuse_keyframes(void* ba, void* stream, const float* origin3, float voxel_size, const int* dims3, float truncation) {
+  BSH_TRY({
+    DirectBA::VolumeSpec spec;
+    std::memcpy(spec.origin, origin3, sizeof(spec.origin));
+    spec.voxel_size = voxel_size;
+    spec.nx = dims3[0]; spec.ny = dims3[1]; spec.nz = dims3[2];
+    static_cast<DirectBA*>(ba)->FuseKeyframes(static_cast<hipStream_t>(stream), spec, truncation);
+  });
+}
+// DirectBA::ExtractMesh in two steps: bsh_extract_mesh extracts, keeps the mesh for this thread and reports counts2 = {vertices,
+// triangles}; bsh_mesh_copy copies it out (positions, normals: 3 floats per vertex; colors: 4 bytes per vertex; indices: 3 per
+// triangle) and drops it.
+static thread_local DirectBA::Mesh g_mesh;
+int bsh_extract_mesh(void* ba, void* stream, uint32_t min_count, uint64_t* counts2) {
+  BSH_TRY({
+    static_cast<DirectBA*>(ba)->ExtractMesh(static_cast<hipStream_t>(stream), min_count, &g_mesh);
+    counts2[0] = g_mesh.vertex_count();
+    counts2[1] = g_mesh.triangle_count();
+  });
+}
+int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
+  BSH_TRY({
+    if (positions) std::memcpy(positions, g_mesh.positions.data(), g_mesh.positions.size() * sizeof(float));
+    if (normals) std::memcpy(normals, g_mesh.normals.data(), g_mesh.normals.size() * sizeof(float));
+    if (colors) std::memcpy(colors, g_mesh.colors.data(), g_mesh.colors.size() * sizeof(uchar4_t));
+    if (indices) std::memcpy(indices, g_mesh.indices.data(), g_mesh.indices.size() * sizeof(uint32_t));
+    g_mesh = DirectBA::Mesh();
+  });
+}
+// DirectBA::Volume.  With tsdf == null only the description is returned: dims3 = nx ny nz, floats5 = origin x y z, voxel size,
+// truncation; else the three arrays of nx * ny * nz elements (colour: 4 bytes each) are filled as well.
+int bsh_volume(void* ba, void* stream, int* dims3, float* floats5, float* tsdf, uint32_t* count, uint8_t* color) {
+  BSH_TRY({
+    DirectBA::VolumeData v;
+    static_cast<DirectBA*>(ba)->Volume(static_cast<hipStream_t>(stream), &v);
+    dims3[0] = v.spec.nx; dims3[1] = v.spec.ny; dims3[2] = v.spec.nz;
+    std::memcpy(floats5, v.spec.origin, 12);
+    floats5[3] = v.spec.voxel_size; floats5[4] = v.truncation;
+    if (tsdf) std::memcpy(tsdf, v.tsdf.data(), v.tsdf.size() * sizeof(float));
+    if (count) std::memcpy(count, v.count.data(), v.count.size() * sizeof(uint32_t));
+    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
+  });
+}
+int bsh_save_point_cloud_ply(const char* path, uint64_t count, const float* positions, const uint8_t* colors_rgb, const float* normals) {
+  BSH_TRY(if (!SavePointCloudAsPLY(path, count, positions, colors_rgb, normals)) throw std::runtime_error(std::string("cannot write ") + path));
+}
+int bsh_save_mesh_ply(const char* path, uint64_t vertex_count, const float* positions, const float* normals, const uint8_t* colors_rgba, uint64_t triangle_count,
+                      const uint32_t* indices) {
+  BSH_TRY(if (!SaveMeshAsPLY(path, vertex_count, positions, normals, colors_rgba, triangle_count, indices))
+            throw std::runtime_error(std::string("cannot write ") + path + " (or an index is out of range)"));
+}
 int bsh_set_scheme_end_tasks(void* ba, int enable) { BSH_TRY(static_cast<DirectBA*>(ba)->SetSchemeEndTasks(enable != 0)); }
 int bsh_create_surfels_for_keyframe(void* ba, void* stream, int filter_new_surfels, int keyframe_id) {
   BSH_TRY({

@@ -6,6 +6,7 @@
 
 #include <chrono>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <limits>
@@ -472,6 +473,96 @@ void DirectBA::RenderModel(hipStream_t stream, const SE3f& global_T_camera, cons
   if (options.index) { views->index.resize(pixels); render_index_->Download(stream, views->index.data(), static_cast<size_t>(w) * sizeof(u32)); }
   if (options.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), static_cast<size_t>(w) * sizeof(uchar4_t)); }
   if (options.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), static_cast<size_t>(w) * 3 * sizeof(float)); }
+}
+
+static bslam_volume VolumePod(const DirectBA::VolumeSpec& spec) {
+  bslam_volume v;
+  std::memcpy(v.origin, spec.origin, sizeof(v.origin));
+  v.voxel_size = spec.voxel_size;
+  v.nx = spec.nx; v.ny = spec.ny; v.nz = spec.nz;
+  return v;
+}
+
+void DirectBA::FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation) {
+  if (spec.nx < 2 || spec.ny < 2 || spec.nz < 2 || static_cast<int64_t>(spec.nx) * spec.ny * spec.nz > (int64_t{1} << 30)) {
+    char msg[256];
+    std::snprintf(msg, sizeof(msg), "FuseKeyframes: a volume of %d x %d x %d voxels at voxel size %g m is outside 2 per axis ... 2^30 in all", spec.nx, spec.ny,
+                  spec.nz, static_cast<double>(spec.voxel_size));
+    throw std::invalid_argument(msg);
+  }
+  const int rows = spec.nz * spec.ny;
+  if (!volume_tsdf_ || volume_tsdf_->height() != rows || volume_tsdf_->width() != spec.nx) {
+    volume_tsdf_.reset(); volume_count_.reset(); volume_color_.reset();   // the old volume goes before the new one is allocated
+    volume_spec_ = VolumeSpec();
+    volume_tsdf_.reset(new DeviceBuffer<float>(rows, spec.nx));
+    volume_count_.reset(new DeviceBuffer<u32>(rows, spec.nx));
+    volume_color_.reset(new DeviceBuffer<uchar4_t>(rows, spec.nx));
+  }
+  const std::vector<bslam_keyframe_view> views = KeyframeViews();
+  const bslam_camera4f color_cam = color_camera_.pod(), depth_cam = depth_camera_.pod();
+  const bslam_depth_params dp = depth_params();
+  const bslam_volume vol = VolumePod(spec);
+  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
+  volume_spec_ = VolumeSpec();   // no volume until the call has gone through
+  Check(bslam_fuse_keyframes(ctx_, stream, &color_cam, &depth_cam, &dp, static_cast<int>(views.size()), views.data(), &vol, truncation, &tsdf, &count, &color),
+        "bslam_fuse_keyframes");
+  volume_spec_ = spec;
+  volume_truncation_ = truncation;
+}
+
+void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) {
+  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("ExtractMesh: no fused volume (call FuseKeyframes first)");
+  const bslam_volume vol = VolumePod(volume_spec_);
+  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
+  u32 vertices = 0, triangles = 0;
+  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, min_count, 0, 0, nullptr, nullptr, nullptr, nullptr, &vertices, &triangles),
+        "bslam_extract_mesh");
+  mesh->positions.assign(3 * static_cast<size_t>(vertices), 0.f);
+  mesh->normals.assign(3 * static_cast<size_t>(vertices), 0.f);
+  mesh->colors.assign(vertices, uchar4_t{0, 0, 0, 0});
+  mesh->indices.assign(3 * static_cast<size_t>(triangles), 0u);
+  if (vertices == 0) return;
+  // one-row device images; three floats per vertex do not fit an int width beyond 2^31 / 3 vertices, far above the 2^30 cells
+  DeviceBuffer<float> positions(1, static_cast<int>(3 * vertices)), normals(1, static_cast<int>(3 * vertices));
+  DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
+  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1)));
+  u32 v2 = 0, t2 = 0;
+  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, min_count, vertices, triangles, positions.address(), normals.address(), colors.address(),
+                           indices.address(), &v2, &t2),
+        "bslam_extract_mesh");
+  if (v2 != vertices || t2 != triangles) throw std::runtime_error("ExtractMesh: the volume changed between the two extraction calls");
+  positions.Download(stream, mesh->positions.data(), mesh->positions.size() * sizeof(float));
+  normals.Download(stream, mesh->normals.data(), mesh->normals.size() * sizeof(float));
+  colors.Download(stream, mesh->colors.data(), mesh->colors.size() * sizeof(uchar4_t));
+  if (triangles) indices.Download(stream, mesh->indices.data(), mesh->indices.size() * sizeof(u32));
+}
+
+void DirectBA::Volume(hipStream_t stream, VolumeData* volume) const {
+  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("Volume: no fused volume (call FuseKeyframes first)");
+  volume->spec = volume_spec_;
+  volume->truncation = volume_truncation_;
+  const size_t n = static_cast<size_t>(volume_spec_.nx) * volume_spec_.ny * volume_spec_.nz, nx = volume_spec_.nx;
+  volume->tsdf.resize(n); volume->count.resize(n); volume->color.resize(n);
+  volume_tsdf_->Download(stream, volume->tsdf.data(), nx * sizeof(float));
+  volume_count_->Download(stream, volume->count.data(), nx * sizeof(u32));
+  volume_color_->Download(stream, volume->color.data(), nx * sizeof(uchar4_t));
+}
+
+bool DirectBA::ModelBounds(hipStream_t stream, float min[3], float max[3]) const {
+  const size_t n = surfels_size_;
+  std::vector<float> rows(3 * std::max<size_t>(n, 1));   // rows 0..2: x, y, z
+  if (n) GetSurfels(stream, rows.data(), n * sizeof(float), 3);
+  bool any = false;
+  for (size_t i = 0; i < n; ++i) {
+    if (std::isnan(rows[i])) continue;   // deleted surfels carry NaN in x
+    for (int d = 0; d < 3; ++d) {
+      const float v = rows[d * n + i];
+      min[d] = any ? std::min(min[d], v) : v;
+      max[d] = any ? std::max(max[d], v) : v;
+    }
+    any = true;
+  }
+  return any;
 }
 
 void DirectBA::ComputeCost(hipStream_t stream, bool active_surfels_only, CostReport* report) {

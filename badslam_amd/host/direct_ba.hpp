@@ -222,6 +222,36 @@ class DirectBA {
   };
   void RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views);
 
+  // Volumetric fusion and meshing (bslam_fuse_keyframes, bslam_extract_mesh; the reference ends at the point cloud).  The
+  // volume is fused from scratch from all keyframes that are not deleted, at their current poses and with the object's
+  // cameras and depth parameters -- call it after bundle adjustment.  The device volume is kept by the object and re-used
+  // while its dimensions stay the same; an object that never calls these allocates and launches nothing for them.
+  // Keyframes are replicated on a surfel-sharded object, so every rank fuses the same volume and nothing is exchanged.
+  struct VolumeSpec {
+    float origin[3] = {0.f, 0.f, 0.f};   // sample (x, y, z) lies at origin + (i + 0.5) * voxel_size per axis
+    float voxel_size = 0.01f;
+    int nx = 0, ny = 0, nz = 0;
+  };
+  struct VolumeData {   // host copy of the fused volume, element (z * ny + y) * nx + x
+    VolumeSpec spec;
+    float truncation = 0.f;
+    std::vector<float> tsdf;
+    std::vector<u32> count;
+    std::vector<uchar4_t> color;
+  };
+  struct Mesh {
+    std::vector<float> positions, normals;   // 3 per vertex
+    std::vector<uchar4_t> colors;            // 1 per vertex
+    std::vector<u32> indices;                // 3 per triangle, counter-clockwise seen from free space
+    size_t vertex_count() const { return positions.size() / 3; }
+    size_t triangle_count() const { return indices.size() / 3; }
+  };
+  void FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation);
+  void ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh);   // of the volume of the last FuseKeyframes
+  void Volume(hipStream_t stream, VolumeData* volume) const;         // download of that volume
+  // Axis-aligned box of the valid (non-NaN) surfels; false when there is none.
+  bool ModelBounds(hipStream_t stream, float min[3], float max[3]) const;
+
   // Place recognition (host/place_recognition.hpp; the methods are defined in place_recognition.cpp).  The database of
   // keyframe features is created by the first of these calls; an object that never calls them allocates and launches
   // nothing for it.
@@ -376,6 +406,12 @@ class DirectBA {
   std::unique_ptr<DeviceBuffer<uchar4_t>> render_color_;
   std::unique_ptr<DeviceBuffer<float>> render_normal_;   // 3 floats per pixel
   std::unique_ptr<PlaceRecognizer> place_recognizer_;   // null until place recognition is used
+  // device volume of FuseKeyframes: nz * ny rows of nx elements each; null until fusion is used
+  std::unique_ptr<DeviceBuffer<float>> volume_tsdf_;
+  std::unique_ptr<DeviceBuffer<u32>> volume_count_;
+  std::unique_ptr<DeviceBuffer<uchar4_t>> volume_color_;
+  VolumeSpec volume_spec_;
+  float volume_truncation_ = 0.f;
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

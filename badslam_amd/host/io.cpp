@@ -511,4 +511,62 @@ bool LoadState(const std::string& path, StateV1* s, std::string* error) {
   return true;
 }
 
+// ------------------------------------------------------------------------------------------------
+// PLY exports
+// ------------------------------------------------------------------------------------------------
+namespace {
+void AppendLE32(std::string* out, const void* value) {   // a 4-byte value in little-endian order, whatever the host's
+  uint32_t v;
+  std::memcpy(&v, value, 4);
+  const char b[4] = {static_cast<char>(v & 0xff), static_cast<char>((v >> 8) & 0xff), static_cast<char>((v >> 16) & 0xff), static_cast<char>(v >> 24)};
+  out->append(b, 4);
+}
+bool WriteWhole(const std::string& path, const std::string& header, const std::string& body) {
+  FILE* file = std::fopen(path.c_str(), "wb");
+  if (!file) return false;
+  bool ok = std::fwrite(header.data(), 1, header.size(), file) == header.size();
+  ok = ok && std::fwrite(body.data(), 1, body.size(), file) == body.size();
+  return (std::fclose(file) == 0) && ok;
+}
+}  // namespace
+
+bool SavePointCloudAsPLY(const std::string& path, size_t count, const float* positions, const uint8_t* colors_rgb, const float* normals) {
+  if (count && !positions) return false;
+  std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(count) + "\nproperty float x\nproperty float y\nproperty float z\n";
+  if (colors_rgb) header += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+  if (normals) header += "property float nx\nproperty float ny\nproperty float nz\n";
+  header += "end_header\n";
+  std::string body;
+  body.reserve(count * 27);
+  for (size_t i = 0; i < count; ++i) {
+    for (int d = 0; d < 3; ++d) AppendLE32(&body, positions + 3 * i + d);
+    if (colors_rgb) body.append(reinterpret_cast<const char*>(colors_rgb + 3 * i), 3);
+    if (normals) for (int d = 0; d < 3; ++d) AppendLE32(&body, normals + 3 * i + d);
+  }
+  return WriteWhole(path, header, body);
+}
+
+bool SaveMeshAsPLY(const std::string& path, size_t vertex_count, const float* positions, const float* normals, const uint8_t* colors_rgba,
+                   size_t triangle_count, const uint32_t* indices) {
+  if ((vertex_count && (!positions || !normals || !colors_rgba)) || (triangle_count && !indices)) return false;
+  for (size_t i = 0; i < 3 * triangle_count; ++i)
+    if (indices[i] >= vertex_count || indices[i] > 0x7fffffffu) return false;   // "int" indices
+  const std::string header = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(vertex_count) +
+                             "\nproperty float x\nproperty float y\nproperty float z\nproperty float nx\nproperty float ny\nproperty float nz\n"
+                             "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face " + std::to_string(triangle_count) +
+                             "\nproperty list uchar int vertex_indices\nend_header\n";
+  std::string body;
+  body.reserve(vertex_count * 27 + triangle_count * 13);
+  for (size_t i = 0; i < vertex_count; ++i) {
+    for (int d = 0; d < 3; ++d) AppendLE32(&body, positions + 3 * i + d);
+    for (int d = 0; d < 3; ++d) AppendLE32(&body, normals + 3 * i + d);
+    body.append(reinterpret_cast<const char*>(colors_rgba + 4 * i), 3);
+  }
+  for (size_t t = 0; t < triangle_count; ++t) {
+    body.push_back(static_cast<char>(3));
+    for (int d = 0; d < 3; ++d) AppendLE32(&body, indices + 3 * t + d);
+  }
+  return WriteWhole(path, header, body);
+}
+
 }  // namespace bslam_host

@@ -50,6 +50,15 @@ bool SaveCalibration(const std::string& base_path, const float depth_camera[4], 
 bool LoadCalibration(const std::string& base_path, float depth_camera[4], float color_camera[4], float* a, int cfactor_width, int cfactor_height,
                      float* cfactor_row_major);
 
+// ---- PLY exports, binary little-endian ----
+// SavePointCloudAsPLY (BS/io.cc:694, LV/point_cloud.h:491-660): per vertex x y z (float), red green blue (uchar), nx ny nz
+// (float) -- the arrays of DirectBA::ExportToPointCloud.  colors / normals may be null: their properties are left out.
+bool SavePointCloudAsPLY(const std::string& path, size_t count, const float* positions, const uint8_t* colors_rgb, const float* normals);
+// Triangle mesh of DirectBA::ExtractMesh: per vertex x y z nx ny nz (float), red green blue (uchar; colors_rgba has 4 bytes per
+// vertex, alpha is not written); per face "list uchar int vertex_indices" with 3 indices.
+bool SaveMeshAsPLY(const std::string& path, size_t vertex_count, const float* positions, const float* normals, const uint8_t* colors_rgba,
+                   size_t triangle_count, const uint32_t* indices);
+
 // ---- state file v1 (BS/io.cc:38-536, config block BS/bad_slam_config.cc:28-200) ----
 // The file holds the SLAM configuration, the per-frame poses of the video, the cameras, the depth deformation, the
 // keyframe list (metadata only: keyframe images are re-created from the dataset on load) and rows 0-7 of the

@@ -597,6 +597,66 @@ int bslam_render_surfels(bslam_context* ctx, void* stream, const bslam_mat3x4* c
                          float radius_scale, float metres_to_depth, const bslam_buffer2d* out_depth,
                          const bslam_buffer2d* out_index, const bslam_buffer2d* out_color, const bslam_buffer2d* out_normal);
 
+/* Volumetric fusion (the reference ends at the surfel point cloud, BS/io.cc:694, and leaves meshing to other tools): the
+ * calibrated depth of every keyframe is averaged into a truncated signed distance volume, from scratch -- bundle
+ * adjustment moves all poses, so there is no incremental mode.  Sample (x, y, z) of the volume, 0 <= x < nx and alike,
+ * lies at  origin + (float(i) + 0.5f) * voxel_size  per axis (a multiply, then an add).  All arithmetic is fp32 in a
+ * fixed expression order (csrc/fusion_kernels.hpp, DESIGN.md 8 "Volumetric fusion"); two calls give identical bits. */
+typedef struct bslam_volume {
+  float origin[3];
+  float voxel_size;
+  int32_t nx, ny, nz;
+} bslam_volume;
+
+/* Per sample, the keyframes in list order (`activation` is not looked at, as in bslam_assign_colors):
+ *   the centre is projected exactly like a surfel (same transform, reciprocal, rounding and bounds test); outside the
+ *   depth image or behind the camera: no observation
+ *   d = calibrated depth of that pixel (the derived records; bslam_set_keyframe_cache applies); d == 0: no observation
+ *   sdf = d - local.z;  sdf < -truncation: no observation (occluded);  else  S += fminf(sdf, truncation), n += 1
+ *   colour, only when `color` is given and sdf <= truncation: the uchar4 pixel nearest to the projection of the centre
+ *   with color_camera (truncated coordinates), if inside the colour image: r, g, b added to integer sums, nc += 1
+ * Outputs, 2-D buffers of nz * ny rows of nx 4-byte elements, row = z * ny + y, rows 4 byte aligned, pitches may exceed
+ * the content and padding is never written; every sample of every given output is written:
+ *   tsdf   f32     n ? S / float(n) : truncation       (metres, not normalised)
+ *   count  u32     n
+ *   color  uchar4  nc ? {(sum + nc / 2) / nc per channel, 255} : {0, 0, 0, 0};  may be null (color_camera too, then)
+ * Refused: null arguments, voxel_size or truncation not finite and > 0, a dimension < 2, nx * ny * nz > 2^30, pitches
+ * too small or misaligned, outputs that overlap, and what the keyframe list checks of the other calls refuse.
+ * keyframe_count == 0 is legal: count 0, tsdf = truncation everywhere.
+ * A workgroup owns a brick of 8 x 8 x 4 samples and skips the keyframes whose frustum its box cannot reach
+ * (bslam_set_culling; counted in bslam_debug_cull_stats as (brick, keyframe) pairs while profiling is on); the outputs
+ * are the same bits either way.  Launched on `stream` without synchronisation.  Keyframes are replicated in a
+ * surfel-sharded run: every rank computes the same volume, nothing is exchanged. */
+int bslam_fuse_keyframes(bslam_context* ctx, void* stream, const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
+                         const bslam_depth_params* depth_params, int keyframe_count, const bslam_keyframe_view* keyframes,
+                         const bslam_volume* volume, float truncation, const bslam_buffer2d* tsdf,
+                         const bslam_buffer2d* count, const bslam_buffer2d* color);
+
+/* Triangle mesh of a fused volume by naive surface nets.  A sample is observed iff count >= min_count (>= 1) and inside
+ * iff tsdf < 0.  Cell (x, y, z), 0 <= x < nx - 1 and alike, has the samples (x + dx, y + dy, z + dz) as corners, is active
+ * iff all eight are observed and not all on one side, and has the linear index (z (ny - 1) + y)(nx - 1) + x.
+ * Vertices: one per active cell, id = the cell's rank among the active cells in linear order.  Over the cell's edges
+ * a -> b = a + axis whose ends lie on different sides (the four x-edges at (dy, dz) = (0,0), (1,0), (0,1), (1,1), then the
+ * y-edges at (dx, dz) and the z-edges at (dx, dy) in the same pattern):  t = Da / (Da - Db), the corner offset of a with t
+ * in place of the axis component is added to a running sum;  mean = sum / float(edges);
+ *   position = origin + ((float(x) + 0.5f) + mean.x) * voxel_size                              per component
+ *   normal   = g / sqrtf((g.x g.x + g.y g.y) + g.z g.z) with g.axis = the sum of Db - Da over the four edges of the
+ *              axis in the order above; 0 where the root is 0.  Points towards free space.
+ *   colour   = {(sum + k / 2) / k per channel, 255} over the k corners whose colour sample has alpha 255; 0 for k = 0
+ * Faces: an active cell owns the grid edges from its minimum corner a along +x, +y, +z.  Such an edge gives a quad iff
+ * the sides of its ends differ and the four cells around it are active; for +x these are q0 .. q3 = (x, y-1, z-1),
+ * (x, y, z-1), (x, y, z), (x, y-1, z), for +y and +z the same with (z, x) and (x, y) in the places of (y, z).  Triangles
+ * (q0, q1, q2), (q0, q2, q3) if a is inside, else of the reversed quad (q3, q2, q1, q0): counter-clockwise seen from free
+ * space.  Faces are ordered by (linear cell index, axis).
+ * Device outputs: positions float[3 V], normals float[3 V] (may be null), colors uchar4[V] (may be null; written only
+ * when a colour volume is given), indices uint32[3 T]; *vertex_count = V and *triangle_count = T on the host.  When
+ * positions or indices is null, or V > vertex_capacity or T > triangle_capacity, only the counts are returned and
+ * nothing is written: call once for the counts and once with buffers.  Synchronises `stream`. */
+int bslam_extract_mesh(bslam_context* ctx, void* stream, const bslam_volume* volume, const bslam_buffer2d* tsdf,
+                       const bslam_buffer2d* count, const bslam_buffer2d* color, uint32_t min_count, uint32_t vertex_capacity,
+                       uint32_t triangle_capacity, float* positions, float* normals, void* colors, uint32_t* indices,
+                       uint32_t* vertex_count, uint32_t* triangle_count);
+
 /* Place recognition (in place of the FAST + BRIEF + DBoW2 half of vis::LoopDetector::AddImage, BS/loop_detector.cc:98-127,
  * 160-167): one Harris corner with an unoriented 256-bit BRIEF descriptor per cell of 16 x 16 pixels of a keyframe.  All
  * arithmetic is integer (csrc/place_kernels.hpp, DESIGN.md 8 "Place recognition"); two calls give identical bits.

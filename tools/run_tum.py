@@ -8,6 +8,7 @@ has a ground truth, prints the ATE RMSE.
                             [--pyramid-level-for-depth L] [--pyramid-level-for-color L]
                             [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
                             [--place-recognition] [--place-min-gap N]
+                            [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--point-cloud PATH]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -26,6 +27,13 @@ the dataset reader loads back: depth/<timestamp>.png (16-bit, the units of the i
 calibration.txt and groundtruth.txt (the keyframe poses the views were rendered from).  --render-radius-scale S: the discs are
 drawn with S times the surfels' radii; the default is the sparse surfel cell size of the run (4), because a surfel stands for a
 cell of that many pixels a side while its radius is that of one pixel, so that scale closes the gaps between neighbours.
+
+--mesh PATH: after the last BA, all keyframes are fused into a truncated signed distance volume at their optimised poses
+(DirectBA.FuseKeyframes) over the box of the surfel model (DirectBA.ModelBounds) padded by the truncation, and its surface
+(DirectBA.ExtractMesh, surface nets) is written as a binary PLY with normals and colours.  --mesh-voxel-size M: metres, default
+0.01; --mesh-truncation M: metres, default 4 voxels; --mesh-min-count N: a sample takes part when N keyframes saw it, default 1.
+A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
+(DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 """
 import argparse
 import os
@@ -88,10 +96,40 @@ def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0):
     return written
 
 
+MAX_VOXELS = 1 << 30
+
+
+def mesh_volume(bounds_min, bounds_max, voxel_size, truncation):
+    """The volume over the box [bounds_min, bounds_max] padded by the truncation: (origin (3,) float32, (nx, ny, nz)); every
+    dimension at least 2.  Raises ValueError, naming the voxel size, beyond 2^30 samples."""
+    if not (voxel_size > 0 and truncation > 0):
+        raise ValueError("--mesh-voxel-size and --mesh-truncation must be positive")
+    lo = np.asarray(bounds_min, np.float64) - truncation
+    hi = np.asarray(bounds_max, np.float64) + truncation
+    dims = tuple(max(2, int(np.ceil((hi[i] - lo[i]) / voxel_size))) for i in range(3))
+    if dims[0] * dims[1] * dims[2] > MAX_VOXELS:
+        raise ValueError(f"a volume of {dims[0]} x {dims[1]} x {dims[2]} samples at --mesh-voxel-size {voxel_size:g} m exceeds 2^30: "
+                         f"use a voxel size of at least {voxel_size * (dims[0] * dims[1] * dims[2] / MAX_VOXELS) ** (1 / 3) * 1.01:.3g} m")
+    return lo.astype(np.float32), dims
+
+
+def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1):
+    """FuseKeyframes over the padded ModelBounds, ExtractMesh, SaveMeshAsPLY -> (mesh dict, origin, dims)."""
+    truncation = 4 * voxel_size if truncation is None else truncation
+    bounds = ba.ModelBounds()
+    if bounds is None:
+        raise ValueError("--mesh: the model has no surfels to take the volume's bounds from")
+    origin, dims = mesh_volume(bounds[0], bounds[1], voxel_size, truncation)
+    ba.FuseKeyframes(origin, voxel_size, dims, truncation)
+    mesh = ba.ExtractMesh(min_count)
+    dba.SaveMeshAsPLY(path, mesh)
+    return mesh, origin, dims
+
+
 def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterations=10, max_depth=3.0, end_frame=None, raw_to_float_depth=1.0 / 5000,
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
-        place_recognition=False, place_min_gap=10):
+        place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -129,6 +167,13 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if render_dir:
         result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, float(render_radius_scale or cell))
         result["render_dir"] = str(render_dir)
+    if point_cloud:
+        positions, colors, normals = slam.ba().ExportToPointCloud()
+        dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
+        result["point_cloud"] = (str(point_cloud), len(positions))
+    if mesh:
+        m, origin, dims = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count)
+        result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
     if inspect:
         inspect(slam, result)
     if trajectory:
@@ -154,6 +199,11 @@ def arg_parser():
     ap.add_argument("--render-radius-scale", type=float, default=None)
     ap.add_argument("--place-recognition", action="store_true")
     ap.add_argument("--place-min-gap", type=int, default=10)
+    ap.add_argument("--mesh", default=None)
+    ap.add_argument("--mesh-voxel-size", type=float, default=0.01)
+    ap.add_argument("--mesh-truncation", type=float, default=None)
+    ap.add_argument("--mesh-min-count", type=int, default=1)
+    ap.add_argument("--point-cloud", default=None)
     return ap
 
 
@@ -162,7 +212,8 @@ def main():
     r = run(a.dataset_dir, a.trajectory, a.out, a.keyframe_interval, a.ba_iterations, a.max_depth, a.end_frame, ba_cost=a.ba_cost,
             pyramid_level_for_depth=a.pyramid_level_for_depth, pyramid_level_for_color=a.pyramid_level_for_color,
             median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
-            render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap)
+            render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap, mesh=a.mesh,
+            mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -172,6 +223,10 @@ def main():
                   f"{e['status'] if e['loop_attempted'] else 'no start pose'}")
     if "rendered" in r:
         print(f"{len(r['rendered'])} model views -> {r['render_dir']}")
+    if "point_cloud" in r:
+        print(f"{r['point_cloud'][1]} points -> {r['point_cloud'][0]}")
+    if "mesh" in r:
+        print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples -> {r['mesh']['path']}")
     if "ate" in r:
         print(f"ATE RMSE {r['ate']['rmse']:.6f} m over {r['ate']['pairs']} poses")
 

@@ -122,22 +122,29 @@ static int check_keyframe_images(const bslam_keyframe_view& v, const bslam_camer
 // Row r of a surfel buffer.
 static float* surfel_row(const bslam_buffer2d* s, int r) { return (float*)((uint8_t*)s->address + (size_t)r * s->pitch); }
 
-static SurfelRows surfel_rows(const bslam_buffer2d* s, uint32_t size) {
-  SurfelRows o;
-  o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
-  o.normal = (const uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
-  o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
-  o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
-  o.size = size;
-  return o;
-}
-
-static SurfelRowsRW surfel_rows_rw(const bslam_buffer2d* s, const bslam_buffer2d* active, uint32_t size) {
-  SurfelRowsRW o;
+// The one mapping from a surfel buffer to its row pointers; the kernels' row structs below are views of it.
+static SurfelRowsAll surfel_rows_all(const bslam_buffer2d* s) {
+  SurfelRowsAll o;
   o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
   o.normal = (uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
   o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
+  o.color = (uint32_t*)surfel_row(s, BSLAM_SURFEL_COLOR);
   o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
+  return o;
+}
+
+static SurfelRows surfel_rows(const bslam_buffer2d* s, uint32_t size) {
+  const SurfelRowsAll a = surfel_rows_all(s);
+  return SurfelRows{a.x, a.y, a.z, a.normal, a.radius_squared, a.d1, a.d2, size};
+}
+
+static SurfelRowsRW surfel_rows_rw(const bslam_buffer2d* s, const bslam_buffer2d* active, uint32_t size) {
+  const SurfelRowsAll a = surfel_rows_all(s);
+  SurfelRowsRW o;
+  o.x = a.x; o.y = a.y; o.z = a.z;
+  o.normal = a.normal;
+  o.radius_squared = a.radius_squared;
+  o.d1 = a.d1; o.d2 = a.d2;
   o.active = active ? (uint8_t*)active->address : nullptr;
   o.size = size;
   o.perm = nullptr;
@@ -226,6 +233,24 @@ static int upload_kf_table(bslam_context* ctx, hipStream_t stream, std::vector<K
   return BSLAM_OK;
 }
 
+// Device view of one keyframe view: its images checked against the cameras (check_keyframe_images), colour and radius as
+// requested, poses, activation and id; records and quads stay null (upload_kf_table sets them for a table).
+static int make_kf_dev(const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, const bslam_keyframe_view& v, bool need_color,
+                       bool need_radius, KfDev* d) {
+  int rc = check_keyframe_images(v, depth_camera, color_camera, need_color, need_radius);
+  if (rc) return rc;
+  std::memset(d, 0, sizeof(*d));
+  d->depth = (const uint8_t*)v.depth.address;     d->depth_pitch = (uint32_t)v.depth.pitch;
+  d->normals = (const uint8_t*)v.normals.address; d->normals_pitch = (uint32_t)v.normals.pitch;
+  if (need_color) { d->color = (const uint8_t*)v.color.address; d->color_pitch = (uint32_t)v.color.pitch; }
+  if (need_radius) { d->radius = (const uint8_t*)v.radius.address; d->radius_pitch = (uint32_t)v.radius.pitch; }
+  std::memcpy(d->frame_T_global.m, v.frame_T_global.m, sizeof(float) * 12);
+  std::memcpy(d->global_R_frame, v.global_R_frame.m, sizeof(float) * 9);
+  d->activation = v.activation;
+  d->id = v.id;
+  return BSLAM_OK;
+}
+
 // The setup of every call that walks a keyframe table: validates the arguments (check_surfel_call), sets the device, builds the
 // table from the keyframe views with their colour / radius images as requested, forms the camera constants into *c and uploads
 // the table.  An empty list becomes one zeroed entry, which keeps the table pointer valid (the calls that refuse an empty list,
@@ -241,19 +266,8 @@ static int setup_keyframe_table(bslam_context* ctx, hipStream_t stream, const bs
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   std::vector<KfDev> table((size_t)std::max(keyframe_count, 1));
   std::memset(table.data(), 0, table.size() * sizeof(KfDev));
-  for (int k = 0; k < keyframe_count; ++k) {
-    const bslam_keyframe_view& v = keyframes[k];
-    if ((rc = check_keyframe_images(v, depth_camera, color_camera, need_color, need_radius))) return rc;
-    KfDev& d = table[(size_t)k];
-    d.depth = (const uint8_t*)v.depth.address;     d.depth_pitch = (uint32_t)v.depth.pitch;
-    d.normals = (const uint8_t*)v.normals.address; d.normals_pitch = (uint32_t)v.normals.pitch;
-    if (need_color) { d.color = (const uint8_t*)v.color.address; d.color_pitch = (uint32_t)v.color.pitch; }
-    if (need_radius) { d.radius = (const uint8_t*)v.radius.address; d.radius_pitch = (uint32_t)v.radius.pitch; }
-    std::memcpy(d.frame_T_global.m, v.frame_T_global.m, sizeof(float) * 12);
-    std::memcpy(d.global_R_frame, v.global_R_frame.m, sizeof(float) * 9);
-    d.activation = v.activation;
-    d.id = v.id;
-  }
+  for (int k = 0; k < keyframe_count; ++k)
+    if ((rc = make_kf_dev(depth_camera, color_camera, keyframes[k], need_color, need_radius, &table[(size_t)k]))) return rc;
   *c = make_cam_consts(ctx, color_camera, depth_camera, dp);
   return upload_kf_table(ctx, stream, table, *c);
 }
@@ -308,9 +322,8 @@ static int make_schedule(bslam_context* ctx, hipStream_t stream, const bslam_buf
   int rc = ctx->centroids.reserve((size_t)G * sizeof(float4));
   if (rc) return rc;
   float4* d_cent = (float4*)ctx->centroids.ptr;
-  const float* x = surfel_row(surfels, BSLAM_SURFEL_X);
-  const float* y = surfel_row(surfels, BSLAM_SURFEL_Y);
-  const float* z = surfel_row(surfels, BSLAM_SURFEL_Z);
+  const SurfelRowsAll all = surfel_rows_all(surfels);
+  const float *x = all.x, *y = all.y, *z = all.z;
   hipLaunchKernelGGL(granule_centroid_kernel, dim3(G), dim3(kGranule), 0, stream, x, y, z, surfels_size, d_cent);
   BSLAM_HIP_TRY(hipGetLastError());
   std::vector<float4> cent(G);
@@ -839,7 +852,7 @@ int bslam_assign_colors(
   CamConsts c;
   if ((rc = setup_keyframe_table(ctx, stream, color_camera, depth_camera, depth_params, keyframe_count, keyframes, true, surfels_size, surfels, &c))) return rc;
   hipLaunchKernelGGL(assign_colors_kernel, dim3((surfels_size + 255) / 256), dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, keyframe_count,
-                     surfel_rows_rw(surfels, nullptr, surfels_size), (uint32_t*)surfel_row(surfels, BSLAM_SURFEL_COLOR));
+                     surfel_rows_rw(surfels, nullptr, surfels_size), surfel_rows_all(surfels).color);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }

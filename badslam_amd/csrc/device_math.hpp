@@ -9,6 +9,7 @@
 // each function names the file:line whose behaviour it reproduces.
 #pragma once
 
+#include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -302,6 +303,16 @@ __device__ __forceinline__ PixelRecord gload_record(const PixelRecord* p) {   //
   const v4f v = gload((const v4f*)p);
   return PixelRecord{v.x, v.y, v.z, v.w};
 }
+
+// u16 pixel (x, y) of an image with a byte pitch (raw depth, normal code, half radius^2)
+__device__ __forceinline__ uint32_t img_u16(const uint8_t* base, uint32_t pitch, int y, int x) {
+  return gload((const uint16_t*)(base + (size_t)y * pitch) + x);
+}
+// cfactor of the sparse cell that holds pixel (px, py)
+__device__ __forceinline__ float cfactor_at(const CamConsts& c, int px, int py) {
+  return gload((const float*)((const uint8_t*)c.cfactor + (size_t)(py / c.cell) * c.cfactor_pitch) + (px / c.cell));
+}
+__device__ __forceinline__ float half_bits_to_float(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 
 struct LumaQuad { float tl, tr, bl, br; };   // texels (i,j), (i+1,j), (i,j+1), (i+1,j+1) in [0,1]
 
@@ -622,8 +633,7 @@ __global__ __launch_bounds__(256) void build_records_kernel(CamConsts c, const K
   const uint32_t normal = *(const uint16_t*)(kf.normals + (size_t)y * kf.normals_pitch + 2 * (size_t)x);
   float depth = 0.f;
   if (!(measured & BSLAM_INVALID_DEPTH_BIT)) {
-    const float cf = *(const float*)((const uint8_t*)c.cfactor + (size_t)(y / c.cell) * c.cfactor_pitch + 4 * (size_t)(x / c.cell));
-    depth = raw_to_calibrated_depth(c.a, cf, c.raw_to_float_depth, measured);
+    depth = raw_to_calibrated_depth(c.a, cfactor_at(c, x, y), c.raw_to_float_depth, measured);
   }
   const f3 n = u16_to_image_space_normal(normal);
   records[((size_t)k * c.height + y) * c.width + x] = PixelRecord{depth, n.x, n.y, n.z};
@@ -690,10 +700,15 @@ __global__ __launch_bounds__(256) void quad_samples_probe_kernel(CamConsts c, co
 
 // Projection + association in three stages, so that a kernel can put the record gathers of several surfels in flight before
 // it consumes the first (project_and_associate below is their composition; same arithmetic either way).
-// Stage 1: MultiplyIfResultZIsPositive BS/cuda_matrix.cuh:113-124 + ProjectSurfelToImage BS/util.cuh:86-99.  True when the
-// surfel projects into the image; fills local, pxy, px, py.
-__device__ __forceinline__ bool project_to_pixel(const CamConsts& c, const KfDev& kf, f3 gp, Proj* r) {
-  const M34& T = kf.frame_T_global;
+// Stage 1: MultiplyIfResultZIsPositive BS/cuda_matrix.cuh:113-124 + ProjectSurfelToImage BS/util.cuh:86-99 with the 3x4 transform
+// T.  True when gp lies in front of the camera and projects into the image; fills local, pxy, px, py.
+// The two z tests differ exactly for a NaN position, the mark of a merged or deleted surfel, and both are intended:
+//   kNanPasses = false  `z > 0`: a NaN is rejected (project_to_pixel: every BA kernel, fusion);
+//   kNanPasses = true   `!(z <= 0)`, the reference's own `if (result->z <= 0.f) return false` (BS/cuda_matrix.cuh:116): a NaN
+//                       passes, projects to pixel (0, 0) (f2i(NaN) == 0) and may hold that cell -- the surfel lifecycle
+//                       (lifecycle_kernels.hpp), as in the reference; the CPU checker of the tests models it.
+template <bool kNanPasses>
+__device__ __forceinline__ bool project_with(const CamConsts& c, const M34& T, f3 gp, Proj* r) {
   r->local.z = tr_row(T.m[8], T.m[9], T.m[10], T.m[11], gp);
   r->local.x = tr_row(T.m[0], T.m[1], T.m[2], T.m[3], gp);
   r->local.y = tr_row(T.m[4], T.m[5], T.m[6], T.m[7], gp);
@@ -702,7 +717,10 @@ __device__ __forceinline__ bool project_to_pixel(const CamConsts& c, const KfDev
   r->py = f2i(r->pxy.y);
   // one exit (with the per-surfel work order a wave's lanes almost always agree, so early outs only cost exec-mask
   // bookkeeping): a point behind the camera projects to garbage (finite or not) that the z test discards
-  return (r->local.z > 0.f) & !(r->pxy.x < 0 || r->pxy.y < 0 || r->px >= c.width || r->py >= c.height);
+  return (kNanPasses ? !(r->local.z <= 0.f) : (r->local.z > 0.f)) & !(r->pxy.x < 0 || r->pxy.y < 0 || r->px >= c.width || r->py >= c.height);
+}
+__device__ __forceinline__ bool project_to_pixel(const CamConsts& c, const KfDev& kf, f3 gp, Proj* r) {
+  return project_with<false>(c, kf.frame_T_global, gp, r);
 }
 // Stage 2: the pixel's derived record.  The offset inside one keyframe's table fits 24 bits (v_mad_u32_u24, full rate) and is
 // added to the uniform base as a 32-bit offset (global_load with an SGPR base): no 64-bit vector arithmetic per gather.
@@ -713,7 +731,7 @@ __device__ __forceinline__ PixelRecord load_record(const CamConsts& c, const KfD
 }
 // raw u16 depth of the associated pixel (only the depth-intrinsics Jacobians need it)
 __device__ __forceinline__ uint32_t raw_depth_of(const KfDev& kf, const Proj& r) {
-  return gload((const uint16_t*)(kf.depth + (size_t)r.py * kf.depth_pitch + 2 * (size_t)r.px));
+  return img_u16(kf.depth, kf.depth_pitch, r.py, r.px);
 }
 // Stage 3: IsAssociatedWithPixel<false, true> BS/surfel_projection_nvcc_only.cuh:49-127 on the loaded record.
 __device__ __forceinline__ bool associate_with_record(const CamConsts& c, const KfDev& kf, f3 gn, PixelRecord rec, Proj* r) {

@@ -2,29 +2,6 @@
 
 namespace bslam {
 
-static SurfelRowsAll surfel_rows_all(const bslam_buffer2d* s) {
-  SurfelRowsAll o;
-  o.x = surfel_row(s, BSLAM_SURFEL_X); o.y = surfel_row(s, BSLAM_SURFEL_Y); o.z = surfel_row(s, BSLAM_SURFEL_Z);
-  o.normal = (uint32_t*)surfel_row(s, BSLAM_SURFEL_NORMAL);
-  o.radius_squared = surfel_row(s, BSLAM_SURFEL_RADIUS_SQUARED);
-  o.color = (uint32_t*)surfel_row(s, BSLAM_SURFEL_COLOR);
-  o.d1 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR1); o.d2 = surfel_row(s, BSLAM_SURFEL_DESCRIPTOR2);
-  return o;
-}
-
-static int make_kf_images(const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, const bslam_keyframe_view* v,
-                          bool need_radius, bool need_color, KfImages* out) {
-  int rc = check_keyframe_images(*v, depth_camera, color_camera, need_color, need_radius);
-  if (rc) return rc;
-  std::memset(out, 0, sizeof(*out));
-  out->depth = (const uint8_t*)v->depth.address;     out->depth_pitch = (uint32_t)v->depth.pitch;
-  out->normals = (const uint8_t*)v->normals.address; out->normals_pitch = (uint32_t)v->normals.pitch;
-  if (need_radius) { out->radius = (const uint8_t*)v->radius.address; out->radius_pitch = (uint32_t)v->radius.pitch; }
-  if (need_color) { out->color = (const uint8_t*)v->color.address; out->color_pitch = (uint32_t)v->color.pitch; }
-  std::memcpy(out->frame_T_global.m, v->frame_T_global.m, sizeof(float) * 12);
-  return BSLAM_OK;
-}
-
 // Device scratch of the lifecycle calls, carved out of one slab:
 //   sup[3][cells] | cell_of[S] | flags8[pixels] | idx[max(pixels, S)] x 3 | tile sums | counters
 struct LifecycleScratch {
@@ -77,17 +54,44 @@ static int read_u32(bslam_context* ctx, hipStream_t stream, const uint32_t* dev,
   return BSLAM_OK;
 }
 
+// Setup of the two calls that work on one keyframe: the arguments every surfel call validates, the device, the keyframe's device
+// view (with colour and radius images when a colour camera is given: creation), camera constants, cell grid and scratch.
+struct KeyframeCall {
+  KfDev kf;
+  CamConsts c;
+  int cells_w, cells_h;
+  uint32_t pixels;
+  LifecycleScratch sc;
+};
+// created: creation's output count, zeroed once check_surfel_call has passed (it is valid on every later return); may be null.
+static int setup_keyframe_call(bslam_context* ctx, const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera, const bslam_depth_params* dp,
+                               const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* created,
+                               KeyframeCall* o) {
+  int rc = check_surfel_call(ctx, depth_camera, dp, surfels, surfels_size);
+  if (rc) return rc;
+  if (created) *created = 0;
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  const bool creating = color_camera != nullptr;
+  if ((rc = make_kf_dev(depth_camera, color_camera, *keyframe, creating, creating, &o->kf))) return rc;
+  o->c = make_cam_consts(ctx, color_camera, depth_camera, dp);
+  o->cells_w = (o->c.width - 1) / o->c.cell + 1;
+  o->cells_h = (o->c.height - 1) / o->c.cell + 1;
+  o->pixels = (uint32_t)(o->c.width * o->c.height);
+  return lifecycle_scratch(ctx, (size_t)o->cells_w * o->cells_h, surfels_size, o->pixels, &o->sc);
+}
+
 // DetermineSupportingSurfelsCUDAImpl (BS/kernel_supporting_surfels.cc:38-112)
-static int supporting_surfels(bslam_context* ctx, hipStream_t stream, bool merge, float merge_dist_factor, const CamConsts& c, const KfImages& kf,
-                              uint32_t surfels_size, const bslam_buffer2d* surfels, const LifecycleScratch& sc, int cells_w, int cells_h,
-                              uint32_t* deleted_out) {
-  const size_t cells = (size_t)cells_w * cells_h;
+static int supporting_surfels(bslam_context* ctx, hipStream_t stream, bool merge, float merge_dist_factor, const KeyframeCall& k,
+                              uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* deleted_out) {
+  const CamConsts& c = k.c;
+  const LifecycleScratch& sc = k.sc;
+  const size_t cells = (size_t)k.cells_w * k.cells_h;
   BSLAM_HIP_TRY(hipMemsetAsync(sc.sup[0], 0xff, 3 * cells * sizeof(uint32_t), stream));   // Clear(kInvalidIndex)
   if (deleted_out) *deleted_out = 0;
   if (surfels_size == 0) return BSLAM_OK;
   const SurfelRowsAll rows = surfel_rows_all(surfels);
   const dim3 grid((surfels_size + 255) / 256), block(256);
-  hipLaunchKernelGGL(support_claim0_kernel, grid, block, 0, stream, c, kf, rows, surfels_size, cells_w, sc.cell_of, sc.sup[0]);
+  hipLaunchKernelGGL(support_claim0_kernel, grid, block, 0, stream, c, k.kf, rows, surfels_size, k.cells_w, sc.cell_of, sc.sup[0]);
   BSLAM_HIP_TRY(hipGetLastError());
   if (!merge) return BSLAM_OK;   // creation only asks "is the cell occupied"
   hipLaunchKernelGGL(support_claim_next_kernel, grid, block, 0, stream, surfels_size, (const uint32_t*)sc.cell_of, (const uint32_t*)sc.sup[0],
@@ -116,17 +120,11 @@ int bslam_determine_supporting_surfels_and_merge(
     const bslam_keyframe_view* keyframe, uint32_t surfels_size, const bslam_buffer2d* surfels, uint32_t* surfel_count) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!keyframe || !surfel_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
-  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
+  KeyframeCall k;
+  int rc = setup_keyframe_call(ctx, nullptr, depth_camera, depth_params, keyframe, surfels_size, surfels, nullptr, &k);
   if (rc) return rc;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  KfImages kf;
-  if ((rc = make_kf_images(depth_camera, nullptr, keyframe, false, false, &kf))) return rc;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
-  const int cells_w = (c.width - 1) / c.cell + 1, cells_h = (c.height - 1) / c.cell + 1;
-  LifecycleScratch sc;
-  if ((rc = lifecycle_scratch(ctx, (size_t)cells_w * cells_h, surfels_size, (size_t)c.width * c.height, &sc))) return rc;
   uint32_t deleted = 0;
-  if ((rc = supporting_surfels(ctx, stream, true, merge_dist_factor, c, kf, surfels_size, surfels, sc, cells_w, cells_h, &deleted))) return rc;
+  if ((rc = supporting_surfels(ctx, stream, true, merge_dist_factor, k, surfels_size, surfels, &deleted))) return rc;
   *surfel_count -= deleted;
   return BSLAM_OK;
 }
@@ -140,18 +138,15 @@ int bslam_create_surfels_for_keyframe(
   hipStream_t stream = (hipStream_t)stream_;
   if (!keyframe || !color_camera || !global_T_frame || !new_surfel_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (covis_count < 0 || (covis_count > 0 && filter_new_surfels && (!covis_keyframes || !covis_T_frame))) return fail(BSLAM_ERR_INVALID_ARGUMENT, "bad co-visibility list");
-  int rc = check_surfel_call(ctx, depth_camera, depth_params, surfels, surfels_size);
+  KeyframeCall call;
+  int rc = setup_keyframe_call(ctx, color_camera, depth_camera, depth_params, keyframe, surfels_size, surfels, new_surfel_count, &call);
   if (rc) return rc;
-  *new_surfel_count = 0;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  KfImages kf;
-  if ((rc = make_kf_images(depth_camera, color_camera, keyframe, true, true, &kf))) return rc;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, depth_params);
-  const int cells_w = (c.width - 1) / c.cell + 1, cells_h = (c.height - 1) / c.cell + 1;
-  const uint32_t pixels = (uint32_t)(c.width * c.height);
-  LifecycleScratch sc;
-  if ((rc = lifecycle_scratch(ctx, (size_t)cells_w * cells_h, surfels_size, pixels, &sc))) return rc;
-  if ((rc = supporting_surfels(ctx, stream, false, 0.f, c, kf, surfels_size, surfels, sc, cells_w, cells_h, nullptr))) return rc;   // BS/direct_ba.cc:349-358
+  const CamConsts& c = call.c;
+  const KfDev& kf = call.kf;
+  const LifecycleScratch& sc = call.sc;
+  const int cells_w = call.cells_w, cells_h = call.cells_h;
+  const uint32_t pixels = call.pixels;
+  if ((rc = supporting_surfels(ctx, stream, false, 0.f, call, surfels_size, surfels, nullptr))) return rc;   // BS/direct_ba.cc:349-358
 
   BSLAM_HIP_TRY(hipMemsetAsync(sc.flags, 0, pixels, stream));
   hipLaunchKernelGGL(create_flag_kernel, dim3((unsigned)((cells_w + 255) / 256), (unsigned)cells_h), dim3(256), 0, stream, c, kf, cells_w, cells_h, sc.sup[0], sc.flags);
@@ -161,25 +156,24 @@ int bslam_create_surfels_for_keyframe(
   if ((rc = read_u32(ctx, stream, sc.counters + 1, &count))) return rc;
   if (count == 0) return BSLAM_OK;
   if (filter_new_surfels) {   // BS/kernel_create_surfels.cc:84-136
-    const KfImages* covis_dev = nullptr;
-    const M34* covis_T_dev = nullptr;
+    // the co-visibility list as a keyframe table of its own (raw images only: no records, no quads), entry k's frame_T_global
+    // being covis_T_frame[k]; an empty list launches with a null table and removes every candidate
+    const KfDev* covis_dev = nullptr;
     if (covis_count > 0) {
-      std::vector<KfImages> covis((size_t)covis_count);
-      for (int k = 0; k < covis_count; ++k)
-        if ((rc = make_kf_images(depth_camera, nullptr, &covis_keyframes[k], false, false, &covis[(size_t)k]))) return rc;
-      const size_t img_bytes = covis.size() * sizeof(KfImages), mat_bytes = (size_t)covis_count * sizeof(M34);
-      if ((rc = ctx->exchange.reserve(img_bytes + mat_bytes))) return rc;
+      const size_t bytes = (size_t)covis_count * sizeof(KfDev);
+      if ((rc = ctx->exchange.reserve(bytes))) return rc;
       void* stage = nullptr;
-      if ((rc = ctx->upload_ring.acquire(img_bytes + mat_bytes, &stage))) return rc;
-      std::memcpy(stage, covis.data(), img_bytes);
-      std::memcpy((uint8_t*)stage + img_bytes, covis_T_frame, mat_bytes);
-      BSLAM_HIP_TRY(hipMemcpyAsync(ctx->exchange.ptr, stage, img_bytes + mat_bytes, hipMemcpyHostToDevice, stream));
+      if ((rc = ctx->upload_ring.acquire(bytes, &stage))) return rc;
+      KfDev* covis = (KfDev*)stage;
+      for (int k = 0; k < covis_count; ++k) {
+        if ((rc = make_kf_dev(depth_camera, nullptr, covis_keyframes[k], false, false, &covis[k]))) return rc;
+        std::memcpy(covis[k].frame_T_global.m, covis_T_frame[k].m, sizeof(float) * 12);
+      }
+      BSLAM_HIP_TRY(hipMemcpyAsync(ctx->exchange.ptr, stage, bytes, hipMemcpyHostToDevice, stream));
       if ((rc = ctx->upload_ring.commit(stream))) return rc;
-      covis_dev = (const KfImages*)ctx->exchange.ptr;
-      covis_T_dev = (const M34*)((const uint8_t*)ctx->exchange.ptr + img_bytes);
+      covis_dev = (const KfDev*)ctx->exchange.ptr;
     }
-    hipLaunchKernelGGL(create_filter_kernel, dim3((pixels + 255) / 256), dim3(256), 0, stream, c, kf, covis_count, covis_dev, covis_T_dev,
-                       min_observation_count, sc.flags);
+    hipLaunchKernelGGL(create_filter_kernel, dim3((pixels + 255) / 256), dim3(256), 0, stream, c, kf, covis_count, covis_dev, min_observation_count, sc.flags);
     BSLAM_HIP_TRY(hipGetLastError());
     if ((rc = device_scan(stream, 0, sc.flags, pixels, false, sc.a, sc.tile_sums, sc.counters + 1))) return rc;
     if ((rc = read_u32(ctx, stream, sc.counters + 1, &count))) return rc;
@@ -235,7 +229,7 @@ int bslam_compact_surfels(bslam_context* ctx, void* stream_, uint32_t surfel_cou
   if (rc) return rc;
   const uint32_t free_spot_count = n - surfel_count;
   const dim3 grid((n + 255) / 256), block(256);
-  const float* x = surfel_row(surfels, BSLAM_SURFEL_X);
+  const float* x = surfel_rows_all(surfels).x;
   uint32_t* invalid = sc.cell_of;   // [n]
   hipLaunchKernelGGL(compact_flag_kernel, grid, block, 0, stream, n, x, invalid);
   BSLAM_HIP_TRY(hipGetLastError());

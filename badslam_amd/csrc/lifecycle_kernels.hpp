@@ -11,32 +11,14 @@
 //     observation-count launches by one kernel that walks the keyframe table.
 #pragma once
 
-#include <hip/hip_fp16.h>
-
 #include "device_math.hpp"
+#include "pose_kernels.hpp"
 
 namespace bslam {
 
 constexpr uint32_t kInvalidIndex = 0xffffffffu;
 constexpr uint32_t kNanBits = 0x7fffffffu;   // CUDART_NAN_F marks a deleted surfel (BS/kernel_delete_surfels.cu:145)
 constexpr int kMergeBufferCount = 3;         // BS/kernels.cuh:51
-
-// Raw images of one keyframe, passed by value to the single-keyframe kernels (no derived records needed).
-struct KfImages {
-  const uint8_t* depth;   uint32_t depth_pitch;
-  const uint8_t* normals; uint32_t normals_pitch;
-  const uint8_t* radius;  uint32_t radius_pitch;
-  const uint8_t* color;   uint32_t color_pitch;
-  M34 frame_T_global;
-};
-
-__device__ __forceinline__ uint32_t img_u16(const uint8_t* base, uint32_t pitch, int y, int x) {
-  return gload((const uint16_t*)(base + (size_t)y * pitch) + x);
-}
-__device__ __forceinline__ float cfactor_at(const CamConsts& c, int px, int py) {
-  return gload((const float*)((const uint8_t*)c.cfactor + (size_t)(py / c.cell) * c.cfactor_pitch) + (px / c.cell));
-}
-__device__ __forceinline__ float half_bits_to_float(uint32_t h) { return __half2float(__ushort_as_half((unsigned short)h)); }
 
 // Shared tail of the association test (BS/surfel_projection_nvcc_only.cuh:76-126), kFreeSpace selects the
 // <true> variant's depth test.  n_local: surfel normal in the keyframe's frame.
@@ -58,59 +40,47 @@ __device__ __forceinline__ bool association_tail(const CamConsts& c, f3 local, f
   return true;
 }
 
-// SurfelProjectsToAssociatedPixel on the raw images of one keyframe.
-template <bool kFreeSpace>
-__device__ __forceinline__ bool associate_direct(const CamConsts& c, const KfImages& kf, f3 gp, f3 gn, int* px, int* py, bool* fsv) {
-  const M34& T = kf.frame_T_global;
-  f3 local;
-  local.z = tr_row(T.m[8], T.m[9], T.m[10], T.m[11], gp);
-  if (local.z <= 0.f) return false;
-  local.x = tr_row(T.m[0], T.m[1], T.m[2], T.m[3], gp);
-  local.y = tr_row(T.m[4], T.m[5], T.m[6], T.m[7], gp);
-  const f2 pxy = project(c.fx, c.fy, c.cx, c.cy, local);
-  *px = f2i(pxy.x);
-  *py = f2i(pxy.y);
-  if (pxy.x < 0 || pxy.y < 0 || *px >= c.width || *py >= c.height) return false;
-  const uint32_t measured = img_u16(kf.depth, kf.depth_pitch, *py, *px);
-  if (measured & BSLAM_INVALID_DEPTH_BIT) return false;
-  const float depth = raw_to_calibrated_depth(c.a, cfactor_at(c, *px, *py), c.raw_to_float_depth, measured);
-  return association_tail<kFreeSpace>(c, local, rot34(T, gn), *px, *py, depth, img_u16(kf.normals, kf.normals_pitch, *py, *px), fsv);
+// Where the association reads a pixel's measurement: false when the pixel has none, else its calibrated depth.  kRecords: the
+// derived records of the keyframe table (same arithmetic, done once per pixel); otherwise the raw depth image, for the
+// single-keyframe calls and the co-visibility list, whose records nobody has built.
+template <bool kRecords>
+__device__ __forceinline__ bool pixel_depth(const CamConsts& c, const KfDev& kf, const Proj& r, float* depth) {
+  if constexpr (kRecords) {
+    *depth = load_record(c, kf, r).depth;
+    return *depth != 0.f;
+  } else {
+    const uint32_t measured = img_u16(kf.depth, kf.depth_pitch, r.py, r.px);
+    if (measured & BSLAM_INVALID_DEPTH_BIT) return false;
+    *depth = raw_to_calibrated_depth(c.a, cfactor_at(c, r.px, r.py), c.raw_to_float_depth, measured);
+    return true;
+  }
 }
 
-// Same test against the derived records of the keyframe table (free-space variant for deletion).
-__device__ __forceinline__ bool associate_records_fs(const CamConsts& c, const KfDev& kf, f3 gp, f3 gn, int* px, int* py, bool* fsv) {
-  const M34& T = kf.frame_T_global;
-  f3 local;
-  local.z = tr_row(T.m[8], T.m[9], T.m[10], T.m[11], gp);
-  if (local.z <= 0.f) return false;
-  local.x = tr_row(T.m[0], T.m[1], T.m[2], T.m[3], gp);
-  local.y = tr_row(T.m[4], T.m[5], T.m[6], T.m[7], gp);
-  const f2 pxy = project(c.fx, c.fy, c.cx, c.cy, local);
-  *px = f2i(pxy.x);
-  *py = f2i(pxy.y);
-  if (pxy.x < 0 || pxy.y < 0 || *px >= c.width || *py >= c.height) return false;
-  const PixelRecord rec = gload_record(kf.records + ((size_t)*py * c.width + *px));
-  if (rec.depth == 0.f) return false;
-  return association_tail<true>(c, local, rot34(T, gn), *px, *py, rec.depth, img_u16(kf.normals, kf.normals_pitch, *py, *px), fsv);
+// SurfelProjectsToAssociatedPixel (BS/surfel_projection_nvcc_only.cuh:302-332) of a point gp with normal gn against the keyframe
+// whose frame_T_global is kf's; fills r->local, pxy, px, py.
+template <bool kFreeSpace, bool kRecords>
+__device__ __forceinline__ bool associate_pixel(const CamConsts& c, const KfDev& kf, f3 gp, f3 gn, Proj* r, bool* fsv) {
+  // the reference's `z <= 0` test, which a NaN position (a merged or deleted surfel) passes: it projects to pixel (0, 0) and may
+  // hold that cell, unlike in the BA kernels (device_math.hpp: project_with)
+  if (!project_with<true>(c, kf.frame_T_global, gp, r)) return false;
+  float depth;
+  if (!pixel_depth<kRecords>(c, kf, *r, &depth)) return false;
+  return association_tail<kFreeSpace>(c, r->local, rot34(kf.frame_T_global, gn), r->px, r->py, depth, img_u16(kf.normals, kf.normals_pitch, r->py, r->px), fsv);
 }
-
-struct SurfelRowsAll {   // the eight persistent rows, writable
-  float* x; float* y; float* z; uint32_t* normal; float* radius_squared; uint32_t* color; float* d1; float* d2;
-};
 
 // ---------------------------------------------------------------------------------------------
 // supporting surfels (+ merge): BS/kernel_supporting_surfels.cu:45-97
 // ---------------------------------------------------------------------------------------------
 // Pass 0: association -> cell_of[i]; holder 0 of a cell = smallest projecting index.
-__global__ __launch_bounds__(256) void support_claim0_kernel(CamConsts c, KfImages kf, SurfelRowsAll s, uint32_t size, int cells_w,
+__global__ __launch_bounds__(256) void support_claim0_kernel(CamConsts c, KfDev kf, SurfelRowsAll s, uint32_t size, int cells_w,
                                                             uint32_t* __restrict__ cell_of, uint32_t* __restrict__ sup0) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= size) return;
-  int px, py;
+  Proj r;
   bool fsv;
   uint32_t cell = kInvalidIndex;
-  if (associate_direct<false>(c, kf, mk3(s.x[i], s.y[i], s.z[i]), unpack_normal(s.normal[i]), &px, &py, &fsv)) {
-    cell = (uint32_t)((py / c.cell) * cells_w + (px / c.cell));
+  if (associate_pixel<false, false>(c, kf, mk3(s.x[i], s.y[i], s.z[i]), unpack_normal(s.normal[i]), &r, &fsv)) {
+    cell = (uint32_t)((r.py / c.cell) * cells_w + (r.px / c.cell));
     atomicMin(&sup0[cell], i);
   }
   cell_of[i] = cell;
@@ -257,7 +227,7 @@ __global__ __launch_bounds__(kScanThreads) void scan_add_kernel(uint32_t* __rest
 // ---------------------------------------------------------------------------------------------
 // CreateSurfelsForKeyframeCUDASerializingKernel (:41-72): one thread per free cell, first valid pixel in
 // raster order becomes the new surfel.  flags must be zeroed by the caller.
-__global__ __launch_bounds__(256) void create_flag_kernel(CamConsts c, KfImages kf, int cells_w, int cells_h, uint32_t* __restrict__ sup0,
+__global__ __launch_bounds__(256) void create_flag_kernel(CamConsts c, KfDev kf, int cells_w, int cells_h, uint32_t* __restrict__ sup0,
                                                          uint8_t* __restrict__ flags) {
   const int cellx = blockIdx.x * blockDim.x + threadIdx.x;
   const int celly = blockIdx.y;
@@ -278,9 +248,9 @@ __global__ __launch_bounds__(256) void create_flag_kernel(CamConsts c, KfImages 
 
 // WriteNewSurfelIndexAndInitializeObservations + CountObservationsForNewSurfels (per co-visible keyframe) +
 // FilterNewSurfels (:163-305) in one pass per candidate pixel.
-__global__ __launch_bounds__(256) void create_filter_kernel(CamConsts c, KfImages kf, int covis_count, const KfImages* __restrict__ covis,
-                                                           const M34* __restrict__ covis_T_frame, int min_observation_count,
-                                                           uint8_t* __restrict__ flags) {
+// covis[k]: raw images of co-visible keyframe k, with covis_T_frame[k] (co-visible frame <- this frame) as its frame_T_global.
+__global__ __launch_bounds__(256) void create_filter_kernel(CamConsts c, KfDev kf, int covis_count, const KfDev* __restrict__ covis,
+                                                           int min_observation_count, uint8_t* __restrict__ flags) {
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   if (seq >= (uint32_t)(c.width * c.height) || flags[seq] != 1) return;
   const int y = (int)(seq / (uint32_t)c.width), x = (int)(seq - (uint32_t)y * (uint32_t)c.width);
@@ -289,55 +259,34 @@ __global__ __launch_bounds__(256) void create_filter_kernel(CamConsts c, KfImage
   const f3 input_position = unproject(c, x, y, depth);
   const f3 image_normal = u16_to_image_space_normal(img_u16(kf.normals, kf.normals_pitch, y, x));
   for (int k = 0; k < covis_count; ++k) {
-    const KfImages& ck = covis[k];
-    const M34& T = covis_T_frame[k];
-    f3 local;
-    local.z = tr_row(T.m[8], T.m[9], T.m[10], T.m[11], input_position);
-    if (local.z <= 0.f) continue;
-    local.x = tr_row(T.m[0], T.m[1], T.m[2], T.m[3], input_position);
-    local.y = tr_row(T.m[4], T.m[5], T.m[6], T.m[7], input_position);
-    const f2 pxy = project(c.fx, c.fy, c.cx, c.cy, local);
-    const int px = f2i(pxy.x), py = f2i(pxy.y);
-    if (pxy.x < 0 || pxy.y < 0 || px >= c.width || py >= c.height) continue;
-    const uint32_t measured = img_u16(ck.depth, ck.depth_pitch, py, px);
-    if (measured & BSLAM_INVALID_DEPTH_BIT) continue;
-    const float pixel_depth = raw_to_calibrated_depth(c.a, cfactor_at(c, px, py), c.raw_to_float_depth, measured);
+    Proj r;
     bool fsv = false;
-    if (association_tail<true>(c, local, rot34(T, image_normal), px, py, pixel_depth, img_u16(ck.normals, ck.normals_pitch, py, px), &fsv)) ++observations;
+    if (associate_pixel<true, false>(c, covis[k], input_position, image_normal, &r, &fsv)) ++observations;
     else if (fsv) ++violations;
   }
   if ((uint16_t)observations < (uint16_t)min_observation_count || (uint16_t)violations > (uint16_t)observations) flags[seq] = 0;
 }
 
-// bilinear fetch of one colour channel from the uchar4 image (same filter model as tex_filter)
-__device__ __forceinline__ float tex_channel_direct(const CamConsts& c, const KfImages& kf, float x, float y, int chn) {
-  const TexFootprint f = tex_footprint(c, x, y);
+// The 2x2 texel footprint of one byte channel of the uchar4 image as floats in byte units, clamp addressing (direct loads: the
+// creation kernels run before any quad table of this keyframe exists).
+__device__ __forceinline__ LumaQuad gather_quad_bytes(const CamConsts& c, const KfDev& kf, const TexFootprint& f, int chn) {
   auto texel = [&](int ix, int iy) {
     ix = max(0, min(ix, c.color_width - 1));
     iy = max(0, min(iy, c.color_height - 1));
-    return (float)gload(kf.color + (size_t)iy * kf.color_pitch + 4 * (size_t)ix + chn) * (1.0f / 255.0f);
+    return (float)gload(kf.color + (size_t)iy * kf.color_pitch + 4 * (size_t)ix + chn);
   };
-  LumaQuad q;
-  q.tl = texel(f.i, f.j); q.tr = texel(f.i + 1, f.j); q.bl = texel(f.i, f.j + 1); q.br = texel(f.i + 1, f.j + 1);
+  return LumaQuad{texel(f.i, f.j), texel(f.i + 1, f.j), texel(f.i, f.j + 1), texel(f.i + 1, f.j + 1)};
+}
+// bilinear fetch of one colour channel in [0, 1] (same filter model as tex_filter)
+__device__ __forceinline__ float tex_channel_direct(const CamConsts& c, const KfDev& kf, float x, float y, int chn) {
+  const TexFootprint f = tex_footprint(c, x, y);
+  LumaQuad q = gather_quad_bytes(c, kf, f, chn);
+  q.tl *= 1.0f / 255.0f; q.tr *= 1.0f / 255.0f; q.bl *= 1.0f / 255.0f; q.br *= 1.0f / 255.0f;
   return tex_filter(q, f.a, f.b);
 }
 
-// the luma channel in byte units through the residual path's filter (device_math.hpp: bilinear_bytes): the initial descriptor
-// is ComputeRawDescriptorResidual with a zero descriptor (:141-152), i.e. the same arithmetic as every later residual
-__device__ __forceinline__ float tex_luma_bytes_direct(const CamConsts& c, const KfImages& kf, float x, float y) {
-  const TexFootprint f = tex_footprint(c, x, y);
-  auto texel = [&](int ix, int iy) {
-    ix = max(0, min(ix, c.color_width - 1));
-    iy = max(0, min(iy, c.color_height - 1));
-    return (float)gload(kf.color + (size_t)iy * kf.color_pitch + 4 * (size_t)ix + 3);
-  };
-  LumaQuad q;
-  q.tl = texel(f.i, f.j); q.tr = texel(f.i + 1, f.j); q.bl = texel(f.i, f.j + 1); q.br = texel(f.i + 1, f.j + 1);
-  return bilinear_bytes(q, f.a, f.b);
-}
-
 // CreateSurfelsForKeyframeCUDACreationAppendKernel + CreateNewSurfel (:96-161, 357-385)
-__global__ __launch_bounds__(256) void create_append_kernel(CamConsts c, KfImages kf, M34 global_T_frame, const uint8_t* __restrict__ flags,
+__global__ __launch_bounds__(256) void create_append_kernel(CamConsts c, KfDev kf, M34 global_T_frame, const uint8_t* __restrict__ flags,
                                                            const uint32_t* __restrict__ indices, uint32_t surfels_size, SurfelRowsAll s) {
   const uint32_t seq = blockIdx.x * blockDim.x + threadIdx.x;
   if (seq >= (uint32_t)(c.width * c.height) || flags[seq] != 1) return;
@@ -358,9 +307,13 @@ __global__ __launch_bounds__(256) void create_append_kernel(CamConsts c, KfImage
   s.color[si] = col;
   f2 t1, t2;
   tangent_projections(gp, gn, radius_squared, kf.frame_T_global, c, &t1, &t2);   // the unquantised normal, as in the reference (:124-131)
-  const float b0 = tex_luma_bytes_direct(c, kf, color_pxy.x, color_pxy.y);
-  const float b1 = tex_luma_bytes_direct(c, kf, t1.x, t1.y);
-  const float b2 = tex_luma_bytes_direct(c, kf, t2.x, t2.y);
+  // the luma channel in byte units through the residual path's filter (bilinear_bytes): the initial descriptor is
+  // ComputeRawDescriptorResidual with a zero descriptor (:141-152), i.e. the same arithmetic as every later residual
+  auto luma_bytes = [&](float px, float py) {
+    const TexFootprint f = tex_footprint(c, px, py);
+    return bilinear_bytes(gather_quad_bytes(c, kf, f, 3), f.a, f.b);
+  };
+  const float b0 = luma_bytes(color_pxy.x, color_pxy.y), b1 = luma_bytes(t1.x, t1.y), b2 = luma_bytes(t2.x, t2.y);
   s.d1[si] = __builtin_fmaf(kDescScale, b1 - b0, -0.f);
   s.d2[si] = __builtin_fmaf(kDescScale, b2 - b0, -0.f);
 }
@@ -387,12 +340,12 @@ __global__ __launch_bounds__(256) void delete_and_update_radii_kernel(CamConsts 
   const f3 gn = unpack_normal(sorted.normal[j]);
   float observations = 0.f, violations = 0.f, min_radius = __uint_as_float(0x7f800000u);
   BSLAM_FOR_VISITED_KEYFRAMES_IF(k, 0, kf_count, 1, true) {
-    int px, py;
+    Proj r;
     bool fsv = false;
     if (!valid) continue;
-    if (associate_records_fs(c, kfs[k], gp, gn, &px, &py, &fsv)) {
+    if (associate_pixel<true, true>(c, kfs[k], gp, gn, &r, &fsv)) {
       observations += 1.f;
-      min_radius = fminf(min_radius, half_bits_to_float(img_u16(kfs[k].radius, kfs[k].radius_pitch, py, px)));
+      min_radius = fminf(min_radius, half_bits_to_float(img_u16(kfs[k].radius, kfs[k].radius_pitch, r.py, r.px)));
     } else if (fsv) {
       violations += 1.f;
     }

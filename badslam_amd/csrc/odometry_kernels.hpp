@@ -55,8 +55,7 @@ __global__ __launch_bounds__(256) void calibrate_depth_kernel(CamConsts c, Img d
   const uint32_t raw = depth_u16.at<uint16_t>(y, x);
   float depth = 0.f;
   if (!(raw & BSLAM_INVALID_DEPTH_BIT)) {
-    const float cf = *(const float*)((const uint8_t*)c.cfactor + (size_t)(y / c.cell) * c.cfactor_pitch + 4 * (size_t)(x / c.cell));
-    depth = raw_to_calibrated_depth(c.a, cf, c.raw_to_float_depth, raw);
+    depth = raw_to_calibrated_depth(c.a, cfactor_at(c, x, y), c.raw_to_float_depth, raw);
   }
   if (kTransformColor) {
     f2 color_pxy;
@@ -126,8 +125,7 @@ __global__ __launch_bounds__(256) void calibrate_and_downsample_kernel(CamConsts
   for (int i = 0; i < 4; ++i) {
     const uint32_t raw = depth_u16.at<uint16_t>(2 * y + (i >> 1), 2 * x + (i & 1));
     if (!(raw & BSLAM_INVALID_DEPTH_BIT)) {
-      const float cf = *(const float*)((const uint8_t*)c.cfactor + (size_t)(y / c.cell) * c.cfactor_pitch + 4 * (size_t)(x / c.cell));
-      depths[i] = raw_to_calibrated_depth(c.a, cf, c.raw_to_float_depth, raw);
+      depths[i] = raw_to_calibrated_depth(c.a, cfactor_at(c, x, y), c.raw_to_float_depth, raw);
       depth_sum += depths[i];
       depth_count += 1;
     } else {

@@ -68,6 +68,11 @@ struct SurfelRows {
   const float* d1; const float* d2;
   uint32_t size;
 };
+// The eight persistent rows, writable (the surfel lifecycle).  The host's surfel_rows_all is the one place that maps
+// BSLAM_SURFEL_* to row pointers; every other row struct is derived from its result.
+struct SurfelRowsAll {
+  float* x; float* y; float* z; uint32_t* normal; float* radius_squared; uint32_t* color; float* d1; float* d2;
+};
 
 struct PoseState {
   float q[4];

@@ -52,12 +52,8 @@ int bslam_render_surfels(bslam_context* ctx, void* stream_, const bslam_mat3x4* 
   const int pixels = camera->width * camera->height;
   if ((rc = ctx->zbuffer.reserve((size_t)pixels * sizeof(unsigned long long)))) return rc;
   unsigned long long* keys = (unsigned long long*)ctx->zbuffer.ptr;
-  RenderRows rows;
-  rows.x = surfel_row(surfels, BSLAM_SURFEL_X); rows.y = surfel_row(surfels, BSLAM_SURFEL_Y); rows.z = surfel_row(surfels, BSLAM_SURFEL_Z);
-  rows.normal = (const uint32_t*)surfel_row(surfels, BSLAM_SURFEL_NORMAL);
-  rows.radius_squared = surfel_row(surfels, BSLAM_SURFEL_RADIUS_SQUARED);
-  rows.color = (const uint32_t*)surfel_row(surfels, BSLAM_SURFEL_COLOR);
-  rows.size = surfels_size;
+  const SurfelRowsAll all = surfel_rows_all(surfels);   // the descriptor rows may lie beyond this buffer: their addresses are not used
+  const RenderRows rows{all.x, all.y, all.z, all.normal, all.radius_squared, all.color, surfels_size};
   hipLaunchKernelGGL(render_clear_kernel, flat_grid((size_t)pixels), dim3(256), 0, stream, keys, pixels);
   if (surfels_size > 0)
     hipLaunchKernelGGL(render_splat_kernel, flat_grid((size_t)surfels_size), dim3(256), 0, stream, rows, *camera_T_global, *camera, min_depth, max_depth,

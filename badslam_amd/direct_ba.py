@@ -61,6 +61,7 @@ def host_lib():
     L.bsh_create_surfels_for_keyframe.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.bsh_depth_camera_size.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     L.bsh_render_model.argtypes = [C.c_void_p, C.c_void_p, f32p, f32p, C.c_int, C.c_int, f32p, u16p, C.POINTER(C.c_uint32), u8p, f32p, f32p]
+    L.bsh_render_volume.argtypes = [C.c_void_p, C.c_void_p, f32p, f32p, C.c_int, C.c_int, f32p, C.c_uint32, u16p, u8p, f32p, f32p]
     L.bsh_set_allreduce.argtypes = [C.c_void_p, abi.ALLREDUCE_FN, C.c_void_p]
     L.bsh_comm_init.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
     L.bsh_comm_destroy.argtypes = [C.c_void_p]
@@ -680,6 +681,36 @@ class DirectBA:
         self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), _f(tsdf), count.ctypes.data_as(C.POINTER(C.c_uint32)),
                                       color.ctypes.data_as(C.POINTER(C.c_uint8))))
         return dict(origin=fl[:3].copy(), voxel_size=float(fl[3]), truncation=float(fl[4]), dims=(nx, ny, nz), tsdf=tsdf, count=count, color=color)
+
+    def RenderVolume(self, global_T_camera, camera=None, min_depth=0.05, max_depth=50.0, step=None, min_count=1, views=("depth", "color")):
+        """Views of the volume of the last FuseKeyframes from the pose global_T_camera (abi.SE3f) with `camera` (abi.Camera4f,
+        pixel-corner; default: the depth camera): per pixel the first front-facing zero crossing of the interpolated volume along
+        the ray, sampled every `step` metres of depth (default: the voxel size; at most 65536 steps) between min_depth and
+        max_depth, over the samples seen by at least min_count keyframes.  Returns the dict of RenderModel with the entries named
+        in `views` -- "depth" (h, w) uint16, "color" (h, w, 4) uint8, "normal" (h, w, 3) float32 in the camera frame, 0 where
+        nothing is hit -- and "global_T_camera" (3, 4) float32, the matrix the kernel took.  Raises if nothing was fused."""
+        unknown = set(views) - {"depth", "color", "normal"}
+        if unknown or not views:
+            raise ValueError(f"views must name some of depth, color, normal (got {sorted(views)})")
+        if camera is None:
+            size = (C.c_int * 2)()
+            self._check(self.L.bsh_depth_camera_size(self._ba, size))
+            params, w, h = self.intrinsics()[1], size[0], size[1]
+        else:
+            params, w, h = np.array([camera.fx, camera.fy, camera.cx, camera.cy], np.float32), int(camera.width), int(camera.height)
+        out = {}
+        if "depth" in views:
+            out["depth"] = np.zeros((h, w), np.uint16)
+        if "color" in views:
+            out["color"] = np.zeros((h, w, 4), np.uint8)
+        if "normal" in views:
+            out["normal"] = np.zeros((h, w, 3), np.float32)
+        out["global_T_camera"] = np.zeros((3, 4), np.float32)
+        ptr = lambda name, ctype: out[name].ctypes.data_as(C.POINTER(ctype)) if name in out else None
+        options = np.array([min_depth, max_depth, 0.0 if step is None else step], np.float32)
+        self._check(self.L.bsh_render_volume(self._ba, self.stream, _f(pose7(global_T_camera)), _f(np.ascontiguousarray(params, np.float32)), w, h, _f(options),
+                                             int(min_count), ptr("depth", C.c_uint16), ptr("color", C.c_uint8), ptr("normal", C.c_float), _f(out["global_T_camera"])))
+        return out
 
     def upload_keyframe_depth(self, kf_id, depth):
         d = np.ascontiguousarray(depth, np.uint16)

@@ -189,6 +189,24 @@ int bsh_render_model(void* ba, void* stream, const float* global_T_camera_pose7,
     if (camera_T_global) std::memcpy(camera_T_global, v.camera_T_global.m, sizeof(v.camera_T_global.m));
   });
 }
+// DirectBA::RenderVolume.  camera as in bsh_render_model; options3: min_depth, max_depth, step (0: the voxel size).  Each output
+// is a row-major host image of the camera's size, or null for a view that is not wanted; global_T_camera (12 floats, may be
+// null) receives the matrix the kernel took.
+int bsh_render_volume(void* ba, void* stream, const float* global_T_camera_pose7, const float* camera_params4, int width, int height, const float* options3,
+                      uint32_t min_count, uint16_t* depth, uint8_t* color, float* normal, float* global_T_camera) {
+  BSH_TRY({
+    DirectBA::VolumeViewOptions o;
+    o.min_depth = options3[0]; o.max_depth = options3[1]; o.step = options3[2];
+    o.min_count = min_count;
+    o.depth = depth != nullptr; o.color = color != nullptr; o.normal = normal != nullptr;
+    DirectBA::ModelViews v;
+    static_cast<DirectBA*>(ba)->RenderVolume(static_cast<hipStream_t>(stream), pose_from7(global_T_camera_pose7), PinholeCamera4f(width, height, camera_params4), o, &v);
+    if (depth) std::memcpy(depth, v.depth.data(), v.depth.size() * sizeof(uint16_t));
+    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
+    if (normal) std::memcpy(normal, v.normal.data(), v.normal.size() * sizeof(float));
+    if (global_T_camera) std::memcpy(global_T_camera, v.global_T_camera.m, sizeof(v.global_T_camera.m));
+  });
+}
 // DirectBA::ModelBounds.  bounds6: min x y z, max x y z; returns 1 when there is a valid surfel, 0 when none, -1 on error.
 int bsh_model_bounds(void* ba, void* stream, float* bounds6) {
   try { return static_cast<DirectBA*>(ba)->ModelBounds(static_cast<hipStream_t>(stream), bounds6, bounds6 + 3) ? 1 : 0; }

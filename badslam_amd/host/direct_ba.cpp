@@ -504,6 +504,7 @@ void DirectBA::FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float t
   const bslam_volume vol = VolumePod(spec);
   const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
   volume_spec_ = VolumeSpec();   // no volume until the call has gone through
+  volume_aux_min_count_ = 0;     // RenderVolume prepares its aux buffer again
   Check(bslam_fuse_keyframes(ctx_, stream, &color_cam, &depth_cam, &dp, static_cast<int>(views.size()), views.data(), &vol, truncation, &tsdf, &count, &color),
         "bslam_fuse_keyframes");
   volume_spec_ = spec;
@@ -535,6 +536,53 @@ void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) {
   normals.Download(stream, mesh->normals.data(), mesh->normals.size() * sizeof(float));
   colors.Download(stream, mesh->colors.data(), mesh->colors.size() * sizeof(uchar4_t));
   if (triangles) indices.Download(stream, mesh->indices.data(), mesh->indices.size() * sizeof(u32));
+}
+
+void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
+  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("RenderVolume: no fused volume (call FuseKeyframes first)");
+  const int w = camera.width(), h = camera.height();
+  if (w <= 0 || h <= 0) throw std::invalid_argument("RenderVolume: the camera has no pixels");
+  if (!options.depth && !options.color && !options.normal) throw std::invalid_argument("RenderVolume: no view was asked for");
+  if (options.min_count < 1) throw std::invalid_argument("RenderVolume: min_count must be >= 1");
+  const bslam_volume vol = VolumePod(volume_spec_);
+  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), volume_color = volume_color_->ToPod();
+  size_t aux_bytes = 0;
+  Check(bslam_volume_views_aux_bytes(&vol, &aux_bytes), "bslam_volume_views_aux_bytes");
+  constexpr size_t kAuxRow = size_t{1} << 20;   // the aux bytes as rows of 1 MiB
+  const int aux_rows = static_cast<int>((aux_bytes + kAuxRow - 1) / kAuxRow);
+  if (!volume_aux_ || volume_aux_->height() != aux_rows) {
+    volume_aux_.reset();
+    volume_aux_min_count_ = 0;
+    volume_aux_.reset(new DeviceBuffer<u8>(aux_rows, static_cast<int>(kAuxRow)));
+  }
+  if (volume_aux_min_count_ != options.min_count) {
+    volume_aux_min_count_ = 0;
+    Check(bslam_prepare_volume_views(ctx_, stream, &vol, &tsdf, &count, options.min_count, volume_aux_->address(), static_cast<size_t>(aux_rows) * volume_aux_->pitch()),
+          "bslam_prepare_volume_views");
+    volume_aux_min_count_ = options.min_count;
+  }
+  const auto fits = [w, h](int bw, int bh, int elems) { return bw == w * elems && bh == h; };
+  if (options.depth && !(render_depth_ && fits(render_depth_->width(), render_depth_->height(), 1))) render_depth_.reset(new DeviceBuffer<u16>(h, w));
+  if (options.color && !(render_color_ && fits(render_color_->width(), render_color_->height(), 1))) render_color_.reset(new DeviceBuffer<uchar4_t>(h, w));
+  if (options.normal && !(render_normal_ && fits(render_normal_->width(), render_normal_->height(), 3))) render_normal_.reset(new DeviceBuffer<float>(h, 3 * w));
+  bslam_buffer2d depth, color, normal;
+  if (options.depth) depth = render_depth_->ToPod();
+  if (options.color) color = render_color_->ToPod();
+  if (options.normal) { normal = render_normal_->ToPod(); normal.width = w; }   // 12 bytes per pixel
+  const bslam_camera4f cam = camera.pod();
+  views->width = w;
+  views->height = h;
+  views->global_T_camera = global_T_camera.Matrix3x4();
+  views->camera_T_global = global_T_camera.Inverse().Matrix3x4();
+  Check(bslam_raycast_volume(ctx_, stream, &vol, &tsdf, &volume_color, volume_aux_->address(), &views->global_T_camera, &cam, options.min_depth, options.max_depth,
+                             options.step > 0.f ? options.step : volume_spec_.voxel_size, 1.0f / raw_to_float_depth_, options.depth ? &depth : nullptr,
+                             options.color ? &color : nullptr, options.normal ? &normal : nullptr),
+        "bslam_raycast_volume");
+  const size_t pixels = static_cast<size_t>(w) * h;
+  views->depth.clear(); views->index.clear(); views->color.clear(); views->normal.clear();
+  if (options.depth) { views->depth.resize(pixels); render_depth_->Download(stream, views->depth.data(), static_cast<size_t>(w) * sizeof(u16)); }
+  if (options.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), static_cast<size_t>(w) * sizeof(uchar4_t)); }
+  if (options.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), static_cast<size_t>(w) * 3 * sizeof(float)); }
 }
 
 void DirectBA::Volume(hipStream_t stream, VolumeData* volume) const {

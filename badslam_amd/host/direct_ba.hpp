@@ -219,6 +219,7 @@ class DirectBA {
     std::vector<u32> index;       // 0xFFFFFFFF: nothing drawn
     std::vector<uchar4_t> color;
     std::vector<float> normal;    // 3 per pixel, camera frame
+    bslam_mat3x4 global_T_camera; // set by RenderVolume only: the matrix its kernel took
   };
   void RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views);
 
@@ -249,6 +250,18 @@ class DirectBA {
   void FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation);
   void ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh);   // of the volume of the last FuseKeyframes
   void Volume(hipStream_t stream, VolumeData* volume) const;         // download of that volume
+  // Views of the volume of the last FuseKeyframes from a pose (bslam_raycast_volume): per pixel the first front-facing zero
+  // crossing of the trilinear interpolant along the ray, as depth (units of a keyframe's depth image), colour and normal -- no
+  // holes where surfels are sparse, comparable pixel by pixel with a keyframe's depth image.  Samples seen by fewer than
+  // min_count keyframes are unobserved.  The object owns the prepared aux buffer and prepares it again only after a new fusion
+  // or for a new min_count; the device images are those of RenderModel.  Throws std::logic_error if nothing was fused.
+  struct VolumeViewOptions {
+    float min_depth = 0.05f, max_depth = 50.f;   // metres of depth; at most 65536 steps between them
+    float step = 0.f;                            // metres of depth between samples; 0: the voxel size
+    u32 min_count = 1;
+    bool depth = true, color = true, normal = false;   // the views wanted, at least one
+  };
+  void RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views);
   // Axis-aligned box of the valid (non-NaN) surfels; false when there is none.
   bool ModelBounds(hipStream_t stream, float min[3], float max[3]) const;
 
@@ -412,6 +425,9 @@ class DirectBA {
   std::unique_ptr<DeviceBuffer<uchar4_t>> volume_color_;
   VolumeSpec volume_spec_;
   float volume_truncation_ = 0.f;
+  // prepared aux buffer of RenderVolume and the min_count it was prepared for (0: stale -- a new fusion, or never prepared)
+  std::unique_ptr<DeviceBuffer<u8>> volume_aux_;
+  u32 volume_aux_min_count_ = 0;
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

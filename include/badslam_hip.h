@@ -657,6 +657,48 @@ int bslam_extract_mesh(bslam_context* ctx, void* stream, const bslam_volume* vol
                        uint32_t triangle_capacity, float* positions, float* normals, void* colors, uint32_t* indices,
                        uint32_t* vertex_count, uint32_t* triangle_count);
 
+/* Surface views: a per-pixel ray-cast of a fused volume (depth, colour and normal from a pose, without the holes of the disc
+ * view where surfels are sparse).  All arithmetic is fp32 in a fixed expression order with explicit fused multiply-adds
+ * (csrc/raycast_kernels.hpp, DESIGN.md 8 "Surface views"); two calls give identical bits.  With G = global_T_camera,
+ * inv_voxel = fl(1 / voxel_size) and lerp(a, b, w) = fmaf(w, b - a, a):
+ *   pixel (i, j):  dx = ((float(i) + 0.5f) - cx) / fx, dy alike (the expressions of bslam_render_surfels)
+ *   sample k:      t = fmaf(float(k), step, min_depth) for k = 0 .. N - 1, N = the number of k with t <= max_depth;
+ *                  P.a = fmaf(G[a][2], t, fmaf(G[a][1], dy * t, fmaf(G[a][0], dx * t, G[a][3])));
+ *                  g.a = (P.a - origin.a) * inv_voxel - 0.5f;  c.a = floorf(g.a);  f.a = g.a - c.a
+ *   in range iff g.a >= 0 and c.a <= n.a - 2 on all axes (as floats).  Cell c is valid iff its 8 corner samples have
+ *   count >= min_count; a sample is valid iff it is in range and its cell is valid.  Its value F is the trilinear interpolation
+ *   of the corners D[dz][dy][dx] as seven nested lerps: the four x-edges (dy, dz) = (0,0), (1,0), (0,1), (1,1) with f.x, the
+ *   two pairs (0,0)-(1,0), (0,1)-(1,1) with f.y, then f.z.
+ *   The ray ends at the first k whose sample is valid with F_k < 0.  It is a hit iff k >= 1, sample k - 1 is valid and
+ *   F_{k-1} >= 0:  t* = t_{k-1} + step * (F_{k-1} / (F_{k-1} - F_k)).  Otherwise, and when no k ends the ray, the pixel is
+ *   empty: surfaces seen from behind, entered from unobserved space or beginning inside are not drawn.
+ * Outputs as bslam_render_surfels has them (each optional, at least one; empty pixels are 0):
+ *   out_depth   u16     v = metres_to_depth * t* + 0.5f;  v < 65536 ? (u16)v : 0
+ *   out_normal  12 B    the gradient of the interpolant in the cell of P(t*) if that cell is valid, else in the cell of sample
+ *                       k (differences of the face lerps; towards free space), rotated into the camera frame and divided by
+ *                       its sqrtf length; 0 for a zero gradient
+ *   out_color   uchar4  in that same cell, over the corners whose colour sample has alpha 255, in corner order, with the
+ *                       trilinear weights w = (wx * wy) * wz:  {u8(sum(w * ch) / sum(w) + 0.5f) per channel, 255}; 0 when
+ *                       sum(w) is not > 0 or `color` is null
+ * The march needs a prepared aux buffer of the caller's: bslam_volume_views_aux_bytes gives its size (8 byte aligned device
+ * memory), bslam_prepare_volume_views fills it for one (tsdf, count, min_count) -- a validity bit per cell and a flag per
+ * block of 8 x 8 x 8 cells that is set iff the block holds a valid cell with a corner < 0 -- and bslam_raycast_volume reads
+ * it; the library caches nothing about it, so prepare again when the volume or min_count changes.  A sample in an unflagged
+ * block cannot end a ray (nested lerps with weights in [0, 1) over corners none of which is < 0 are never < 0) and is passed
+ * after one test; bslam_set_culling switches that test, with identical output bits, and while profiling is on
+ * bslam_debug_cull_stats counts the in-range samples that reached the test and those it skipped.
+ * Refused: null arguments, no output, step / depths / metres_to_depth / voxel_size not finite and > 0, min_depth >=
+ * max_depth, N > 65536, min_count < 1, outputs that are misaligned or overlap each other, the volume or the aux buffer, an
+ * aux buffer that is misaligned or too small, and what bslam_extract_mesh refuses of a volume.
+ * Launched on `stream` without synchronisation.  Every rank of a surfel-sharded run holds the same volume. */
+int bslam_volume_views_aux_bytes(const bslam_volume* volume, size_t* bytes);
+int bslam_prepare_volume_views(bslam_context* ctx, void* stream, const bslam_volume* volume, const bslam_buffer2d* tsdf,
+                               const bslam_buffer2d* count, uint32_t min_count, void* aux, size_t aux_bytes);
+int bslam_raycast_volume(bslam_context* ctx, void* stream, const bslam_volume* volume, const bslam_buffer2d* tsdf,
+                         const bslam_buffer2d* color /* may be null */, const void* aux, const bslam_mat3x4* global_T_camera,
+                         const bslam_camera4f* camera, float min_depth, float max_depth, float step, float metres_to_depth,
+                         const bslam_buffer2d* out_depth, const bslam_buffer2d* out_color, const bslam_buffer2d* out_normal);
+
 /* Place recognition (in place of the FAST + BRIEF + DBoW2 half of vis::LoopDetector::AddImage, BS/loop_detector.cc:98-127,
  * 160-167): one Harris corner with an unoriented 256-bit BRIEF descriptor per cell of 16 x 16 pixels of a keyframe.  All
  * arithmetic is integer (csrc/place_kernels.hpp, DESIGN.md 8 "Place recognition"); two calls give identical bits.

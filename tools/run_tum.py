@@ -7,6 +7,7 @@ has a ground truth, prints the ATE RMSE.
                             [--ba-iterations 10] [--max-depth 3.0] [--end-frame N] [--ba-cost]
                             [--pyramid-level-for-depth L] [--pyramid-level-for-color L]
                             [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
+                            [--render-source {surfels,volume}]
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--point-cloud PATH]
 
@@ -27,6 +28,9 @@ the dataset reader loads back: depth/<timestamp>.png (16-bit, the units of the i
 calibration.txt and groundtruth.txt (the keyframe poses the views were rendered from).  --render-radius-scale S: the discs are
 drawn with S times the surfels' radii; the default is the sparse surfel cell size of the run (4), because a surfel stands for a
 cell of that many pixels a side while its radius is that of one pixel, so that scale closes the gaps between neighbours.
+--render-source volume: the views are ray-cast from the fused surface instead of drawn from the discs (DirectBA.RenderVolume):
+the keyframes are fused once with the --mesh-* options, whether or not --mesh is given, and every view is sampled at the voxel
+size up to --max-depth.  The directory has the same layout.
 
 --mesh PATH: after the last BA, all keyframes are fused into a truncated signed distance volume at their optimised poses
 (DirectBA.FuseKeyframes) over the box of the surfel model (DirectBA.ModelBounds) padded by the truncation, and its surface
@@ -67,9 +71,12 @@ def check_level_fits(width, height, level):
         raise ValueError(f"pyramid level {level} does not fit a {width}x{height} dataset: levels are 0 ... 3 and the size must be divisible by 2^level")
 
 
-def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0):
+def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0, source="surfels", max_depth=50.0, min_count=1):
     """Writes the model views from the poses of keyframes[::every] -- (keyframe id, timestamp string) pairs -- as a TUM-style
-    directory; deleted keyframes are left out.  Returns the (keyframe id, timestamp) pairs written."""
+    directory; deleted keyframes are left out.  source "surfels": RenderModel; "volume": RenderVolume of the fused volume, up to
+    max_depth and over the samples at least min_count keyframes saw.  Returns the (keyframe id, timestamp) pairs written."""
+    if source not in ("surfels", "volume"):
+        raise ValueError("--render-source must be surfels or volume")
     if every < 1:
         raise ValueError("--render-every must be at least 1")
     os.makedirs(os.path.join(str(render_dir), "depth"), exist_ok=True)
@@ -80,7 +87,10 @@ def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0):
         if ba.keyframe_is_deleted(kf_id):
             continue
         pose = ba.keyframe_pose(kf_id)
-        views = ba.RenderModel(pose, radius_scale=radius_scale, views=("depth", "color"))
+        if source == "volume":
+            views = ba.RenderVolume(pose, max_depth=max_depth, min_count=min_count, views=("depth", "color"))
+        else:
+            views = ba.RenderModel(pose, radius_scale=radius_scale, views=("depth", "color"))
         png.write_png(os.path.join(str(render_dir), "depth", f"{ts}.png"), views["depth"])
         png.write_png(os.path.join(str(render_dir), "rgb", f"{ts}.png"), np.ascontiguousarray(views["color"][:, :, :3]))
         associated.append(f"{ts} rgb/{ts}.png {ts} depth/{ts}.png")
@@ -113,14 +123,21 @@ def mesh_volume(bounds_min, bounds_max, voxel_size, truncation):
     return lo.astype(np.float32), dims
 
 
-def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1):
-    """FuseKeyframes over the padded ModelBounds, ExtractMesh, SaveMeshAsPLY -> (mesh dict, origin, dims)."""
+def fuse_model(ba, voxel_size=0.01, truncation=None):
+    """FuseKeyframes over the padded ModelBounds -> (origin, dims)."""
     truncation = 4 * voxel_size if truncation is None else truncation
     bounds = ba.ModelBounds()
     if bounds is None:
-        raise ValueError("--mesh: the model has no surfels to take the volume's bounds from")
+        raise ValueError("--mesh / --render-source volume: the model has no surfels to take the volume's bounds from")
     origin, dims = mesh_volume(bounds[0], bounds[1], voxel_size, truncation)
     ba.FuseKeyframes(origin, voxel_size, dims, truncation)
+    return origin, dims
+
+
+def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1, fused=None):
+    """FuseKeyframes over the padded ModelBounds (unless `fused`, the (origin, dims) of fuse_model, says it was done), ExtractMesh,
+    SaveMeshAsPLY -> (mesh dict, origin, dims)."""
+    origin, dims = fused if fused is not None else fuse_model(ba, voxel_size, truncation)
     mesh = ba.ExtractMesh(min_count)
     dba.SaveMeshAsPLY(path, mesh)
     return mesh, origin, dims
@@ -129,7 +146,8 @@ def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1):
 def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterations=10, max_depth=3.0, end_frame=None, raw_to_float_depth=1.0 / 5000,
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
-        place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None):
+        place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
+        render_source="surfels"):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -164,15 +182,20 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     result.update({"frames": len(frames), "keyframes": slam.ba().keyframe_count(), "surfels": slam.ba().surfels_size(), "poses_file": out})
     if place_recognition:
         result["place_recognition"] = slam.place_recognition_log()
+    fused = None
     if render_dir:
-        result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, float(render_radius_scale or cell))
+        if render_source == "volume":
+            fused = fuse_model(slam.ba(), mesh_voxel_size, mesh_truncation)
+            result["volume"] = {"origin": fused[0], "dims": fused[1]}
+        result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, float(render_radius_scale or cell), render_source, max_depth,
+                                              mesh_min_count)
         result["render_dir"] = str(render_dir)
     if point_cloud:
         positions, colors, normals = slam.ba().ExportToPointCloud()
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh:
-        m, origin, dims = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count)
+        m, origin, dims = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused)
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
     if inspect:
         inspect(slam, result)
@@ -197,6 +220,7 @@ def arg_parser():
     ap.add_argument("--render-dir", default=None)
     ap.add_argument("--render-every", type=int, default=1)
     ap.add_argument("--render-radius-scale", type=float, default=None)
+    ap.add_argument("--render-source", choices=("surfels", "volume"), default="surfels")
     ap.add_argument("--place-recognition", action="store_true")
     ap.add_argument("--place-min-gap", type=int, default=10)
     ap.add_argument("--mesh", default=None)
@@ -213,7 +237,8 @@ def main():
             pyramid_level_for_depth=a.pyramid_level_for_depth, pyramid_level_for_color=a.pyramid_level_for_color,
             median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
             render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap, mesh=a.mesh,
-            mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud)
+            mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
+            render_source=a.render_source)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")

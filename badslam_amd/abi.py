@@ -119,6 +119,9 @@ SIGNATURES = {
     "bslam_fuse_keyframes": (C.c_int, [C.c_void_p, C.c_void_p, _CAM, _CAM, _DP, C.c_int, _KFS, P(Volume), C.c_float, _BUF, _BUF, _BUF]),
     "bslam_extract_mesh": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, _BUF, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
+    "bslam_mesh_components": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]),
+    "bslam_filter_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "bslam_volume_views_aux_bytes": (C.c_int, [P(Volume), P(C.c_size_t)]),
     "bslam_prepare_volume_views": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, C.c_uint32, C.c_void_p, C.c_size_t]),
     "bslam_raycast_volume": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, C.c_void_p, P(Mat3x4), _CAM, C.c_float, C.c_float, C.c_float, C.c_float,

@@ -19,6 +19,7 @@
 #include "rectify_kernels.hpp"
 #include "render_kernels.hpp"
 #include "fusion_kernels.hpp"
+#include "mesh_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1400,6 +1401,7 @@ int bslam_debug_pose_residuals(
 #include "rectify_abi.inc"
 #include "render_abi.inc"
 #include "fusion_abi.inc"
+#include "mesh_abi.inc"
 #include "raycast_abi.inc"
 #include "place_abi.inc"
 #include "odometry_abi.inc"

@@ -159,7 +159,8 @@ struct bslam_context {
                              // uint64[h][w]: (float bits of the depth << 32) | surfel index (bslam_render_surfels)
   bslam::Slab place_pattern; // uint32[256]: the BRIEF point pairs of bslam_extract_keyframe_features, uploaded by its first call
   bool place_pattern_ready = false;
-  bslam::Slab fusion;        // bslam_extract_mesh: active flags and quad counts u8[cells], vertex ids and quad offsets u32[cells], scan sums
+  bslam::Slab fusion;        // bslam_extract_mesh: active flags and quad counts u8[cells], vertex ids and quad offsets u32[cells], scan sums;
+                             // bslam_mesh_components: parent and root sizes u32[V]; bslam_filter_mesh: keep flags, ranks, scan sums
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

@@ -1,0 +1,132 @@
+// mesh_abi.inc -- mesh component entry points of include/badslam_hip.h (included by badslam_hip.hip after lifecycle_abi.inc,
+// preprocess_abi.inc and fusion_abi.inc: device_scan, flat_grid, the fusion slab).
+
+namespace bslam {
+
+// A flat device array of `bytes` bytes a mesh call reads or writes.
+struct MeshSpan { const void* ptr; size_t bytes; const char* name; bool output; };
+
+// Every non-empty array is non-null and 4 byte aligned; no output overlaps an input or another output.
+static int check_mesh_spans(const MeshSpan* spans, int count) {
+  for (int i = 0; i < count; ++i) {
+    if (spans[i].bytes == 0) continue;
+    if (!spans[i].ptr) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s is null", spans[i].name);
+    if ((uintptr_t)spans[i].ptr % 4 != 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s must be 4 byte aligned", spans[i].name);
+  }
+  for (int i = 0; i < count; ++i) {
+    for (int j = i + 1; j < count; ++j) {
+      if (!(spans[i].output || spans[j].output) || spans[i].bytes == 0 || spans[j].bytes == 0) continue;
+      const uintptr_t a0 = (uintptr_t)spans[i].ptr, b0 = (uintptr_t)spans[j].ptr;
+      if (a0 < b0 + spans[j].bytes && b0 < a0 + spans[i].bytes) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s and %s overlap", spans[i].name, spans[j].name);
+    }
+  }
+  return BSLAM_OK;
+}
+
+static int mesh_error(uint32_t bits, const char* call) {
+  if (bits & kMeshBadIndex) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a triangle names a vertex beyond vertex_count", call);
+  if (bits & kMeshOverrun) return fail(BSLAM_ERR_INTERNAL, "%s: a union-find loop ran into its cap", call);
+  return BSLAM_OK;
+}
+
+}  // namespace bslam
+
+extern "C" {
+
+int bslam_mesh_components(bslam_context* ctx, void* stream_, uint32_t vertex_count, uint32_t triangle_count, const uint32_t* indices, uint32_t* labels,
+                          uint32_t* sizes, uint32_t* component_count) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx || !component_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  const size_t V = vertex_count, T = triangle_count;
+  const MeshSpan spans[3] = {{indices, 12 * T, "indices", false}, {labels, 4 * V, "labels", true}, {sizes, 4 * V, "sizes", true}};
+  int rc = check_mesh_spans(spans, 3);
+  if (rc) return rc;
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  if (V == 0) {   // no vertex: any triangle names one that does not exist
+    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+    if (T != 0) return mesh_error(kMeshBadIndex, "bslam_mesh_components");
+    *component_count = 0;
+    return BSLAM_OK;
+  }
+  // scratch: parent u32[V] | size_of_root u32[V] | words u32[2] = {error bits, component count}
+  if ((rc = ctx->fusion.reserve((2 * V + 16) * sizeof(uint32_t)))) return rc;
+  uint32_t* parent = (uint32_t*)ctx->fusion.ptr;
+  uint32_t* size_of_root = parent + V;
+  uint32_t* words = size_of_root + V;
+  const dim3 block(256);
+  hipLaunchKernelGGL(mesh_init_kernel, flat_grid(V), block, 0, stream, vertex_count, parent, size_of_root, words);
+  BSLAM_HIP_TRY(hipGetLastError());
+  if (T != 0) {
+    hipLaunchKernelGGL(mesh_seed_kernel, flat_grid(T), block, 0, stream, vertex_count, triangle_count, indices, parent, words);
+    BSLAM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mesh_compress_kernel, flat_grid(V), block, 0, stream, vertex_count, parent, words);
+    BSLAM_HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(mesh_union_kernel, flat_grid(T), block, 0, stream, vertex_count, triangle_count, indices, parent, words, cull_stats_ptr(ctx));
+    BSLAM_HIP_TRY(hipGetLastError());
+  }
+  hipLaunchKernelGGL(mesh_flatten_kernel, flat_grid(V), block, 0, stream, vertex_count, (const uint32_t*)parent, labels, size_of_root, words);
+  BSLAM_HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(mesh_sizes_kernel, flat_grid(V), block, 0, stream, vertex_count, (const uint32_t*)labels, (const uint32_t*)size_of_root, sizes);
+  BSLAM_HIP_TRY(hipGetLastError());
+  const uint32_t* host = nullptr;
+  if ((rc = read_back(ctx, stream, (const uint32_t*)words, 2, &host))) return rc;
+  if ((rc = mesh_error(host[0], "bslam_mesh_components"))) return rc;
+  *component_count = host[1];
+  return BSLAM_OK;
+}
+
+int bslam_filter_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, uint32_t triangle_count, const float* positions, const float* normals,
+                      const void* colors, const uint32_t* indices, const uint32_t* sizes, uint32_t min_vertices, float* out_positions, float* out_normals,
+                      void* out_colors, uint32_t* out_indices, uint32_t* out_vertex_count, uint32_t* out_triangle_count) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (!ctx || !out_vertex_count || !out_triangle_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  if (min_vertices < 1) return fail(BSLAM_ERR_INVALID_ARGUMENT, "min_vertices must be >= 1");
+  if ((normals != nullptr) != (out_normals != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_normals must be given exactly when normals is");
+  if ((colors != nullptr) != (out_colors != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_colors must be given exactly when colors is");
+  const size_t V = vertex_count, T = triangle_count;
+  const MeshSpan spans[9] = {{positions, 12 * V, "positions", false}, {normals, normals ? 12 * V : 0, "normals", false}, {colors, colors ? 4 * V : 0, "colors", false},
+                             {indices, 12 * T, "indices", false}, {sizes, 4 * V, "sizes", false}, {out_positions, 12 * V, "out_positions", true},
+                             {out_normals, normals ? 12 * V : 0, "out_normals", true}, {out_colors, colors ? 4 * V : 0, "out_colors", true},
+                             {out_indices, 12 * T, "out_indices", true}};
+  int rc = check_mesh_spans(spans, 9);
+  if (rc) return rc;
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  if (V == 0) {
+    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+    if (T != 0) return mesh_error(kMeshBadIndex, "bslam_filter_mesh");
+    *out_vertex_count = 0;
+    *out_triangle_count = 0;
+    return BSLAM_OK;
+  }
+  // scratch: keep_vertex u8[V] | keep_triangle u8[T] | vertex_rank u32[V] | triangle_rank u32[T] | tile sums |
+  //          words u32[4] = {error bits, unused, kept vertices, kept triangles}
+  const size_t nv = (V + 63) & ~(size_t)63, nt = (T + 63) & ~(size_t)63, tiles = std::max(nv, nt) / kScanTile + 2;
+  if ((rc = ctx->fusion.reserve(nv + nt + (nv + nt + tiles + 16) * sizeof(uint32_t)))) return rc;
+  uint8_t* keep_vertex = (uint8_t*)ctx->fusion.ptr;
+  uint8_t* keep_triangle = keep_vertex + nv;
+  uint32_t* vertex_rank = (uint32_t*)(keep_triangle + nt);
+  uint32_t* triangle_rank = vertex_rank + nv;
+  uint32_t* tile_sums = triangle_rank + nt;
+  uint32_t* words = tile_sums + tiles;
+  MeshFilter m;
+  m.vertices = vertex_count; m.triangles = triangle_count; m.vertex_blocks = flat_grid(V).x; m.min_vertices = min_vertices;
+  m.positions = positions; m.normals = normals; m.colors = (const uint32_t*)colors; m.indices = indices; m.sizes = sizes;
+  m.out_positions = out_positions; m.out_normals = out_normals; m.out_colors = (uint32_t*)out_colors; m.out_indices = out_indices;
+  const dim3 grid(m.vertex_blocks + flat_grid(T).x), block(256);   // < 2^25 blocks
+  BSLAM_HIP_TRY(hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), stream));
+  hipLaunchKernelGGL(mesh_keep_flags_kernel, grid, block, 0, stream, m, keep_vertex, keep_triangle, words);
+  BSLAM_HIP_TRY(hipGetLastError());
+  if ((rc = device_scan(stream, 0, keep_vertex, vertex_count, true, vertex_rank, tile_sums, words + 2))) return rc;
+  if ((rc = device_scan(stream, 0, keep_triangle, triangle_count, true, triangle_rank, tile_sums, words + 3))) return rc;
+  hipLaunchKernelGGL(mesh_scatter_kernel, grid, block, 0, stream, m, (const uint8_t*)keep_vertex, (const uint8_t*)keep_triangle, (const uint32_t*)vertex_rank,
+                     (const uint32_t*)triangle_rank);
+  BSLAM_HIP_TRY(hipGetLastError());
+  const uint32_t* host = nullptr;
+  if ((rc = read_back(ctx, stream, (const uint32_t*)words, 4, &host))) return rc;
+  if ((rc = mesh_error(host[0], "bslam_filter_mesh"))) return rc;
+  *out_vertex_count = host[2];
+  *out_triangle_count = host[3];
+  return BSLAM_OK;
+}
+
+}  // extern "C"

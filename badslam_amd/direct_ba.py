@@ -79,6 +79,9 @@ def host_lib():
     L.bsh_fuse_keyframes.argtypes = [C.c_void_p, C.c_void_p, f32p, C.c_float, C.POINTER(C.c_int), C.c_float]
     L.bsh_extract_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]
     L.bsh_mesh_copy.argtypes = [f32p, f32p, u8p, u32p]
+    L.bsh_extract_mesh_filtered.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), u32p]
+    L.bsh_mesh_component_sizes.argtypes = [u32p, C.c_uint32]
+    L.bsh_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]
     L.bsh_volume.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), f32p, f32p, u32p, u8p]
     _host = L
     return L
@@ -659,17 +662,41 @@ class DirectBA:
         d = (C.c_int * 3)(*[int(v) for v in dims])
         self._check(self.L.bsh_fuse_keyframes(self._ba, self.stream, _f(o), float(voxel_size), d, float(truncation)))
 
-    def ExtractMesh(self, min_count=1):
+    def ExtractMesh(self, min_count=1, min_component_vertices=0, report=False):
         """Surface nets of the fused volume over the samples seen by at least min_count keyframes: dict of positions (V, 3) f32,
-        normals (V, 3) f32 (towards free space), colors (V, 4) u8, triangles (T, 3) u32 (counter-clockwise seen from free space)."""
+        normals (V, 3) f32 (towards free space), colors (V, 4) u8, triangles (T, 3) u32 (counter-clockwise seen from free space).
+        min_component_vertices >= 2: connected components (vertices joined by a triangle) of fewer vertices are dropped on the
+        device before the download; the rest keeps its order.  report=True: returns (mesh, dict of components, removed_vertices,
+        removed_triangles, sizes_descending -- the vertex count of every component of the mesh as extracted)."""
         counts = (C.c_uint64 * 2)()
-        self._check(self.L.bsh_extract_mesh(self._ba, self.stream, int(min_count), counts))
+        info = None
+        if not report and int(min_component_vertices) < 2:
+            self._check(self.L.bsh_extract_mesh(self._ba, self.stream, int(min_count), counts))
+        else:
+            report3 = (C.c_uint32 * 3)()
+            self._check(self.L.bsh_extract_mesh_filtered(self._ba, self.stream, int(min_count), int(min_component_vertices), counts, report3 if report else None))
+            if report:
+                sizes = np.zeros(report3[0], np.uint32)
+                self._check(self.L.bsh_mesh_component_sizes(sizes.ctypes.data_as(C.POINTER(C.c_uint32)), len(sizes)))
+                info = dict(components=int(report3[0]), removed_vertices=int(report3[1]), removed_triangles=int(report3[2]), sizes_descending=sizes)
         V, T = int(counts[0]), int(counts[1])
         out = dict(positions=np.zeros((V, 3), np.float32), normals=np.zeros((V, 3), np.float32), colors=np.zeros((V, 4), np.uint8),
                    triangles=np.zeros((T, 3), np.uint32))
         self._check(self.L.bsh_mesh_copy(_f(out["positions"]), _f(out["normals"]), out["colors"].ctypes.data_as(C.POINTER(C.c_uint8)),
                                          out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32))))
-        return out
+        return (out, info) if report else out
+
+    def MeshComponents(self, mesh):
+        """Connected components of a mesh dict (positions (V, 3), triangles (T, 3)): vertices are joined iff a triangle holds both.
+        -> (labels (V,) u32: the smallest vertex id of the vertex's component, sizes (V,) u32: its vertex count)."""
+        V = len(mesh["positions"])
+        tri = np.ascontiguousarray(mesh["triangles"], np.uint32).reshape(-1, 3)
+        labels, sizes = np.zeros(V, np.uint32), np.zeros(V, np.uint32)
+        u32p = C.POINTER(C.c_uint32)
+        n = C.c_uint32()
+        self._check(self.L.bsh_mesh_components(self._ba, self.stream, V, len(tri), tri.ctypes.data_as(u32p), labels.ctypes.data_as(u32p), sizes.ctypes.data_as(u32p),
+                                               C.byref(n)))
+        return labels, sizes
 
     def Volume(self):
         """Download of the fused volume: dict of origin (3,), voxel_size, truncation, dims (nx, ny, nz) and the arrays tsdf f32,

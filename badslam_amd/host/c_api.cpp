@@ -233,6 +233,42 @@ int bsh_extract_mesh(void* ba, void* stream, uint32_t min_count, uint64_t* count
     counts2[1] = g_mesh.triangle_count();
   });
 }
+// DirectBA::ExtractMesh with MeshOptions: as bsh_extract_mesh, then bsh_mesh_copy.  report3 (may be null; with it the report is
+// computed and kept for this thread) receives {components, removed vertices, removed triangles} of the mesh as extracted;
+// bsh_mesh_component_sizes then copies out the vertex count of every component in descending order (`components` entries).
+static thread_local DirectBA::MeshComponentReport g_mesh_report;
+int bsh_extract_mesh_filtered(void* ba, void* stream, uint32_t min_count, uint32_t min_component_vertices, uint64_t* counts2, uint32_t* report3) {
+  BSH_TRY({
+    DirectBA::MeshOptions options;
+    options.min_count = min_count;
+    options.min_component_vertices = min_component_vertices;
+    g_mesh_report = DirectBA::MeshComponentReport();
+    static_cast<DirectBA*>(ba)->ExtractMesh(static_cast<hipStream_t>(stream), options, &g_mesh, report3 ? &g_mesh_report : nullptr);
+    counts2[0] = g_mesh.vertex_count();
+    counts2[1] = g_mesh.triangle_count();
+    if (report3) { report3[0] = g_mesh_report.components; report3[1] = g_mesh_report.removed_vertices; report3[2] = g_mesh_report.removed_triangles; }
+  });
+}
+int bsh_mesh_component_sizes(uint32_t* sizes, uint32_t capacity) {
+  BSH_TRY({
+    std::memcpy(sizes, g_mesh_report.sizes_descending.data(), std::min<size_t>(g_mesh_report.sizes_descending.size(), capacity) * sizeof(uint32_t));
+    g_mesh_report = DirectBA::MeshComponentReport();
+  });
+}
+// DirectBA::MeshComponents of a host mesh of `vertices` vertices and `triangles` index triples: labels, sizes (vertices entries
+// each, either may be null) and *components.
+int bsh_mesh_components(void* ba, void* stream, uint32_t vertices, uint32_t triangles, const uint32_t* indices, uint32_t* labels, uint32_t* sizes,
+                        uint32_t* components) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(3 * static_cast<size_t>(vertices), 0.f);
+    mesh.indices.assign(indices, indices + 3 * static_cast<size_t>(triangles));
+    std::vector<uint32_t> l, s;
+    *components = static_cast<DirectBA*>(ba)->MeshComponents(static_cast<hipStream_t>(stream), mesh, labels ? &l : nullptr, sizes ? &s : nullptr);
+    if (labels) std::memcpy(labels, l.data(), l.size() * sizeof(uint32_t));
+    if (sizes) std::memcpy(sizes, s.data(), s.size() * sizeof(uint32_t));
+  });
+}
 int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
   BSH_TRY({
     if (positions) std::memcpy(positions, g_mesh.positions.data(), g_mesh.positions.size() * sizeof(float));

@@ -538,6 +538,101 @@ void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) {
   if (triangles) indices.Download(stream, mesh->indices.data(), mesh->indices.size() * sizeof(u32));
 }
 
+// Component sizes in descending order from per-vertex labels and sizes: one entry per v with label[v] == v.
+static void ComponentSizes(const std::vector<u32>& labels, const std::vector<u32>& sizes, std::vector<u32>* out) {
+  out->clear();
+  for (size_t v = 0; v < labels.size(); ++v)
+    if (labels[v] == v) out->push_back(sizes[v]);
+  std::sort(out->begin(), out->end(), std::greater<u32>());
+}
+
+void DirectBA::ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh* mesh, MeshComponentReport* report) {
+  const bool filter = options.min_component_vertices >= 2;
+  if (!filter && !report) { ExtractMesh(stream, options.min_count, mesh); return; }
+  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("ExtractMesh: no fused volume (call FuseKeyframes first)");
+  const bslam_volume vol = VolumePod(volume_spec_);
+  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
+  u32 vertices = 0, triangles = 0;
+  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, options.min_count, 0, 0, nullptr, nullptr, nullptr, nullptr, &vertices, &triangles),
+        "bslam_extract_mesh");
+  if (report) *report = MeshComponentReport();
+  mesh->positions.clear(); mesh->normals.clear(); mesh->colors.clear(); mesh->indices.clear();
+  if (vertices == 0) return;
+  DeviceBuffer<float> positions(1, static_cast<int>(3 * vertices)), normals(1, static_cast<int>(3 * vertices));
+  DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
+  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1))), labels(1, static_cast<int>(vertices)), sizes(1, static_cast<int>(vertices));
+  u32 v2 = 0, t2 = 0;
+  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, options.min_count, vertices, triangles, positions.address(), normals.address(),
+                           colors.address(), indices.address(), &v2, &t2),
+        "bslam_extract_mesh");
+  if (v2 != vertices || t2 != triangles) throw std::runtime_error("ExtractMesh: the volume changed between the two extraction calls");
+  u32 components = 0;
+  Check(bslam_mesh_components(ctx_, stream, vertices, triangles, indices.address(), labels.address(), sizes.address(), &components), "bslam_mesh_components");
+  u32 kept_vertices = vertices, kept_triangles = triangles;
+  const float* from_positions = positions.address();
+  const float* from_normals = normals.address();
+  const uchar4_t* from_colors = colors.address();
+  const u32* from_indices = indices.address();
+  std::unique_ptr<DeviceBuffer<float>> out_positions, out_normals;
+  std::unique_ptr<DeviceBuffer<uchar4_t>> out_colors;
+  std::unique_ptr<DeviceBuffer<u32>> out_indices;
+  if (filter) {
+    out_positions.reset(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
+    out_normals.reset(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
+    out_colors.reset(new DeviceBuffer<uchar4_t>(1, static_cast<int>(vertices)));
+    out_indices.reset(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
+    Check(bslam_filter_mesh(ctx_, stream, vertices, triangles, positions.address(), normals.address(), colors.address(), indices.address(), sizes.address(),
+                            options.min_component_vertices, out_positions->address(), out_normals->address(), out_colors->address(), out_indices->address(),
+                            &kept_vertices, &kept_triangles),
+          "bslam_filter_mesh");
+    from_positions = out_positions->address(); from_normals = out_normals->address(); from_colors = out_colors->address(); from_indices = out_indices->address();
+  }
+  mesh->positions.resize(3 * static_cast<size_t>(kept_vertices));
+  mesh->normals.resize(3 * static_cast<size_t>(kept_vertices));
+  mesh->colors.resize(kept_vertices);
+  mesh->indices.resize(3 * static_cast<size_t>(kept_triangles));
+  std::vector<u32> host_labels, host_sizes;
+  if (report) { host_labels.resize(vertices); host_sizes.resize(vertices); }
+  // the one download: everything is enqueued, then the stream is waited for once
+  const auto fetch = [stream](void* to, const void* from, size_t bytes) {
+    if (bytes) HIP_OR_THROW(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, stream));
+  };
+  fetch(mesh->positions.data(), from_positions, mesh->positions.size() * sizeof(float));
+  fetch(mesh->normals.data(), from_normals, mesh->normals.size() * sizeof(float));
+  fetch(mesh->colors.data(), from_colors, mesh->colors.size() * sizeof(uchar4_t));
+  fetch(mesh->indices.data(), from_indices, mesh->indices.size() * sizeof(u32));
+  fetch(host_labels.data(), labels.address(), host_labels.size() * sizeof(u32));
+  fetch(host_sizes.data(), sizes.address(), host_sizes.size() * sizeof(u32));
+  HIP_OR_THROW(hipStreamSynchronize(stream));
+  if (report) {
+    report->components = components;
+    report->removed_vertices = vertices - kept_vertices;
+    report->removed_triangles = triangles - kept_triangles;
+    ComponentSizes(host_labels, host_sizes, &report->sizes_descending);
+  }
+}
+
+u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes) {
+  if (mesh.vertex_count() > 0xffffffffull || mesh.triangle_count() > 0xffffffffull || mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0)
+    throw std::invalid_argument("MeshComponents: positions and indices must hold 3 entries per vertex and per triangle, fewer than 2^32 of each");
+  const u32 vertices = static_cast<u32>(mesh.vertex_count()), triangles = static_cast<u32>(mesh.triangle_count());
+  if (labels) labels->assign(vertices, 0u);
+  if (sizes) sizes->assign(vertices, 0u);
+  if (3 * static_cast<uint64_t>(triangles) > 0x7fffffffull || vertices > 0x7fffffffu) throw std::invalid_argument("MeshComponents: the mesh is too large for one device image");
+  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1))), dev_labels(1, static_cast<int>(std::max<u32>(vertices, 1))),
+      dev_sizes(1, static_cast<int>(std::max<u32>(vertices, 1)));
+  if (triangles) {
+    HIP_OR_THROW(hipMemcpyAsync(indices.address(), mesh.indices.data(), mesh.indices.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+  }
+  u32 components = 0;
+  Check(bslam_mesh_components(ctx_, stream, vertices, triangles, indices.address(), dev_labels.address(), dev_sizes.address(), &components), "bslam_mesh_components");
+  if (vertices && labels) HIP_OR_THROW(hipMemcpyAsync(labels->data(), dev_labels.address(), vertices * sizeof(u32), hipMemcpyDeviceToHost, stream));
+  if (vertices && sizes) HIP_OR_THROW(hipMemcpyAsync(sizes->data(), dev_sizes.address(), vertices * sizeof(u32), hipMemcpyDeviceToHost, stream));
+  HIP_OR_THROW(hipStreamSynchronize(stream));
+  return components;
+}
+
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
   if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("RenderVolume: no fused volume (call FuseKeyframes first)");
   const int w = camera.width(), h = camera.height();

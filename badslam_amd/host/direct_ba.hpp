@@ -249,6 +249,23 @@ class DirectBA {
   };
   void FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation);
   void ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh);   // of the volume of the last FuseKeyframes
+  // Extraction with clean-up (bslam_mesh_components, bslam_filter_mesh): the extracted mesh stays on the device, is labelled by
+  // connected component -- vertices are joined iff a triangle holds both -- and, from min_component_vertices = 2 on, loses every
+  // component of fewer vertices (flying pixels at occlusion edges, single noisy blobs) before the one download; the kept
+  // vertices and triangles keep their order.  With min_component_vertices 0 or 1 and no report this is ExtractMesh(stream,
+  // min_count, mesh): nothing else is launched.  The report describes the mesh as extracted, before anything was dropped.
+  struct MeshOptions {
+    u32 min_count = 1;
+    u32 min_component_vertices = 0;
+  };
+  struct MeshComponentReport {
+    u32 components = 0, removed_vertices = 0, removed_triangles = 0;
+    std::vector<u32> sizes_descending;   // vertices per component
+  };
+  void ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh* mesh, MeshComponentReport* report = nullptr);
+  // Components of a caller's mesh: labels[v] = the smallest vertex id of v's component, sizes[v] = its vertex count (either may
+  // be null).  Returns the number of components.
+  u32 MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes);
   void Volume(hipStream_t stream, VolumeData* volume) const;         // download of that volume
   // Views of the volume of the last FuseKeyframes from a pose (bslam_raycast_volume): per pixel the first front-facing zero
   // crossing of the trilinear interpolant along the ray, as depth (units of a keyframe's depth image), colour and normal -- no

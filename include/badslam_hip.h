@@ -67,7 +67,8 @@ typedef enum bslam_status {
   BSLAM_ERR_INVALID_ARGUMENT = -1,  /* a reference CHECK() would have fired */
   BSLAM_ERR_HIP = -2,               /* a HIP runtime call failed */
   BSLAM_ERR_NO_DEVICE = -3,         /* no gfx950 device visible */
-  BSLAM_ERR_OUT_OF_MEMORY = -4
+  BSLAM_ERR_OUT_OF_MEMORY = -4,
+  BSLAM_ERR_INTERNAL = -5           /* a device-side loop ran into its iteration cap: a bug in the library, never the caller's input */
 } bslam_status;
 
 /* ------------------------------------------------------------------------- */
@@ -656,6 +657,42 @@ int bslam_extract_mesh(bslam_context* ctx, void* stream, const bslam_volume* vol
                        const bslam_buffer2d* count, const bslam_buffer2d* color, uint32_t min_count, uint32_t vertex_capacity,
                        uint32_t triangle_capacity, float* positions, float* normals, void* colors, uint32_t* indices,
                        uint32_t* vertex_count, uint32_t* triangle_count);
+
+/* Mesh components: an indexed triangle mesh as a graph (DESIGN.md 8 "Mesh components", csrc/mesh_kernels.hpp).  The input has
+ * V vertices, T triangles and indices uint32[3 T]; it may come from bslam_extract_mesh or from anywhere else.
+ * Components:
+ *   Vertices a and b are joined iff some triangle contains both.  Degenerate triangles such as (a, a, b) and (a, a, a) are
+ *   legal, duplicated triangles too.
+ *   A component is a class of the transitive closure of "joined".  A vertex in no triangle is a component of its own.
+ *   label[v] is the smallest vertex id in v's component.
+ *   size[v] is the number of vertices in v's component, stored per vertex, not per component.
+ *   component_count is the number of v with label[v] == v.
+ *   All three are integers and do not depend on the order of execution: two runs give identical bits.
+ * bslam_mesh_components: indices, labels uint32[V] and sizes uint32[V] are device arrays, 4 byte aligned, that do not overlap;
+ * *component_count is written on the host.  V == 0 and T == 0 are legal (an array of no elements may be null).  A triangle
+ * with an index >= V is never dereferenced: the call returns BSLAM_ERR_INVALID_ARGUMENT, labels and sizes are then
+ * unspecified, and nothing outside the given buffers is touched.  Refused without a launch: a null context or
+ * component_count, null or misaligned arrays, labels or sizes that overlap each other or the indices.  A union-find over
+ * parent[v] <= v: a fixed number of launches whatever the graph's diameter (one union launch); every loop is capped, and
+ * BSLAM_ERR_INTERNAL reports a cap that was reached (it cannot be).  While profiling is on, bslam_debug_cull_stats counts the
+ * hooks (compare-and-swaps) attempted and, as "culled", those that failed and were retried.  Synchronises `stream`.
+ * Filter:
+ *   Given size (as bslam_mesh_components wrote it) and min_vertices (>= 1), vertex v is kept iff size[v] >= min_vertices.
+ *   A triangle is kept iff its first vertex is kept; its three vertices share a label, so they are all kept or all dropped.
+ *   Kept vertices and kept triangles keep their relative order.  The new vertex id is the rank among the kept vertices.
+ *   Positions, normals and colours are copied with their bits unchanged; indices are remapped.
+ *   V' and T' are returned on the host; output entries at and beyond V' / T' are not written.
+ * bslam_filter_mesh: positions float[3 V], normals float[3 V] (may be null), colors uchar4[V] (may be null), indices
+ * uint32[3 T], sizes uint32[V] and the outputs of the same shapes (room for V vertices and T triangles) are device arrays.
+ * Refused without a launch: null required arguments, an out_normals / out_colors that does not match the presence of its
+ * input, min_vertices == 0, misaligned (4 byte) pointers, and an output that overlaps an input or another output -- compaction
+ * in place races.  An index >= V: as above.  Synchronises `stream`.  Every rank of a surfel-sharded run holds the same mesh. */
+int bslam_mesh_components(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const uint32_t* indices,
+                          uint32_t* labels, uint32_t* sizes, uint32_t* component_count);
+int bslam_filter_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                      const float* normals, const void* colors, const uint32_t* indices, const uint32_t* sizes, uint32_t min_vertices,
+                      float* out_positions, float* out_normals, void* out_colors, uint32_t* out_indices, uint32_t* out_vertex_count,
+                      uint32_t* out_triangle_count);
 
 /* Surface views: a per-pixel ray-cast of a fused volume (depth, colour and normal from a pose, without the holes of the disc
  * view where surfels are sparse).  All arithmetic is fp32 in a fixed expression order with explicit fused multiply-adds

@@ -9,7 +9,8 @@ has a ground truth, prints the ATE RMSE.
                             [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
                             [--render-source {surfels,volume}]
                             [--place-recognition] [--place-min-gap N]
-                            [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--point-cloud PATH]
+                            [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
+                            [--point-cloud PATH]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -36,6 +37,9 @@ size up to --max-depth.  The directory has the same layout.
 (DirectBA.FuseKeyframes) over the box of the surfel model (DirectBA.ModelBounds) padded by the truncation, and its surface
 (DirectBA.ExtractMesh, surface nets) is written as a binary PLY with normals and colours.  --mesh-voxel-size M: metres, default
 0.01; --mesh-truncation M: metres, default 4 voxels; --mesh-min-count N: a sample takes part when N keyframes saw it, default 1.
+--mesh-min-component N: connected pieces of the surface with fewer than N vertices (flying pixels at occlusion edges, single noisy
+blobs) are removed on the GPU before the file is written (DirectBA.ExtractMesh(min_component_vertices=N)); default 0, off.  The
+summary line then names the pieces found and the vertices and triangles removed.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 """
@@ -134,20 +138,25 @@ def fuse_model(ba, voxel_size=0.01, truncation=None):
     return origin, dims
 
 
-def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1, fused=None):
+def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1, fused=None, min_component=0):
     """FuseKeyframes over the padded ModelBounds (unless `fused`, the (origin, dims) of fuse_model, says it was done), ExtractMesh,
-    SaveMeshAsPLY -> (mesh dict, origin, dims)."""
+    SaveMeshAsPLY -> (mesh dict, origin, dims, component report or None).  min_component >= 2: the components of fewer vertices are
+    removed before the file is written, and the report says what was found and removed."""
     origin, dims = fused if fused is not None else fuse_model(ba, voxel_size, truncation)
-    mesh = ba.ExtractMesh(min_count)
+    report = None
+    if min_component >= 2:
+        mesh, report = ba.ExtractMesh(min_count, min_component_vertices=min_component, report=True)
+    else:
+        mesh = ba.ExtractMesh(min_count)
     dba.SaveMeshAsPLY(path, mesh)
-    return mesh, origin, dims
+    return mesh, origin, dims, report
 
 
 def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterations=10, max_depth=3.0, end_frame=None, raw_to_float_depth=1.0 / 5000,
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
-        render_source="surfels"):
+        render_source="surfels", mesh_min_component=0):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -195,8 +204,10 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh:
-        m, origin, dims = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused)
+        m, origin, dims, report = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused, mesh_min_component)
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
+        if report is not None:
+            result["mesh"].update(components=report["components"], removed_vertices=report["removed_vertices"], removed_triangles=report["removed_triangles"])
     if inspect:
         inspect(slam, result)
     if trajectory:
@@ -227,6 +238,7 @@ def arg_parser():
     ap.add_argument("--mesh-voxel-size", type=float, default=0.01)
     ap.add_argument("--mesh-truncation", type=float, default=None)
     ap.add_argument("--mesh-min-count", type=int, default=1)
+    ap.add_argument("--mesh-min-component", type=int, default=0)
     ap.add_argument("--point-cloud", default=None)
     return ap
 
@@ -238,7 +250,7 @@ def main():
             median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
             render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap, mesh=a.mesh,
             mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
-            render_source=a.render_source)
+            render_source=a.render_source, mesh_min_component=a.mesh_min_component)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -251,7 +263,11 @@ def main():
     if "point_cloud" in r:
         print(f"{r['point_cloud'][1]} points -> {r['point_cloud'][0]}")
     if "mesh" in r:
-        print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples -> {r['mesh']['path']}")
+        cleaned = ""
+        if "components" in r["mesh"]:
+            cleaned = (f" ({r['mesh']['components']} components before clean-up, {r['mesh']['removed_vertices']} vertices and "
+                       f"{r['mesh']['removed_triangles']} triangles removed)")
+        print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
     if "ate" in r:
         print(f"ATE RMSE {r['ate']['rmse']:.6f} m over {r['ate']['pairs']} poses")
 

@@ -115,18 +115,23 @@ __device__ __forceinline__ float ny_of(const CamConsts& c, float py) { return __
 __device__ __forceinline__ f3 unproject(const CamConsts& c, int x, int y, float depth) {                    // BS/surfel_projection.cuh:110
   return mk3(depth * nx_of(c, (float)x), depth * ny_of(c, (float)y), depth);
 }
-// Correctly rounded 1 / x for 2^-96 < |x| < 2^96: the compiler's expansion of an IEEE division (v_div_scale x 2, v_rcp, four
-// fmas, a multiply, v_div_fmas, v_div_fixup) with the parts that only serve numerators != 1, denormal scaling and special
-// operands removed -- the same v_rcp seed and the same fma chain, so the same bits as 1.0f / x there, in 7 instead of 11
-// instructions.  (tests/test_gpu_parity.py::test_midrange_reciprocal_is_correctly_rounded sweeps it against 1.0f / x.)
+// Correctly rounded 1 / x for 2^-96 < |x| < 2^96, the same bits as 1.0f / x there.
+// Markstein's theorem: when the seed r0 is one of the two floats that bracket 1 / x, the residual e0 = fma(-x, r0, 1) is exact
+// (it fits 24 bits), and ONE Newton step fma(e0, r0, r0) is RN(1 / x) for every significand of x except the all-ones one
+// (0xffffff), where it is RN(1 / x) only from the upper neighbour.  From a seed that is merely within a few ulp the first step
+// lands on a bracketing float and the second one is RN, again except for 0xffffff.  (tests/test_reciprocal_chain_cpu.py states both
+// in integer arithmetic over all 2^23 significands.)
+// (Until this sweep decided, every kernel ran v_rcp_f32 + 6 fmas: the compiler's own expansion of an IEEE division with the parts
+// that only serve numerators != 1, denormal scaling and special operands removed.)
+// Whether a chain equals 1.0f / x on gfx950 is decided by sweeping it on the device, not by the theorem:
+// tests/test_gpu_jacobians.py::test_midrange_reciprocal_is_correctly_rounded (every significand at three exponents, 4 M random
+// values) and tests/test_gpu_reciprocal_chain.py (every significand at each biased exponent 117 .. 134, and the raw seed).
+// Found on MI355X: v_rcp_f32 returns a bracketing float for all 2^23 significands (the lower neighbour for 4 820 636, the upper for
+// 3 567 971, the upper for 0xffffff), and one step equals 1.0f / x everywhere swept.  So one step ships.
 __device__ __forceinline__ float rcp_rn_midrange(float x) {
   const float r0 = __builtin_amdgcn_rcpf(x);
   const float e0 = __builtin_fmaf(-x, r0, 1.0f);
-  const float r1 = __builtin_fmaf(e0, r0, r0);
-  const float e1 = __builtin_fmaf(-x, r1, 1.0f);
-  const float r2 = __builtin_fmaf(e1, r1, r1);
-  const float e2 = __builtin_fmaf(-x, r2, 1.0f);
-  return __builtin_fmaf(e2, r1, r2);
+  return __builtin_fmaf(e0, r0, r0);
 }
 
 __device__ __forceinline__ f2 project(float fx, float fy, float cx, float cy, f3 p) {                       // BS/surfel_projection.cuh:52

@@ -255,6 +255,13 @@ __global__ __launch_bounds__(256) void jacobian_probe_kernel(int kind, int count
   } else if (kind == 7) {
     o[0] = rcp_rn_midrange(a[0]);
     o[1] = 1.0f / a[0];
+  } else if (kind == 8) {   // the raw v_rcp_f32 seed of rcp_rn_midrange, and one and two Newton steps from it
+    const float x = a[0];
+    const float r0 = __builtin_amdgcn_rcpf(x);
+    const float r1 = __builtin_fmaf(__builtin_fmaf(-x, r0, 1.0f), r0, r0);
+    o[0] = r0;
+    o[1] = r1;
+    o[2] = __builtin_fmaf(__builtin_fmaf(-x, r1, 1.0f), r1, r1);
   } else if (kind == 2) {
     const float m[12] = {a[9], a[10], a[11], 0, a[12], a[13], a[14], 0, 0, 0, 0, 0};
     float dj[6];

@@ -20,6 +20,7 @@
 #include "render_kernels.hpp"
 #include "fusion_kernels.hpp"
 #include "mesh_kernels.hpp"
+#include "distance_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1402,6 +1403,7 @@ int bslam_debug_pose_residuals(
 #include "render_abi.inc"
 #include "fusion_abi.inc"
 #include "mesh_abi.inc"
+#include "distance_abi.inc"
 #include "raycast_abi.inc"
 #include "place_abi.inc"
 #include "odometry_abi.inc"

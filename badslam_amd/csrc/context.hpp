@@ -161,6 +161,7 @@ struct bslam_context {
   bool place_pattern_ready = false;
   bslam::Slab fusion;        // bslam_extract_mesh: active flags and quad counts u8[cells], vertex ids and quad offsets u32[cells], scan sums;
                              // bslam_mesh_components: parent and root sizes u32[V]; bslam_filter_mesh: keep flags, ranks, scan sums
+  bslam::Slab distance;      // bslam_point_mesh_distance: triangle records, cell lists, sorted points, scan sums
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

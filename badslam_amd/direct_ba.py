@@ -83,6 +83,11 @@ def host_lib():
     L.bsh_mesh_component_sizes.argtypes = [u32p, C.c_uint32]
     L.bsh_mesh_components.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, u32p, u32p, u32p, u32p]
     L.bsh_volume.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int), f32p, f32p, u32p, u8p]
+    u64p = C.POINTER(C.c_uint64)
+    L.bsh_point_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_float, C.c_uint64, f32p, u32p,
+                                          f32p, u64p]
+    L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
+    L.bsh_distance_copy.argtypes = [f32p, u32p]
     _host = L
     return L
 
@@ -267,6 +272,8 @@ def _io_lib():
     L.bsh_save_poses.argtypes = [C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.c_int, C.c_char_p]
     L.bsh_save_point_cloud_ply.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_float)]
     L.bsh_save_mesh_ply.argtypes = [C.c_char_p, C.c_uint64, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.c_uint64, C.POINTER(C.c_uint32)]
+    L.bsh_load_ply.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
+    L.bsh_ply_copy.argtypes = [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)]
     L.bsh_save_calibration_arrays.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.bsh_load_calibration_arrays.argtypes = [C.c_char_p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]
     L.bsh_save_calibration.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p]
@@ -351,6 +358,21 @@ def SaveMeshAsPLY(path, mesh):
         raise ValueError("normals and colors need one row per vertex")
     _io_check(L, L.bsh_save_mesh_ply(str(path).encode(), len(pos), _f(pos), _f(nrm), col.ctypes.data_as(C.POINTER(C.c_uint8)), len(tri),
                                      tri.ctypes.data_as(C.POINTER(C.c_uint32))))
+
+
+def LoadPLY(path):
+    """Reads a PLY point cloud or mesh (ascii or binary little-endian; float or double x y z; faces with any integer count and index
+    types, polygons fan-triangulated; other properties and elements skipped) -> dict of positions (V, 3) f32, normals (V, 3) f32 or
+    None, colors (V, 3) u8 or None, triangles (T, 3) u32 (T may be 0).  A malformed or truncated file raises DirectBAError."""
+    L = _io_lib()
+    counts = (C.c_uint64 * 4)()
+    _io_check(L, L.bsh_load_ply(str(path).encode(), counts))
+    V, T = int(counts[0]), int(counts[1])
+    out = dict(positions=np.zeros((V, 3), np.float32), normals=np.zeros((V, 3), np.float32) if counts[2] else None,
+               colors=np.zeros((V, 3), np.uint8) if counts[3] else None, triangles=np.zeros((T, 3), np.uint32))
+    _io_check(L, L.bsh_ply_copy(_f(out["positions"]), None if out["normals"] is None else _f(out["normals"]),
+                                None if out["colors"] is None else out["colors"].ctypes.data_as(C.POINTER(C.c_uint8)), out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32))))
+    return out
 
 
 def save_calibration_arrays(base, depth4, color4, a, cfactor):
@@ -697,6 +719,41 @@ class DirectBA:
         self._check(self.L.bsh_mesh_components(self._ba, self.stream, V, len(tri), tri.ctypes.data_as(u32p), labels.ctypes.data_as(u32p), sizes.ctypes.data_as(u32p),
                                                C.byref(n)))
         return labels, sizes
+
+    # --- surface evaluation (bslam_point_mesh_distance)
+    @staticmethod
+    def _distance_result(distance, triangle, cell, grid):
+        return dict(distance=distance, triangle=triangle, cell_size=float(cell.value), grid_cells=int(grid[0]), grid_entries=int(grid[1]))
+
+    def PointMeshDistance(self, points, mesh, max_distance, cell_size=None, max_grid_entries=1 << 28):
+        """Distance of every point (n, 3) to the nearest triangle of `mesh` within max_distance: dict of distance (n,) f32 (+inf
+        beyond max_distance), triangle (n,) u32 (0xFFFFFFFF there), cell_size (the grid cell used), grid_cells, grid_entries.
+        mesh: the dict of ExtractMesh or LoadPLY, or {"positions": ...} alone for a point cloud (a mesh without triangles counts
+        as one too): every vertex then is the triangle (i, i, i).  cell_size None: max_distance, doubled while the grid exceeds
+        max_grid_entries."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        if tri is None or len(tri) == 0:
+            tri = np.repeat(np.arange(len(pos), dtype=np.uint32)[:, None], 3, axis=1)
+        tri = np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        distance, triangle = np.zeros(len(pts), np.float32), np.zeros(len(pts), np.uint32)
+        cell, grid = C.c_float(), (C.c_uint64 * 2)()
+        u32p = C.POINTER(C.c_uint32)
+        self._check(self.L.bsh_point_mesh_distance(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), tri.ctypes.data_as(u32p), float(max_distance),
+                                                   0.0 if cell_size is None else float(cell_size), int(max_grid_entries), _f(distance), triangle.ctypes.data_as(u32p),
+                                                   C.byref(cell), grid))
+        return self._distance_result(distance, triangle, cell, grid)
+
+    def SurfelMeshDistance(self, max_distance, cell_size=None, max_grid_entries=1 << 28):
+        """PointMeshDistance of the centres of the valid surfels (the positions of ExportToPointCloud, in its order) against the mesh
+        the last ExtractMesh returned, which is still on the device.  Raises if no mesh was extracted."""
+        count, cell, grid = C.c_uint64(), C.c_float(), (C.c_uint64 * 2)()
+        self._check(self.L.bsh_surfel_mesh_distance(self._ba, self.stream, float(max_distance), 0.0 if cell_size is None else float(cell_size), int(max_grid_entries),
+                                                    C.byref(count), C.byref(cell), grid))
+        distance, triangle = np.zeros(count.value, np.float32), np.zeros(count.value, np.uint32)
+        self._check(self.L.bsh_distance_copy(_f(distance), triangle.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return self._distance_result(distance, triangle, cell, grid)
 
     def Volume(self):
         """Download of the fused volume: dict of origin (3,), voxel_size, truncation, dims (nx, ny, nz) and the arrays tsdf f32,

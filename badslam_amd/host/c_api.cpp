@@ -278,6 +278,67 @@ int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* i
     g_mesh = DirectBA::Mesh();
   });
 }
+// DirectBA::PointMeshDistance of host arrays: points 3 per point, positions 3 per vertex, indices 3 per triangle; distance and
+// triangle receive `points_count` entries; *cell_used the grid cell of the call that succeeded, grid2 = {cells, entries}.
+int bsh_point_mesh_distance(void* ba, void* stream, uint64_t point_count, const float* points, uint64_t vertices, const float* positions, uint64_t triangles,
+                            const uint32_t* indices, float max_distance, float cell_size, uint64_t max_grid_entries, float* distance, uint32_t* triangle,
+                            float* cell_used, uint64_t* grid2) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::PointMeshOptions options;
+    options.max_distance = max_distance; options.cell_size = cell_size; options.max_grid_entries = max_grid_entries;
+    DirectBA::PointMeshResult result;
+    static_cast<DirectBA*>(ba)->PointMeshDistance(static_cast<hipStream_t>(stream), points, point_count, mesh, options, &result);
+    if (distance) std::memcpy(distance, result.distance.data(), result.distance.size() * sizeof(float));
+    if (triangle) std::memcpy(triangle, result.triangle.data(), result.triangle.size() * sizeof(uint32_t));
+    if (cell_used) *cell_used = result.cell_size;
+    if (grid2) { grid2[0] = result.grid_cells; grid2[1] = result.grid_entries; }
+  });
+}
+// DirectBA::SurfelMeshDistance in two steps, like the mesh: the call keeps its result for this thread and reports *count (the
+// valid surfels), *cell_used and grid2; bsh_distance_copy copies distance and triangle out (`count` entries each) and drops it.
+static thread_local DirectBA::PointMeshResult g_distance;
+int bsh_surfel_mesh_distance(void* ba, void* stream, float max_distance, float cell_size, uint64_t max_grid_entries, uint64_t* count, float* cell_used,
+                             uint64_t* grid2) {
+  BSH_TRY({
+    DirectBA::PointMeshOptions options;
+    options.max_distance = max_distance; options.cell_size = cell_size; options.max_grid_entries = max_grid_entries;
+    g_distance = DirectBA::PointMeshResult();
+    static_cast<DirectBA*>(ba)->SurfelMeshDistance(static_cast<hipStream_t>(stream), options, &g_distance);
+    *count = g_distance.distance.size();
+    if (cell_used) *cell_used = g_distance.cell_size;
+    if (grid2) { grid2[0] = g_distance.grid_cells; grid2[1] = g_distance.grid_entries; }
+  });
+}
+int bsh_distance_copy(float* distance, uint32_t* triangle) {
+  BSH_TRY({
+    if (distance) std::memcpy(distance, g_distance.distance.data(), g_distance.distance.size() * sizeof(float));
+    if (triangle) std::memcpy(triangle, g_distance.triangle.data(), g_distance.triangle.size() * sizeof(uint32_t));
+    g_distance = DirectBA::PointMeshResult();
+  });
+}
+// LoadPLY in two steps: bsh_load_ply reads the file, keeps it for this thread and reports counts4 = {vertices, triangles, has
+// normals, has colours}; bsh_ply_copy copies it out (positions, normals: 3 floats per vertex; colors: 3 bytes per vertex; indices:
+// 3 per triangle; any may be null) and drops it.
+static thread_local PlyMesh g_ply;
+int bsh_load_ply(const char* path, uint64_t* counts4) {
+  BSH_TRY({
+    std::string error;
+    if (!LoadPLY(path, &g_ply, &error)) { g_ply = PlyMesh(); throw std::runtime_error(error); }
+    counts4[0] = g_ply.vertex_count(); counts4[1] = g_ply.triangle_count(); counts4[2] = g_ply.has_normals; counts4[3] = g_ply.has_colors;
+  });
+}
+int bsh_ply_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
+  BSH_TRY({
+    if (positions) std::memcpy(positions, g_ply.positions.data(), g_ply.positions.size() * sizeof(float));
+    if (normals) std::memcpy(normals, g_ply.normals.data(), g_ply.normals.size() * sizeof(float));
+    if (colors) std::memcpy(colors, g_ply.colors_rgb.data(), g_ply.colors_rgb.size());
+    if (indices) std::memcpy(indices, g_ply.indices.data(), g_ply.indices.size() * sizeof(uint32_t));
+    g_ply = PlyMesh();
+  });
+}
 // DirectBA::Volume.  With tsdf == null only the description is returned: dims3 = nx ny nz, floats5 = origin x y z, voxel size,
 // truncation; else the three arrays of nx * ny * nz elements (colour: 4 bytes each) are filled as well.
 int bsh_volume(void* ba, void* stream, int* dims3, float* floats5, float* tsdf, uint32_t* count, uint8_t* color) {

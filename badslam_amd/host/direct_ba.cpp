@@ -522,16 +522,21 @@ void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) {
   mesh->normals.assign(3 * static_cast<size_t>(vertices), 0.f);
   mesh->colors.assign(vertices, uchar4_t{0, 0, 0, 0});
   mesh->indices.assign(3 * static_cast<size_t>(triangles), 0u);
+  KeepDeviceMesh(nullptr, nullptr, 0, 0);
   if (vertices == 0) return;
   // one-row device images; three floats per vertex do not fit an int width beyond 2^31 / 3 vertices, far above the 2^30 cells
-  DeviceBuffer<float> positions(1, static_cast<int>(3 * vertices)), normals(1, static_cast<int>(3 * vertices));
+  std::unique_ptr<DeviceBuffer<float>> positions_owner(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
+  std::unique_ptr<DeviceBuffer<u32>> indices_owner(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
+  DeviceBuffer<float>& positions = *positions_owner;
+  DeviceBuffer<u32>& indices = *indices_owner;
+  DeviceBuffer<float> normals(1, static_cast<int>(3 * vertices));
   DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
-  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1)));
   u32 v2 = 0, t2 = 0;
   Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, min_count, vertices, triangles, positions.address(), normals.address(), colors.address(),
                            indices.address(), &v2, &t2),
         "bslam_extract_mesh");
   if (v2 != vertices || t2 != triangles) throw std::runtime_error("ExtractMesh: the volume changed between the two extraction calls");
+  KeepDeviceMesh(std::move(positions_owner), std::move(indices_owner), vertices, triangles);   // for SurfelMeshDistance
   positions.Download(stream, mesh->positions.data(), mesh->positions.size() * sizeof(float));
   normals.Download(stream, mesh->normals.data(), mesh->normals.size() * sizeof(float));
   colors.Download(stream, mesh->colors.data(), mesh->colors.size() * sizeof(uchar4_t));
@@ -557,10 +562,15 @@ void DirectBA::ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh*
         "bslam_extract_mesh");
   if (report) *report = MeshComponentReport();
   mesh->positions.clear(); mesh->normals.clear(); mesh->colors.clear(); mesh->indices.clear();
+  KeepDeviceMesh(nullptr, nullptr, 0, 0);
   if (vertices == 0) return;
-  DeviceBuffer<float> positions(1, static_cast<int>(3 * vertices)), normals(1, static_cast<int>(3 * vertices));
+  std::unique_ptr<DeviceBuffer<float>> positions_owner(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
+  std::unique_ptr<DeviceBuffer<u32>> indices_owner(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
+  DeviceBuffer<float>& positions = *positions_owner;
+  DeviceBuffer<u32>& indices = *indices_owner;
+  DeviceBuffer<float> normals(1, static_cast<int>(3 * vertices));
   DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
-  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1))), labels(1, static_cast<int>(vertices)), sizes(1, static_cast<int>(vertices));
+  DeviceBuffer<u32> labels(1, static_cast<int>(vertices)), sizes(1, static_cast<int>(vertices));
   u32 v2 = 0, t2 = 0;
   Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, options.min_count, vertices, triangles, positions.address(), normals.address(),
                            colors.address(), indices.address(), &v2, &t2),
@@ -604,12 +614,90 @@ void DirectBA::ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh*
   fetch(host_labels.data(), labels.address(), host_labels.size() * sizeof(u32));
   fetch(host_sizes.data(), sizes.address(), host_sizes.size() * sizeof(u32));
   HIP_OR_THROW(hipStreamSynchronize(stream));
+  // the mesh as returned stays on the device for SurfelMeshDistance
+  if (filter) KeepDeviceMesh(std::move(out_positions), std::move(out_indices), kept_vertices, kept_triangles);
+  else KeepDeviceMesh(std::move(positions_owner), std::move(indices_owner), vertices, triangles);
   if (report) {
     report->components = components;
     report->removed_vertices = vertices - kept_vertices;
     report->removed_triangles = triangles - kept_triangles;
     ComponentSizes(host_labels, host_sizes, &report->sizes_descending);
   }
+}
+
+void DirectBA::KeepDeviceMesh(std::unique_ptr<DeviceBuffer<float>> positions, std::unique_ptr<DeviceBuffer<u32>> indices, u32 vertices, u32 triangles) {
+  mesh_positions_ = std::move(positions);
+  mesh_indices_ = std::move(indices);
+  mesh_vertices_ = vertices;
+  mesh_triangles_ = triangles;
+  mesh_extracted_ = true;
+}
+
+void DirectBA::PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count, const float* points, u32 vertices, const float* positions, u32 triangles,
+                                         const u32* indices, const PointMeshOptions& options, PointMeshResult* result) {
+  if (point_count > 0x7fffffffull) throw std::invalid_argument("PointMeshDistance: too many points for one device image");
+  const u32 n = static_cast<u32>(point_count);
+  result->distance.assign(n, 0.f);
+  result->triangle.assign(n, 0u);
+  DeviceBuffer<float> distance(1, static_cast<int>(std::max<u32>(n, 1)));
+  DeviceBuffer<u32> triangle(1, static_cast<int>(std::max<u32>(n, 1)));
+  // cell_size 0: the search radius, doubled while the call reports that the grid does not fit its budget
+  float cell = options.cell_size > 0.f ? options.cell_size : options.max_distance;
+  for (int attempt = 0;; ++attempt) {
+    uint64_t cells = 0, entries = 0;
+    const int rc = bslam_point_mesh_distance(ctx_, stream, n, points, vertices, positions, triangles, indices, options.max_distance, cell, options.max_grid_entries,
+                                             distance.address(), triangle.address(), &cells, &entries);
+    const bool over_budget = rc == BSLAM_ERR_INVALID_ARGUMENT && (entries > options.max_grid_entries || cells > BSLAM_POINT_MESH_MAX_CELLS);
+    if (over_budget && !(options.cell_size > 0.f) && attempt < 64 && std::isfinite(cell * 2.f)) { cell *= 2.f; continue; }
+    Check(rc, "bslam_point_mesh_distance");
+    result->cell_size = cell;
+    result->grid_cells = cells;
+    result->grid_entries = entries;
+    break;
+  }
+  if (n) {
+    HIP_OR_THROW(hipMemcpyAsync(result->distance.data(), distance.address(), n * sizeof(float), hipMemcpyDeviceToHost, stream));
+    HIP_OR_THROW(hipMemcpyAsync(result->triangle.data(), triangle.address(), n * sizeof(u32), hipMemcpyDeviceToHost, stream));
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+  }
+}
+
+void DirectBA::PointMeshDistance(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const PointMeshOptions& options, PointMeshResult* result) {
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
+      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull || 3 * static_cast<uint64_t>(point_count) > 0x7fffffffull)
+    throw std::invalid_argument("PointMeshDistance: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  const u32 vertices = static_cast<u32>(mesh.vertex_count()), triangles = static_cast<u32>(mesh.triangle_count());
+  DeviceBuffer<float> dev_points(1, static_cast<int>(std::max<size_t>(3 * point_count, 1))), dev_positions(1, static_cast<int>(std::max<u32>(3 * vertices, 1)));
+  DeviceBuffer<u32> dev_indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1)));
+  if (point_count) HIP_OR_THROW(hipMemcpyAsync(dev_points.address(), points, 3 * point_count * sizeof(float), hipMemcpyHostToDevice, stream));
+  if (vertices) HIP_OR_THROW(hipMemcpyAsync(dev_positions.address(), mesh.positions.data(), mesh.positions.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+  if (triangles) HIP_OR_THROW(hipMemcpyAsync(dev_indices.address(), mesh.indices.data(), mesh.indices.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
+  HIP_OR_THROW(hipStreamSynchronize(stream));   // the host arrays are the caller's and pageable
+  PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), vertices, dev_positions.address(), triangles, dev_indices.address(), options, result);
+}
+
+void DirectBA::SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& options, PointMeshResult* result) {
+  if (!mesh_extracted_) throw std::logic_error("SurfelMeshDistance: no extracted mesh (call ExtractMesh first)");
+  // the centres of the valid surfels, the set and the order of ExportToPointCloud
+  std::vector<float> centres;
+  if (surfels_size_ != 0) {
+    const size_t n = surfels_size_;
+    std::vector<float> rows(3 * n);
+    GetSurfels(stream, rows.data(), n * sizeof(float), 3);
+    centres.reserve(3 * n);
+    for (size_t i = 0; i < n; ++i) {
+      if (std::isnan(rows[i])) continue;
+      centres.insert(centres.end(), {rows[i], rows[n + i], rows[2 * n + i]});
+    }
+  }
+  const size_t count = centres.size() / 3;
+  DeviceBuffer<float> dev_points(1, static_cast<int>(std::max<size_t>(3 * count, 1)));
+  if (count) {
+    HIP_OR_THROW(hipMemcpyAsync(dev_points.address(), centres.data(), centres.size() * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_OR_THROW(hipStreamSynchronize(stream));
+  }
+  PointMeshDistanceOnDevice(stream, count, dev_points.address(), mesh_vertices_, mesh_positions_ ? mesh_positions_->address() : nullptr, mesh_triangles_,
+                            mesh_indices_ ? mesh_indices_->address() : nullptr, options, result);
 }
 
 u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes) {

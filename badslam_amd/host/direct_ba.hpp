@@ -266,6 +266,30 @@ class DirectBA {
   // Components of a caller's mesh: labels[v] = the smallest vertex id of v's component, sizes[v] = its vertex count (either may
   // be null).  Returns the number of components.
   u32 MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes);
+  // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
+  // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
+  // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.
+  struct PointMeshOptions {
+    float max_distance = 0.1f;
+    float cell_size = 0.f;
+    uint64_t max_grid_entries = 1ull << 28;
+  };
+  struct PointMeshResult {
+    std::vector<float> distance;
+    std::vector<u32> triangle;
+    float cell_size = 0.f;
+    uint64_t grid_cells = 0, grid_entries = 0;
+  };
+  // Host arrays: points float[3 point_count] and a mesh whose normals and colours are not looked at; a point cloud is a mesh with
+  // the triangles (i, i, i).
+  void PointMeshDistance(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const PointMeshOptions& options, PointMeshResult* result);
+  // The same on device arrays (4 byte aligned; see bslam_point_mesh_distance); the results are downloaded.
+  void PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count, const float* points, u32 vertices, const float* positions, u32 triangles,
+                                 const u32* indices, const PointMeshOptions& options, PointMeshResult* result);
+  // The centres of the valid surfels (the points of ExportToPointCloud, in its order) against the mesh the last ExtractMesh
+  // returned, which stays on the device for this: how far the surfels that bundle adjustment optimised lie from the surface the
+  // volume produced -- a consistency figure that needs no ground truth.  Throws std::logic_error if no mesh was extracted.
+  void SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& options, PointMeshResult* result);
   void Volume(hipStream_t stream, VolumeData* volume) const;         // download of that volume
   // Views of the volume of the last FuseKeyframes from a pose (bslam_raycast_volume): per pixel the first front-facing zero
   // crossing of the trilinear interpolant along the ray, as depth (units of a keyframe's depth image), colour and normal -- no
@@ -445,6 +469,12 @@ class DirectBA {
   // prepared aux buffer of RenderVolume and the min_count it was prepared for (0: stale -- a new fusion, or never prepared)
   std::unique_ptr<DeviceBuffer<u8>> volume_aux_;
   u32 volume_aux_min_count_ = 0;
+  // device copy of the mesh the last ExtractMesh returned (positions 3 V floats, indices 3 T), for SurfelMeshDistance
+  std::unique_ptr<DeviceBuffer<float>> mesh_positions_;
+  std::unique_ptr<DeviceBuffer<u32>> mesh_indices_;
+  u32 mesh_vertices_ = 0, mesh_triangles_ = 0;
+  bool mesh_extracted_ = false;
+  void KeepDeviceMesh(std::unique_ptr<DeviceBuffer<float>> positions, std::unique_ptr<DeviceBuffer<u32>> indices, u32 vertices, u32 triangles);
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

@@ -3,12 +3,14 @@
 
 #include <zlib.h>
 
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iomanip>
+#include <iterator>
 #include <limits>
 #include <sstream>
 
@@ -567,6 +569,199 @@ bool SaveMeshAsPLY(const std::string& path, size_t vertex_count, const float* po
     for (int d = 0; d < 3; ++d) AppendLE32(&body, indices + 3 * t + d);
   }
   return WriteWhole(path, header, body);
+}
+
+// ---- PLY import -------------------------------------------------------------------------------
+namespace {
+struct PlyProperty {
+  std::string name;
+  int type = -1;         // index into kPlyTypes
+  int count_type = -1;   // >= 0: a list with this count type
+};
+struct PlyElement {
+  std::string name;
+  uint64_t count = 0;
+  std::vector<PlyProperty> properties;
+};
+struct PlyType { const char* a; const char* b; int bytes; char kind; };   // kind: i signed, u unsigned, f float
+const PlyType kPlyTypes[8] = {{"char", "int8", 1, 'i'},  {"uchar", "uint8", 1, 'u'}, {"short", "int16", 2, 'i'}, {"ushort", "uint16", 2, 'u'},
+                              {"int", "int32", 4, 'i'},  {"uint", "uint32", 4, 'u'}, {"float", "float32", 4, 'f'}, {"double", "float64", 8, 'f'}};
+int PlyTypeIndex(const std::string& word) {
+  for (int i = 0; i < 8; ++i)
+    if (word == kPlyTypes[i].a || word == kPlyTypes[i].b) return i;
+  return -1;
+}
+
+// The body of a PLY file, read value by value; every read checks what is left.
+struct PlyBody {
+  const char* p;
+  const char* end;
+  bool ascii;
+  bool Read(int type, double* out) {
+    if (ascii) {
+      while (p < end && std::isspace(static_cast<unsigned char>(*p))) ++p;
+      const char* start = p;
+      while (p < end && !std::isspace(static_cast<unsigned char>(*p))) ++p;
+      if (p == start || p - start > 63) return false;
+      char word[64];
+      std::memcpy(word, start, p - start);
+      word[p - start] = 0;
+      char* stop = nullptr;
+      *out = std::strtod(word, &stop);
+      if (stop != word + (p - start)) return false;
+      if (kPlyTypes[type].kind == 'f' && kPlyTypes[type].bytes == 4) *out = static_cast<double>(static_cast<float>(*out));
+      return true;
+    }
+    const int bytes = kPlyTypes[type].bytes;
+    if (end - p < bytes) return false;
+    switch (type) {
+      case 0: { int8_t v; std::memcpy(&v, p, 1); *out = v; break; }
+      case 1: { uint8_t v; std::memcpy(&v, p, 1); *out = v; break; }
+      case 2: { int16_t v; std::memcpy(&v, p, 2); *out = v; break; }
+      case 3: { uint16_t v; std::memcpy(&v, p, 2); *out = v; break; }
+      case 4: { int32_t v; std::memcpy(&v, p, 4); *out = v; break; }
+      case 5: { uint32_t v; std::memcpy(&v, p, 4); *out = v; break; }
+      case 6: { float v; std::memcpy(&v, p, 4); *out = v; break; }
+      default: { double v; std::memcpy(&v, p, 8); *out = v; break; }
+    }
+    p += bytes;
+    return true;
+  }
+};
+bool PlyFail(std::string* error, const std::string& what) {
+  if (error) *error = what;
+  return false;
+}
+}  // namespace
+
+bool LoadPLY(const std::string& path, PlyMesh* mesh, std::string* error) {
+  *mesh = PlyMesh();
+  std::ifstream file(path, std::ios::binary);
+  if (!file) return PlyFail(error, "cannot open " + path);
+  const std::string data((std::istreambuf_iterator<char>(file)), std::istreambuf_iterator<char>());
+  // header: lines up to end_header
+  size_t pos = 0;
+  std::vector<PlyElement> elements;
+  int format = -1;   // 0 ascii, 1 binary little-endian
+  bool first = true, ended = false;
+  while (pos < data.size()) {
+    const size_t eol = data.find('\n', pos);
+    if (eol == std::string::npos) break;
+    std::string line = data.substr(pos, eol - pos);
+    pos = eol + 1;
+    if (!line.empty() && line.back() == '\r') line.pop_back();
+    std::istringstream words(line);
+    std::string word;
+    words >> word;
+    if (first) {
+      if (word != "ply") return PlyFail(error, path + ": not a PLY file");
+      first = false;
+      continue;
+    }
+    if (word.empty() || word == "comment" || word == "obj_info") continue;
+    if (word == "end_header") { ended = true; break; }
+    if (word == "format") {
+      std::string kind, version;
+      words >> kind >> version;
+      if (kind == "ascii") format = 0;
+      else if (kind == "binary_little_endian") format = 1;
+      else return PlyFail(error, path + ": format '" + kind + "' is not supported (ascii, binary_little_endian)");
+    } else if (word == "element") {
+      PlyElement e;
+      long long count = -1;
+      if (!(words >> e.name >> count) || count < 0) return PlyFail(error, path + ": malformed element line '" + line + "'");
+      e.count = static_cast<uint64_t>(count);
+      elements.push_back(e);
+    } else if (word == "property") {
+      if (elements.empty()) return PlyFail(error, path + ": a property before any element");
+      PlyProperty prop;
+      std::string type;
+      words >> type;
+      if (type == "list") {
+        std::string count_type, item_type;
+        words >> count_type >> item_type;
+        prop.count_type = PlyTypeIndex(count_type);
+        prop.type = PlyTypeIndex(item_type);
+        if (prop.count_type < 0 || kPlyTypes[prop.count_type].kind == 'f') return PlyFail(error, path + ": malformed list property '" + line + "'");
+      } else {
+        prop.type = PlyTypeIndex(type);
+      }
+      if (prop.type < 0 || !(words >> prop.name)) return PlyFail(error, path + ": malformed property line '" + line + "'");
+      elements.back().properties.push_back(prop);
+    } else {
+      return PlyFail(error, path + ": unknown header line '" + line + "'");
+    }
+  }
+  if (!ended || format < 0) return PlyFail(error, path + ": the header has no format or no end_header");
+  PlyBody body{data.data() + pos, data.data() + data.size(), format == 0};
+  bool seen_vertices = false;
+  uint64_t vertex_count = 0;
+  for (const PlyElement& e : elements) {
+    const bool is_vertex = e.name == "vertex", is_face = e.name == "face";
+    if (is_face && !seen_vertices) return PlyFail(error, path + ": the face element stands before the vertex element");
+    // the least a row can take, so that a count the file cannot hold is refused before anything is reserved
+    uint64_t row_bytes = 0;
+    for (const PlyProperty& prop : e.properties) row_bytes += format == 0 ? 2 : static_cast<uint64_t>(kPlyTypes[prop.count_type >= 0 ? prop.count_type : prop.type].bytes);
+    const uint64_t left = static_cast<uint64_t>(body.end - body.p);
+    if (row_bytes != 0 && e.count > (left + 1) / row_bytes) return PlyFail(error, path + ": truncated (element " + e.name + ")");
+    if (row_bytes == 0 && e.count != 0 && !e.properties.empty()) return PlyFail(error, path + ": malformed element " + e.name);
+    int slot[9];   // x y z nx ny nz red green blue -> property index
+    for (int& v : slot) v = -1;
+    if (is_vertex) {
+      static const char* const names[9] = {"x", "y", "z", "nx", "ny", "nz", "red", "green", "blue"};
+      for (size_t k = 0; k < e.properties.size(); ++k)
+        for (int n = 0; n < 9; ++n)
+          if (e.properties[k].count_type < 0 && e.properties[k].name == names[n] && slot[n] < 0) slot[n] = static_cast<int>(k);
+      if (slot[0] < 0 || slot[1] < 0 || slot[2] < 0) return PlyFail(error, path + ": the vertex element has no x, y, z");
+      if (e.count > 0xffffffffull) return PlyFail(error, path + ": too many vertices");
+      mesh->has_normals = slot[3] >= 0 && slot[4] >= 0 && slot[5] >= 0;
+      mesh->has_colors = slot[6] >= 0 && slot[7] >= 0 && slot[8] >= 0;
+      mesh->positions.resize(3 * e.count);
+      if (mesh->has_normals) mesh->normals.resize(3 * e.count);
+      if (mesh->has_colors) mesh->colors_rgb.resize(3 * e.count);
+      seen_vertices = true;
+      vertex_count = e.count;
+    }
+    std::vector<uint32_t> polygon;
+    for (uint64_t row = 0; row < e.count; ++row) {
+      for (size_t k = 0; k < e.properties.size(); ++k) {
+        const PlyProperty& prop = e.properties[k];
+        double v = 0;
+        if (prop.count_type < 0) {
+          if (!body.Read(prop.type, &v)) return PlyFail(error, path + ": truncated or malformed (element " + e.name + ")");
+          if (!is_vertex) continue;
+          for (int n = 0; n < 9; ++n) {
+            if (slot[n] != static_cast<int>(k)) continue;
+            if (n < 3) mesh->positions[3 * row + n] = static_cast<float>(v);
+            else if (n < 6) { if (mesh->has_normals) mesh->normals[3 * row + (n - 3)] = static_cast<float>(v); }
+            else if (mesh->has_colors) {
+              const double c = kPlyTypes[prop.type].kind == 'f' ? v * 255.0 : v;   // float colours are in [0, 1]
+              mesh->colors_rgb[3 * row + (n - 6)] = static_cast<uint8_t>(c < 0 ? 0 : (c > 255 ? 255 : c));
+            }
+          }
+          continue;
+        }
+        double n_items = 0;
+        if (!body.Read(prop.count_type, &n_items) || n_items < 0) return PlyFail(error, path + ": truncated or malformed (element " + e.name + ")");
+        const bool indices = is_face && (prop.name == "vertex_indices" || prop.name == "vertex_index");
+        polygon.clear();
+        for (uint64_t i = 0; i < static_cast<uint64_t>(n_items); ++i) {
+          if (!body.Read(prop.type, &v)) return PlyFail(error, path + ": truncated or malformed (element " + e.name + ")");
+          if (!indices) continue;
+          if (!(v >= 0 && v < static_cast<double>(vertex_count)) || v != std::floor(v)) return PlyFail(error, path + ": a face names a vertex that does not exist");
+          polygon.push_back(static_cast<uint32_t>(v));
+        }
+        for (size_t i = 2; i < polygon.size(); ++i) {   // a fan from the first vertex
+          mesh->indices.push_back(polygon[0]);
+          mesh->indices.push_back(polygon[i - 1]);
+          mesh->indices.push_back(polygon[i]);
+        }
+      }
+    }
+  }
+  if (!seen_vertices) return PlyFail(error, path + ": no vertex element");
+  if (mesh->indices.size() / 3 > 0xffffffffull) return PlyFail(error, path + ": too many triangles");
+  return true;
 }
 
 }  // namespace bslam_host

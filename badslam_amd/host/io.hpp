@@ -59,6 +59,22 @@ bool SavePointCloudAsPLY(const std::string& path, size_t count, const float* pos
 bool SaveMeshAsPLY(const std::string& path, size_t vertex_count, const float* positions, const float* normals, const uint8_t* colors_rgba,
                    size_t triangle_count, const uint32_t* indices);
 
+// ---- PLY import ----
+// A vertex element with float or double x y z, optionally nx ny nz and red green blue, and optionally a face element whose list
+// property vertex_indices (or vertex_index) may have any integer count and index types; polygons are fan-triangulated, faces of
+// fewer than three vertices give no triangle.  ascii and binary_little_endian.  Other properties and other elements are skipped
+// by their declared sizes.  A malformed or truncated file, or a face that names a vertex the file does not have, is an error:
+// nothing is read past the end of the file.  Reads back what SavePointCloudAsPLY and SaveMeshAsPLY write, bit for bit.
+struct PlyMesh {
+  std::vector<float> positions, normals;   // 3 per vertex; normals empty unless has_normals
+  std::vector<uint8_t> colors_rgb;         // 3 per vertex; empty unless has_colors
+  std::vector<uint32_t> indices;           // 3 per triangle, may be empty (a point cloud)
+  bool has_normals = false, has_colors = false;
+  size_t vertex_count() const { return positions.size() / 3; }
+  size_t triangle_count() const { return indices.size() / 3; }
+};
+bool LoadPLY(const std::string& path, PlyMesh* mesh, std::string* error);
+
 // ---- state file v1 (BS/io.cc:38-536, config block BS/bad_slam_config.cc:28-200) ----
 // The file holds the SLAM configuration, the per-frame poses of the video, the cameras, the depth deformation, the
 // keyframe list (metadata only: keyframe images are re-created from the dataset on load) and rows 0-7 of the

@@ -695,6 +695,51 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, u
                       float* out_positions, float* out_normals, void* out_colors, uint32_t* out_indices, uint32_t* out_vertex_count,
                       uint32_t* out_triangle_count);
 
+/* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
+ * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
+ * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components
+ * (csrc/device_math.hpp).  Point p, triangle t with vertices a, b, c = positions[indices[3 t + 0 .. 2]], R = max_distance.
+ * Box:
+ *   lo, hi = the component-wise minimum and maximum of a, b, c.  t is a candidate for p iff all nine coordinates of the triangle
+ *   are finite and on every axis p.a >= lo.a - R && p.a <= hi.a + R (the two sums rounded to fp32, float comparisons).  A point
+ *   with a NaN or infinite coordinate has no candidate.
+ * Segment, seg(p, a, b):
+ *   e = b - a, w = p - a, ee = dot(e, e), we = dot(w, e);  t = ee > 0 ? we / ee : 0, then t = t < 0 ? 0 : (t > 1 ? 1 : t);
+ *   q.k = fmaf(-t, e.k, w.k);  the value is dot(q, q).
+ * Face, face(p, a, b, c):
+ *   u = b - a, v = c - a, w = p - a, n = cross(u, v), nn = dot(n, n).  There is a face term iff nn > 0 and
+ *   dot(cross(u, w), n) >= 0 and dot(cross(c - b, p - b), n) >= 0 and dot(cross(a - c, p - c), n) >= 0;  then
+ *   d = dot(w, n) / sqrtf(nn) and the value is d * d.
+ * Pair:
+ *   d2(p, t) = the minimum of seg(p, a, b), seg(p, b, c), seg(p, c, a) and the face term if there is one; a NaN is no value.
+ *   Degenerate triangles need no special case: (i, i, i) measures the distance to a point (a point cloud), (i, i, j) to a
+ *   segment.  Duplicated triangles are legal.
+ * Result:
+ *   best = the smallest d2 over the candidates of p, triangle = the smallest t that attains it.  The point hits iff
+ *   best <= fl(R * R) (formed on the host).  On a hit distance = sqrtf(best); else distance = +INFINITY and triangle =
+ *   0xffffffff.  Nothing depends on the order of execution: two calls give identical bits.
+ * bslam_point_mesh_distance: points float[3 N], positions float[3 V], indices uint32[3 T], out_distance float[N] and
+ * out_triangle uint32[N] (may be null) are device arrays, non-null where not empty, 4 byte aligned, no output overlapping
+ * anything.  Refused without a launch: a null context or out_distance, a max_distance or cell_size that is not finite and > 0,
+ * max_grid_entries == 0, more than 2^32 - 256 points or triangles.  An index >= V is never dereferenced:
+ * BSLAM_ERR_INVALID_ARGUMENT, outputs untouched.  N == 0 and T == 0 are legal; with T == 0 every point misses.
+ * Grid: a uniform grid of cell_size holds each valid triangle in every cell its dilated box [lo - R, hi + R] touches, and a
+ * point reads only its own cell.  origin.a = the minimum of the computed lo.a - R; the cell of x is
+ * floorf((x - origin.a) * fl(1 / cell_size)), monotone in x, so a point that passes the box predicate lies in a cell the
+ * triangle is registered in: the grid is exactly conservative, and it changes no result.  *grid_cells and *grid_entries (host,
+ * may be null) receive the number of cells and of (triangle, cell) entries.  If the entries exceed max_grid_entries (or
+ * 2^32 - 1), or the cells BSLAM_POINT_MESH_MAX_CELLS (2^26: the scans' 32-bit totals stay safe and the per-cell words at
+ * 1 GiB; *grid_cells then holds the number asked for, saturated), the call stops behind the count pass: outputs untouched,
+ * BSLAM_ERR_INVALID_ARGUMENT, both
+ * numbers in bslam_last_error -- use a larger cell_size.  Scratch lives in a context slab that grows on demand.  While profiling
+ * is on, bslam_debug_cull_stats counts the pairs the grid offered and, as "culled", those the box predicate rejected.
+ * Synchronises `stream`.  Every rank of a surfel-sharded run holds the same mesh. */
+#define BSLAM_POINT_MESH_MAX_CELLS (1ull << 26)
+int bslam_point_mesh_distance(bslam_context* ctx, void* stream, uint32_t point_count, const float* points, uint32_t vertex_count,
+                              const float* positions, uint32_t triangle_count, const uint32_t* indices, float max_distance,
+                              float cell_size, uint64_t max_grid_entries, float* out_distance, uint32_t* out_triangle,
+                              uint64_t* grid_cells, uint64_t* grid_entries);
+
 /* Surface views: a per-pixel ray-cast of a fused volume (depth, colour and normal from a pose, without the holes of the disc
  * view where surfels are sparse).  All arithmetic is fp32 in a fixed expression order with explicit fused multiply-adds
  * (csrc/raycast_kernels.hpp, DESIGN.md 8 "Surface views"); two calls give identical bits.  With G = global_T_camera,

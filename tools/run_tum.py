@@ -11,6 +11,8 @@ has a ground truth, prints the ATE RMSE.
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
                             [--point-cloud PATH]
+                            [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
+                            [--surfel-mesh-distance] [--surface-report FILE.json]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -42,15 +44,24 @@ blobs) are removed on the GPU before the file is written (DirectBA.ExtractMesh(m
 summary line then names the pieces found and the vertices and triangles removed.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
+
+--ground-truth-surface FILE.ply: the fused mesh (after --mesh-min-component) is evaluated against a ground-truth mesh or point
+cloud given in the frame of the run (badslam_amd/surface_eval.py: accuracy from the mesh's vertices to the ground truth,
+completeness from the ground truth's vertices to the mesh, precision / recall / F-score per threshold; a coarse ground truth has
+to be subdivided by its owner).  --surface-max-distance M: the search radius, default 0.1; a point with nothing within it fails
+every threshold.  --surface-thresholds: default 0.01,0.02,0.05.  --surfel-mesh-distance: the summary of the distances from the
+surfels' centres to the fused mesh (DirectBA.SurfelMeshDistance), a consistency figure that needs no ground truth.
+--surface-report FILE.json: what was printed, as JSON.  Either option fuses with the --mesh-* options whether or not --mesh is given.
 """
 import argparse
+import json
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from badslam_amd import abi, ate, bad_slam, png     # noqa: E402
+from badslam_amd import abi, ate, bad_slam, png, surface_eval     # noqa: E402
 from badslam_amd import direct_ba as dba            # noqa: E402
 
 
@@ -140,7 +151,7 @@ def fuse_model(ba, voxel_size=0.01, truncation=None):
 
 def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1, fused=None, min_component=0):
     """FuseKeyframes over the padded ModelBounds (unless `fused`, the (origin, dims) of fuse_model, says it was done), ExtractMesh,
-    SaveMeshAsPLY -> (mesh dict, origin, dims, component report or None).  min_component >= 2: the components of fewer vertices are
+    SaveMeshAsPLY (unless path is None) -> (mesh dict, origin, dims, component report or None).  min_component >= 2: the components of fewer vertices are
     removed before the file is written, and the report says what was found and removed."""
     origin, dims = fused if fused is not None else fuse_model(ba, voxel_size, truncation)
     report = None
@@ -148,7 +159,8 @@ def fuse_and_mesh(ba, path, voxel_size=0.01, truncation=None, min_count=1, fused
         mesh, report = ba.ExtractMesh(min_count, min_component_vertices=min_component, report=True)
     else:
         mesh = ba.ExtractMesh(min_count)
-    dba.SaveMeshAsPLY(path, mesh)
+    if path:
+        dba.SaveMeshAsPLY(path, mesh)
     return mesh, origin, dims, report
 
 
@@ -156,7 +168,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         num_scales=5, max_surfel_count=25 * 1000 * 1000, ba_cost=False, pyramid_level_for_depth=0, pyramid_level_for_color=0,
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
-        render_source="surfels", mesh_min_component=0):
+        render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
+        surfel_mesh_distance=False, surface_report=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -203,8 +216,21 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         positions, colors, normals = slam.ba().ExportToPointCloud()
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
-    if mesh:
+    if mesh or ground_truth_surface or surfel_mesh_distance:
         m, origin, dims, report = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused, mesh_min_component)
+        surface = {}
+        if ground_truth_surface:
+            surface["ground_truth"] = str(ground_truth_surface)
+            surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), surface_max_distance, tuple(surface_thresholds)))
+        if surfel_mesh_distance:
+            surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
+        if surface:
+            surface["max_distance"] = float(surface_max_distance)
+            result["surface"] = surface
+            if surface_report:
+                with open(surface_report, "w") as f:
+                    json.dump(surface, f, indent=1)
+    if mesh:
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
         if report is not None:
             result["mesh"].update(components=report["components"], removed_vertices=report["removed_vertices"], removed_triangles=report["removed_triangles"])
@@ -240,6 +266,11 @@ def arg_parser():
     ap.add_argument("--mesh-min-count", type=int, default=1)
     ap.add_argument("--mesh-min-component", type=int, default=0)
     ap.add_argument("--point-cloud", default=None)
+    ap.add_argument("--ground-truth-surface", default=None)
+    ap.add_argument("--surface-max-distance", type=float, default=0.1)
+    ap.add_argument("--surface-thresholds", type=lambda text: tuple(float(v) for v in text.split(",")), default=(0.01, 0.02, 0.05))
+    ap.add_argument("--surfel-mesh-distance", action="store_true")
+    ap.add_argument("--surface-report", default=None)
     return ap
 
 
@@ -250,7 +281,9 @@ def main():
             median_filter_and_densify_iterations=a.median_filter_and_densify_iterations, render_dir=a.render_dir, render_every=a.render_every,
             render_radius_scale=a.render_radius_scale, place_recognition=a.place_recognition, place_min_gap=a.place_min_gap, mesh=a.mesh,
             mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
-            render_source=a.render_source, mesh_min_component=a.mesh_min_component)
+            render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
+            surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
+            surface_report=a.surface_report)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -268,6 +301,15 @@ def main():
             cleaned = (f" ({r['mesh']['components']} components before clean-up, {r['mesh']['removed_vertices']} vertices and "
                        f"{r['mesh']['removed_triangles']} triangles removed)")
         print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
+    if "surface" in r:
+        sf = r["surface"]
+        if "accuracy" in sf:
+            print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, within {sf['max_distance']:g} m)", sf["accuracy"]))
+            print(surface_eval.format_summary("completeness (ground truth -> mesh)", sf["completeness"]))
+            for row in sf["f_scores"]:
+                print(f"  at {row['threshold']:g} m: precision {row['precision']:.4f}, recall {row['recall']:.4f}, F-score {row['f_score']:.4f}")
+        if "surfel_mesh_distance" in sf:
+            print(surface_eval.format_summary("surfel centres -> mesh", sf["surfel_mesh_distance"]))
     if "ate" in r:
         print(f"ATE RMSE {r['ate']['rmse']:.6f} m over {r['ate']['pairs']} poses")
 

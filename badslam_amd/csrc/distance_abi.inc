@@ -23,8 +23,8 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream_, uint32_t point_
                               float* out_distance, uint32_t* out_triangle, uint64_t* grid_cells, uint64_t* grid_entries) {
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx) return fail(BSLAM_ERR_INVALID_ARGUMENT, "context is null");
-  if (!(std::isfinite(max_distance) && max_distance > 0.f)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "max_distance must be finite and > 0");
-  if (!(std::isfinite(cell_size) && cell_size > 0.f)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "cell_size must be finite and > 0");
+  if (!finite_positive(max_distance)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "max_distance must be finite and > 0");
+  if (!finite_positive(cell_size)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "cell_size must be finite and > 0");
   if (max_grid_entries == 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "max_grid_entries must be >= 1");
   if (!out_distance) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_distance is null");
   const size_t N = point_count, V = vertex_count, T = triangle_count;
@@ -37,7 +37,7 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream_, uint32_t point_
   const float R = max_distance;
   const float r_squared = R * R;
   const float inv_cell = 1.0f / cell_size;
-  if (!(std::isfinite(inv_cell) && inv_cell > 0.f)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "1 / cell_size is not a positive float");
+  if (!finite_positive(inv_cell)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "1 / cell_size is not a positive float");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   const dim3 block(256);
   uint64_t cells = 0, entries = 0;
@@ -45,10 +45,7 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream_, uint32_t point_
   PmdGrid g;
   std::memset(&g, 0, sizeof(g));
   if (T != 0) {
-    if (V == 0) {   // no vertex: every index is beyond
-      BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-      return mesh_error(kMeshBadIndex, "bslam_point_mesh_distance");
-    }
+    if (V == 0) return empty_mesh(stream, T, "bslam_point_mesh_distance");   // every index is beyond
     if ((rc = ctx->distance.reserve(kPmdWords * sizeof(uint32_t)))) return rc;
     uint32_t* words = (uint32_t*)ctx->distance.ptr;
     BSLAM_HIP_TRY(hipMemsetAsync(words, 0, kPmdWords * sizeof(uint32_t), stream));
@@ -103,19 +100,14 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream_, uint32_t point_
   }
   // scratch (u32 units; every piece 16 byte aligned): words | records float4[9 T] | cell_count[cells] | cell_start[cells + 1] |
   //   point_start[cells + 1] | tile sums | list[entries] | point_cell[N] | sorted[N]
-  const auto pad = [](size_t n) { return (n + 3) & ~(size_t)3; };
   const size_t tiles = cells / kScanTile + 2;
-  const size_t total_words = kPmdWords + 4 * (size_t)kPmdRecordQuads * T + pad(cells) + 2 * pad(cells + 1) + pad(tiles) + pad(entries) + 2 * pad(N);
-  if ((rc = ctx->distance.reserve(total_words * sizeof(uint32_t)))) return rc;
-  uint32_t* w = (uint32_t*)ctx->distance.ptr + kPmdWords;
-  float4* records = (float4*)w; w += 4 * (size_t)kPmdRecordQuads * T;
-  uint32_t* cell_count = w; w += pad(cells);
-  uint32_t* cell_start = w; w += pad(cells + 1);
-  uint32_t* point_start = w; w += pad(cells + 1);
-  uint32_t* tile_sums = w; w += pad(tiles);
-  uint32_t* list = w; w += pad(entries);
-  uint32_t* point_cell = w; w += pad(N);
-  uint32_t* sorted = w;
+  float4* records;
+  uint32_t *cell_count, *cell_start, *point_start, *tile_sums, *list, *point_cell, *sorted;
+  if ((rc = carve(ctx->distance, [&](Carver& c) {
+         c.take<uint32_t>(kPmdWords, 16); records = c.take<float4>((size_t)kPmdRecordQuads * T, 16); cell_count = c.take<uint32_t>(cells, 16);
+         cell_start = c.take<uint32_t>(cells + 1, 16); point_start = c.take<uint32_t>(cells + 1, 16); tile_sums = c.take<uint32_t>(tiles, 16);
+         list = c.take<uint32_t>(entries, 16); point_cell = c.take<uint32_t>(N, 16); sorted = c.take<uint32_t>(N, 16);
+       }))) return rc;
   BSLAM_HIP_TRY(hipMemsetAsync(cell_count, 0, cells * sizeof(uint32_t), stream));
   hipLaunchKernelGGL(pmd_records_kernel, flat_grid(T), block, 0, stream, g, vertex_count, triangle_count, positions, indices, R, records, cell_count);
   BSLAM_HIP_TRY(hipGetLastError());

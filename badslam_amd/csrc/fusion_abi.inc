@@ -27,6 +27,19 @@ static int make_volume_img(const bslam_buffer2d* b, const VolumeDev& v, const ch
   return BSLAM_OK;
 }
 
+// A volume and its buffers as a call takes them: the tsdf image always, the count and colour images where given; an absent one
+// stays an empty Img, which overlaps nothing.
+struct VolumeArgs { VolumeDev vol; Img tsdf, count, color; };
+static int load_volume(const bslam_volume* v, const bslam_buffer2d* tsdf, const bslam_buffer2d* count, const bslam_buffer2d* color, VolumeArgs* out) {
+  *out = VolumeArgs{};
+  int rc = check_volume(v, &out->vol);
+  if (rc) return rc;
+  if ((rc = make_volume_img(tsdf, out->vol, "tsdf volume", &out->tsdf))) return rc;
+  if (count && (rc = make_volume_img(count, out->vol, "count volume", &out->count))) return rc;
+  if (color && (rc = make_volume_img(color, out->vol, "colour volume", &out->color))) return rc;
+  return BSLAM_OK;
+}
+
 }  // namespace bslam
 
 extern "C" {
@@ -37,18 +50,12 @@ int bslam_fuse_keyframes(bslam_context* ctx, void* stream_, const bslam_camera4f
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !depth_camera || !depth_params || !tsdf || !count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (color && !color_camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "a colour volume needs the colour camera");
-  VolumeDev vol;
-  int rc = check_volume(volume, &vol);
+  VolumeArgs v;
+  int rc = load_volume(volume, tsdf, count, color, &v);
   if (rc) return rc;
+  const VolumeDev& vol = v.vol;
   if (!finite_positive(truncation)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "truncation must be finite and > 0");
-  Img out[3];
-  out[2].base = nullptr; out[2].pitch = 0; out[2].width = 0; out[2].height = 0;
-  if ((rc = make_volume_img(tsdf, vol, "tsdf volume", &out[0]))) return rc;
-  if ((rc = make_volume_img(count, vol, "count volume", &out[1]))) return rc;
-  if (color && (rc = make_volume_img(color, vol, "colour volume", &out[2]))) return rc;
-  for (int a = 0; a < 3; ++a)
-    for (int b = a + 1; b < 3; ++b)
-      if (out[a].base && out[b].base && overlap(out[a], out[b])) return fail(BSLAM_ERR_INVALID_ARGUMENT, "two output volumes overlap");
+  if (overlap(v.tsdf, v.count) || overlap(v.tsdf, v.color) || overlap(v.count, v.color)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "two output volumes overlap");
   // The keyframe list goes through the setup of every call that walks one; fusion reads no surfels, so it hands that setup an
   // empty surfel buffer of the required height.
   bslam_buffer2d no_surfels;
@@ -60,10 +67,10 @@ int bslam_fuse_keyframes(bslam_context* ctx, void* stream_, const bslam_camera4f
   const dim3 grid(bricks_x * bricks_y * bricks_z);   // <= 2^30 / 2 bricks (every dimension is >= 2)
   if (color)
     hipLaunchKernelGGL(fuse_keyframes_kernel<true>, grid, dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, keyframe_count, vol, truncation,
-                       ctx->culling ? 1 : 0, bricks_x, bricks_y, out[0], out[1], out[2], cull_stats_ptr(ctx));
+                       ctx->culling ? 1 : 0, bricks_x, bricks_y, v.tsdf, v.count, v.color, cull_stats_ptr(ctx));
   else
     hipLaunchKernelGGL(fuse_keyframes_kernel<false>, grid, dim3(256), 0, stream, c, (const KfDev*)ctx->kf_table.ptr, keyframe_count, vol, truncation,
-                       ctx->culling ? 1 : 0, bricks_x, bricks_y, out[0], out[1], out[2], cull_stats_ptr(ctx));
+                       ctx->culling ? 1 : 0, bricks_x, bricks_y, v.tsdf, v.count, v.color, cull_stats_ptr(ctx));
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }
@@ -74,25 +81,22 @@ int bslam_extract_mesh(bslam_context* ctx, void* stream_, const bslam_volume* vo
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !tsdf || !count || !vertex_count || !triangle_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (min_count < 1) return fail(BSLAM_ERR_INVALID_ARGUMENT, "min_count must be >= 1");
-  MeshVolume m;
-  int rc = check_volume(volume, &m.vol);
+  VolumeArgs v;
+  int rc = load_volume(volume, tsdf, count, color, &v);
   if (rc) return rc;
-  m.color.base = nullptr; m.color.pitch = 0; m.color.width = 0; m.color.height = 0;
-  if ((rc = make_volume_img(tsdf, m.vol, "tsdf volume", &m.tsdf))) return rc;
-  if ((rc = make_volume_img(count, m.vol, "count volume", &m.count))) return rc;
-  if (color && (rc = make_volume_img(color, m.vol, "colour volume", &m.color))) return rc;
+  MeshVolume m;
+  m.vol = v.vol; m.tsdf = v.tsdf; m.count = v.count; m.color = v.color;
   m.min_count = min_count;
   m.cells = (uint32_t)(m.vol.nx - 1) * (uint32_t)(m.vol.ny - 1) * (uint32_t)(m.vol.nz - 1);
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   // scratch: active u8[cells] | quads u8[cells] | vertex_id u32[cells] | quad_offset u32[cells] | tile sums | totals u32[2]
-  const size_t n = ((size_t)m.cells + 63) & ~(size_t)63, tiles = n / kScanTile + 2;
-  if ((rc = ctx->fusion.reserve(2 * n + (2 * n + tiles + 16) * sizeof(uint32_t)))) return rc;
-  uint8_t* active = (uint8_t*)ctx->fusion.ptr;
-  uint8_t* quads = active + n;
-  uint32_t* vertex_id = (uint32_t*)(quads + n);
-  uint32_t* quad_offset = vertex_id + n;
-  uint32_t* tile_sums = quad_offset + n;
-  uint32_t* totals = tile_sums + tiles;
+  const size_t n = ((size_t)m.cells + 63) & ~(size_t)63, tiles = n / kScanTile + 2;   // the cells padded to 64: every array starts 64 byte aligned
+  uint8_t *active, *quads;
+  uint32_t *vertex_id, *quad_offset, *tile_sums, *totals;
+  if ((rc = carve(ctx->fusion, [&](Carver& c) {
+         active = c.take<uint8_t>(n, 64); quads = c.take<uint8_t>(n, 64); vertex_id = c.take<uint32_t>(n, 64); quad_offset = c.take<uint32_t>(n, 64);
+         tile_sums = c.take<uint32_t>(tiles); totals = c.take<uint32_t>(16);
+       }))) return rc;
   const dim3 grid = flat_grid(m.cells), block(256);
   hipLaunchKernelGGL(mesh_flag_cells_kernel, grid, block, 0, stream, m, active);
   BSLAM_HIP_TRY(hipGetLastError());

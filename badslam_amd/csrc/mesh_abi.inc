@@ -29,6 +29,12 @@ static int mesh_error(uint32_t bits, const char* call) {
   return BSLAM_OK;
 }
 
+// The V == 0 case of a mesh call: nothing is launched, and any triangle names a vertex that does not exist.
+static int empty_mesh(hipStream_t stream, size_t triangles, const char* call) {
+  BSLAM_HIP_TRY(hipStreamSynchronize(stream));
+  return triangles != 0 ? mesh_error(kMeshBadIndex, call) : BSLAM_OK;
+}
+
 }  // namespace bslam
 
 extern "C" {
@@ -42,17 +48,13 @@ int bslam_mesh_components(bslam_context* ctx, void* stream_, uint32_t vertex_cou
   int rc = check_mesh_spans(spans, 3);
   if (rc) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  if (V == 0) {   // no vertex: any triangle names one that does not exist
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-    if (T != 0) return mesh_error(kMeshBadIndex, "bslam_mesh_components");
-    *component_count = 0;
-    return BSLAM_OK;
+  if (V == 0) {
+    if ((rc = empty_mesh(stream, T, "bslam_mesh_components")) == BSLAM_OK) *component_count = 0;
+    return rc;
   }
   // scratch: parent u32[V] | size_of_root u32[V] | words u32[2] = {error bits, component count}
-  if ((rc = ctx->fusion.reserve((2 * V + 16) * sizeof(uint32_t)))) return rc;
-  uint32_t* parent = (uint32_t*)ctx->fusion.ptr;
-  uint32_t* size_of_root = parent + V;
-  uint32_t* words = size_of_root + V;
+  uint32_t *parent, *size_of_root, *words;
+  if ((rc = carve(ctx->fusion, [&](Carver& c) { parent = c.take<uint32_t>(V); size_of_root = c.take<uint32_t>(V); words = c.take<uint32_t>(16); }))) return rc;
   const dim3 block(256);
   hipLaunchKernelGGL(mesh_init_kernel, flat_grid(V), block, 0, stream, vertex_count, parent, size_of_root, words);
   BSLAM_HIP_TRY(hipGetLastError());
@@ -92,22 +94,18 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   if (rc) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   if (V == 0) {
-    BSLAM_HIP_TRY(hipStreamSynchronize(stream));
-    if (T != 0) return mesh_error(kMeshBadIndex, "bslam_filter_mesh");
-    *out_vertex_count = 0;
-    *out_triangle_count = 0;
-    return BSLAM_OK;
+    if ((rc = empty_mesh(stream, T, "bslam_filter_mesh")) == BSLAM_OK) *out_vertex_count = *out_triangle_count = 0;
+    return rc;
   }
   // scratch: keep_vertex u8[V] | keep_triangle u8[T] | vertex_rank u32[V] | triangle_rank u32[T] | tile sums |
   //          words u32[4] = {error bits, unused, kept vertices, kept triangles}
-  const size_t nv = (V + 63) & ~(size_t)63, nt = (T + 63) & ~(size_t)63, tiles = std::max(nv, nt) / kScanTile + 2;
-  if ((rc = ctx->fusion.reserve(nv + nt + (nv + nt + tiles + 16) * sizeof(uint32_t)))) return rc;
-  uint8_t* keep_vertex = (uint8_t*)ctx->fusion.ptr;
-  uint8_t* keep_triangle = keep_vertex + nv;
-  uint32_t* vertex_rank = (uint32_t*)(keep_triangle + nt);
-  uint32_t* triangle_rank = vertex_rank + nv;
-  uint32_t* tile_sums = triangle_rank + nt;
-  uint32_t* words = tile_sums + tiles;
+  const size_t nv = (V + 63) & ~(size_t)63, nt = (T + 63) & ~(size_t)63, tiles = std::max(nv, nt) / kScanTile + 2;   // padded to 64 as in bslam_extract_mesh
+  uint8_t *keep_vertex, *keep_triangle;
+  uint32_t *vertex_rank, *triangle_rank, *tile_sums, *words;
+  if ((rc = carve(ctx->fusion, [&](Carver& c) {
+         keep_vertex = c.take<uint8_t>(nv, 64); keep_triangle = c.take<uint8_t>(nt, 64); vertex_rank = c.take<uint32_t>(nv, 64);
+         triangle_rank = c.take<uint32_t>(nt, 64); tile_sums = c.take<uint32_t>(tiles); words = c.take<uint32_t>(16);
+       }))) return rc;
   MeshFilter m;
   m.vertices = vertex_count; m.triangles = triangle_count; m.vertex_blocks = flat_grid(V).x; m.min_vertices = min_vertices;
   m.positions = positions; m.normals = normals; m.colors = (const uint32_t*)colors; m.indices = indices; m.sizes = sizes;

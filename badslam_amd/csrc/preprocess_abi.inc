@@ -18,6 +18,29 @@ static bool overlap(const Img& a, const Img& b) {
 }
 static bool rows_aligned(const Img& i, size_t bytes) { return ((uintptr_t)i.base | (uintptr_t)i.pitch) % bytes == 0; }
 
+// Bump carver over a slab: take<T>(count, alignment in bytes) hands out the next piece.  Without a base it only counts.
+struct Carver {
+  uint8_t* base;
+  size_t used;
+  template <class T> T* take(size_t count, size_t align = alignof(T)) {
+    used = (used + align - 1) / align * align;
+    T* piece = base ? (T*)(base + used) : nullptr;
+    used += count * sizeof(T);
+    return piece;
+  }
+};
+// Runs `layout` once to count the bytes, reserves them and runs it again over the slab, so the total and the pointers come from
+// the same statements.  The slab's base is aligned for every piece (hipMalloc: 256 bytes).
+template <class Layout>
+static int carve(Slab& slab, Layout layout) {
+  Carver count{nullptr, 0};
+  layout(count);
+  if (int rc = slab.reserve(count.used)) return rc;
+  Carver pieces{(uint8_t*)slab.ptr, 0};
+  layout(pieces);
+  return BSLAM_OK;
+}
+
 // The pyramid level L (1 ... 3) with in = out * 2^L in both dimensions; 0 if there is none.
 static int pyramid_level(const Img& in, const Img& out) {
   for (int level = 1; level <= 3; ++level)

@@ -19,6 +19,13 @@ static RayAuxLayout ray_aux_layout(const VolumeDev& v) {
   return l;
 }
 
+// The aux bytes as an image of one row (more beyond 2^32 - 1 bytes), for the overlap tests.
+static Img aux_img(const void* aux, size_t bytes) {
+  Img a;
+  a.base = (uint8_t*)aux; a.pitch = (uint32_t)std::min<size_t>(bytes, 0xffffffffu); a.width = 0; a.height = (int)((bytes + a.pitch - 1) / a.pitch);
+  return a;
+}
+
 // N = the number of k >= 0 with fmaf(float(k), step, min_depth) <= max_depth (t is monotone in k); refused above kRayMaxSamples.
 static int ray_sample_count(float min_depth, float max_depth, float step, int* out) {
   const double estimate = std::floor(((double)max_depth - (double)min_depth) / (double)step);
@@ -49,21 +56,17 @@ int bslam_prepare_volume_views(bslam_context* ctx, void* stream_, const bslam_vo
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !tsdf || !count || !aux) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (min_count < 1) return fail(BSLAM_ERR_INVALID_ARGUMENT, "min_count must be >= 1");
-  VolumeDev vol;
-  int rc = check_volume(volume, &vol);
+  VolumeArgs v;
+  int rc = load_volume(volume, tsdf, count, nullptr, &v);
   if (rc) return rc;
-  Img t, c;
-  if ((rc = make_volume_img(tsdf, vol, "tsdf volume", &t))) return rc;
-  if ((rc = make_volume_img(count, vol, "count volume", &c))) return rc;
-  const RayAuxLayout l = ray_aux_layout(vol);
+  const RayAuxLayout l = ray_aux_layout(v.vol);
   if ((uintptr_t)aux % 8 != 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the aux buffer must be 8 byte aligned");
   if (aux_bytes < l.bytes) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the aux buffer has %zu bytes, the volume needs %zu", aux_bytes, l.bytes);
-  Img a;   // the aux bytes as a one-row image, for the overlap test
-  a.base = (uint8_t*)aux; a.pitch = (uint32_t)std::min<size_t>(l.bytes, 0xffffffffu); a.width = 0; a.height = (int)((l.bytes + a.pitch - 1) / a.pitch);
-  if (overlap(a, t) || overlap(a, c)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the aux buffer overlaps a volume");
+  const Img a = aux_img(aux, l.bytes);
+  if (overlap(a, v.tsdf) || overlap(a, v.count)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the aux buffer overlaps a volume");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   // <= 2^30 / 8 / 8 / 2 groups: words_x * 64 <= nx + 62 and every dimension is >= 2
-  hipLaunchKernelGGL(raycast_prepare_kernel, dim3((unsigned)l.flag_bytes), dim3(256), 0, stream, vol, t, c, min_count, l.words_x, l.groups_y,
+  hipLaunchKernelGGL(raycast_prepare_kernel, dim3((unsigned)l.flag_bytes), dim3(256), 0, stream, v.vol, v.tsdf, v.count, min_count, l.words_x, l.groups_y,
                      (unsigned long long*)((uint8_t*)aux + l.bits_offset), (uint8_t*)aux);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
@@ -75,34 +78,19 @@ int bslam_raycast_volume(bslam_context* ctx, void* stream_, const bslam_volume* 
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !tsdf || !aux || !global_T_camera || !camera) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (!out_depth && !out_color && !out_normal) return fail(BSLAM_ERR_INVALID_ARGUMENT, "no output view was asked for");
-  VolumeDev vol;
-  int rc = check_volume(volume, &vol);
+  VolumeArgs v;
+  int rc = load_volume(volume, tsdf, nullptr, color, &v);
   if (rc) return rc;
-  if (camera->width <= 0 || camera->height <= 0 || (int64_t)camera->width * camera->height > 0x7fffffff)
-    return fail(BSLAM_ERR_INVALID_ARGUMENT, "the camera must have between 1 and 2^31 - 1 pixels");
-  if (!finite_positive(camera->fx) || !finite_positive(camera->fy)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "focal lengths must be positive");
+  const VolumeDev& vol = v.vol;
   if (!finite_positive(step) || !finite_positive(metres_to_depth)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "step and metres_to_depth must be finite and > 0");
   if (!finite_positive(min_depth) || !finite_positive(max_depth) || !(min_depth < max_depth)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need 0 < min_depth < max_depth, both finite");
   RayParams p;
   if ((rc = ray_sample_count(min_depth, max_depth, step, &p.samples))) return rc;
-  Img t, c;
-  c.base = nullptr; c.pitch = 0; c.width = 0; c.height = 0;
-  if ((rc = make_volume_img(tsdf, vol, "tsdf volume", &t))) return rc;
-  if (color && (rc = make_volume_img(color, vol, "colour volume", &c))) return rc;
   if ((uintptr_t)aux % 8 != 0) return fail(BSLAM_ERR_INVALID_ARGUMENT, "the aux buffer must be 8 byte aligned");
   const RayAuxLayout l = ray_aux_layout(vol);
-  Img a;
-  a.base = (uint8_t*)aux; a.pitch = (uint32_t)std::min<size_t>(l.bytes, 0xffffffffu); a.width = 0; a.height = (int)((l.bytes + a.pitch - 1) / a.pitch);
   Img view[3];
-  if ((rc = make_view(out_depth, 2, 2, "depth view", camera, &view[0]))) return rc;
-  if ((rc = make_view(out_color, 4, 4, "colour view", camera, &view[1]))) return rc;
-  if ((rc = make_view(out_normal, 12, 4, "normal view", camera, &view[2]))) return rc;
-  for (int i = 0; i < 3; ++i) {
-    if (!view[i].base) continue;
-    if (overlap(view[i], t) || (c.base && overlap(view[i], c)) || overlap(view[i], a)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "an output view overlaps the volume or the aux buffer");
-    for (int j = i + 1; j < 3; ++j)
-      if (view[j].base && overlap(view[i], view[j])) return fail(BSLAM_ERR_INVALID_ARGUMENT, "two output views overlap");
-  }
+  if ((rc = load_views(camera, {{out_depth, 2, 2, "depth view"}, {out_color, 4, 4, "colour view"}, {out_normal, 12, 4, "normal view"}},
+                       {v.tsdf, v.color, aux_img(aux, l.bytes)}, "the volume or the aux buffer", view))) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   p.min_depth = min_depth; p.step = step; p.metres_to_depth = metres_to_depth;
   p.inv_voxel = 1.0f / vol.voxel;   // IEEE single division on the host
@@ -114,7 +102,7 @@ int bslam_raycast_volume(bslam_context* ctx, void* stream_, const bslam_volume* 
   ra.words_x = l.words_x; ra.groups_x = l.words_x; ra.blocks_y = l.groups_y;
   const RayCam cam{camera->fx, camera->fy, camera->cx, camera->cy, camera->width, camera->height};
   const uint32_t tiles_x = (uint32_t)(camera->width + 15) / 16, tiles_y = (uint32_t)(camera->height + 15) / 16;   // <= 2^31 / 16 tiles in all
-  hipLaunchKernelGGL(raycast_march_kernel, dim3(tiles_x * tiles_y), dim3(256), 0, stream, *global_T_camera, cam, vol, p, ra, ctx->culling ? 1 : 0, tiles_x, t, c,
+  hipLaunchKernelGGL(raycast_march_kernel, dim3(tiles_x * tiles_y), dim3(256), 0, stream, *global_T_camera, cam, vol, p, ra, ctx->culling ? 1 : 0, tiles_x, v.tsdf, v.color,
                      view[0], view[1], view[2], cull_stats_ptr(ctx));
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;

@@ -14,6 +14,25 @@ static int make_view(const bslam_buffer2d* b, size_t elem, size_t align, const c
   return BSLAM_OK;
 }
 
+// A camera and its optional output views: the camera's pixel count and focal lengths, every view of `specs` through make_view
+// into views[], and no view may share a byte with another view or with one of `inputs` (named by inputs_name in the message).
+struct ViewSpec { const bslam_buffer2d* buffer; size_t elem, align; const char* name; };
+static int load_views(const bslam_camera4f* cam, std::initializer_list<ViewSpec> specs, std::initializer_list<Img> inputs, const char* inputs_name, Img* views) {
+  if (cam->width <= 0 || cam->height <= 0 || (int64_t)cam->width * cam->height > 0x7fffffff)
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "the camera must have between 1 and 2^31 - 1 pixels");
+  if (!finite_positive(cam->fx) || !finite_positive(cam->fy)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "focal lengths must be positive");
+  int n = 0, rc;
+  for (const ViewSpec& s : specs)
+    if ((rc = make_view(s.buffer, s.elem, s.align, s.name, cam, &views[n++]))) return rc;
+  for (int a = 0; a < n; ++a) {   // an absent view is an empty Img, which overlaps nothing
+    for (const Img& in : inputs)
+      if (overlap(views[a], in)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "an output view overlaps %s", inputs_name);
+    for (int b = a + 1; b < n; ++b)
+      if (overlap(views[a], views[b])) return fail(BSLAM_ERR_INVALID_ARGUMENT, "two output views overlap");
+  }
+  return BSLAM_OK;
+}
+
 }  // namespace bslam
 
 extern "C" {
@@ -25,9 +44,6 @@ int bslam_render_surfels(bslam_context* ctx, void* stream_, const bslam_mat3x4* 
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !camera_T_global || !camera || !surfels || !surfels->address) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (!out_depth && !out_index && !out_color && !out_normal) return fail(BSLAM_ERR_INVALID_ARGUMENT, "no output view was asked for");
-  if (camera->width <= 0 || camera->height <= 0 || (int64_t)camera->width * camera->height > 0x7fffffff)
-    return fail(BSLAM_ERR_INVALID_ARGUMENT, "the camera must have between 1 and 2^31 - 1 pixels");
-  if (!finite_positive(camera->fx) || !finite_positive(camera->fy)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "focal lengths must be positive");
   if (!finite_positive(radius_scale) || !finite_positive(metres_to_depth)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "radius_scale and metres_to_depth must be > 0");
   if (!(min_depth > 0.0f) || !(max_depth >= min_depth)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need 0 < min_depth <= max_depth");
   if (surfels->height <= BSLAM_SURFEL_COLOR || surfels->width < 0 || surfels->pitch < (size_t)surfels->width * sizeof(float))
@@ -38,16 +54,8 @@ int bslam_render_surfels(bslam_context* ctx, void* stream_, const bslam_mat3x4* 
   rows_img.base = (uint8_t*)surfels->address; rows_img.pitch = (uint32_t)surfels->pitch; rows_img.width = surfels->width; rows_img.height = surfels->height;
   if (surfels->pitch > 0xffffffffu || !rows_aligned(rows_img, sizeof(float))) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfel rows must be 4 byte aligned");
   Img view[4];
-  if ((rc = make_view(out_depth, 2, 2, "depth view", camera, &view[0]))) return rc;
-  if ((rc = make_view(out_index, 4, 4, "index view", camera, &view[1]))) return rc;
-  if ((rc = make_view(out_color, 4, 4, "colour view", camera, &view[2]))) return rc;
-  if ((rc = make_view(out_normal, 12, 4, "normal view", camera, &view[3]))) return rc;
-  for (int a = 0; a < 4; ++a) {
-    if (!view[a].base) continue;
-    if (overlap(view[a], rows_img)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "an output view overlaps the surfel rows");
-    for (int b = a + 1; b < 4; ++b)
-      if (view[b].base && overlap(view[a], view[b])) return fail(BSLAM_ERR_INVALID_ARGUMENT, "two output views overlap");
-  }
+  if ((rc = load_views(camera, {{out_depth, 2, 2, "depth view"}, {out_index, 4, 4, "index view"}, {out_color, 4, 4, "colour view"}, {out_normal, 12, 4, "normal view"}},
+                       {rows_img}, "the surfel rows", view))) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   const int pixels = camera->width * camera->height;
   if ((rc = ctx->zbuffer.reserve((size_t)pixels * sizeof(unsigned long long)))) return rc;

@@ -96,6 +96,28 @@ def _f(a):
     return a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+def _u8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint8))
+
+
+def _u16(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint16))
+
+
+def _u32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint32))
+
+
+_VIEW_ARRAYS = {"depth": ((), np.uint16), "index": ((), np.uint32), "color": ((4,), np.uint8), "normal": ((3,), np.float32)}
+
+
+def _alloc_views(views, allowed, h, w):
+    """The zeroed (h, w) output arrays of the views named in `views`, which must be some of `allowed`."""
+    if not views or set(views) - set(allowed):
+        raise ValueError(f"views must name some of {', '.join(allowed)} (got {sorted(views)})")
+    return {name: np.zeros((h, w) + _VIEW_ARRAYS[name][0], _VIEW_ARRAYS[name][1]) for name in allowed if name in views}
+
+
 def pose7(se3f):
     return np.array(list(se3f.q) + list(se3f.t), np.float32)
 
@@ -631,7 +653,7 @@ class DirectBA:
         cap = max(1, self.surfels_size())
         pos, col, nrm = np.zeros((cap, 3), np.float32), np.zeros((cap, 3), np.uint8), np.zeros((cap, 3), np.float32)
         n = C.c_uint64()
-        self._check(self.L.bsh_export_point_cloud(self._ba, self.stream, cap, _f(pos), col.ctypes.data_as(C.POINTER(C.c_uint8)), _f(nrm), C.byref(n)))
+        self._check(self.L.bsh_export_point_cloud(self._ba, self.stream, cap, _f(pos), _u8(col), _f(nrm), C.byref(n)))
         return pos[:n.value], col[:n.value], nrm[:n.value]
 
     def RenderModel(self, global_T_camera, camera=None, min_depth=0.05, max_depth=50.0, radius_scale=1.0, views=("depth", "color")):
@@ -642,31 +664,22 @@ class DirectBA:
         (h, w, 4) uint8, "normal" (h, w, 3) float32 in the camera frame -- and "camera_T_global" (3, 4) float32, the matrix
         the kernels took.  Surfels whose ball leaves [min_depth, max_depth] metres are dropped.  A sharded (multi-GPU) object
         renders its local shard only."""
-        unknown = set(views) - {"depth", "index", "color", "normal"}
-        if unknown or not views:
-            raise ValueError(f"views must name some of depth, index, color, normal (got {sorted(views)})")
+        params, w, h = self._view_camera(camera)
+        out = _alloc_views(views, ("depth", "index", "color", "normal"), h, w)
+        ptr = lambda name, pointer: pointer(out[name]) if name in out else None
+        out["camera_T_global"] = np.zeros((3, 4), np.float32)
+        options = np.array([min_depth, max_depth, radius_scale], np.float32)
+        self._check(self.L.bsh_render_model(self._ba, self.stream, _f(pose7(global_T_camera)), _f(params), w, h, _f(options), ptr("depth", _u16), ptr("index", _u32),
+                                            ptr("color", _u8), ptr("normal", _f), _f(out["camera_T_global"])))
+        return out
+
+    def _view_camera(self, camera):
+        """(fx fy cx cy as float32, width, height) of `camera` (abi.Camera4f), by default of the depth camera."""
         if camera is None:
             size = (C.c_int * 2)()
             self._check(self.L.bsh_depth_camera_size(self._ba, size))
-            params, w, h = self.intrinsics()[1], size[0], size[1]
-        else:
-            params, w, h = np.array([camera.fx, camera.fy, camera.cx, camera.cy], np.float32), int(camera.width), int(camera.height)
-        out = {}
-        if "depth" in views:
-            out["depth"] = np.zeros((h, w), np.uint16)
-        if "index" in views:
-            out["index"] = np.zeros((h, w), np.uint32)
-        if "color" in views:
-            out["color"] = np.zeros((h, w, 4), np.uint8)
-        if "normal" in views:
-            out["normal"] = np.zeros((h, w, 3), np.float32)
-        out["camera_T_global"] = np.zeros((3, 4), np.float32)
-        ptr = lambda name, ctype: out[name].ctypes.data_as(C.POINTER(ctype)) if name in out else None
-        options = np.array([min_depth, max_depth, radius_scale], np.float32)
-        self._check(self.L.bsh_render_model(self._ba, self.stream, _f(pose7(global_T_camera)), _f(np.ascontiguousarray(params, np.float32)), w, h, _f(options),
-                                            ptr("depth", C.c_uint16), ptr("index", C.c_uint32), ptr("color", C.c_uint8), ptr("normal", C.c_float),
-                                            _f(out["camera_T_global"])))
-        return out
+            return np.ascontiguousarray(self.intrinsics()[1], np.float32), size[0], size[1]
+        return np.array([camera.fx, camera.fy, camera.cx, camera.cy], np.float32), int(camera.width), int(camera.height)
 
     # --- volumetric fusion and meshing (bslam_fuse_keyframes, bslam_extract_mesh)
     def ModelBounds(self):
@@ -699,13 +712,12 @@ class DirectBA:
             self._check(self.L.bsh_extract_mesh_filtered(self._ba, self.stream, int(min_count), int(min_component_vertices), counts, report3 if report else None))
             if report:
                 sizes = np.zeros(report3[0], np.uint32)
-                self._check(self.L.bsh_mesh_component_sizes(sizes.ctypes.data_as(C.POINTER(C.c_uint32)), len(sizes)))
+                self._check(self.L.bsh_mesh_component_sizes(_u32(sizes), len(sizes)))
                 info = dict(components=int(report3[0]), removed_vertices=int(report3[1]), removed_triangles=int(report3[2]), sizes_descending=sizes)
         V, T = int(counts[0]), int(counts[1])
         out = dict(positions=np.zeros((V, 3), np.float32), normals=np.zeros((V, 3), np.float32), colors=np.zeros((V, 4), np.uint8),
                    triangles=np.zeros((T, 3), np.uint32))
-        self._check(self.L.bsh_mesh_copy(_f(out["positions"]), _f(out["normals"]), out["colors"].ctypes.data_as(C.POINTER(C.c_uint8)),
-                                         out["triangles"].ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._check(self.L.bsh_mesh_copy(_f(out["positions"]), _f(out["normals"]), _u8(out["colors"]), _u32(out["triangles"])))
         return (out, info) if report else out
 
     def MeshComponents(self, mesh):
@@ -714,9 +726,8 @@ class DirectBA:
         V = len(mesh["positions"])
         tri = np.ascontiguousarray(mesh["triangles"], np.uint32).reshape(-1, 3)
         labels, sizes = np.zeros(V, np.uint32), np.zeros(V, np.uint32)
-        u32p = C.POINTER(C.c_uint32)
         n = C.c_uint32()
-        self._check(self.L.bsh_mesh_components(self._ba, self.stream, V, len(tri), tri.ctypes.data_as(u32p), labels.ctypes.data_as(u32p), sizes.ctypes.data_as(u32p),
+        self._check(self.L.bsh_mesh_components(self._ba, self.stream, V, len(tri), _u32(tri), _u32(labels), _u32(sizes),
                                                C.byref(n)))
         return labels, sizes
 
@@ -739,9 +750,8 @@ class DirectBA:
         tri = np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
         distance, triangle = np.zeros(len(pts), np.float32), np.zeros(len(pts), np.uint32)
         cell, grid = C.c_float(), (C.c_uint64 * 2)()
-        u32p = C.POINTER(C.c_uint32)
-        self._check(self.L.bsh_point_mesh_distance(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), tri.ctypes.data_as(u32p), float(max_distance),
-                                                   0.0 if cell_size is None else float(cell_size), int(max_grid_entries), _f(distance), triangle.ctypes.data_as(u32p),
+        self._check(self.L.bsh_point_mesh_distance(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), _u32(tri), float(max_distance),
+                                                   0.0 if cell_size is None else float(cell_size), int(max_grid_entries), _f(distance), _u32(triangle),
                                                    C.byref(cell), grid))
         return self._distance_result(distance, triangle, cell, grid)
 
@@ -752,7 +762,7 @@ class DirectBA:
         self._check(self.L.bsh_surfel_mesh_distance(self._ba, self.stream, float(max_distance), 0.0 if cell_size is None else float(cell_size), int(max_grid_entries),
                                                     C.byref(count), C.byref(cell), grid))
         distance, triangle = np.zeros(count.value, np.float32), np.zeros(count.value, np.uint32)
-        self._check(self.L.bsh_distance_copy(_f(distance), triangle.ctypes.data_as(C.POINTER(C.c_uint32))))
+        self._check(self.L.bsh_distance_copy(_f(distance), _u32(triangle)))
         return self._distance_result(distance, triangle, cell, grid)
 
     def Volume(self):
@@ -762,8 +772,7 @@ class DirectBA:
         self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), None, None, None))
         nx, ny, nz = dims[0], dims[1], dims[2]
         tsdf, count, color = np.zeros((nz, ny, nx), np.float32), np.zeros((nz, ny, nx), np.uint32), np.zeros((nz, ny, nx, 4), np.uint8)
-        self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), _f(tsdf), count.ctypes.data_as(C.POINTER(C.c_uint32)),
-                                      color.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._check(self.L.bsh_volume(self._ba, self.stream, dims, _f(fl), _f(tsdf), _u32(count), _u8(color)))
         return dict(origin=fl[:3].copy(), voxel_size=float(fl[3]), truncation=float(fl[4]), dims=(nx, ny, nz), tsdf=tsdf, count=count, color=color)
 
     def RenderVolume(self, global_T_camera, camera=None, min_depth=0.05, max_depth=50.0, step=None, min_count=1, views=("depth", "color")):
@@ -773,27 +782,13 @@ class DirectBA:
         max_depth, over the samples seen by at least min_count keyframes.  Returns the dict of RenderModel with the entries named
         in `views` -- "depth" (h, w) uint16, "color" (h, w, 4) uint8, "normal" (h, w, 3) float32 in the camera frame, 0 where
         nothing is hit -- and "global_T_camera" (3, 4) float32, the matrix the kernel took.  Raises if nothing was fused."""
-        unknown = set(views) - {"depth", "color", "normal"}
-        if unknown or not views:
-            raise ValueError(f"views must name some of depth, color, normal (got {sorted(views)})")
-        if camera is None:
-            size = (C.c_int * 2)()
-            self._check(self.L.bsh_depth_camera_size(self._ba, size))
-            params, w, h = self.intrinsics()[1], size[0], size[1]
-        else:
-            params, w, h = np.array([camera.fx, camera.fy, camera.cx, camera.cy], np.float32), int(camera.width), int(camera.height)
-        out = {}
-        if "depth" in views:
-            out["depth"] = np.zeros((h, w), np.uint16)
-        if "color" in views:
-            out["color"] = np.zeros((h, w, 4), np.uint8)
-        if "normal" in views:
-            out["normal"] = np.zeros((h, w, 3), np.float32)
+        params, w, h = self._view_camera(camera)
+        out = _alloc_views(views, ("depth", "color", "normal"), h, w)
+        ptr = lambda name, pointer: pointer(out[name]) if name in out else None
         out["global_T_camera"] = np.zeros((3, 4), np.float32)
-        ptr = lambda name, ctype: out[name].ctypes.data_as(C.POINTER(ctype)) if name in out else None
         options = np.array([min_depth, max_depth, 0.0 if step is None else step], np.float32)
-        self._check(self.L.bsh_render_volume(self._ba, self.stream, _f(pose7(global_T_camera)), _f(np.ascontiguousarray(params, np.float32)), w, h, _f(options),
-                                             int(min_count), ptr("depth", C.c_uint16), ptr("color", C.c_uint8), ptr("normal", C.c_float), _f(out["global_T_camera"])))
+        self._check(self.L.bsh_render_volume(self._ba, self.stream, _f(pose7(global_T_camera)), _f(params), w, h, _f(options), int(min_count), ptr("depth", _u16),
+                                             ptr("color", _u8), ptr("normal", _f), _f(out["global_T_camera"])))
         return out
 
     def upload_keyframe_depth(self, kf_id, depth):

@@ -25,6 +25,9 @@ static thread_local std::string g_err;
   catch (const std::exception& e) { g_err = e.what(); return -1; } \
   catch (...) { g_err = "unknown exception"; return -1; }
 
+// Copy of a whole vector into a caller's array that may be null (an output that is not wanted).
+template <typename T, typename U>
+static void copy_out(T* dst, const std::vector<U>& v) { if (dst) std::memcpy(dst, v.data(), v.size() * sizeof(U)); }
 static SE3f pose_from7(const float* p) { bslam_se3f q; std::memcpy(q.q, p, 16); std::memcpy(q.t, p + 4, 12); return SE3f::FromPod(q); }
 static void pose_to7(const SE3f& T, float* p) { const bslam_se3f q = T.ToPod(); std::memcpy(p, q.q, 16); std::memcpy(p + 4, q.t, 12); }
 
@@ -174,6 +177,9 @@ int bsh_depth_camera_size(void* ba, int* size2) {
 // DirectBA::RenderModel.  camera: fx, fy, cx, cy (pixel-corner) + size; options: min_depth, max_depth, radius_scale.  Each output is a
 // row-major host image of the camera's size, or null for a view that is not wanted; camera_T_global (12 floats, may be null)
 // receives the matrix the kernels took.
+static void views_out(const DirectBA::ModelViews& v, uint16_t* depth, uint32_t* index, uint8_t* color, float* normal) {
+  copy_out(depth, v.depth); copy_out(index, v.index); copy_out(color, v.color); copy_out(normal, v.normal);
+}
 int bsh_render_model(void* ba, void* stream, const float* global_T_camera_pose7, const float* camera_params4, int width, int height, const float* options3,
                      uint16_t* depth, uint32_t* index, uint8_t* color, float* normal, float* camera_T_global) {
   BSH_TRY({
@@ -182,10 +188,7 @@ int bsh_render_model(void* ba, void* stream, const float* global_T_camera_pose7,
     o.depth = depth != nullptr; o.index = index != nullptr; o.color = color != nullptr; o.normal = normal != nullptr;
     DirectBA::ModelViews v;
     static_cast<DirectBA*>(ba)->RenderModel(static_cast<hipStream_t>(stream), pose_from7(global_T_camera_pose7), PinholeCamera4f(width, height, camera_params4), o, &v);
-    if (depth) std::memcpy(depth, v.depth.data(), v.depth.size() * sizeof(uint16_t));
-    if (index) std::memcpy(index, v.index.data(), v.index.size() * sizeof(uint32_t));
-    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
-    if (normal) std::memcpy(normal, v.normal.data(), v.normal.size() * sizeof(float));
+    views_out(v, depth, index, color, normal);
     if (camera_T_global) std::memcpy(camera_T_global, v.camera_T_global.m, sizeof(v.camera_T_global.m));
   });
 }
@@ -201,9 +204,7 @@ int bsh_render_volume(void* ba, void* stream, const float* global_T_camera_pose7
     o.depth = depth != nullptr; o.color = color != nullptr; o.normal = normal != nullptr;
     DirectBA::ModelViews v;
     static_cast<DirectBA*>(ba)->RenderVolume(static_cast<hipStream_t>(stream), pose_from7(global_T_camera_pose7), PinholeCamera4f(width, height, camera_params4), o, &v);
-    if (depth) std::memcpy(depth, v.depth.data(), v.depth.size() * sizeof(uint16_t));
-    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
-    if (normal) std::memcpy(normal, v.normal.data(), v.normal.size() * sizeof(float));
+    views_out(v, depth, nullptr, color, normal);
     if (global_T_camera) std::memcpy(global_T_camera, v.global_T_camera.m, sizeof(v.global_T_camera.m));
   });
 }
@@ -226,27 +227,22 @@ int bsh_fuse_keyframes(void* ba, void* stream, const float* origin3, float voxel
 // triangles}; bsh_mesh_copy copies it out (positions, normals: 3 floats per vertex; colors: 4 bytes per vertex; indices: 3 per
 // triangle) and drops it.
 static thread_local DirectBA::Mesh g_mesh;
-int bsh_extract_mesh(void* ba, void* stream, uint32_t min_count, uint64_t* counts2) {
-  BSH_TRY({
-    static_cast<DirectBA*>(ba)->ExtractMesh(static_cast<hipStream_t>(stream), min_count, &g_mesh);
-    counts2[0] = g_mesh.vertex_count();
-    counts2[1] = g_mesh.triangle_count();
-  });
-}
 // DirectBA::ExtractMesh with MeshOptions: as bsh_extract_mesh, then bsh_mesh_copy.  report3 (may be null; with it the report is
 // computed and kept for this thread) receives {components, removed vertices, removed triangles} of the mesh as extracted;
 // bsh_mesh_component_sizes then copies out the vertex count of every component in descending order (`components` entries).
 static thread_local DirectBA::MeshComponentReport g_mesh_report;
+static void extract_mesh(void* ba, void* stream, uint32_t min_count, uint32_t min_component_vertices, uint64_t* counts2, uint32_t* report3) {
+  static_cast<DirectBA*>(ba)->ExtractMesh(static_cast<hipStream_t>(stream), DirectBA::MeshOptions{min_count, min_component_vertices}, &g_mesh,
+                                          report3 ? &g_mesh_report : nullptr);
+  counts2[0] = g_mesh.vertex_count();
+  counts2[1] = g_mesh.triangle_count();
+  if (report3) { report3[0] = g_mesh_report.components; report3[1] = g_mesh_report.removed_vertices; report3[2] = g_mesh_report.removed_triangles; }
+}
+int bsh_extract_mesh(void* ba, void* stream, uint32_t min_count, uint64_t* counts2) { BSH_TRY(extract_mesh(ba, stream, min_count, 0, counts2, nullptr)); }
 int bsh_extract_mesh_filtered(void* ba, void* stream, uint32_t min_count, uint32_t min_component_vertices, uint64_t* counts2, uint32_t* report3) {
   BSH_TRY({
-    DirectBA::MeshOptions options;
-    options.min_count = min_count;
-    options.min_component_vertices = min_component_vertices;
     g_mesh_report = DirectBA::MeshComponentReport();
-    static_cast<DirectBA*>(ba)->ExtractMesh(static_cast<hipStream_t>(stream), options, &g_mesh, report3 ? &g_mesh_report : nullptr);
-    counts2[0] = g_mesh.vertex_count();
-    counts2[1] = g_mesh.triangle_count();
-    if (report3) { report3[0] = g_mesh_report.components; report3[1] = g_mesh_report.removed_vertices; report3[2] = g_mesh_report.removed_triangles; }
+    extract_mesh(ba, stream, min_count, min_component_vertices, counts2, report3);
   });
 }
 int bsh_mesh_component_sizes(uint32_t* sizes, uint32_t capacity) {
@@ -265,21 +261,25 @@ int bsh_mesh_components(void* ba, void* stream, uint32_t vertices, uint32_t tria
     mesh.indices.assign(indices, indices + 3 * static_cast<size_t>(triangles));
     std::vector<uint32_t> l, s;
     *components = static_cast<DirectBA*>(ba)->MeshComponents(static_cast<hipStream_t>(stream), mesh, labels ? &l : nullptr, sizes ? &s : nullptr);
-    if (labels) std::memcpy(labels, l.data(), l.size() * sizeof(uint32_t));
-    if (sizes) std::memcpy(sizes, s.data(), s.size() * sizeof(uint32_t));
+    copy_out(labels, l);
+    copy_out(sizes, s);
   });
 }
 int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
   BSH_TRY({
-    if (positions) std::memcpy(positions, g_mesh.positions.data(), g_mesh.positions.size() * sizeof(float));
-    if (normals) std::memcpy(normals, g_mesh.normals.data(), g_mesh.normals.size() * sizeof(float));
-    if (colors) std::memcpy(colors, g_mesh.colors.data(), g_mesh.colors.size() * sizeof(uchar4_t));
-    if (indices) std::memcpy(indices, g_mesh.indices.data(), g_mesh.indices.size() * sizeof(uint32_t));
+    copy_out(positions, g_mesh.positions);
+    copy_out(normals, g_mesh.normals);
+    copy_out(colors, g_mesh.colors);
+    copy_out(indices, g_mesh.indices);
     g_mesh = DirectBA::Mesh();
   });
 }
 // DirectBA::PointMeshDistance of host arrays: points 3 per point, positions 3 per vertex, indices 3 per triangle; distance and
 // triangle receive `points_count` entries; *cell_used the grid cell of the call that succeeded, grid2 = {cells, entries}.
+static void grid_out(const DirectBA::PointMeshResult& result, float* cell_used, uint64_t* grid2) {
+  if (cell_used) *cell_used = result.cell_size;
+  if (grid2) { grid2[0] = result.grid_cells; grid2[1] = result.grid_entries; }
+}
 int bsh_point_mesh_distance(void* ba, void* stream, uint64_t point_count, const float* points, uint64_t vertices, const float* positions, uint64_t triangles,
                             const uint32_t* indices, float max_distance, float cell_size, uint64_t max_grid_entries, float* distance, uint32_t* triangle,
                             float* cell_used, uint64_t* grid2) {
@@ -287,14 +287,12 @@ int bsh_point_mesh_distance(void* ba, void* stream, uint64_t point_count, const 
     DirectBA::Mesh mesh;
     mesh.positions.assign(positions, positions + 3 * vertices);
     mesh.indices.assign(indices, indices + 3 * triangles);
-    DirectBA::PointMeshOptions options;
-    options.max_distance = max_distance; options.cell_size = cell_size; options.max_grid_entries = max_grid_entries;
+    const DirectBA::PointMeshOptions options{max_distance, cell_size, max_grid_entries};
     DirectBA::PointMeshResult result;
     static_cast<DirectBA*>(ba)->PointMeshDistance(static_cast<hipStream_t>(stream), points, point_count, mesh, options, &result);
-    if (distance) std::memcpy(distance, result.distance.data(), result.distance.size() * sizeof(float));
-    if (triangle) std::memcpy(triangle, result.triangle.data(), result.triangle.size() * sizeof(uint32_t));
-    if (cell_used) *cell_used = result.cell_size;
-    if (grid2) { grid2[0] = result.grid_cells; grid2[1] = result.grid_entries; }
+    copy_out(distance, result.distance);
+    copy_out(triangle, result.triangle);
+    grid_out(result, cell_used, grid2);
   });
 }
 // DirectBA::SurfelMeshDistance in two steps, like the mesh: the call keeps its result for this thread and reports *count (the
@@ -303,19 +301,16 @@ static thread_local DirectBA::PointMeshResult g_distance;
 int bsh_surfel_mesh_distance(void* ba, void* stream, float max_distance, float cell_size, uint64_t max_grid_entries, uint64_t* count, float* cell_used,
                              uint64_t* grid2) {
   BSH_TRY({
-    DirectBA::PointMeshOptions options;
-    options.max_distance = max_distance; options.cell_size = cell_size; options.max_grid_entries = max_grid_entries;
     g_distance = DirectBA::PointMeshResult();
-    static_cast<DirectBA*>(ba)->SurfelMeshDistance(static_cast<hipStream_t>(stream), options, &g_distance);
+    static_cast<DirectBA*>(ba)->SurfelMeshDistance(static_cast<hipStream_t>(stream), DirectBA::PointMeshOptions{max_distance, cell_size, max_grid_entries}, &g_distance);
     *count = g_distance.distance.size();
-    if (cell_used) *cell_used = g_distance.cell_size;
-    if (grid2) { grid2[0] = g_distance.grid_cells; grid2[1] = g_distance.grid_entries; }
+    grid_out(g_distance, cell_used, grid2);
   });
 }
 int bsh_distance_copy(float* distance, uint32_t* triangle) {
   BSH_TRY({
-    if (distance) std::memcpy(distance, g_distance.distance.data(), g_distance.distance.size() * sizeof(float));
-    if (triangle) std::memcpy(triangle, g_distance.triangle.data(), g_distance.triangle.size() * sizeof(uint32_t));
+    copy_out(distance, g_distance.distance);
+    copy_out(triangle, g_distance.triangle);
     g_distance = DirectBA::PointMeshResult();
   });
 }
@@ -332,10 +327,10 @@ int bsh_load_ply(const char* path, uint64_t* counts4) {
 }
 int bsh_ply_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
   BSH_TRY({
-    if (positions) std::memcpy(positions, g_ply.positions.data(), g_ply.positions.size() * sizeof(float));
-    if (normals) std::memcpy(normals, g_ply.normals.data(), g_ply.normals.size() * sizeof(float));
-    if (colors) std::memcpy(colors, g_ply.colors_rgb.data(), g_ply.colors_rgb.size());
-    if (indices) std::memcpy(indices, g_ply.indices.data(), g_ply.indices.size() * sizeof(uint32_t));
+    copy_out(positions, g_ply.positions);
+    copy_out(normals, g_ply.normals);
+    copy_out(colors, g_ply.colors_rgb);
+    copy_out(indices, g_ply.indices);
     g_ply = PlyMesh();
   });
 }
@@ -348,9 +343,9 @@ int bsh_volume(void* ba, void* stream, int* dims3, float* floats5, float* tsdf, 
     dims3[0] = v.spec.nx; dims3[1] = v.spec.ny; dims3[2] = v.spec.nz;
     std::memcpy(floats5, v.spec.origin, 12);
     floats5[3] = v.spec.voxel_size; floats5[4] = v.truncation;
-    if (tsdf) std::memcpy(tsdf, v.tsdf.data(), v.tsdf.size() * sizeof(float));
-    if (count) std::memcpy(count, v.count.data(), v.count.size() * sizeof(uint32_t));
-    if (color) std::memcpy(color, v.color.data(), v.color.size() * sizeof(uchar4_t));
+    copy_out(tsdf, v.tsdf);
+    copy_out(count, v.count);
+    copy_out(color, v.color);
   });
 }
 int bsh_save_point_cloud_ply(const char* path, uint64_t count, const float* positions, const uint8_t* colors_rgb, const float* normals) {
@@ -782,7 +777,7 @@ int bsh_estimate_relative_pose(int current_id, int matched_id, int n, const doub
       for (int i = 0; i < 4; ++i) pose7[i] = e.q[i];
       for (int i = 0; i < 3; ++i) pose7[4 + i] = e.t[i];
       *inlier_count = e.inlier_count;
-      if (inliers) std::memcpy(inliers, e.inliers.data(), e.inliers.size());
+      copy_out(inliers, e.inliers);
       found = e.found ? 1 : 0;
     });
   }();

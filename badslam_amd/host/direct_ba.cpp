@@ -52,6 +52,8 @@ template class DeviceBuffer<u16>;
 template class DeviceBuffer<u32>;
 template class DeviceBuffer<uchar4_t>;
 
+static void Wait(hipStream_t stream) { HIP_OR_THROW(hipStreamSynchronize(stream)); }
+
 // ------------------------------------------------------------------------------------------------
 // Keyframe
 // ------------------------------------------------------------------------------------------------
@@ -444,35 +446,45 @@ void DirectBA::ExportToPointCloud(hipStream_t stream, PointCloud* cloud) const {
   }
 }
 
+void DirectBA::ViewImages(int w, int h, const ViewSet& want, bslam_buffer2d pods[4]) {
+  const auto ensure = [w, h](auto& image, bool wanted, int elems, bslam_buffer2d* pod) {
+    if (!wanted) return;
+    if (!image || image->width() != w * elems || image->height() != h) image.reset(new typename std::decay_t<decltype(image)>::element_type(h, w * elems));
+    *pod = image->ToPod();
+    pod->width = w;   // the normal image holds 3 floats, one element of 12 bytes, per pixel
+  };
+  ensure(render_depth_, want.depth, 1, &pods[0]);
+  ensure(render_index_, want.index, 1, &pods[1]);
+  ensure(render_color_, want.color, 1, &pods[2]);
+  ensure(render_normal_, want.normal, 3, &pods[3]);
+}
+
+void DirectBA::DownloadViews(hipStream_t stream, const ViewSet& want, ModelViews* views) const {
+  const size_t w = views->width, pixels = w * views->height;
+  views->depth.clear(); views->index.clear(); views->color.clear(); views->normal.clear();
+  if (want.depth) { views->depth.resize(pixels); render_depth_->Download(stream, views->depth.data(), w * sizeof(u16)); }
+  if (want.index) { views->index.resize(pixels); render_index_->Download(stream, views->index.data(), w * sizeof(u32)); }
+  if (want.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), w * sizeof(uchar4_t)); }
+  if (want.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), w * 3 * sizeof(float)); }
+}
+
 void DirectBA::RenderModel(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const RenderOptions& options, ModelViews* views) {
   const int w = camera.width(), h = camera.height();
   if (w <= 0 || h <= 0) throw std::invalid_argument("RenderModel: the camera has no pixels");
-  if (!options.depth && !options.index && !options.color && !options.normal) throw std::invalid_argument("RenderModel: no view was asked for");
-  const auto fits = [w, h](int bw, int bh, int elems) { return bw == w * elems && bh == h; };
-  if (options.depth && !(render_depth_ && fits(render_depth_->width(), render_depth_->height(), 1))) render_depth_.reset(new DeviceBuffer<u16>(h, w));
-  if (options.index && !(render_index_ && fits(render_index_->width(), render_index_->height(), 1))) render_index_.reset(new DeviceBuffer<u32>(h, w));
-  if (options.color && !(render_color_ && fits(render_color_->width(), render_color_->height(), 1))) render_color_.reset(new DeviceBuffer<uchar4_t>(h, w));
-  if (options.normal && !(render_normal_ && fits(render_normal_->width(), render_normal_->height(), 3))) render_normal_.reset(new DeviceBuffer<float>(h, 3 * w));
-  bslam_buffer2d depth, index, color, normal;
-  if (options.depth) depth = render_depth_->ToPod();
-  if (options.index) index = render_index_->ToPod();
-  if (options.color) color = render_color_->ToPod();
-  if (options.normal) { normal = render_normal_->ToPod(); normal.width = w; }   // 12 bytes per pixel
+  const ViewSet want{options.depth, options.index, options.color, options.normal};
+  if (!want.depth && !want.index && !want.color && !want.normal) throw std::invalid_argument("RenderModel: no view was asked for");
+  bslam_buffer2d pods[4];
+  ViewImages(w, h, want, pods);
   const bslam_camera4f cam = camera.pod();
   const bslam_buffer2d surfels = surfels_->ToPod();
   views->width = w;
   views->height = h;
   views->camera_T_global = global_T_camera.Inverse().Matrix3x4();
   Check(bslam_render_surfels(ctx_, stream, &views->camera_T_global, &cam, surfels_size_, &surfels, options.min_depth, options.max_depth, options.radius_scale,
-                             1.0f / raw_to_float_depth_, options.depth ? &depth : nullptr, options.index ? &index : nullptr,
-                             options.color ? &color : nullptr, options.normal ? &normal : nullptr),
+                             1.0f / raw_to_float_depth_, want.depth ? &pods[0] : nullptr, want.index ? &pods[1] : nullptr, want.color ? &pods[2] : nullptr,
+                             want.normal ? &pods[3] : nullptr),
         "bslam_render_surfels");
-  const size_t pixels = static_cast<size_t>(w) * h;
-  views->depth.clear(); views->index.clear(); views->color.clear(); views->normal.clear();
-  if (options.depth) { views->depth.resize(pixels); render_depth_->Download(stream, views->depth.data(), static_cast<size_t>(w) * sizeof(u16)); }
-  if (options.index) { views->index.resize(pixels); render_index_->Download(stream, views->index.data(), static_cast<size_t>(w) * sizeof(u32)); }
-  if (options.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), static_cast<size_t>(w) * sizeof(uchar4_t)); }
-  if (options.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), static_cast<size_t>(w) * 3 * sizeof(float)); }
+  DownloadViews(stream, want, views);
 }
 
 static bslam_volume VolumePod(const DirectBA::VolumeSpec& spec) {
@@ -481,6 +493,11 @@ static bslam_volume VolumePod(const DirectBA::VolumeSpec& spec) {
   v.voxel_size = spec.voxel_size;
   v.nx = spec.nx; v.ny = spec.ny; v.nz = spec.nz;
   return v;
+}
+
+DirectBA::FusedVolume DirectBA::Fused(const char* caller) const {
+  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error(std::string(caller) + ": no fused volume (call FuseKeyframes first)");
+  return FusedVolume{VolumePod(volume_spec_), volume_tsdf_->ToPod(), volume_count_->ToPod(), volume_color_->ToPod()};
 }
 
 void DirectBA::FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation) {
@@ -511,37 +528,23 @@ void DirectBA::FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float t
   volume_truncation_ = truncation;
 }
 
-void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) {
-  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("ExtractMesh: no fused volume (call FuseKeyframes first)");
-  const bslam_volume vol = VolumePod(volume_spec_);
-  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
+DirectBA::DeviceMesh DirectBA::ExtractDeviceMesh(hipStream_t stream, u32 min_count) {
+  const FusedVolume v = Fused("ExtractMesh");
   u32 vertices = 0, triangles = 0;
-  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, min_count, 0, 0, nullptr, nullptr, nullptr, nullptr, &vertices, &triangles),
+  Check(bslam_extract_mesh(ctx_, stream, &v.vol, &v.tsdf, &v.count, &v.color, min_count, 0, 0, nullptr, nullptr, nullptr, nullptr, &vertices, &triangles),
         "bslam_extract_mesh");
-  mesh->positions.assign(3 * static_cast<size_t>(vertices), 0.f);
-  mesh->normals.assign(3 * static_cast<size_t>(vertices), 0.f);
-  mesh->colors.assign(vertices, uchar4_t{0, 0, 0, 0});
-  mesh->indices.assign(3 * static_cast<size_t>(triangles), 0u);
-  KeepDeviceMesh(nullptr, nullptr, 0, 0);
-  if (vertices == 0) return;
-  // one-row device images; three floats per vertex do not fit an int width beyond 2^31 / 3 vertices, far above the 2^30 cells
-  std::unique_ptr<DeviceBuffer<float>> positions_owner(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
-  std::unique_ptr<DeviceBuffer<u32>> indices_owner(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
-  DeviceBuffer<float>& positions = *positions_owner;
-  DeviceBuffer<u32>& indices = *indices_owner;
-  DeviceBuffer<float> normals(1, static_cast<int>(3 * vertices));
-  DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
+  KeepDeviceMesh(DeviceMesh());
+  DeviceMesh m(vertices, triangles);
+  if (vertices == 0) return m;
   u32 v2 = 0, t2 = 0;
-  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, min_count, vertices, triangles, positions.address(), normals.address(), colors.address(),
-                           indices.address(), &v2, &t2),
+  Check(bslam_extract_mesh(ctx_, stream, &v.vol, &v.tsdf, &v.count, &v.color, min_count, vertices, triangles, m.positions->address(), m.normals->address(),
+                           m.colors->address(), m.indices->address(), &v2, &t2),
         "bslam_extract_mesh");
   if (v2 != vertices || t2 != triangles) throw std::runtime_error("ExtractMesh: the volume changed between the two extraction calls");
-  KeepDeviceMesh(std::move(positions_owner), std::move(indices_owner), vertices, triangles);   // for SurfelMeshDistance
-  positions.Download(stream, mesh->positions.data(), mesh->positions.size() * sizeof(float));
-  normals.Download(stream, mesh->normals.data(), mesh->normals.size() * sizeof(float));
-  colors.Download(stream, mesh->colors.data(), mesh->colors.size() * sizeof(uchar4_t));
-  if (triangles) indices.Download(stream, mesh->indices.data(), mesh->indices.size() * sizeof(u32));
+  return m;
 }
+
+void DirectBA::ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh) { ExtractMesh(stream, MeshOptions{min_count, 0}, mesh, nullptr); }
 
 // Component sizes in descending order from per-vertex labels and sizes: one entry per v with label[v] == v.
 static void ComponentSizes(const std::vector<u32>& labels, const std::vector<u32>& sizes, std::vector<u32>* out) {
@@ -552,84 +555,49 @@ static void ComponentSizes(const std::vector<u32>& labels, const std::vector<u32
 }
 
 void DirectBA::ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh* mesh, MeshComponentReport* report) {
-  const bool filter = options.min_component_vertices >= 2;
-  if (!filter && !report) { ExtractMesh(stream, options.min_count, mesh); return; }
-  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("ExtractMesh: no fused volume (call FuseKeyframes first)");
-  const bslam_volume vol = VolumePod(volume_spec_);
-  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), color = volume_color_->ToPod();
-  u32 vertices = 0, triangles = 0;
-  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, options.min_count, 0, 0, nullptr, nullptr, nullptr, nullptr, &vertices, &triangles),
-        "bslam_extract_mesh");
+  DeviceMesh m = ExtractDeviceMesh(stream, options.min_count), kept;
+  const u32 vertices = m.vertices, triangles = m.triangles;
+  // nothing beyond the extraction is launched for an empty mesh, or without a clean-up and a report
+  const bool filter = vertices != 0 && options.min_component_vertices >= 2, label = vertices != 0 && (filter || report);
   if (report) *report = MeshComponentReport();
-  mesh->positions.clear(); mesh->normals.clear(); mesh->colors.clear(); mesh->indices.clear();
-  KeepDeviceMesh(nullptr, nullptr, 0, 0);
-  if (vertices == 0) return;
-  std::unique_ptr<DeviceBuffer<float>> positions_owner(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
-  std::unique_ptr<DeviceBuffer<u32>> indices_owner(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
-  DeviceBuffer<float>& positions = *positions_owner;
-  DeviceBuffer<u32>& indices = *indices_owner;
-  DeviceBuffer<float> normals(1, static_cast<int>(3 * vertices));
-  DeviceBuffer<uchar4_t> colors(1, static_cast<int>(vertices));
-  DeviceBuffer<u32> labels(1, static_cast<int>(vertices)), sizes(1, static_cast<int>(vertices));
-  u32 v2 = 0, t2 = 0;
-  Check(bslam_extract_mesh(ctx_, stream, &vol, &tsdf, &count, &color, options.min_count, vertices, triangles, positions.address(), normals.address(),
-                           colors.address(), indices.address(), &v2, &t2),
-        "bslam_extract_mesh");
-  if (v2 != vertices || t2 != triangles) throw std::runtime_error("ExtractMesh: the volume changed between the two extraction calls");
+  DeviceArray<u32> labels(label ? vertices : 0), sizes(label ? vertices : 0);
   u32 components = 0;
-  Check(bslam_mesh_components(ctx_, stream, vertices, triangles, indices.address(), labels.address(), sizes.address(), &components), "bslam_mesh_components");
-  u32 kept_vertices = vertices, kept_triangles = triangles;
-  const float* from_positions = positions.address();
-  const float* from_normals = normals.address();
-  const uchar4_t* from_colors = colors.address();
-  const u32* from_indices = indices.address();
-  std::unique_ptr<DeviceBuffer<float>> out_positions, out_normals;
-  std::unique_ptr<DeviceBuffer<uchar4_t>> out_colors;
-  std::unique_ptr<DeviceBuffer<u32>> out_indices;
+  if (label) Check(bslam_mesh_components(ctx_, stream, vertices, triangles, m.indices->address(), labels.address(), sizes.address(), &components), "bslam_mesh_components");
   if (filter) {
-    out_positions.reset(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
-    out_normals.reset(new DeviceBuffer<float>(1, static_cast<int>(3 * vertices)));
-    out_colors.reset(new DeviceBuffer<uchar4_t>(1, static_cast<int>(vertices)));
-    out_indices.reset(new DeviceBuffer<u32>(1, static_cast<int>(std::max<u32>(3 * triangles, 1))));
-    Check(bslam_filter_mesh(ctx_, stream, vertices, triangles, positions.address(), normals.address(), colors.address(), indices.address(), sizes.address(),
-                            options.min_component_vertices, out_positions->address(), out_normals->address(), out_colors->address(), out_indices->address(),
-                            &kept_vertices, &kept_triangles),
+    kept = DeviceMesh(vertices, triangles);
+    Check(bslam_filter_mesh(ctx_, stream, vertices, triangles, m.positions->address(), m.normals->address(), m.colors->address(), m.indices->address(), sizes.address(),
+                            options.min_component_vertices, kept.positions->address(), kept.normals->address(), kept.colors->address(), kept.indices->address(),
+                            &kept.vertices, &kept.triangles),
           "bslam_filter_mesh");
-    from_positions = out_positions->address(); from_normals = out_normals->address(); from_colors = out_colors->address(); from_indices = out_indices->address();
   }
-  mesh->positions.resize(3 * static_cast<size_t>(kept_vertices));
-  mesh->normals.resize(3 * static_cast<size_t>(kept_vertices));
-  mesh->colors.resize(kept_vertices);
-  mesh->indices.resize(3 * static_cast<size_t>(kept_triangles));
-  std::vector<u32> host_labels, host_sizes;
-  if (report) { host_labels.resize(vertices); host_sizes.resize(vertices); }
+  DeviceMesh& out = filter ? kept : m;
+  mesh->positions.resize(3 * static_cast<size_t>(out.vertices));
+  mesh->normals.resize(3 * static_cast<size_t>(out.vertices));
+  mesh->colors.resize(out.vertices);
+  mesh->indices.resize(3 * static_cast<size_t>(out.triangles));
+  std::vector<u32> host_labels(report ? labels.count() : 0), host_sizes(host_labels.size());
   // the one download: everything is enqueued, then the stream is waited for once
-  const auto fetch = [stream](void* to, const void* from, size_t bytes) {
-    if (bytes) HIP_OR_THROW(hipMemcpyAsync(to, from, bytes, hipMemcpyDeviceToHost, stream));
-  };
-  fetch(mesh->positions.data(), from_positions, mesh->positions.size() * sizeof(float));
-  fetch(mesh->normals.data(), from_normals, mesh->normals.size() * sizeof(float));
-  fetch(mesh->colors.data(), from_colors, mesh->colors.size() * sizeof(uchar4_t));
-  fetch(mesh->indices.data(), from_indices, mesh->indices.size() * sizeof(u32));
-  fetch(host_labels.data(), labels.address(), host_labels.size() * sizeof(u32));
-  fetch(host_sizes.data(), sizes.address(), host_sizes.size() * sizeof(u32));
-  HIP_OR_THROW(hipStreamSynchronize(stream));
-  // the mesh as returned stays on the device for SurfelMeshDistance
-  if (filter) KeepDeviceMesh(std::move(out_positions), std::move(out_indices), kept_vertices, kept_triangles);
-  else KeepDeviceMesh(std::move(positions_owner), std::move(indices_owner), vertices, triangles);
-  if (report) {
+  out.positions->Download(stream, mesh->positions.data(), mesh->positions.size());
+  out.normals->Download(stream, mesh->normals.data(), mesh->normals.size());
+  out.colors->Download(stream, mesh->colors.data(), mesh->colors.size());
+  out.indices->Download(stream, mesh->indices.data(), mesh->indices.size());
+  labels.Download(stream, host_labels.data(), host_labels.size());
+  sizes.Download(stream, host_sizes.data(), host_sizes.size());
+  Wait(stream);
+  if (report && label) {
     report->components = components;
-    report->removed_vertices = vertices - kept_vertices;
-    report->removed_triangles = triangles - kept_triangles;
+    report->removed_vertices = vertices - out.vertices;
+    report->removed_triangles = triangles - out.triangles;
     ComponentSizes(host_labels, host_sizes, &report->sizes_descending);
   }
+  KeepDeviceMesh(std::move(out));   // the mesh as returned stays on the device for SurfelMeshDistance
 }
 
-void DirectBA::KeepDeviceMesh(std::unique_ptr<DeviceBuffer<float>> positions, std::unique_ptr<DeviceBuffer<u32>> indices, u32 vertices, u32 triangles) {
-  mesh_positions_ = std::move(positions);
-  mesh_indices_ = std::move(indices);
-  mesh_vertices_ = vertices;
-  mesh_triangles_ = triangles;
+void DirectBA::KeepDeviceMesh(DeviceMesh mesh) {
+  mesh_positions_ = std::move(mesh.positions);
+  mesh_indices_ = std::move(mesh.indices);
+  mesh_vertices_ = mesh.vertices;
+  mesh_triangles_ = mesh.triangles;
   mesh_extracted_ = true;
 }
 
@@ -639,8 +607,8 @@ void DirectBA::PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count,
   const u32 n = static_cast<u32>(point_count);
   result->distance.assign(n, 0.f);
   result->triangle.assign(n, 0u);
-  DeviceBuffer<float> distance(1, static_cast<int>(std::max<u32>(n, 1)));
-  DeviceBuffer<u32> triangle(1, static_cast<int>(std::max<u32>(n, 1)));
+  DeviceArray<float> distance(n);
+  DeviceArray<u32> triangle(n);
   // cell_size 0: the search radius, doubled while the call reports that the grid does not fit its budget
   float cell = options.cell_size > 0.f ? options.cell_size : options.max_distance;
   for (int attempt = 0;; ++attempt) {
@@ -655,48 +623,44 @@ void DirectBA::PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count,
     result->grid_entries = entries;
     break;
   }
-  if (n) {
-    HIP_OR_THROW(hipMemcpyAsync(result->distance.data(), distance.address(), n * sizeof(float), hipMemcpyDeviceToHost, stream));
-    HIP_OR_THROW(hipMemcpyAsync(result->triangle.data(), triangle.address(), n * sizeof(u32), hipMemcpyDeviceToHost, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-  }
+  distance.Download(stream, result->distance.data(), n);
+  triangle.Download(stream, result->triangle.data(), n);
+  Wait(stream);
 }
 
 void DirectBA::PointMeshDistance(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const PointMeshOptions& options, PointMeshResult* result) {
   if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
       3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull || 3 * static_cast<uint64_t>(point_count) > 0x7fffffffull)
     throw std::invalid_argument("PointMeshDistance: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  const u32 vertices = static_cast<u32>(mesh.vertex_count()), triangles = static_cast<u32>(mesh.triangle_count());
-  DeviceBuffer<float> dev_points(1, static_cast<int>(std::max<size_t>(3 * point_count, 1))), dev_positions(1, static_cast<int>(std::max<u32>(3 * vertices, 1)));
-  DeviceBuffer<u32> dev_indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1)));
-  if (point_count) HIP_OR_THROW(hipMemcpyAsync(dev_points.address(), points, 3 * point_count * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (vertices) HIP_OR_THROW(hipMemcpyAsync(dev_positions.address(), mesh.positions.data(), mesh.positions.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-  if (triangles) HIP_OR_THROW(hipMemcpyAsync(dev_indices.address(), mesh.indices.data(), mesh.indices.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
-  HIP_OR_THROW(hipStreamSynchronize(stream));   // the host arrays are the caller's and pageable
-  PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), vertices, dev_positions.address(), triangles, dev_indices.address(), options, result);
+  DeviceArray<float> dev_points(3 * point_count), dev_positions(mesh.positions.size());
+  DeviceArray<u32> dev_indices(mesh.indices.size());
+  dev_points.Upload(stream, points, 3 * point_count);
+  dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
+  dev_indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
+  Wait(stream);   // the host arrays are the caller's and pageable
+  PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), static_cast<u32>(mesh.vertex_count()), dev_positions.address(),
+                            static_cast<u32>(mesh.triangle_count()), dev_indices.address(), options, result);
+}
+
+std::vector<float> DirectBA::ValidSurfelCentres(hipStream_t stream) const {
+  std::vector<float> centres;
+  const size_t n = surfels_size_;
+  if (n == 0) return centres;
+  std::vector<float> rows(3 * n);   // rows 0..2: x, y, z
+  GetSurfels(stream, rows.data(), n * sizeof(float), 3);
+  centres.reserve(3 * n);
+  for (size_t i = 0; i < n; ++i)
+    if (!std::isnan(rows[i])) centres.insert(centres.end(), {rows[i], rows[n + i], rows[2 * n + i]});
+  return centres;
 }
 
 void DirectBA::SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& options, PointMeshResult* result) {
   if (!mesh_extracted_) throw std::logic_error("SurfelMeshDistance: no extracted mesh (call ExtractMesh first)");
-  // the centres of the valid surfels, the set and the order of ExportToPointCloud
-  std::vector<float> centres;
-  if (surfels_size_ != 0) {
-    const size_t n = surfels_size_;
-    std::vector<float> rows(3 * n);
-    GetSurfels(stream, rows.data(), n * sizeof(float), 3);
-    centres.reserve(3 * n);
-    for (size_t i = 0; i < n; ++i) {
-      if (std::isnan(rows[i])) continue;
-      centres.insert(centres.end(), {rows[i], rows[n + i], rows[2 * n + i]});
-    }
-  }
-  const size_t count = centres.size() / 3;
-  DeviceBuffer<float> dev_points(1, static_cast<int>(std::max<size_t>(3 * count, 1)));
-  if (count) {
-    HIP_OR_THROW(hipMemcpyAsync(dev_points.address(), centres.data(), centres.size() * sizeof(float), hipMemcpyHostToDevice, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-  }
-  PointMeshDistanceOnDevice(stream, count, dev_points.address(), mesh_vertices_, mesh_positions_ ? mesh_positions_->address() : nullptr, mesh_triangles_,
+  const std::vector<float> centres = ValidSurfelCentres(stream);
+  DeviceArray<float> dev_points(centres.size());
+  dev_points.Upload(stream, centres.data(), centres.size());
+  Wait(stream);
+  PointMeshDistanceOnDevice(stream, centres.size() / 3, dev_points.address(), mesh_vertices_, mesh_positions_ ? mesh_positions_->address() : nullptr, mesh_triangles_,
                             mesh_indices_ ? mesh_indices_->address() : nullptr, options, result);
 }
 
@@ -707,69 +671,52 @@ u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u
   if (labels) labels->assign(vertices, 0u);
   if (sizes) sizes->assign(vertices, 0u);
   if (3 * static_cast<uint64_t>(triangles) > 0x7fffffffull || vertices > 0x7fffffffu) throw std::invalid_argument("MeshComponents: the mesh is too large for one device image");
-  DeviceBuffer<u32> indices(1, static_cast<int>(std::max<u32>(3 * triangles, 1))), dev_labels(1, static_cast<int>(std::max<u32>(vertices, 1))),
-      dev_sizes(1, static_cast<int>(std::max<u32>(vertices, 1)));
-  if (triangles) {
-    HIP_OR_THROW(hipMemcpyAsync(indices.address(), mesh.indices.data(), mesh.indices.size() * sizeof(u32), hipMemcpyHostToDevice, stream));
-    HIP_OR_THROW(hipStreamSynchronize(stream));
-  }
+  DeviceArray<u32> indices(mesh.indices.size()), dev_labels(vertices), dev_sizes(vertices);
+  indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
+  Wait(stream);
   u32 components = 0;
   Check(bslam_mesh_components(ctx_, stream, vertices, triangles, indices.address(), dev_labels.address(), dev_sizes.address(), &components), "bslam_mesh_components");
-  if (vertices && labels) HIP_OR_THROW(hipMemcpyAsync(labels->data(), dev_labels.address(), vertices * sizeof(u32), hipMemcpyDeviceToHost, stream));
-  if (vertices && sizes) HIP_OR_THROW(hipMemcpyAsync(sizes->data(), dev_sizes.address(), vertices * sizeof(u32), hipMemcpyDeviceToHost, stream));
-  HIP_OR_THROW(hipStreamSynchronize(stream));
+  if (labels) dev_labels.Download(stream, labels->data(), vertices);
+  if (sizes) dev_sizes.Download(stream, sizes->data(), vertices);
+  Wait(stream);
   return components;
 }
 
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
-  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("RenderVolume: no fused volume (call FuseKeyframes first)");
+  const FusedVolume v = Fused("RenderVolume");
   const int w = camera.width(), h = camera.height();
   if (w <= 0 || h <= 0) throw std::invalid_argument("RenderVolume: the camera has no pixels");
-  if (!options.depth && !options.color && !options.normal) throw std::invalid_argument("RenderVolume: no view was asked for");
+  const ViewSet want{options.depth, false, options.color, options.normal};
+  if (!want.depth && !want.color && !want.normal) throw std::invalid_argument("RenderVolume: no view was asked for");
   if (options.min_count < 1) throw std::invalid_argument("RenderVolume: min_count must be >= 1");
-  const bslam_volume vol = VolumePod(volume_spec_);
-  const bslam_buffer2d tsdf = volume_tsdf_->ToPod(), count = volume_count_->ToPod(), volume_color = volume_color_->ToPod();
   size_t aux_bytes = 0;
-  Check(bslam_volume_views_aux_bytes(&vol, &aux_bytes), "bslam_volume_views_aux_bytes");
-  constexpr size_t kAuxRow = size_t{1} << 20;   // the aux bytes as rows of 1 MiB
-  const int aux_rows = static_cast<int>((aux_bytes + kAuxRow - 1) / kAuxRow);
-  if (!volume_aux_ || volume_aux_->height() != aux_rows) {
+  Check(bslam_volume_views_aux_bytes(&v.vol, &aux_bytes), "bslam_volume_views_aux_bytes");
+  if (!volume_aux_ || volume_aux_->count() != aux_bytes) {
     volume_aux_.reset();
     volume_aux_min_count_ = 0;
-    volume_aux_.reset(new DeviceBuffer<u8>(aux_rows, static_cast<int>(kAuxRow)));
+    volume_aux_.reset(new DeviceArray<u8>(aux_bytes));
   }
   if (volume_aux_min_count_ != options.min_count) {
     volume_aux_min_count_ = 0;
-    Check(bslam_prepare_volume_views(ctx_, stream, &vol, &tsdf, &count, options.min_count, volume_aux_->address(), static_cast<size_t>(aux_rows) * volume_aux_->pitch()),
-          "bslam_prepare_volume_views");
+    Check(bslam_prepare_volume_views(ctx_, stream, &v.vol, &v.tsdf, &v.count, options.min_count, volume_aux_->address(), aux_bytes), "bslam_prepare_volume_views");
     volume_aux_min_count_ = options.min_count;
   }
-  const auto fits = [w, h](int bw, int bh, int elems) { return bw == w * elems && bh == h; };
-  if (options.depth && !(render_depth_ && fits(render_depth_->width(), render_depth_->height(), 1))) render_depth_.reset(new DeviceBuffer<u16>(h, w));
-  if (options.color && !(render_color_ && fits(render_color_->width(), render_color_->height(), 1))) render_color_.reset(new DeviceBuffer<uchar4_t>(h, w));
-  if (options.normal && !(render_normal_ && fits(render_normal_->width(), render_normal_->height(), 3))) render_normal_.reset(new DeviceBuffer<float>(h, 3 * w));
-  bslam_buffer2d depth, color, normal;
-  if (options.depth) depth = render_depth_->ToPod();
-  if (options.color) color = render_color_->ToPod();
-  if (options.normal) { normal = render_normal_->ToPod(); normal.width = w; }   // 12 bytes per pixel
+  bslam_buffer2d pods[4];
+  ViewImages(w, h, want, pods);
   const bslam_camera4f cam = camera.pod();
   views->width = w;
   views->height = h;
   views->global_T_camera = global_T_camera.Matrix3x4();
   views->camera_T_global = global_T_camera.Inverse().Matrix3x4();
-  Check(bslam_raycast_volume(ctx_, stream, &vol, &tsdf, &volume_color, volume_aux_->address(), &views->global_T_camera, &cam, options.min_depth, options.max_depth,
-                             options.step > 0.f ? options.step : volume_spec_.voxel_size, 1.0f / raw_to_float_depth_, options.depth ? &depth : nullptr,
-                             options.color ? &color : nullptr, options.normal ? &normal : nullptr),
+  Check(bslam_raycast_volume(ctx_, stream, &v.vol, &v.tsdf, &v.color, volume_aux_->address(), &views->global_T_camera, &cam, options.min_depth, options.max_depth,
+                             options.step > 0.f ? options.step : volume_spec_.voxel_size, 1.0f / raw_to_float_depth_, want.depth ? &pods[0] : nullptr,
+                             want.color ? &pods[2] : nullptr, want.normal ? &pods[3] : nullptr),
         "bslam_raycast_volume");
-  const size_t pixels = static_cast<size_t>(w) * h;
-  views->depth.clear(); views->index.clear(); views->color.clear(); views->normal.clear();
-  if (options.depth) { views->depth.resize(pixels); render_depth_->Download(stream, views->depth.data(), static_cast<size_t>(w) * sizeof(u16)); }
-  if (options.color) { views->color.resize(pixels); render_color_->Download(stream, views->color.data(), static_cast<size_t>(w) * sizeof(uchar4_t)); }
-  if (options.normal) { views->normal.resize(3 * pixels); render_normal_->Download(stream, views->normal.data(), static_cast<size_t>(w) * 3 * sizeof(float)); }
+  DownloadViews(stream, want, views);
 }
 
 void DirectBA::Volume(hipStream_t stream, VolumeData* volume) const {
-  if (!volume_tsdf_ || volume_spec_.nx == 0) throw std::logic_error("Volume: no fused volume (call FuseKeyframes first)");
+  Fused("Volume");
   volume->spec = volume_spec_;
   volume->truncation = volume_truncation_;
   const size_t n = static_cast<size_t>(volume_spec_.nx) * volume_spec_.ny * volume_spec_.nz, nx = volume_spec_.nx;
@@ -780,20 +727,13 @@ void DirectBA::Volume(hipStream_t stream, VolumeData* volume) const {
 }
 
 bool DirectBA::ModelBounds(hipStream_t stream, float min[3], float max[3]) const {
-  const size_t n = surfels_size_;
-  std::vector<float> rows(3 * std::max<size_t>(n, 1));   // rows 0..2: x, y, z
-  if (n) GetSurfels(stream, rows.data(), n * sizeof(float), 3);
-  bool any = false;
-  for (size_t i = 0; i < n; ++i) {
-    if (std::isnan(rows[i])) continue;   // deleted surfels carry NaN in x
-    for (int d = 0; d < 3; ++d) {
-      const float v = rows[d * n + i];
-      min[d] = any ? std::min(min[d], v) : v;
-      max[d] = any ? std::max(max[d], v) : v;
-    }
-    any = true;
+  const std::vector<float> centres = ValidSurfelCentres(stream);
+  for (size_t i = 0; i < centres.size(); ++i) {
+    const float v = centres[i];
+    min[i % 3] = i < 3 ? v : std::min(min[i % 3], v);
+    max[i % 3] = i < 3 ? v : std::max(max[i % 3], v);
   }
-  return any;
+  return !centres.empty();
 }
 
 void DirectBA::ComputeCost(hipStream_t stream, bool active_surfels_only, CostReport* report) {

@@ -75,6 +75,34 @@ class DeviceBuffer {
   size_t pitch_;
 };
 
+inline void ThrowOnHipError(hipError_t e, const char* what) {
+  if (e != hipSuccess) throw std::runtime_error(std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// Flat device array of `count` elements (plain hipMalloc; count 0 is allowed and still has an address).  Upload and Download
+// enqueue asynchronous copies of the first n elements: the caller waits for the stream once, where it needs the data.
+template <typename T>
+class DeviceArray {
+ public:
+  explicit DeviceArray(size_t count) : data_(nullptr), count_(count) {
+    ThrowOnHipError(hipMalloc(reinterpret_cast<void**>(&data_), std::max<size_t>(count * sizeof(T), 1)), "hipMalloc");
+  }
+  ~DeviceArray() { hipError_t e = hipFree(data_); (void)e; }
+  DeviceArray(const DeviceArray&) = delete;
+  DeviceArray& operator=(const DeviceArray&) = delete;
+  size_t count() const { return count_; }
+  T* address() const { return data_; }
+  void Upload(hipStream_t stream, const T* host, size_t n) { Copy(data_, host, n, hipMemcpyHostToDevice, stream); }
+  void Download(hipStream_t stream, T* host, size_t n) const { Copy(host, data_, n, hipMemcpyDeviceToHost, stream); }
+
+ private:
+  static void Copy(void* to, const void* from, size_t n, hipMemcpyKind kind, hipStream_t stream) {
+    if (n) ThrowOnHipError(hipMemcpyAsync(to, from, n * sizeof(T), kind, stream), "hipMemcpyAsync");
+  }
+  T* data_;
+  size_t count_;
+};
+
 struct uchar4_t { u8 x, y, z, w; };
 
 // = vis::Keyframe (BS/keyframe.h) reduced to what the path reads.
@@ -466,15 +494,36 @@ class DirectBA {
   std::unique_ptr<DeviceBuffer<uchar4_t>> volume_color_;
   VolumeSpec volume_spec_;
   float volume_truncation_ = 0.f;
+  // the fused volume as the library takes it; throws "<caller>: no fused volume (call FuseKeyframes first)" if there is none
+  struct FusedVolume { bslam_volume vol; bslam_buffer2d tsdf, count, color; };
+  FusedVolume Fused(const char* caller) const;
   // prepared aux buffer of RenderVolume and the min_count it was prepared for (0: stale -- a new fusion, or never prepared)
-  std::unique_ptr<DeviceBuffer<u8>> volume_aux_;
+  std::unique_ptr<DeviceArray<u8>> volume_aux_;
   u32 volume_aux_min_count_ = 0;
+  // The views a render call wants: ViewImages gives their render_*_ images the camera's size and fills pods[] (depth, index,
+  // colour, normal) for them; DownloadViews copies them into `views`, whose size is set.
+  struct ViewSet { bool depth, index, color, normal; };
+  void ViewImages(int w, int h, const ViewSet& want, bslam_buffer2d pods[4]);
+  void DownloadViews(hipStream_t stream, const ViewSet& want, ModelViews* views) const;
+  struct DeviceMesh {   // positions and normals 3 V floats, colours V, indices 3 T
+    std::unique_ptr<DeviceArray<float>> positions, normals;
+    std::unique_ptr<DeviceArray<uchar4_t>> colors;
+    std::unique_ptr<DeviceArray<u32>> indices;
+    u32 vertices = 0, triangles = 0;
+    DeviceMesh() = default;
+    DeviceMesh(u32 v, u32 t) : positions(new DeviceArray<float>(size_t{3} * v)), normals(new DeviceArray<float>(size_t{3} * v)), colors(new DeviceArray<uchar4_t>(v)),
+                               indices(new DeviceArray<u32>(size_t{3} * t)), vertices(v), triangles(t) {}
+  };
+  // The extraction: the count call, the allocations and the emit call.  Forgets the kept mesh once the count call is through.
+  DeviceMesh ExtractDeviceMesh(hipStream_t stream, u32 min_count);
   // device copy of the mesh the last ExtractMesh returned (positions 3 V floats, indices 3 T), for SurfelMeshDistance
-  std::unique_ptr<DeviceBuffer<float>> mesh_positions_;
-  std::unique_ptr<DeviceBuffer<u32>> mesh_indices_;
+  std::unique_ptr<DeviceArray<float>> mesh_positions_;
+  std::unique_ptr<DeviceArray<u32>> mesh_indices_;
   u32 mesh_vertices_ = 0, mesh_triangles_ = 0;
   bool mesh_extracted_ = false;
-  void KeepDeviceMesh(std::unique_ptr<DeviceBuffer<float>> positions, std::unique_ptr<DeviceBuffer<u32>> indices, u32 vertices, u32 triangles);
+  void KeepDeviceMesh(DeviceMesh mesh);   // keeps its positions and indices
+  // xyz of the valid surfels (a deleted one carries NaN in x), in the order of ExportToPointCloud
+  std::vector<float> ValidSurfelCentres(hipStream_t stream) const;
   bool comm_ = false, sharded_ = false;
   bslam_allreduce_fn allreduce_ = nullptr;
   void* allreduce_user_ = nullptr;

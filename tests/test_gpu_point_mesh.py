@@ -280,3 +280,38 @@ def test_profiling_counts_offered_and_evaluated_pairs(gpu, sphere):
     print(f"{offered} pairs offered, {evaluated} evaluated, of {len(points) * len(triangles)}")
     assert offered >= evaluated > 0 and evaluated == candidates and offered < len(points) * len(triangles)
     assert (tested.value, culled.value) == (0, 0)
+
+
+def test_scratch_carving_at_its_boundaries():
+    """The mesh calls and this one carve their scratch out of slabs that only grow.  On one fresh context: bslam_mesh_components and
+    bslam_filter_mesh (min_vertices 2) on strips with isolated vertices of (V, T) around the padding to 64 elements, from the largest
+    to the smallest and back up, then this call on 7 triangles, 9 vertices and 13, then 5 points in a grid of 54 cells (54, 55,
+    the 174 entries, 13 and 5: no multiple of four) -- so a slab reserved for a larger call is carved for a smaller one and grown
+    again.  Every output equals the restatements of tests/mesh_components_util.py and tests/point_mesh_util.py exactly."""
+    import torch
+    from tests import mesh_components_util as mu
+    from tests.test_gpu_mesh_components import assert_components_equal, assert_filtered_equal, gpu_components, gpu_filter
+    gpu = (torch, badslam_amd.lib(), badslam_amd.Context(0))
+    rng = np.random.default_rng(41)
+    shapes = [(129, 127), (65, 1), (64, 62), (63, 61), (1, 0)]
+    for V, T in shapes + shapes[-2::-1]:
+        i = np.arange(T, dtype=np.uint32)
+        triangles = np.stack([i, i + 1, i + 2], -1).reshape(T, 3)          # a strip on the first T + 2 vertices; the rest is isolated
+        positions, normals = rng.normal(size=(V, 3)).astype(F), rng.normal(size=(V, 3)).astype(F)
+        colors = rng.integers(0, 256, (V, 4), dtype=np.uint8)
+        want = mu.components(V, triangles)
+        assert want[2] == (V - T - 1 if T else V)
+        got = gpu_components(gpu, V, triangles)
+        assert_components_equal(got, want)
+        assert_filtered_equal(gpu_filter(gpu, positions, normals, colors, triangles, got[1], 2), want[1], 2, positions, normals, colors, triangles)
+    i = np.arange(9)
+    positions = np.stack([0.5 * i, (i % 2) * 1.0, 0.1 * i], -1).astype(F)
+    triangles = np.stack([i[:7], i[:7] + 1, i[:7] + 2], -1).astype(np.uint32)
+    points = (rng.uniform(-0.5, 1.5, (13, 3)) * np.array([3.0, 1.0, 0.8])).astype(F)
+    assert pm.grid_census(positions, triangles, 0.6, 0.9) == (54, 174)
+    for N in (13, 5):
+        want = pm.point_mesh_distance(points[:N], positions, triangles, 0.6)
+        assert np.isfinite(want[0]).any() and np.isinf(want[0]).any()
+        rc, d, t, cells, entries = call(gpu, points[:N], positions, triangles, 0.6, 0.9)
+        assert (rc, cells, entries) == (0, 54, 174)
+        assert_equal(d, t, want, f"{N} points")

@@ -427,6 +427,76 @@ def test_views_through_direct_ba():
 MEASURED_SHARE, MEASURED_MEDIAN, MEASURED_P99 = 0.9961, 2.0, 12.0
 
 
+@pytest.fixture(scope="module")
+def fused_ba():
+    """The DirectBA of test_views_through_direct_ba with its three keyframes fused once, for the tests that share it."""
+    from badslam_amd.direct_ba import DirectBA
+    from tests import bso, scenes
+    from tools import run_tum
+    cam = bso.make_camera(131.25, 131.25, 80.0, 60.0, 160, 120)
+    scene = scenes.synthetic_scene(3, width=160, height=120, cell=2, camera=cam)
+    ba = DirectBA(scene.max_surfels, scene.raw_to_float_depth, scene.baseline_fx, scene.cell, 0.8, 1, 1, 1, scene.color_camera, scene.depth_camera, 0, True, False)
+    for kf in scene.keyframes:
+        ba.AddKeyframe(kf.id, max(kf.min_depth, 1e-3), max(kf.max_depth, 1e-2), kf.depth, kf.normals, kf.radius, kf.color, kf.global_T_frame)
+    for kf in scene.keyframes:
+        ba.CreateSurfelsForKeyframe(False, kf.id)
+    voxel, truncation = 0.02, 0.08
+    origin, dims = run_tum.mesh_volume(*ba.ModelBounds(), voxel, truncation)
+    ba.FuseKeyframes(origin, voxel, dims, truncation)
+    yield ba, scene, origin, voxel
+    ba.close()
+
+
+def test_view_images_are_shared_across_sizes(fused_ba):
+    """RenderVolume at 160 x 120 and RenderModel at 80 x 60 take turns on one object, whose device images they share and
+    re-allocate for each other: each repeat equals its first call byte for byte, the small views equal render_util.render32 on the
+    surfel rows and the large ones raycast_util.raycast on the downloaded volume (normals as everywhere in these files: 1e-6)."""
+    from tests import render_util
+    from tests.test_gpu_render import assert_equal_to_restatement
+    ba, scene, origin, voxel = fused_ba
+    pose = ba.keyframe_pose(0)
+    fx, fy, cx, cy = [float(v) for v in ba.intrinsics()[1]]
+    half = abi.Camera4f(fx / 2, fy / 2, cx / 2, cy / 2, 80, 60)
+    volume_call = lambda: ba.RenderVolume(pose, min_depth=0.5, max_depth=6.0, views=("depth", "color", "normal"))
+    model_call = lambda: ba.RenderModel(pose, camera=half, radius_scale=2.0, views=("depth", "index", "color", "normal"))
+    volume_views, model_views, volume_again, model_again = volume_call(), model_call(), volume_call(), model_call()
+    for first, again in ((volume_views, volume_again), (model_views, model_again)):
+        assert set(first) == set(again)
+        for name in first:
+            assert first[name].shape == again[name].shape and first[name].tobytes() == again[name].tobytes(), name
+    assert model_views["depth"].shape == (60, 80) and model_views["index"].shape == (60, 80) and model_views["normal"].shape == (60, 80, 3)
+    assert volume_views["depth"].shape == (120, 160) and volume_views["color"].shape == (120, 160, 4)
+    m2d = F(1.0) / F(scene.raw_to_float_depth)
+    want_model = render_util.render32(ba.GetSurfels(8), ba.surfels_size(), model_views["camera_T_global"], half, 0.05, 50.0, 2.0, m2d)
+    assert_equal_to_restatement(model_views, want_model)
+    assert (model_views["depth"] != 0).mean() > 0.5
+    v = ba.Volume()
+    want_volume = ru.raycast(ru.Volume(v["tsdf"], v["count"], v["color"], origin, voxel, 1), volume_views["global_T_camera"], abi.Camera4f(fx, fy, cx, cy, 160, 120),
+                             0.5, 6.0, voxel, float(m2d))
+    assert_views_equal({k: volume_views[k] for k in ("depth", "color", "normal")}, want_volume)
+    assert (volume_views["depth"] != 0).mean() > 0.5
+
+
+def test_an_extraction_that_yields_nothing(fused_ba):
+    """No sample is seen by four of three keyframes: ExtractMesh(min_count=4) is empty by the plain route and by the one with
+    clean-up and report, SurfelMeshDistance then finds nothing near any surfel, and ExtractMesh(1) is what it was before."""
+    ba = fused_ba[0]
+    before = ba.ExtractMesh(1)
+    assert len(before["positions"]) > 1000 and len(before["triangles"]) > 1000
+    plain = ba.ExtractMesh(min_count=4)
+    cleaned, report = ba.ExtractMesh(min_count=4, min_component_vertices=64, report=True)
+    for mesh in (plain, cleaned):
+        assert mesh["positions"].shape == (0, 3) and mesh["normals"].shape == (0, 3) and mesh["colors"].shape == (0, 4) and mesh["triangles"].shape == (0, 3)
+    assert (report["components"], report["removed_vertices"], report["removed_triangles"]) == (0, 0, 0) and report["sizes_descending"].shape == (0,)
+    points = ba.ExportToPointCloud()[0]
+    result = ba.SurfelMeshDistance(0.1)
+    assert len(points) > 4000 and result["distance"].shape == (len(points),) and result["triangle"].shape == (len(points),)
+    assert np.isposinf(result["distance"]).all() and (result["triangle"] == 0xFFFFFFFF).all()
+    after = ba.ExtractMesh(1)
+    for name in before:
+        assert before[name].dtype == after[name].dtype and np.array_equal(before[name], after[name]), name
+
+
 # ------------------------------------------------------------------------------------------------
 # 5. the tool
 # ------------------------------------------------------------------------------------------------

@@ -145,7 +145,8 @@ int bslam_compute_normals(bslam_context* ctx, void* stream_, const bslam_camera4
   if (rc) return rc;
   if ((rc = make_img(output_depth, 2, "output depth", &out))) return rc;
   if ((rc = make_img(normals_buffer, 2, "normals", &nrm))) return rc;
-  if (!same_shape(in, out) || !same_shape(in, nrm) || in.base == out.base) return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth / normals buffers must be distinct and of one size");
+  if (!same_shape(in, out) || !same_shape(in, nrm) || in.base == out.base || in.base == nrm.base || out.base == nrm.base)
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth / normals buffers must be distinct and of one size");
   if (in.width != depth_camera->width || in.height != depth_camera->height) return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth image does not match the camera");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, depth_params);
@@ -164,7 +165,8 @@ int bslam_compute_point_radii_and_remove_isolated_pixels(bslam_context* ctx, voi
   if (rc) return rc;
   if ((rc = make_img(radius_buffer, 2, "radius", &rad))) return rc;
   if ((rc = make_img(out_depth, 2, "output depth", &out))) return rc;
-  if (!same_shape(in, rad) || !same_shape(in, out) || in.base == out.base) return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth / radius buffers must be distinct and of one size");
+  if (!same_shape(in, rad) || !same_shape(in, out) || in.base == out.base || in.base == rad.base || rad.base == out.base)
+    return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth / radius buffers must be distinct and of one size");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   bslam_depth_params dp;
   std::memset(&dp, 0, sizeof(dp));

@@ -819,6 +819,9 @@ int bslam_place_pattern(int8_t* pairs);
 int bslam_match_features(bslam_context* ctx, void* stream, const uint32_t* query_xy, const uint32_t* query_desc, int cells,
                          const uint32_t* database, int n_db, int max_distance, int32_t* out_match, uint32_t* out_count);
 
+/* The five producers below take pitched images of one size (pitch >= width * element size; u16 rows need 2 byte, colour
+ * rows 4 byte alignment) and write nothing outside width x height.  The bilateral filter, the normals and the radii read a
+ * pixel's neighbours, so none of their images may be another one of the same call: such a call is refused. */
 /* Replaces ComputeBrightnessCUDA (BS/cuda_image_processing.cuh, kernel BS/cuda_image_processing.cu:165-194):
  * rgb_buffer has 3 bytes per pixel, color_buffer 4 (r, g, b, luma). */
 int bslam_compute_brightness(bslam_context* ctx, void* stream,

@@ -178,8 +178,11 @@ void bso_compute_normals(const bslam_camera4f* depth_camera, const bslam_depth_p
   }
 }
 
-/* ComputePointRadiiAndRemoveIsolatedPixelsCUDAKernel<4> BS/cuda_depth_processing.cu:286-357.  in_depth is the
- * output of bso_compute_normals (its 1-pixel border is invalid, so the 4-neighbourhood never leaves the image). */
+/* ComputePointRadiiAndRemoveIsolatedPixelsCUDAKernel<4> BS/cuda_depth_processing.cu:286-357.  In the pipeline in_depth is
+ * the output of bso_compute_normals, whose 1-pixel border is invalid, so the 4-neighbourhood never leaves the image there.
+ * The image-bounds test below decides only for an input with a valid border: tests/test_preprocess_reference_cpu.py
+ * (test_radii_and_isolated_pixel_removal, valid_border) and tests/test_gpu_preprocess_edges.py
+ * (test_radii_on_an_input_with_a_valid_border) feed it the bilateral filter's output to reach it. */
 void bso_compute_point_radii_and_remove_isolated_pixels(const bslam_camera4f* depth_camera, float raw_to_float_depth,
                                                         const bslam_buffer2d* in_depth, const bslam_buffer2d* out_radius,
                                                         const bslam_buffer2d* out_depth) {
@@ -200,7 +203,7 @@ void bso_compute_point_radii_and_remove_isolated_pixels(const bslam_camera4f* de
       for (int dy = y - 1; dy < y + 2; ++dy) {
         for (int dx = x - 1; dx < x + 2; ++dx) {
           if ((dx != x && dy != y) || (dx == x && dy == y)) continue;
-          if (dx < 0 || dy < 0 || dx >= w || dy >= h) continue;     /* only reachable if the input has a valid border */
+          if (dx < 0 || dy < 0 || dx >= w || dy >= h) continue;     /* a border pixel has fewer than 4 neighbours: never kept */
           uint16_t dd = BSO_AT(uint16_t, in_depth, dy, dx);
           if (dd & BSLAM_INVALID_DEPTH_BIT) continue;
           ++neighbor_count;

@@ -84,6 +84,11 @@ def lib():
         "bso_compact_surfels": (None, [C.c_uint32, u32p, _BUF, _BUF]),
         "bso_track_frame_pairwise": (None, [C.c_int, C.c_int, C.c_int, _CAM, _CAM, _DP, _BUF, _BUF, _BUF, _BUF, _BUF, _BUF, C.c_int, C.c_int,
                                             P(abi.SE3f), P(abi.SE3f), P(abi.SE3f), P(C.c_int)]),
+        "bso_brightness_from_color": (None, [_BUF, _BUF]),
+        "bso_set_to_read_mode_normalized": (None, [_BUF, _BUF]),
+        "bso_calibrate_depth": (None, [_DP, _BUF, _BUF]),
+        "bso_calibrate_depth_and_transform_color_to_depth": (None, [_CAM, _CAM, _DP, _BUF, _BUF, C.c_int, _BUF, _BUF]),   # depth camera first
+        "bso_downsample_images": (None, [_BUF, _BUF, _BUF, C.c_int, _BUF, _BUF, _BUF]),
         "bso_compute_sobel_gradient_magnitude": (None, [_BUF, _BUF]),
         "bso_calibrate_and_downsample_images": (None, [C.c_int, _DP, _BUF, _BUF, _BUF, C.c_int, _BUF, _BUF, _BUF]),
         "bso_set_tracking_variant": (None, [C.c_int, C.c_int]),

@@ -10,40 +10,13 @@ import badslam_amd
 from badslam_amd import abi
 from badslam_amd import direct_ba as dba
 from tests import bso
+from tests.preprocess_util import np_downsample
 from tests.test_gpu_bad_slam_input_conditioning import render_sequence
 from tests.test_gpu_input_conditioning import np_downscale_rgb
 from tests.test_gpu_preprocess import stream_ptr
 
 pytestmark = pytest.mark.gpu
 f32 = np.float32
-
-
-def np_downsample(depth, normals, color, out_normals_fill):
-    """DownsampleImages (BS/kernel_downsample.cu:105-152), all in fp32.  Depth: of each 2x2 block the valid (> 0) depth nearest
-    to the block's mean of valid depths (first one on a tie; 0 without a valid one), with that pixel's normal.  Colour, on its
-    own grid: the bilinear sample at the block's centre, i.e. weights 1/4 on texels normalised by 1/255, then
-    trunc(255 * value + 0.5)."""
-    h, w = depth.shape[0] // 2, depth.shape[1] // 2
-    d4 = np.stack([depth[i >> 1:2 * h:2, i & 1:2 * w:2] for i in range(4)], -1).astype(f32)
-    n4 = np.stack([normals[i >> 1:2 * h:2, i & 1:2 * w:2] for i in range(4)], -1)
-    valid = d4 > 0
-    total = np.zeros((h, w), f32)
-    for i in range(4):
-        total = np.where(valid[..., i], total + d4[..., i], total).astype(f32)
-    count = valid.sum(-1)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        mean = (total / count.astype(f32)).astype(f32)
-        distance = np.abs(np.where(valid, d4, f32(np.inf)) - mean[..., None])
-    pick = np.argmin(np.where(count[..., None] > 0, distance, 0), -1)[..., None]
-    out_depth = np.where(count > 0, np.take_along_axis(d4, pick, -1)[..., 0], f32(0)).astype(f32)
-    out_normals = np.where(count > 0, np.take_along_axis(n4, pick, -1)[..., 0], out_normals_fill).astype(np.uint16)
-    ch, cw = color.shape[0] // 2, color.shape[1] // 2
-    t = [color[i >> 1:2 * ch:2, i & 1:2 * cw:2].astype(f32) * f32(1.0 / 255.0) for i in range(4)]
-    q = f32(0.25)
-    value = ((q * t[0] + q * t[1]) + q * t[2]) + q * t[3]
-    assert value.dtype == f32
-    out_color = np.clip(np.trunc(f32(255) * value + f32(0.5)), 0, 255).astype(np.uint8)
-    return out_depth, out_normals, out_color
 
 
 def padded(torch, array, pad, fill):

@@ -124,6 +124,10 @@ SIGNATURES = {
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "bslam_point_mesh_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float,
                                             C.c_uint64, C.c_void_p, C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
+    "bslam_registration_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_uint64,
+                                             P(C.c_uint64), P(C.c_uint64)]),
+    "bslam_registration_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, P(C.c_float), C.c_float, C.c_int, C.c_float, C.c_void_p, C.c_void_p,
+                                          P(C.c_float), P(C.c_uint64)]),
     "bslam_volume_views_aux_bytes": (C.c_int, [P(Volume), P(C.c_size_t)]),
     "bslam_prepare_volume_views": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, C.c_uint32, C.c_void_p, C.c_size_t]),
     "bslam_raycast_volume": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, C.c_void_p, P(Mat3x4), _CAM, C.c_float, C.c_float, C.c_float, C.c_float,

@@ -22,6 +22,7 @@
 #include "fusion_kernels.hpp"
 #include "mesh_kernels.hpp"
 #include "distance_kernels.hpp"
+#include "registration_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1405,6 +1406,7 @@ int bslam_debug_pose_residuals(
 #include "fusion_abi.inc"
 #include "mesh_abi.inc"
 #include "distance_abi.inc"
+#include "registration_abi.inc"
 #include "raycast_abi.inc"
 #include "place_abi.inc"
 #include "odometry_abi.inc"

@@ -161,7 +161,17 @@ struct bslam_context {
   bool place_pattern_ready = false;
   bslam::Slab fusion;        // bslam_extract_mesh: active flags and quad counts u8[cells], vertex ids and quad offsets u32[cells], scan sums;
                              // bslam_mesh_components: parent and root sizes u32[V]; bslam_filter_mesh: keep flags, ranks, scan sums
-  bslam::Slab distance;      // bslam_point_mesh_distance: triangle records, cell lists, sorted points, scan sums
+  bslam::Slab distance;      // bslam_point_mesh_distance: triangle records, cell lists, sorted points, scan sums; bslam_registration_step: its per-call scratch
+  bslam::Slab registration;  // bslam_registration_prepare: words | records | cell_count (all zero between calls) | cell_start | list -- a slab of its
+                             // own, because a slab that grows discards what it held and `distance` is per-call scratch
+  struct PreparedMesh {      // what that slab holds; the pointers lie inside it
+    bool ready = false;
+    float radius = 0.f;      // R0 of the dilated boxes
+    float origin[3] = {0.f, 0.f, 0.f}, inv_cell = 0.f;
+    int dim[3] = {0, 0, 0};
+    uint32_t cells = 0, valid = 0, triangles = 0;
+    void *records = nullptr, *cell_count = nullptr, *cell_start = nullptr, *list = nullptr;
+  } prepared;
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

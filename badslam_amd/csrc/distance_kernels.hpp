@@ -174,15 +174,31 @@ __global__ __launch_bounds__(256) void pmd_miss_kernel(uint32_t points, float* _
   if (out_triangle != nullptr) out_triangle[i] = kPmdNoTriangle;
 }
 
+// A rigid transform of the points, applied on the fly (bslam_registration_step): row-major 3 x 4.
+struct PmdTransform { float m[12]; };
+
+// Point i as the query sees it: the caller's point, or (kTransform) M applied to it,
+//   p'.a = fmaf(M[a][2], p.z, fmaf(M[a][1], p.y, fmaf(M[a][0], p.x, M[a][3]))),
+// the one expression every kernel that needs p' repeats, so that each of them holds the same bits.
+template <bool kTransform>
+__device__ __forceinline__ f3 pmd_point(const float* __restrict__ xyz, const PmdTransform& M, uint32_t i) {
+  const f3 p = mk3(xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2]);
+  if (!kTransform) return p;
+  return mk3(__builtin_fmaf(M.m[2], p.z, __builtin_fmaf(M.m[1], p.y, __builtin_fmaf(M.m[0], p.x, M.m[3]))),
+             __builtin_fmaf(M.m[6], p.z, __builtin_fmaf(M.m[5], p.y, __builtin_fmaf(M.m[4], p.x, M.m[7]))),
+             __builtin_fmaf(M.m[10], p.z, __builtin_fmaf(M.m[9], p.y, __builtin_fmaf(M.m[8], p.x, M.m[11]))));
+}
+
 // The cell of every point.  A point outside the grid (a NaN fails every comparison) or in a cell without triangles is written as
 // a miss here and is not sorted; the others are counted per cell.
-__global__ __launch_bounds__(256) void pmd_point_cells_kernel(PmdGrid g, uint32_t points, const float* __restrict__ xyz, const uint32_t* __restrict__ cell_start,
-                                                              uint32_t* __restrict__ cell_count, uint32_t* __restrict__ point_cell, float* __restrict__ out_distance,
-                                                              uint32_t* __restrict__ out_triangle) {
+template <bool kTransform>
+__global__ __launch_bounds__(256) void pmd_point_cells_kernel(PmdGrid g, uint32_t points, const float* __restrict__ xyz, PmdTransform M,
+                                                              const uint32_t* __restrict__ cell_start, uint32_t* __restrict__ cell_count,
+                                                              uint32_t* __restrict__ point_cell, float* __restrict__ out_distance, uint32_t* __restrict__ out_triangle) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= points) return;
-  const float cx = pmd_cell(xyz[3 * (size_t)i], g.origin[0], g.inv_cell), cy = pmd_cell(xyz[3 * (size_t)i + 1], g.origin[1], g.inv_cell),
-              cz = pmd_cell(xyz[3 * (size_t)i + 2], g.origin[2], g.inv_cell);
+  const f3 p = pmd_point<kTransform>(xyz, M, i);
+  const float cx = pmd_cell(p.x, g.origin[0], g.inv_cell), cy = pmd_cell(p.y, g.origin[1], g.inv_cell), cz = pmd_cell(p.z, g.origin[2], g.inv_cell);
   uint32_t cell = kPmdNoTriangle;
   if (cx >= 0.f && cx < (float)g.dim[0] && cy >= 0.f && cy < (float)g.dim[1] && cz >= 0.f && cz < (float)g.dim[2]) {
     cell = pmd_cell_index(g, (int)cx, (int)cy, (int)cz);
@@ -209,12 +225,16 @@ __global__ __launch_bounds__(256) void pmd_point_fill_kernel(uint32_t points, co
 }
 
 // seg(p, a, b) of the rule from w = p - a and the record's e = b - a, ee = dot(e, e).
-__device__ __forceinline__ float pmd_segment(f3 w, float4 e) {
+// The q of the rule is the offset from the segment's nearest point to p.
+__device__ __forceinline__ f3 pmd_segment_offset(f3 w, float4 e) {
   const f3 ev = mk3(e.x, e.y, e.z);
   const float we = dot(w, ev);
   float t = e.w > 0.f ? we / e.w : 0.f;
   t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-  const f3 q = mk3(__builtin_fmaf(-t, ev.x, w.x), __builtin_fmaf(-t, ev.y, w.y), __builtin_fmaf(-t, ev.z, w.z));
+  return mk3(__builtin_fmaf(-t, ev.x, w.x), __builtin_fmaf(-t, ev.y, w.y), __builtin_fmaf(-t, ev.z, w.z));
+}
+__device__ __forceinline__ float pmd_segment(f3 w, float4 e) {
+  const f3 q = pmd_segment_offset(w, e);
   return dot(q, q);
 }
 
@@ -227,7 +247,8 @@ struct PmdQuery {
   const uint32_t* cell_start;    // [cells + 1]
   const uint32_t* list;
   const float4* records;
-  float r_squared;               // fl(R * R), formed on the host
+  float r_squared;               // fl(R * R), formed on the host: of the call's R, which may be below the radius of the boxes
+  PmdTransform transform;        // read by the kTransform variant only
   float* out_distance;
   uint32_t* out_triangle;        // may be null
 };
@@ -239,8 +260,8 @@ struct PmdQuery {
 // four waves of a block share nothing but the barriers, which keep the stage and the walk of a tile apart; a wave that has
 // finished goes on attending them until the block's last wave has.  (best, triangle) stay in registers, every lane writes its own
 // point once, at the point's original index.  No atomics but the profiling counters' (kStats: {pairs offered, pairs that passed
-// the box test} of bslam_debug_cull_stats).
-template <bool kStats>
+// the box test} of bslam_debug_cull_stats).  kTransform: the point is M applied to the caller's (bslam_registration_step).
+template <bool kStats, bool kTransform>
 __global__ __launch_bounds__(256) void pmd_query_kernel(PmdQuery q, unsigned long long* __restrict__ stats) {
   __shared__ float4 tiles[4][kPmdTile * kPmdRecordQuads];
   const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
@@ -252,7 +273,7 @@ __global__ __launch_bounds__(256) void pmd_query_kernel(PmdQuery q, unsigned lon
   if (live) {
     index = q.sorted[slot];
     my_cell = q.point_cell[index];
-    p = mk3(q.points[3 * (size_t)index], q.points[3 * (size_t)index + 1], q.points[3 * (size_t)index + 2]);
+    p = pmd_point<kTransform>(q.points, q.transform, index);
   }
   float best = __uint_as_float(0x7f800000u);
   uint32_t best_triangle = kPmdNoTriangle;

@@ -88,6 +88,11 @@ def host_lib():
                                           f32p, u64p]
     L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
     L.bsh_distance_copy.argtypes = [f32p, u32p]
+    f64p = C.POINTER(C.c_double)
+    L.bsh_register_points.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, f64p, f64p, f64p, C.POINTER(C.c_int32), f64p]
+    L.bsh_registration_history.argtypes = [f64p]
+    L.bsh_registration_reason.argtypes = [C.c_int]
+    L.bsh_registration_reason.restype = C.c_char_p
     _host = L
     return L
 
@@ -764,6 +769,40 @@ class DirectBA:
         distance, triangle = np.zeros(count.value, np.float32), np.zeros(count.value, np.uint32)
         self._check(self.L.bsh_distance_copy(_f(distance), _u32(triangle)))
         return self._distance_result(distance, triangle, cell, grid)
+
+    # --- surface registration (bslam_registration_prepare / bslam_registration_step)
+    REGISTRATION_PLANE, REGISTRATION_POINT = 0, 1
+
+    def RegisterPoints(self, points, mesh, max_distance, min_distance=None, initial=None, mode=None, huber=None, shrink=0.5, iterations_per_stage=20,
+                       cell_size=None, max_grid_entries=1 << 28):
+        """The rigid motion that lays `points` (n, 3) onto `mesh` (the dict of ExtractMesh or LoadPLY; without triangles a point
+        cloud), by iterative closest point from `initial` (4 x 4, default identity): stages at the search radii max_distance, shrink
+        * that, ... down to min_distance (default max_distance / 8), each until the step is below 10 um / 1 urad or
+        iterations_per_stage steps were taken.  mode: REGISTRATION_PLANE (point to plane; the default for a mesh with triangles) or
+        REGISTRATION_POINT (point to nearest point of the surface; the default for a cloud).  huber: the Huber width of the
+        residuals (default: half the radius of the stage; float("inf"): none).  These defaults are provisional: they were tried on
+        synthetic scenes only.
+        -> dict of target_T_source (4, 4) float64, iterations, converged (the last stage ended by the convergence test), reason,
+        history (a dict per step: radius, hits, used, cost, rmse, step_translation, step_rotation) and the grid of the prepared
+        mesh (cell_size, grid_cells, grid_entries).  Fewer than 6 pairs or a singular system end the loop with converged False
+        and the last valid transform; nothing is raised for them."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        options = np.array([max_distance, 0.0 if min_distance is None else min_distance, -1 if mode is None else int(mode), 0.0 if huber is None else huber,
+                            shrink, iterations_per_stage, 0.0 if cell_size is None else cell_size, max_grid_entries], np.float64)
+        start = np.ascontiguousarray(np.eye(4) if initial is None else initial, np.float64).reshape(4, 4)
+        transform, status, grid = np.zeros((4, 4), np.float64), (C.c_int32 * 3)(), np.zeros(3, np.float64)
+        d = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        self._check(self.L.bsh_register_points(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), _u32(tri), d(options), d(start), d(transform),
+                                               status, d(grid)))
+        rows = np.zeros((status[0], 7), np.float64)
+        self._check(self.L.bsh_registration_history(d(rows)))
+        history = [dict(radius=float(r[0]), hits=int(r[1]), used=int(r[2]), cost=float(r[3]), rmse=float(r[4]), step_translation=float(r[5]),
+                        step_rotation=float(r[6])) for r in rows]
+        return dict(target_T_source=transform, iterations=int(status[0]), converged=bool(status[1]), reason=self.L.bsh_registration_reason(status[2]).decode(),
+                    history=history, cell_size=float(grid[0]), grid_cells=int(grid[1]), grid_entries=int(grid[2]))
 
     def Volume(self):
         """Download of the fused volume: dict of origin (3,), voxel_size, truncation, dims (nx, ny, nz) and the arrays tsdf f32,

@@ -314,6 +314,49 @@ int bsh_distance_copy(float* distance, uint32_t* triangle) {
     g_distance = DirectBA::PointMeshResult();
   });
 }
+// DirectBA::RegisterPoints of host arrays, in two steps like the mesh.  options8 = {max_distance, min_distance (0: max / 8), mode
+// (-1: by the mesh), huber (0: half the stage's radius), shrink, iterations_per_stage, cell_size (0: doubling), max_grid_entries};
+// initial16 and transform16 are row-major 4 x 4; status3 = {steps, converged, DirectBA::RegistrationEnd}; grid3 = {cell used, cells,
+// entries}.  bsh_registration_history copies 7 doubles per step (radius, hits, used, cost, rmse, step translation, step rotation)
+// and drops them; bsh_registration_reason names an end.
+static thread_local std::vector<DirectBA::RegistrationStep> g_registration;
+int bsh_register_points(void* ba, void* stream, uint64_t point_count, const float* points, uint64_t vertices, const float* positions, uint64_t triangles,
+                        const uint32_t* indices, const double* options8, const double* initial16, double* transform16, int32_t* status3, double* grid3) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::RegistrationOptions options;
+    options.max_distance = static_cast<float>(options8[0]);
+    options.min_distance = static_cast<float>(options8[1]);
+    options.mode = static_cast<int>(options8[2]);
+    options.huber = static_cast<float>(options8[3]);
+    options.shrink = options8[4];
+    options.iterations_per_stage = static_cast<int>(options8[5]);
+    options.cell_size = static_cast<float>(options8[6]);
+    options.max_grid_entries = static_cast<uint64_t>(options8[7]);
+    std::copy(initial16, initial16 + 16, options.initial);
+    DirectBA::RegistrationResult result;
+    static_cast<DirectBA*>(ba)->RegisterPoints(static_cast<hipStream_t>(stream), points, point_count, mesh, options, &result);
+    std::copy(result.target_T_source, result.target_T_source + 16, transform16);
+    status3[0] = static_cast<int32_t>(result.history.size());
+    status3[1] = result.converged ? 1 : 0;
+    status3[2] = result.end;
+    if (grid3) { grid3[0] = result.cell_size; grid3[1] = static_cast<double>(result.grid_cells); grid3[2] = static_cast<double>(result.grid_entries); }
+    g_registration = std::move(result.history);
+  });
+}
+int bsh_registration_history(double* rows7) {
+  BSH_TRY({
+    for (size_t i = 0; i < g_registration.size(); ++i) {
+      const DirectBA::RegistrationStep& s = g_registration[i];
+      const double row[7] = {s.radius, static_cast<double>(s.hits), static_cast<double>(s.used), s.cost, s.rmse, s.step_translation, s.step_rotation};
+      std::copy(row, row + 7, rows7 + 7 * i);
+    }
+    g_registration.clear();
+  });
+}
+const char* bsh_registration_reason(int end) { return DirectBA::RegistrationReason(end); }
 // LoadPLY in two steps: bsh_load_ply reads the file, keeps it for this thread and reports counts4 = {vertices, triangles, has
 // normals, has colours}; bsh_ply_copy copies it out (positions, normals: 3 floats per vertex; colors: 3 bytes per vertex; indices:
 // 3 per triangle; any may be null) and drops it.

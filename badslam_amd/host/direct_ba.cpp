@@ -664,6 +664,110 @@ void DirectBA::SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& op
                             mesh_indices_ ? mesh_indices_->address() : nullptr, options, result);
 }
 
+const char* DirectBA::RegistrationReason(int end) {
+  switch (end) {
+    case kRegistrationConverged: return "converged";
+    case kRegistrationIterationsExhausted: return "iterations exhausted";
+    case kRegistrationTooFewPairs: return "fewer than 6 pairs";
+    case kRegistrationSingular: return "singular system";
+  }
+  return "unknown";
+}
+
+void DirectBA::RegisterPoints(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const RegistrationOptions& options,
+                              RegistrationResult* result) {
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
+      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull || 3 * static_cast<uint64_t>(point_count) > 0x7fffffffull)
+    throw std::invalid_argument("RegisterPoints: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  if (!(options.max_distance > 0.f) || !(options.shrink > 0.0 && options.shrink < 1.0) || options.iterations_per_stage < 1 || options.min_distance < 0.f ||
+      options.huber < 0.f)
+    throw std::invalid_argument("RegisterPoints: max_distance > 0, 0 < shrink < 1, iterations_per_stage >= 1, min_distance and huber >= 0 are required");
+  for (double v : options.initial)
+    if (!std::isfinite(v)) throw std::invalid_argument("RegisterPoints: the initial transform is not finite");
+  // a point cloud: every vertex is its own degenerate triangle
+  const bool cloud = mesh.indices.empty();
+  std::vector<u32> own;
+  if (cloud) {
+    own.resize(mesh.positions.size());
+    for (size_t i = 0; i < own.size(); ++i) own[i] = static_cast<u32>(i / 3);
+  }
+  const std::vector<u32>& indices = cloud ? own : mesh.indices;
+  const int mode = options.mode >= 0 ? options.mode : (cloud ? BSLAM_REGISTRATION_POINT : BSLAM_REGISTRATION_PLANE);
+  const u32 n = static_cast<u32>(point_count), vertices = static_cast<u32>(mesh.vertex_count()), triangles = static_cast<u32>(indices.size() / 3);
+  *result = RegistrationResult();
+  std::copy(options.initial, options.initial + 16, result->target_T_source);
+  {
+    DeviceArray<float> dev_positions(mesh.positions.size());
+    DeviceArray<u32> dev_indices(indices.size());
+    dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
+    dev_indices.Upload(stream, indices.data(), indices.size());
+    Wait(stream);
+    float cell = options.cell_size > 0.f ? options.cell_size : options.max_distance;
+    for (int attempt = 0;; ++attempt) {
+      uint64_t cells = 0, entries = 0;
+      const int rc = bslam_registration_prepare(ctx_, stream, vertices, dev_positions.address(), triangles, dev_indices.address(), options.max_distance, cell,
+                                                options.max_grid_entries, &cells, &entries);
+      const bool over_budget = rc == BSLAM_ERR_INVALID_ARGUMENT && (entries > options.max_grid_entries || cells > BSLAM_POINT_MESH_MAX_CELLS);
+      if (over_budget && !(options.cell_size > 0.f) && attempt < 64 && std::isfinite(cell * 2.f)) { cell *= 2.f; continue; }
+      Check(rc, "bslam_registration_prepare");
+      result->cell_size = cell;
+      result->grid_cells = cells;
+      result->grid_entries = entries;
+      break;
+    }
+  }   // the records hold copies of the vertices
+  DeviceArray<float> dev_points(3 * point_count);
+  dev_points.Upload(stream, points, 3 * point_count);
+  Wait(stream);
+  double* T = result->target_T_source;
+  const double min_distance = options.min_distance > 0.f ? options.min_distance : static_cast<double>(options.max_distance) / 8.0;
+  const double weigh = kRegistrationStepTranslation / kRegistrationStepRotation;
+  bool stop = false;
+  for (double R = options.max_distance; !stop && R >= min_distance; R *= options.shrink) {
+    const float huber = options.huber > 0.f ? options.huber : static_cast<float>(R / 2.0);
+    result->converged = false;
+    result->end = kRegistrationIterationsExhausted;
+    for (int it = 0; it < options.iterations_per_stage; ++it) {
+      float M[12], sums[32];
+      uint64_t counts[4];
+      for (int k = 0; k < 12; ++k) M[k] = static_cast<float>(T[k]);
+      Check(bslam_registration_step(ctx_, stream, n, dev_points.address(), M, static_cast<float>(R), mode, huber, nullptr, nullptr, sums, counts),
+            "bslam_registration_step");
+      RegistrationStep entry;
+      entry.radius = R;
+      entry.hits = counts[1];
+      entry.used = counts[2];
+      entry.cost = sums[27];
+      entry.rmse = counts[2] ? std::sqrt(static_cast<double>(sums[28]) / static_cast<double>(counts[2])) : std::nan("");
+      entry.step_translation = entry.step_rotation = std::nan("");
+      result->history.push_back(entry);
+      if (counts[2] < 6) { result->end = kRegistrationTooFewPairs; stop = true; break; }
+      float minus_b[6], x[6];
+      for (int k = 0; k < 6; ++k) minus_b[k] = -sums[21 + k];
+      double share = 0.0;
+      SolveLDLTUpper(6, sums, minus_b, x, &share);
+      bool finite = true;
+      for (float v : x) finite = finite && std::isfinite(v);
+      if (!(share > kRegistrationSingularShare) || !finite) { result->end = kRegistrationSingular; stop = true; break; }
+      double delta[6], E[16], next[16];
+      for (int k = 0; k < 6; ++k) delta[k] = x[k];
+      ExpSE3d(delta, E);
+      for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) next[4 * r + c] = E[4 * r] * T[c] + E[4 * r + 1] * T[4 + c] + E[4 * r + 2] * T[8 + c] + E[4 * r + 3] * T[12 + c];
+      std::copy(next, next + 16, T);
+      RegistrationStep& taken = result->history.back();
+      taken.step_translation = std::sqrt(delta[0] * delta[0] + delta[1] * delta[1] + delta[2] * delta[2]);
+      taken.step_rotation = std::sqrt(delta[3] * delta[3] + delta[4] * delta[4] + delta[5] * delta[5]);
+      const double rot = taken.step_rotation * weigh;
+      if (taken.step_translation * taken.step_translation + rot * rot < kRegistrationStepTranslation * kRegistrationStepTranslation) {
+        result->converged = true;
+        result->end = kRegistrationConverged;
+        break;
+      }
+    }
+  }
+}
+
 u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes) {
   if (mesh.vertex_count() > 0xffffffffull || mesh.triangle_count() > 0xffffffffull || mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0)
     throw std::invalid_argument("MeshComponents: positions and indices must hold 3 entries per vertex and per triangle, fewer than 2^32 of each");

@@ -318,6 +318,46 @@ class DirectBA {
   // returned, which stays on the device for this: how far the surfels that bundle adjustment optimised lie from the surface the
   // volume produced -- a consistency figure that needs no ground truth.  Throws std::logic_error if no mesh was extracted.
   void SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& options, PointMeshResult* result);
+  // Surface registration (bslam_registration_prepare / bslam_registration_step): the rigid motion target_T_source that lays the
+  // points onto the mesh, by iterative closest point from `initial`.  The points are uploaded and the mesh is prepared once, at
+  // max_distance (with the cell doubling of PointMeshDistance while over budget); stages run at the radii max_distance, shrink *
+  // that, ... down to min_distance, each until the step falls below kRegistrationStepTranslation / Rotation or
+  // iterations_per_stage steps were taken.  Per step the normal equations come from the device, delta = (translation, rotation)
+  // solves H delta = -b (SolveLDLTUpper) and the estimate becomes Exp(delta) * estimate, in double.  A mesh without triangles is a
+  // point cloud: every vertex is the triangle (i, i, i).  The defaults below -- and the stage schedule -- are provisional: they
+  // were tried on synthetic scenes only.
+  static constexpr double kRegistrationStepTranslation = 1e-5;   // metres: IsScale1PoseEstimationConverged's form of test, the
+  static constexpr double kRegistrationStepRotation = 1e-6;      // rotation weighing 10 x, at a scale that fits a scan in metres
+  static constexpr double kRegistrationSingularShare = 1e-5;     // a pivot that keeps less of its variable's diagonal: singular
+  struct RegistrationOptions {
+    float max_distance = 0.1f;
+    float min_distance = 0.f;          // 0: max_distance / 8
+    int mode = -1;                     // BSLAM_REGISTRATION_PLANE / _POINT; -1: PLANE for a mesh with triangles, POINT for a cloud
+    float huber = 0.f;                 // 0: half the radius of the stage
+    double shrink = 0.5;
+    int iterations_per_stage = 20;
+    float cell_size = 0.f;
+    uint64_t max_grid_entries = 1ull << 28;
+    double initial[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // row-major 4 x 4
+  };
+  struct RegistrationStep {
+    double radius = 0.0;
+    uint64_t hits = 0, used = 0;
+    double cost = 0.0, rmse = 0.0;                                // rmse: sqrt(sum r^2 / used); NaN without a pair
+    double step_translation = 0.0, step_rotation = 0.0;           // norms of the step's parts; NaN when none was taken
+  };
+  enum RegistrationEnd { kRegistrationConverged = 0, kRegistrationIterationsExhausted = 1, kRegistrationTooFewPairs = 2, kRegistrationSingular = 3 };
+  static const char* RegistrationReason(int end);
+  struct RegistrationResult {
+    double target_T_source[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bool converged = false;            // the last stage ended by the convergence test
+    int end = kRegistrationIterationsExhausted;
+    std::vector<RegistrationStep> history;   // one entry per step
+    float cell_size = 0.f;
+    uint64_t grid_cells = 0, grid_entries = 0;
+  };
+  // Too few pairs (< 6) or a singular system end the loop: converged = false, the last valid estimate is returned, nothing throws.
+  void RegisterPoints(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const RegistrationOptions& options, RegistrationResult* result);
   void Volume(hipStream_t stream, VolumeData* volume) const;         // download of that volume
   // Views of the volume of the last FuseKeyframes from a pose (bslam_raycast_volume): per pixel the first front-facing zero
   // crossing of the trilinear interpolant along the ray, as depth (units of a keyframe's depth image), colour and normal -- no

@@ -5,7 +5,9 @@
 // routines Sophus relies on are written out.
 #pragma once
 
+#include <algorithm>
 #include <cmath>
+#include <limits>
 #include <utility>
 
 #include "../../include/badslam_hip.h"
@@ -187,12 +189,18 @@ inline bool IsScale1PoseEstimationConverged(const float* x) {
 
 // x = H^-1 b for the packed upper triangle H (row-major) in double: LDL^T with diagonal pivoting,
 // what Eigen's selfadjointView<Upper>().ldlt().solve() computes (BS/direct_ba_alternating.cc:206).
-inline void SolveLDLTUpper(int n, const float* H_upper, const float* b, float* x) {
+// *min_pivot_share (may be null) receives the smallest d_k / H_pp over the pivots, p the variable of pivot k and H_pp its diagonal
+// entry before any elimination (0 where H_pp is not > 0): the share of a variable's curvature the variables eliminated before it
+// do not explain.  Not positive, or tiny: the system is singular in that direction.
+inline void SolveLDLTUpper(int n, const float* H_upper, const float* b, float* x, double* min_pivot_share = nullptr) {
   double A[36];
   int idx = 0;
   for (int r = 0; r < n; ++r)
     for (int c = r; c < n; ++c) { A[r * n + c] = H_upper[idx]; A[c * n + r] = H_upper[idx]; ++idx; }
   int perm[6];
+  double diag0[6];
+  for (int i = 0; i < n; ++i) diag0[i] = A[i * n + i];
+  double share = std::numeric_limits<double>::infinity();
   for (int k = 0; k < n; ++k) {
     int p = k;
     double biggest = std::fabs(A[k * n + k]);
@@ -201,6 +209,7 @@ inline void SolveLDLTUpper(int n, const float* H_upper, const float* b, float* x
     if (p != k) {
       for (int c = 0; c < n; ++c) std::swap(A[k * n + c], A[p * n + c]);
       for (int r = 0; r < n; ++r) std::swap(A[r * n + k], A[r * n + p]);
+      std::swap(diag0[k], diag0[p]);
     }
     double temp[6];
     for (int j = 0; j < k; ++j) temp[j] = A[j * n + j] * A[k * n + j];
@@ -208,6 +217,7 @@ inline void SolveLDLTUpper(int n, const float* H_upper, const float* b, float* x
     for (int j = 0; j < k; ++j) acc += A[k * n + j] * temp[j];
     const double dk = A[k * n + k] - acc;
     A[k * n + k] = dk;
+    share = std::min(share, diag0[k] > 0.0 ? dk / diag0[k] : 0.0);
     for (int i = k + 1; i < n; ++i) {
       double s = 0.0;
       for (int j = 0; j < k; ++j) s += A[i * n + j] * temp[j];
@@ -223,6 +233,35 @@ inline void SolveLDLTUpper(int n, const float* H_upper, const float* b, float* x
   for (int i = n - 1; i >= 0; --i) for (int j = i + 1; j < n; ++j) y[i] -= A[j * n + i] * y[j];
   for (int k = n - 1; k >= 0; --k) if (perm[k] != k) std::swap(y[k], y[perm[k]]);
   for (int i = 0; i < n; ++i) x[i] = static_cast<float>(y[i]);
+  if (min_pivot_share) *min_pivot_share = share;
+}
+
+// Exp of se(3) in double, delta = (translation, rotation), as a row-major 4 x 4 matrix (SE3f::Exp's formulas; its small-angle
+// branch by the series).
+inline void ExpSE3d(const double* delta, double* T) {
+  const double ox = delta[3], oy = delta[4], oz = delta[5];
+  const double theta_sq = ox * ox + oy * oy + oz * oz, theta = std::sqrt(theta_sq);
+  double a, b, c;   // sin(theta) / theta, (1 - cos(theta)) / theta^2, (theta - sin(theta)) / theta^3
+  if (theta < 1e-8) {
+    a = 1.0 - theta_sq / 6.0; b = 0.5 - theta_sq / 24.0; c = 1.0 / 6.0 - theta_sq / 120.0;
+  } else {
+    a = std::sin(theta) / theta; b = (1.0 - std::cos(theta)) / theta_sq; c = (theta - std::sin(theta)) / (theta_sq * theta);
+  }
+  const double O[9] = {0.0, -oz, oy, oz, 0.0, -ox, -oy, ox, 0.0};
+  double O2[9];
+  for (int r = 0; r < 3; ++r)
+    for (int col = 0; col < 3; ++col) O2[3 * r + col] = O[3 * r + 0] * O[0 + col] + O[3 * r + 1] * O[3 + col] + O[3 * r + 2] * O[6 + col];
+  for (int r = 0; r < 3; ++r) {
+    double t = 0.0;
+    for (int col = 0; col < 3; ++col) {
+      const double id = r == col ? 1.0 : 0.0;
+      T[4 * r + col] = id + a * O[3 * r + col] + b * O2[3 * r + col];
+      t += (id + b * O[3 * r + col] + c * O2[3 * r + col]) * delta[col];
+    }
+    T[4 * r + 3] = t;
+  }
+  T[12] = T[13] = T[14] = 0.0;
+  T[15] = 1.0;
 }
 
 }  // namespace bslam_host

@@ -12,8 +12,9 @@ search radius fails every threshold.
 
 Completeness is sampled at the ground truth's VERTICES.  A coarsely tessellated ground truth (a wall of two triangles) says
 nothing about the surface between its corners: its owner has to subdivide it to the resolution the thresholds ask for.  No
-surface sampler is part of this.  The ground truth has to be given in the frame of the reconstruction; align it first, for
-example with the transform ate.align_rigid finds for the trajectory.  A ground truth without triangles is a point cloud (the form the
+surface sampler is part of this.  The ground truth has to be given in the frame of the reconstruction, or evaluate(register=True)
+has to bring the reconstruction into the ground truth's frame first (DirectBA.RegisterPoints, an iterative closest point that
+needs a start within its search radius, for example the transform ate.align_rigid finds for the trajectory).  A ground truth without triangles is a point cloud (the form the
 ETH3D SLAM scans come in): every point then is its own degenerate triangle.
 
 distance_summary is pure NumPy; evaluate needs a DirectBA for the distance calls.
@@ -55,17 +56,38 @@ def f_scores(accuracy, completeness):
     return out
 
 
-def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.01, 0.02, 0.05), cell_size=None):
+def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.01, 0.02, 0.05), cell_size=None, register=False, initial=None):
     """reconstruction, ground_truth: mesh dicts (positions (V, 3), triangles (T, 3); DirectBA.ExtractMesh, LoadPLY) in one frame; the
     ground truth may be a point cloud (no or empty triangles).  -> dict of accuracy and completeness (distance_summary each),
     f_scores (a list per threshold), max_distance and the grids the two calls used.  Completeness is sampled at the ground truth's
-    vertices: see the module's docstring."""
+    vertices: see the module's docstring.
+    register: the ground truth is in another frame.  The reconstruction's vertices are registered to it first
+    (DirectBA.RegisterPoints at max_distance from `initial`, a 4 x 4 ground_truth_T_reconstruction, default identity), the motion found
+    is applied to a copy of the reconstruction's positions (in float64, then rounded to float32), and that copy is evaluated.  The
+    result then also has `registration`: target_T_source (4 x 4 as nested lists), iterations, converged, reason, history, and
+    `before`, the accuracy and completeness summaries under `initial` alone."""
+    if register:
+        start = np.eye(4) if initial is None else np.asarray(initial, np.float64).reshape(4, 4)
+        before = evaluate(ba, dict(reconstruction, positions=transform_positions(reconstruction["positions"], start)), ground_truth, max_distance, thresholds, cell_size)
+        found = ba.RegisterPoints(reconstruction["positions"], ground_truth, max_distance, initial=start, cell_size=cell_size)
+        moved = dict(reconstruction, positions=transform_positions(reconstruction["positions"], found["target_T_source"]))
+        result = evaluate(ba, moved, ground_truth, max_distance, thresholds, cell_size)
+        result["registration"] = dict(target_T_source=np.asarray(found["target_T_source"], np.float64).tolist(), iterations=found["iterations"],
+                                      converged=found["converged"], reason=found["reason"], history=found["history"],
+                                      before=dict(accuracy=before["accuracy"], completeness=before["completeness"]))
+        return result
     acc = ba.PointMeshDistance(reconstruction["positions"], ground_truth, max_distance, cell_size)
     com = ba.PointMeshDistance(ground_truth["positions"], reconstruction, max_distance, cell_size)
     accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
     grid = lambda r: dict(cell_size=r["cell_size"], grid_cells=r["grid_cells"], grid_entries=r["grid_entries"])
     return dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
                 accuracy_grid=grid(acc), completeness_grid=grid(com))
+
+
+def transform_positions(positions, T):
+    """T (4 x 4) applied to positions (n, 3) in float64, rounded to float32."""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return np.ascontiguousarray(np.asarray(positions, np.float64).reshape(-1, 3) @ T[:3, :3].T + T[:3, 3], np.float32)
 
 
 def format_summary(name, s):

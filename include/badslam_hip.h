@@ -740,6 +740,54 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream, uint32_t point_c
                               float cell_size, uint64_t max_grid_entries, float* out_distance, uint32_t* out_triangle,
                               uint64_t* grid_cells, uint64_t* grid_entries);
 
+/* Surface registration: one step of an iterative closest point alignment of N points to a mesh -- the correspondences of the
+ * transformed points and their normal equations (DESIGN.md 8 "Surface registration", csrc/registration_kernels.hpp).  The
+ * arithmetic is fp32, nothing is contracted implicitly, and dot, cross, `/`, sqrtf, seg, face and the pair are those of "Surface
+ * evaluation" above.
+ * bslam_registration_prepare builds the triangle side of bslam_point_mesh_distance once -- bounds, entry count with the same
+ * budget refusals and messages, records, cell scan and lists, the same grid with boxes dilated by R0 = max_distance -- and keeps
+ * it in a context slab of its own.  The records hold copies of the vertices: the caller's arrays may be freed when the call
+ * returns (it synchronises `stream`).  The prepared mesh stays valid until the next prepare that gets past its refusals, or
+ * bslam_destroy; bslam_point_mesh_distance calls in between neither disturb it nor are disturbed.  T == 0 is legal: every point
+ * of a step misses.
+ * bslam_registration_step, with M = target_T_source (row-major 3 x 4, host), R = max_distance of the call:
+ * Transform:
+ *   p'.a = fmaf(M[a][2], p.z, fmaf(M[a][1], p.y, fmaf(M[a][0], p.x, M[a][3])));  the points themselves are never written.
+ * Correspondence:
+ *   the rule of bslam_point_mesh_distance for p', with the box predicate at the prepared R0 and the hit test best <= fl(R * R):
+ *   the nearest triangle, the lowest index on ties.  With the identity and R == R0 distance and triangle equal
+ *   bslam_point_mesh_distance bit for bit.  out_distance float[N] and out_triangle uint32[N] (device, each may be null) receive
+ *   them at the point's index.
+ * Offset vector v of a hit, from the winning triangle alone:
+ *   its terms in the order seg ab, seg bc, seg ca, face; a later term replaces an earlier one only when it is strictly smaller.
+ *   For a segment v = the q of the rule; for the face s = d / sqrtf(nn), v.k = s * n.k.
+ * Rows:
+ *   row(m, r, w) with c = cross(p', m), J = (m.x, m.y, m.z, c.x, c.y, c.z) adds (w * J_i) * J_j for i <= j (21 values, upper
+ *   triangle, row-major), (w * J_i) * r (6 values) and r * r.
+ *   BSLAM_REGISTRATION_PLANE: a hit whose triangle has nn > 0 contributes row(nh, d, w) with nh.k = n.k / sqrtf(nn),
+ *     d = dot(p' - a, n) / sqrtf(nn); every other hit counts as degenerate and contributes nothing.
+ *   BSLAM_REGISTRATION_POINT: every hit contributes row(e_x, v.x, w), row(e_y, v.y, w), row(e_z, v.z, w) with one weight.
+ *   Huber: a = |d| (PLANE) or sqrtf(dot(v, v)) (POINT);  w = a <= k ? 1 : k / a;  rho = a <= k ? (0.5f * a) * a :
+ *     k * (a - 0.5f * k), added once per pair.  huber_k = +INFINITY is legal.
+ * Outputs (host): out_sums[0..20] = H, [21..26] = b, [27] = the sum of rho, [28] = the sum of r * r, [29..31] = 0;
+ *   out_counts = {points, hits, pairs used, degenerate hits}, exact.  The update is left-multiplicative: delta = (translation,
+ *   rotation) solves H delta = -b, M <- Exp(delta) * M; the host does that in double.
+ * The sums are formed in a fixed order over the points in their original order -- per wave of 64 consecutive points by a shuffle
+ * tree, then over the waves' rows by pose_reduce_kernel's two stages -- so two calls give identical bits.
+ * Refused without a launch, outputs untouched: a null context, points (N > 0), matrix, out_sums or out_counts; no prepared mesh;
+ * a matrix entry that is not finite; R not finite and > 0, or R > R0; huber_k not > 0 (a NaN included); an unknown mode; more
+ * than 2^32 - 256 points; arrays that are misaligned or outputs that overlap.  N == 0 is legal: sums and counts zero.
+ * Synchronises `stream`.  Every rank of a surfel-sharded run holds the same points and mesh and computes the same result;
+ * nothing is exchanged. */
+#define BSLAM_REGISTRATION_PLANE 0
+#define BSLAM_REGISTRATION_POINT 1
+int bslam_registration_prepare(bslam_context* ctx, void* stream, uint32_t vertex_count, const float* positions, uint32_t triangle_count,
+                               const uint32_t* indices, float max_distance, float cell_size, uint64_t max_grid_entries,
+                               uint64_t* grid_cells, uint64_t* grid_entries);
+int bslam_registration_step(bslam_context* ctx, void* stream, uint32_t point_count, const float* points, const float* target_T_source,
+                            float max_distance, int mode, float huber_k, float* out_distance, uint32_t* out_triangle,
+                            float* out_sums, uint64_t* out_counts);
+
 /* Surface views: a per-pixel ray-cast of a fused volume (depth, colour and normal from a pose, without the holes of the disc
  * view where surfels are sparse).  All arithmetic is fp32 in a fixed expression order with explicit fused multiply-adds
  * (csrc/raycast_kernels.hpp, DESIGN.md 8 "Surface views"); two calls give identical bits.  With G = global_T_camera,

@@ -12,7 +12,7 @@ has a ground truth, prints the ATE RMSE.
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
-                            [--surfel-mesh-distance] [--surface-report FILE.json]
+                            [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -51,6 +51,9 @@ completeness from the ground truth's vertices to the mesh, precision / recall / 
 to be subdivided by its owner).  --surface-max-distance M: the search radius, default 0.1; a point with nothing within it fails
 every threshold.  --surface-thresholds: default 0.01,0.02,0.05.  --surfel-mesh-distance: the summary of the distances from the
 surfels' centres to the fused mesh (DirectBA.SurfelMeshDistance), a consistency figure that needs no ground truth.
+--register-surface: the ground truth is in a frame of its own; the mesh's vertices are registered to it first (DirectBA.RegisterPoints
+from the rigid alignment of the trajectories when --trajectory is given, else from the identity, within --surface-max-distance), and
+the transform and the figures before it are printed and reported with the rest.
 --surface-report FILE.json: what was printed, as JSON.  Either option fuses with the --mesh-* options whether or not --mesh is given.
 """
 import argparse
@@ -169,7 +172,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
-        surfel_mesh_distance=False, surface_report=None):
+        surfel_mesh_distance=False, surface_report=None, register_surface=False):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -221,7 +224,13 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         surface = {}
         if ground_truth_surface:
             surface["ground_truth"] = str(ground_truth_surface)
-            surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), surface_max_distance, tuple(surface_thresholds)))
+            start = None
+            if register_surface and trajectory:       # the rigid alignment of the trajectories (estimate -> ground truth) is the start
+                aligned = ate.ate_files(os.path.join(str(dataset_dir), trajectory), out)
+                start = np.eye(4)
+                start[:3, :3], start[:3, 3] = aligned["R"], aligned["t"]
+            surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), surface_max_distance, tuple(surface_thresholds),
+                                                 register=bool(register_surface), initial=start))
         if surfel_mesh_distance:
             surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
         if surface:
@@ -271,6 +280,7 @@ def arg_parser():
     ap.add_argument("--surface-thresholds", type=lambda text: tuple(float(v) for v in text.split(",")), default=(0.01, 0.02, 0.05))
     ap.add_argument("--surfel-mesh-distance", action="store_true")
     ap.add_argument("--surface-report", default=None)
+    ap.add_argument("--register-surface", action="store_true")
     return ap
 
 
@@ -283,7 +293,7 @@ def main():
             mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
-            surface_report=a.surface_report)
+            surface_report=a.surface_report, register_surface=a.register_surface)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -303,6 +313,13 @@ def main():
         print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
     if "surface" in r:
         sf = r["surface"]
+        if "registration" in sf:
+            reg = sf["registration"]
+            print(f"registration to the ground truth: {reg['reason']} after {reg['iterations']} steps; ground_truth_T_mesh =")
+            for row in reg["target_T_source"][:3]:
+                print("  " + " ".join(f"{v: .9f}" for v in row))
+            print(surface_eval.format_summary("accuracy before registration", reg["before"]["accuracy"]))
+            print(surface_eval.format_summary("completeness before registration", reg["before"]["completeness"]))
         if "accuracy" in sf:
             print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, within {sf['max_distance']:g} m)", sf["accuracy"]))
             print(surface_eval.format_summary("completeness (ground truth -> mesh)", sf["completeness"]))

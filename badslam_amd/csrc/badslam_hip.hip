@@ -23,6 +23,7 @@
 #include "mesh_kernels.hpp"
 #include "distance_kernels.hpp"
 #include "registration_kernels.hpp"
+#include "sampling_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1406,6 +1407,7 @@ int bslam_debug_pose_residuals(
 #include "fusion_abi.inc"
 #include "mesh_abi.inc"
 #include "distance_abi.inc"
+#include "sampling_abi.inc"
 #include "registration_abi.inc"
 #include "raycast_abi.inc"
 #include "place_abi.inc"

@@ -172,6 +172,7 @@ struct bslam_context {
     uint32_t cells = 0, valid = 0, triangles = 0;
     void *records = nullptr, *cell_count = nullptr, *cell_start = nullptr, *list = nullptr;
   } prepared;
+  bslam::Slab sampling;      // bslam_sample_mesh: words | counts u32[T] | offsets u32[T] | scan sums; reserved by its first call
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

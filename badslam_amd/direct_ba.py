@@ -88,6 +88,8 @@ def host_lib():
                                           f32p, u64p]
     L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
     L.bsh_distance_copy.argtypes = [f32p, u32p]
+    L.bsh_sample_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_uint32, u64p]
+    L.bsh_samples_copy.argtypes = [f32p, f32p, u32p]
     f64p = C.POINTER(C.c_double)
     L.bsh_register_points.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, f64p, f64p, f64p, C.POINTER(C.c_int32), f64p]
     L.bsh_registration_history.argtypes = [f64p]
@@ -769,6 +771,26 @@ class DirectBA:
         distance, triangle = np.zeros(count.value, np.float32), np.zeros(count.value, np.uint32)
         self._check(self.L.bsh_distance_copy(_f(distance), _u32(triangle)))
         return self._distance_result(distance, triangle, cell, grid)
+
+    # --- surface sampling (bslam_sample_mesh)
+    def SampleMesh(self, mesh, density=None, spacing=None, seed=0):
+        """Points drawn uniformly by area from `mesh` (the dict of ExtractMesh or LoadPLY): dict of positions (N, 3) f32, normals
+        (N, 3) f32 (the triangle's) and triangle (N,) u32, ordered by triangle.  density: samples per square unit; each triangle gets
+        area * density samples on average, however small it is.  spacing: shorthand for density = 1 / spacing^2.  Exactly one of
+        the two has to be given.  The samples are a function of (seed, triangle, ordinal) alone: two calls give identical bits.
+        Degenerate triangles and a mesh without triangles (a point cloud) yield nothing."""
+        if (density is None) == (spacing is None):
+            raise ValueError("SampleMesh: give exactly one of density and spacing")
+        if density is None:
+            density = 1.0 / (float(spacing) * float(spacing))
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        count = C.c_uint64()
+        self._check(self.L.bsh_sample_mesh(self._ba, self.stream, len(pos), _f(pos), len(tri), _u32(tri), float(density), int(seed) & 0xFFFFFFFF, C.byref(count)))
+        out = dict(positions=np.zeros((count.value, 3), np.float32), normals=np.zeros((count.value, 3), np.float32), triangle=np.zeros(count.value, np.uint32))
+        self._check(self.L.bsh_samples_copy(_f(out["positions"]), _f(out["normals"]), _u32(out["triangle"])))
+        return out
 
     # --- surface registration (bslam_registration_prepare / bslam_registration_step)
     REGISTRATION_PLANE, REGISTRATION_POINT = 0, 1

@@ -314,6 +314,28 @@ int bsh_distance_copy(float* distance, uint32_t* triangle) {
     g_distance = DirectBA::PointMeshResult();
   });
 }
+// DirectBA::SampleMesh of host arrays in two steps, like the mesh: bsh_sample_mesh keeps the samples for this thread and reports
+// *count; bsh_samples_copy copies them out (positions, normals: 3 floats per sample; triangle: 1 per sample) and drops them.
+static thread_local DirectBA::MeshSamples g_samples;
+int bsh_sample_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, uint64_t triangles, const uint32_t* indices, float density, uint32_t seed,
+                    uint64_t* count) {
+  BSH_TRY({
+    g_samples = DirectBA::MeshSamples();
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    static_cast<DirectBA*>(ba)->SampleMesh(static_cast<hipStream_t>(stream), mesh, density, seed, &g_samples);
+    *count = g_samples.count();
+  });
+}
+int bsh_samples_copy(float* positions, float* normals, uint32_t* triangle) {
+  BSH_TRY({
+    copy_out(positions, g_samples.positions);
+    copy_out(normals, g_samples.normals);
+    copy_out(triangle, g_samples.triangles);
+    g_samples = DirectBA::MeshSamples();
+  });
+}
 // DirectBA::RegisterPoints of host arrays, in two steps like the mesh.  options8 = {max_distance, min_distance (0: max / 8), mode
 // (-1: by the mesh), huber (0: half the stage's radius), shrink, iterations_per_stage, cell_size (0: doubling), max_grid_entries};
 // initial16 and transform16 are row-major 4 x 4; status3 = {steps, converged, DirectBA::RegistrationEnd}; grid3 = {cell used, cells,

@@ -664,6 +664,50 @@ void DirectBA::SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& op
                             mesh_indices_ ? mesh_indices_->address() : nullptr, options, result);
 }
 
+DirectBA::DeviceSamples DirectBA::SampleMeshOnDevice(hipStream_t stream, u32 vertices, const float* positions, u32 triangles, const u32* indices, float density,
+                                                     u32 seed) {
+  DeviceSamples s;
+  Check(bslam_sample_mesh(ctx_, stream, vertices, positions, triangles, indices, density, seed, 0, nullptr, nullptr, nullptr, &s.count), "bslam_sample_mesh");
+  const size_t n = static_cast<size_t>(s.count);
+  s.positions.reset(new DeviceArray<float>(3 * n));
+  s.normals.reset(new DeviceArray<float>(3 * n));
+  s.triangles.reset(new DeviceArray<u32>(n));
+  if (n == 0) return s;
+  uint64_t again = 0;
+  Check(bslam_sample_mesh(ctx_, stream, vertices, positions, triangles, indices, density, seed, s.count, s.positions->address(), s.normals->address(),
+                          s.triangles->address(), &again),
+        "bslam_sample_mesh");
+  if (again != s.count) throw std::runtime_error("SampleMesh: the mesh changed between the two sampling calls");
+  return s;
+}
+
+DirectBA::DeviceSamples DirectBA::SampleMeshOnDevice(hipStream_t stream, float density, u32 seed) {
+  if (!mesh_extracted_) throw std::logic_error("SampleMeshOnDevice: no extracted mesh (call ExtractMesh first)");
+  return SampleMeshOnDevice(stream, mesh_vertices_, mesh_positions_ ? mesh_positions_->address() : nullptr, mesh_triangles_,
+                            mesh_indices_ ? mesh_indices_->address() : nullptr, density, seed);
+}
+
+void DirectBA::SampleMesh(hipStream_t stream, const Mesh& mesh, float density, u32 seed, MeshSamples* samples) {
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
+      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull)
+    throw std::invalid_argument("SampleMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  DeviceArray<float> dev_positions(mesh.positions.size());
+  DeviceArray<u32> dev_indices(mesh.indices.size());
+  dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
+  dev_indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
+  Wait(stream);   // the host arrays are the caller's and pageable
+  const DeviceSamples s = SampleMeshOnDevice(stream, static_cast<u32>(mesh.vertex_count()), dev_positions.address(), static_cast<u32>(mesh.triangle_count()),
+                                             dev_indices.address(), density, seed);
+  const size_t n = static_cast<size_t>(s.count);
+  samples->positions.resize(3 * n);
+  samples->normals.resize(3 * n);
+  samples->triangles.resize(n);
+  s.positions->Download(stream, samples->positions.data(), 3 * n);
+  s.normals->Download(stream, samples->normals.data(), 3 * n);
+  s.triangles->Download(stream, samples->triangles.data(), n);
+  Wait(stream);
+}
+
 const char* DirectBA::RegistrationReason(int end) {
   switch (end) {
     case kRegistrationConverged: return "converged";

@@ -318,6 +318,25 @@ class DirectBA {
   // returned, which stays on the device for this: how far the surfels that bundle adjustment optimised lie from the surface the
   // volume produced -- a consistency figure that needs no ground truth.  Throws std::logic_error if no mesh was extracted.
   void SurfelMeshDistance(hipStream_t stream, const PointMeshOptions& options, PointMeshResult* result);
+  // Surface sampling (bslam_sample_mesh): points drawn uniformly by area, `density` per square unit on average, a function of
+  // (seed, triangle, ordinal within the triangle) alone; ordered by triangle.  Degenerate triangles -- a point cloud -- yield nothing.
+  struct MeshSamples {
+    std::vector<float> positions, normals;   // 3 per sample; the normal is the triangle's, cross(b - a, c - a) normalised
+    std::vector<u32> triangles;              // 1 per sample
+    size_t count() const { return triangles.size(); }
+  };
+  struct DeviceSamples {   // the same on the device
+    std::unique_ptr<DeviceArray<float>> positions, normals;
+    std::unique_ptr<DeviceArray<u32>> triangles;
+    uint64_t count = 0;
+  };
+  // Host arrays: the count call, the allocation, the emit call and one download.
+  void SampleMesh(hipStream_t stream, const Mesh& mesh, float density, u32 seed, MeshSamples* samples);
+  // The same on device arrays (4 byte aligned; see bslam_sample_mesh); the samples stay on the device, where
+  // PointMeshDistanceOnDevice takes them as its points.
+  DeviceSamples SampleMeshOnDevice(hipStream_t stream, u32 vertices, const float* positions, u32 triangles, const u32* indices, float density, u32 seed);
+  // ... of the mesh the last ExtractMesh returned, which is still on the device.  Throws std::logic_error if no mesh was extracted.
+  DeviceSamples SampleMeshOnDevice(hipStream_t stream, float density, u32 seed);
   // Surface registration (bslam_registration_prepare / bslam_registration_step): the rigid motion target_T_source that lays the
   // points onto the mesh, by iterative closest point from `initial`.  The points are uploaded and the mesh is prepared once, at
   // max_distance (with the cell doubling of PointMeshDistance while over budget); stages run at the radii max_distance, shrink *

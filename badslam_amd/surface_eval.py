@@ -10,10 +10,14 @@ with, per threshold d, precision = the share of the reconstruction's vertices wi
 of the ground truth's vertices within d of the reconstruction, and F-score = 2 P R / (P + R).  A point without a hit inside the
 search radius fails every threshold.
 
-Completeness is sampled at the ground truth's VERTICES.  A coarsely tessellated ground truth (a wall of two triangles) says
-nothing about the surface between its corners: its owner has to subdivide it to the resolution the thresholds ask for.  No
-surface sampler is part of this.  The ground truth has to be given in the frame of the reconstruction, or evaluate(register=True)
-has to bring the reconstruction into the ground truth's frame first (DirectBA.RegisterPoints, an iterative closest point that
+By default both point sets are the meshes' VERTICES, and then the figures depend on how the meshes happen to be tessellated: a
+wall of two triangles says nothing about the surface between its corners, and a scan meshed at 1 mm outweighs a plane next to it
+by orders of magnitude.  evaluate(sample_density=...) measures at points drawn uniformly by area instead, as the published surface
+benchmarks do (DirectBA.SampleMesh, bslam_sample_mesh on the GPU): accuracy from samples of the reconstruction, completeness from
+samples of the ground truth, `sample_density` per square unit on each, the meshes themselves staying the targets.  A side
+without triangles (a point cloud) cannot be sampled and keeps its vertices.
+
+The ground truth has to be given in the frame of the reconstruction, or evaluate(register=True) has to bring the reconstruction into the ground truth's frame first (DirectBA.RegisterPoints, an iterative closest point that
 needs a start within its search radius, for example the transform ate.align_rigid finds for the trajectory).  A ground truth without triangles is a point cloud (the form the
 ETH3D SLAM scans come in): every point then is its own degenerate triangle.
 
@@ -56,32 +60,55 @@ def f_scores(accuracy, completeness):
     return out
 
 
-def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.01, 0.02, 0.05), cell_size=None, register=False, initial=None):
+def _has_triangles(mesh):
+    triangles = mesh.get("triangles")
+    return triangles is not None and len(triangles) > 0
+
+
+def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.01, 0.02, 0.05), cell_size=None, register=False, initial=None,
+             sample_density=None, sample_seed=0):
     """reconstruction, ground_truth: mesh dicts (positions (V, 3), triangles (T, 3); DirectBA.ExtractMesh, LoadPLY) in one frame; the
     ground truth may be a point cloud (no or empty triangles).  -> dict of accuracy and completeness (distance_summary each),
-    f_scores (a list per threshold), max_distance and the grids the two calls used.  Completeness is sampled at the ground truth's
-    vertices: see the module's docstring.
+    f_scores (a list per threshold), max_distance and the grids the two calls used.  Both are measured at the vertices unless
+    sample_density is given: see the module's docstring.
+    sample_density: each side that has triangles is replaced as a query point set by DirectBA.SampleMesh(side, density=sample_density,
+    seed=sample_seed); the result then also has `sampling`: density, seed, reconstruction_samples and ground_truth_samples (the
+    numbers of samples; None for a side without triangles, which keeps its vertices).
     register: the ground truth is in another frame.  The reconstruction's vertices are registered to it first
     (DirectBA.RegisterPoints at max_distance from `initial`, a 4 x 4 ground_truth_T_reconstruction, default identity), the motion found
     is applied to a copy of the reconstruction's positions (in float64, then rounded to float32), and that copy is evaluated.  The
     result then also has `registration`: target_T_source (4 x 4 as nested lists), iterations, converged, reason, history, and
-    `before`, the accuracy and completeness summaries under `initial` alone."""
+    `before`, the accuracy and completeness summaries under `initial` alone.  The registration itself runs on the reconstruction's
+    vertices; the sampling arguments apply to the evaluations before and after it."""
+    sampled = {} if sample_density is None else dict(sample_density=sample_density, sample_seed=sample_seed)
     if register:
         start = np.eye(4) if initial is None else np.asarray(initial, np.float64).reshape(4, 4)
-        before = evaluate(ba, dict(reconstruction, positions=transform_positions(reconstruction["positions"], start)), ground_truth, max_distance, thresholds, cell_size)
+        before = evaluate(ba, dict(reconstruction, positions=transform_positions(reconstruction["positions"], start)), ground_truth, max_distance, thresholds, cell_size,
+                          **sampled)
         found = ba.RegisterPoints(reconstruction["positions"], ground_truth, max_distance, initial=start, cell_size=cell_size)
         moved = dict(reconstruction, positions=transform_positions(reconstruction["positions"], found["target_T_source"]))
-        result = evaluate(ba, moved, ground_truth, max_distance, thresholds, cell_size)
+        result = evaluate(ba, moved, ground_truth, max_distance, thresholds, cell_size, **sampled)
         result["registration"] = dict(target_T_source=np.asarray(found["target_T_source"], np.float64).tolist(), iterations=found["iterations"],
                                       converged=found["converged"], reason=found["reason"], history=found["history"],
                                       before=dict(accuracy=before["accuracy"], completeness=before["completeness"]))
         return result
-    acc = ba.PointMeshDistance(reconstruction["positions"], ground_truth, max_distance, cell_size)
-    com = ba.PointMeshDistance(ground_truth["positions"], reconstruction, max_distance, cell_size)
+    queries, counts = [], []
+    for side in (reconstruction, ground_truth):
+        if sample_density is not None and _has_triangles(side):
+            queries.append(ba.SampleMesh(side, density=sample_density, seed=sample_seed)["positions"])
+            counts.append(int(len(queries[-1])))
+        else:
+            queries.append(side["positions"])
+            counts.append(None)
+    acc = ba.PointMeshDistance(queries[0], ground_truth, max_distance, cell_size)
+    com = ba.PointMeshDistance(queries[1], reconstruction, max_distance, cell_size)
     accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
     grid = lambda r: dict(cell_size=r["cell_size"], grid_cells=r["grid_cells"], grid_entries=r["grid_entries"])
-    return dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
-                accuracy_grid=grid(acc), completeness_grid=grid(com))
+    result = dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
+                  accuracy_grid=grid(acc), completeness_grid=grid(com))
+    if sample_density is not None:
+        result["sampling"] = dict(density=float(sample_density), seed=int(sample_seed), reconstruction_samples=counts[0], ground_truth_samples=counts[1])
+    return result
 
 
 def transform_positions(positions, T):

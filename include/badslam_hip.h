@@ -740,6 +740,44 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream, uint32_t point_c
                               float cell_size, uint64_t max_grid_entries, float* out_distance, uint32_t* out_triangle,
                               uint64_t* grid_cells, uint64_t* grid_entries);
 
+/* Surface sampling: points drawn uniformly by area from an indexed mesh, so that what is measured at them does not depend on how
+ * the mesh happens to be tessellated (DESIGN.md 8 "Surface sampling", csrc/sampling_kernels.hpp).  Integers are uint32 with
+ * wrap-around; floats are fp32, nothing is contracted implicitly, and dot, cross, `/` and sqrtf are those of "Surface evaluation"
+ * above.  Triangle t with vertices a, b, c = positions[indices[3 t + 0 .. 2]], `density` in samples per square unit, `seed`.
+ * Hash:
+ *   mix(x):  x ^= x >> 16;  x *= 0x7feb352d;  x ^= x >> 15;  x *= 0x846ca68b;  x ^= x >> 16.
+ *   h(s, t, j) = mix(mix((seed + s * 0x9e3779b9) ^ mix(t)) + j);  u24(h) = h >> 8.  s selects a stream: 0 rounds the count, 1 and 2
+ *   are the two coordinates of a sample.  (h(0, 0, 0) is 0 at seed 0: there triangle 0 rounds its count up.)
+ * Count:
+ *   u = b - a, v = c - a, n = cross(u, v), nn = dot(n, n).  If one of the nine coordinates is not finite, or !(nn > 0), the count
+ *   is 0: degenerate triangles, and so a whole point cloud, yield nothing.  Otherwise area = 0.5f * sqrtf(nn), x = area * density,
+ *   k = floorf(x) and count = k + (float(u24(h(0, t, 0))) * 2^-24 < x - k ? 1 : 0); an x that is not finite or is >= 2^32 counts
+ *   as 2^32.  The expected count is area * density for every triangle, however small.
+ * Order:
+ *   sample i = offset(t) + j for 0 <= j < count(t), offset the exclusive prefix sum of the counts: the samples are ordered by
+ *   (triangle, j).  N is the 64-bit total.
+ * Sample (t, j):
+ *   i1 = u24(h(1, t, j)), i2 = u24(h(2, t, j));  if i1 + i2 > 2^24 then i1 = 2^24 - i1 and i2 = 2^24 - i2 (the reflection of the
+ *   unit square's upper half onto the lower, exact in integers and uniform on the triangle);  w1 = float(i1) * 2^-24, w2 alike,
+ *   both exact;  p.k = fmaf(w2, v.k, fmaf(w1, u.k, a.k));  normal.k = n.k / sqrtf(nn);  triangle = t.
+ *   A sample depends on (seed, t, j) and its triangle alone: two calls give identical bits, and duplicated triangles get
+ *   different samples.
+ * bslam_sample_mesh: positions float[3 V], indices uint32[3 T], out_points float[3 N], out_normals float[3 N] (may be null) and
+ * out_triangles uint32[N] (may be null) are device arrays with room for `capacity` samples; *sample_count (host) receives N
+ * whenever the arguments have passed and no index was bad.  When out_points is null or N > capacity, only the count is returned
+ * and nothing is written: call once for the count and once with buffers, as with bslam_extract_mesh.  Nothing is written at or
+ * beyond N.  Refused without a launch: a null context or sample_count, positions or indices null where not empty, a density
+ * that is not finite and > 0, more than 2^32 - 256 triangles, misaligned (4 byte) pointers, outputs that overlap anything.
+ * Refused behind the count pass, outputs untouched: an index >= V (never dereferenced; BSLAM_ERR_INVALID_ARGUMENT), and
+ * N > 2^32 - 256 (BSLAM_ERR_INVALID_ARGUMENT, bslam_last_error names N: use a lower density; *sample_count holds N).  T == 0 and
+ * V == 0 are legal: N = 0.  Three passes: the counts with the index check and their 64-bit total (one read-back), the scan over
+ * the counts, and the samples, one per lane, each finding its triangle by a search over the scanned counts that is bounded by
+ * ceil(log2(T + 1)) steps.  Scratch lives in a context slab of its own that the first call reserves.  Synchronises `stream`.
+ * Every rank of a surfel-sharded run holds the same mesh and computes the same samples; nothing is exchanged. */
+int bslam_sample_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, const float* positions, uint32_t triangle_count,
+                      const uint32_t* indices, float density, uint32_t seed, uint64_t capacity, float* out_points, float* out_normals,
+                      uint32_t* out_triangles, uint64_t* sample_count);
+
 /* Surface registration: one step of an iterative closest point alignment of N points to a mesh -- the correspondences of the
  * transformed points and their normal equations (DESIGN.md 8 "Surface registration", csrc/registration_kernels.hpp).  The
  * arithmetic is fp32, nothing is contracted implicitly, and dot, cross, `/`, sqrtf, seg, face and the pair are those of "Surface

@@ -12,7 +12,7 @@ has a ground truth, prints the ATE RMSE.
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
-                            [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface]
+                            [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -47,13 +47,16 @@ A volume of more than 2^30 samples is refused: choose a larger voxel size.  --po
 
 --ground-truth-surface FILE.ply: the fused mesh (after --mesh-min-component) is evaluated against a ground-truth mesh or point
 cloud given in the frame of the run (badslam_amd/surface_eval.py: accuracy from the mesh's vertices to the ground truth,
-completeness from the ground truth's vertices to the mesh, precision / recall / F-score per threshold; a coarse ground truth has
-to be subdivided by its owner).  --surface-max-distance M: the search radius, default 0.1; a point with nothing within it fails
+completeness from the ground truth's vertices to the mesh, precision / recall / F-score per threshold; for a coarse ground truth
+see --surface-sample-spacing).  --surface-max-distance M: the search radius, default 0.1; a point with nothing within it fails
 every threshold.  --surface-thresholds: default 0.01,0.02,0.05.  --surfel-mesh-distance: the summary of the distances from the
 surfels' centres to the fused mesh (DirectBA.SurfelMeshDistance), a consistency figure that needs no ground truth.
 --register-surface: the ground truth is in a frame of its own; the mesh's vertices are registered to it first (DirectBA.RegisterPoints
 from the rigid alignment of the trajectories when --trajectory is given, else from the identity, within --surface-max-distance), and
 the transform and the figures before it are printed and reported with the rest.
+--surface-sample-spacing S: both figures are measured at points drawn uniformly by area, one per S x S metres on average, from each
+side that has triangles (DirectBA.SampleMesh; surface_eval.evaluate(sample_density=1 / S^2)) instead of at the vertices, so that they
+no longer depend on how either mesh is tessellated; the numbers of samples are printed and reported.
 --surface-report FILE.json: what was printed, as JSON.  Either option fuses with the --mesh-* options whether or not --mesh is given.
 """
 import argparse
@@ -172,7 +175,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
-        surfel_mesh_distance=False, surface_report=None, register_surface=False):
+        surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -230,7 +233,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
                 start = np.eye(4)
                 start[:3, :3], start[:3, 3] = aligned["R"], aligned["t"]
             surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), surface_max_distance, tuple(surface_thresholds),
-                                                 register=bool(register_surface), initial=start))
+                                                 register=bool(register_surface), initial=start,
+                                                 sample_density=None if surface_sample_spacing is None else 1.0 / (float(surface_sample_spacing) ** 2)))
         if surfel_mesh_distance:
             surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
         if surface:
@@ -281,6 +285,7 @@ def arg_parser():
     ap.add_argument("--surfel-mesh-distance", action="store_true")
     ap.add_argument("--surface-report", default=None)
     ap.add_argument("--register-surface", action="store_true")
+    ap.add_argument("--surface-sample-spacing", type=float, default=None)
     return ap
 
 
@@ -293,7 +298,7 @@ def main():
             mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
-            surface_report=a.surface_report, register_surface=a.register_surface)
+            surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -320,6 +325,10 @@ def main():
                 print("  " + " ".join(f"{v: .9f}" for v in row))
             print(surface_eval.format_summary("accuracy before registration", reg["before"]["accuracy"]))
             print(surface_eval.format_summary("completeness before registration", reg["before"]["completeness"]))
+        if "sampling" in sf:
+            sm = sf["sampling"]
+            at = lambda n: "its vertices" if n is None else f"{n} samples"
+            print(f"measured at {sm['density']:g} samples per square metre: the mesh at {at(sm['reconstruction_samples'])}, the ground truth at {at(sm['ground_truth_samples'])}")
         if "accuracy" in sf:
             print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, within {sf['max_distance']:g} m)", sf["accuracy"]))
             print(surface_eval.format_summary("completeness (ground truth -> mesh)", sf["completeness"]))

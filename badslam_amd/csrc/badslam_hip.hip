@@ -81,6 +81,16 @@ static CamConsts make_cam_consts(const bslam_context* ctx, const bslam_camera4f*
   return c;
 }
 
+// The constants of a call that calibrates no depth: no depth parameters but the baseline, a cell size of 1 and no cfactor
+// image.  color may be null.
+static CamConsts depth_only_consts(const bslam_context* ctx, const bslam_camera4f* color, const bslam_camera4f* depth, float baseline_fx) {
+  bslam_depth_params dp;
+  std::memset(&dp, 0, sizeof(dp));
+  dp.sparse_surfel_cell_size = 1;
+  dp.baseline_fx = baseline_fx;
+  return make_cam_consts(ctx, color, depth, &dp);
+}
+
 // surfels_size against the width of the surfel buffer and, when given, of the active-surfel buffer.
 static int check_surfels_size(const bslam_buffer2d* surfels, uint32_t surfels_size, const bslam_buffer2d* active = nullptr) {
   if (surfels_size > (uint32_t)surfels->width) return fail(BSLAM_ERR_INVALID_ARGUMENT, "surfels_size %u exceeds the buffer width %d", surfels_size, surfels->width);
@@ -167,6 +177,46 @@ static int read_back(bslam_context* ctx, hipStream_t stream, const T* dev, size_
   BSLAM_HIP_TRY(hipMemcpyAsync(ctx->staging2.ptr, dev, count * sizeof(T), hipMemcpyDeviceToHost, stream));
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));
   *host = (const T*)ctx->staging2.ptr;
+  return BSLAM_OK;
+}
+
+// ---- image arguments and scratch of the entry points (every *_abi.inc below uses them) ----------------------------
+static int make_img(const bslam_buffer2d* b, size_t elem, const char* name, Img* out) {
+  if (!b || !b->address) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s buffer is null", name);
+  if (b->width <= 0 || b->height <= 0 || b->pitch < (size_t)b->width * elem) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s buffer has a bad shape / pitch", name);
+  out->base = (uint8_t*)b->address; out->pitch = (uint32_t)b->pitch; out->width = b->width; out->height = b->height;
+  return BSLAM_OK;
+}
+static bool same_shape(const Img& a, const Img& b) { return a.width == b.width && a.height == b.height; }
+static dim3 image_grid(const Img& i) { return dim3((unsigned)((i.width + 255) / 256), (unsigned)i.height); }
+static dim3 flat_grid(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
+// do the byte ranges [base, base + height * pitch) of two images share a byte?
+static bool overlap(const Img& a, const Img& b) {
+  const uintptr_t a0 = (uintptr_t)a.base, a1 = a0 + (size_t)a.height * a.pitch, b0 = (uintptr_t)b.base, b1 = b0 + (size_t)b.height * b.pitch;
+  return a0 < b1 && b0 < a1;
+}
+static bool rows_aligned(const Img& i, size_t bytes) { return ((uintptr_t)i.base | (uintptr_t)i.pitch) % bytes == 0; }
+
+// Bump carver over a slab: take<T>(count, alignment in bytes) hands out the next piece.  Without a base it only counts.
+struct Carver {
+  uint8_t* base;
+  size_t used;
+  template <class T> T* take(size_t count, size_t align = alignof(T)) {
+    used = (used + align - 1) / align * align;
+    T* piece = base ? (T*)(base + used) : nullptr;
+    used += count * sizeof(T);
+    return piece;
+  }
+};
+// Runs `layout` once to count the bytes, reserves them and runs it again over the slab, so the total and the pointers come from
+// the same statements.  The slab's base is aligned for every piece (hipMalloc: 256 bytes).
+template <class Layout>
+static int carve(Slab& slab, Layout layout) {
+  Carver count{nullptr, 0};
+  layout(count);
+  if (int rc = slab.reserve(count.used)) return rc;
+  Carver pieces{(uint8_t*)slab.ptr, 0};
+  layout(pieces);
   return BSLAM_OK;
 }
 
@@ -973,18 +1023,16 @@ int bslam_debug_quad_samples(bslam_context* ctx, void* stream_, int image_count,
   BSLAM_HIP_TRY(hipMemcpyAsync(base + o_kfs, kfs.data(), image_count * sizeof(KfDev), hipMemcpyHostToDevice, stream));
   if (count > 0) BSLAM_HIP_TRY(hipMemcpyAsync(base + o_pos, positions, (size_t)count * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));   // `kfs` is a local vector
-  // the table through the kernel that builds it in production: keyframe colour (build_quads_kernel), one u8 image
-  // (build_quads_u8_kernel), several u8 images (build_quads_u8_batched_kernel)
+  // the table through the kernel that builds it in production: keyframe colour (build_quads_kernel), u8 images
+  // (build_quads_u8_batched_kernel)
   const dim3 grid((unsigned)((width + 1 + 255) / 256), (unsigned)(height + 1), (unsigned)image_count);
   if (channels == 4) {
     hipLaunchKernelGGL(build_quads_kernel, grid, dim3(256), 0, stream, c, (const KfDev*)(base + o_kfs), table);
-  } else if (image_count == 1) {
-    hipLaunchKernelGGL(build_quads_u8_kernel, grid, dim3(256), 0, stream, Img{base, (uint32_t)pitch, width, height}, table);
   } else {
     PairBatch batch;
     std::memset((void*)&batch, 0, sizeof(batch));
     for (int k = 0; k < image_count; ++k) batch.im[k].frame_color = Img{base + k * image_bytes, (uint32_t)pitch, width, height};
-    hipLaunchKernelGGL(build_quads_u8_batched_kernel, grid, dim3(256), 0, stream, batch, table, quads_per_image);
+    hipLaunchKernelGGL(build_quads_u8_batched_kernel, grid, dim3(256), 0, stream, table, quads_per_image, batch);
   }
   BSLAM_HIP_TRY(hipGetLastError());
   if (count > 0) {

@@ -1,5 +1,5 @@
 // distance_abi.inc -- bslam_point_mesh_distance of include/badslam_hip.h (included by badslam_hip.hip after mesh_abi.inc:
-// check_mesh_spans, mesh_error, device_scan, flat_grid, read_back), and the pieces of its launch sequence that
+// check_mesh_spans, mesh_error, device_scan), and the pieces of its launch sequence that
 // registration_abi.inc runs too: the triangle side once per prepared mesh, the point side once per step.
 
 namespace bslam {

@@ -1,5 +1,5 @@
 // fusion_abi.inc -- volumetric fusion and mesh extraction entry points of include/badslam_hip.h (included by badslam_hip.hip
-// after lifecycle_abi.inc and rectify_abi.inc, whose scan and argument helpers it uses).
+// after lifecycle_abi.inc, whose device_scan it uses).
 
 namespace bslam {
 

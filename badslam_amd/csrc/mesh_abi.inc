@@ -1,5 +1,5 @@
-// mesh_abi.inc -- mesh component entry points of include/badslam_hip.h (included by badslam_hip.hip after lifecycle_abi.inc,
-// preprocess_abi.inc and fusion_abi.inc: device_scan, flat_grid, the fusion slab).
+// mesh_abi.inc -- mesh component entry points of include/badslam_hip.h (included by badslam_hip.hip after lifecycle_abi.inc
+// and fusion_abi.inc: device_scan, the fusion slab).
 
 namespace bslam {
 

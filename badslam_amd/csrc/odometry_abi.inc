@@ -4,79 +4,102 @@ namespace bslam {
 
 static int pair_images(const bslam_buffer2d* frame_depth, const bslam_buffer2d* frame_normals, const bslam_buffer2d* frame_color,
                        const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color,
-                       const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, PairImages* im, Img* frame_color_img) {
+                       const bslam_camera4f* depth_camera, const bslam_camera4f* color_camera, PairImages* im) {
   int rc;
   if ((rc = make_img(frame_depth, 4, "frame depth", &im->frame_depth))) return rc;
   if ((rc = make_img(frame_normals, 2, "frame normals", &im->frame_normals))) return rc;
-  if ((rc = make_img(frame_color, 1, "frame color", frame_color_img))) return rc;
+  if ((rc = make_img(frame_color, 1, "frame color", &im->frame_color))) return rc;
   if ((rc = make_img(surfel_depth, 4, "surfel depth", &im->surfel_depth))) return rc;
   if ((rc = make_img(surfel_normals, 2, "surfel normals", &im->surfel_normals))) return rc;
   if ((rc = make_img(surfel_color, 1, "surfel color", &im->surfel_color))) return rc;
   if (im->frame_depth.width != depth_camera->width || im->frame_depth.height != depth_camera->height || !same_shape(im->frame_depth, im->frame_normals) ||
       !same_shape(im->frame_depth, im->surfel_depth) || !same_shape(im->frame_depth, im->surfel_normals) || !same_shape(im->frame_depth, im->surfel_color))
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth-sized images do not match the (scaled) depth camera %dx%d", depth_camera->width, depth_camera->height);
-  if (frame_color_img->width != color_camera->width || frame_color_img->height != color_camera->height)
+  if (im->frame_color.width != color_camera->width || im->frame_color.height != color_camera->height)
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "frame colour image does not match the (scaled) colour camera %dx%d", color_camera->width, color_camera->height);
   return BSLAM_OK;
 }
 
-// Shared driver of the two image-pair kernels: returns the reduced row (kRow floats) on the host.
-static int run_pair_kernel(bslam_context* ctx, hipStream_t stream, bool coeffs, bool gradmag, int use_depth, int use_desc, const bslam_camera4f* color_camera,
-                           const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor, const bslam_buffer2d* frame_depth,
-                           const bslam_buffer2d* frame_normals, const bslam_buffer2d* frame_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
-                           const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, float* row_out) {
-  if (!ctx || !color_camera || !depth_camera || !estimate_frame_T_surfel_frame) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+// The residual sets of one output kind: depth and descriptor, depth alone, descriptor alone (kGradMag only changes the descriptor).
+template <bool kCoeffs, bool kGradMag>
+static void launch_pairs(bool use_depth, bool use_desc, dim3 grid, hipStream_t stream, const CamConsts& c, float threshold_factor, float* partials, const PairBatch& batch) {
+  if (use_depth && use_desc) hipLaunchKernelGGL((pair_accumulate_kernel<true, true, kCoeffs, kGradMag>), grid, dim3(256), 0, stream, c, threshold_factor, partials, batch);
+  else if (use_depth) hipLaunchKernelGGL((pair_accumulate_kernel<true, false, kCoeffs, false>), grid, dim3(256), 0, stream, c, threshold_factor, partials, batch);
+  else hipLaunchKernelGGL((pair_accumulate_kernel<false, true, kCoeffs, kGradMag>), grid, dim3(256), 0, stream, c, threshold_factor, partials, batch);
+}
+
+// The driver of every image-pair entry point, which has checked its own pointers and pair_count (1 ... kMaxPairBatch): pair p
+// tracks tracked_*[p] with transforms[p] against the base images.  Returns the pair_count reduced rows (kRow floats each) in
+// *rows_out, on the host and valid until the next call on the context.  coeffs: H, b and the visible count, else cost and residual
+// count; gradmag: the one colour residual on gradient-magnitude images in place of the two descriptor residuals.
+static int run_pairs(bslam_context* ctx, hipStream_t stream, bool coeffs, bool gradmag, int use_depth, int use_desc, const bslam_camera4f* color_camera,
+                     const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor, int pair_count, const bslam_buffer2d* tracked_depth,
+                     const bslam_buffer2d* tracked_normals, const bslam_buffer2d* tracked_color, const bslam_mat3x4* transforms,
+                     const bslam_buffer2d* base_depth, const bslam_buffer2d* base_normals, const bslam_buffer2d* base_color, const float** rows_out) {
   if (!use_depth && !use_desc) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
-  PairImages im;
-  Img frame_color_img;
-  int rc = pair_images(frame_depth, frame_normals, frame_color, surfel_depth, surfel_normals, surfel_color, depth_camera, color_camera, &im, &frame_color_img);
-  if (rc) return rc;
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  bslam_depth_params dp;
-  std::memset(&dp, 0, sizeof(dp));
-  dp.sparse_surfel_cell_size = 1;
-  dp.baseline_fx = baseline_fx;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, &dp);
-  // tracked-frame colour as luma quads (one 8-byte gather per bilinear sample)
-  if (!quad_table_addressable(frame_color_img.width, frame_color_img.height))
-    return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", frame_color_img.width, frame_color_img.height);
-  const size_t quad_count = (size_t)(frame_color_img.width + 1) * (frame_color_img.height + 1);
-  if ((rc = ctx->quads_aux.reserve(quad_count * sizeof(QuadEntry)))) return rc;
-  hipLaunchKernelGGL(build_quads_u8_kernel, dim3((unsigned)((frame_color_img.width + 1 + 255) / 256), (unsigned)(frame_color_img.height + 1)), dim3(256), 0, stream,
-                     frame_color_img, (QuadEntry*)ctx->quads_aux.ptr);
-  BSLAM_HIP_TRY(hipGetLastError());
-  im.frame_quads = (const QuadEntry*)ctx->quads_aux.ptr;
-  im.frame_color = frame_color_img;
-  const int pixels = im.surfel_depth.width * im.surfel_depth.height;
-  const int blocks = (pixels + 255) / 256;
-  const int rows = blocks * 4;
-  const size_t partial_floats = (size_t)rows * kRow;
-  if ((rc = ctx->partials.reserve((partial_floats + (size_t)kReduceParts * kRow) * sizeof(float)))) return rc;
-  if ((rc = ctx->coeffs.reserve(kRow * sizeof(float)))) return rc;
-  float* partials = (float*)ctx->partials.ptr;
-  M34 T;
-  std::memcpy(T.m, estimate_frame_T_surfel_frame->m, sizeof(float) * 12);
-  const dim3 grid((unsigned)blocks), block(256);
-#define BSLAM_PAIR(D, S, C) hipLaunchKernelGGL((pair_accumulate_kernel<D, S, C>), grid, block, 0, stream, c, T, threshold_factor, im, partials)
-#define BSLAM_PAIR_GM(D, C) hipLaunchKernelGGL((pair_accumulate_kernel<D, true, C, true>), grid, block, 0, stream, c, T, threshold_factor, im, partials)
-  if (gradmag && use_desc) {
-    if (coeffs) { if (use_depth) BSLAM_PAIR_GM(true, true); else BSLAM_PAIR_GM(false, true); }
-    else { if (use_depth) BSLAM_PAIR_GM(true, false); else BSLAM_PAIR_GM(false, false); }
+  PairBatch batch;
+  std::memset(&batch, 0, sizeof(batch));
+  int rc;
+  for (int p = 0; p < pair_count; ++p) {
+    if ((rc = pair_images(&tracked_depth[p], &tracked_normals[p], &tracked_color[p], base_depth, base_normals, base_color, depth_camera, color_camera, &batch.im[p])))
+      return rc;
+    std::memcpy(batch.im[p].frame_T_surfel.m, transforms[p].m, sizeof(float) * 12);
   }
-  else if (coeffs) { if (use_depth && use_desc) BSLAM_PAIR(true, true, true); else if (use_depth) BSLAM_PAIR(true, false, true); else BSLAM_PAIR(false, true, true); }
-  else { if (use_depth && use_desc) BSLAM_PAIR(true, true, false); else if (use_depth) BSLAM_PAIR(true, false, false); else BSLAM_PAIR(false, true, false); }
-#undef BSLAM_PAIR
-#undef BSLAM_PAIR_GM
+  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
+  const CamConsts c = depth_only_consts(ctx, color_camera, depth_camera, baseline_fx);
+  // every pair's tracked colour as luma quads (one 8-byte gather per bilinear sample), one launch: pair_images checked that
+  // all have the colour camera's size
+  const int cw = color_camera->width, ch = color_camera->height;
+  const size_t quad_count = (size_t)(cw + 1) * (ch + 1);
+  if (!quad_table_addressable(cw, ch)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", cw, ch);
+  if ((rc = ctx->quads_aux.reserve((size_t)pair_count * quad_count * sizeof(QuadEntry)))) return rc;
+  for (int p = 0; p < pair_count; ++p) batch.im[p].frame_quads = (const QuadEntry*)ctx->quads_aux.ptr + (size_t)p * quad_count;
+  hipLaunchKernelGGL(build_quads_u8_batched_kernel, dim3((unsigned)((cw + 1 + 255) / 256), (unsigned)(ch + 1), (unsigned)pair_count), dim3(256), 0, stream,
+                     (QuadEntry*)ctx->quads_aux.ptr, quad_count, batch);
+  BSLAM_HIP_TRY(hipGetLastError());
+  const int pixels = depth_camera->width * depth_camera->height;
+  const int blocks = (pixels + 255) / 256;
+  const int rows = blocks * 4;   // per pair: one per wave
+  const size_t partial_floats = (size_t)pair_count * rows * kRow;
+  if ((rc = ctx->partials.reserve((partial_floats + (size_t)pair_count * kReduceParts * kRow) * sizeof(float)))) return rc;
+  if ((rc = ctx->coeffs.reserve((size_t)pair_count * kRow * sizeof(float)))) return rc;
+  float* partials = (float*)ctx->partials.ptr;
+  const dim3 grid((unsigned)blocks, (unsigned)pair_count);
+  if (gradmag && use_desc) {
+    if (coeffs) launch_pairs<true, true>(use_depth, use_desc, grid, stream, c, threshold_factor, partials, batch);
+    else launch_pairs<false, true>(use_depth, use_desc, grid, stream, c, threshold_factor, partials, batch);
+  } else {
+    if (coeffs) launch_pairs<true, false>(use_depth, use_desc, grid, stream, c, threshold_factor, partials, batch);
+    else launch_pairs<false, false>(use_depth, use_desc, grid, stream, c, threshold_factor, partials, batch);
+  }
   BSLAM_HIP_TRY(hipGetLastError());
   float* parts = partials + partial_floats;
-  hipLaunchKernelGGL(pose_reduce_kernel, dim3(1, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, parts);
+  hipLaunchKernelGGL(pose_reduce_kernel, dim3((unsigned)pair_count, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, parts);
   BSLAM_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3(1), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
+  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3((unsigned)pair_count), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
   BSLAM_HIP_TRY(hipGetLastError());
-  const float* h = nullptr;
-  if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, kRow, &h))) return rc;   // results valid on return (BS/kernel_opt_pose.cc:189-191)
-  std::memcpy(row_out, h, kRow * sizeof(float));
-  return BSLAM_OK;
+  return read_back(ctx, stream, (const float*)ctx->coeffs.ptr, (size_t)pair_count * kRow, rows_out);   // results valid on return (BS/kernel_opt_pose.cc:189-191)
+}
+
+// The single-pair entry points: a batch of one.
+static int run_pair(bslam_context* ctx, void* stream, bool coeffs, bool gradmag, int use_depth, int use_desc, const bslam_camera4f* color_camera,
+                    const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor, const bslam_buffer2d* frame_depth,
+                    const bslam_buffer2d* frame_normals, const bslam_buffer2d* frame_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
+                    const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, const float** row) {
+  if (!ctx || !color_camera || !depth_camera || !estimate_frame_T_surfel_frame) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
+  return run_pairs(ctx, (hipStream_t)stream, coeffs, gradmag, use_depth, use_desc, color_camera, depth_camera, baseline_fx, threshold_factor, 1, frame_depth,
+                   frame_normals, frame_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
+}
+
+// What the entry points copy out of a row.
+static void copy_coeffs(const float* row, uint32_t* visible_count, float* H, float* b) {
+  std::memcpy(H, row, 21 * sizeof(float));
+  std::memcpy(b, row + 21, 6 * sizeof(float));
+  if (visible_count) *visible_count = read_row_count(row);
+}
+static void copy_cost(const float* row, uint32_t* residual_count, float* residual_sum) {
+  *residual_count = read_row_count(row);
+  *residual_sum = row[kRowCost];
 }
 
 }  // namespace bslam
@@ -92,7 +115,7 @@ int bslam_compute_brightness_from_color(bslam_context* ctx, void* stream_, const
   if ((rc = make_img(intensity_buffer, 1, "intensity", &out))) return rc;
   if (!same_shape(color, out)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "color and intensity buffers differ in size");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(brightness_from_color_kernel, image_grid(out), dim3(256), 0, stream, color, out);
+  hipLaunchKernelGGL(normalize_byte_kernel<uint32_t>, image_grid(out), dim3(256), 0, stream, color, out);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }
@@ -106,7 +129,7 @@ int bslam_set_to_read_mode_normalized(bslam_context* ctx, void* stream_, const b
   if ((rc = make_img(output_u8, 1, "output", &out))) return rc;
   if (!same_shape(in, out)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "buffers differ in size");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  hipLaunchKernelGGL(read_mode_normalized_kernel, image_grid(out), dim3(256), 0, stream, in, out);
+  hipLaunchKernelGGL(normalize_byte_kernel<uint8_t>, image_grid(out), dim3(256), 0, stream, in, out);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }
@@ -175,13 +198,11 @@ int bslam_accumulate_pose_coeffs_from_images(
     const bslam_buffer2d* downsampled_normals, const bslam_buffer2d* downsampled_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
     const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, uint32_t* visible_count, float* H, float* b) {
   if (!H || !b) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
-  float row[kRow];
-  int rc = run_pair_kernel(ctx, (hipStream_t)stream, true, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
-                           downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
+  const float* row = nullptr;
+  int rc = run_pair(ctx, stream, true, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
+                    downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, &row);
   if (rc) return rc;
-  std::memcpy(H, row, 21 * sizeof(float));
-  std::memcpy(b, row + 21, 6 * sizeof(float));
-  if (visible_count) *visible_count = read_row_count(row);
+  copy_coeffs(row, visible_count, H, b);
   return BSLAM_OK;
 }
 
@@ -191,12 +212,11 @@ int bslam_compute_cost_and_residual_count_from_images(
     const bslam_buffer2d* downsampled_normals, const bslam_buffer2d* downsampled_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
     const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, uint32_t* residual_count, float* residual_sum) {
   if (!residual_count || !residual_sum) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
-  float row[kRow];
-  int rc = run_pair_kernel(ctx, (hipStream_t)stream, false, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
-                           downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
+  const float* row = nullptr;
+  int rc = run_pair(ctx, stream, false, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
+                    downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, &row);
   if (rc) return rc;
-  *residual_count = read_row_count(row);
-  *residual_sum = row[kRowCost];
+  copy_cost(row, residual_count, residual_sum);
   return BSLAM_OK;
 }
 
@@ -206,13 +226,11 @@ int bslam_accumulate_pose_coeffs_from_images_gradmag(
     const bslam_buffer2d* downsampled_normals, const bslam_buffer2d* downsampled_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
     const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, uint32_t* visible_count, float* H, float* b) {
   if (!H || !b) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
-  float row[kRow];
-  int rc = run_pair_kernel(ctx, (hipStream_t)stream, true, true, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
-                           downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
+  const float* row = nullptr;
+  int rc = run_pair(ctx, stream, true, true, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
+                    downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, &row);
   if (rc) return rc;
-  std::memcpy(H, row, 21 * sizeof(float));
-  std::memcpy(b, row + 21, 6 * sizeof(float));
-  if (visible_count) *visible_count = read_row_count(row);
+  copy_coeffs(row, visible_count, H, b);
   return BSLAM_OK;
 }
 
@@ -222,76 +240,28 @@ int bslam_compute_cost_and_residual_count_from_images_gradmag(
     const bslam_buffer2d* downsampled_normals, const bslam_buffer2d* downsampled_color, const bslam_mat3x4* estimate_frame_T_surfel_frame,
     const bslam_buffer2d* surfel_depth, const bslam_buffer2d* surfel_normals, const bslam_buffer2d* surfel_color, uint32_t* residual_count, float* residual_sum) {
   if (!residual_count || !residual_sum) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
-  float row[kRow];
-  int rc = run_pair_kernel(ctx, (hipStream_t)stream, false, true, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
-                           downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, row);
+  const float* row = nullptr;
+  int rc = run_pair(ctx, stream, false, true, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
+                    downsampled_depth, downsampled_normals, downsampled_color, estimate_frame_T_surfel_frame, surfel_depth, surfel_normals, surfel_color, &row);
   if (rc) return rc;
-  *residual_count = read_row_count(row);
-  *residual_sum = row[kRowCost];
+  copy_cost(row, residual_count, residual_sum);
   return BSLAM_OK;
 }
 
 int bslam_accumulate_pose_coeffs_from_images_batched(
-    bslam_context* ctx, void* stream_, int use_depth_residuals, int use_descriptor_residuals, const bslam_camera4f* color_camera,
+    bslam_context* ctx, void* stream, int use_depth_residuals, int use_descriptor_residuals, const bslam_camera4f* color_camera,
     const bslam_camera4f* depth_camera, float baseline_fx, float threshold_factor, int pair_count, const bslam_buffer2d* tracked_depth,
     const bslam_buffer2d* tracked_normals, const bslam_buffer2d* tracked_color, const bslam_mat3x4* estimates_frame_T_surfel_frame,
     const bslam_buffer2d* base_depth, const bslam_buffer2d* base_normals, const bslam_buffer2d* base_color, uint32_t* visible_counts, float* H, float* b) {
-  hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !color_camera || !depth_camera || !estimates_frame_T_surfel_frame || !tracked_depth || !tracked_normals || !tracked_color)
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (!H || !b) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null output");
   if (pair_count < 1 || pair_count > kMaxPairBatch) return fail(BSLAM_ERR_INVALID_ARGUMENT, "pair_count %d outside [1, %d]", pair_count, kMaxPairBatch);
-  if (!use_depth_residuals && !use_descriptor_residuals) return fail(BSLAM_ERR_INVALID_ARGUMENT, "need depth and/or descriptor residuals");
-  PairBatch batch;
-  std::memset(&batch, 0, sizeof(batch));
-  int rc;
-  for (int p = 0; p < pair_count; ++p) {
-    Img frame_color_img;
-    if ((rc = pair_images(&tracked_depth[p], &tracked_normals[p], &tracked_color[p], base_depth, base_normals, base_color, depth_camera, color_camera,
-                          &batch.im[p], &frame_color_img)))
-      return rc;
-    batch.im[p].frame_color = frame_color_img;
-    std::memcpy(batch.T[p].m, estimates_frame_T_surfel_frame[p].m, sizeof(float) * 12);
-  }
-  BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  bslam_depth_params dp;
-  std::memset(&dp, 0, sizeof(dp));
-  dp.sparse_surfel_cell_size = 1;
-  dp.baseline_fx = baseline_fx;
-  const CamConsts c = make_cam_consts(ctx, color_camera, depth_camera, &dp);
-  // every pair's tracked colour as luma quads, one launch (pair_images checked that all have the colour camera's size)
-  const int cw = color_camera->width, ch = color_camera->height;
-  const size_t quad_count = (size_t)(cw + 1) * (ch + 1);
-  if (!quad_table_addressable(cw, ch)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "colour image %dx%d is beyond the luma quad table's 32-bit addressing", cw, ch);
-  if ((rc = ctx->quads_aux.reserve((size_t)pair_count * quad_count * sizeof(QuadEntry)))) return rc;
-  for (int p = 0; p < pair_count; ++p) batch.im[p].frame_quads = (const QuadEntry*)ctx->quads_aux.ptr + (size_t)p * quad_count;
-  hipLaunchKernelGGL(build_quads_u8_batched_kernel, dim3((unsigned)((cw + 1 + 255) / 256), (unsigned)(ch + 1), (unsigned)pair_count), dim3(256), 0, stream,
-                     batch, (QuadEntry*)ctx->quads_aux.ptr, quad_count);
-  BSLAM_HIP_TRY(hipGetLastError());
-  const int pixels = depth_camera->width * depth_camera->height;
-  const int blocks = (pixels + 255) / 256;
-  const int rows = blocks * 4;
-  const size_t partial_floats = (size_t)pair_count * rows * kRow;
-  if ((rc = ctx->partials.reserve((partial_floats + (size_t)pair_count * kReduceParts * kRow) * sizeof(float)))) return rc;
-  if ((rc = ctx->coeffs.reserve((size_t)pair_count * kRow * sizeof(float)))) return rc;
-  float* partials = (float*)ctx->partials.ptr;
-  const dim3 grid((unsigned)blocks, (unsigned)pair_count), block(256);
-  if (use_depth_residuals && use_descriptor_residuals) hipLaunchKernelGGL((pair_accumulate_batched_kernel<true, true>), grid, block, 0, stream, c, threshold_factor, batch, partials);
-  else if (use_depth_residuals) hipLaunchKernelGGL((pair_accumulate_batched_kernel<true, false>), grid, block, 0, stream, c, threshold_factor, batch, partials);
-  else hipLaunchKernelGGL((pair_accumulate_batched_kernel<false, true>), grid, block, 0, stream, c, threshold_factor, batch, partials);
-  BSLAM_HIP_TRY(hipGetLastError());
-  float* parts = partials + partial_floats;
-  hipLaunchKernelGGL(pose_reduce_kernel, dim3((unsigned)pair_count, kReduceParts), dim3(256), 0, stream, (const float*)partials, rows, parts);
-  BSLAM_HIP_TRY(hipGetLastError());
-  hipLaunchKernelGGL(pose_reduce_final_kernel, dim3((unsigned)pair_count), dim3(64), 0, stream, (const float*)parts, (float*)ctx->coeffs.ptr);
-  BSLAM_HIP_TRY(hipGetLastError());
-  const float* rows_out = nullptr;
-  if ((rc = read_back(ctx, stream, (const float*)ctx->coeffs.ptr, (size_t)pair_count * kRow, &rows_out))) return rc;
-  for (int p = 0; p < pair_count; ++p) {
-    std::memcpy(H + 21 * p, rows_out + (size_t)p * kRow, 21 * sizeof(float));
-    std::memcpy(b + 6 * p, rows_out + (size_t)p * kRow + 21, 6 * sizeof(float));
-    if (visible_counts) visible_counts[p] = read_row_count(rows_out + (size_t)p * kRow);
-  }
+  const float* rows = nullptr;
+  int rc = run_pairs(ctx, (hipStream_t)stream, true, false, use_depth_residuals, use_descriptor_residuals, color_camera, depth_camera, baseline_fx, threshold_factor,
+                     pair_count, tracked_depth, tracked_normals, tracked_color, estimates_frame_T_surfel_frame, base_depth, base_normals, base_color, &rows);
+  if (rc) return rc;
+  for (int p = 0; p < pair_count; ++p) copy_coeffs(rows + (size_t)p * kRow, visible_counts ? visible_counts + p : nullptr, H + 21 * p, b + 6 * p);
   return BSLAM_OK;
 }
 

@@ -1,8 +1,11 @@
 // odometry_kernels.hpp -- pairwise frame tracking for gfx950: pyramid construction
-// (BS/kernel_downsample.cu) and the image-pair Gauss-Newton coefficients / cost kernels of
+// (BS/kernel_downsample.cu) and the image-pair Gauss-Newton coefficients / cost kernel of
 // BS/kernel_opt_pose.cu:422-661, 939-1171 (GradientXY variant, the one BadSlam::RunOdometry uses).
 // Naming follows the reference: "surfel" images = the BASE frame (whose pixels are projected), "frame" images = the
 // TRACKED frame; estimate_frame_T_surfel_frame = (base_T_frame)^-1.
+// What the kernels share is written once: texel_u8 (the clamped, normalised byte every bilinear fetch and gradient footprint
+// reads), closest_to_average (the 2x2 depth pick of both pyramid kernels), normalize_byte_kernel (both u8 -> u8 copies),
+// build_quads_u8_batched_kernel and pair_accumulate_kernel, which take a PairBatch: a single pair is a batch of one.
 // The reduction is the pose kernel's: 32 accumulators per lane -> transposed wave butterfly -> one row per wave
 // -> pose_reduce_kernel / pose_reduce_final_kernel (deterministic, no atomics).
 #pragma once
@@ -12,6 +15,12 @@
 
 namespace bslam {
 
+// texel of a single-channel u8 image, clamp addressing, normalised to [0, 1] (a texel-centre fetch of the reference's texture)
+__device__ __forceinline__ float texel_u8(const Img& img, int ix, int iy) {
+  ix = max(0, min(ix, img.width - 1));
+  iy = max(0, min(iy, img.height - 1));
+  return (float)img.at<uint8_t>(iy, ix) * (1.0f / 255.0f);
+}
 // bilinear fetch from a single-channel u8 image (texture model of tex_filter / tex_footprint)
 __device__ __forceinline__ float tex_u8_direct(const Img& img, float x, float y, int tex_mode) {
   const float xb = x - 0.5f, yb = y - 0.5f;
@@ -23,29 +32,20 @@ __device__ __forceinline__ float tex_u8_direct(const Img& img, float x, float y,
   }
   const int i = (int)fminf(fmaxf(fx, -1.0f), (float)(img.width - 1));
   const int j = (int)fminf(fmaxf(fy, -1.0f), (float)(img.height - 1));
-  auto texel = [&](int ix, int iy) {
-    ix = max(0, min(ix, img.width - 1));
-    iy = max(0, min(iy, img.height - 1));
-    return (float)img.at<uint8_t>(iy, ix) * (1.0f / 255.0f);
-  };
   LumaQuad q;
-  q.tl = texel(i, j); q.tr = texel(i + 1, j); q.bl = texel(i, j + 1); q.br = texel(i + 1, j + 1);
+  q.tl = texel_u8(img, i, j); q.tr = texel_u8(img, i + 1, j); q.bl = texel_u8(img, i, j + 1); q.br = texel_u8(img, i + 1, j + 1);
   return tex_filter(q, a, b);
 }
 __device__ __forceinline__ uint8_t sat_u8(float v) { return (uint8_t)min(255, max(0, f2i(v))); }   // cvt.rzi.u8.f32
 
-// ComputeBrightnessKernel(texture) BS/cuda_image_processing.cu:196-205
-__global__ __launch_bounds__(256) void brightness_from_color_kernel(Img color, Img out) {
+// ComputeBrightnessKernel(texture) BS/cuda_image_processing.cu:196-205 (Src = uint32_t: the luma is the top byte of the pixel) and
+// CUDABuffer_<u8>::SetToReadModeNormalized LV/cuda/cuda_buffer.cu:82-102 (Src = uint8_t): the byte through the texture's [0, 1]
+template <class Src>
+__global__ __launch_bounds__(256) void normalize_byte_kernel(Img in, Img out) {
   const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
   if (x >= out.width || y >= out.height) return;
-  const uint32_t luma = color.at<uint32_t>(y, x) >> 24;
-  out.at<uint8_t>(y, x) = sat_u8(255.f * ((float)luma * (1.0f / 255.0f)));
-}
-// CUDABuffer_<u8>::SetToReadModeNormalized LV/cuda/cuda_buffer.cu:82-102
-__global__ __launch_bounds__(256) void read_mode_normalized_kernel(Img in, Img out) {
-  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
-  if (x >= out.width || y >= out.height) return;
-  out.at<uint8_t>(y, x) = sat_u8(255.f * ((float)in.at<uint8_t>(y, x) * (1.0f / 255.0f)));
+  const uint32_t byte = sizeof(Src) == 4 ? (uint32_t)in.at<Src>(y, x) >> 24 : (uint32_t)in.at<Src>(y, x);
+  out.at<uint8_t>(y, x) = sat_u8(255.f * ((float)byte * (1.0f / 255.0f)));
 }
 // CalibrateDepthCUDAKernel / CalibrateDepthAndTransformColorToDepthCUDAKernel BS/kernel_downsample.cu:236-312
 template <bool kTransformColor>
@@ -66,6 +66,20 @@ __global__ __launch_bounds__(256) void calibrate_depth_kernel(CamConsts c, Img d
     out_depth.at<float>(y, x) = depth;
   }
 }
+// The 2x2 depth pick of the pyramid kernels (BS/kernel_downsample.cu:78-95, :132-149): of four depths, +inf marking an invalid
+// one, the index of the one closest to the average of the depth_count > 0 valid ones (their sum: depth_sum); the first of equal
+// candidates wins.
+__device__ __forceinline__ int closest_to_average(const float (&depths)[4], int depth_count, float depth_sum) {
+  const float average_depth = depth_sum / (float)depth_count;
+  int closest_index = 0;
+  float closest_distance = __uint_as_float(0x7f800000u);
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float distance = fabsf(depths[i] - average_depth);
+    if (distance < closest_distance) { closest_index = i; closest_distance = distance; }
+  }
+  return closest_index;
+}
 // DownsampleImagesCUDAKernel BS/kernel_downsample.cu:105-152.  The colour pyramid may have another size than the depth
 // pyramid (a colour camera of another pyramid level): the grid covers the larger of the two outputs.
 __global__ __launch_bounds__(256) void downsample_kernel(Img depth, Img normals, Img color, int tex_mode, Img out_depth, Img out_normals, Img out_color) {
@@ -83,14 +97,7 @@ __global__ __launch_bounds__(256) void downsample_kernel(Img depth, Img normals,
   if (depth_count == 0) {
     out_depth.at<float>(y, x) = 0.f;
   } else {
-    const float average_depth = depth_sum / (float)depth_count;
-    int closest_index = 0;
-    float closest_distance = __uint_as_float(0x7f800000u);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float distance = fabsf(depths[i] - average_depth);
-      if (distance < closest_distance) { closest_index = i; closest_distance = distance; }
-    }
+    const int closest_index = closest_to_average(depths, depth_count, depth_sum);
     out_depth.at<float>(y, x) = depths[closest_index];
     out_normals.at<uint16_t>(y, x) = normals.at<uint16_t>(2 * y + (closest_index >> 1), 2 * x + (closest_index & 1));
   }
@@ -135,28 +142,12 @@ __global__ __launch_bounds__(256) void calibrate_and_downsample_kernel(CamConsts
   if (depth_count == 0) {
     out_depth.at<float>(y, x) = 0.f;
   } else {
-    const float average_depth = depth_sum / (float)depth_count;
-    int closest_index = 0;
-    float closest_distance = __uint_as_float(0x7f800000u);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float distance = fabsf(depths[i] - average_depth);
-      if (distance < closest_distance) { closest_index = i; closest_distance = distance; }
-    }
+    const int closest_index = closest_to_average(depths, depth_count, depth_sum);
     out_depth.at<float>(y, x) = depths[closest_index];
     out_normals.at<uint16_t>(y, x) = normals.at<uint16_t>(2 * y + (closest_index >> 1), 2 * x + (closest_index & 1));
   }
   const float col = kDownsampleColor ? tex_u8_direct(color, 2 * x + 1.0f, 2 * y + 1.0f, c.tex_mode) : tex_u8_direct(color, x + 0.5f, y + 0.5f, c.tex_mode);
   out_color.at<uint8_t>(y, x) = sat_u8(255.f * col + 0.5f);
-}
-// luma quads of a u8 image (see KfDev::quads)
-__global__ __launch_bounds__(256) void build_quads_u8_kernel(Img img, QuadEntry* __restrict__ quads) {
-  const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
-  const int w = img.width, h = img.height;
-  if (qx > w) return;
-  const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
-  const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
-  quads[(size_t)qy * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
 }
 
 struct PairImages {
@@ -164,16 +155,44 @@ struct PairImages {
   Img frame_depth, frame_normals;                   // tracked frame: f32 depth, u16 normals
   const QuadEntry* frame_quads;                     // tracked frame colour as luma quads (colour intrinsics)
   Img frame_color;                                  // the same image, direct (the gradient-magnitude variant reads it as the reference does)
+  M34 frame_T_surfel;                               // estimate_frame_T_surfel_frame
 };
+
+// Loop verification (BS/loop_detector.cc:440-712) tracks one base frame against up to kMaxPairBatch tracked frames at
+// once, and a single pair is a batch of one.  The per-pair images and transforms travel in the kernel arguments; the base
+// images are the same in every entry.  Entry 0 comes first and whole, and the kernels take the batch as their last
+// argument: what a batch of one reads of its arguments is one contiguous piece at their start.
+constexpr int kMaxPairBatch = BSLAM_MAX_PAIR_BATCH;
+struct PairBatch {
+  PairImages im[kMaxPairBatch];
+};
+
+static_assert(sizeof(PairBatch) + sizeof(CamConsts) + 64 <= 4096, "the pair kernels' arguments must stay below the 4 KB kernarg limit");
+
+// luma quads of the tracked u8 colour image of every pair (see KfDev::quads); grid (ceil((w+1)/256), h+1, pairs)
+__global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(QuadEntry* __restrict__ quads, size_t quads_per_pair, PairBatch batch) {
+  const int p = blockIdx.z;
+  const Img img = batch.im[p].frame_color;
+  const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
+  const int w = img.width, h = img.height;
+  if (qx > w) return;
+  const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
+  const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
+  quads[(size_t)p * quads_per_pair + (size_t)qy * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
+}
 
 // One thread per base pixel.  kCoeffs: H (21) + b (6) of AccumulatePoseEstimationCoeffsFromImagesCUDAKernel_GradientXY
 // (column 28 = number of visible pixels); !kCoeffs: cost (column 27) and residual count (column 28) of
 // ComputeCostAndResidualCountFromImagesCUDAKernel_GradientXY.
 // kGradMag: ONE colour residual on gradient-magnitude images (ComputeRawColorResidualAndJacobian BS/kernel_opt_pose.cu:192-222,
 // kernels :713-937 and :1173-1338) instead of the two descriptor residuals.
-// The body is shared with pair_accumulate_batched_kernel: `partials` is the first row of the pair's own blocks.
+// blockIdx.y = pair: each pair writes its own gridDim.x * 4 rows, which pose_reduce_kernel then sums per pair in one order
+// whatever the batch (so the row of a pair does not depend on the pairs it shares a launch with).
 template <bool kDepth, bool kDesc, bool kCoeffs, bool kGradMag>
-__device__ __forceinline__ void pair_accumulate_body(const CamConsts& c, const M34& T, float threshold_factor, const PairImages& im, float* __restrict__ partials) {
+__global__ __launch_bounds__(256) void pair_accumulate_kernel(CamConsts c, float threshold_factor, float* __restrict__ partials, PairBatch batch) {
+  const PairImages& im = batch.im[blockIdx.y];
+  const M34& T = im.frame_T_surfel;
+  partials += (size_t)blockIdx.y * gridDim.x * (blockDim.x / 64) * kRow;
   const int pixel = blockIdx.x * blockDim.x + threadIdx.x;
   const int w = im.surfel_depth.width, h = im.surfel_depth.height;
   float acc[kRow];
@@ -221,11 +240,7 @@ __device__ __forceinline__ void pair_accumulate_body(const CamConsts& c, const M
         r1 = 255.f * tex_u8_direct(im.frame_color, cp.x, cp.y, c.tex_mode) - (float)im.surfel_color.at<uint8_t>(y, x);   // BS/cost_function.cuh:324-331
         if (kCoeffs) {                                                                                                    // :335-352
           const GradFootprint g = grad_footprint(c, cp);
-          auto texel = [&](int ix, int iy) {
-            ix = max(0, min(ix, im.frame_color.width - 1));
-            iy = max(0, min(iy, im.frame_color.height - 1));
-            return 255.f * ((float)im.frame_color.at<uint8_t>(iy, ix) * (1.0f / 255.0f));
-          };
+          auto texel = [&](int ix, int iy) { return 255.f * texel_u8(im.frame_color, ix, iy); };
           const LumaQuad q{texel(g.ix, g.iy), texel(g.ix + 1, g.iy), texel(g.ix, g.iy + 1), texel(g.ix + 1, g.iy + 1)};
           float gx, gy;
           grad_filter(q, g, &gx, &gy);
@@ -297,38 +312,6 @@ __device__ __forceinline__ void pair_accumulate_body(const CamConsts& c, const M
   const float total = wave_transpose_sum32(acc);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if ((lane & 1) == 0) partials[((size_t)blockIdx.x * (blockDim.x / 64) + wave) * kRow + (lane >> 1)] = total;
-}
-
-template <bool kDepth, bool kDesc, bool kCoeffs, bool kGradMag = false>
-__global__ __launch_bounds__(256) void pair_accumulate_kernel(CamConsts c, M34 T, float threshold_factor, PairImages im, float* __restrict__ partials) {
-  pair_accumulate_body<kDepth, kDesc, kCoeffs, kGradMag>(c, T, threshold_factor, im, partials);
-}
-
-// Loop verification (BS/loop_detector.cc:440-712) tracks one base frame against up to kMaxPairBatch tracked frames at
-// once: blockIdx.y = pair, each pair writes its own gridDim.x * 4 rows, which pose_reduce_kernel then sums per pair in
-// the single-pair order (so row p is bit-identical to a single-pair call).  The per-pair images travel in the kernel
-// arguments; the base images are the same in every entry.
-constexpr int kMaxPairBatch = BSLAM_MAX_PAIR_BATCH;
-struct PairBatch {
-  PairImages im[kMaxPairBatch];
-  M34 T[kMaxPairBatch];
-};
-
-__global__ __launch_bounds__(256) void build_quads_u8_batched_kernel(PairBatch batch, QuadEntry* __restrict__ quads, size_t quads_per_pair) {
-  const int p = blockIdx.z;
-  const Img img = batch.im[p].frame_color;
-  const int qx = blockIdx.x * blockDim.x + threadIdx.x, qy = blockIdx.y;
-  const int w = img.width, h = img.height;
-  if (qx > w) return;
-  const int i0 = max(0, qx - 1), i1 = min(qx, w - 1), j0 = max(0, qy - 1), j1 = min(qy, h - 1);
-  const uint32_t tl = img.at<uint8_t>(j0, i0), tr = img.at<uint8_t>(j0, i1), bl = img.at<uint8_t>(j1, i0), br = img.at<uint8_t>(j1, i1);
-  quads[(size_t)p * quads_per_pair + (size_t)qy * (size_t)(w + 1) + qx] = pack_quad(tl, tr, bl, br);
-}
-
-template <bool kDepth, bool kDesc>
-__global__ __launch_bounds__(256) void pair_accumulate_batched_kernel(CamConsts c, float threshold_factor, PairBatch batch, float* __restrict__ partials) {
-  const int p = blockIdx.y;
-  pair_accumulate_body<kDepth, kDesc, true, false>(c, batch.T[p], threshold_factor, batch.im[p], partials + (size_t)p * gridDim.x * (blockDim.x / 64) * kRow);
 }
 
 }  // namespace bslam

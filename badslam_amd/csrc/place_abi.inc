@@ -1,5 +1,4 @@
-// place_abi.inc -- place recognition entry points of include/badslam_hip.h (included by badslam_hip.hip after
-// render_abi.inc; uses the argument helpers of preprocess_abi.inc).
+// place_abi.inc -- place recognition entry points of include/badslam_hip.h (included by badslam_hip.hip).
 
 namespace bslam {
 

@@ -2,45 +2,6 @@
 
 namespace bslam {
 
-static int make_img(const bslam_buffer2d* b, size_t elem, const char* name, Img* out) {
-  if (!b || !b->address) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s buffer is null", name);
-  if (b->width <= 0 || b->height <= 0 || b->pitch < (size_t)b->width * elem) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s buffer has a bad shape / pitch", name);
-  out->base = (uint8_t*)b->address; out->pitch = (uint32_t)b->pitch; out->width = b->width; out->height = b->height;
-  return BSLAM_OK;
-}
-static bool same_shape(const Img& a, const Img& b) { return a.width == b.width && a.height == b.height; }
-static dim3 image_grid(const Img& i) { return dim3((unsigned)((i.width + 255) / 256), (unsigned)i.height); }
-static dim3 flat_grid(size_t threads) { return dim3((unsigned)((threads + 255) / 256)); }
-// do the byte ranges [base, base + height * pitch) of two images share a byte?
-static bool overlap(const Img& a, const Img& b) {
-  const uintptr_t a0 = (uintptr_t)a.base, a1 = a0 + (size_t)a.height * a.pitch, b0 = (uintptr_t)b.base, b1 = b0 + (size_t)b.height * b.pitch;
-  return a0 < b1 && b0 < a1;
-}
-static bool rows_aligned(const Img& i, size_t bytes) { return ((uintptr_t)i.base | (uintptr_t)i.pitch) % bytes == 0; }
-
-// Bump carver over a slab: take<T>(count, alignment in bytes) hands out the next piece.  Without a base it only counts.
-struct Carver {
-  uint8_t* base;
-  size_t used;
-  template <class T> T* take(size_t count, size_t align = alignof(T)) {
-    used = (used + align - 1) / align * align;
-    T* piece = base ? (T*)(base + used) : nullptr;
-    used += count * sizeof(T);
-    return piece;
-  }
-};
-// Runs `layout` once to count the bytes, reserves them and runs it again over the slab, so the total and the pointers come from
-// the same statements.  The slab's base is aligned for every piece (hipMalloc: 256 bytes).
-template <class Layout>
-static int carve(Slab& slab, Layout layout) {
-  Carver count{nullptr, 0};
-  layout(count);
-  if (int rc = slab.reserve(count.used)) return rc;
-  Carver pieces{(uint8_t*)slab.ptr, 0};
-  layout(pieces);
-  return BSLAM_OK;
-}
-
 // The pyramid level L (1 ... 3) with in = out * 2^L in both dimensions; 0 if there is none.
 static int pyramid_level(const Img& in, const Img& out) {
   for (int level = 1; level <= 3; ++level)
@@ -168,10 +129,7 @@ int bslam_compute_point_radii_and_remove_isolated_pixels(bslam_context* ctx, voi
   if (!same_shape(in, rad) || !same_shape(in, out) || in.base == out.base || in.base == rad.base || rad.base == out.base)
     return fail(BSLAM_ERR_INVALID_ARGUMENT, "depth / radius buffers must be distinct and of one size");
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
-  bslam_depth_params dp;
-  std::memset(&dp, 0, sizeof(dp));
-  dp.sparse_surfel_cell_size = 1;
-  const CamConsts c = make_cam_consts(ctx, nullptr, depth_camera, &dp);
+  const CamConsts c = depth_only_consts(ctx, nullptr, depth_camera, 0.f);
   hipLaunchKernelGGL(radii_kernel, image_grid(in), dim3(256), 0, stream, c, raw_to_float_depth, in, rad, out);
   BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;

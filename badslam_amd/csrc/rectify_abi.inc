@@ -1,5 +1,4 @@
-// rectify_abi.inc -- sensor rectification entry points of include/badslam_hip.h (included by badslam_hip.hip after
-// preprocess_abi.inc, whose argument helpers it uses).
+// rectify_abi.inc -- sensor rectification entry points of include/badslam_hip.h (included by badslam_hip.hip).
 
 namespace bslam {
 

@@ -1,5 +1,4 @@
-// render_abi.inc -- model view entry point of include/badslam_hip.h (included by badslam_hip.hip after rectify_abi.inc,
-// whose argument helpers it uses).
+// render_abi.inc -- model view entry point of include/badslam_hip.h (included by badslam_hip.hip).
 
 namespace bslam {
 

@@ -1,5 +1,5 @@
 // sampling_abi.inc -- bslam_sample_mesh of include/badslam_hip.h (included by badslam_hip.hip after distance_abi.inc:
-// check_mesh_spans, mesh_error, empty_mesh, device_scan, flat_grid, read_back, carve).
+// check_mesh_spans, mesh_error, empty_mesh, device_scan).
 
 extern "C" {
 

@@ -27,6 +27,68 @@ bool IsScaleNPoseEstimationConverged(const float* x, float scaling_factor) {
   for (int i = 0; i < 6; ++i) { const float v = (i < 3) ? x[i] : x[i] * (translation_threshold / rotation_threshold); n += v * v; }
   return n < scaling_factor * scaling_factor * translation_threshold;
 }
+
+// The per-scale images of one side (base or tracked) of a buffers object as the library takes them; level 0 of the normals is the
+// frame's own image.
+struct LevelPods {
+  std::vector<bslam_buffer2d> depth, normals, color;
+};
+LevelPods Pods(const PairwiseFrameTrackingBuffers& b, bool base, const DeviceBuffer<u16>& normals_l0) {
+  LevelPods pods;
+  for (int s = 0; s < b.num_scales; ++s) {
+    pods.depth.push_back((base ? b.base_depth : b.tracked_depth)[s]->ToPod());
+    pods.color.push_back((base ? b.base_color : b.tracked_color)[s]->ToPod());
+    pods.normals.push_back(s ? (base ? b.base_normals : b.tracked_normals)[s]->ToPod() : normals_l0.ToPod());
+  }
+  return pods;
+}
+// gradient-magnitude images instead of brightness images when use_gradmag (BS/bad_slam.cc:859-869, 888-898)
+void ColourCue(bslam_context* ctx, hipStream_t stream, bool use_gradmag, const DeviceBuffer<uchar4_t>& rgba, const bslam_buffer2d& out) {
+  const bslam_buffer2d in = rgba.ToPod();
+  if (use_gradmag) Check(bslam_compute_sobel_gradient_magnitude(ctx, stream, &in, &out), "bslam_compute_sobel_gradient_magnitude");
+  else Check(bslam_compute_brightness_from_color(ctx, stream, &in, &out), "bslam_compute_brightness_from_color");
+}
+void Downsample(bslam_context* ctx, hipStream_t stream, const LevelPods& l, int s) {
+  Check(bslam_downsample_images(ctx, stream, &l.depth[s - 1], &l.normals[s - 1], &l.color[s - 1], &l.depth[s], &l.normals[s], &l.color[s]), "bslam_downsample_images");
+}
+// The base frame's pyramid: colour cue, depth calibrated and colour brought into the depth image's geometry, then halved per scale
+// (BS/bad_slam.cc:859-897, BS/pairwise_frame_tracking.cc:283-341).
+void PrepareBase(bslam_context* ctx, hipStream_t stream, bool use_gradmag, const bslam_camera4f& color_cam, const bslam_camera4f& depth_cam,
+                 const bslam_depth_params& dp, const DeviceBuffer<u16>& depth_u16, const DeviceBuffer<uchar4_t>& rgba, const bslam_buffer2d& cue,
+                 const LevelPods& base) {
+  const bslam_buffer2d d16 = depth_u16.ToPod();
+  ColourCue(ctx, stream, use_gradmag, rgba, cue);
+  Check(bslam_calibrate_depth_and_transform_color_to_depth(ctx, stream, &color_cam, &depth_cam, &dp, &d16, &cue, &base.depth[0], &base.color[0]),
+        "bslam_calibrate_depth_and_transform_color_to_depth");
+  for (size_t s = 1; s < base.depth.size(); ++s) Downsample(ctx, stream, base, static_cast<int>(s));
+}
+// A tracked frame's pyramid: colour cue, then level 0 (calibrated depth, normalised colour) or, without it, level 1 straight from
+// the raw images (:303-323), then halved per scale.
+void PrepareTracked(bslam_context* ctx, hipStream_t stream, bool use_gradmag, bool use_pyramid_level_0, bool downsample_color, const bslam_depth_params& dp,
+                    const DeviceBuffer<u16>& depth_u16, const DeviceBuffer<u16>& normals_l0, const DeviceBuffer<uchar4_t>& rgba, const bslam_buffer2d& cue,
+                    const LevelPods& tracked) {
+  const bslam_buffer2d d16 = depth_u16.ToPod(), normals_in = normals_l0.ToPod();
+  const int num_scales = static_cast<int>(tracked.depth.size());
+  ColourCue(ctx, stream, use_gradmag, rgba, cue);
+  if (use_pyramid_level_0) {
+    Check(bslam_calibrate_depth(ctx, stream, &dp, &d16, &tracked.depth[0]), "bslam_calibrate_depth");
+    Check(bslam_set_to_read_mode_normalized(ctx, stream, &cue, &tracked.color[0]), "bslam_set_to_read_mode_normalized");
+  } else if (num_scales > 1) {
+    Check(bslam_calibrate_and_downsample_images(ctx, stream, downsample_color, &dp, &d16, &normals_in, &cue, &tracked.depth[1], &tracked.normals[1],
+                                                &tracked.color[1]),
+          "bslam_calibrate_and_downsample_images");
+  }
+  for (int s = use_pyramid_level_0 ? 1 : 2; s < num_scales; ++s) Downsample(ctx, stream, tracked, s);
+}
+// The better of two estimates (BS/pairwise_frame_tracking.cc:428-489): the one with more than twice the residuals, else the cheaper.
+bool BetterOf(u32 count_a, float cost_a, u32 count_b, float cost_b) {
+  if (count_a > 2 * count_b) return true;
+  if (count_b > 2 * count_a) return false;
+  return cost_a < cost_b;
+}
+// Step damping at the two coarsest scales (:573-579).
+float Damping(int scale, int num_scales) { return scale == num_scales - 1 ? 0.25f : scale == num_scales - 2 ? 0.5f : 1.f; }
+constexpr int kMaxIterationsPerScale = 30;
 }  // namespace
 
 PairwiseFrameTrackingBuffers::PairwiseFrameTrackingBuffers(int depth_width, int depth_height, int color_width, int color_height, int num_scales_)
@@ -58,50 +120,11 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
   if (!use_pyramid_level_0 && (depth_camera.width() != color_camera.width() || depth_camera.height() != color_camera.height()))
     throw std::invalid_argument("TrackFramePairwise: without pyramid level 0, depth and colour images must have the same size");   // :303-323 builds level 1 of both at once
   const int num_scales = buffers->num_scales;
-  const bslam_camera4f color_cam = color_camera.pod(), depth_cam = depth_camera.pod();
-  std::vector<bslam_buffer2d> base_depth(num_scales), base_normals(num_scales), base_color(num_scales), tracked_depth(num_scales),
-      tracked_normals(num_scales), tracked_color(num_scales);
-  for (int s = 0; s < num_scales; ++s) {
-    base_depth[s] = buffers->base_depth[s]->ToPod();
-    base_color[s] = buffers->base_color[s]->ToPod();
-    tracked_depth[s] = buffers->tracked_depth[s]->ToPod();
-    tracked_color[s] = buffers->tracked_color[s]->ToPod();
-    base_normals[s] = s ? buffers->base_normals[s]->ToPod() : base_normals_l0.ToPod();
-    tracked_normals[s] = s ? buffers->tracked_normals[s]->ToPod() : tracked_normals_l0.ToPod();
-  }
-  // --- input preparation (BadSlam::RunOdometry, BS/bad_slam.cc:859-897)
-  const bslam_buffer2d base_rgba = base_color_rgba.ToPod(), tracked_rgba = tracked_color_rgba.ToPod();
-  const bslam_buffer2d base_gm = buffers->base_gradmag->ToPod(), tracked_gm = buffers->tracked_gradmag->ToPod();
-  const bslam_buffer2d base_d16 = base_depth_u16.ToPod(), tracked_d16 = tracked_depth_u16.ToPod();
-  // gradient-magnitude images instead of brightness images when use_gradmag (:859-869, 888-898)
-  auto colour_cue = [&](const bslam_buffer2d* rgba, const bslam_buffer2d* out) {
-    if (use_gradmag) Check(bslam_compute_sobel_gradient_magnitude(ctx, stream, rgba, out), "bslam_compute_sobel_gradient_magnitude");
-    else Check(bslam_compute_brightness_from_color(ctx, stream, rgba, out), "bslam_compute_brightness_from_color");
-  };
-  colour_cue(&base_rgba, &base_gm);
-  Check(bslam_calibrate_depth_and_transform_color_to_depth(ctx, stream, &color_cam, &depth_cam, &dp, &base_d16, &base_gm, &base_depth[0], &base_color[0]),
-        "bslam_calibrate_depth_and_transform_color_to_depth");
-  colour_cue(&tracked_rgba, &tracked_gm);
-  // --- pyramids (BS/pairwise_frame_tracking.cc:283-341)
-  const bslam_buffer2d tracked_normals_in = tracked_normals_l0.ToPod();
-  if (use_pyramid_level_0) {
-    Check(bslam_calibrate_depth(ctx, stream, &dp, &tracked_d16, &tracked_depth[0]), "bslam_calibrate_depth");
-    Check(bslam_set_to_read_mode_normalized(ctx, stream, &tracked_gm, &tracked_color[0]), "bslam_set_to_read_mode_normalized");
-  } else if (num_scales > 1) {   // :303-323
-    Check(bslam_calibrate_and_downsample_images(ctx, stream, depth_camera.width() == color_camera.width(), &dp, &tracked_d16, &tracked_normals_in, &tracked_gm,
-                                                &tracked_depth[1], &tracked_normals[1], &tracked_color[1]),
-          "bslam_calibrate_and_downsample_images");
-  }
-  for (int s = 1; s < num_scales; ++s) {
-    if (s >= 2 || use_pyramid_level_0)
-      Check(bslam_downsample_images(ctx, stream, &tracked_depth[s - 1], &tracked_normals[s - 1], &tracked_color[s - 1], &tracked_depth[s], &tracked_normals[s],
-                                    &tracked_color[s]),
-            "bslam_downsample_images");
-    Check(bslam_downsample_images(ctx, stream, &base_depth[s - 1], &base_normals[s - 1], &base_color[s - 1], &base_depth[s], &base_normals[s], &base_color[s]),
-          "bslam_downsample_images");
-  }
+  const LevelPods base = Pods(*buffers, true, base_normals_l0), tracked = Pods(*buffers, false, tracked_normals_l0);
+  PrepareBase(ctx, stream, use_gradmag, color_camera.pod(), depth_camera.pod(), dp, base_depth_u16, base_color_rgba, buffers->base_gradmag->ToPod(), base);
+  PrepareTracked(ctx, stream, use_gradmag, use_pyramid_level_0, depth_camera.width() == color_camera.width(), dp, tracked_depth_u16, tracked_normals_l0,
+                 tracked_color_rgba, buffers->tracked_gradmag->ToPod(), tracked);
   // --- coarse to fine (:343-640)
-  constexpr int kMaxIterationsPerScale = 30;
   SE3f estimate = init1, chosen_initial = init1;
   for (int scale = num_scales - 1; scale >= (use_pyramid_level_0 ? 0 : 1); --scale) {   // :367
     const float scaling_factor = static_cast<float>(std::pow(2, scale));
@@ -110,8 +133,8 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
     auto cost_of = [&](const SE3f& base_T_frame, u32* count, float* cost) {
       const bslam_mat3x4 M = base_T_frame.Inverse().Matrix3x4();
       Check((use_gradmag ? bslam_compute_cost_and_residual_count_from_images_gradmag : bslam_compute_cost_and_residual_count_from_images)(
-                ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx, threshold_factor, &tracked_depth[scale],
-                &tracked_normals[scale], &tracked_color[scale], &M, &base_depth[scale], &base_normals[scale], &base_color[scale], count, cost),
+                ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx, threshold_factor, &tracked.depth[scale],
+                &tracked.normals[scale], &tracked.color[scale], &M, &base.depth[scale], &base.normals[scale], &base.color[scale], count, cost),
             "bslam_compute_cost_and_residual_count_from_images");
     };
     if (scale != num_scales - 1 || test_different_initial_estimates) {   // :428-489
@@ -121,10 +144,7 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
       float cost_last = 0, cost_other = 0;
       cost_of(last, &count_last, &cost_last);
       cost_of(other, &count_other, &cost_other);
-      if (count_last > 2 * count_other) estimate = last;
-      else if (count_other > 2 * count_last) estimate = other;
-      else if (cost_last < cost_other) estimate = last;
-      else estimate = other;
+      estimate = BetterOf(count_last, cost_last, count_other, cost_other) ? last : other;
       if (scale == num_scales - 1) chosen_initial = estimate;
     }
     int iteration;
@@ -132,13 +152,11 @@ void TrackFramePairwise(bslam_context* ctx, hipStream_t stream, PairwiseFrameTra
       const bslam_mat3x4 M = estimate.Inverse().Matrix3x4();
       float H[21], b[6], x[6];
       Check((use_gradmag ? bslam_accumulate_pose_coeffs_from_images_gradmag : bslam_accumulate_pose_coeffs_from_images)(
-                ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx, threshold_factor, &tracked_depth[scale],
-                &tracked_normals[scale], &tracked_color[scale], &M, &base_depth[scale], &base_normals[scale], &base_color[scale], nullptr, H, b),
+                ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx, threshold_factor, &tracked.depth[scale],
+                &tracked.normals[scale], &tracked.color[scale], &M, &base.depth[scale], &base.normals[scale], &base.color[scale], nullptr, H, b),
             "bslam_accumulate_pose_coeffs_from_images");
       SolveLDLTUpper(6, H, b, x);   // :561
-      float damping = 1.f;          // :573-579
-      if (scale == num_scales - 2) damping = 0.5f;
-      else if (scale == num_scales - 1) damping = 0.25f;
+      const float damping = Damping(scale, num_scales);
       float step[6];
       for (int i = 0; i < 6; ++i) step[i] = -damping * x[i];
       estimate = estimate * SE3f::Exp(step);
@@ -161,43 +179,17 @@ void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vec
     buffers->emplace_back(new PairwiseFrameTrackingBuffers(depth_camera.width(), depth_camera.height(), color_camera.width(), color_camera.height(), num_scales));
   for (int p = 0; p < pairs; ++p)
     if ((*buffers)[p]->num_scales != num_scales) throw std::invalid_argument("TrackFramesPairwiseBatched: buffers built for another scale count");
-  const bslam_camera4f color_cam = color_camera.pod(), depth_cam = depth_camera.pod();
+  // --- input preparation and pyramids, as TrackFramePairwise does them (base once, in entry 0; each tracked frame once)
   PairwiseFrameTrackingBuffers& b0 = *(*buffers)[0];
-  // per scale: the base level (shared) and every pair's tracked level
-  std::vector<bslam_buffer2d> base_depth(num_scales), base_normals(num_scales), base_color(num_scales);
-  std::vector<std::vector<bslam_buffer2d>> tracked_depth(num_scales, std::vector<bslam_buffer2d>(pairs)), tracked_normals = tracked_depth,
-                                           tracked_color = tracked_depth;
-  for (int s = 0; s < num_scales; ++s) {
-    base_depth[s] = b0.base_depth[s]->ToPod();
-    base_color[s] = b0.base_color[s]->ToPod();
-    base_normals[s] = s ? b0.base_normals[s]->ToPod() : base_normals_l0.ToPod();
-    for (int p = 0; p < pairs; ++p) {
-      PairwiseFrameTrackingBuffers& bp = *(*buffers)[p];
-      tracked_depth[s][p] = bp.tracked_depth[s]->ToPod();
-      tracked_color[s][p] = bp.tracked_color[s]->ToPod();
-      tracked_normals[s][p] = s ? bp.tracked_normals[s]->ToPod() : tracked[p].normals->ToPod();
-    }
-  }
-  // --- input preparation and pyramids, as TrackFramePairwise does them (base once, each tracked frame once)
-  const bslam_buffer2d base_rgba = base_color_rgba.ToPod(), base_gm = b0.base_gradmag->ToPod(), base_d16 = base_depth_u16.ToPod();
-  Check(bslam_compute_brightness_from_color(ctx, stream, &base_rgba, &base_gm), "bslam_compute_brightness_from_color");
-  Check(bslam_calibrate_depth_and_transform_color_to_depth(ctx, stream, &color_cam, &depth_cam, &dp, &base_d16, &base_gm, &base_depth[0], &base_color[0]),
-        "bslam_calibrate_depth_and_transform_color_to_depth");
-  for (int s = 1; s < num_scales; ++s)
-    Check(bslam_downsample_images(ctx, stream, &base_depth[s - 1], &base_normals[s - 1], &base_color[s - 1], &base_depth[s], &base_normals[s], &base_color[s]),
-          "bslam_downsample_images");
+  const LevelPods base = Pods(b0, true, base_normals_l0);
+  PrepareBase(ctx, stream, false, color_camera.pod(), depth_camera.pod(), dp, base_depth_u16, base_color_rgba, b0.base_gradmag->ToPod(), base);
+  std::vector<LevelPods> tracked_pods;
   for (int p = 0; p < pairs; ++p) {
-    const bslam_buffer2d rgba = tracked[p].color->ToPod(), gm = (*buffers)[p]->tracked_gradmag->ToPod(), d16 = tracked[p].depth->ToPod();
-    Check(bslam_compute_brightness_from_color(ctx, stream, &rgba, &gm), "bslam_compute_brightness_from_color");
-    Check(bslam_calibrate_depth(ctx, stream, &dp, &d16, &tracked_depth[0][p]), "bslam_calibrate_depth");
-    Check(bslam_set_to_read_mode_normalized(ctx, stream, &gm, &tracked_color[0][p]), "bslam_set_to_read_mode_normalized");
-    for (int s = 1; s < num_scales; ++s)
-      Check(bslam_downsample_images(ctx, stream, &tracked_depth[s - 1][p], &tracked_normals[s - 1][p], &tracked_color[s - 1][p], &tracked_depth[s][p],
-                                    &tracked_normals[s][p], &tracked_color[s][p]),
-            "bslam_downsample_images");
+    tracked_pods.push_back(Pods(*(*buffers)[p], false, *tracked[p].normals));
+    PrepareTracked(ctx, stream, false, true, false, dp, *tracked[p].depth, *tracked[p].normals, *tracked[p].color, (*buffers)[p]->tracked_gradmag->ToPod(),
+                   tracked_pods[p]);
   }
   // --- coarse to fine in lockstep (TrackFramePairwise's loop per pair)
-  constexpr int kMaxIterationsPerScale = 30;
   std::vector<SE3f> estimate = inits;
   iterations_per_scale->assign(pairs, std::vector<int>(num_scales, 0));
   for (int scale = num_scales - 1; scale >= 0; --scale) {
@@ -212,20 +204,15 @@ void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vec
         for (int i = 0; i < 2; ++i) {
           const bslam_mat3x4 M = cand[i].Inverse().Matrix3x4();
           Check(bslam_compute_cost_and_residual_count_from_images(ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx,
-                                                                  threshold_factor, &tracked_depth[scale][p], &tracked_normals[scale][p],
-                                                                  &tracked_color[scale][p], &M, &base_depth[scale], &base_normals[scale], &base_color[scale],
+                                                                  threshold_factor, &tracked_pods[p].depth[scale], &tracked_pods[p].normals[scale],
+                                                                  &tracked_pods[p].color[scale], &M, &base.depth[scale], &base.normals[scale], &base.color[scale],
                                                                   &count[i], &cost[i]),
                 "bslam_compute_cost_and_residual_count_from_images");
         }
-        if (count[0] > 2 * count[1]) estimate[p] = cand[0];
-        else if (count[1] > 2 * count[0]) estimate[p] = cand[1];
-        else if (cost[0] < cost[1]) estimate[p] = cand[0];
-        else estimate[p] = cand[1];
+        estimate[p] = cand[BetterOf(count[0], cost[0], count[1], cost[1]) ? 0 : 1];
       }
     }
-    float damping = 1.f;   // :573-579
-    if (scale == num_scales - 2) damping = 0.5f;
-    else if (scale == num_scales - 1) damping = 0.25f;
+    const float damping = Damping(scale, num_scales);
     std::vector<int> active(pairs);
     for (int p = 0; p < pairs; ++p) active[p] = p;
     while (!active.empty()) {
@@ -234,13 +221,13 @@ void TrackFramesPairwiseBatched(bslam_context* ctx, hipStream_t stream, std::vec
       std::vector<bslam_mat3x4> M(n);
       for (int i = 0; i < n; ++i) {
         const int p = active[i];
-        td[i] = tracked_depth[scale][p]; tn[i] = tracked_normals[scale][p]; tc[i] = tracked_color[scale][p];
+        td[i] = tracked_pods[p].depth[scale]; tn[i] = tracked_pods[p].normals[scale]; tc[i] = tracked_pods[p].color[scale];
         M[i] = estimate[p].Inverse().Matrix3x4();
       }
       std::vector<float> H(21 * static_cast<size_t>(n)), b(6 * static_cast<size_t>(n));
       Check(bslam_accumulate_pose_coeffs_from_images_batched(ctx, stream, use_depth_residuals, use_descriptor_residuals, &tcc, &tdc, dp.baseline_fx,
-                                                              threshold_factor, n, td.data(), tn.data(), tc.data(), M.data(), &base_depth[scale],
-                                                              &base_normals[scale], &base_color[scale], nullptr, H.data(), b.data()),
+                                                              threshold_factor, n, td.data(), tn.data(), tc.data(), M.data(), &base.depth[scale],
+                                                              &base.normals[scale], &base.color[scale], nullptr, H.data(), b.data()),
             "bslam_accumulate_pose_coeffs_from_images_batched");
       std::vector<int> still;
       for (int i = 0; i < n; ++i) {

@@ -1,7 +1,7 @@
 """-m gpu: the luma quad table as fp16 differences (C-ABI probe bslam_debug_quad_samples).
 
-(a) The table the production kernels build -- build_quads_kernel for keyframe colour, build_quads_u8_kernel and
-    build_quads_u8_batched_kernel for the odometry's u8 images -- equals the numpy table (tests/quad_table.py) bit for bit at every
+(a) The table the production kernels build -- build_quads_kernel for keyframe colour, build_quads_u8_batched_kernel
+    for the odometry's u8 images (one image and several) -- equals the numpy table (tests/quad_table.py) bit for bit at every
     (i, j) in [-1, w - 1] x [-1, h - 1], clamp rows and columns included.
 (b) A sample through the table (one 8-byte gather, conversions only) and a sample from four byte loads with the differences
     formed per sample in integers give the same bits in val, gx, gy, in both texture modes.  No tolerance: every operand of

@@ -17,7 +17,13 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-ffp
 
 
 def sources():
+    """The translation unit of the project's kernels (what tools/kernel_regs.py and tools/isa_stats.py look at)."""
     return [os.path.join(CSRC, "badslam_hip.hip")]
+
+
+def library_sources():
+    """... and the ones that only wrap a rocPRIM call, kept apart so that they leave the device code of the first alone."""
+    return sources() + [os.path.join(CSRC, "simplify_sort.hip")]
 
 
 def needs_build():
@@ -45,7 +51,7 @@ def needs_host_build():
 
 def build(force=False, verbose=False):
     if force or needs_build():
-        cmd = [HIPCC] + FLAGS + sources() + ["-o", SO]
+        cmd = [HIPCC] + FLAGS + library_sources() + ["-o", SO]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
         subprocess.run(cmd, check=True)

@@ -24,6 +24,7 @@
 #include "distance_kernels.hpp"
 #include "registration_kernels.hpp"
 #include "sampling_kernels.hpp"
+#include "simplify_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1454,6 +1455,7 @@ int bslam_debug_pose_residuals(
 #include "render_abi.inc"
 #include "fusion_abi.inc"
 #include "mesh_abi.inc"
+#include "simplify_abi.inc"
 #include "distance_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"

@@ -173,6 +173,11 @@ struct bslam_context {
     void *records = nullptr, *cell_count = nullptr, *cell_start = nullptr, *list = nullptr;
   } prepared;
   bslam::Slab sampling;      // bslam_sample_mesh: words | counts u32[T] | offsets u32[T] | scan sums; reserved by its first call
+  bslam::Slab simplify;      // bslam_simplify_mesh: words | keys, sorted keys u64[V] | ids, sorted ids, head flags, ranks, clusters [V] | keep flags, ranks [T] |
+                             // scan sums | the radix sort's scratch; reserved by its first call
+  // bslam_simplify_mesh while profiling is on: events around its five stages and the last call's times (bslam_simplify_stage_times)
+  hipEvent_t simplify_events[6] = {};
+  float simplify_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;
@@ -213,6 +218,7 @@ struct bslam_context {
   ~bslam_context() {
     for (hipEvent_t e : iter_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+    for (hipEvent_t e : simplify_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     if (perm_ready) { hipError_t err = hipEventDestroy(perm_ready); (void)err; }
     if (copy_stream) { hipError_t err = hipStreamDestroy(copy_stream); (void)err; }
     for (const ProfEntry& p : prof_pending) { hipError_t err = hipEventDestroy(p.start); err = hipEventDestroy(p.stop); (void)err; }

@@ -88,6 +88,8 @@ def host_lib():
                                           f32p, u64p]
     L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
     L.bsh_distance_copy.argtypes = [f32p, u32p]
+    L.bsh_simplify_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, f32p, C.c_float, u64p]
+    L.bsh_simplified_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
     L.bsh_sample_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_uint32, u64p]
     L.bsh_samples_copy.argtypes = [f32p, f32p, u32p]
     f64p = C.POINTER(C.c_double)
@@ -737,6 +739,46 @@ class DirectBA:
         self._check(self.L.bsh_mesh_components(self._ba, self.stream, V, len(tri), _u32(tri), _u32(labels), _u32(sizes),
                                                C.byref(n)))
         return labels, sizes
+
+    # --- mesh simplification (bslam_simplify_mesh)
+    def SimplifyMesh(self, mesh, cell_size, origin=None):
+        """Vertex clustering of `mesh` (the dict of ExtractMesh or LoadPLY) on a uniform grid of cells of cell_size: all vertices of a
+        cell become one vertex (the mean position, the normalised sum of the normals, the rounded mean colour), triangles are remapped
+        and those whose corners no longer differ are dropped.  -> dict with the keys of ExtractMesh (normals / colors None where the
+        input has none, colors with the input's channel count) plus vertex_cluster (V,) u32, the new vertex of every input vertex.
+        New vertices are ordered by cell (z, then y, then x); kept triangles keep their order and orientation.  origin (3,): the
+        grid's corner, default the per-axis minimum of the positions; every vertex has to lie at or above it and within 2^21 cells.
+        A mesh without triangles is a point cloud: voxel-grid down-sampling."""
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        nrm, col, tri = mesh.get("normals"), mesh.get("colors"), mesh.get("triangles")
+        if nrm is not None:
+            nrm = np.ascontiguousarray(nrm, np.float32).reshape(-1, 3)
+        channels = 4
+        if col is not None:
+            col = np.ascontiguousarray(col, np.uint8).reshape(len(pos), -1)
+            channels = col.shape[1]
+            if channels == 3:
+                col = np.concatenate([col, np.full((len(col), 1), 255, np.uint8)], axis=1)
+            if col.shape[1] != 4:
+                raise ValueError("SimplifyMesh: colors need 3 or 4 channels")
+            col = np.ascontiguousarray(col)
+        if nrm is not None and len(nrm) != len(pos):
+            raise ValueError("SimplifyMesh: normals need one row per vertex")
+        tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        if origin is None:
+            origin = pos.min(axis=0) if len(pos) else np.zeros(3, np.float32)
+        o = np.ascontiguousarray(origin, np.float32).reshape(3)
+        counts = (C.c_uint64 * 2)()
+        self._check(self.L.bsh_simplify_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), None if col is None else _u8(col),
+                                             len(tri), _u32(tri), _f(o), float(cell_size), counts))
+        V, T = int(counts[0]), int(counts[1])
+        out = dict(positions=np.zeros((V, 3), np.float32), normals=None if nrm is None else np.zeros((V, 3), np.float32),
+                   colors=None if col is None else np.zeros((V, 4), np.uint8), triangles=np.zeros((T, 3), np.uint32), vertex_cluster=np.zeros(len(pos), np.uint32))
+        self._check(self.L.bsh_simplified_copy(_f(out["positions"]), None if nrm is None else _f(out["normals"]), None if col is None else _u8(out["colors"]),
+                                               _u32(out["triangles"]), _u32(out["vertex_cluster"])))
+        if col is not None and channels == 3:
+            out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
+        return out
 
     # --- surface evaluation (bslam_point_mesh_distance)
     @staticmethod

@@ -274,6 +274,41 @@ int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* i
     g_mesh = DirectBA::Mesh();
   });
 }
+// DirectBA::SimplifyMesh of host arrays in two steps, like the mesh: bsh_simplify_mesh (normals, colors -- 4 bytes per vertex --
+// and indices may be null; origin3: x y z) keeps the result for this thread and reports counts2 = {vertices, triangles};
+// bsh_simplified_copy copies it out (normals and colors only where the input had them; vertex_cluster: one entry per input vertex;
+// any pointer may be null) and drops it.
+static thread_local DirectBA::Mesh g_simplified;
+static thread_local std::vector<uint32_t> g_simplified_cluster;
+int bsh_simplify_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles,
+                      const uint32_t* indices, const float* origin3, float cell_size, uint64_t* counts2) {
+  BSH_TRY({
+    g_simplified = DirectBA::Mesh();
+    g_simplified_cluster.clear();
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
+    if (colors) {
+      mesh.colors.resize(vertices);
+      std::memcpy(mesh.colors.data(), colors, 4 * vertices);
+    }
+    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    static_cast<DirectBA*>(ba)->SimplifyMesh(static_cast<hipStream_t>(stream), mesh, origin3, cell_size, &g_simplified, &g_simplified_cluster);
+    counts2[0] = g_simplified.vertex_count();
+    counts2[1] = g_simplified.triangle_count();
+  });
+}
+int bsh_simplified_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices, uint32_t* vertex_cluster) {
+  BSH_TRY({
+    copy_out(positions, g_simplified.positions);
+    copy_out(normals, g_simplified.normals);
+    copy_out(colors, g_simplified.colors);
+    copy_out(indices, g_simplified.indices);
+    copy_out(vertex_cluster, g_simplified_cluster);
+    g_simplified = DirectBA::Mesh();
+    g_simplified_cluster = std::vector<uint32_t>();
+  });
+}
 // DirectBA::PointMeshDistance of host arrays: points 3 per point, positions 3 per vertex, indices 3 per triangle; distance and
 // triangle receive `points_count` entries; *cell_used the grid cell of the call that succeeded, grid2 = {cells, entries}.
 static void grid_out(const DirectBA::PointMeshResult& result, float* cell_used, uint64_t* grid2) {

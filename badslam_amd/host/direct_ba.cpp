@@ -830,6 +830,53 @@ u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u
   return components;
 }
 
+DirectBA::DeviceSimplifiedMesh DirectBA::SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
+                                                              const uchar4_t* colors, const u32* indices, const float origin[3], float cell_size) {
+  DeviceSimplifiedMesh s;
+  s.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (normals) s.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (colors) s.colors.reset(new DeviceArray<uchar4_t>(vertices));
+  s.indices.reset(new DeviceArray<u32>(size_t{3} * triangles));
+  s.vertex_cluster.reset(new DeviceArray<u32>(vertices));
+  Check(bslam_simplify_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, origin, cell_size, s.positions->address(),
+                            s.normals ? s.normals->address() : nullptr, s.colors ? s.colors->address() : nullptr, s.indices->address(), s.vertex_cluster->address(),
+                            &s.vertices, &s.triangles),
+        "bslam_simplify_mesh");
+  return s;
+}
+
+void DirectBA::SimplifyMesh(hipStream_t stream, const Mesh& mesh, const float origin[3], float cell_size, Mesh* out, std::vector<u32>* vertex_cluster) {
+  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
+    throw std::invalid_argument("SimplifyMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
+    throw std::invalid_argument("SimplifyMesh: normals and colors need one entry per vertex, or none");
+  const bool has_normals = !mesh.normals.empty(), has_colors = !mesh.colors.empty();
+  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
+  DeviceArray<uchar4_t> dev_colors(mesh.colors.size());
+  DeviceArray<u32> dev_indices(3 * T);
+  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
+  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
+  dev_colors.Upload(stream, mesh.colors.data(), mesh.colors.size());
+  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
+  Wait(stream);   // the host arrays are the caller's and pageable
+  const DeviceSimplifiedMesh s = SimplifyMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
+                                                      has_colors ? dev_colors.address() : nullptr, dev_indices.address(), origin, cell_size);
+  out->positions.resize(3 * static_cast<size_t>(s.vertices));
+  out->normals.resize(has_normals ? 3 * static_cast<size_t>(s.vertices) : 0);
+  out->colors.resize(has_colors ? s.vertices : 0);
+  out->indices.resize(3 * static_cast<size_t>(s.triangles));
+  s.positions->Download(stream, out->positions.data(), out->positions.size());
+  if (has_normals) s.normals->Download(stream, out->normals.data(), out->normals.size());
+  if (has_colors) s.colors->Download(stream, out->colors.data(), out->colors.size());
+  s.indices->Download(stream, out->indices.data(), out->indices.size());
+  if (vertex_cluster) {
+    vertex_cluster->resize(V);
+    s.vertex_cluster->Download(stream, vertex_cluster->data(), V);
+  }
+  Wait(stream);
+}
+
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
   const FusedVolume v = Fused("RenderVolume");
   const int w = camera.width(), h = camera.height();

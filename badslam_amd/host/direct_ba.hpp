@@ -294,6 +294,24 @@ class DirectBA {
   // Components of a caller's mesh: labels[v] = the smallest vertex id of v's component, sizes[v] = its vertex count (either may
   // be null).  Returns the number of components.
   u32 MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u32>* labels, std::vector<u32>* sizes);
+  // Mesh simplification (bslam_simplify_mesh): vertex clustering on the uniform grid of cells of cell_size from origin.  All
+  // vertices of a cell become one -- the mean position, the normalised normal sum, the rounded mean colour, each over the members
+  // in ascending vertex id --, clusters are numbered in ascending (c_z, c_y, c_x), triangles are remapped and kept iff their three
+  // clusters differ.  A mesh without triangles is a point cloud: voxel-grid down-sampling.  Every vertex has to lie at or above
+  // origin and within 2^21 cells of it on every axis.
+  struct DeviceSimplifiedMesh {   // on the device, with room for the input's counts; vertices and triangles are the counts in use
+    std::unique_ptr<DeviceArray<float>> positions, normals;   // normals, colors: null when the input has none
+    std::unique_ptr<DeviceArray<uchar4_t>> colors;
+    std::unique_ptr<DeviceArray<u32>> indices, vertex_cluster;   // vertex_cluster: one entry per input vertex
+    u32 vertices = 0, triangles = 0;
+  };
+  // Host arrays: mesh.normals and mesh.colors may be empty, and so may mesh.indices; *out gets what the input has.  vertex_cluster
+  // (may be null) receives the cluster of every input vertex.
+  void SimplifyMesh(hipStream_t stream, const Mesh& mesh, const float origin[3], float cell_size, Mesh* out, std::vector<u32>* vertex_cluster);
+  // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_simplify_mesh); the result stays on the
+  // device.
+  DeviceSimplifiedMesh SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                            const u32* indices, const float origin[3], float cell_size);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.

@@ -695,6 +695,47 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, u
                       float* out_positions, float* out_normals, void* out_colors, uint32_t* out_indices, uint32_t* out_vertex_count,
                       uint32_t* out_triangle_count);
 
+/* Mesh simplification: vertex clustering on a uniform grid (DESIGN.md 8 "Mesh simplification", csrc/simplify_kernels.hpp).  All
+ * vertices of a grid cell become one vertex, triangles are remapped and those that collapse are dropped.  With T == 0 it is
+ * voxel-grid down-sampling of a point cloud.  Nothing is contracted implicitly.
+ * Cell:
+ *   inv = 1.0f / cell_size, once, in fp32;  c_a = floorf((x_a - origin_a) * inv) per axis, the subtraction and the multiplication
+ *   separate fp32 operations (the cell of "Surface evaluation").  A vertex is valid iff its three coordinates are finite and
+ *   0 <= c_a < 2^21 on every axis.  -0.0f and values exactly on a cell face follow from the formula; there is no epsilon.
+ * Clusters:
+ *   Vertices with equal (c_x, c_y, c_z) form a cluster, referenced by a triangle or not; clusters are numbered 0 .. C - 1 in
+ *   ascending (c_z, c_y, c_x) order; vertex_cluster[v] is the cluster of vertex v.
+ * Representative of a cluster of n members; every sum runs over the members in ascending vertex id:
+ *   position.a = (float)(sum_a / (double)n), sum_a a double sum that starts from the first member (a cluster of one keeps its
+ *     bits, the sign of a zero included);
+ *   normal.a = (float)(s_a / sqrt(ss)), s_a a double sum, ss = (s_x * s_x + s_y * s_y) + s_z * s_z in double; (0, 0, 0) when ss is
+ *     not > 0 or a member's normal is not finite;
+ *   colour, per channel, alpha included: (S + n / 2) / n in integers, S a 64-bit sum (the rounding of the fusion colours).
+ * Triangles:
+ *   Triangle t becomes (cluster[i0], cluster[i1], cluster[i2]) in that order and is kept iff the three are pairwise distinct;
+ *   kept triangles keep their relative order.  Duplicate triangles are not removed.
+ * bslam_simplify_mesh: positions float[3 V], normals float[3 V] (may be null), colors uchar4[V] (may be null), indices uint32[3 T]
+ * and the outputs of the same shapes (room for V vertices and T triangles; out_normals and out_colors exactly when their inputs
+ * are given) and vertex_cluster uint32[V] (may be null) are device arrays; origin float[3] is a host array.  *out_vertex_count = C
+ * and *out_triangle_count are returned on the host; nothing at or beyond them is written.  V == 0 is legal with T == 0, and T == 0
+ * is a point cloud.  Refused without a launch: null required arguments, an origin that is not finite, a cell_size that is not
+ * finite and > 0 or whose reciprocal is not, an out_normals / out_colors that does not match its input, more than 2^32 - 256
+ * vertices or triangles, misaligned (4 byte) pointers, an output that overlaps an input or another output.  Refused behind the
+ * launches, by a device error bit, with BSLAM_ERR_INVALID_ARGUMENT and unspecified output contents: an index >= V (never
+ * dereferenced; the message of the mesh component calls) and an invalid vertex ("a vertex is not finite or lies outside the grid";
+ * no attribute is gathered through it).  A key pass, a stable radix sort of (cell key, vertex id), head flags and their scan, a
+ * cluster pass with one lane per cluster walking its members, and a keep-flag / scan / scatter triangle pass; one read-back.
+ * Scratch lives in a context slab of its own that the first call reserves.  Synchronises `stream`.  Every rank of a
+ * surfel-sharded run holds the same mesh and computes the same result; nothing is exchanged. */
+int bslam_simplify_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                        const float* normals, const void* colors, const uint32_t* indices, const float* origin, float cell_size,
+                        float* out_positions, float* out_normals, void* out_colors, uint32_t* out_indices, uint32_t* vertex_cluster,
+                        uint32_t* out_vertex_count, uint32_t* out_triangle_count);
+/* The device time in milliseconds of the five stages of the last bslam_simplify_mesh on `ctx` that ran its launches while
+ * bslam_profile_enable was on (HOST out): {key pass, sort, head flags and their scan, cluster pass, triangle pass}, taken from
+ * events on the call's stream.  Zeros before such a call.  For tools/bench_simplify_mesh.py. */
+int bslam_simplify_stage_times(bslam_context* ctx, float* stage_ms5);
+
 /* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
  * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
  * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components

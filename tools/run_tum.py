@@ -10,6 +10,7 @@ has a ground truth, prints the ATE RMSE.
                             [--render-source {surfels,volume}]
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
+                            [--mesh-simplify-cell M]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
                             [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
@@ -42,6 +43,10 @@ size up to --max-depth.  The directory has the same layout.
 --mesh-min-component N: connected pieces of the surface with fewer than N vertices (flying pixels at occlusion edges, single noisy
 blobs) are removed on the GPU before the file is written (DirectBA.ExtractMesh(min_component_vertices=N)); default 0, off.  The
 summary line then names the pieces found and the vertices and triangles removed.
+--mesh-simplify-cell M: the mesh (after --mesh-min-component) is simplified by vertex clustering on a grid of M metres
+(DirectBA.SimplifyMesh: all vertices of a cell become their mean, collapsed triangles are dropped) without coarsening the volume
+itself; default off.  The simplified mesh is what is written and what --ground-truth-surface scores (--surfel-mesh-distance keeps
+measuring against the extracted one); the counts before and after are printed and reported.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 
@@ -175,7 +180,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
-        surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None):
+        surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
@@ -223,8 +228,16 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh or ground_truth_surface or surfel_mesh_distance:
-        m, origin, dims, report = fuse_and_mesh(slam.ba(), mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused, mesh_min_component)
-        surface = {}
+        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if mesh_simplify_cell else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
+                                                mesh_min_component)
+        surface, simplified = {}, None
+        if mesh_simplify_cell:
+            extracted = m
+            m = slam.ba().SimplifyMesh(extracted, float(mesh_simplify_cell))
+            simplified = {"cell": float(mesh_simplify_cell), "vertices_before": len(extracted["positions"]), "triangles_before": len(extracted["triangles"]),
+                          "vertices": len(m["positions"]), "triangles": len(m["triangles"])}
+            if mesh:
+                dba.SaveMeshAsPLY(mesh, m)
         if ground_truth_surface:
             surface["ground_truth"] = str(ground_truth_surface)
             start = None
@@ -239,6 +252,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
         if surface:
             surface["max_distance"] = float(surface_max_distance)
+            if simplified:
+                surface["mesh_simplification"] = simplified
             result["surface"] = surface
             if surface_report:
                 with open(surface_report, "w") as f:
@@ -247,6 +262,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
         if report is not None:
             result["mesh"].update(components=report["components"], removed_vertices=report["removed_vertices"], removed_triangles=report["removed_triangles"])
+        if simplified:
+            result["mesh"]["simplification"] = simplified
     if inspect:
         inspect(slam, result)
     if trajectory:
@@ -278,6 +295,7 @@ def arg_parser():
     ap.add_argument("--mesh-truncation", type=float, default=None)
     ap.add_argument("--mesh-min-count", type=int, default=1)
     ap.add_argument("--mesh-min-component", type=int, default=0)
+    ap.add_argument("--mesh-simplify-cell", type=float, default=None)
     ap.add_argument("--point-cloud", default=None)
     ap.add_argument("--ground-truth-surface", default=None)
     ap.add_argument("--surface-max-distance", type=float, default=0.1)
@@ -298,7 +316,8 @@ def main():
             mesh_voxel_size=a.mesh_voxel_size, mesh_truncation=a.mesh_truncation, mesh_min_count=a.mesh_min_count, point_cloud=a.point_cloud,
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
-            surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing)
+            surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
+            mesh_simplify_cell=a.mesh_simplify_cell)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -315,9 +334,15 @@ def main():
         if "components" in r["mesh"]:
             cleaned = (f" ({r['mesh']['components']} components before clean-up, {r['mesh']['removed_vertices']} vertices and "
                        f"{r['mesh']['removed_triangles']} triangles removed)")
+        if "simplification" in r["mesh"]:
+            sp = r["mesh"]["simplification"]
+            cleaned += f" (simplified at {sp['cell']:g} m from {sp['vertices_before']} vertices, {sp['triangles_before']} triangles)"
         print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
     if "surface" in r:
         sf = r["surface"]
+        if "mesh_simplification" in sf and "mesh" not in r:
+            sp = sf["mesh_simplification"]
+            print(f"mesh simplified at {sp['cell']:g} m: {sp['vertices_before']} vertices, {sp['triangles_before']} triangles -> {sp['vertices']}, {sp['triangles']}")
         if "registration" in sf:
             reg = sf["registration"]
             print(f"registration to the ground truth: {reg['reason']} after {reg['iterations']} steps; ground_truth_T_mesh =")

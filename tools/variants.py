@@ -25,7 +25,7 @@ def build(specs):
     for spec in specs:
         name, _, defs = spec.partition(":")
         flags = [d for d in defs.split(",") if d]
-        cmd = [b.HIPCC] + b.FLAGS + flags + b.sources() + ["-o", os.path.join(OUT, f"libbadslam_hip_{name}.so")]
+        cmd = [b.HIPCC] + b.FLAGS + flags + b.library_sources() + ["-o", os.path.join(OUT, f"libbadslam_hip_{name}.so")]
         procs.append((name, subprocess.Popen(cmd)))
     for name, p in procs:
         if p.wait() != 0:

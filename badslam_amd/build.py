@@ -23,7 +23,7 @@ def sources():
 
 def library_sources():
     """... and the ones that only wrap a rocPRIM call, kept apart so that they leave the device code of the first alone."""
-    return sources() + [os.path.join(CSRC, "simplify_sort.hip")]
+    return sources() + [os.path.join(CSRC, "simplify_sort.hip"), os.path.join(CSRC, "decimate_sort.hip")]
 
 
 def needs_build():

@@ -25,6 +25,7 @@
 #include "registration_kernels.hpp"
 #include "sampling_kernels.hpp"
 #include "simplify_kernels.hpp"
+#include "decimate_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1456,6 +1457,7 @@ int bslam_debug_pose_residuals(
 #include "fusion_abi.inc"
 #include "mesh_abi.inc"
 #include "simplify_abi.inc"
+#include "decimate_abi.inc"
 #include "distance_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"

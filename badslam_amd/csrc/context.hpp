@@ -178,6 +178,13 @@ struct bslam_context {
   // bslam_simplify_mesh while profiling is on: events around its five stages and the last call's times (bslam_simplify_stage_times)
   hipEvent_t simplify_events[6] = {};
   float simplify_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bslam::Slab decimate;      // bslam_decimate_mesh: words | working attributes, quadrics, parents [V] | two triangle buffers | per slot: keys, sorted keys, slots,
+                             // flags, ranks, candidate keys | per vertex: fans, flags, minima | scan sums | the radix sort's scratch; reserved by its first call
+  // bslam_decimate_mesh while profiling is on: events around the seven stages of a round and their sums over the last call's rounds
+  // (bslam_decimate_stage_times); the collapses of every round of the last call (bslam_decimate_round_collapses)
+  hipEvent_t decimate_events[8] = {};
+  float decimate_stage_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  std::vector<uint32_t> decimate_collapses;
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;
@@ -219,6 +226,7 @@ struct bslam_context {
     for (hipEvent_t e : iter_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : simplify_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+    for (hipEvent_t e : decimate_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     if (perm_ready) { hipError_t err = hipEventDestroy(perm_ready); (void)err; }
     if (copy_stream) { hipError_t err = hipStreamDestroy(copy_stream); (void)err; }
     for (const ProfEntry& p : prof_pending) { hipError_t err = hipEventDestroy(p.start); err = hipEventDestroy(p.stop); (void)err; }

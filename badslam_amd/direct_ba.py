@@ -90,6 +90,8 @@ def host_lib():
     L.bsh_distance_copy.argtypes = [f32p, u32p]
     L.bsh_simplify_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, f32p, C.c_float, u64p]
     L.bsh_simplified_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
+    L.bsh_decimate_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
+    L.bsh_decimated_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
     L.bsh_sample_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_uint32, u64p]
     L.bsh_samples_copy.argtypes = [f32p, f32p, u32p]
     f64p = C.POINTER(C.c_double)
@@ -740,15 +742,10 @@ class DirectBA:
                                                C.byref(n)))
         return labels, sizes
 
-    # --- mesh simplification (bslam_simplify_mesh)
-    def SimplifyMesh(self, mesh, cell_size, origin=None):
-        """Vertex clustering of `mesh` (the dict of ExtractMesh or LoadPLY) on a uniform grid of cells of cell_size: all vertices of a
-        cell become one vertex (the mean position, the normalised sum of the normals, the rounded mean colour), triangles are remapped
-        and those whose corners no longer differ are dropped.  -> dict with the keys of ExtractMesh (normals / colors None where the
-        input has none, colors with the input's channel count) plus vertex_cluster (V,) u32, the new vertex of every input vertex.
-        New vertices are ordered by cell (z, then y, then x); kept triangles keep their order and orientation.  origin (3,): the
-        grid's corner, default the per-axis minimum of the positions; every vertex has to lie at or above it and within 2^21 cells.
-        A mesh without triangles is a point cloud: voxel-grid down-sampling."""
+    @staticmethod
+    def _mesh_arrays(mesh, who):
+        """(positions (V, 3) f32, normals or None, colors (V, 4) u8 or None, triangles (T, 3) u32, the input's colour channels) of an
+        ExtractMesh or LoadPLY dict; three colour channels get an alpha of 255."""
         pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
         nrm, col, tri = mesh.get("normals"), mesh.get("colors"), mesh.get("triangles")
         if nrm is not None:
@@ -760,11 +757,55 @@ class DirectBA:
             if channels == 3:
                 col = np.concatenate([col, np.full((len(col), 1), 255, np.uint8)], axis=1)
             if col.shape[1] != 4:
-                raise ValueError("SimplifyMesh: colors need 3 or 4 channels")
+                raise ValueError(f"{who}: colors need 3 or 4 channels")
             col = np.ascontiguousarray(col)
         if nrm is not None and len(nrm) != len(pos):
-            raise ValueError("SimplifyMesh: normals need one row per vertex")
+            raise ValueError(f"{who}: normals need one row per vertex")
         tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        return pos, nrm, col, tri, channels
+
+    # --- mesh decimation (bslam_decimate_mesh)
+    def DecimateMesh(self, mesh, target_vertices=None, ratio=None, boundary_weight=1.0, max_cost=None, max_rounds=0):
+        """Quadric-error edge collapse of `mesh` (the dict of ExtractMesh or LoadPLY) down to target_vertices, or to
+        ceil(ratio * V) of its V vertices; exactly one of the two is given.  Rounds of pairwise non-adjacent collapses, each to the
+        cheaper end or the midpoint of its edge, run until the target is met, no edge may collapse any more or max_rounds (0: no limit)
+        have run.  boundary_weight (>= 0) holds open boundaries in place, max_cost (None: no bound) refuses dearer collapses.  -> dict
+        with the keys of ExtractMesh (normals / colors None where the input has none, colors with the input's channel count) plus
+        vertex_map (V,) u32, the output vertex of every input vertex, and rounds.  Survivors keep their relative order, and so do the
+        triangles."""
+        if (target_vertices is None) == (ratio is None):
+            raise ValueError("DecimateMesh: give exactly one of target_vertices and ratio")
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "DecimateMesh")
+        if ratio is not None:
+            if not 0.0 <= float(ratio) <= 1.0:
+                raise ValueError("DecimateMesh: ratio must lie in [0, 1]")
+            target_vertices = int(np.ceil(float(ratio) * len(pos)))
+        if not 0 <= int(target_vertices) <= 0xFFFFFFFF or not 0 <= int(max_rounds) <= 0xFFFFFFFF:
+            raise ValueError("DecimateMesh: target_vertices and max_rounds must fit 32 bits")
+        counts = (C.c_uint64 * 3)()
+        self._check(self.L.bsh_decimate_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), None if col is None else _u8(col),
+                                             len(tri), _u32(tri), int(target_vertices), float(boundary_weight), float("inf") if max_cost is None else float(max_cost),
+                                             int(max_rounds), counts))
+        V, T = int(counts[0]), int(counts[1])
+        out = dict(positions=np.zeros((V, 3), np.float32), normals=None if nrm is None else np.zeros((V, 3), np.float32),
+                   colors=None if col is None else np.zeros((V, 4), np.uint8), triangles=np.zeros((T, 3), np.uint32), vertex_map=np.zeros(len(pos), np.uint32),
+                   rounds=int(counts[2]))
+        self._check(self.L.bsh_decimated_copy(_f(out["positions"]), None if nrm is None else _f(out["normals"]), None if col is None else _u8(out["colors"]),
+                                              _u32(out["triangles"]), _u32(out["vertex_map"])))
+        if col is not None and channels == 3:
+            out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
+        return out
+
+    # --- mesh simplification (bslam_simplify_mesh)
+    def SimplifyMesh(self, mesh, cell_size, origin=None):
+        """Vertex clustering of `mesh` (the dict of ExtractMesh or LoadPLY) on a uniform grid of cells of cell_size: all vertices of a
+        cell become one vertex (the mean position, the normalised sum of the normals, the rounded mean colour), triangles are remapped
+        and those whose corners no longer differ are dropped.  -> dict with the keys of ExtractMesh (normals / colors None where the
+        input has none, colors with the input's channel count) plus vertex_cluster (V,) u32, the new vertex of every input vertex.
+        New vertices are ordered by cell (z, then y, then x); kept triangles keep their order and orientation.  origin (3,): the
+        grid's corner, default the per-axis minimum of the positions; every vertex has to lie at or above it and within 2^21 cells.
+        A mesh without triangles is a point cloud: voxel-grid down-sampling."""
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "SimplifyMesh")
         if origin is None:
             origin = pos.min(axis=0) if len(pos) else np.zeros(3, np.float32)
         o = np.ascontiguousarray(origin, np.float32).reshape(3)

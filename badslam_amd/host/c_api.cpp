@@ -309,6 +309,45 @@ int bsh_simplified_copy(float* positions, float* normals, uint8_t* colors, uint3
     g_simplified_cluster = std::vector<uint32_t>();
   });
 }
+// DirectBA::DecimateMesh of host arrays in the same two steps: bsh_decimate_mesh keeps the result for this thread and reports
+// counts3 = {vertices, triangles, rounds}; bsh_decimated_copy copies it out (vertex_map: one entry per input vertex; any pointer may
+// be null) and drops it.
+static thread_local DirectBA::Mesh g_decimated;
+static thread_local std::vector<uint32_t> g_decimated_map;
+int bsh_decimate_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles,
+                      const uint32_t* indices, uint32_t target_vertices, float boundary_weight, float max_cost, uint32_t max_rounds, uint64_t* counts3) {
+  BSH_TRY({
+    g_decimated = DirectBA::Mesh();
+    g_decimated_map.clear();
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
+    if (colors) {
+      mesh.colors.resize(vertices);
+      std::memcpy(mesh.colors.data(), colors, 4 * vertices);
+    }
+    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::DecimateOptions options;
+    options.target_vertices = target_vertices;
+    options.boundary_weight = boundary_weight;
+    options.max_cost = max_cost;
+    options.max_rounds = max_rounds;
+    counts3[2] = static_cast<DirectBA*>(ba)->DecimateMesh(static_cast<hipStream_t>(stream), mesh, options, &g_decimated, &g_decimated_map);
+    counts3[0] = g_decimated.vertex_count();
+    counts3[1] = g_decimated.triangle_count();
+  });
+}
+int bsh_decimated_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices, uint32_t* vertex_map) {
+  BSH_TRY({
+    copy_out(positions, g_decimated.positions);
+    copy_out(normals, g_decimated.normals);
+    copy_out(colors, g_decimated.colors);
+    copy_out(indices, g_decimated.indices);
+    copy_out(vertex_map, g_decimated_map);
+    g_decimated = DirectBA::Mesh();
+    g_decimated_map = std::vector<uint32_t>();
+  });
+}
 // DirectBA::PointMeshDistance of host arrays: points 3 per point, positions 3 per vertex, indices 3 per triangle; distance and
 // triangle receive `points_count` entries; *cell_used the grid cell of the call that succeeded, grid2 = {cells, entries}.
 static void grid_out(const DirectBA::PointMeshResult& result, float* cell_used, uint64_t* grid2) {

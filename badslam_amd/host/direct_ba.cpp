@@ -877,6 +877,54 @@ void DirectBA::SimplifyMesh(hipStream_t stream, const Mesh& mesh, const float or
   Wait(stream);
 }
 
+DirectBA::DeviceDecimatedMesh DirectBA::DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
+                                                             const uchar4_t* colors, const u32* indices, const DecimateOptions& options) {
+  DeviceDecimatedMesh d;
+  d.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (normals) d.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (colors) d.colors.reset(new DeviceArray<uchar4_t>(vertices));
+  d.indices.reset(new DeviceArray<u32>(size_t{3} * triangles));
+  d.vertex_map.reset(new DeviceArray<u32>(vertices));
+  Check(bslam_decimate_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, options.target_vertices, options.boundary_weight, options.max_cost,
+                            options.max_rounds, d.positions->address(), d.normals ? d.normals->address() : nullptr, d.colors ? d.colors->address() : nullptr,
+                            d.indices->address(), d.vertex_map->address(), &d.vertices, &d.triangles, &d.rounds),
+        "bslam_decimate_mesh");
+  return d;
+}
+
+u32 DirectBA::DecimateMesh(hipStream_t stream, const Mesh& mesh, const DecimateOptions& options, Mesh* out, std::vector<u32>* vertex_map) {
+  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
+    throw std::invalid_argument("DecimateMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
+    throw std::invalid_argument("DecimateMesh: normals and colors need one entry per vertex, or none");
+  const bool has_normals = !mesh.normals.empty(), has_colors = !mesh.colors.empty();
+  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
+  DeviceArray<uchar4_t> dev_colors(mesh.colors.size());
+  DeviceArray<u32> dev_indices(3 * T);
+  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
+  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
+  dev_colors.Upload(stream, mesh.colors.data(), mesh.colors.size());
+  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
+  Wait(stream);   // the host arrays are the caller's and pageable
+  const DeviceDecimatedMesh d = DecimateMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
+                                                     has_colors ? dev_colors.address() : nullptr, dev_indices.address(), options);
+  out->positions.resize(3 * static_cast<size_t>(d.vertices));
+  out->normals.resize(has_normals ? 3 * static_cast<size_t>(d.vertices) : 0);
+  out->colors.resize(has_colors ? d.vertices : 0);
+  out->indices.resize(3 * static_cast<size_t>(d.triangles));
+  d.positions->Download(stream, out->positions.data(), out->positions.size());
+  if (has_normals) d.normals->Download(stream, out->normals.data(), out->normals.size());
+  if (has_colors) d.colors->Download(stream, out->colors.data(), out->colors.size());
+  d.indices->Download(stream, out->indices.data(), out->indices.size());
+  if (vertex_map) {
+    vertex_map->resize(V);
+    d.vertex_map->Download(stream, vertex_map->data(), V);
+  }
+  Wait(stream);
+  return d.rounds;
+}
+
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
   const FusedVolume v = Fused("RenderVolume");
   const int w = camera.width(), h = camera.height();

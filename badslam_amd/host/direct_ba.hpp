@@ -18,6 +18,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <ostream>
@@ -312,6 +313,27 @@ class DirectBA {
   // device.
   DeviceSimplifiedMesh SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
                                             const u32* indices, const float origin[3], float cell_size);
+  // Mesh decimation (bslam_decimate_mesh): quadric-error edge collapse in rounds of pairwise non-adjacent collapses until
+  // target_vertices are left, no edge may collapse any more or max_rounds (0: no limit) have run.  Boundary edges are held by a
+  // quadric of weight boundary_weight; an edge whose cost exceeds max_cost never collapses.
+  struct DecimateOptions {
+    u32 target_vertices = 0;
+    float boundary_weight = 1.f;
+    float max_cost = std::numeric_limits<float>::infinity();
+    u32 max_rounds = 0;
+  };
+  struct DeviceDecimatedMesh {   // on the device, with room for the input's counts; vertices and triangles are the counts in use
+    std::unique_ptr<DeviceArray<float>> positions, normals;   // normals, colors: null when the input has none
+    std::unique_ptr<DeviceArray<uchar4_t>> colors;
+    std::unique_ptr<DeviceArray<u32>> indices, vertex_map;    // vertex_map: one entry per input vertex
+    u32 vertices = 0, triangles = 0, rounds = 0;
+  };
+  // Host arrays: mesh.normals and mesh.colors may be empty; *out gets what the input has.  vertex_map (may be null) receives the
+  // output vertex of every input vertex.  Returns the number of rounds.
+  u32 DecimateMesh(hipStream_t stream, const Mesh& mesh, const DecimateOptions& options, Mesh* out, std::vector<u32>* vertex_map);
+  // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_decimate_mesh); the result stays on the device.
+  DeviceDecimatedMesh DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                           const u32* indices, const DecimateOptions& options);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.

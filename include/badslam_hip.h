@@ -736,6 +736,63 @@ int bslam_simplify_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count,
  * events on the call's stream.  Zeros before such a call.  For tools/bench_simplify_mesh.py. */
 int bslam_simplify_stage_times(bslam_context* ctx, float* stage_ms5);
 
+/* Mesh decimation: quadric-error edge collapse in data-parallel rounds (DESIGN.md 8 "Mesh decimation", csrc/decimate_kernels.hpp).
+ * Every operation that decides anything is float64, `+ - * /` separately in the written order, nothing contracted; fp32 inputs
+ * are widened first.  cross(u, v) = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x), dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z.
+ * Input: triangles that repeat an index are dropped first; the others are the live triangles, in their order.  A vertex without a
+ *   triangle is kept and never moves.  A vertex is live until it is merged away; live = V at the start.
+ * Plane quadric K(n, a) of a normal n and a point a:  d = -dot(n, a);  the ten products (xx, xy, xz, xd, yy, yz, yd, zz, zd, dd) =
+ *   (n.x n.x, n.x n.y, n.x n.z, n.x d, n.y n.y, n.y n.z, n.y d, n.z n.z, n.z d, d d).  Quadrics add entry by entry.
+ * 1. Triangle t = (i0, i1, i2) with positions a, b, c:  n_t = cross(b - a, c - a), not normalised;  Q_t = K(n_t, a): the form is
+ *   (2 area distance)^2, the squared-volume measure of Lindstrom and Turk, without a root or a division.
+ * 2. Edge k of t runs from corner k to corner (k + 1) mod 3, a -> b.  It is a boundary edge iff no other input triangle uses the
+ *   undirected edge.  Then e = b - a, ee = (e.x e.x + e.y e.y) + e.z e.z, and if ee > 0 every entry p of K(cross(e, n_t), a) becomes
+ *   (p * (double)boundary_weight) / ee; that quadric is added to both ends.
+ * 3. Q[v] starts from +0.0, adds Q_t over the triangles at v in ascending t, then the boundary quadrics of the boundary edges at v in
+ *   ascending (t, k).  Computed once; a collapse sets Q[lo] = Q[lo] + Q[hi].
+ * 4. A round.  The unique undirected edges (lo < hi) of the live triangles in ascending (lo, hi) have rank 0, 1, ...; c is the
+ *   number of live triangles on the edge; N(v) the vertices that share a live triangle with v; v is boundary iff an edge at v has
+ *   c = 1.  An edge is a candidate iff c <= 2, |N(lo) & N(hi)| + [lo and hi boundary] = c + [c = 1] (the link condition with a virtual
+ *   vertex beyond the boundary), no common neighbour is a non-boundary vertex in exactly three live triangles, and the cost and
+ *   flip tests hold.  Q = Q[lo] + Q[hi]; the places are p0 = p_lo, p1 = p_hi, p2 = per axis (float)((p_lo + p_hi) * 0.5);
+ *   cost(p) = (sq + 2 cr) + (2 li + dd) with sq = ((xx x) x + (yy y) y) + (zz z) z, cr = ((xy x) y + (xz x) z) + (yz y) z,
+ *   li = (xd x + yd y) + zd z.  The place is 0, replaced by 1 iff cost(p1) < cost(p0), then by 2 iff cost(p2) < the cost so far.
+ *   cost32 = (float)(cost > 0 ? cost : 0); the cost must not be NaN, cost32 must be finite and <= max_cost.  Flip test: every live
+ *   triangle that holds exactly one of lo and hi, with normal n and, that corner moved to the place, normal n', has dot(n, n') > 0.
+ * 5. key = bits(cost32) << 32 | (rank * 0x9E3779B1 mod 2^32), unique since the constant is odd.  m1[v] = the least key of the
+ *   candidates at v, m2[v] = the least m1 over v and N(v).  A candidate is selected iff key = m2[lo] = m2[hi]; selected edges have
+ *   pairwise non-adjacent ends.  If more are selected than live - target_vertices, the first that many in ascending key collapse.
+ * 6. Collapse: lo takes the place and Q; with place 1 the normal and colour of hi, with place 2 the normal (float)(s / sqrt(ss)) per
+ *   axis, s the double sum of the two and ss = (s.x s.x + s.y s.y) + s.z s.z, or (0, 0, 0) when ss is not > 0 or a component is not
+ *   finite, and the colour (a + b + 1) / 2 per channel in integers.  hi is merged into lo; triangles are remapped and dropped where
+ *   two corners meet; live decreases by one.  Rounds repeat while live > target_vertices and fewer than max_rounds (0: no limit) have
+ *   run; a round that selects nothing is the last.  *out_rounds counts the rounds evaluated, that last one included.
+ * 7. Output: the live vertices in ascending id with their positions, normals and colours; the live triangles in their order;
+ *   vertex_map[v] = the new id of the vertex v was merged into, through every merge.  target_vertices >= V returns the input bit for
+ *   bit, less the dropped triangles.
+ * bslam_decimate_mesh: the arrays are those of bslam_simplify_mesh (device; room for V vertices and T triangles; vertex_map may be
+ * null); the three counts are returned on the host; nothing at or beyond the counts is written.  Refused without a launch: null
+ * required arguments, a boundary_weight that is not finite and >= 0, a max_cost that is NaN or < 0 (+inf is legal), an out_normals /
+ * out_colors that does not match its input, more than 2^32 - 256 vertices or triangle corners, misaligned (4 byte) pointers, an
+ * output that overlaps an input or another output.  Refused behind the first launches, with BSLAM_ERR_INVALID_ARGUMENT and no output
+ * written: an index >= V (never dereferenced) and "a vertex is not finite".  Per round: two stable radix sorts over the key bits in
+ * use -- (edge, slot) and (vertex, slot) -- head flags and their scan, an evaluation pass with one lane per edge that walks the fans
+ * of its ends, integer atomic minima for m1, a fan walk for m2, one read-back of the selected count and the error word, the
+ * collapses, and the keep-flag / scan / scatter of the triangles.  No floating-point atomics.  Scratch lives in a context slab of its
+ * own that the first call reserves.  Synchronises `stream`.  Every rank of a surfel-sharded run computes the same result. */
+int bslam_decimate_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                        const float* normals, const void* colors, const uint32_t* indices, uint32_t target_vertices, float boundary_weight,
+                        float max_cost, uint32_t max_rounds, float* out_positions, float* out_normals, void* out_colors,
+                        uint32_t* out_indices, uint32_t* vertex_map, uint32_t* out_vertex_count, uint32_t* out_triangle_count,
+                        uint32_t* out_rounds);
+/* The device time in milliseconds, summed over the rounds, of the seven stages of the last bslam_decimate_mesh on `ctx` that ran
+ * while bslam_profile_enable was on (HOST out): {keys, the two sorts, head flags with their scan and in round 1 the quadrics,
+ * evaluation, m2 and selection, cut and collapses, triangle compaction}.  For tools/bench_decimate_mesh.py. */
+int bslam_decimate_stage_times(bslam_context* ctx, float* stage_ms7);
+/* The collapses of every round of the last bslam_decimate_mesh on `ctx`: *rounds entries, of which the first `capacity` are copied
+ * to collapses (HOST out; may be null with capacity 0). */
+int bslam_decimate_round_collapses(bslam_context* ctx, uint32_t* collapses, uint32_t capacity, uint32_t* rounds);
+
 /* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
  * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
  * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components

@@ -10,7 +10,7 @@ has a ground truth, prints the ATE RMSE.
                             [--render-source {surfels,volume}]
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
-                            [--mesh-simplify-cell M]
+                            [--mesh-simplify-cell M] [--mesh-decimate-ratio R | --mesh-decimate-vertices N]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
                             [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
@@ -47,6 +47,10 @@ summary line then names the pieces found and the vertices and triangles removed.
 (DirectBA.SimplifyMesh: all vertices of a cell become their mean, collapsed triangles are dropped) without coarsening the volume
 itself; default off.  The simplified mesh is what is written and what --ground-truth-surface scores (--surfel-mesh-distance keeps
 measuring against the extracted one); the counts before and after are printed and reported.
+--mesh-decimate-ratio R / --mesh-decimate-vertices N: the mesh (after --mesh-min-component and --mesh-simplify-cell) is decimated by
+quadric-error edge collapse (DirectBA.DecimateMesh) to R times its vertices, or to N vertices; default off, and at most one of the
+two.  Unlike clustering it spends the vertices where the surface bends and keeps creases and open boundaries.  The decimated mesh is
+what is written and scored; the counts before and after and the number of rounds are printed and reported.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 
@@ -180,8 +184,12 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         median_filter_and_densify_iterations=0, render_dir=None, render_every=1, render_radius_scale=None, inspect=None,
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
-        surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None):
+        surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
+        mesh_decimate_ratio=None, mesh_decimate_vertices=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
+    if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
+        raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
+    decimate = mesh_decimate_ratio is not None or mesh_decimate_vertices is not None
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
@@ -228,16 +236,21 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh or ground_truth_surface or surfel_mesh_distance:
-        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if mesh_simplify_cell else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
+        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if mesh_simplify_cell or decimate else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
                                                 mesh_min_component)
-        surface, simplified = {}, None
+        surface, simplified, decimated = {}, None, None
         if mesh_simplify_cell:
             extracted = m
             m = slam.ba().SimplifyMesh(extracted, float(mesh_simplify_cell))
             simplified = {"cell": float(mesh_simplify_cell), "vertices_before": len(extracted["positions"]), "triangles_before": len(extracted["triangles"]),
                           "vertices": len(m["positions"]), "triangles": len(m["triangles"])}
-            if mesh:
-                dba.SaveMeshAsPLY(mesh, m)
+        if decimate:
+            before = m
+            m = slam.ba().DecimateMesh(before, target_vertices=mesh_decimate_vertices, ratio=mesh_decimate_ratio)
+            decimated = {"target_vertices": mesh_decimate_vertices, "ratio": mesh_decimate_ratio, "vertices_before": len(before["positions"]),
+                         "triangles_before": len(before["triangles"]), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "rounds": int(m["rounds"])}
+        if mesh and (mesh_simplify_cell or decimate):
+            dba.SaveMeshAsPLY(mesh, m)
         if ground_truth_surface:
             surface["ground_truth"] = str(ground_truth_surface)
             start = None
@@ -254,6 +267,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             surface["max_distance"] = float(surface_max_distance)
             if simplified:
                 surface["mesh_simplification"] = simplified
+            if decimated:
+                surface["mesh_decimation"] = decimated
             result["surface"] = surface
             if surface_report:
                 with open(surface_report, "w") as f:
@@ -264,6 +279,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             result["mesh"].update(components=report["components"], removed_vertices=report["removed_vertices"], removed_triangles=report["removed_triangles"])
         if simplified:
             result["mesh"]["simplification"] = simplified
+        if decimated:
+            result["mesh"]["decimation"] = decimated
     if inspect:
         inspect(slam, result)
     if trajectory:
@@ -296,6 +313,8 @@ def arg_parser():
     ap.add_argument("--mesh-min-count", type=int, default=1)
     ap.add_argument("--mesh-min-component", type=int, default=0)
     ap.add_argument("--mesh-simplify-cell", type=float, default=None)
+    ap.add_argument("--mesh-decimate-ratio", type=float, default=None)
+    ap.add_argument("--mesh-decimate-vertices", type=int, default=None)
     ap.add_argument("--point-cloud", default=None)
     ap.add_argument("--ground-truth-surface", default=None)
     ap.add_argument("--surface-max-distance", type=float, default=0.1)
@@ -317,7 +336,7 @@ def main():
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
-            mesh_simplify_cell=a.mesh_simplify_cell)
+            mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -337,12 +356,18 @@ def main():
         if "simplification" in r["mesh"]:
             sp = r["mesh"]["simplification"]
             cleaned += f" (simplified at {sp['cell']:g} m from {sp['vertices_before']} vertices, {sp['triangles_before']} triangles)"
+        if "decimation" in r["mesh"]:
+            dc = r["mesh"]["decimation"]
+            cleaned += f" (decimated in {dc['rounds']} rounds from {dc['vertices_before']} vertices, {dc['triangles_before']} triangles)"
         print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
     if "surface" in r:
         sf = r["surface"]
         if "mesh_simplification" in sf and "mesh" not in r:
             sp = sf["mesh_simplification"]
             print(f"mesh simplified at {sp['cell']:g} m: {sp['vertices_before']} vertices, {sp['triangles_before']} triangles -> {sp['vertices']}, {sp['triangles']}")
+        if "mesh_decimation" in sf and "mesh" not in r:
+            dc = sf["mesh_decimation"]
+            print(f"mesh decimated in {dc['rounds']} rounds: {dc['vertices_before']} vertices, {dc['triangles_before']} triangles -> {dc['vertices']}, {dc['triangles']}")
         if "registration" in sf:
             reg = sf["registration"]
             print(f"registration to the ground truth: {reg['reason']} after {reg['iterations']} steps; ground_truth_T_mesh =")

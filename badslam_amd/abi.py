@@ -129,6 +129,9 @@ SIGNATURES = {
                                       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
     "bslam_decimate_stage_times": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "bslam_decimate_round_collapses": (C.c_int, [C.c_void_p, P(C.c_uint32), C.c_uint32, P(C.c_uint32)]),
+    "bslam_smooth_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
+                                    C.c_void_p, C.c_void_p]),
+    "bslam_smooth_stage_times": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "bslam_point_mesh_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float,
                                             C.c_uint64, C.c_void_p, C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "bslam_sample_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,

@@ -26,6 +26,7 @@
 #include "sampling_kernels.hpp"
 #include "simplify_kernels.hpp"
 #include "decimate_kernels.hpp"
+#include "smooth_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
@@ -1458,6 +1459,7 @@ int bslam_debug_pose_residuals(
 #include "mesh_abi.inc"
 #include "simplify_abi.inc"
 #include "decimate_abi.inc"
+#include "smooth_abi.inc"
 #include "distance_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"

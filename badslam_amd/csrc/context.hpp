@@ -185,6 +185,13 @@ struct bslam_context {
   hipEvent_t decimate_events[8] = {};
   float decimate_stage_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   std::vector<uint32_t> decimate_collapses;
+  bslam::Slab smooth;        // bslam_smooth_mesh: words | per directed pair: keys, sorted keys, ids, slots, head flags, ranks, neighbours, rim flags | per corner:
+                             // keys, sorted keys, fans | per vertex: list and fan ends, boundary flags | working positions | scan sums | the radix sort's scratch;
+                             // reserved by its first call
+  // bslam_smooth_mesh while profiling is on: events around keys, sorts and adjacency, then -- behind the read-back -- around steps and normals, and
+  // the last call's five stage times (bslam_smooth_stage_times)
+  hipEvent_t smooth_events[7] = {};
+  float smooth_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;
@@ -227,6 +234,7 @@ struct bslam_context {
     for (hipEvent_t e : solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : simplify_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : decimate_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+    for (hipEvent_t e : smooth_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     if (perm_ready) { hipError_t err = hipEventDestroy(perm_ready); (void)err; }
     if (copy_stream) { hipError_t err = hipStreamDestroy(copy_stream); (void)err; }
     for (const ProfEntry& p : prof_pending) { hipError_t err = hipEventDestroy(p.start); err = hipEventDestroy(p.stop); (void)err; }

@@ -92,6 +92,9 @@ def host_lib():
     L.bsh_simplified_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
     L.bsh_decimate_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
     L.bsh_decimated_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
+    L.bsh_smooth_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32]
+    L.bsh_smooth_extracted_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
+    L.bsh_smoothed_copy.argtypes = [f32p, f32p]
     L.bsh_sample_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_uint32, u64p]
     L.bsh_samples_copy.argtypes = [f32p, f32p, u32p]
     f64p = C.POINTER(C.c_double)
@@ -795,6 +798,45 @@ class DirectBA:
         if col is not None and channels == 3:
             out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
         return out
+
+    # --- mesh smoothing (bslam_smooth_mesh)
+    SMOOTH_BOUNDARY = {"fixed": 0, "rim": 1, "free": 2}
+
+    def SmoothMesh(self, mesh, iterations=10, lambda_=0.5, mu=-0.53, boundary="fixed"):
+        """Taubin lambda|mu smoothing of `mesh` (the dict of ExtractMesh or LoadPLY): `iterations` times a one-ring step with lambda_
+        in (0, 1] and then, unless mu is 0, one with mu in [-1, 0]; mu = 0 is plain Laplacian smoothing, which shrinks.  boundary:
+        "fixed" holds the vertices of open boundaries, "rim" smooths them along the boundary, "free" treats them like any other.  The
+        defaults are provisional: they have been tried on synthetic meshes only.  -> the dict of ExtractMesh: positions and normals
+        new -- the normals are the area-weighted ones of the smoothed geometry, the input's (or zero) where a vertex has no triangle
+        with an area --, colors (with the input's channel count) and triangles passed through."""
+        if boundary not in self.SMOOTH_BOUNDARY:
+            raise ValueError("SmoothMesh: boundary must be 'fixed', 'rim' or 'free'")
+        if not 0 <= int(iterations) <= 0xFFFFFFFF:
+            raise ValueError("SmoothMesh: iterations must fit 32 bits")
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "SmoothMesh")
+        self._check(self.L.bsh_smooth_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), len(tri), _u32(tri), int(iterations),
+                                           float(lambda_), float(mu), self.SMOOTH_BOUNDARY[boundary]))
+        out = dict(positions=np.zeros((len(pos), 3), np.float32), normals=np.zeros((len(pos), 3), np.float32),
+                   colors=None if col is None else np.ascontiguousarray(col[:, :channels]), triangles=tri.copy())
+        self._check(self.L.bsh_smoothed_copy(_f(out["positions"]), _f(out["normals"])))
+        return out
+
+    def SmoothExtractedMesh(self, iterations=10, lambda_=0.5, mu=-0.53, boundary="fixed"):
+        """SmoothMesh of the mesh the last ExtractMesh left on the device, without an upload -> (positions (V, 3) f32, normals (V, 3)
+        f32).  The device mesh stays as it is and holds no normals, so a vertex without a triangle that has an area gets (0, 0, 0)."""
+        if boundary not in self.SMOOTH_BOUNDARY:
+            raise ValueError("SmoothExtractedMesh: boundary must be 'fixed', 'rim' or 'free'")
+        if not 0 <= int(iterations) <= 0xFFFFFFFF:
+            raise ValueError("SmoothExtractedMesh: iterations must fit 32 bits")
+        count = C.c_uint64()
+        self._check(self.L.bsh_smooth_extracted_mesh(self._ba, self.stream, int(iterations), float(lambda_), float(mu), self.SMOOTH_BOUNDARY[boundary], C.byref(count)))
+        positions, normals = np.zeros((count.value, 3), np.float32), np.zeros((count.value, 3), np.float32)
+        self._check(self.L.bsh_smoothed_copy(_f(positions), _f(normals)))
+        return positions, normals
+
+    def MeshNormals(self, mesh):
+        """`mesh` with vertex normals computed from its geometry: SmoothMesh with iterations=0, so the positions keep their bits."""
+        return self.SmoothMesh(mesh, iterations=0)
 
     # --- mesh simplification (bslam_simplify_mesh)
     def SimplifyMesh(self, mesh, cell_size, origin=None):

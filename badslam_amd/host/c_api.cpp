@@ -348,6 +348,55 @@ int bsh_decimated_copy(float* positions, float* normals, uint8_t* colors, uint32
     g_decimated_map = std::vector<uint32_t>();
   });
 }
+// DirectBA::SmoothMesh of host arrays in the same two steps: bsh_smooth_mesh (normals and indices may be null; boundary 0 fixed, 1 rim,
+// 2 free) keeps the new positions and normals for this thread; bsh_smoothed_copy copies them out (either pointer may be null) and
+// drops them.  Colours and indices are the caller's own.
+static thread_local DirectBA::Mesh g_smoothed;
+int bsh_smooth_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, uint64_t triangles, const uint32_t* indices,
+                    uint32_t iterations, float lambda, float mu, uint32_t boundary) {
+  BSH_TRY({
+    g_smoothed = DirectBA::Mesh();
+    if (boundary > 2u) throw std::invalid_argument("SmoothMesh: boundary must be 0 (fixed), 1 (rim) or 2 (free)");
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
+    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::SmoothOptions options;
+    options.iterations = iterations;
+    options.lambda = lambda;
+    options.mu = mu;
+    options.boundary = static_cast<DirectBA::SmoothBoundary>(boundary);
+    static_cast<DirectBA*>(ba)->SmoothMesh(static_cast<hipStream_t>(stream), mesh, options, &g_smoothed);
+  });
+}
+// DirectBA::SmoothMeshOnDevice of the mesh the last ExtractMesh left on the device: *vertices receives its vertex count, and
+// bsh_smoothed_copy copies the result out as above.
+int bsh_smooth_extracted_mesh(void* ba, void* stream, uint32_t iterations, float lambda, float mu, uint32_t boundary, uint64_t* vertices) {
+  BSH_TRY({
+    g_smoothed = DirectBA::Mesh();
+    if (boundary > 2u) throw std::invalid_argument("SmoothMesh: boundary must be 0 (fixed), 1 (rim) or 2 (free)");
+    DirectBA::SmoothOptions options;
+    options.iterations = iterations;
+    options.lambda = lambda;
+    options.mu = mu;
+    options.boundary = static_cast<DirectBA::SmoothBoundary>(boundary);
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    const DirectBA::DeviceSmoothedMesh d = static_cast<DirectBA*>(ba)->SmoothMeshOnDevice(s, options);
+    g_smoothed.positions.resize(size_t{3} * d.vertices);
+    g_smoothed.normals.resize(size_t{3} * d.vertices);
+    d.positions->Download(s, g_smoothed.positions.data(), g_smoothed.positions.size());
+    d.normals->Download(s, g_smoothed.normals.data(), g_smoothed.normals.size());
+    if (hipStreamSynchronize(s) != hipSuccess) throw std::runtime_error("SmoothMeshOnDevice: the download failed");
+    *vertices = d.vertices;
+  });
+}
+int bsh_smoothed_copy(float* positions, float* normals) {
+  BSH_TRY({
+    copy_out(positions, g_smoothed.positions);
+    copy_out(normals, g_smoothed.normals);
+    g_smoothed = DirectBA::Mesh();
+  });
+}
 // DirectBA::PointMeshDistance of host arrays: points 3 per point, positions 3 per vertex, indices 3 per triangle; distance and
 // triangle receive `points_count` entries; *cell_used the grid cell of the call that succeeded, grid2 = {cells, entries}.
 static void grid_out(const DirectBA::PointMeshResult& result, float* cell_used, uint64_t* grid2) {

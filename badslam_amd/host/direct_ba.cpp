@@ -925,6 +925,52 @@ u32 DirectBA::DecimateMesh(hipStream_t stream, const Mesh& mesh, const DecimateO
   return d.rounds;
 }
 
+DirectBA::DeviceSmoothedMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
+                                                          const u32* indices, const SmoothOptions& options) {
+  DeviceSmoothedMesh d;
+  d.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
+  d.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
+  d.vertices = vertices;
+  Check(bslam_smooth_mesh(ctx_, stream, vertices, triangles, positions, normals, indices, options.iterations, options.lambda, options.mu, options.boundary,
+                          d.positions->address(), d.normals->address()),
+        "bslam_smooth_mesh");
+  return d;
+}
+
+DirectBA::DeviceSmoothedMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options) {
+  if (!mesh_extracted_) throw std::logic_error("SmoothMeshOnDevice: no extracted mesh (call ExtractMesh first)");
+  // the kept mesh holds positions and indices only, so there is no input normal to fall back on: a vertex without a live triangle gets (0, 0, 0)
+  return SmoothMeshOnDevice(stream, mesh_vertices_, mesh_triangles_, mesh_positions_ ? mesh_positions_->address() : nullptr, nullptr,
+                            mesh_indices_ ? mesh_indices_->address() : nullptr, options);
+}
+
+void DirectBA::SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOptions& options, Mesh* out) {
+  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
+    throw std::invalid_argument("SmoothMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
+    throw std::invalid_argument("SmoothMesh: normals and colors need one entry per vertex, or none");
+  const bool has_normals = !mesh.normals.empty();
+  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
+  DeviceArray<u32> dev_indices(3 * T);
+  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
+  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
+  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
+  Wait(stream);   // the host arrays are the caller's and pageable
+  const DeviceSmoothedMesh d = SmoothMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
+                                                  dev_indices.address(), options);
+  std::vector<float> positions(3 * V), normals(3 * V);   // `out` may be `mesh`
+  d.positions->Download(stream, positions.data(), positions.size());
+  d.normals->Download(stream, normals.data(), normals.size());
+  Wait(stream);
+  if (out != &mesh) {
+    out->colors = mesh.colors;
+    out->indices = mesh.indices;
+  }
+  out->positions = std::move(positions);
+  out->normals = std::move(normals);
+}
+
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
   const FusedVolume v = Fused("RenderVolume");
   const int w = camera.width(), h = camera.height();

@@ -334,6 +334,27 @@ class DirectBA {
   // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_decimate_mesh); the result stays on the device.
   DeviceDecimatedMesh DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
                                            const u32* indices, const DecimateOptions& options);
+  // Mesh smoothing (bslam_smooth_mesh): `iterations` of a one-ring step with lambda followed, unless mu is 0, by one with mu (Taubin;
+  // mu = 0 is plain Laplacian smoothing), then vertex normals from the smoothed geometry.  Counts, indices and colours stay.  The
+  // defaults have been tried on synthetic meshes only and are provisional.
+  enum SmoothBoundary : u32 { kSmoothFixed = 0, kSmoothRim = 1, kSmoothFree = 2 };   // boundary vertices: held, smoothed along the rim, smoothed like any other
+  struct SmoothOptions {
+    u32 iterations = 10;
+    float lambda = 0.5f, mu = -0.53f;
+    SmoothBoundary boundary = kSmoothFixed;
+  };
+  struct DeviceSmoothedMesh {   // on the device: the new positions and normals of `vertices` vertices
+    std::unique_ptr<DeviceArray<float>> positions, normals;
+    u32 vertices = 0;
+  };
+  // Host arrays: mesh.normals (the fall-back where the geometry gives no normal) and mesh.colors may be empty; *out gets new positions
+  // and normals, and the input's colours and indices.
+  void SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOptions& options, Mesh* out);
+  // The same on the mesh the last ExtractMesh left on the device, which stays as it is; the result stays on the device.
+  DeviceSmoothedMesh SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options);
+  // ... and on a caller's device arrays (4 byte aligned; normals may be null; see bslam_smooth_mesh).
+  DeviceSmoothedMesh SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const u32* indices,
+                                        const SmoothOptions& options);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.

@@ -793,6 +793,48 @@ int bslam_decimate_stage_times(bslam_context* ctx, float* stage_ms7);
  * to collapses (HOST out; may be null with capacity 0). */
 int bslam_decimate_round_collapses(bslam_context* ctx, uint32_t* collapses, uint32_t capacity, uint32_t* rounds);
 
+/* Mesh smoothing: the Taubin lambda|mu filter over the one-ring, and vertex normals recomputed from the geometry (DESIGN.md 8 "Mesh
+ * smoothing", csrc/smooth_kernels.hpp).  Everything that decides a bit is float64, `+ - * /` separately in the written order,
+ * nothing contracted; fp32 inputs are widened first and a result is narrowed to fp32 once.  cross and dot are those of "Mesh
+ * decimation".
+ * 1. Live triangles: a triangle that repeats an index is ignored everywhere; the others are live.
+ * 2. Neighbours: N(v) is the set of distinct vertices that share a live triangle with v, in ascending id; c(v, u) the number of live
+ *   triangles that hold both.  v is a boundary vertex iff some u has c(v, u) = 1.  An edge with three or more uses is interior.
+ * 3. Stencil S(v) by boundary_mode:  0 (fixed): empty for a boundary vertex, N(v) for every other;  1 (rim): {u in N(v) : c(v, u) = 1}
+ *   for a boundary vertex -- the rim is smoothed along itself, the VCG convention --, N(v) for every other;  2 (free): N(v) for every
+ *   vertex.  A vertex with an empty stencil keeps its position bits through every step: isolated vertices, fixed boundaries, a mesh
+ *   without triangles.
+ * 4. One step with factor f, a Jacobi step over the previous positions:  per axis s starts from the first member of S(v) and adds the
+ *   others in ascending id;  m = s / (double)|S(v)|;  p' = (float)(p + f * (m - p)) with f the fp32 parameter widened.
+ * 5. An iteration is a step with lambda, then a step with mu unless mu == 0 (plain Laplacian smoothing).  The stencils are built once
+ *   per call.  iterations == 0 returns the positions bit for bit.
+ * 6. Normals, written only if out_normals is given, from the final positions:  g(v) starts from +0.0 and adds, over the live triangles
+ *   at v in ascending t, cross(b - a, c - a) with a, b, c the corners in index order -- not normalised, so area weighted;
+ *   ss = (g.x g.x + g.y g.y) + g.z g.z;  the normal is (float)(g / sqrt(ss)) per axis.  Triangles of bslam_extract_mesh are
+ *   counter-clockwise seen from free space, so these normals point the way its own do.  When ss is not > 0 or v has no live
+ *   triangle, the normal is the input normal if `normals` is given, else (0, 0, 0).
+ * 7. Vertex count, triangle count and indices do not change; colours are no argument.
+ * bslam_smooth_mesh: positions float[3 V], normals float[3 V] (may be null), indices uint32[3 T], out_positions float[3 V] and
+ * out_normals float[3 V] (may be null, whether or not normals is given) are device arrays, 4 byte aligned.  V == 0 is legal with
+ * T == 0, and T == 0 is a point cloud: positions are copied, normals are the input's or zero.  Refused without a launch: null
+ * required arguments, a lambda that is not finite or outside (0, 1], a mu that is not finite or outside [-1, 0], boundary_mode > 2,
+ * iterations > 65535, more than 2^32 - 256 vertices or 6 T adjacency entries, misaligned pointers, an output that overlaps an input
+ * or the other output.  Refused behind the first launches, by a device error bit, with BSLAM_ERR_INVALID_ARGUMENT and no output
+ * written: an index >= V (never dereferenced; the message of the mesh component calls) and "a vertex is not finite".  Once per call: a
+ * key pass (six directed pairs v << bits | u and three corners per live triangle), the stable radix sort of decimation over (pair,
+ * slot) and, for normals, over (vertex, slot), head flags and their scan, and a pass that writes the neighbour list of every vertex
+ * -- ascending in u by construction; the run length of a pair is c(v, u) -- then one read-back of the error word.  Per step one launch
+ * with one lane per vertex; iterations x (1 or 2) launches between the input, two working buffers and the output.  No
+ * floating-point atomics.  Scratch lives in a context slab of its own that the first call reserves.  Synchronises `stream`.  Every
+ * rank of a surfel-sharded run computes the same result. */
+int bslam_smooth_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                      const float* normals, const uint32_t* indices, uint32_t iterations, float lambda, float mu, uint32_t boundary_mode,
+                      float* out_positions, float* out_normals);
+/* The device time in milliseconds of the five stages of the last bslam_smooth_mesh on `ctx` that ran while bslam_profile_enable was
+ * on (HOST out): {keys, sort(s), adjacency, steps, normals}, from events on the call's stream; the read-back between adjacency and
+ * steps is in none of them.  Zeros before such a call.  For tools/bench_smooth_mesh.py. */
+int bslam_smooth_stage_times(bslam_context* ctx, float* stage_ms5);
+
 /* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
  * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
  * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components

@@ -10,6 +10,7 @@ has a ground truth, prints the ATE RMSE.
                             [--render-source {surfels,volume}]
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
+                            [--mesh-smooth-iterations N] [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-boundary fixed|rim|free]
                             [--mesh-simplify-cell M] [--mesh-decimate-ratio R | --mesh-decimate-vertices N]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
@@ -43,7 +44,13 @@ size up to --max-depth.  The directory has the same layout.
 --mesh-min-component N: connected pieces of the surface with fewer than N vertices (flying pixels at occlusion edges, single noisy
 blobs) are removed on the GPU before the file is written (DirectBA.ExtractMesh(min_component_vertices=N)); default 0, off.  The
 summary line then names the pieces found and the vertices and triangles removed.
---mesh-simplify-cell M: the mesh (after --mesh-min-component) is simplified by vertex clustering on a grid of M metres
+--mesh-smooth-iterations N: the mesh (after --mesh-min-component, before --mesh-simplify-cell and the decimation) is smoothed by N
+iterations of the Taubin lambda|mu filter (DirectBA.SmoothMesh: a one-ring step with --mesh-smooth-lambda, default 0.5, then one with
+--mesh-smooth-mu, default -0.53; 0 makes it plain Laplacian smoothing) and gets the normals of the smoothed geometry; default 0, off.
+--mesh-smooth-boundary: open boundaries are held (fixed, the default), smoothed along themselves (rim) or like the rest (free).  The
+defaults are provisional: they have been tried on synthetic meshes only.  The smoothed mesh is what is written, simplified, decimated
+and scored; the parameters are printed and reported.
+--mesh-simplify-cell M: the mesh (after --mesh-min-component and the smoothing) is simplified by vertex clustering on a grid of M metres
 (DirectBA.SimplifyMesh: all vertices of a cell become their mean, collapsed triangles are dropped) without coarsening the volume
 itself; default off.  The simplified mesh is what is written and what --ground-truth-surface scores (--surfel-mesh-distance keeps
 measuring against the extracted one); the counts before and after are printed and reported.
@@ -185,11 +192,15 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
         surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
-        mesh_decimate_ratio=None, mesh_decimate_vertices=None):
+        mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
+        mesh_smooth_boundary="fixed"):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
         raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
     decimate = mesh_decimate_ratio is not None or mesh_decimate_vertices is not None
+    if mesh_smooth_iterations < 0:
+        raise ValueError("--mesh-smooth-iterations must be >= 0")
+    smooth = mesh_smooth_iterations > 0
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
@@ -236,9 +247,12 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh or ground_truth_surface or surfel_mesh_distance:
-        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if mesh_simplify_cell or decimate else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
+        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if smooth or mesh_simplify_cell or decimate else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
                                                 mesh_min_component)
-        surface, simplified, decimated = {}, None, None
+        surface, smoothed, simplified, decimated = {}, None, None, None
+        if smooth:
+            m = slam.ba().SmoothMesh(m, iterations=int(mesh_smooth_iterations), lambda_=float(mesh_smooth_lambda), mu=float(mesh_smooth_mu), boundary=mesh_smooth_boundary)
+            smoothed = {"iterations": int(mesh_smooth_iterations), "lambda": float(mesh_smooth_lambda), "mu": float(mesh_smooth_mu), "boundary": mesh_smooth_boundary}
         if mesh_simplify_cell:
             extracted = m
             m = slam.ba().SimplifyMesh(extracted, float(mesh_simplify_cell))
@@ -249,7 +263,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             m = slam.ba().DecimateMesh(before, target_vertices=mesh_decimate_vertices, ratio=mesh_decimate_ratio)
             decimated = {"target_vertices": mesh_decimate_vertices, "ratio": mesh_decimate_ratio, "vertices_before": len(before["positions"]),
                          "triangles_before": len(before["triangles"]), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "rounds": int(m["rounds"])}
-        if mesh and (mesh_simplify_cell or decimate):
+        if mesh and (smooth or mesh_simplify_cell or decimate):
             dba.SaveMeshAsPLY(mesh, m)
         if ground_truth_surface:
             surface["ground_truth"] = str(ground_truth_surface)
@@ -265,6 +279,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
         if surface:
             surface["max_distance"] = float(surface_max_distance)
+            if smoothed:
+                surface["mesh_smoothing"] = smoothed
             if simplified:
                 surface["mesh_simplification"] = simplified
             if decimated:
@@ -277,6 +293,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
         if report is not None:
             result["mesh"].update(components=report["components"], removed_vertices=report["removed_vertices"], removed_triangles=report["removed_triangles"])
+        if smoothed:
+            result["mesh"]["smoothing"] = smoothed
         if simplified:
             result["mesh"]["simplification"] = simplified
         if decimated:
@@ -312,6 +330,10 @@ def arg_parser():
     ap.add_argument("--mesh-truncation", type=float, default=None)
     ap.add_argument("--mesh-min-count", type=int, default=1)
     ap.add_argument("--mesh-min-component", type=int, default=0)
+    ap.add_argument("--mesh-smooth-iterations", type=int, default=0)
+    ap.add_argument("--mesh-smooth-lambda", type=float, default=0.5)
+    ap.add_argument("--mesh-smooth-mu", type=float, default=-0.53)
+    ap.add_argument("--mesh-smooth-boundary", choices=("fixed", "rim", "free"), default="fixed")
     ap.add_argument("--mesh-simplify-cell", type=float, default=None)
     ap.add_argument("--mesh-decimate-ratio", type=float, default=None)
     ap.add_argument("--mesh-decimate-vertices", type=int, default=None)
@@ -336,7 +358,9 @@ def main():
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
-            mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices)
+            mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
+            mesh_smooth_iterations=a.mesh_smooth_iterations, mesh_smooth_lambda=a.mesh_smooth_lambda, mesh_smooth_mu=a.mesh_smooth_mu,
+            mesh_smooth_boundary=a.mesh_smooth_boundary)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -353,6 +377,9 @@ def main():
         if "components" in r["mesh"]:
             cleaned = (f" ({r['mesh']['components']} components before clean-up, {r['mesh']['removed_vertices']} vertices and "
                        f"{r['mesh']['removed_triangles']} triangles removed)")
+        if "smoothing" in r["mesh"]:
+            sm = r["mesh"]["smoothing"]
+            cleaned += f" (smoothed by {sm['iterations']} iterations of lambda {sm['lambda']:g}, mu {sm['mu']:g}, boundary {sm['boundary']})"
         if "simplification" in r["mesh"]:
             sp = r["mesh"]["simplification"]
             cleaned += f" (simplified at {sp['cell']:g} m from {sp['vertices_before']} vertices, {sp['triangles_before']} triangles)"
@@ -362,6 +389,9 @@ def main():
         print(f"mesh of {r['mesh']['vertices']} vertices, {r['mesh']['triangles']} triangles from {r['mesh']['dims']} samples{cleaned} -> {r['mesh']['path']}")
     if "surface" in r:
         sf = r["surface"]
+        if "mesh_smoothing" in sf and "mesh" not in r:
+            sm = sf["mesh_smoothing"]
+            print(f"mesh smoothed by {sm['iterations']} iterations of lambda {sm['lambda']:g}, mu {sm['mu']:g}, boundary {sm['boundary']}")
         if "mesh_simplification" in sf and "mesh" not in r:
             sp = sf["mesh_simplification"]
             print(f"mesh simplified at {sp['cell']:g} m: {sp['vertices_before']} vertices, {sp['triangles_before']} triangles -> {sp['vertices']}, {sp['triangles']}")

@@ -22,8 +22,8 @@ def sources():
 
 
 def library_sources():
-    """... and the ones that only wrap a rocPRIM call, kept apart so that they leave the device code of the first alone."""
-    return sources() + [os.path.join(CSRC, "simplify_sort.hip"), os.path.join(CSRC, "decimate_sort.hip")]
+    """... and the one that only wraps a rocPRIM call, kept apart so that it leaves the device code of the first alone."""
+    return sources() + [os.path.join(CSRC, "mesh_sort.hip")]
 
 
 def needs_build():

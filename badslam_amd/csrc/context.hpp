@@ -122,6 +122,32 @@ struct StagingRing {
   }
 };
 
+// The events at the stage boundaries of a call that times its stages while profiling is on: created at their first use, destroyed
+// with their owner.
+template <int kCount>
+struct StageEvents {
+  hipEvent_t event[kCount] = {};
+  StageEvents() = default;
+  StageEvents(const StageEvents&) = delete;
+  StageEvents& operator=(const StageEvents&) = delete;
+  ~StageEvents() {
+    for (hipEvent_t e : event)
+      if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
+  }
+  // Boundary `at`: an event on the stream while profiling is on, nothing otherwise.
+  int mark(bool profiling, hipStream_t stream, int at) {
+    if (!profiling) return BSLAM_OK;
+    if (!event[at]) BSLAM_HIP_TRY(hipEventCreate(&event[at]));
+    BSLAM_HIP_TRY(hipEventRecord(event[at], stream));
+    return BSLAM_OK;
+  }
+  // The time between two recorded boundaries; both have completed.
+  int elapsed(int from, int to, float* ms) const {
+    BSLAM_HIP_TRY(hipEventElapsedTime(ms, event[from], event[to]));
+    return BSLAM_OK;
+  }
+};
+
 }  // namespace bslam
 
 struct bslam_context {
@@ -176,13 +202,13 @@ struct bslam_context {
   bslam::Slab simplify;      // bslam_simplify_mesh: words | keys, sorted keys u64[V] | ids, sorted ids, head flags, ranks, clusters [V] | keep flags, ranks [T] |
                              // scan sums | the radix sort's scratch; reserved by its first call
   // bslam_simplify_mesh while profiling is on: events around its five stages and the last call's times (bslam_simplify_stage_times)
-  hipEvent_t simplify_events[6] = {};
+  bslam::StageEvents<6> simplify_events;
   float simplify_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   bslam::Slab decimate;      // bslam_decimate_mesh: words | working attributes, quadrics, parents [V] | two triangle buffers | per slot: keys, sorted keys, slots,
                              // flags, ranks, candidate keys | per vertex: fans, flags, minima | scan sums | the radix sort's scratch; reserved by its first call
   // bslam_decimate_mesh while profiling is on: events around the seven stages of a round and their sums over the last call's rounds
   // (bslam_decimate_stage_times); the collapses of every round of the last call (bslam_decimate_round_collapses)
-  hipEvent_t decimate_events[8] = {};
+  bslam::StageEvents<8> decimate_events;
   float decimate_stage_ms[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   std::vector<uint32_t> decimate_collapses;
   bslam::Slab smooth;        // bslam_smooth_mesh: words | per directed pair: keys, sorted keys, ids, slots, head flags, ranks, neighbours, rim flags | per corner:
@@ -190,7 +216,7 @@ struct bslam_context {
                              // reserved by its first call
   // bslam_smooth_mesh while profiling is on: events around keys, sorts and adjacency, then -- behind the read-back -- around steps and normals, and
   // the last call's five stage times (bslam_smooth_stage_times)
-  hipEvent_t smooth_events[7] = {};
+  bslam::StageEvents<7> smooth_events;
   float smooth_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
@@ -232,9 +258,6 @@ struct bslam_context {
   ~bslam_context() {
     for (hipEvent_t e : iter_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     for (hipEvent_t e : solve_done) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
-    for (hipEvent_t e : simplify_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
-    for (hipEvent_t e : decimate_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
-    for (hipEvent_t e : smooth_events) if (e) { hipError_t err = hipEventDestroy(e); (void)err; }
     if (perm_ready) { hipError_t err = hipEventDestroy(perm_ready); (void)err; }
     if (copy_stream) { hipError_t err = hipStreamDestroy(copy_stream); (void)err; }
     for (const ProfEntry& p : prof_pending) { hipError_t err = hipEventDestroy(p.start); err = hipEventDestroy(p.stop); (void)err; }

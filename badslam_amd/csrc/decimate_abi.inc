@@ -1,40 +1,16 @@
-// decimate_abi.inc -- bslam_decimate_mesh of include/badslam_hip.h (included by badslam_hip.hip after simplify_abi.inc:
-// check_mesh_spans, mesh_error, empty_mesh, device_scan, flat_grid, read_back, carve).
+// decimate_abi.inc -- bslam_decimate_mesh of include/badslam_hip.h (included by badslam_hip.hip after mesh_abi.inc:
+// check_attribute_pairs, mesh_array_spans, check_mesh_spans, mesh_error, empty_mesh, pad64, vertex_id_bits, mesh_sort, remap_triangles;
+// device_scan, flat_grid, read_back, carve).
 
 namespace bslam {
-// decimate_sort.hip
-hipError_t decimate_sort_pairs(void* temp, size_t* temp_bytes, const unsigned long long* keys, unsigned long long* sorted_keys, const uint32_t* ids,
-                               uint32_t* sorted_ids, size_t count, unsigned end_bit, hipStream_t stream);
-
-// Stage boundary `at` (0 .. kDecimateStages) of a round: an event on the stream while profiling is on, nothing otherwise.
-static int decimate_mark(bslam_context* ctx, hipStream_t stream, int at) {
-  if (!ctx->profiling) return BSLAM_OK;
-  if (!ctx->decimate_events[at]) BSLAM_HIP_TRY(hipEventCreate(&ctx->decimate_events[at]));
-  BSLAM_HIP_TRY(hipEventRecord(ctx->decimate_events[at], stream));
-  return BSLAM_OK;
-}
-// Adds the times between the recorded boundaries first .. last to the stage sums; the stream is idle.
+// Adds the times between the recorded boundaries first .. last of a round to the stage sums; the stream is idle.
 static int decimate_collect(bslam_context* ctx, int first, int last) {
   if (!ctx->profiling) return BSLAM_OK;
   for (int s = first; s < last; ++s) {
     float ms = 0.f;
-    BSLAM_HIP_TRY(hipEventElapsedTime(&ms, ctx->decimate_events[s], ctx->decimate_events[s + 1]));
+    if (int rc = ctx->decimate_events.elapsed(s, s + 1, &ms)) return rc;
     ctx->decimate_stage_ms[s] += ms;
   }
-  return BSLAM_OK;
-}
-// One sort of `count` pairs over the key bits [0, end_bit) in the `temp_bytes` of scratch at `temp`.
-static int decimate_sort(void* temp, size_t temp_bytes, const unsigned long long* keys, unsigned long long* sorted_keys, const uint32_t* ids, uint32_t* sorted_ids,
-                         size_t count, unsigned end_bit, hipStream_t stream) {
-  size_t need = 0;
-  BSLAM_HIP_TRY(decimate_sort_pairs(nullptr, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
-  if (need > temp_bytes) return fail(BSLAM_ERR_INTERNAL, "bslam_decimate_mesh: a sort of %zu pairs needs %zu bytes of scratch where %zu were reserved", count, need, temp_bytes);
-  BSLAM_HIP_TRY(decimate_sort_pairs(temp, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
-  return BSLAM_OK;
-}
-static int decimate_error(uint32_t bits, const char* call) {
-  if (int rc = mesh_error(bits, call)) return rc;
-  if (bits & kDecimateBadVertex) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a vertex is not finite", call);
   return BSLAM_OK;
 }
 }  // namespace bslam
@@ -50,17 +26,16 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
   if (!ctx || !out_vertex_count || !out_triangle_count || !out_rounds) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (!std::isfinite(boundary_weight) || boundary_weight < 0.f) return fail(BSLAM_ERR_INVALID_ARGUMENT, "boundary_weight must be finite and >= 0");
   if (!(max_cost >= 0.f)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "max_cost must be >= 0 or +inf");
-  if ((normals != nullptr) != (out_normals != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_normals must be given exactly when normals is");
-  if ((colors != nullptr) != (out_colors != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_colors must be given exactly when colors is");
+  const MeshArrays arrays = {positions, normals, colors, indices, out_positions, out_normals, out_colors, out_indices};
+  int rc = check_attribute_pairs(arrays);
+  if (rc) return rc;
   const size_t V = vertex_count, T = triangle_count;
   // one thread per slot (three per triangle) in blocks of 256, and a scan of 32-bit ranks over the slots
   if (V > 0xffffff00ull || 3 * T > 0xffffff00ull) return fail(BSLAM_ERR_INVALID_ARGUMENT, "more than 2^32 - 256 vertices or triangle corners");
-  const MeshSpan spans[9] = {{positions, 12 * V, "positions", false}, {normals, normals ? 12 * V : 0, "normals", false}, {colors, colors ? 4 * V : 0, "colors", false},
-                             {indices, 12 * T, "indices", false}, {out_positions, 12 * V, "out_positions", true},
-                             {out_normals, normals ? 12 * V : 0, "out_normals", true}, {out_colors, colors ? 4 * V : 0, "out_colors", true},
-                             {out_indices, 12 * T, "out_indices", true}, {vertex_map, vertex_map ? 4 * V : 0, "vertex_map", true}};
-  int rc = check_mesh_spans(spans, 9);
-  if (rc) return rc;
+  MeshSpan spans[9];
+  mesh_array_spans(arrays, V, T, spans, spans + 4);
+  spans[8] = {vertex_map, vertex_map ? 4 * V : 0, "vertex_map", true};
+  if ((rc = check_mesh_spans(spans, 9))) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   ctx->decimate_collapses.clear();
   for (float& ms : ctx->decimate_stage_ms) ms = 0.f;
@@ -68,13 +43,12 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
     if ((rc = empty_mesh(stream, T, call)) == BSLAM_OK) *out_vertex_count = *out_triangle_count = *out_rounds = 0;
     return rc;
   }
-  unsigned bits = 1;
-  while (bits < 32 && (V - 1) >> bits) ++bits;
+  const unsigned bits = vertex_id_bits(V);
   // scratch: words | working positions, normals, colours, quadrics, parents [V] | two triangle buffers [T] | per slot (E = 3 T): the keys
   //          of the two sorts and their sorted copies, slots, flags, ranks, candidate keys | per vertex: fans, flags, minima | scan sums | the sort's own
-  const size_t E = 3 * T, nv = (V + 63) & ~(size_t)63, nt = (T + 63) & ~(size_t)63, ne = (E + 63) & ~(size_t)63, tiles = std::max(nv, ne) / kScanTile + 2;
+  const size_t E = 3 * T, nv = pad64(V), nt = pad64(T), ne = pad64(E), tiles = std::max(nv, ne) / kScanTile + 2;
   size_t sort_bytes = 0;
-  BSLAM_HIP_TRY(decimate_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, std::max<size_t>(E, 1), 64, stream));
+  if ((rc = mesh_sort_bytes(std::max<size_t>(E, 1), stream, &sort_bytes))) return rc;
   DecimateState s = {};
   uint32_t *tri_a, *tri_b, *triangle_rank, *live_rank, *tile_sums, *scratch32;
   uint8_t *keep, *live, *sort_temp;
@@ -98,18 +72,9 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
   hipLaunchKernelGGL(decimate_init_kernel, flat_grid(V), block, 0, stream, s, positions, normals, (const uint32_t*)colors);
   BSLAM_HIP_TRY(hipGetLastError());
   // the input's triangles without those that repeat an index; parent is the identity
-  if (T != 0) {
-    hipLaunchKernelGGL(decimate_keep_kernel, flat_grid(T), block, 0, stream, vertex_count, triangle_count, indices, (const uint32_t*)s.parent, keep, s.words);
-    BSLAM_HIP_TRY(hipGetLastError());
-  }
-  if ((rc = device_scan(stream, 0, keep, triangle_count, true, triangle_rank, tile_sums, s.words + kDecimateTriangles))) return rc;
-  if (T != 0) {
-    hipLaunchKernelGGL(decimate_scatter_kernel, flat_grid(T), block, 0, stream, triangle_count, indices, (const uint32_t*)s.parent, (const uint8_t*)keep,
-                       (const uint32_t*)triangle_rank, tri_a);
-    BSLAM_HIP_TRY(hipGetLastError());
-  }
+  if ((rc = remap_triangles(stream, vertex_count, triangle_count, indices, s.parent, keep, triangle_rank, tile_sums, s.words, s.words + kDecimateTriangles, tri_a))) return rc;
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, 4, &host))) return rc;
-  if ((rc = decimate_error(host[kDecimateError], call))) return rc;
+  if ((rc = mesh_error(host[kDecimateError], call))) return rc;
   uint32_t live_count = vertex_count, triangles = host[kDecimateTriangles], rounds = 0;
   uint32_t *tri = tri_a, *tri_next = tri_b;
   bool exact = true;   // `triangles` is the live count, not only a bound for it
@@ -118,7 +83,7 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
     if (triangles == 0) { ctx->decimate_collapses.push_back(0); break; }   // no edge, no candidate
     const uint32_t edges = 3 * triangles;
     s.tri = tri; s.triangles = triangles; s.edges = edges;
-    if ((rc = decimate_mark(ctx, stream, 0))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 0))) return rc;
     BSLAM_HIP_TRY(hipMemsetAsync(s.fan_start, 0, V * sizeof(uint32_t), stream));
     BSLAM_HIP_TRY(hipMemsetAsync(s.fan_end, 0, V * sizeof(uint32_t), stream));
     BSLAM_HIP_TRY(hipMemsetAsync(s.boundary, 0, V, stream));
@@ -126,11 +91,11 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
     BSLAM_HIP_TRY(hipMemsetAsync(s.words + kDecimateSelected, 0, 2 * sizeof(uint32_t), stream));
     hipLaunchKernelGGL(decimate_keys_kernel, flat_grid(triangles), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = decimate_mark(ctx, stream, 1))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 1))) return rc;
     // stable: the uses of an edge and the fan of a vertex stay in ascending slot, so in ascending triangle
-    if ((rc = decimate_sort(sort_temp, sort_bytes, s.edge_keys, s.sorted_edges, s.ids, s.edge_slots, edges, 2 * bits, stream))) return rc;
-    if ((rc = decimate_sort(sort_temp, sort_bytes, s.vertex_keys, s.sorted_vertices, s.ids, s.fan, edges, bits, stream))) return rc;
-    if ((rc = decimate_mark(ctx, stream, 2))) return rc;
+    if ((rc = mesh_sort(call, sort_temp, sort_bytes, s.edge_keys, s.sorted_edges, s.ids, s.edge_slots, edges, 2 * bits, stream))) return rc;
+    if ((rc = mesh_sort(call, sort_temp, sort_bytes, s.vertex_keys, s.sorted_vertices, s.ids, s.fan, edges, bits, stream))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 2))) return rc;
     hipLaunchKernelGGL(decimate_heads_kernel, flat_grid(edges), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
     if ((rc = device_scan(stream, 0, s.head, edges, false, s.rank, tile_sums, s.words + kDecimateEdges))) return rc;
@@ -138,23 +103,23 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
       hipLaunchKernelGGL(decimate_quadrics_kernel, flat_grid(V), block, 0, stream, s, (double)boundary_weight);
       BSLAM_HIP_TRY(hipGetLastError());
     }
-    if ((rc = decimate_mark(ctx, stream, 3))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 3))) return rc;
     hipLaunchKernelGGL(decimate_eval_kernel, flat_grid(edges), block, 0, stream, s, max_cost);
     BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = decimate_mark(ctx, stream, 4))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 4))) return rc;
     hipLaunchKernelGGL(decimate_neighbourhood_kernel, flat_grid(V), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(decimate_select_kernel, flat_grid(edges), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = decimate_mark(ctx, stream, 5))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 5))) return rc;
     // the read-back of the round: what was selected decides whether it is the last
     if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, 4, &host))) return rc;
     if ((rc = decimate_collect(ctx, 0, 5))) return rc;
-    if ((rc = decimate_error(host[kDecimateError], call))) return rc;
+    if ((rc = mesh_error(host[kDecimateError], call))) return rc;
     uint32_t selected = host[kDecimateSelected];
     const uint32_t removed = host[kDecimateRemoved], room = live_count - target_vertices;
     if (selected == 0) { ctx->decimate_collapses.push_back(0); break; }
-    if ((rc = decimate_mark(ctx, stream, 5))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 5))) return rc;
     const bool cut = selected > room;
     if (cut) {
       // only the first `room` by key collapse: the selected keys to the front, sorted, and the key at room - 1 is the last to pass
@@ -162,21 +127,16 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
       if ((rc = device_scan(stream, 0, s.selected, edges, true, scratch32, tile_sums, s.words + kDecimateCut))) return rc;
       hipLaunchKernelGGL(decimate_cut_gather_kernel, flat_grid(edges), block, 0, stream, s, (const uint32_t*)scratch32, cut_keys);
       BSLAM_HIP_TRY(hipGetLastError());
-      if ((rc = decimate_sort(sort_temp, sort_bytes, cut_keys, cut_sorted, s.ids, scratch32, selected, 64, stream))) return rc;
+      if ((rc = mesh_sort(call, sort_temp, sort_bytes, cut_keys, cut_sorted, s.ids, scratch32, selected, 64, stream))) return rc;
       hipLaunchKernelGGL(decimate_cut_kernel, flat_grid(edges), block, 0, stream, s, (const unsigned long long*)cut_sorted, room);
       BSLAM_HIP_TRY(hipGetLastError());
       selected = room;
     }
     hipLaunchKernelGGL(decimate_apply_kernel, flat_grid(edges), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = decimate_mark(ctx, stream, 6))) return rc;
-    hipLaunchKernelGGL(decimate_keep_kernel, flat_grid(triangles), block, 0, stream, vertex_count, triangles, (const uint32_t*)tri, (const uint32_t*)s.parent, keep, s.words);
-    BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = device_scan(stream, 0, keep, triangles, true, triangle_rank, tile_sums, s.words + kDecimateTriangles))) return rc;
-    hipLaunchKernelGGL(decimate_scatter_kernel, flat_grid(triangles), block, 0, stream, triangles, (const uint32_t*)tri, (const uint32_t*)s.parent, (const uint8_t*)keep,
-                       (const uint32_t*)triangle_rank, tri_next);
-    BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = decimate_mark(ctx, stream, 7))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 6))) return rc;
+    if ((rc = remap_triangles(stream, vertex_count, triangles, tri, s.parent, keep, triangle_rank, tile_sums, s.words, s.words + kDecimateTriangles, tri_next))) return rc;
+    if ((rc = ctx->decimate_events.mark(ctx->profiling, stream, 7))) return rc;
     if (ctx->profiling) {
       BSLAM_HIP_TRY(hipStreamSynchronize(stream));
       if ((rc = decimate_collect(ctx, 5, 7))) return rc;
@@ -201,7 +161,7 @@ int bslam_decimate_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count
     BSLAM_HIP_TRY(hipGetLastError());
   }
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, 8, &host))) return rc;
-  if ((rc = decimate_error(host[kDecimateError], call))) return rc;
+  if ((rc = mesh_error(host[kDecimateError], call))) return rc;
   if (host[kDecimateVertices] != live_count) return fail(BSLAM_ERR_INTERNAL, "%s: %u vertices survive where %u were counted", call, host[kDecimateVertices], live_count);
   if (exact ? host[kDecimateTriangles] != triangles : host[kDecimateTriangles] > triangles)
     return fail(BSLAM_ERR_INTERNAL, "%s: %u triangles are live where %u were counted", call, host[kDecimateTriangles], triangles);

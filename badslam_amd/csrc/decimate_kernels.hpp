@@ -1,8 +1,8 @@
 // decimate_kernels.hpp -- quadric-error edge collapse of an indexed triangle mesh in data-parallel rounds, for gfx950.  Per round: the
-// three edge keys and the three (vertex, slot) keys of every live triangle, two stable radix sorts (rocPRIM, decimate_sort.hip),
+// three edge keys and the three (vertex, slot) keys of every live triangle, two stable radix sorts (rocPRIM, mesh_sort.hip),
 // head flags of the sorted edges and their scan (lifecycle_kernels.hpp), an evaluation pass with one lane per unique edge that walks
 // the triangle fans of its two ends, a minimum per vertex and per vertex neighbourhood that selects collapses with pairwise
-// non-adjacent ends, the collapses, and the keep flag / scan / scatter of the triangles.  The reference has no mesh.
+// non-adjacent ends, the collapses, and the triangle remap of mesh_kernels.hpp through the parents.  The reference has no mesh.
 //
 // The rule (include/badslam_hip.h "Mesh decimation", DESIGN.md 8 "Mesh decimation"): every decision is float64 in separate
 // operations in a stated order, every ordered sum is a walk in that order, and the only atomics are integer: the 64-bit minimum of
@@ -19,7 +19,6 @@
 
 namespace bslam {
 
-constexpr uint32_t kDecimateBadVertex = 8u;   // a bit of the mesh error word: a position is not finite
 constexpr unsigned long long kDecimateNoKey = ~0ull;   // no candidate has it: the bits of a finite cost32 stay below 0x7f800000
 constexpr uint32_t kDecimateGolden = 0x9E3779B1u;
 
@@ -27,12 +26,7 @@ constexpr uint32_t kDecimateGolden = 0x9E3779B1u;
 constexpr int kDecimateError = 0, kDecimateSelected = 1, kDecimateRemoved = 2, kDecimateTriangles = 3, kDecimateVertices = 4, kDecimateEdges = 5,
               kDecimateCut = 6, kDecimateWords = 16;
 
-struct dec3 { double x, y, z; };
-__device__ __forceinline__ dec3 dec_sub(dec3 a, dec3 b) { return dec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ dec3 dec_cross(dec3 u, dec3 v) { return dec3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
 __device__ __forceinline__ double dec_dot(dec3 a, dec3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ dec3 dec_load(const float* __restrict__ p, uint32_t v) { return dec3{(double)p[3 * (size_t)v], (double)p[3 * (size_t)v + 1], (double)p[3 * (size_t)v + 2]}; }
-__device__ __forceinline__ dec3 dec_normal(dec3 a, dec3 b, dec3 c) { return dec_cross(dec_sub(b, a), dec_sub(c, a)); }
 
 // The ten products (xx, xy, xz, xd, yy, yz, yd, zz, zd, dd) of the plane (n, d = -n . a).
 __device__ __forceinline__ void dec_plane_quadric(dec3 n, dec3 a, double* k) {
@@ -89,34 +83,7 @@ __global__ __launch_bounds__(256) void decimate_init_kernel(DecimateState s, con
   }
   if (colors != nullptr) s.colors[v] = colors[v];
   s.parent[v] = v;
-  if (!finite) atomicOr(&s.words[kDecimateError], kDecimateBadVertex);
-}
-
-// keep[t] = the three corners, each taken to what it was merged into, are pairwise distinct.  A triangle with an index >= V raises
-// the error bit and is not kept, so that nothing behind this launch dereferences it.
-__global__ __launch_bounds__(256) void decimate_keep_kernel(uint32_t vertices, uint32_t triangles, const uint32_t* __restrict__ tri, const uint32_t* __restrict__ parent,
-                                                            uint8_t* __restrict__ keep, uint32_t* __restrict__ words) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= triangles) return;
-  const uint32_t i0 = tri[3 * (size_t)t], i1 = tri[3 * (size_t)t + 1], i2 = tri[3 * (size_t)t + 2];
-  if (i0 >= vertices || i1 >= vertices || i2 >= vertices) {
-    atomicOr(&words[kDecimateError], kMeshBadIndex);
-    keep[t] = 0;
-    return;
-  }
-  const uint32_t a = parent[i0], b = parent[i1], c = parent[i2];
-  keep[t] = (a != b && a != c && b != c) ? 1 : 0;
-}
-
-// ... a kept triangle goes to its rank among the kept ones with its corners remapped, in their order.
-__global__ __launch_bounds__(256) void decimate_scatter_kernel(uint32_t triangles, const uint32_t* __restrict__ tri, const uint32_t* __restrict__ parent,
-                                                               const uint8_t* __restrict__ keep, const uint32_t* __restrict__ rank, uint32_t* __restrict__ out) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= triangles || !keep[t]) return;
-  const size_t from = 3 * (size_t)t, to = 3 * (size_t)rank[t];
-  out[to] = parent[tri[from]];
-  out[to + 1] = parent[tri[from + 1]];
-  out[to + 2] = parent[tri[from + 2]];
+  if (!finite) atomicOr(&s.words[kDecimateError], kMeshBadPosition);
 }
 
 // The keys of the two sorts of a round, one triangle per lane.

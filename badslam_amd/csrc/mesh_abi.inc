@@ -1,5 +1,6 @@
-// mesh_abi.inc -- mesh component entry points of include/badslam_hip.h (included by badslam_hip.hip after lifecycle_abi.inc
-// and fusion_abi.inc: device_scan, the fusion slab).
+// mesh_abi.inc -- mesh component entry points of include/badslam_hip.h, and the host pieces the mesh operators behind it share
+// (simplify_abi.inc, decimate_abi.inc, smooth_abi.inc): span checks, the error word, the triangle remap, the radix sort.  Included by
+// badslam_hip.hip after lifecycle_abi.inc and fusion_abi.inc: device_scan, the fusion slab.
 
 namespace bslam {
 
@@ -23,9 +24,32 @@ static int check_mesh_spans(const MeshSpan* spans, int count) {
   return BSLAM_OK;
 }
 
+// An attributed mesh in and out: normals and colors are optional, and each output is given exactly when its input is.
+struct MeshArrays {
+  const float* positions; const float* normals; const void* colors; const uint32_t* indices;
+  float* out_positions; float* out_normals; void* out_colors; uint32_t* out_indices;
+};
+
+static int check_attribute_pairs(const MeshArrays& m) {
+  if ((m.normals != nullptr) != (m.out_normals != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_normals must be given exactly when normals is");
+  if ((m.colors != nullptr) != (m.out_colors != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_colors must be given exactly when colors is");
+  return BSLAM_OK;
+}
+
+// The spans of `m` for V vertices and T triangles: the four inputs to in[0 .. 3], the four outputs to out[0 .. 3].  The caller places
+// them among the spans of its own, in the order in which check_mesh_spans is to report.
+static void mesh_array_spans(const MeshArrays& m, size_t V, size_t T, MeshSpan* in, MeshSpan* out) {
+  const size_t nb = m.normals ? 12 * V : 0, cb = m.colors ? 4 * V : 0;
+  in[0] = {m.positions, 12 * V, "positions", false}; in[1] = {m.normals, nb, "normals", false}; in[2] = {m.colors, cb, "colors", false};
+  in[3] = {m.indices, 12 * T, "indices", false};
+  out[0] = {m.out_positions, 12 * V, "out_positions", true}; out[1] = {m.out_normals, nb, "out_normals", true}; out[2] = {m.out_colors, cb, "out_colors", true};
+  out[3] = {m.out_indices, 12 * T, "out_indices", true};
+}
+
 static int mesh_error(uint32_t bits, const char* call) {
   if (bits & kMeshBadIndex) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a triangle names a vertex beyond vertex_count", call);
   if (bits & kMeshOverrun) return fail(BSLAM_ERR_INTERNAL, "%s: a union-find loop ran into its cap", call);
+  if (bits & kMeshBadPosition) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a vertex is not finite", call);
   return BSLAM_OK;
 }
 
@@ -33,6 +57,54 @@ static int mesh_error(uint32_t bits, const char* call) {
 static int empty_mesh(hipStream_t stream, size_t triangles, const char* call) {
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));
   return triangles != 0 ? mesh_error(kMeshBadIndex, call) : BSLAM_OK;
+}
+
+// A count padded to a multiple of 64, as the scratch arrays of the mesh calls are (and as in bslam_extract_mesh).
+static size_t pad64(size_t count) { return (count + 63) & ~(size_t)63; }
+
+// The bits of a vertex id below V >= 1: at least one.
+static unsigned vertex_id_bits(size_t V) {
+  unsigned bits = 1;
+  while (bits < 32 && (V - 1) >> bits) ++bits;
+  return bits;
+}
+
+// The triangle remap of mesh_kernels.hpp: the keep flags of `triangles` triangles through `map`, their exclusive scan -- whose total
+// goes to *kept, a word of the call's device block -- and the scatter into `out`.  words[0] is the call's error word.  Without
+// triangles the scan alone runs: it writes the total.
+static int remap_triangles(hipStream_t stream, uint32_t vertices, uint32_t triangles, const uint32_t* indices, const uint32_t* map, uint8_t* keep, uint32_t* rank,
+                           uint32_t* tile_sums, uint32_t* words, uint32_t* kept, uint32_t* out) {
+  const dim3 block(256);
+  if (triangles != 0) {
+    hipLaunchKernelGGL(mesh_remap_keep_kernel, flat_grid(triangles), block, 0, stream, vertices, triangles, indices, map, keep, words);
+    BSLAM_HIP_TRY(hipGetLastError());
+  }
+  if (int rc = device_scan(stream, 0, keep, triangles, true, rank, tile_sums, kept)) return rc;
+  if (triangles != 0) {
+    hipLaunchKernelGGL(mesh_remap_scatter_kernel, flat_grid(triangles), block, 0, stream, triangles, indices, map, (const uint8_t*)keep, (const uint32_t*)rank, out);
+    BSLAM_HIP_TRY(hipGetLastError());
+  }
+  return BSLAM_OK;
+}
+
+// mesh_sort.hip
+hipError_t mesh_sort_pairs(void* temp, size_t* temp_bytes, const unsigned long long* keys, unsigned long long* sorted_keys, const uint32_t* ids,
+                           uint32_t* sorted_ids, size_t count, unsigned end_bit, hipStream_t stream);
+
+// The scratch a sort of up to `count` pairs over all 64 key bits needs.
+static int mesh_sort_bytes(size_t count, hipStream_t stream, size_t* bytes) {
+  BSLAM_HIP_TRY(mesh_sort_pairs(nullptr, bytes, nullptr, nullptr, nullptr, nullptr, count, 64, stream));
+  return BSLAM_OK;
+}
+
+// One stable sort of `count` pairs over the key bits [0, end_bit) in the `temp_bytes` of scratch at `temp`.
+static int mesh_sort(const char* call, void* temp, size_t temp_bytes, const unsigned long long* keys, unsigned long long* sorted_keys, const uint32_t* ids,
+                     uint32_t* sorted_ids, size_t count, unsigned end_bit, hipStream_t stream) {
+  size_t need = 0;
+  BSLAM_HIP_TRY(mesh_sort_pairs(nullptr, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
+  if (need > temp_bytes) return fail(BSLAM_ERR_INTERNAL, "%s: a sort of %zu pairs needs %zu bytes of scratch where %zu were reserved", call, count, need, temp_bytes);
+  BSLAM_HIP_TRY(mesh_sort_pairs(temp, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
+  return BSLAM_OK;
 }
 
 }  // namespace bslam
@@ -83,15 +155,14 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   hipStream_t stream = (hipStream_t)stream_;
   if (!ctx || !out_vertex_count || !out_triangle_count) return fail(BSLAM_ERR_INVALID_ARGUMENT, "null argument");
   if (min_vertices < 1) return fail(BSLAM_ERR_INVALID_ARGUMENT, "min_vertices must be >= 1");
-  if ((normals != nullptr) != (out_normals != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_normals must be given exactly when normals is");
-  if ((colors != nullptr) != (out_colors != nullptr)) return fail(BSLAM_ERR_INVALID_ARGUMENT, "out_colors must be given exactly when colors is");
-  const size_t V = vertex_count, T = triangle_count;
-  const MeshSpan spans[9] = {{positions, 12 * V, "positions", false}, {normals, normals ? 12 * V : 0, "normals", false}, {colors, colors ? 4 * V : 0, "colors", false},
-                             {indices, 12 * T, "indices", false}, {sizes, 4 * V, "sizes", false}, {out_positions, 12 * V, "out_positions", true},
-                             {out_normals, normals ? 12 * V : 0, "out_normals", true}, {out_colors, colors ? 4 * V : 0, "out_colors", true},
-                             {out_indices, 12 * T, "out_indices", true}};
-  int rc = check_mesh_spans(spans, 9);
+  const MeshArrays arrays = {positions, normals, colors, indices, out_positions, out_normals, out_colors, out_indices};
+  int rc = check_attribute_pairs(arrays);
   if (rc) return rc;
+  const size_t V = vertex_count, T = triangle_count;
+  MeshSpan spans[9];
+  mesh_array_spans(arrays, V, T, spans, spans + 5);
+  spans[4] = {sizes, 4 * V, "sizes", false};
+  if ((rc = check_mesh_spans(spans, 9))) return rc;
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   if (V == 0) {
     if ((rc = empty_mesh(stream, T, "bslam_filter_mesh")) == BSLAM_OK) *out_vertex_count = *out_triangle_count = 0;
@@ -99,7 +170,7 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   }
   // scratch: keep_vertex u8[V] | keep_triangle u8[T] | vertex_rank u32[V] | triangle_rank u32[T] | tile sums |
   //          words u32[4] = {error bits, unused, kept vertices, kept triangles}
-  const size_t nv = (V + 63) & ~(size_t)63, nt = (T + 63) & ~(size_t)63, tiles = std::max(nv, nt) / kScanTile + 2;   // padded to 64 as in bslam_extract_mesh
+  const size_t nv = pad64(V), nt = pad64(T), tiles = std::max(nv, nt) / kScanTile + 2;
   uint8_t *keep_vertex, *keep_triangle;
   uint32_t *vertex_rank, *triangle_rank, *tile_sums, *words;
   if ((rc = carve(ctx->fusion, [&](Carver& c) {

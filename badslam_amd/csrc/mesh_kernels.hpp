@@ -5,6 +5,9 @@
 //
 // The rule (include/badslam_hip.h, DESIGN.md 8 "Mesh components"): vertices a and b are joined iff a triangle contains both; a
 // component is a class of the transitive closure; label[v] = the smallest vertex id of v's component, size[v] = its vertex count.
+//
+// Behind them, what the mesh operators built on this file share (simplify_, decimate_, smooth_kernels.hpp): the triangle remap --
+// keep flag and scatter of the triangles through a vertex map -- and the float64 vector helpers of their ordered sums.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -13,9 +16,10 @@
 
 namespace bslam {
 
-// Bits of the device error word of both calls.
-constexpr uint32_t kMeshBadIndex = 1u;   // a triangle names a vertex >= V: never dereferenced
-constexpr uint32_t kMeshOverrun = 2u;    // a find or a retry loop ran into its cap: cannot happen while parent[v] <= v holds
+// Bits of the device error word of every mesh call: words[0] of its small device block.
+constexpr uint32_t kMeshBadIndex = 1u;      // a triangle names a vertex >= V: never dereferenced
+constexpr uint32_t kMeshOverrun = 2u;       // a find or a retry loop ran into its cap: cannot happen while parent[v] <= v holds
+constexpr uint32_t kMeshBadPosition = 8u;   // a position is not finite (4 is simplification's own, kSimplifyBadVertex)
 
 // ---------------------------------------------------------------------------------------------
 // Union-find over parent[V] with the invariant parent[v] <= v at all times: a find walks strictly downwards, so it ends after at
@@ -257,5 +261,47 @@ __global__ __launch_bounds__(256) void mesh_scatter_kernel(MeshFilter m, const u
   m.out_indices[to + 1] = vertex_rank[m.indices[from + 1]];
   m.out_indices[to + 2] = vertex_rank[m.indices[from + 2]];
 }
+
+// ---------------------------------------------------------------------------------------------
+// Triangle remap.  map[v] is what vertex v became (its cluster; the vertex it was merged into, or itself).  A triangle is kept iff
+// its three mapped corners are pairwise distinct; an exclusive scan of the flags (device_scan) gives the new ids; a kept triangle
+// goes to its rank with its corners mapped, in their order.
+// ---------------------------------------------------------------------------------------------
+
+// keep[t] as u8.  A triangle with an index >= V raises the error bit and is not kept, so that nothing behind this launch
+// dereferences it.
+__global__ __launch_bounds__(256) void mesh_remap_keep_kernel(uint32_t vertices, uint32_t triangles, const uint32_t* __restrict__ indices, const uint32_t* __restrict__ map,
+                                                              uint8_t* __restrict__ keep, uint32_t* __restrict__ words) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= triangles) return;
+  const uint32_t i0 = indices[3 * (size_t)t], i1 = indices[3 * (size_t)t + 1], i2 = indices[3 * (size_t)t + 2];
+  if (i0 >= vertices || i1 >= vertices || i2 >= vertices) {
+    atomicOr(&words[0], kMeshBadIndex);
+    keep[t] = 0;
+    return;
+  }
+  const uint32_t a = map[i0], b = map[i1], c = map[i2];
+  keep[t] = (a != b && a != c && b != c) ? 1 : 0;
+}
+
+__global__ __launch_bounds__(256) void mesh_remap_scatter_kernel(uint32_t triangles, const uint32_t* __restrict__ indices, const uint32_t* __restrict__ map,
+                                                                 const uint8_t* __restrict__ keep, const uint32_t* __restrict__ rank, uint32_t* __restrict__ out) {
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= triangles || !keep[t]) return;
+  const size_t from = 3 * (size_t)t, to = 3 * (size_t)rank[t];
+  out[to] = map[indices[from]];
+  out[to + 1] = map[indices[from + 1]];
+  out[to + 2] = map[indices[from + 2]];
+}
+
+// ---------------------------------------------------------------------------------------------
+// float64 vectors of the ordered sums of decimation and smoothing: separate operations in the stated order (the library is built
+// without contraction).
+// ---------------------------------------------------------------------------------------------
+struct dec3 { double x, y, z; };
+__device__ __forceinline__ dec3 dec_sub(dec3 a, dec3 b) { return dec3{a.x - b.x, a.y - b.y, a.z - b.z}; }
+__device__ __forceinline__ dec3 dec_cross(dec3 u, dec3 v) { return dec3{u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x}; }
+__device__ __forceinline__ dec3 dec_load(const float* __restrict__ p, uint32_t v) { return dec3{(double)p[3 * (size_t)v], (double)p[3 * (size_t)v + 1], (double)p[3 * (size_t)v + 2]}; }
+__device__ __forceinline__ dec3 dec_normal(dec3 a, dec3 b, dec3 c) { return dec_cross(dec_sub(b, a), dec_sub(c, a)); }
 
 }  // namespace bslam

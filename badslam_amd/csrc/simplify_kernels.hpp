@@ -1,6 +1,6 @@
 // simplify_kernels.hpp -- vertex clustering of an indexed triangle mesh on a uniform grid, for gfx950: a key pass with one vertex per
-// lane, a stable radix sort of (key, vertex id) (rocPRIM, in simplify_abi.inc), head flags of the sorted keys and their scan
-// (lifecycle_kernels.hpp), a cluster pass that walks each segment from its head, and a triangle pass of keep flag, scan and scatter.
+// lane, a stable radix sort of (key, vertex id) (rocPRIM, mesh_sort.hip), head flags of the sorted keys and their scan
+// (lifecycle_kernels.hpp), a cluster pass that walks each segment from its head, and the triangle remap of mesh_kernels.hpp.
 // The reference has no mesh; every mesher its users know ships this step.  With no triangles it is voxel-grid down-sampling.
 //
 // The rule (include/badslam_hip.h "Mesh simplification", DESIGN.md 8 "Mesh simplification"): the cell is fp32 in the form of
@@ -105,33 +105,6 @@ __global__ __launch_bounds__(256) void simplify_cluster_kernel(SimplifyClusters 
     const unsigned long long half = n / 2u;
     m.out_colors[cluster] = (uint32_t)((c0 + half) / n) | ((uint32_t)((c1 + half) / n) << 8) | ((uint32_t)((c2 + half) / n) << 16) | ((uint32_t)((c3 + half) / n) << 24);
   }
-}
-
-// Triangle pass, first half: keep[t] = the three clusters are pairwise distinct.  A triangle with an index >= V raises the error
-// bit and is not kept, so that nothing behind this launch dereferences it.
-__global__ __launch_bounds__(256) void simplify_keep_flags_kernel(uint32_t vertices, uint32_t triangles, const uint32_t* __restrict__ indices,
-                                                                  const uint32_t* __restrict__ vertex_cluster, uint8_t* __restrict__ keep, uint32_t* __restrict__ words) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= triangles) return;
-  const uint32_t i0 = indices[3 * (size_t)t], i1 = indices[3 * (size_t)t + 1], i2 = indices[3 * (size_t)t + 2];
-  if (i0 >= vertices || i1 >= vertices || i2 >= vertices) {
-    atomicOr(&words[kSimplifyError], kMeshBadIndex);
-    keep[t] = 0;
-    return;
-  }
-  const uint32_t a = vertex_cluster[i0], b = vertex_cluster[i1], c = vertex_cluster[i2];
-  keep[t] = (a != b && a != c && b != c) ? 1 : 0;
-}
-
-// ... second half: a kept triangle goes to its rank among the kept ones with its vertices' clusters in their order.
-__global__ __launch_bounds__(256) void simplify_scatter_kernel(uint32_t triangles, const uint32_t* __restrict__ indices, const uint32_t* __restrict__ vertex_cluster,
-                                                               const uint8_t* __restrict__ keep, const uint32_t* __restrict__ rank, uint32_t* __restrict__ out_indices) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= triangles || !keep[t]) return;
-  const size_t from = 3 * (size_t)t, to = 3 * (size_t)rank[t];
-  out_indices[to] = vertex_cluster[indices[from]];
-  out_indices[to + 1] = vertex_cluster[indices[from + 1]];
-  out_indices[to + 2] = vertex_cluster[indices[from + 2]];
 }
 
 }  // namespace bslam

@@ -1,27 +1,5 @@
-// smooth_abi.inc -- bslam_smooth_mesh of include/badslam_hip.h (included by badslam_hip.hip after decimate_abi.inc:
-// check_mesh_spans, empty_mesh, device_scan, flat_grid, read_back, carve, decimate_sort_pairs, decimate_error).
-
-namespace bslam {
-
-// Event `at` (0 .. 6) of a call: 0 .. 3 bound keys, sorts and adjacency, 4 .. 6 -- behind the read-back -- steps and normals.
-static int smooth_mark(bslam_context* ctx, hipStream_t stream, int at) {
-  if (!ctx->profiling) return BSLAM_OK;
-  if (!ctx->smooth_events[at]) BSLAM_HIP_TRY(hipEventCreate(&ctx->smooth_events[at]));
-  BSLAM_HIP_TRY(hipEventRecord(ctx->smooth_events[at], stream));
-  return BSLAM_OK;
-}
-
-// One sort of `count` pairs over the key bits [0, end_bit) in the `temp_bytes` of scratch at `temp`: decimation's, under this call's name.
-static int smooth_sort(void* temp, size_t temp_bytes, const unsigned long long* keys, unsigned long long* sorted_keys, const uint32_t* ids, uint32_t* sorted_ids,
-                       size_t count, unsigned end_bit, hipStream_t stream) {
-  size_t need = 0;
-  BSLAM_HIP_TRY(decimate_sort_pairs(nullptr, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
-  if (need > temp_bytes) return fail(BSLAM_ERR_INTERNAL, "bslam_smooth_mesh: a sort of %zu pairs needs %zu bytes of scratch where %zu were reserved", count, need, temp_bytes);
-  BSLAM_HIP_TRY(decimate_sort_pairs(temp, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
-  return BSLAM_OK;
-}
-
-}  // namespace bslam
+// smooth_abi.inc -- bslam_smooth_mesh of include/badslam_hip.h (included by badslam_hip.hip after mesh_abi.inc:
+// check_mesh_spans, mesh_error, empty_mesh, pad64, vertex_id_bits, mesh_sort; device_scan, flat_grid, read_back, carve).
 
 extern "C" {
 
@@ -44,16 +22,15 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   BSLAM_HIP_TRY(hipSetDevice(ctx->device));
   for (float& ms : ctx->smooth_stage_ms) ms = 0.f;
   if (V == 0) return empty_mesh(stream, T, call);
-  unsigned bits = 1;
-  while (bits < 32 && (V - 1) >> bits) ++bits;
+  const unsigned bits = vertex_id_bits(V);
   const uint32_t steps = T == 0 ? 0u : iterations * (mu != 0.f ? 2u : 1u);
   const bool fans = T != 0 && out_normals != nullptr;
   // scratch: words | per directed pair (P = 6 T): keys, sorted keys, ids, slots, head flags, ranks, neighbours, rim flags | per corner (3 T), when
   //          normals are asked for: keys, sorted keys, the fans | per vertex: list and fan ends, boundary flags | the working positions of the steps
   //          between the first and the last | scan sums | the sort's own
-  const size_t P = 6 * T, C3 = fans ? 3 * T : 0, nv = (V + 63) & ~(size_t)63, np = (P + 63) & ~(size_t)63, nc = (C3 + 63) & ~(size_t)63, tiles = np / kScanTile + 2;
+  const size_t P = 6 * T, C3 = fans ? 3 * T : 0, nv = pad64(V), np = pad64(P), nc = pad64(C3), tiles = np / kScanTile + 2;
   size_t sort_bytes = 0;
-  BSLAM_HIP_TRY(decimate_sort_pairs(nullptr, &sort_bytes, nullptr, nullptr, nullptr, nullptr, std::max<size_t>(P, 1), 64, stream));
+  if ((rc = mesh_sort_bytes(std::max<size_t>(P, 1), stream, &sort_bytes))) return rc;
   SmoothState s = {};
   uint32_t* tile_sums;
   uint8_t* sort_temp;
@@ -73,20 +50,20 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   s.vertices = vertex_count; s.triangles = triangle_count; s.pairs = (uint32_t)P; s.corners = (uint32_t)(3 * T); s.bits = bits; s.tri = indices;
   const dim3 block(256);
   BSLAM_HIP_TRY(hipMemsetAsync(s.words, 0, kSmoothWords * sizeof(uint32_t), stream));
-  if ((rc = smooth_mark(ctx, stream, 0))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 0))) return rc;
   hipLaunchKernelGGL(smooth_check_kernel, flat_grid(V), block, 0, stream, vertex_count, positions, s.words);
   BSLAM_HIP_TRY(hipGetLastError());
   if (T != 0) {
     hipLaunchKernelGGL(smooth_keys_kernel, flat_grid(T), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
   }
-  if ((rc = smooth_mark(ctx, stream, 1))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 1))) return rc;
   if (T != 0) {
     // stable: the fan of a vertex stays in ascending slot, so in ascending triangle
-    if ((rc = smooth_sort(sort_temp, sort_bytes, s.pair_keys, s.sorted_pairs, s.ids, s.pair_slots, P, 2 * bits, stream))) return rc;
-    if (fans && (rc = smooth_sort(sort_temp, sort_bytes, s.fan_keys, s.sorted_fans, s.ids, s.fan, 3 * T, bits + 1, stream))) return rc;
+    if ((rc = mesh_sort(call, sort_temp, sort_bytes, s.pair_keys, s.sorted_pairs, s.ids, s.pair_slots, P, 2 * bits, stream))) return rc;
+    if (fans && (rc = mesh_sort(call, sort_temp, sort_bytes, s.fan_keys, s.sorted_fans, s.ids, s.fan, 3 * T, bits + 1, stream))) return rc;
   }
-  if ((rc = smooth_mark(ctx, stream, 2))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 2))) return rc;
   if (T != 0) {
     BSLAM_HIP_TRY(hipMemsetAsync(s.list_start, 0, V * sizeof(uint32_t), stream));
     BSLAM_HIP_TRY(hipMemsetAsync(s.list_end, 0, V * sizeof(uint32_t), stream));
@@ -103,12 +80,12 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
       BSLAM_HIP_TRY(hipGetLastError());
     }
   }
-  if ((rc = smooth_mark(ctx, stream, 3))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 3))) return rc;
   // the one read-back: nothing is written to the outputs before the error word is known
   const uint32_t* host = nullptr;
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, 2, &host))) return rc;
-  if ((rc = decimate_error(host[kSmoothError], call))) return rc;
-  if ((rc = smooth_mark(ctx, stream, 4))) return rc;
+  if ((rc = mesh_error(host[kSmoothError], call))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 4))) return rc;
   if (steps == 0) {
     BSLAM_HIP_TRY(hipMemcpyAsync(out_positions, positions, 12 * V, hipMemcpyDeviceToDevice, stream));
   } else {
@@ -121,16 +98,17 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
       from = to;
     }
   }
-  if ((rc = smooth_mark(ctx, stream, 5))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 5))) return rc;
   if (out_normals != nullptr) {
     hipLaunchKernelGGL(smooth_normals_kernel, flat_grid(V), block, 0, stream, s, (const float*)out_positions, normals, out_normals, fans ? 1 : 0);
     BSLAM_HIP_TRY(hipGetLastError());
   }
-  if ((rc = smooth_mark(ctx, stream, 6))) return rc;
+  if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 6))) return rc;
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));
   if (ctx->profiling) {
     const int from[5] = {0, 1, 2, 4, 5};
-    for (int st = 0; st < 5; ++st) BSLAM_HIP_TRY(hipEventElapsedTime(&ctx->smooth_stage_ms[st], ctx->smooth_events[from[st]], ctx->smooth_events[from[st] + 1]));
+    for (int st = 0; st < 5; ++st)
+      if ((rc = ctx->smooth_events.elapsed(from[st], from[st] + 1, &ctx->smooth_stage_ms[st]))) return rc;
   }
   return BSLAM_OK;
 }

@@ -1,6 +1,6 @@
 // smooth_kernels.hpp -- Taubin lambda|mu smoothing of an indexed triangle mesh and vertex normals from its geometry, for gfx950.
 // Once per call: the six directed pairs v << bits | u and the three (vertex, slot) keys of every live triangle, two stable radix
-// sorts (rocPRIM, decimate_sort.hip), head flags of the sorted pairs and their scan (lifecycle_kernels.hpp), and a pass that
+// sorts (rocPRIM, mesh_sort.hip), head flags of the sorted pairs and their scan (lifecycle_kernels.hpp), and a pass that
 // turns the runs into a CSR neighbour list per vertex -- ascending in u by construction, with the run length 1 as the rim flag --
 // and the fans.  Per step: one lane per vertex walks its list over the previous positions and writes the other buffer.  The
 // reference has no mesh.
@@ -14,7 +14,8 @@
 
 #include <cstdint>
 
-#include "decimate_kernels.hpp"
+#include "distance_kernels.hpp"
+#include "mesh_kernels.hpp"
 
 namespace bslam {
 
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void smooth_check_kernel(uint32_t vertices, co
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= vertices) return;
   const bool finite = pmd_finite(positions[3 * (size_t)v]) && pmd_finite(positions[3 * (size_t)v + 1]) && pmd_finite(positions[3 * (size_t)v + 2]);
-  if (!finite) atomicOr(&words[kSmoothError], kDecimateBadVertex);
+  if (!finite) atomicOr(&words[kSmoothError], kMeshBadPosition);
 }
 
 // The keys of the two sorts, one triangle per lane.  A triangle with an index >= V raises the error bit and, like one that repeats

@@ -274,6 +274,18 @@ int bsh_mesh_copy(float* positions, float* normals, uint8_t* colors, uint32_t* i
     g_mesh = DirectBA::Mesh();
   });
 }
+// A host mesh from a caller's arrays: normals, colors (4 bytes per vertex) and indices may be null.
+static DirectBA::Mesh mesh_from(uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles, const uint32_t* indices) {
+  DirectBA::Mesh mesh;
+  mesh.positions.assign(positions, positions + 3 * vertices);
+  if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
+  if (colors) {
+    mesh.colors.resize(vertices);
+    std::memcpy(mesh.colors.data(), colors, 4 * vertices);
+  }
+  if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+  return mesh;
+}
 // DirectBA::SimplifyMesh of host arrays in two steps, like the mesh: bsh_simplify_mesh (normals, colors -- 4 bytes per vertex --
 // and indices may be null; origin3: x y z) keeps the result for this thread and reports counts2 = {vertices, triangles};
 // bsh_simplified_copy copies it out (normals and colors only where the input had them; vertex_cluster: one entry per input vertex;
@@ -285,14 +297,7 @@ int bsh_simplify_mesh(void* ba, void* stream, uint64_t vertices, const float* po
   BSH_TRY({
     g_simplified = DirectBA::Mesh();
     g_simplified_cluster.clear();
-    DirectBA::Mesh mesh;
-    mesh.positions.assign(positions, positions + 3 * vertices);
-    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
-    if (colors) {
-      mesh.colors.resize(vertices);
-      std::memcpy(mesh.colors.data(), colors, 4 * vertices);
-    }
-    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, colors, triangles, indices);
     static_cast<DirectBA*>(ba)->SimplifyMesh(static_cast<hipStream_t>(stream), mesh, origin3, cell_size, &g_simplified, &g_simplified_cluster);
     counts2[0] = g_simplified.vertex_count();
     counts2[1] = g_simplified.triangle_count();
@@ -319,14 +324,7 @@ int bsh_decimate_mesh(void* ba, void* stream, uint64_t vertices, const float* po
   BSH_TRY({
     g_decimated = DirectBA::Mesh();
     g_decimated_map.clear();
-    DirectBA::Mesh mesh;
-    mesh.positions.assign(positions, positions + 3 * vertices);
-    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
-    if (colors) {
-      mesh.colors.resize(vertices);
-      std::memcpy(mesh.colors.data(), colors, 4 * vertices);
-    }
-    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, colors, triangles, indices);
     DirectBA::DecimateOptions options;
     options.target_vertices = target_vertices;
     options.boundary_weight = boundary_weight;
@@ -352,20 +350,21 @@ int bsh_decimated_copy(float* positions, float* normals, uint8_t* colors, uint32
 // 2 free) keeps the new positions and normals for this thread; bsh_smoothed_copy copies them out (either pointer may be null) and
 // drops them.  Colours and indices are the caller's own.
 static thread_local DirectBA::Mesh g_smoothed;
+static DirectBA::SmoothOptions smooth_options(uint32_t iterations, float lambda, float mu, uint32_t boundary) {
+  if (boundary > 2u) throw std::invalid_argument("SmoothMesh: boundary must be 0 (fixed), 1 (rim) or 2 (free)");
+  DirectBA::SmoothOptions options;
+  options.iterations = iterations;
+  options.lambda = lambda;
+  options.mu = mu;
+  options.boundary = static_cast<DirectBA::SmoothBoundary>(boundary);
+  return options;
+}
 int bsh_smooth_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, uint64_t triangles, const uint32_t* indices,
                     uint32_t iterations, float lambda, float mu, uint32_t boundary) {
   BSH_TRY({
     g_smoothed = DirectBA::Mesh();
-    if (boundary > 2u) throw std::invalid_argument("SmoothMesh: boundary must be 0 (fixed), 1 (rim) or 2 (free)");
-    DirectBA::Mesh mesh;
-    mesh.positions.assign(positions, positions + 3 * vertices);
-    if (normals) mesh.normals.assign(normals, normals + 3 * vertices);
-    if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
-    DirectBA::SmoothOptions options;
-    options.iterations = iterations;
-    options.lambda = lambda;
-    options.mu = mu;
-    options.boundary = static_cast<DirectBA::SmoothBoundary>(boundary);
+    const DirectBA::SmoothOptions options = smooth_options(iterations, lambda, mu, boundary);
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, nullptr, triangles, indices);
     static_cast<DirectBA*>(ba)->SmoothMesh(static_cast<hipStream_t>(stream), mesh, options, &g_smoothed);
   });
 }
@@ -374,14 +373,8 @@ int bsh_smooth_mesh(void* ba, void* stream, uint64_t vertices, const float* posi
 int bsh_smooth_extracted_mesh(void* ba, void* stream, uint32_t iterations, float lambda, float mu, uint32_t boundary, uint64_t* vertices) {
   BSH_TRY({
     g_smoothed = DirectBA::Mesh();
-    if (boundary > 2u) throw std::invalid_argument("SmoothMesh: boundary must be 0 (fixed), 1 (rim) or 2 (free)");
-    DirectBA::SmoothOptions options;
-    options.iterations = iterations;
-    options.lambda = lambda;
-    options.mu = mu;
-    options.boundary = static_cast<DirectBA::SmoothBoundary>(boundary);
     const hipStream_t s = static_cast<hipStream_t>(stream);
-    const DirectBA::DeviceSmoothedMesh d = static_cast<DirectBA*>(ba)->SmoothMeshOnDevice(s, options);
+    const DirectBA::DeviceMesh d = static_cast<DirectBA*>(ba)->SmoothMeshOnDevice(s, smooth_options(iterations, lambda, mu, boundary));
     g_smoothed.positions.resize(size_t{3} * d.vertices);
     g_smoothed.normals.resize(size_t{3} * d.vertices);
     d.positions->Download(s, g_smoothed.positions.data(), g_smoothed.positions.size());

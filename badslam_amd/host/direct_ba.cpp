@@ -571,19 +571,11 @@ void DirectBA::ExtractMesh(hipStream_t stream, const MeshOptions& options, Mesh*
           "bslam_filter_mesh");
   }
   DeviceMesh& out = filter ? kept : m;
-  mesh->positions.resize(3 * static_cast<size_t>(out.vertices));
-  mesh->normals.resize(3 * static_cast<size_t>(out.vertices));
-  mesh->colors.resize(out.vertices);
-  mesh->indices.resize(3 * static_cast<size_t>(out.triangles));
   std::vector<u32> host_labels(report ? labels.count() : 0), host_sizes(host_labels.size());
-  // the one download: everything is enqueued, then the stream is waited for once
-  out.positions->Download(stream, mesh->positions.data(), mesh->positions.size());
-  out.normals->Download(stream, mesh->normals.data(), mesh->normals.size());
-  out.colors->Download(stream, mesh->colors.data(), mesh->colors.size());
-  out.indices->Download(stream, mesh->indices.data(), mesh->indices.size());
+  // the one download: the labels and sizes of the report ride on the wait of DownloadMesh
   labels.Download(stream, host_labels.data(), host_labels.size());
   sizes.Download(stream, host_sizes.data(), host_sizes.size());
-  Wait(stream);
+  DownloadMesh(stream, out, mesh, nullptr);
   if (report && label) {
     report->components = components;
     report->removed_vertices = vertices - out.vertices;
@@ -600,6 +592,65 @@ void DirectBA::KeepDeviceMesh(DeviceMesh mesh) {
   mesh_triangles_ = mesh.triangles;
   mesh_extracted_ = true;
 }
+
+void DirectBA::CheckMeshSizes(const Mesh& mesh, const char* who, unsigned what, size_t points) {
+  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
+  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull ||
+      3 * static_cast<uint64_t>(points) > 0x7fffffffull)
+    throw std::invalid_argument(std::string(who) + ": positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  if (((what & kMeshNormals) && !mesh.normals.empty() && mesh.normals.size() != 3 * V) ||
+      ((what & kMeshColors) && !mesh.colors.empty() && mesh.colors.size() != V))
+    throw std::invalid_argument(std::string(who) + ": normals and colors need one entry per vertex, or none");
+}
+
+DirectBA::DeviceMesh DirectBA::UploadMesh(hipStream_t stream, const Mesh& mesh, const char* who, unsigned what, const std::vector<u32>* indices) {
+  if (who) CheckMeshSizes(mesh, who, what);
+  const size_t V = mesh.vertex_count();
+  const bool normals = (what & kMeshNormals) && !mesh.normals.empty(), colors = (what & kMeshColors) && !mesh.colors.empty();
+  const std::vector<u32>& triangles = indices ? *indices : mesh.indices;
+  DeviceMesh m;
+  m.vertices = static_cast<u32>(V);
+  m.triangles = static_cast<u32>(triangles.size() / 3);
+  if (what & kMeshPositions) {
+    m.positions.reset(new DeviceArray<float>(3 * V));
+    m.positions->Upload(stream, mesh.positions.data(), 3 * V);
+  }
+  if (normals) {
+    m.normals.reset(new DeviceArray<float>(3 * V));
+    m.normals->Upload(stream, mesh.normals.data(), 3 * V);
+  }
+  if (colors) {
+    m.colors.reset(new DeviceArray<uchar4_t>(V));
+    m.colors->Upload(stream, mesh.colors.data(), V);
+  }
+  if (what & kMeshIndices) {
+    m.indices.reset(new DeviceArray<u32>(triangles.size()));
+    m.indices->Upload(stream, triangles.data(), triangles.size());
+  }
+  Wait(stream);
+  return m;
+}
+
+void DirectBA::DownloadMesh(hipStream_t stream, const DeviceMesh& mesh, Mesh* out, std::vector<u32>* map) {
+  const size_t V = mesh.vertices, T = mesh.triangles;
+  out->positions.resize(mesh.positions ? 3 * V : 0);
+  out->normals.resize(mesh.normals ? 3 * V : 0);
+  out->colors.resize(mesh.colors ? V : 0);
+  out->indices.resize(mesh.indices ? 3 * T : 0);
+  if (mesh.positions) mesh.positions->Download(stream, out->positions.data(), 3 * V);
+  if (mesh.normals) mesh.normals->Download(stream, out->normals.data(), 3 * V);
+  if (mesh.colors) mesh.colors->Download(stream, out->colors.data(), V);
+  if (mesh.indices) mesh.indices->Download(stream, out->indices.data(), 3 * T);
+  if (map && mesh.vertex_map) {
+    map->resize(mesh.vertex_map->count());
+    mesh.vertex_map->Download(stream, map->data(), map->size());
+  }
+  Wait(stream);
+}
+
+// The address of an array a DeviceMesh may lack.
+template <typename T>
+static T* AddressOf(const std::unique_ptr<DeviceArray<T>>& array) { return array ? array->address() : nullptr; }
 
 void DirectBA::PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count, const float* points, u32 vertices, const float* positions, u32 triangles,
                                          const u32* indices, const PointMeshOptions& options, PointMeshResult* result) {
@@ -629,17 +680,11 @@ void DirectBA::PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count,
 }
 
 void DirectBA::PointMeshDistance(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const PointMeshOptions& options, PointMeshResult* result) {
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
-      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull || 3 * static_cast<uint64_t>(point_count) > 0x7fffffffull)
-    throw std::invalid_argument("PointMeshDistance: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  DeviceArray<float> dev_points(3 * point_count), dev_positions(mesh.positions.size());
-  DeviceArray<u32> dev_indices(mesh.indices.size());
+  CheckMeshSizes(mesh, "PointMeshDistance", kMeshPositions | kMeshIndices, point_count);
+  DeviceArray<float> dev_points(3 * point_count);
   dev_points.Upload(stream, points, 3 * point_count);
-  dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
-  dev_indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
-  Wait(stream);   // the host arrays are the caller's and pageable
-  PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), static_cast<u32>(mesh.vertex_count()), dev_positions.address(),
-                            static_cast<u32>(mesh.triangle_count()), dev_indices.address(), options, result);
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshIndices);   // its wait covers the points
+  PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), m.vertices, m.positions->address(), m.triangles, m.indices->address(), options, result);
 }
 
 std::vector<float> DirectBA::ValidSurfelCentres(hipStream_t stream) const {
@@ -688,16 +733,8 @@ DirectBA::DeviceSamples DirectBA::SampleMeshOnDevice(hipStream_t stream, float d
 }
 
 void DirectBA::SampleMesh(hipStream_t stream, const Mesh& mesh, float density, u32 seed, MeshSamples* samples) {
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
-      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull)
-    throw std::invalid_argument("SampleMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  DeviceArray<float> dev_positions(mesh.positions.size());
-  DeviceArray<u32> dev_indices(mesh.indices.size());
-  dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
-  dev_indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
-  Wait(stream);   // the host arrays are the caller's and pageable
-  const DeviceSamples s = SampleMeshOnDevice(stream, static_cast<u32>(mesh.vertex_count()), dev_positions.address(), static_cast<u32>(mesh.triangle_count()),
-                                             dev_indices.address(), density, seed);
+  const DeviceMesh m = UploadMesh(stream, mesh, "SampleMesh", kMeshPositions | kMeshIndices);
+  const DeviceSamples s = SampleMeshOnDevice(stream, m.vertices, m.positions->address(), m.triangles, m.indices->address(), density, seed);
   const size_t n = static_cast<size_t>(s.count);
   samples->positions.resize(3 * n);
   samples->normals.resize(3 * n);
@@ -720,9 +757,7 @@ const char* DirectBA::RegistrationReason(int end) {
 
 void DirectBA::RegisterPoints(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, const RegistrationOptions& options,
                               RegistrationResult* result) {
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(mesh.triangle_count()) > 0x7fffffffull ||
-      3 * static_cast<uint64_t>(mesh.vertex_count()) > 0x7fffffffull || 3 * static_cast<uint64_t>(point_count) > 0x7fffffffull)
-    throw std::invalid_argument("RegisterPoints: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
+  CheckMeshSizes(mesh, "RegisterPoints", kMeshPositions | kMeshIndices, point_count);
   if (!(options.max_distance > 0.f) || !(options.shrink > 0.0 && options.shrink < 1.0) || options.iterations_per_stage < 1 || options.min_distance < 0.f ||
       options.huber < 0.f)
     throw std::invalid_argument("RegisterPoints: max_distance > 0, 0 < shrink < 1, iterations_per_stage >= 1, min_distance and huber >= 0 are required");
@@ -735,21 +770,16 @@ void DirectBA::RegisterPoints(hipStream_t stream, const float* points, size_t po
     own.resize(mesh.positions.size());
     for (size_t i = 0; i < own.size(); ++i) own[i] = static_cast<u32>(i / 3);
   }
-  const std::vector<u32>& indices = cloud ? own : mesh.indices;
   const int mode = options.mode >= 0 ? options.mode : (cloud ? BSLAM_REGISTRATION_POINT : BSLAM_REGISTRATION_PLANE);
-  const u32 n = static_cast<u32>(point_count), vertices = static_cast<u32>(mesh.vertex_count()), triangles = static_cast<u32>(indices.size() / 3);
+  const u32 n = static_cast<u32>(point_count);
   *result = RegistrationResult();
   std::copy(options.initial, options.initial + 16, result->target_T_source);
   {
-    DeviceArray<float> dev_positions(mesh.positions.size());
-    DeviceArray<u32> dev_indices(indices.size());
-    dev_positions.Upload(stream, mesh.positions.data(), mesh.positions.size());
-    dev_indices.Upload(stream, indices.data(), indices.size());
-    Wait(stream);
+    const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshIndices, cloud ? &own : nullptr);
     float cell = options.cell_size > 0.f ? options.cell_size : options.max_distance;
     for (int attempt = 0;; ++attempt) {
       uint64_t cells = 0, entries = 0;
-      const int rc = bslam_registration_prepare(ctx_, stream, vertices, dev_positions.address(), triangles, dev_indices.address(), options.max_distance, cell,
+      const int rc = bslam_registration_prepare(ctx_, stream, m.vertices, m.positions->address(), m.triangles, m.indices->address(), options.max_distance, cell,
                                                 options.max_grid_entries, &cells, &entries);
       const bool over_budget = rc == BSLAM_ERR_INVALID_ARGUMENT && (entries > options.max_grid_entries || cells > BSLAM_POINT_MESH_MAX_CELLS);
       if (over_budget && !(options.cell_size > 0.f) && attempt < 64 && std::isfinite(cell * 2.f)) { cell *= 2.f; continue; }
@@ -819,117 +849,63 @@ u32 DirectBA::MeshComponents(hipStream_t stream, const Mesh& mesh, std::vector<u
   if (labels) labels->assign(vertices, 0u);
   if (sizes) sizes->assign(vertices, 0u);
   if (3 * static_cast<uint64_t>(triangles) > 0x7fffffffull || vertices > 0x7fffffffu) throw std::invalid_argument("MeshComponents: the mesh is too large for one device image");
-  DeviceArray<u32> indices(mesh.indices.size()), dev_labels(vertices), dev_sizes(vertices);
-  indices.Upload(stream, mesh.indices.data(), mesh.indices.size());
-  Wait(stream);
+  DeviceArray<u32> dev_labels(vertices), dev_sizes(vertices);
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshIndices);
   u32 components = 0;
-  Check(bslam_mesh_components(ctx_, stream, vertices, triangles, indices.address(), dev_labels.address(), dev_sizes.address(), &components), "bslam_mesh_components");
+  Check(bslam_mesh_components(ctx_, stream, vertices, triangles, m.indices->address(), dev_labels.address(), dev_sizes.address(), &components), "bslam_mesh_components");
   if (labels) dev_labels.Download(stream, labels->data(), vertices);
   if (sizes) dev_sizes.Download(stream, sizes->data(), vertices);
   Wait(stream);
   return components;
 }
 
-DirectBA::DeviceSimplifiedMesh DirectBA::SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
-                                                              const uchar4_t* colors, const u32* indices, const float origin[3], float cell_size) {
-  DeviceSimplifiedMesh s;
-  s.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
-  if (normals) s.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
-  if (colors) s.colors.reset(new DeviceArray<uchar4_t>(vertices));
-  s.indices.reset(new DeviceArray<u32>(size_t{3} * triangles));
-  s.vertex_cluster.reset(new DeviceArray<u32>(vertices));
-  Check(bslam_simplify_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, origin, cell_size, s.positions->address(),
-                            s.normals ? s.normals->address() : nullptr, s.colors ? s.colors->address() : nullptr, s.indices->address(), s.vertex_cluster->address(),
-                            &s.vertices, &s.triangles),
+// The room of an operator's result: positions and indices for the input's counts, normals and colours where the input has them.
+static DirectBA::DeviceMesh ResultMesh(u32 vertices, u32 triangles, bool normals, bool colors, bool indices, bool vertex_map) {
+  DirectBA::DeviceMesh m;
+  m.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (normals) m.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
+  if (colors) m.colors.reset(new DeviceArray<uchar4_t>(vertices));
+  if (indices) m.indices.reset(new DeviceArray<u32>(size_t{3} * triangles));
+  if (vertex_map) m.vertex_map.reset(new DeviceArray<u32>(vertices));
+  return m;
+}
+
+DirectBA::DeviceMesh DirectBA::SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                                    const u32* indices, const float origin[3], float cell_size) {
+  DeviceMesh s = ResultMesh(vertices, triangles, normals, colors, true, true);
+  Check(bslam_simplify_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, origin, cell_size, s.positions->address(), AddressOf(s.normals),
+                            AddressOf(s.colors), s.indices->address(), s.vertex_map->address(), &s.vertices, &s.triangles),
         "bslam_simplify_mesh");
   return s;
 }
 
 void DirectBA::SimplifyMesh(hipStream_t stream, const Mesh& mesh, const float origin[3], float cell_size, Mesh* out, std::vector<u32>* vertex_cluster) {
-  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
-    throw std::invalid_argument("SimplifyMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
-    throw std::invalid_argument("SimplifyMesh: normals and colors need one entry per vertex, or none");
-  const bool has_normals = !mesh.normals.empty(), has_colors = !mesh.colors.empty();
-  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
-  DeviceArray<uchar4_t> dev_colors(mesh.colors.size());
-  DeviceArray<u32> dev_indices(3 * T);
-  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
-  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
-  dev_colors.Upload(stream, mesh.colors.data(), mesh.colors.size());
-  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
-  Wait(stream);   // the host arrays are the caller's and pageable
-  const DeviceSimplifiedMesh s = SimplifyMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
-                                                      has_colors ? dev_colors.address() : nullptr, dev_indices.address(), origin, cell_size);
-  out->positions.resize(3 * static_cast<size_t>(s.vertices));
-  out->normals.resize(has_normals ? 3 * static_cast<size_t>(s.vertices) : 0);
-  out->colors.resize(has_colors ? s.vertices : 0);
-  out->indices.resize(3 * static_cast<size_t>(s.triangles));
-  s.positions->Download(stream, out->positions.data(), out->positions.size());
-  if (has_normals) s.normals->Download(stream, out->normals.data(), out->normals.size());
-  if (has_colors) s.colors->Download(stream, out->colors.data(), out->colors.size());
-  s.indices->Download(stream, out->indices.data(), out->indices.size());
-  if (vertex_cluster) {
-    vertex_cluster->resize(V);
-    s.vertex_cluster->Download(stream, vertex_cluster->data(), V);
-  }
-  Wait(stream);
+  const DeviceMesh m = UploadMesh(stream, mesh, "SimplifyMesh", kMeshAll);
+  DownloadMesh(stream, SimplifyMeshOnDevice(stream, m.vertices, m.triangles, m.positions->address(), AddressOf(m.normals), AddressOf(m.colors), m.indices->address(),
+                                            origin, cell_size),
+               out, vertex_cluster);
 }
 
-DirectBA::DeviceDecimatedMesh DirectBA::DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
-                                                             const uchar4_t* colors, const u32* indices, const DecimateOptions& options) {
-  DeviceDecimatedMesh d;
-  d.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
-  if (normals) d.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
-  if (colors) d.colors.reset(new DeviceArray<uchar4_t>(vertices));
-  d.indices.reset(new DeviceArray<u32>(size_t{3} * triangles));
-  d.vertex_map.reset(new DeviceArray<u32>(vertices));
+DirectBA::DeviceMesh DirectBA::DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                                    const u32* indices, const DecimateOptions& options) {
+  DeviceMesh d = ResultMesh(vertices, triangles, normals, colors, true, true);
   Check(bslam_decimate_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, options.target_vertices, options.boundary_weight, options.max_cost,
-                            options.max_rounds, d.positions->address(), d.normals ? d.normals->address() : nullptr, d.colors ? d.colors->address() : nullptr,
-                            d.indices->address(), d.vertex_map->address(), &d.vertices, &d.triangles, &d.rounds),
+                            options.max_rounds, d.positions->address(), AddressOf(d.normals), AddressOf(d.colors), d.indices->address(), d.vertex_map->address(),
+                            &d.vertices, &d.triangles, &d.rounds),
         "bslam_decimate_mesh");
   return d;
 }
 
 u32 DirectBA::DecimateMesh(hipStream_t stream, const Mesh& mesh, const DecimateOptions& options, Mesh* out, std::vector<u32>* vertex_map) {
-  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
-    throw std::invalid_argument("DecimateMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
-    throw std::invalid_argument("DecimateMesh: normals and colors need one entry per vertex, or none");
-  const bool has_normals = !mesh.normals.empty(), has_colors = !mesh.colors.empty();
-  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
-  DeviceArray<uchar4_t> dev_colors(mesh.colors.size());
-  DeviceArray<u32> dev_indices(3 * T);
-  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
-  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
-  dev_colors.Upload(stream, mesh.colors.data(), mesh.colors.size());
-  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
-  Wait(stream);   // the host arrays are the caller's and pageable
-  const DeviceDecimatedMesh d = DecimateMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
-                                                     has_colors ? dev_colors.address() : nullptr, dev_indices.address(), options);
-  out->positions.resize(3 * static_cast<size_t>(d.vertices));
-  out->normals.resize(has_normals ? 3 * static_cast<size_t>(d.vertices) : 0);
-  out->colors.resize(has_colors ? d.vertices : 0);
-  out->indices.resize(3 * static_cast<size_t>(d.triangles));
-  d.positions->Download(stream, out->positions.data(), out->positions.size());
-  if (has_normals) d.normals->Download(stream, out->normals.data(), out->normals.size());
-  if (has_colors) d.colors->Download(stream, out->colors.data(), out->colors.size());
-  d.indices->Download(stream, out->indices.data(), out->indices.size());
-  if (vertex_map) {
-    vertex_map->resize(V);
-    d.vertex_map->Download(stream, vertex_map->data(), V);
-  }
-  Wait(stream);
+  const DeviceMesh m = UploadMesh(stream, mesh, "DecimateMesh", kMeshAll);
+  const DeviceMesh d = DecimateMeshOnDevice(stream, m.vertices, m.triangles, m.positions->address(), AddressOf(m.normals), AddressOf(m.colors), m.indices->address(), options);
+  DownloadMesh(stream, d, out, vertex_map);
   return d.rounds;
 }
 
-DirectBA::DeviceSmoothedMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals,
-                                                          const u32* indices, const SmoothOptions& options) {
-  DeviceSmoothedMesh d;
-  d.positions.reset(new DeviceArray<float>(size_t{3} * vertices));
-  d.normals.reset(new DeviceArray<float>(size_t{3} * vertices));
+DirectBA::DeviceMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const u32* indices,
+                                                  const SmoothOptions& options) {
+  DeviceMesh d = ResultMesh(vertices, triangles, true, false, false, false);
   d.vertices = vertices;
   Check(bslam_smooth_mesh(ctx_, stream, vertices, triangles, positions, normals, indices, options.iterations, options.lambda, options.mu, options.boundary,
                           d.positions->address(), d.normals->address()),
@@ -937,38 +913,23 @@ DirectBA::DeviceSmoothedMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, u3
   return d;
 }
 
-DirectBA::DeviceSmoothedMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options) {
+DirectBA::DeviceMesh DirectBA::SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options) {
   if (!mesh_extracted_) throw std::logic_error("SmoothMeshOnDevice: no extracted mesh (call ExtractMesh first)");
   // the kept mesh holds positions and indices only, so there is no input normal to fall back on: a vertex without a live triangle gets (0, 0, 0)
-  return SmoothMeshOnDevice(stream, mesh_vertices_, mesh_triangles_, mesh_positions_ ? mesh_positions_->address() : nullptr, nullptr,
-                            mesh_indices_ ? mesh_indices_->address() : nullptr, options);
+  return SmoothMeshOnDevice(stream, mesh_vertices_, mesh_triangles_, AddressOf(mesh_positions_), nullptr, AddressOf(mesh_indices_), options);
 }
 
 void DirectBA::SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOptions& options, Mesh* out) {
-  const size_t V = mesh.vertex_count(), T = mesh.triangle_count();
-  if (mesh.indices.size() % 3 != 0 || mesh.positions.size() % 3 != 0 || 3 * static_cast<uint64_t>(T) > 0x7fffffffull || 3 * static_cast<uint64_t>(V) > 0x7fffffffull)
-    throw std::invalid_argument("SmoothMesh: positions and indices must hold 3 entries per vertex and per triangle, and fit one device image");
-  if ((!mesh.normals.empty() && mesh.normals.size() != 3 * V) || (!mesh.colors.empty() && mesh.colors.size() != V))
-    throw std::invalid_argument("SmoothMesh: normals and colors need one entry per vertex, or none");
-  const bool has_normals = !mesh.normals.empty();
-  DeviceArray<float> dev_positions(3 * V), dev_normals(mesh.normals.size());
-  DeviceArray<u32> dev_indices(3 * T);
-  dev_positions.Upload(stream, mesh.positions.data(), 3 * V);
-  dev_normals.Upload(stream, mesh.normals.data(), mesh.normals.size());
-  dev_indices.Upload(stream, mesh.indices.data(), 3 * T);
-  Wait(stream);   // the host arrays are the caller's and pageable
-  const DeviceSmoothedMesh d = SmoothMeshOnDevice(stream, static_cast<u32>(V), static_cast<u32>(T), dev_positions.address(), has_normals ? dev_normals.address() : nullptr,
-                                                  dev_indices.address(), options);
-  std::vector<float> positions(3 * V), normals(3 * V);   // `out` may be `mesh`
-  d.positions->Download(stream, positions.data(), positions.size());
-  d.normals->Download(stream, normals.data(), normals.size());
-  Wait(stream);
+  CheckMeshSizes(mesh, "SmoothMesh", kMeshAll);   // the colours stay on the host, but have to fit the mesh
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshNormals | kMeshIndices);
+  Mesh smoothed;   // `out` may be `mesh`
+  DownloadMesh(stream, SmoothMeshOnDevice(stream, m.vertices, m.triangles, m.positions->address(), AddressOf(m.normals), m.indices->address(), options), &smoothed, nullptr);
   if (out != &mesh) {
     out->colors = mesh.colors;
     out->indices = mesh.indices;
   }
-  out->positions = std::move(positions);
-  out->normals = std::move(normals);
+  out->positions = std::move(smoothed.positions);
+  out->normals = std::move(smoothed.normals);
 }
 
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {

@@ -276,6 +276,18 @@ class DirectBA {
     size_t vertex_count() const { return positions.size() / 3; }
     size_t triangle_count() const { return indices.size() / 3; }
   };
+  // A mesh on the device: positions and normals 3 floats per vertex, colours 1, indices 3 per triangle, each null where the mesh has
+  // none.  The arrays may have room for more than the `vertices` and `triangles` in use (the result of an operator has room for its
+  // input's counts).  vertex_map, where an operator gives one: the output vertex of every input vertex; rounds: of a decimation.
+  struct DeviceMesh {
+    std::unique_ptr<DeviceArray<float>> positions, normals;
+    std::unique_ptr<DeviceArray<uchar4_t>> colors;
+    std::unique_ptr<DeviceArray<u32>> indices, vertex_map;
+    u32 vertices = 0, triangles = 0, rounds = 0;
+    DeviceMesh() = default;
+    DeviceMesh(u32 v, u32 t) : positions(new DeviceArray<float>(size_t{3} * v)), normals(new DeviceArray<float>(size_t{3} * v)), colors(new DeviceArray<uchar4_t>(v)),
+                               indices(new DeviceArray<u32>(size_t{3} * t)), vertices(v), triangles(t) {}
+  };
   void FuseKeyframes(hipStream_t stream, const VolumeSpec& spec, float truncation);
   void ExtractMesh(hipStream_t stream, u32 min_count, Mesh* mesh);   // of the volume of the last FuseKeyframes
   // Extraction with clean-up (bslam_mesh_components, bslam_filter_mesh): the extracted mesh stays on the device, is labelled by
@@ -300,19 +312,13 @@ class DirectBA {
   // in ascending vertex id --, clusters are numbered in ascending (c_z, c_y, c_x), triangles are remapped and kept iff their three
   // clusters differ.  A mesh without triangles is a point cloud: voxel-grid down-sampling.  Every vertex has to lie at or above
   // origin and within 2^21 cells of it on every axis.
-  struct DeviceSimplifiedMesh {   // on the device, with room for the input's counts; vertices and triangles are the counts in use
-    std::unique_ptr<DeviceArray<float>> positions, normals;   // normals, colors: null when the input has none
-    std::unique_ptr<DeviceArray<uchar4_t>> colors;
-    std::unique_ptr<DeviceArray<u32>> indices, vertex_cluster;   // vertex_cluster: one entry per input vertex
-    u32 vertices = 0, triangles = 0;
-  };
   // Host arrays: mesh.normals and mesh.colors may be empty, and so may mesh.indices; *out gets what the input has.  vertex_cluster
   // (may be null) receives the cluster of every input vertex.
   void SimplifyMesh(hipStream_t stream, const Mesh& mesh, const float origin[3], float cell_size, Mesh* out, std::vector<u32>* vertex_cluster);
   // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_simplify_mesh); the result stays on the
-  // device.
-  DeviceSimplifiedMesh SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
-                                            const u32* indices, const float origin[3], float cell_size);
+  // device, its vertex_map the cluster of every input vertex.
+  DeviceMesh SimplifyMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                  const u32* indices, const float origin[3], float cell_size);
   // Mesh decimation (bslam_decimate_mesh): quadric-error edge collapse in rounds of pairwise non-adjacent collapses until
   // target_vertices are left, no edge may collapse any more or max_rounds (0: no limit) have run.  Boundary edges are held by a
   // quadric of weight boundary_weight; an edge whose cost exceeds max_cost never collapses.
@@ -322,18 +328,12 @@ class DirectBA {
     float max_cost = std::numeric_limits<float>::infinity();
     u32 max_rounds = 0;
   };
-  struct DeviceDecimatedMesh {   // on the device, with room for the input's counts; vertices and triangles are the counts in use
-    std::unique_ptr<DeviceArray<float>> positions, normals;   // normals, colors: null when the input has none
-    std::unique_ptr<DeviceArray<uchar4_t>> colors;
-    std::unique_ptr<DeviceArray<u32>> indices, vertex_map;    // vertex_map: one entry per input vertex
-    u32 vertices = 0, triangles = 0, rounds = 0;
-  };
   // Host arrays: mesh.normals and mesh.colors may be empty; *out gets what the input has.  vertex_map (may be null) receives the
   // output vertex of every input vertex.  Returns the number of rounds.
   u32 DecimateMesh(hipStream_t stream, const Mesh& mesh, const DecimateOptions& options, Mesh* out, std::vector<u32>* vertex_map);
   // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_decimate_mesh); the result stays on the device.
-  DeviceDecimatedMesh DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
-                                           const u32* indices, const DecimateOptions& options);
+  DeviceMesh DecimateMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                  const u32* indices, const DecimateOptions& options);
   // Mesh smoothing (bslam_smooth_mesh): `iterations` of a one-ring step with lambda followed, unless mu is 0, by one with mu (Taubin;
   // mu = 0 is plain Laplacian smoothing), then vertex normals from the smoothed geometry.  Counts, indices and colours stay.  The
   // defaults have been tried on synthetic meshes only and are provisional.
@@ -343,18 +343,15 @@ class DirectBA {
     float lambda = 0.5f, mu = -0.53f;
     SmoothBoundary boundary = kSmoothFixed;
   };
-  struct DeviceSmoothedMesh {   // on the device: the new positions and normals of `vertices` vertices
-    std::unique_ptr<DeviceArray<float>> positions, normals;
-    u32 vertices = 0;
-  };
   // Host arrays: mesh.normals (the fall-back where the geometry gives no normal) and mesh.colors may be empty; *out gets new positions
   // and normals, and the input's colours and indices.
   void SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOptions& options, Mesh* out);
-  // The same on the mesh the last ExtractMesh left on the device, which stays as it is; the result stays on the device.
-  DeviceSmoothedMesh SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options);
+  // The same on the mesh the last ExtractMesh left on the device, which stays as it is; the result -- positions and normals -- stays
+  // on the device.
+  DeviceMesh SmoothMeshOnDevice(hipStream_t stream, const SmoothOptions& options);
   // ... and on a caller's device arrays (4 byte aligned; normals may be null; see bslam_smooth_mesh).
-  DeviceSmoothedMesh SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const u32* indices,
-                                        const SmoothOptions& options);
+  DeviceMesh SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const u32* indices,
+                                const SmoothOptions& options);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.
@@ -625,15 +622,18 @@ class DirectBA {
   struct ViewSet { bool depth, index, color, normal; };
   void ViewImages(int w, int h, const ViewSet& want, bslam_buffer2d pods[4]);
   void DownloadViews(hipStream_t stream, const ViewSet& want, ModelViews* views) const;
-  struct DeviceMesh {   // positions and normals 3 V floats, colours V, indices 3 T
-    std::unique_ptr<DeviceArray<float>> positions, normals;
-    std::unique_ptr<DeviceArray<uchar4_t>> colors;
-    std::unique_ptr<DeviceArray<u32>> indices;
-    u32 vertices = 0, triangles = 0;
-    DeviceMesh() = default;
-    DeviceMesh(u32 v, u32 t) : positions(new DeviceArray<float>(size_t{3} * v)), normals(new DeviceArray<float>(size_t{3} * v)), colors(new DeviceArray<uchar4_t>(v)),
-                               indices(new DeviceArray<u32>(size_t{3} * t)), vertices(v), triangles(t) {}
-  };
+  // Which arrays of a host mesh a call takes to the device.
+  enum MeshPart : unsigned { kMeshPositions = 1, kMeshNormals = 2, kMeshColors = 4, kMeshIndices = 8, kMeshAll = 15 };
+  // Throws std::invalid_argument in the name of `who` unless positions and indices hold whole vertices and triangles and, like a
+  // caller's `points` points, fit one device image, and the normals and colours `what` names have one entry per vertex or none.
+  static void CheckMeshSizes(const Mesh& mesh, const char* who, unsigned what, size_t points = 0);
+  // CheckMeshSizes in the name of `who` (null: the caller has checked by a rule of its own), then uploads the parts `what` names
+  // -- normals and colours only where the mesh has them; `indices`, when given, in place of the mesh's -- and waits once: the host
+  // arrays are the caller's and pageable.
+  DeviceMesh UploadMesh(hipStream_t stream, const Mesh& mesh, const char* who, unsigned what, const std::vector<u32>* indices = nullptr);
+  // The `vertices` and `triangles` in use of what `mesh` holds into *out, sized to fit, and its vertex map into *map (may be null);
+  // everything is enqueued, then the stream is waited for once.
+  void DownloadMesh(hipStream_t stream, const DeviceMesh& mesh, Mesh* out, std::vector<u32>* map);
   // The extraction: the count call, the allocations and the emit call.  Forgets the kept mesh once the count call is through.
   DeviceMesh ExtractDeviceMesh(hipStream_t stream, u32 min_count);
   // device copy of the mesh the last ExtractMesh returned (positions 3 V floats, indices 3 T), for SurfelMeshDistance

@@ -215,6 +215,39 @@ def test_two_calls_agree(gpu):
         assert np.array_equal(bits(a[k]) if a[k].dtype == F else a[k], bits(b[k]) if b[k].dtype == F else b[k]), k
 
 
+def test_stage_times_with_profiling_on(gpu):
+    """Profiling changes no result, a profiled call leaves seven stage sums, and every call resets them at entry.  A context of its
+    own: the switch is the context's."""
+    torch, L, _ = gpu
+    ctx = badslam_amd.Context(0)
+    positions, normals, colors, triangles = dressed(du.noisy_plane(9, seed=9), seed=9)
+    assert len(positions) == 81 and len(triangles) == 128
+
+    def stage_times():
+        ms = (C.c_float * 7)(*[-1.0] * 7)
+        badslam_amd.check(L.bslam_decimate_stage_times(ctx.handle, ms))
+        return np.array(ms[:], np.float64)
+
+    runs = []
+    try:
+        for on in (0, 1, 0):
+            badslam_amd.check(L.bslam_profile_enable(ctx.handle, on))
+            runs.append(decimate(gpu, positions, normals, colors, triangles, 41, ctx=ctx))
+            if on:
+                ms = stage_times()
+                assert np.isfinite(ms).all() and (ms >= 0).all() and (ms > 0).any(), ms
+        badslam_amd.check(L.bslam_profile_enable(ctx.handle, 1))
+        decimate(gpu, np.zeros((0, 3), F), None, None, None, 0, ctx=ctx)
+        assert (stage_times() == 0).all(), "the empty mesh did not reset the stage times"
+    finally:
+        L.bslam_profile_enable(ctx.handle, 0)
+    assert len(runs[0]["positions"]) == 41 and runs[0]["rounds"] > 1
+    for other in runs[1:]:
+        assert other["rounds"] == runs[0]["rounds"]
+        for k in ("positions", "normals", "colors", "triangles", "vertex_map"):
+            assert np.array_equal(bits(runs[0][k]) if runs[0][k].dtype == F else runs[0][k], bits(other[k]) if other[k].dtype == F else other[k]), k
+
+
 def test_a_second_call_with_a_larger_mesh_grows_the_slab(gpu):
     """A context of its own, so that its first decimation is the small one."""
     ctx = badslam_amd.Context(0)

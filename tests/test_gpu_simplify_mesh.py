@@ -242,6 +242,32 @@ def test_two_calls_agree(gpu):
         assert np.array_equal(bits(a[k]) if a[k].dtype == F else a[k], bits(b[k]) if b[k].dtype == F else b[k]), k
 
 
+def test_stage_times_with_profiling_on(gpu):
+    """Profiling changes no result, and a profiled call leaves five stage times.  A context of its own: the switch is the context's."""
+    from tests import decimate_mesh_util as du
+    torch, L, _ = gpu
+    ctx = badslam_amd.Context(0)
+    positions, tri = du.noisy_plane(9, seed=9)
+    normals, colors = du.attributes(81, 9)
+    assert len(positions) == 81 and len(tri) == 128
+    runs = []
+    try:
+        for on in (0, 1, 0):
+            badslam_amd.check(L.bslam_profile_enable(ctx.handle, on))
+            runs.append(simplify(gpu, positions, normals, colors, tri, (0, 0, 0), 2.0, ctx=ctx))
+            if on:
+                ms = (C.c_float * 5)(*[-1.0] * 5)
+                badslam_amd.check(L.bslam_simplify_stage_times(ctx.handle, ms))
+                ms = np.array(ms[:], np.float64)
+                assert np.isfinite(ms).all() and (ms >= 0).all() and (ms > 0).any(), ms
+    finally:
+        L.bslam_profile_enable(ctx.handle, 0)
+    assert 1 < len(runs[0]["positions"]) < 81
+    for other in runs[1:]:
+        for k in runs[0]:
+            assert np.array_equal(bits(runs[0][k]) if runs[0][k].dtype == F else runs[0][k], bits(other[k]) if other[k].dtype == F else other[k]), k
+
+
 def test_a_second_call_with_a_larger_mesh_grows_the_slab(gpu):
     """A context of its own, so that its first simplification is the small one."""
     ctx = badslam_amd.Context(0)

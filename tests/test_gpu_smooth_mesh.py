@@ -181,6 +181,38 @@ def test_two_calls_agree(gpu):
     assert np.array_equal(bits(a[0]), bits(b[0])) and np.array_equal(bits(a[1]), bits(b[1]))
 
 
+def test_stage_times_with_profiling_on(gpu):
+    """Profiling changes no result, a profiled call leaves five stage times, and every call resets them at entry.  A context of its
+    own: the switch is the context's."""
+    torch, L, _ = gpu
+    ctx = badslam_amd.Context(0)
+    positions, triangles = mu_.noisy_plane(9, seed=9)
+    normals = unit_normals(81, 9)
+    assert len(positions) == 81 and len(triangles) == 128
+
+    def stage_times():
+        ms = (C.c_float * 5)(*[-1.0] * 5)
+        badslam_amd.check(L.bslam_smooth_stage_times(ctx.handle, ms))
+        return np.array(ms[:], np.float64)
+
+    runs = []
+    try:
+        for on in (0, 1, 0):
+            badslam_amd.check(L.bslam_profile_enable(ctx.handle, on))
+            runs.append(smooth(gpu, positions, normals, triangles, ctx=ctx, iterations=2))
+            if on:
+                ms = stage_times()
+                assert np.isfinite(ms).all() and (ms >= 0).all() and (ms > 0).any(), ms
+        badslam_amd.check(L.bslam_profile_enable(ctx.handle, 1))
+        smooth(gpu, np.zeros((0, 3), F), None, None, ctx=ctx, iterations=2)
+        assert (stage_times() == 0).all(), "the empty mesh did not reset the stage times"
+    finally:
+        L.bslam_profile_enable(ctx.handle, 0)
+    assert (bits(runs[0][0]) != bits(positions)).any()
+    for other in runs[1:]:
+        assert np.array_equal(bits(runs[0][0]), bits(other[0])) and np.array_equal(bits(runs[0][1]), bits(other[1]))
+
+
 def test_small_large_small_on_one_context(gpu):
     """A context of its own, so that its first smoothing is the small one and the slab grows."""
     ctx = badslam_amd.Context(0)

@@ -81,6 +81,12 @@ class PCGVectors(C.Structure):
                 ("alpha_n", C.c_void_p), ("alpha_d", C.c_void_p), ("beta_n", C.c_void_p)]
 
 
+class IntrinsicsTap(C.Structure):
+    """bslam_intrinsics_tap: host arrays of bslam_debug_optimize_intrinsics, null = skipped."""
+    _fields_ = [("sums", C.c_void_p), ("cells", C.c_void_p), ("obs", C.c_void_p), ("schur_sums", C.c_void_p),
+                ("schur_cells", C.c_void_p), ("x1", C.c_void_p), ("x", C.c_void_p)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 P = C.POINTER
@@ -222,6 +228,8 @@ SIGNATURES = {
         C.c_void_p, C.c_void_p, C.c_int, C.c_int, _CAM, _CAM, _DP, C.c_int, _KFS, C.c_uint32, _BUF, _BUF]),
     "bslam_optimize_intrinsics": (C.c_int, [
         C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _KFS, _CAM, _CAM, _DP, C.c_uint32, _BUF, _CAM, _CAM, P(C.c_float)]),
+    "bslam_debug_optimize_intrinsics": (C.c_int, [
+        C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _KFS, _CAM, _CAM, _DP, C.c_uint32, _BUF, _CAM, _CAM, P(C.c_float), P(IntrinsicsTap)]),
     "bslam_debug_association": (C.c_int, [
         C.c_void_p, C.c_void_p, _CAM, _DP, _KFS, C.c_uint32, _BUF, C.c_void_p]),
     "bslam_debug_pose_residuals": (C.c_int, [

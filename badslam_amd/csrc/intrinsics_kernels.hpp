@@ -3,7 +3,8 @@
 // Replaces the three kernels of BS/kernel_opt_intrinsics.cu.  The reference accumulates one
 // keyframe per launch with 20 + 28 block reductions and 8 contended float atomics per thread.
 // Here one launch walks all keyframes; the 5x5 (+5) depth system and the 4x4 (+4) colour system
-// are accumulated per thread over the whole loop and reduced once per block (fixed-order sums);
+// are accumulated per thread over the whole loop and reduced once per block (fixed-order sums, in float64 from the
+// wave reduction on: the reduced 5x5 system is ill-conditioned in `a`, see intrinsics_sum_rows_kernel);
 // only the per-cell Schur blocks B, D, b2 and the observation counts use atomics, as they are
 // scattered by pixel cell (BS/kernel_opt_intrinsics.cu:176-196).
 #pragma once
@@ -23,7 +24,8 @@ struct IntrinsicsCells {
   float* b2;         // [cells]
   uint32_t* obs;     // [cells]
   double* acc;       // [7][cells]: B, D, b2 summed with fp64 atomics, rounded into the float arrays by intrinsics_cells_round_kernel
-  int cells;
+  int cells;         // grid_width * grid height
+  int grid_width;    // (image width - 1) / cell + 1: cell (x, y) has index x + y * grid_width, whatever the width of the cfactor buffer
 };
 
 // The reference adds floats atomically in arrival order (BS/kernel_opt_intrinsics.cu:176-196); the fp64 sums make the
@@ -36,10 +38,29 @@ __global__ __launch_bounds__(256) void intrinsics_cells_round_kernel(IntrinsicsC
   cells.b2[cell] = (float)cells.acc[(size_t)6 * cells.cells + cell];
 }
 
+// The 256 threads' fp32 values acc[0 .. live) summed in float64, in a fixed order, into row[0 .. kIntrRow) (zero from `live`
+// on).  Every thread of the block calls it.
+__device__ __forceinline__ void block_row_sum_f64(const float (&acc)[kIntrRow], int live, double* __restrict__ row) {
+  __shared__ double red[4][kIntrRow];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < kIntrRow; ++i) {
+    double v = 0.0;
+    if (i < live) {
+      v = (double)acc[i];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    }
+    if (lane == 0) red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kIntrRow) row[threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
 template <bool kDepthIntr, bool kColorIntr>
 __global__ __launch_bounds__(kIntrThreads) void intrinsics_accumulate_kernel(
     CamConsts c, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRows s, IntrinsicsCells cells,
-    float* __restrict__ partial) {
+    double* __restrict__ partial) {
   uint32_t slot;
   if (!slot_of_block(sc, blockIdx.x, &slot)) return;
   f3 gp[kIntrR], gn[kIntrR];
@@ -102,7 +123,7 @@ __global__ __launch_bounds__(kIntrThreads) void intrinsics_accumulate_kernel(
           const float wr = w * raw;
 #pragma unroll
           for (int i = 0; i < 5; ++i) acc[15 + i] += wr * dj[i];
-          const int cell = sparse_px + sparse_py * c.cfactor_width;
+          const int cell = sparse_px + sparse_py * cells.grid_width;
 #pragma unroll
           for (int q = 0; q < 5; ++q) atomicAdd(&cells.acc[(size_t)q * cells.cells + cell], (double)(w * dj[q] * dj[5]));
           atomicAdd(&cells.acc[(size_t)5 * cells.cells + cell], (double)(w * dj[5] * dj[5]));
@@ -145,31 +166,25 @@ __global__ __launch_bounds__(kIntrThreads) void intrinsics_accumulate_kernel(
       }
     }
   }
-  // one row of 40 sums per block, fixed order
-  __shared__ float red[4][kIntrRow];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < kIntrRow; ++i) acc[i] = wave_sum(acc[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < kIntrRow; ++i) red[wave][i] = acc[i];
-  }
-  __syncthreads();
-  if (threadIdx.x < kIntrRow) partial[(size_t)slot * kIntrRow + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  // one row of 40 sums per block, fixed order, in float64 from the threads' fp32 sums on
+  block_row_sum_f64(acc, kIntrRow, partial + (size_t)slot * kIntrRow);
 }
 
-// Sums `rows` rows of kIntrRow floats in index order: out[col] (+)= sum.  One block.
-__global__ __launch_bounds__(64) void intrinsics_sum_rows_kernel(const float* __restrict__ rows_in, int rows, float* __restrict__ out, float scale, int accumulate) {
+// Sums `rows` rows of kIntrRow doubles in index order.  One block.  reduced == nullptr: sums[col] = the sum, rounded once.
+// Otherwise reduced[col] = sums[col] - the sum, kept in float64: the Schur correction of A and b1 cancels most of the `a`
+// entries, and the solve behind it has a condition number of 1e8 and more.
+__global__ __launch_bounds__(64) void intrinsics_sum_rows_kernel(const double* __restrict__ rows_in, int rows, float* __restrict__ sums, double* __restrict__ reduced) {
   const int col = threadIdx.x;
   if (col >= kIntrRow) return;
-  float v = 0.f;
+  double v = 0.0;
   for (int t = 0; t < rows; ++t) v += rows_in[(size_t)t * kIntrRow + col];
-  out[col] = accumulate ? out[col] + scale * v : scale * v;
+  if (reduced) reduced[col] = (double)sums[col] - v;
+  else sums[col] = (float)v;
 }
 
 // ComputeIntrinsicsIntermediateMatricesCUDAKernel (BS/kernel_opt_intrinsics.cu:265-340): Schur
 // complement terms per cell; the 15 + 5 sums over cells go to one row per block.
-__global__ __launch_bounds__(256) void intrinsics_intermediate_kernel(IntrinsicsCells cells, float* __restrict__ partial) {
+__global__ __launch_bounds__(256) void intrinsics_intermediate_kernel(IntrinsicsCells cells, double* __restrict__ partial) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   float acc[kIntrRow];
 #pragma unroll
@@ -196,20 +211,12 @@ __global__ __launch_bounds__(256) void intrinsics_intermediate_kernel(Intrinsics
       for (int row = 0; row < 5; ++row) cells.B[(size_t)row * cells.cells + p] = D_inverse * Bv[row];
     }
   }
-  __shared__ float red[4][kIntrRow];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int i = 0; i < 20; ++i) acc[i] = wave_sum(acc[i]);
-  if (lane == 0) {
-#pragma unroll
-    for (int i = 0; i < kIntrRow; ++i) red[wave][i] = (i < 20) ? acc[i] : 0.f;
-  }
-  __syncthreads();
-  if (threadIdx.x < kIntrRow) partial[(size_t)blockIdx.x * kIntrRow + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  block_row_sum_f64(acc, 20, partial + (size_t)blockIdx.x * kIntrRow);
 }
 
-// SolveForPixelIntrinsicsUpdateCUDAKernel (BS/kernel_opt_intrinsics.cu:374-420)
-__global__ __launch_bounds__(256) void intrinsics_pixel_update_kernel(IntrinsicsCells cells, const float* __restrict__ x1, uint8_t* cfactor, uint32_t cfactor_pitch, int cfactor_width) {
+// SolveForPixelIntrinsicsUpdateCUDAKernel (BS/kernel_opt_intrinsics.cu:374-420).  The cfactor image is the top-left
+// grid_width x (cells / grid_width) pixels of the buffer, addressed by (x, y) through its pitch.
+__global__ __launch_bounds__(256) void intrinsics_pixel_update_kernel(IntrinsicsCells cells, const float* __restrict__ x1, uint8_t* cfactor, uint32_t cfactor_pitch) {
   const int p = blockIdx.x * blockDim.x + threadIdx.x;
   if (p >= cells.cells) return;
   float offset = cells.D[p];
@@ -219,7 +226,7 @@ __global__ __launch_bounds__(256) void intrinsics_pixel_update_kernel(Intrinsics
 #pragma unroll
     for (int row = 0; row < 5; ++row) offset -= cells.B[(size_t)row * cells.cells + p] * x1[row];
   }
-  const int y = p / cfactor_width, x = p - y * cfactor_width;
+  const int y = p / cells.grid_width, x = p - y * cells.grid_width;
   float* cf = (float*)(cfactor + (size_t)y * cfactor_pitch) + x;
   float v = *cf - offset;
   if (cells.obs[p] == 0) v = 0;

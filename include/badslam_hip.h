@@ -365,7 +365,8 @@ int bslam_optimize_geometry_iteration(
  * Gauss-Newton step on the depth intrinsics (1/fx, 1/fy, -cx/fx, -cy/fy, a, then the per-cell
  * cfactors through the Schur complement, prior 100 a^2) and / or the colour intrinsics.
  * depth_params->cfactor_buffer (device) is updated in place; *a is in/out (the value in
- * depth_params->a is ignored in favour of *a); the out cameras are HOST structs. */
+ * depth_params->a is ignored in favour of *a); the out cameras are HOST structs.  The cfactor buffer may be wider or taller
+ * than the cell grid of the depth camera: its top-left grid is the image, nothing outside it is read or written. */
 int bslam_optimize_intrinsics(
     bslam_context* ctx, void* stream,
     int optimize_depth_intrinsics, int optimize_color_intrinsics,
@@ -374,6 +375,34 @@ int bslam_optimize_intrinsics(
     const bslam_depth_params* depth_params,
     uint32_t surfels_size, const bslam_buffer2d* surfels,
     bslam_camera4f* out_color_camera, bslam_camera4f* out_depth_camera, float* a);
+
+/* HOST arrays that bslam_debug_optimize_intrinsics fills; a null member is skipped.  cells = the cell grid of the depth
+ * camera, ((width - 1) / cell + 1) * ((height - 1) / cell + 1); cell (x, y) has index x + y * ((width - 1) / cell + 1).
+ * The 40 sums are A[15] (upper triangle, row by row), b1[5], colour H[10], colour b[4], 6 zeros.  The cell members and x1
+ * are written only with optimize_depth_intrinsics, x only with optimize_color_intrinsics. */
+typedef struct bslam_intrinsics_tap {
+  float* sums;          /* [40]        accumulated over every (keyframe, surfel) pair, before the Schur correction */
+  float* cells;         /* [7][cells]  B[5], D, b2 as rounded from the cell sums, at that same point */
+  uint32_t* obs;        /* [cells]     observation counts */
+  double* schur_sums;   /* [40]        the sums after the Schur correction of A and b1 (before the prior on a): float64, as the
+                                       solves read them */
+  float* schur_cells;   /* [6][cells]  D^-1 B[5] and D^-1 b2 (NaN: the cell has no usable D) */
+  float* x1;            /* [5]         solution of the depth system */
+  float* x;             /* [4]         solution of the colour system */
+} bslam_intrinsics_tap;
+
+/* bslam_optimize_intrinsics with a tap on its intermediate values (test aid; the same code path, tap == NULL is the product
+ * call).  Every copy into the tap waits for the stream.  A call that returns before any device work (surfels_size == 0)
+ * writes nothing. */
+int bslam_debug_optimize_intrinsics(
+    bslam_context* ctx, void* stream,
+    int optimize_depth_intrinsics, int optimize_color_intrinsics,
+    int keyframe_count, const bslam_keyframe_view* keyframes,
+    const bslam_camera4f* color_camera, const bslam_camera4f* depth_camera,
+    const bslam_depth_params* depth_params,
+    uint32_t surfels_size, const bslam_buffer2d* surfels,
+    bslam_camera4f* out_color_camera, bslam_camera4f* out_depth_camera, float* a,
+    const bslam_intrinsics_tap* tap);
 
 /* Per-surfel association probe (test / debugging aid; the reference has no such
  * export, the tests need it to check the bit-exact parity target of

@@ -146,6 +146,26 @@ void bso_optimize_intrinsics(
     uint32_t surfels_size, const bslam_buffer2d* surfels,
     bslam_camera4f* out_color_camera, bslam_camera4f* out_depth_camera, float* a, int tex_mode);
 
+/* float64 shadow of the last bso_optimize_intrinsics call that did not return at once (surfels_size > 0), as
+ * bso_pcg_last_shared_sums keeps it for the PCG entries.  Every accumulated entry -- the 40 global sums in the order A[15]
+ * (upper triangle, row by row), b1[5], colour H[10], colour b[4], 6 unused; per cell B[5], D, b2 as [7][cells] -- has
+ *   sum64 = the float64 sum of the oracle's own fp32 terms, abs64 = that of their absolute values, terms = their number,
+ * and its own fp32 serial sum (sums32 / cells32: the cell arrays as they stood before the Schur pass).  Also kept: the integer
+ * observation counts, A and b1 after the Schur corrections (before the prior on a) and the cell arrays D^-1 B[5], D^-1 b2 (NaN
+ * flag) after the pass, x1[5] and x[4].  cells = the cell grid of the depth camera, cell (x, y) at x + y * grid width.
+ * Members the call did not form (cell members and x1 without depth intrinsics, x without colour intrinsics) are zero. */
+typedef struct bso_intrinsics_shadow {
+  double* sum64; double* abs64; uint32_t* terms; float* sums32;                         /* [40] */
+  double* cell_sum64; double* cell_abs64; uint32_t* cell_terms; float* cells32;         /* [7][cells] */
+  uint32_t* obs;                                                                        /* [cells] */
+  float* schur_sums32;                                                                  /* [20] */
+  float* schur_cells32;                                                                 /* [6][cells] */
+  float* x1;                                                                            /* [5] */
+  float* x;                                                                             /* [4] */
+} bso_intrinsics_shadow;
+/* Returns the cell count of that call (0: there was none); copies into every non-null member when `cells` equals it. */
+uint32_t bso_intrinsics_last_shadow(uint32_t cells, const bso_intrinsics_shadow* out);
+
 /* ---- scene construction (restates the producers either side of the path so the
  * reference's known-answer scenes can be rebuilt; "next" rows of SURVEY.md 8f) ---- */
 

@@ -21,6 +21,12 @@ P = C.POINTER
 _CAM, _DP, _BUF, _KFS = P(abi.Camera4f), P(abi.DepthParams), P(abi.Buffer2D), P(abi.KeyframeView)
 
 
+class IntrinsicsShadow(C.Structure):
+    """bso_intrinsics_shadow (oracle/bslam_oracle.h): host arrays, null = skipped."""
+    _fields_ = [(name, C.c_void_p) for name in ("sum64", "abs64", "terms", "sums32", "cell_sum64", "cell_abs64", "cell_terms", "cells32",
+                                                "obs", "schur_sums32", "schur_cells32", "x1", "x")]
+
+
 def build_oracle():
     """Compiles the oracle's C restatement with gcc (oracle/Makefile)."""
     subprocess.run(["make", "-s", "-C", ORACLE_DIR], check=True)
@@ -100,6 +106,7 @@ def lib():
                                                                    _BUF, _BUF, _BUF, C.c_int, u32p, f64p]),
         "bso_jacobian_probe": (C.c_int, [C.c_int, C.c_int, f32p, f32p]),
         "bso_set_intrinsics_sum64": (None, [C.c_int]),
+        "bso_intrinsics_last_shadow": (C.c_uint32, [C.c_uint32, P(IntrinsicsShadow)]),
         "bso_set_literal_mode": (None, [C.c_int]),
         "bso_get_literal_mode": (C.c_int, []),
         "bso_association_margins": (None, [_CAM, _DP, _KFS, C.c_uint32, _BUF, f64p]),
@@ -423,9 +430,25 @@ class HostScene:
             C.byref(self.depth_camera), C.byref(dp), len(self.keyframes), kfs, self.surfels_size, C.byref(sb), C.byref(ab),
             self.tex_mode)
 
-    def optimize_intrinsics(self, optimize_depth, optimize_color):
-        """One OptimizeIntrinsicsCUDA step on the host state (cameras, a, cfactor updated in place)."""
-        dp, sb, kfs = self.depth_params(), self.surfel_buf(), self.keyframe_views()
+    def intrinsics_shadow(self):
+        """The float64 shadow of the oracle's last optimize_intrinsics call on this scene's cell grid
+        (bso_intrinsics_last_shadow): dict of sum64 / abs64 / terms / sums32 [40], cell_sum64 / cell_abs64 / cell_terms /
+        cells32 [7, cells], obs [cells], schur_sums32 [20], schur_cells32 [6, cells], x1 [5], x [4]."""
+        cells = self.cfactor.size
+        shapes = {"sum64": (40, np.float64), "abs64": (40, np.float64), "terms": (40, np.uint32), "sums32": (40, np.float32),
+                  "cell_sum64": ((7, cells), np.float64), "cell_abs64": ((7, cells), np.float64), "cell_terms": ((7, cells), np.uint32),
+                  "cells32": ((7, cells), np.float32), "obs": (cells, np.uint32), "schur_sums32": (20, np.float32),
+                  "schur_cells32": ((6, cells), np.float32), "x1": (5, np.float32), "x": (4, np.float32)}
+        out = {name: np.zeros(shape, dtype) for name, (shape, dtype) in shapes.items()}
+        s = IntrinsicsShadow(**{name: arr.ctypes.data for name, arr in out.items()})
+        got = lib().bso_intrinsics_last_shadow(cells, C.byref(s))
+        assert got == cells, f"the oracle's last intrinsics call had {got} cells, this scene has {cells}"
+        return out
+
+    def optimize_intrinsics(self, optimize_depth, optimize_color, cfactor=None):
+        """One OptimizeIntrinsicsCUDA step on the host state (cameras, a, cfactor updated in place).  cfactor: another
+        (possibly larger) buffer to use as the cfactor image in place of self.cfactor."""
+        dp, sb, kfs = self.depth_params(None if cfactor is None else np_buffer2d(cfactor)), self.surfel_buf(), self.keyframe_views()
         out_c, out_d = abi.Camera4f(), abi.Camera4f()
         a = C.c_float(self.a)
         lib().bso_optimize_intrinsics(int(optimize_depth), int(optimize_color), len(self.keyframes), kfs, C.byref(self.color_camera),

@@ -109,6 +109,28 @@ class Hip:
         self.torch.cuda.synchronize()
         return out_c, out_d, a.value
 
+    def debug_optimize_intrinsics(self, optimize_depth, optimize_color, cfactor_buf=None, tap=None):
+        """bslam_debug_optimize_intrinsics on the device scene (cfactor_buf: a Buffer2D of device memory in place of the
+        scene's cfactor image); returns (color_camera, depth_camera, a, tap).  tap: {member: zeroed numpy array} of
+        bslam_intrinsics_tap, by default all seven; a member left out is passed as null."""
+        dp, sb = self._common()
+        if cfactor_buf is not None:
+            dp.cfactor_buffer = cfactor_buf
+        cells = self.h.cfactor.size
+        if tap is None:
+            tap = {"sums": np.zeros(40, np.float32), "cells": np.zeros((7, cells), np.float32), "obs": np.zeros(cells, np.uint32),
+                   "schur_sums": np.zeros(40, np.float64), "schur_cells": np.zeros((6, cells), np.float32),
+                   "x1": np.zeros(5, np.float32), "x": np.zeros(4, np.float32)}
+        t = abi.IntrinsicsTap(**{name: arr.ctypes.data for name, arr in tap.items()})
+        kfs = self.d.keyframe_views()
+        out_c, out_d = abi.Camera4f(), abi.Camera4f()
+        a = C.c_float(self.h.a)
+        badslam_amd.check(self.L.bslam_debug_optimize_intrinsics(
+            self.ctx.handle, stream_ptr(), int(optimize_depth), int(optimize_color), len(self.h.keyframes), kfs, C.byref(self.h.color_camera),
+            C.byref(self.h.depth_camera), C.byref(dp), self.d.surfels_size, C.byref(sb), C.byref(out_c), C.byref(out_d), C.byref(a), C.byref(t)))
+        self.torch.cuda.synchronize()
+        return out_c, out_d, a.value, tap
+
     def update_activation(self):
         dp, sb = self._common()
         ab, kfs = self.d.active_buf(), self.d.keyframe_views()

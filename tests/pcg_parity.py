@@ -14,12 +14,13 @@ def small_camera():
     return bso.make_camera(525.0 / 4, 525.0 / 4, 320.0 / 4, 240.0 / 4, WIDTH, HEIGHT)
 
 
-def variant_scene(K, cell, use_depth, use_desc, seed, a=0.02, cfactor_range=0.01):
-    """synthetic_scene at 160x120, perturbed as test_gpu_pcg.perturbed_scene does (surfel depth noise, keyframe poses off by a
-    small twist), then given a depth deformation with real values: with a = 0 and cfactor = 0 the `a` column of the
-    depth-intrinsics Jacobian is identically zero."""
-    scene = scenes.synthetic_scene(K, seed=seed, width=WIDTH, height=HEIGHT, cell=cell, camera=small_camera(),
-                                   use_depth_residuals=use_depth, use_descriptor_residuals=use_desc)
+def variant_scene(K, cell, use_depth, use_desc, seed, a=0.02, cfactor_range=0.01, width=WIDTH, height=HEIGHT, camera=None, color_scale=1):
+    """synthetic_scene at 160x120 (or width x height with `camera`), perturbed as test_gpu_pcg.perturbed_scene does (surfel depth
+    noise, keyframe poses off by a small twist), then given a depth deformation with real values: with a = 0 and cfactor = 0 the
+    `a` column of the depth-intrinsics Jacobian is identically zero."""
+    assert camera is not None or (width, height) == (WIDTH, HEIGHT), "another image size needs its own camera"
+    scene = scenes.synthetic_scene(K, seed=seed, width=width, height=height, cell=cell, camera=camera or small_camera(),
+                                   use_depth_residuals=use_depth, use_descriptor_residuals=use_desc, color_scale=color_scale)
     rng = np.random.default_rng(seed)
     n = scene.surfels_size
     scene.surfels[2, :n] += rng.uniform(-0.003, 0.003, n).astype(np.float32)

@@ -31,6 +31,7 @@ EXPECTED = {
     "pcg_init": (INVALID, INVALID, INVALID, OK, INVALID, INVALID),
     "pcg_step1": (INVALID, INVALID, INVALID, OK, INVALID, INVALID),
     "optimize_intrinsics": (INVALID, INVALID, INVALID, OK, INVALID, INVALID),
+    "debug_optimize_intrinsics": (INVALID, INVALID, INVALID, OK, INVALID, INVALID),
     "delete_surfels_and_update_radii": (INVALID, INVALID, OK, OK, INVALID, None),
 }
 PARAMS = [(name, case, codes[i]) for name, codes in EXPECTED.items() for i, case in enumerate(CASES) if codes[i] is not None]
@@ -113,6 +114,13 @@ def call(name, scene, case):
         out_c, out_d, a = abi.Camera4f(), abi.Camera4f(), C.c_float(scene.a)
         rc = L.bslam_optimize_intrinsics(ctx, s, 1, 1, K, kfs, color, depth, C.byref(dp), size, C.byref(sb), C.byref(out_c), C.byref(out_d),
                                          C.byref(a))
+    elif name == "debug_optimize_intrinsics":
+        out_c, out_d, a = abi.Camera4f(), abi.Camera4f(), C.c_float(scene.a)
+        x1 = np.zeros(5, np.float32)
+        tap = abi.IntrinsicsTap(x1=x1.ctypes.data)   # every other member null
+        rc = L.bslam_debug_optimize_intrinsics(ctx, s, 1, 1, K, kfs, color, depth, C.byref(dp), size, C.byref(sb), C.byref(out_c), C.byref(out_d),
+                                               C.byref(a), C.byref(tap))
+        assert not x1.any(), "a call that does no device work leaves the tap alone"
     elif name == "delete_surfels_and_update_radii":
         count = C.c_uint32(scene.surfels_size)
         rc = L.bslam_delete_surfels_and_update_radii(ctx, s, 1, depth, C.byref(dp), K, kfs, C.byref(count), size, C.byref(sb))

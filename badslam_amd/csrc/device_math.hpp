@@ -266,14 +266,19 @@ __device__ __forceinline__ float desc_weight(float r) { return 1.f * kDescWeight
 // desc_weight of both residuals of a pair, same bits.  Near convergence |r| < kDescHuber for almost every pair, where the weight
 // is the constant kDescWeight: the reciprocal, its two multiplies and the select are taken only when some lane of the wave needs
 // them (a wave-uniform branch; call it where the wave's lanes have a common exec mask or not, the ballot covers the active ones).
-__device__ __forceinline__ void desc_weights_pair(float r1, float r2, float* w1, float* w2) {
-  float a = 1.f * kDescWeight * 1.f, b = a;
+// `fast` is that constant as the caller holds it: a kernel that keeps it in a register across its pair loop passes the register
+// (the literal costs two v_mov_b32 per pair at the branch's join).
+__device__ __forceinline__ void desc_weights_pair(float r1, float r2, float fast, float* w1, float* w2) {
+  float a = fast, b = fast;
   if (__ballot(!(fabsf(r1) < kDescHuber) || !(fabsf(r2) < kDescHuber)) != 0) {
     a = desc_weight(r1);
     b = desc_weight(r2);
   }
   *w1 = a;
   *w2 = b;
+}
+__device__ __forceinline__ void desc_weights_pair(float r1, float r2, float* w1, float* w2) {
+  desc_weights_pair(r1, r2, 1.f * kDescWeight * 1.f, w1, w2);
 }
 __device__ __forceinline__ float weighted_desc_residual(float r) { return 1.f * kDescWeight * huber_residual(r, kDescHuber); }
 
@@ -407,14 +412,6 @@ __device__ __forceinline__ LumaQuad unpack_quad(QuadEntry e) {
   r.tl *= 1.0f / 255.0f; r.tr *= 1.0f / 255.0f; r.bl *= 1.0f / 255.0f; r.br *= 1.0f / 255.0f;
   return r;
 }
-// bilinear_bytes on an entry: tr - tl IS dtop, br - bl is dmix + dtop and bl is tl + dleft (exact), so the three fmas see the
-// operands they saw on the unpacked bytes
-__device__ __forceinline__ float bilinear_bytes_entry(QuadEntry e, float a, float b) {
-  const float tl = (float)e.x, dtop = (float)e.y, dleft = (float)e.z, dmix = (float)e.w;
-  const float top = __builtin_fmaf(a, dtop, tl);
-  const float bot = __builtin_fmaf(a, dmix + dtop, tl + dleft);
-  return __builtin_fmaf(b, bot - top, top);
-}
 __device__ __forceinline__ float bilinear_bytes(const LumaQuad& t, float a, float b) {
   const float top = __builtin_fmaf(a, t.tr - t.tl, t.tl);
   const float bot = __builtin_fmaf(a, t.br - t.bl, t.bl);
@@ -442,19 +439,34 @@ __device__ __forceinline__ void bilinear_gradient_diffs(const QuadDiffs& t, floa
   *dx = __builtin_fmaf(ty, t.dmix, t.dtop);
   *dy = __builtin_fmaf(tx, t.dmix, t.dleft);
 }
-// bilinear_bytes for weights on the 1/256 grid (BSLAM_TEX_FIXED_POINT_1_8: a = ka / 256, b = kb / 256, ka, kb in [0, 256]), from
-// the gradient's differences.  Every intermediate of bilinear_bytes is then exact -- top = top' / 256 and bot - top =
-// (256 (bl - tl) + ka ((br - bl) - (tr - tl))) / 256 with integers |top'| < 2^16, |bot' - top'| < 2^18, and the value N / 2^16
-// with N < 2^24 -- and so is each fma here: the same value, bit for bit, in one conversion and three fmas instead of two
-// conversions, three fmas and a subtraction.  (With unquantised weights the intermediates round, and bilinear_bytes stays.)
-__device__ __forceinline__ float bilinear_diffs_fixed(const QuadDiffs& t, float a, float b) {
-  const float top = __builtin_fmaf(a, t.dtop, t.tl);
-  return __builtin_fmaf(b, __builtin_fmaf(a, t.dmix, t.dleft), top);
+// The bilinear value in ONE form for both texture modes (it replaces the two whole filters bilinear_diffs_fixed and
+// bilinear_bytes_entry; same operations on the same operands, the same bits): val = fma(b, inner, top) with top = fma(a, dtop, tl) the interpolation
+// along the upper edge and `inner` the difference of the lower edge's interpolation and top.  The modes differ in `inner` alone:
+//   bilinear_inner_exact  (fma(a, dmix + dtop, tl + dleft)) - top: bilinear_bytes on an entry -- tr - tl IS dtop, br - bl is
+//                         dmix + dtop and bl is tl + dleft (exact), so the fmas see the operands they saw on the unpacked bytes;
+//   bilinear_inner_fixed  fma(a, dmix, dleft), for weights on the 1/256 grid (BSLAM_TEX_FIXED_POINT_1_8: a = ka / 256,
+//                         b = kb / 256, ka, kb in [0, 256]).  Every intermediate of bilinear_bytes is then exact -- top = top' / 256
+//                         and bot - top = (256 (bl - tl) + ka ((br - bl) - (tr - tl))) / 256 with integers |top'| < 2^16,
+//                         |bot' - top'| < 2^18, and the value N / 2^16 with N < 2^24 -- and so is this fma: the same value, bit
+//                         for bit, without the second conversion and the subtraction.  (With unquantised weights the
+//                         intermediates round, and the exact form stays.)
+// A kernel forms top (and the gradient, which reads the same differences) ahead of its mode test, selects `inner` in the test and
+// forms val behind the join, so the join carries one value per sample (descriptor_samples_finish).
+__device__ __forceinline__ float bilinear_top(const QuadDiffs& t, float a) { return __builtin_fmaf(a, t.dtop, t.tl); }
+__device__ __forceinline__ float bilinear_inner_fixed(const QuadDiffs& t, float a) { return __builtin_fmaf(a, t.dmix, t.dleft); }
+__device__ __forceinline__ float bilinear_inner_exact(const QuadDiffs& t, float a, float top) {
+  return __builtin_fmaf(a, t.dmix + t.dtop, t.tl + t.dleft) - top;
 }
+__device__ __forceinline__ float bilinear_inner(const CamConsts& c, const QuadDiffs& t, float a, float top) {
+  return c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8 ? bilinear_inner_fixed(t, a) : bilinear_inner_exact(t, a, top);
+}
+__device__ __forceinline__ float bilinear_value(float b, float inner, float top) { return __builtin_fmaf(b, inner, top); }
 // bilinear luma in byte units at pixel-corner coordinates (x, y)
 __device__ __forceinline__ float tex_b(const KfDev& kf, const CamConsts& c, float x, float y) {
   const TexFootprint f = tex_footprint(c, x, y);
-  return bilinear_bytes_entry(quad_at(kf, c, f.i, f.j), f.a, f.b);
+  const QuadDiffs t = quad_diffs(quad_at(kf, c, f.i, f.j));
+  const float top = bilinear_top(t, f.a);
+  return bilinear_value(f.b, bilinear_inner_exact(t, f.a, top), top);
 }
 
 // BS/cost_function.cuh:115-136
@@ -541,20 +553,25 @@ template <class SamplePoints>
 __device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const CamConsts& c, const DescSamples& d, float d1, float d2, float gx_scale, float gy_scale,
                                                           SamplePoints&& sample_points, float* r1, float* r2, float* gx1, float* gy1, float* gx2, float* gy2) {
   float val[3], gx[3], gy[3];   // byte units
+  // what both texture modes share comes first; the mode test (wave-uniform) assigns the three `inner` and nothing else, so its
+  // join merges three values where two whole filters per arm merged nine (bilinear_value above)
+  QuadDiffs t[3];
+  float top[3], inner[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t[k] = quad_diffs(d.q[k]);
+    top[k] = bilinear_top(t[k], d.f[k].a);
+    bilinear_gradient_diffs(t[k], d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
+  }
   if (c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const QuadDiffs t = quad_diffs(d.q[k]);
-      val[k] = bilinear_diffs_fixed(t, d.f[k].a, d.f[k].b);
-      bilinear_gradient_diffs(t, d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
-    }
+    for (int k = 0; k < 3; ++k) inner[k] = bilinear_inner_fixed(t[k], d.f[k].a);
   } else {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      val[k] = bilinear_bytes_entry(d.q[k], d.f[k].a, d.f[k].b);
-      bilinear_gradient_diffs(quad_diffs(d.q[k]), d.f[k].ua, d.f[k].ub, &gx[k], &gy[k]);
-    }
+    for (int k = 0; k < 3; ++k) inner[k] = bilinear_inner_exact(t[k], d.f[k].a, top[k]);
   }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) val[k] = bilinear_value(d.f[k].b, inner[k], top[k]);
   // some sample's 2x2 footprint touches the image border: a base texel outside [0, w - 2] x [0, h - 2] (-1 is the largest unsigned
   // value), decided on the maxima of the three base texels (two v_max3_u32 and two compares instead of six compares)
   const uint32_t max_i = max(max((uint32_t)d.f[0].i, (uint32_t)d.f[1].i), (uint32_t)d.f[2].i);
@@ -579,13 +596,22 @@ __device__ __forceinline__ void descriptor_samples_finish(const KfDev& kf, const
 // same operands, so r1 and r2 are the same bits (bslam_debug_ba_cost_descriptor_residuals compares the two).
 __device__ __forceinline__ void descriptor_samples_values(const CamConsts& c, const DescSamples& d, float d1, float d2, float* r1, float* r2) {
   float val[3];   // byte units
+  QuadDiffs t[3];
+  float top[3], inner[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    t[k] = quad_diffs(d.q[k]);
+    top[k] = bilinear_top(t[k], d.f[k].a);
+  }
   if (c.tex_mode == BSLAM_TEX_FIXED_POINT_1_8) {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) val[k] = bilinear_diffs_fixed(quad_diffs(d.q[k]), d.f[k].a, d.f[k].b);
+    for (int k = 0; k < 3; ++k) inner[k] = bilinear_inner_fixed(t[k], d.f[k].a);
   } else {
 #pragma unroll
-    for (int k = 0; k < 3; ++k) val[k] = bilinear_bytes_entry(d.q[k], d.f[k].a, d.f[k].b);
+    for (int k = 0; k < 3; ++k) inner[k] = bilinear_inner_exact(t[k], d.f[k].a, top[k]);
   }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) val[k] = bilinear_value(d.f[k].b, inner[k], top[k]);
   *r1 = __builtin_fmaf(kDescScale, val[1] - val[0], -d1);
   *r2 = __builtin_fmaf(kDescScale, val[2] - val[0], -d2);
 }
@@ -662,8 +688,8 @@ __global__ __launch_bounds__(256) void build_quads_kernel(CamConsts c, const KfD
 }
 
 // bslam_debug_quad_samples: one bilinear sample {val, gx, gy} (byte units) per position [image, x, y] (pixel-corner coordinates),
-// twice: out[0..3) through the quad table as the kernels read it (tex_footprint, quad_at, quad_diffs, bilinear_diffs_fixed or
-// bilinear_bytes_entry, bilinear_gradient_diffs, and the border strip's second footprint as in descriptor_samples_finish),
+// twice: out[0..3) through the quad table as the kernels read it (tex_footprint, quad_at, quad_diffs, bilinear_top, the mode's
+// bilinear_inner, bilinear_value, bilinear_gradient_diffs, and the border strip's second footprint as in descriptor_samples_finish),
 // out[3..6) from four byte loads of the image with clamp addressing, differences formed per sample in integers
 // (quad_diffs_from_bytes), then the same filters.  The luma of pixel (x, y) is byte color[y * pitch + x * pixel_stride + luma_offset].
 __global__ __launch_bounds__(256) void quad_samples_probe_kernel(CamConsts c, const KfDev* __restrict__ kfs, int pixel_stride, int luma_offset, int count,
@@ -681,7 +707,8 @@ __global__ __launch_bounds__(256) void quad_samples_probe_kernel(CamConsts c, co
   float val, gx, gy;
   {
     const QuadDiffs d = quad_diffs(e);
-    val = fixed ? bilinear_diffs_fixed(d, f.a, f.b) : bilinear_bytes_entry(e, f.a, f.b);
+    const float top = bilinear_top(d, f.a);
+    val = bilinear_value(f.b, bilinear_inner(c, d, f.a, top), top);
     bilinear_gradient_diffs(d, f.ua, f.ub, &gx, &gy);
     if (border) bilinear_gradient_diffs(quad_diffs(quad_at(kf, c, g.ix, g.iy)), g.tx, g.ty, &gx, &gy);
   }
@@ -696,7 +723,7 @@ __global__ __launch_bounds__(256) void quad_samples_probe_kernel(CamConsts c, co
     const uint32_t q = bytes_at(f.i, f.j);
     const QuadDiffs d = quad_diffs_from_bytes(q);
     const LumaQuad b{(float)(q & 0xffu), (float)((q >> 8) & 0xffu), (float)((q >> 16) & 0xffu), (float)(q >> 24)};
-    val = fixed ? bilinear_diffs_fixed(d, f.a, f.b) : bilinear_bytes(b, f.a, f.b);
+    val = fixed ? bilinear_value(f.b, bilinear_inner_fixed(d, f.a), bilinear_top(d, f.a)) : bilinear_bytes(b, f.a, f.b);
     bilinear_gradient_diffs(d, f.ua, f.ub, &gx, &gy);
     if (border) bilinear_gradient_diffs(quad_diffs_from_bytes(bytes_at(g.ix, g.iy)), g.tx, g.ty, &gx, &gy);
   }

@@ -202,6 +202,13 @@ __device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* 
   __syncthreads();
 
   BSLAM_HOIST_CAM_CENTRES(c);
+  // With the registers the one filter form left free (87 of 96): cx_inv / cy_inv of nx_of / ny_of, and the constant weight of
+  // desc_weights_pair's fast path, held in a register across the pair loop.  The weights' two copies per pair stay (now from the
+  // register, not from a literal), but the compiler no longer moves them into a block of their own that every pair's fast path
+  // reached by a branch out and left by a branch back.  Measured as a pair of changes: DESIGN §6.
+  BSLAM_HOIST_UNPROJECTION_CENTRE(c);
+  float huber_fast = 1.f * kDescWeight * 1.f;
+  BSLAM_TO_VGPR(huber_fast);
   // this wave's keyframes: visited keyframes wave, wave + 4, ... of the chunk; the list entry of the next one is fetched (a
   // scalar load) one visit ahead
   unsigned long long mine = todo;
@@ -263,7 +270,7 @@ __device__ __forceinline__ void pose_accumulate_desc(CamConsts& c, const KfDev* 
           // both rows in one rank-two update (accumulate_h_b_desc_pair); u, v, iz from the 1-ulp reciprocal the projection
           // starts from (the same v_rcp_f32: no second one, and nothing more to carry across the gathers than p.local)
           float w1, w2;
-          desc_weights_pair(r1, rr2, &w1, &w2);
+          desc_weights_pair(r1, rr2, huber_fast, &w1, &w2);
           const float iz = rrcp(p.local.z);
           accumulate_h_b_desc_pair(p.local.x * iz, p.local.y * iz, iz, gx1, gy1, r1, w1, gx2, gy2, rr2, w2, acc);
           if constexpr (kCost) acc[kRowCost] += weighted_desc_residual(r1);        // quirk Q1: only the first residual is counted

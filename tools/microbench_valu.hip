@@ -77,6 +77,54 @@ __global__ __launch_bounds__(256) void k_mov64(float* out, float a, float b) {
   out[blockIdx.x * blockDim.x + threadIdx.x] = (float)(x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7);
 }
 
+// The classes of the photometric pair loop that the list above lacks (DESIGN.md section 5 prices the loop with these figures):
+// the footprint's floor and clamp, the integer address arithmetic, compares that write a lane mask to an SGPR pair and selects
+// that read one, a packed fp32 multiply, and v_fma_f32 with a scalar operand (a VOP3 instruction reads at most one) against the
+// all-vector form k_fma measures.
+KERNEL(k_floor, CHAIN8_1("v_floor_f32"))
+KERNEL(k_med3, CHAIN8("v_med3_f32"))
+KERNEL(k_mad_i24, CHAIN8("v_mad_i32_i24"))
+KERNEL(k_lshl_add, CHAIN8("v_lshl_add_u32"))
+#define CHAIN8_VS(OP)                                                                                      \
+  asm volatile(OP " %0, %0, %8, %9\n" OP " %1, %1, %8, %9\n" OP " %2, %2, %8, %9\n" OP " %3, %3, %8, %9\n"  \
+               OP " %4, %4, %8, %9\n" OP " %5, %5, %8, %9\n" OP " %6, %6, %8, %9\n" OP " %7, %7, %8, %9\n"  \
+               : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7) : "v"(a), "s"(b))
+KERNEL(k_fma_sgpr, CHAIN8_VS("v_fma_f32"))
+__global__ __launch_bounds__(256) void k_pkmul(float* out, float a, float b) {
+  float2_t x0 = {(float)threadIdx.x, 1.f}, x1 = x0 + 1.f, x2 = x0 + 2.f, x3 = x0 + 3.f, x4 = x0 + 4.f, x5 = x0 + 5.f, x6 = x0 + 6.f, x7 = x0 + 7.f;
+  const float2_t va = {a, a};
+  for (int i = 0; i < kIters; ++i) {
+    asm volatile("v_pk_mul_f32 %0, %0, %8\nv_pk_mul_f32 %1, %1, %8\nv_pk_mul_f32 %2, %2, %8\nv_pk_mul_f32 %3, %3, %8\n"
+                 "v_pk_mul_f32 %4, %4, %8\nv_pk_mul_f32 %5, %5, %8\nv_pk_mul_f32 %6, %6, %8\nv_pk_mul_f32 %7, %7, %8\n"
+                 : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7) : "v"(va));
+  }
+  const float2_t s = x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7;
+  out[blockIdx.x * blockDim.x + threadIdx.x] = s.x + s.y;
+}
+// eight compares into eight SGPR pairs per statement; the masks are folded into the result after the loop
+__global__ __launch_bounds__(256) void k_cmp_sgpr(float* out, float a, float b) {
+  float x0 = threadIdx.x + 1, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
+  unsigned long long m0 = 0, m1 = 0, m2 = 0, m3 = 0, m4 = 0, m5 = 0, m6 = 0, m7 = 0;
+  for (int i = 0; i < kIters; ++i) {
+    asm volatile("v_cmp_lt_f32_e64 %0, %8, %16\nv_cmp_lt_f32_e64 %1, %9, %16\nv_cmp_lt_f32_e64 %2, %10, %16\nv_cmp_lt_f32_e64 %3, %11, %16\n"
+                 "v_cmp_lt_f32_e64 %4, %12, %16\nv_cmp_lt_f32_e64 %5, %13, %16\nv_cmp_lt_f32_e64 %6, %14, %16\nv_cmp_lt_f32_e64 %7, %15, %16\n"
+                 : "=s"(m0), "=s"(m1), "=s"(m2), "=s"(m3), "=s"(m4), "=s"(m5), "=s"(m6), "=s"(m7)
+                 : "v"(x0), "v"(x1), "v"(x2), "v"(x3), "v"(x4), "v"(x5), "v"(x6), "v"(x7), "v"(a));
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = (float)__builtin_popcountll(m0 ^ m1 ^ m2 ^ m3 ^ m4 ^ m5 ^ m6 ^ m7);
+}
+// selects by a lane mask held in an SGPR pair (every other lane)
+__global__ __launch_bounds__(256) void k_cndmask_sgpr(float* out, float a, float b) {
+  float x0 = threadIdx.x + 1, x1 = x0 + 1, x2 = x0 + 2, x3 = x0 + 3, x4 = x0 + 4, x5 = x0 + 5, x6 = x0 + 6, x7 = x0 + 7;
+  const unsigned long long mask = 0x5555555555555555ull;
+  for (int i = 0; i < kIters; ++i) {
+    asm volatile("v_cndmask_b32_e64 %0, %0, %8, %9\nv_cndmask_b32_e64 %1, %1, %8, %9\nv_cndmask_b32_e64 %2, %2, %8, %9\nv_cndmask_b32_e64 %3, %3, %8, %9\n"
+                 "v_cndmask_b32_e64 %4, %4, %8, %9\nv_cndmask_b32_e64 %5, %5, %8, %9\nv_cndmask_b32_e64 %6, %6, %8, %9\nv_cndmask_b32_e64 %7, %7, %8, %9\n"
+                 : "+v"(x0), "+v"(x1), "+v"(x2), "+v"(x3), "+v"(x4), "+v"(x5), "+v"(x6), "+v"(x7) : "v"(a), "s"(mask));
+  }
+  out[blockIdx.x * blockDim.x + threadIdx.x] = x0 + x1 + x2 + x3 + x4 + x5 + x6 + x7;
+}
+
 template <typename K>
 static void run(const char* name, K kernel, float* d_out) {
   const int blocks = 256 * 8;   // 8 blocks of 4 waves per CU = 8 waves per SIMD
@@ -113,5 +161,13 @@ int main() {
   run("v_cvt_f32_f16 hi", k_cvt_f16_hi, d_out);
   run("v_mov_b32 0", k_mov32, d_out);
   run("v_mov_b64 0", k_mov64, d_out);
+  run("v_fma_f32 sgpr", k_fma_sgpr, d_out);
+  run("v_pk_mul_f32", k_pkmul, d_out);
+  run("v_floor_f32", k_floor, d_out);
+  run("v_med3_f32", k_med3, d_out);
+  run("v_cmp_e64 sgpr", k_cmp_sgpr, d_out);
+  run("v_cndmask sgpr", k_cndmask_sgpr, d_out);
+  run("v_mad_i32_i24", k_mad_i24, d_out);
+  run("v_lshl_add_u32", k_lshl_add, d_out);
   return 0;
 }

@@ -122,6 +122,9 @@ SIGNATURES = {
                                         P(Buffer2D)]),
     "bslam_render_surfels": (C.c_int, [C.c_void_p, C.c_void_p, P(Mat3x4), P(Camera4f), C.c_uint32, P(Buffer2D), C.c_float, C.c_float, C.c_float, C.c_float,
                                        P(Buffer2D), P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
+    "bslam_render_mesh": (C.c_int, [C.c_void_p, C.c_void_p, P(Mat3x4), P(Camera4f), C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p,
+                                    C.c_float, C.c_float, C.c_int, C.c_float, P(Buffer2D), P(Buffer2D), P(Buffer2D), P(Buffer2D)]),
+    "bslam_set_render_mesh_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "bslam_fuse_keyframes": (C.c_int, [C.c_void_p, C.c_void_p, _CAM, _CAM, _DP, C.c_int, _KFS, P(Volume), C.c_float, _BUF, _BUF, _BUF]),
     "bslam_extract_mesh": (C.c_int, [C.c_void_p, C.c_void_p, P(Volume), _BUF, _BUF, _BUF, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
                                      C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),

@@ -5,6 +5,7 @@
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -28,6 +29,7 @@
 #include "decimate_kernels.hpp"
 #include "smooth_kernels.hpp"
 #include "raycast_kernels.hpp"
+#include "render_mesh_kernels.hpp"
 #include "place_kernels.hpp"
 #include "odometry_kernels.hpp"
 #include "pose_kernels.hpp"
@@ -1464,6 +1466,7 @@ int bslam_debug_pose_residuals(
 #include "sampling_abi.inc"
 #include "registration_abi.inc"
 #include "raycast_abi.inc"
+#include "render_mesh_abi.inc"
 #include "place_abi.inc"
 #include "odometry_abi.inc"
 #include "cost_abi.inc"

@@ -182,7 +182,12 @@ struct bslam_context {
   bslam::Slab quads_aux;     // luma quads of the tracked frame's colour pyramid level (odometry)
   bslam::Slab lifecycle;     // supporting-surfel cell images, scan buffers, flags of the surfel lifecycle calls
   bslam::Slab zbuffer;       // uint32[h][w]: float bits of the nearest surface per target pixel (bslam_reproject_depth); or
-                             // uint64[h][w]: (float bits of the depth << 32) | surfel index (bslam_render_surfels)
+                             // uint64[h][w]: (float bits of the depth << 32) | surfel index (bslam_render_surfels); or those keys with
+                             // the triangle id, the error word, the queue of large triangles and the projected vertices (bslam_render_mesh)
+  // bslam_render_mesh (bslam_set_render_mesh_tuning): the box sizes up to which a lane and a wave draw alone, whether a vertex pass
+  // projects every vertex once into `zbuffer`, and whether the resolve pass reads those records; the views are the same bits either way
+  int render_mesh_small_box = 64, render_mesh_wave_box = 256;
+  bool render_mesh_project_once = false, render_mesh_resolve_projected = false;
   bslam::Slab place_pattern; // uint32[256]: the BRIEF point pairs of bslam_extract_keyframe_features, uploaded by its first call
   bool place_pattern_ready = false;
   bslam::Slab fusion;        // bslam_extract_mesh: active flags and quad counts u8[cells], vertex ids and quad offsets u32[cells], scan sums;

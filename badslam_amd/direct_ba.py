@@ -95,6 +95,8 @@ def host_lib():
     L.bsh_smooth_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32]
     L.bsh_smooth_extracted_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
     L.bsh_smoothed_copy.argtypes = [f32p, f32p]
+    L.bsh_render_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, f32p, f32p, C.c_int, C.c_int, f32p, C.c_int, u16p, u32p, u8p,
+                                  f32p, f32p]
     L.bsh_sample_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_uint32, u64p]
     L.bsh_samples_copy.argtypes = [f32p, f32p, u32p]
     f64p = C.POINTER(C.c_double)
@@ -837,6 +839,27 @@ class DirectBA:
     def MeshNormals(self, mesh):
         """`mesh` with vertex normals computed from its geometry: SmoothMesh with iterations=0, so the positions keep their bits."""
         return self.SmoothMesh(mesh, iterations=0)
+
+    # --- mesh views (bslam_render_mesh)
+    def RenderMesh(self, mesh, global_T_camera, camera=None, min_depth=0.05, max_depth=50.0, cull_backfaces=True, views=("depth", "color")):
+        """Views of `mesh` (a dict with positions and triangles and optionally normals and colors: the result of ExtractMesh, SmoothMesh,
+        SimplifyMesh, DecimateMesh or LoadPLY) from the pose global_T_camera (abi.SE3f) with `camera` (abi.Camera4f, pixel-corner;
+        default: the depth camera): the nearest triangle per pixel.  Returns the dict of RenderModel, where "index" holds triangle ids,
+        "color" the perspective-correct vertex colours and "normal" the interpolated vertex normals -- face normals for a mesh without
+        normals.  A triangle with a vertex outside [min_depth, max_depth] metres is dropped, not clipped; cull_backfaces draws only
+        triangles seen counter-clockwise, i.e. an extracted mesh from free space.  "color" of a mesh without colours is a ValueError."""
+        params, w, h = self._view_camera(camera)
+        out = _alloc_views(views, ("depth", "index", "color", "normal"), h, w)
+        pos, nrm, col, tri, _ = self._mesh_arrays(mesh, "RenderMesh")
+        if "color" in out and col is None:
+            raise ValueError("RenderMesh: a colour view needs a mesh with colours")
+        ptr = lambda name, pointer: pointer(out[name]) if name in out else None
+        out["camera_T_global"] = np.zeros((3, 4), np.float32)
+        options = np.array([min_depth, max_depth], np.float32)
+        self._check(self.L.bsh_render_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), None if col is None else _u8(col), len(tri),
+                                           _u32(tri), _f(pose7(global_T_camera)), _f(params), w, h, _f(options), 1 if cull_backfaces else 0, ptr("depth", _u16),
+                                           ptr("index", _u32), ptr("color", _u8), ptr("normal", _f), _f(out["camera_T_global"])))
+        return out
 
     # --- mesh simplification (bslam_simplify_mesh)
     def SimplifyMesh(self, mesh, cell_size, origin=None):

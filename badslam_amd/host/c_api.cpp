@@ -286,6 +286,23 @@ static DirectBA::Mesh mesh_from(uint64_t vertices, const float* positions, const
   if (triangles) mesh.indices.assign(indices, indices + 3 * triangles);
   return mesh;
 }
+// DirectBA::RenderMesh of host arrays (normals and colors -- 4 bytes per vertex -- may be null).  camera and outputs as in
+// bsh_render_model; options2: min_depth, max_depth.
+int bsh_render_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles,
+                    const uint32_t* indices, const float* global_T_camera_pose7, const float* camera_params4, int width, int height, const float* options2,
+                    int cull_backfaces, uint16_t* depth, uint32_t* index, uint8_t* color, float* normal, float* camera_T_global) {
+  BSH_TRY({
+    DirectBA::MeshViewOptions o;
+    o.min_depth = options2[0]; o.max_depth = options2[1];
+    o.cull_backfaces = cull_backfaces != 0;
+    o.depth = depth != nullptr; o.index = index != nullptr; o.color = color != nullptr; o.normal = normal != nullptr;
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, colors, triangles, indices);
+    DirectBA::ModelViews v;
+    static_cast<DirectBA*>(ba)->RenderMesh(static_cast<hipStream_t>(stream), mesh, pose_from7(global_T_camera_pose7), PinholeCamera4f(width, height, camera_params4), o, &v);
+    views_out(v, depth, index, color, normal);
+    if (camera_T_global) std::memcpy(camera_T_global, v.camera_T_global.m, sizeof(v.camera_T_global.m));
+  });
+}
 // DirectBA::SimplifyMesh of host arrays in two steps, like the mesh: bsh_simplify_mesh (normals, colors -- 4 bytes per vertex --
 // and indices may be null; origin3: x y z) keeps the result for this thread and reports counts2 = {vertices, triangles};
 // bsh_simplified_copy copies it out (normals and colors only where the input had them; vertex_cluster: one entry per input vertex;

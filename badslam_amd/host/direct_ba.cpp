@@ -932,6 +932,27 @@ void DirectBA::SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOpti
   out->normals = std::move(smoothed.normals);
 }
 
+void DirectBA::RenderMesh(hipStream_t stream, const Mesh& mesh, const SE3f& global_T_camera, const PinholeCamera4f& camera, const MeshViewOptions& options,
+                          ModelViews* views) {
+  const int w = camera.width(), h = camera.height();
+  if (w <= 0 || h <= 0) throw std::invalid_argument("RenderMesh: the camera has no pixels");
+  const ViewSet want{options.depth, options.index, options.color, options.normal};
+  if (!want.depth && !want.index && !want.color && !want.normal) throw std::invalid_argument("RenderMesh: no view was asked for");
+  if (want.color && mesh.colors.empty()) throw std::invalid_argument("RenderMesh: a colour view needs a mesh with colours");
+  const DeviceMesh m = UploadMesh(stream, mesh, "RenderMesh", kMeshAll);
+  bslam_buffer2d pods[4];
+  ViewImages(w, h, want, pods);
+  const bslam_camera4f cam = camera.pod();
+  views->width = w;
+  views->height = h;
+  views->camera_T_global = global_T_camera.Inverse().Matrix3x4();
+  Check(bslam_render_mesh(ctx_, stream, &views->camera_T_global, &cam, m.vertices, AddressOf(m.positions), AddressOf(m.normals), AddressOf(m.colors), m.triangles,
+                          AddressOf(m.indices), options.min_depth, options.max_depth, options.cull_backfaces ? 1 : 0, 1.0f / raw_to_float_depth_,
+                          want.depth ? &pods[0] : nullptr, want.index ? &pods[1] : nullptr, want.color ? &pods[2] : nullptr, want.normal ? &pods[3] : nullptr),
+        "bslam_render_mesh");
+  DownloadViews(stream, want, views);
+}
+
 void DirectBA::RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views) {
   const FusedVolume v = Fused("RenderVolume");
   const int w = camera.width(), h = camera.height();

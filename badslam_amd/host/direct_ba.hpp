@@ -448,6 +448,16 @@ class DirectBA {
     bool depth = true, color = true, normal = false;   // the views wanted, at least one
   };
   void RenderVolume(hipStream_t stream, const SE3f& global_T_camera, const PinholeCamera4f& camera, const VolumeViewOptions& options, ModelViews* views);
+  // Views of a triangle mesh from a pose (bslam_render_mesh): the nearest triangle per pixel as depth (units of a keyframe's depth
+  // image), triangle id, perspective-correct colour and normal -- of the result of ExtractMesh, SmoothMesh, SimplifyMesh, DecimateMesh
+  // or LoadPLY alike.  Without vertex normals the normal view shows face normals; a colour view of a mesh without colours throws
+  // std::invalid_argument.  The mesh is uploaded per call; the device images are those of RenderModel.
+  struct MeshViewOptions {
+    float min_depth = 0.05f, max_depth = 50.f;   // metres; a triangle with a vertex outside the range is dropped, not clipped
+    bool cull_backfaces = true;                  // draw only triangles seen counter-clockwise (from free space, for an extracted mesh)
+    bool depth = true, index = false, color = true, normal = false;   // the views wanted, at least one
+  };
+  void RenderMesh(hipStream_t stream, const Mesh& mesh, const SE3f& global_T_camera, const PinholeCamera4f& camera, const MeshViewOptions& options, ModelViews* views);
   // Axis-aligned box of the valid (non-NaN) surfels; false when there is none.
   bool ModelBounds(hipStream_t stream, float min[3], float max[3]) const;
 

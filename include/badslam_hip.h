@@ -1037,6 +1037,59 @@ int bslam_raycast_volume(bslam_context* ctx, void* stream, const bslam_volume* v
                          const bslam_camera4f* camera, float min_depth, float max_depth, float step, float metres_to_depth,
                          const bslam_buffer2d* out_depth, const bslam_buffer2d* out_color, const bslam_buffer2d* out_normal);
 
+/* Views of an indexed triangle mesh from a pose (DESIGN.md 8 "Mesh views", csrc/render_mesh_kernels.hpp): depth, triangle id,
+ * colour and normal of the nearest surface per pixel, with the conventions and outputs of bslam_render_surfels.  The mesh has V
+ * vertices and T triangles in device arrays laid out as bslam_extract_mesh writes them -- positions float[3 V], normals
+ * float[3 V] (may be null), colors uchar4[V] (may be null), indices uint32[3 T] -- and may come from anywhere.  All arithmetic
+ * is fp32 in a fixed expression order; the result does not depend on the order in which triangles arrive: two calls give
+ * identical bits.
+ * Vertex v:  L = ((m0 x + m1 y) + m2 z) + m3 per row of camera_T_global;  px = fx * (L.x / L.z) + cx, py alike.
+ * Triangle t = (a, b, c) draws nothing when two of its indices are equal; when one of its nine camera-frame coordinates is not
+ * finite; when one of its three L.z lies outside [min_depth, max_depth] (dropped, not clipped); when its pixel-space area in its
+ * own winding,  A = (b.px - a.px) * (c.py - a.py) - (b.py - a.py) * (c.px - a.px),  is 0; and, with cull_backfaces = 1, when
+ * not A < 0.  A < 0 is front-facing: counter-clockwise seen from the camera (x right, y down, z forward), which is how
+ * bslam_extract_mesh winds its triangles seen from free space.
+ * Coverage: the rule of bslam_reproject_depth with the three vertices (v0, v1, v2) taken in ascending vertex id, every edge
+ * evaluated from the lower id to the higher, so that two triangles that share an edge get bit-identical edge values and no
+ * pixel centre falls between them.  At a pixel centre:  w0 = edge(v1 -> v2), w1 = -edge(v0 -> v2), w2 = edge(v0 -> v1); covered
+ * iff all three are >= 0 or all <= 0 and s = (w0 + w1) + w2 is not 0;  b_k = (w_k / s) / z_k;  z = 1 / ((b0 + b1) + b2); drawn
+ * iff z > 0.  The pixel keeps the smallest key (float_bits(z) << 32) | t: the nearest surface, and among bit-equal depths the
+ * lower triangle id.
+ * Outputs, each of the camera's size and optional (null = not written), at least one given, rows aligned to 2 / 4 / 4 / 4 bytes:
+ *   out_depth   u16     (u16)(metres_to_depth * z + 0.5f), 0 where nothing was drawn or the value exceeds 65535
+ *   out_index   u32     the triangle id, 0xFFFFFFFF where nothing was drawn
+ *   out_color   uchar4  needs colors: per channel u8(fminf(z * ((b0 * c0 + b1 * c1) + b2 * c2) + 0.5f, 255.0f)) with c_k the
+ *                       channel of v_k as float (perspective-correct), alpha 255; 0 where nothing was drawn
+ *   out_normal  12 B    three floats, a unit vector in the camera frame, 0 where nothing was drawn or its length is 0: with
+ *                       normals, z * ((b0 * n0 + b1 * n1) + b2 * n2) per component, rotated by camera_T_global and divided by
+ *                       its length; without, the face normal (the cross product of the camera-frame edges b - a and c - a),
+ *                       negated where it points away from the camera
+ * triangle_count == 0 or vertex_count == 0 gives empty views.  An index >= vertex_count is never dereferenced: as in
+ * bslam_mesh_components the call returns BSLAM_ERR_INVALID_ARGUMENT, the outputs are then unspecified, and nothing outside the
+ * given buffers is touched.  Refused without a launch: null required arguments, no output at all, out_color without colors,
+ * min_depth, max_depth or metres_to_depth not finite and > 0, min_depth > max_depth, cull_backfaces other than 0 or 1, a camera
+ * outside the limits of bslam_render_surfels, misaligned (4 byte) arrays or image rows, outputs that overlap each other or an
+ * input.  Not done: clipping at the near plane, several views per call, anti-aliasing.
+ * Synchronises `stream`: the error word of the index test is read back.  The key image and the queue of large triangles live in the
+ * context's scratch and are released by bslam_destroy.  Every rank of a surfel-sharded run renders the mesh it was given;
+ * nothing is exchanged. */
+int bslam_render_mesh(bslam_context* ctx, void* stream, const bslam_mat3x4* camera_T_global, const bslam_camera4f* camera,
+                      uint32_t vertex_count, const float* positions, const float* normals /* may be null */,
+                      const void* colors /* uchar4[V], may be null */, uint32_t triangle_count, const uint32_t* indices,
+                      float min_depth, float max_depth, int cull_backfaces, float metres_to_depth,
+                      const bslam_buffer2d* out_depth, const bslam_buffer2d* out_index, const bslam_buffer2d* out_color,
+                      const bslam_buffer2d* out_normal);
+/* How bslam_render_mesh works, for measurements (tools/bench_render_mesh.py); the views are the same bits for every setting.
+ *   small_box                a triangle whose box holds at most this many pixel centres is drawn by its own lane, a larger one
+ *                            by its whole wave (default 64; 0: no triangle by its lane alone)
+ *   wave_box                 a box of more centres than this is queued and drawn by eight workgroups in a launch behind the draw
+ *                            pass (default 256; 0: every box above small_box; INT_MAX: none, and that launch is left out)
+ *   project_once             0 (default): the draw pass projects the three vertices of every triangle itself;  1: a vertex pass
+ *                            projects every vertex once into scratch, 12 bytes per vertex, which the draw pass reads
+ *   resolve_reads_projected  0 (default): the resolve pass projects the winner's vertices again;  1 (needs project_once): it
+ *                            reads those records */
+int bslam_set_render_mesh_tuning(bslam_context* ctx, int small_box, int wave_box, int project_once, int resolve_reads_projected);
+
 /* Place recognition (in place of the FAST + BRIEF + DBoW2 half of vis::LoopDetector::AddImage, BS/loop_detector.cc:98-127,
  * 160-167): one Harris corner with an unoriented 256-bit BRIEF descriptor per cell of 16 x 16 pixels of a keyframe.  All
  * arithmetic is integer (csrc/place_kernels.hpp, DESIGN.md 8 "Place recognition"); two calls give identical bits.

@@ -7,7 +7,7 @@ has a ground truth, prints the ATE RMSE.
                             [--ba-iterations 10] [--max-depth 3.0] [--end-frame N] [--ba-cost]
                             [--pyramid-level-for-depth L] [--pyramid-level-for-color L]
                             [--median-filter-and-densify-iterations N] [--render-dir DIR] [--render-every N] [--render-radius-scale S]
-                            [--render-source {surfels,volume}]
+                            [--render-source {surfels,volume,mesh}]
                             [--place-recognition] [--place-min-gap N]
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
                             [--mesh-smooth-iterations N] [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-boundary fixed|rim|free]
@@ -36,6 +36,8 @@ cell of that many pixels a side while its radius is that of one pixel, so that s
 --render-source volume: the views are ray-cast from the fused surface instead of drawn from the discs (DirectBA.RenderVolume):
 the keyframes are fused once with the --mesh-* options, whether or not --mesh is given, and every view is sampled at the voxel
 size up to --max-depth.  The directory has the same layout.
+--render-source mesh: the views are drawn from the triangle mesh that --mesh writes (DirectBA.RenderMesh), i.e. after
+--mesh-min-component, the smoothing, --mesh-simplify-cell and the decimation, back faces culled, up to --max-depth; it needs --mesh.
 
 --mesh PATH: after the last BA, all keyframes are fused into a truncated signed distance volume at their optimised poses
 (DirectBA.FuseKeyframes) over the box of the surfel model (DirectBA.ModelBounds) padded by the truncation, and its surface
@@ -108,12 +110,15 @@ def check_level_fits(width, height, level):
         raise ValueError(f"pyramid level {level} does not fit a {width}x{height} dataset: levels are 0 ... 3 and the size must be divisible by 2^level")
 
 
-def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0, source="surfels", max_depth=50.0, min_count=1):
+def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0, source="surfels", max_depth=50.0, min_count=1, mesh=None):
     """Writes the model views from the poses of keyframes[::every] -- (keyframe id, timestamp string) pairs -- as a TUM-style
     directory; deleted keyframes are left out.  source "surfels": RenderModel; "volume": RenderVolume of the fused volume, up to
-    max_depth and over the samples at least min_count keyframes saw.  Returns the (keyframe id, timestamp) pairs written."""
-    if source not in ("surfels", "volume"):
-        raise ValueError("--render-source must be surfels or volume")
+    max_depth and over the samples at least min_count keyframes saw; "mesh": RenderMesh of the mesh dict `mesh`, up to max_depth.
+    Returns the (keyframe id, timestamp) pairs written."""
+    if source not in ("surfels", "volume", "mesh"):
+        raise ValueError("--render-source must be surfels, volume or mesh")
+    if source == "mesh" and mesh is None:
+        raise ValueError("--render-source mesh needs a mesh")
     if every < 1:
         raise ValueError("--render-every must be at least 1")
     os.makedirs(os.path.join(str(render_dir), "depth"), exist_ok=True)
@@ -126,6 +131,8 @@ def render_keyframes(ba, keyframes, render_dir, every=1, radius_scale=1.0, sourc
         pose = ba.keyframe_pose(kf_id)
         if source == "volume":
             views = ba.RenderVolume(pose, max_depth=max_depth, min_count=min_count, views=("depth", "color"))
+        elif source == "mesh":
+            views = ba.RenderMesh(mesh, pose, max_depth=max_depth, views=("depth", "color"))
         else:
             views = ba.RenderModel(pose, radius_scale=radius_scale, views=("depth", "color"))
         png.write_png(os.path.join(str(render_dir), "depth", f"{ts}.png"), views["depth"])
@@ -198,6 +205,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
         raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
     decimate = mesh_decimate_ratio is not None or mesh_decimate_vertices is not None
+    if render_dir and render_source == "mesh" and not mesh:
+        raise ValueError("--render-source mesh renders the mesh that --mesh writes: give --mesh PATH")
     if mesh_smooth_iterations < 0:
         raise ValueError("--mesh-smooth-iterations must be >= 0")
     smooth = mesh_smooth_iterations > 0
@@ -235,7 +244,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if place_recognition:
         result["place_recognition"] = slam.place_recognition_log()
     fused = None
-    if render_dir:
+    if render_dir and render_source != "mesh":
         if render_source == "volume":
             fused = fuse_model(slam.ba(), mesh_voxel_size, mesh_truncation)
             result["volume"] = {"origin": fused[0], "dims": fused[1]}
@@ -289,6 +298,9 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             if surface_report:
                 with open(surface_report, "w") as f:
                     json.dump(surface, f, indent=1)
+    if render_dir and render_source == "mesh":      # the mesh as written: after the clean-up, smoothing, simplification and decimation
+        result["rendered"] = render_keyframes(slam.ba(), keyframes, render_dir, render_every, source="mesh", max_depth=max_depth, mesh=m)
+        result["render_dir"] = str(render_dir)
     if mesh:
         result["mesh"] = {"path": str(mesh), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "origin": origin, "dims": dims}
         if report is not None:
@@ -322,7 +334,7 @@ def arg_parser():
     ap.add_argument("--render-dir", default=None)
     ap.add_argument("--render-every", type=int, default=1)
     ap.add_argument("--render-radius-scale", type=float, default=None)
-    ap.add_argument("--render-source", choices=("surfels", "volume"), default="surfels")
+    ap.add_argument("--render-source", choices=("surfels", "volume", "mesh"), default="surfels")
     ap.add_argument("--place-recognition", action="store_true")
     ap.add_argument("--place-min-gap", type=int, default=10)
     ap.add_argument("--mesh", default=None)

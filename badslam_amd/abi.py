@@ -63,6 +63,18 @@ class Volume(C.Structure):
     _fields_ = [("origin", C.c_float * 3), ("voxel_size", C.c_float), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32)]
 
 
+MESH_REPORT_FIELDS = ("referenced_vertices", "unique_edges", "boundary_edges", "interior_edges", "nonmanifold_edges", "inconsistent_edges", "blocked_vertices",
+                      "loops", "longest_loop", "loop_edges", "open_boundary_slots")
+
+
+class MeshReport(C.Structure):
+    """bslam_mesh_report: the census of bslam_mesh_topology."""
+    _fields_ = [(name, C.c_uint32) for name in MESH_REPORT_FIELDS] + [("reserved", C.c_uint32), ("euler", C.c_int64)]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name in MESH_REPORT_FIELDS + ("euler",)}
+
+
 class SE3f(C.Structure):
     _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3)]
 
@@ -141,6 +153,12 @@ SIGNATURES = {
     "bslam_smooth_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32,
                                     C.c_void_p, C.c_void_p]),
     "bslam_smooth_stage_times": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "bslam_clean_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
+    "bslam_mesh_topology": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, P(MeshReport), C.c_void_p, C.c_void_p]),
+    "bslam_fill_mesh_holes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
+    "bslam_repair_stage_times": (C.c_int, [C.c_void_p, P(C.c_float)]),
     "bslam_point_mesh_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float,
                                             C.c_uint64, C.c_void_p, C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "bslam_sample_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,

@@ -223,6 +223,14 @@ struct bslam_context {
   // the last call's five stage times (bslam_smooth_stage_times)
   bslam::StageEvents<7> smooth_events;
   float smooth_stage_ms[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+  bslam::Slab repair;        // bslam_clean_mesh: words | per vertex or triangle: the keys of the two sorts, sorted keys, ids, ranks, run heads, head flags | per vertex:
+                             // representatives, ranks, flags | per triangle: flags, ranks | scan sums | the radix sort's scratch; bslam_mesh_topology and
+                             // bslam_fill_mesh_holes: words | per slot: keys, sorted keys, slots, head flags, ranks, run starts, boundary flags and numbers | per vertex:
+                             // flags, boundary counts, first boundary slot | per boundary slot: two buffers of next, label and open, loop lengths, fans | scan sums |
+                             // the sort's scratch; reserved by the first of these calls
+  // those calls while profiling is on: a pair of events around each of up to eight stages and the last call's times (bslam_repair_stage_times)
+  bslam::StageEvents<16> repair_events;
+  float repair_stage_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   bslam::Slab exchange;      // staging of the multi-rank exchanges (PCG shared unknowns, intrinsics sums)
   bslam_allreduce_fn allreduce = nullptr;   // bslam_set_allreduce: sum across the ranks of a surfel-sharded run
   void* allreduce_user = nullptr;

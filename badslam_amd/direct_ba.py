@@ -92,6 +92,11 @@ def host_lib():
     L.bsh_simplified_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
     L.bsh_decimate_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
     L.bsh_decimated_copy.argtypes = [f32p, f32p, u8p, u32p, u32p]
+    L.bsh_clean_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.POINTER(C.c_int), u64p]
+    L.bsh_cleaned_copy.argtypes = [f32p, f32p, u8p, u32p, u32p, u32p]
+    L.bsh_mesh_topology.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.POINTER(abi.MeshReport), u32p, u32p]
+    L.bsh_fill_mesh_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.c_uint32, u64p]
+    L.bsh_filled_copy.argtypes = [f32p, f32p, u8p, u32p]
     L.bsh_smooth_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32]
     L.bsh_smooth_extracted_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_float, C.c_float, C.c_uint32, u64p]
     L.bsh_smoothed_copy.argtypes = [f32p, f32p]
@@ -882,6 +887,80 @@ class DirectBA:
                    colors=None if col is None else np.zeros((V, 4), np.uint8), triangles=np.zeros((T, 3), np.uint32), vertex_cluster=np.zeros(len(pos), np.uint32))
         self._check(self.L.bsh_simplified_copy(_f(out["positions"]), None if nrm is None else _f(out["normals"]), None if col is None else _u8(out["colors"]),
                                                _u32(out["triangles"]), _u32(out["vertex_cluster"])))
+        if col is not None and channels == 3:
+            out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
+        return out
+
+    # --- mesh repair (bslam_clean_mesh, bslam_mesh_topology, bslam_fill_mesh_holes)
+    def _mesh_result(self, V, T, nrm, col, **extra):
+        """The zeroed dict of an operator's result: the keys of ExtractMesh, normals / colors None where the input has none."""
+        return dict(positions=np.zeros((V, 3), np.float32), normals=None if nrm is None else np.zeros((V, 3), np.float32),
+                    colors=None if col is None else np.zeros((V, 4), np.uint8), triangles=np.zeros((T, 3), np.uint32), **extra)
+
+    def CleanMesh(self, mesh, weld=True, remove_duplicates=True, remove_unreferenced=True):
+        """`mesh` (the dict of ExtractMesh or LoadPLY) without what it should not hold.  weld: vertices with equal coordinates (-0.0
+        equals 0.0) become the one with the smallest id, whose normal and colour stay -- a triangle soup gets its shared vertices back.
+        Triangles that then repeat a vertex are dropped.  remove_duplicates: of the triangles on the same three vertices, whatever their
+        orientation, the first stays.  remove_unreferenced: vertices that no surviving triangle names are dropped (never those of a mesh
+        without triangles).  What stays keeps its order and its bits, so a clean mesh comes back identical.  -> dict with the keys of
+        ExtractMesh (normals / colors None where the input has none, colors with the input's channel count) plus vertex_map (V,) u32
+        and triangle_map (T,) u32 -- the output id of every input vertex and triangle, 0xFFFFFFFF where dropped -- and report, a dict
+        of welded_vertices, unreferenced_vertices, degenerate_triangles and duplicate_triangles."""
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "CleanMesh")
+        counts = (C.c_uint64 * 6)()
+        flags = (C.c_int * 3)(int(bool(weld)), int(bool(remove_duplicates)), int(bool(remove_unreferenced)))
+        self._check(self.L.bsh_clean_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), None if col is None else _u8(col), len(tri),
+                                          _u32(tri), flags, counts))
+        out = self._mesh_result(int(counts[0]), int(counts[1]), nrm, col, vertex_map=np.zeros(len(pos), np.uint32), triangle_map=np.zeros(len(tri), np.uint32),
+                                report=dict(welded_vertices=int(counts[2]), unreferenced_vertices=int(counts[3]), degenerate_triangles=int(counts[4]),
+                                            duplicate_triangles=int(counts[5])))
+        self._check(self.L.bsh_cleaned_copy(_f(out["positions"]), None if nrm is None else _f(out["normals"]), None if col is None else _u8(out["colors"]),
+                                            _u32(out["triangles"]), _u32(out["vertex_map"]), _u32(out["triangle_map"])))
+        if col is not None and channels == 3:
+            out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
+        return out
+
+    def MeshTopology(self, mesh, per_slot=False):
+        """The census of the edges and boundary loops of `mesh` (the dict of ExtractMesh or LoadPLY; triangles that repeat a vertex
+        are refused: CleanMesh first) -> dict of referenced_vertices, unique_edges, boundary_edges (used by one triangle),
+        interior_edges (by two), nonmanifold_edges (by more), inconsistent_edges (interior, and both triangles run along it the same
+        way), blocked_vertices (boundary vertices that do not have exactly one boundary edge in and one out), loops, longest_loop,
+        loop_edges, open_boundary_slots (boundary edges on no loop), euler = referenced_vertices - unique_edges + triangles, components
+        (of MeshComponents, vertices without a triangle included), and closed (no boundary and no non-manifold edge), manifold_edges
+        (no non-manifold edge), oriented (no inconsistent edge).  per_slot=True adds edge_uses (T, 3) u32 -- the uses of the edge from
+        corner k to corner k + 1 -- and loop_of_slot (T, 3) u32: the smallest slot 3 t + k of the boundary loop that edge lies on,
+        0xFFFFFFFF for every other."""
+        pos, _, _, tri, _ = self._mesh_arrays(mesh, "MeshTopology")
+        report = abi.MeshReport()
+        uses = np.zeros((len(tri), 3), np.uint32) if per_slot else None
+        loops = np.zeros((len(tri), 3), np.uint32) if per_slot else None
+        self._check(self.L.bsh_mesh_topology(self._ba, self.stream, len(pos), len(tri), _u32(tri), C.byref(report), None if uses is None else _u32(uses),
+                                             None if loops is None else _u32(loops)))
+        out = report.as_dict()
+        labels, _ = self.MeshComponents(dict(positions=pos, triangles=tri))
+        out["components"] = int((labels == np.arange(len(pos), dtype=np.uint32)).sum())
+        out["closed"] = out["boundary_edges"] == 0 and out["nonmanifold_edges"] == 0
+        out["manifold_edges"] = out["nonmanifold_edges"] == 0
+        out["oriented"] = out["inconsistent_edges"] == 0
+        if per_slot:
+            out["edge_uses"], out["loop_of_slot"] = uses, loops
+        return out
+
+    def FillHoles(self, mesh, max_hole_edges):
+        """`mesh` (the dict of ExtractMesh or LoadPLY) with every boundary loop of at most max_hole_edges (3 .. 4096) edges closed by
+        a new vertex at the centroid of the loop's vertices (mean colour, normalised sum of the normals) and a fan of triangles that
+        continues the orientation across the boundary.  Larger loops -- the outer rim of an open scan -- stay, and so does every
+        boundary through a vertex where more than two boundary edges meet.  The input comes first and unchanged; the new vertices and
+        triangles follow.  -> dict with the keys of ExtractMesh plus filled_holes."""
+        if not 0 <= int(max_hole_edges) <= 0xFFFFFFFF:
+            raise ValueError("FillHoles: max_hole_edges must fit 32 bits")
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "FillHoles")
+        counts = (C.c_uint64 * 3)()
+        self._check(self.L.bsh_fill_mesh_holes(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), None if col is None else _u8(col), len(tri),
+                                               _u32(tri), int(max_hole_edges), counts))
+        out = self._mesh_result(int(counts[0]), int(counts[1]), nrm, col, filled_holes=int(counts[2]))
+        self._check(self.L.bsh_filled_copy(_f(out["positions"]), None if nrm is None else _f(out["normals"]), None if col is None else _u8(out["colors"]),
+                                           _u32(out["triangles"])))
         if col is not None and channels == 3:
             out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
         return out

@@ -363,6 +363,80 @@ int bsh_decimated_copy(float* positions, float* normals, uint8_t* colors, uint32
     g_decimated_map = std::vector<uint32_t>();
   });
 }
+// DirectBA::CleanMesh of host arrays in the same two steps: bsh_clean_mesh (flags3: weld, remove_duplicates, remove_unreferenced) keeps
+// the result for this thread and reports counts6 = {vertices, triangles, welded vertices, unreferenced vertices, degenerate triangles,
+// duplicate triangles}; bsh_cleaned_copy copies it out (vertex_map, triangle_map: one entry per input vertex and triangle; any pointer
+// may be null) and drops it.
+static thread_local DirectBA::Mesh g_cleaned;
+static thread_local std::vector<uint32_t> g_cleaned_vertex_map, g_cleaned_triangle_map;
+int bsh_clean_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles,
+                   const uint32_t* indices, const int* flags3, uint64_t* counts6) {
+  BSH_TRY({
+    g_cleaned = DirectBA::Mesh();
+    g_cleaned_vertex_map.clear();
+    g_cleaned_triangle_map.clear();
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, colors, triangles, indices);
+    DirectBA::CleanOptions options;
+    options.weld = flags3[0] != 0;
+    options.remove_duplicates = flags3[1] != 0;
+    options.remove_unreferenced = flags3[2] != 0;
+    DirectBA::CleanReport report;
+    static_cast<DirectBA*>(ba)->CleanMesh(static_cast<hipStream_t>(stream), mesh, options, &g_cleaned, &g_cleaned_vertex_map, &g_cleaned_triangle_map, &report);
+    counts6[0] = g_cleaned.vertex_count();
+    counts6[1] = g_cleaned.triangle_count();
+    counts6[2] = report.welded_vertices;
+    counts6[3] = report.unreferenced_vertices;
+    counts6[4] = report.degenerate_triangles;
+    counts6[5] = report.duplicate_triangles;
+  });
+}
+int bsh_cleaned_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices, uint32_t* vertex_map, uint32_t* triangle_map) {
+  BSH_TRY({
+    copy_out(positions, g_cleaned.positions);
+    copy_out(normals, g_cleaned.normals);
+    copy_out(colors, g_cleaned.colors);
+    copy_out(indices, g_cleaned.indices);
+    copy_out(vertex_map, g_cleaned_vertex_map);
+    copy_out(triangle_map, g_cleaned_triangle_map);
+    g_cleaned = DirectBA::Mesh();
+    g_cleaned_vertex_map = std::vector<uint32_t>();
+    g_cleaned_triangle_map = std::vector<uint32_t>();
+  });
+}
+// DirectBA::MeshTopology of `triangles` index triples over `vertices` vertices: *report (a bslam_mesh_report), edge_uses and loop_of_slot
+// (3 * triangles entries each, either may be null).
+int bsh_mesh_topology(void* ba, void* stream, uint64_t vertices, uint64_t triangles, const uint32_t* indices, void* report, uint32_t* edge_uses, uint32_t* loop_of_slot) {
+  BSH_TRY({
+    std::vector<uint32_t> triples, uses, loops;
+    if (triangles) triples.assign(indices, indices + 3 * static_cast<size_t>(triangles));
+    static_cast<DirectBA*>(ba)->MeshTopology(static_cast<hipStream_t>(stream), static_cast<size_t>(vertices), triples, static_cast<bslam_mesh_report*>(report),
+                                             edge_uses ? &uses : nullptr, loop_of_slot ? &loops : nullptr);
+    copy_out(edge_uses, uses);
+    copy_out(loop_of_slot, loops);
+  });
+}
+// DirectBA::FillMeshHoles of host arrays in the same two steps: bsh_fill_mesh_holes keeps the result for this thread and reports
+// counts3 = {vertices, triangles, holes filled}; bsh_filled_copy copies it out (any pointer may be null) and drops it.
+static thread_local DirectBA::Mesh g_filled;
+int bsh_fill_mesh_holes(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, const uint8_t* colors, uint64_t triangles,
+                        const uint32_t* indices, uint32_t max_hole_edges, uint64_t* counts3) {
+  BSH_TRY({
+    g_filled = DirectBA::Mesh();
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, colors, triangles, indices);
+    counts3[2] = static_cast<DirectBA*>(ba)->FillMeshHoles(static_cast<hipStream_t>(stream), mesh, max_hole_edges, &g_filled);
+    counts3[0] = g_filled.vertex_count();
+    counts3[1] = g_filled.triangle_count();
+  });
+}
+int bsh_filled_copy(float* positions, float* normals, uint8_t* colors, uint32_t* indices) {
+  BSH_TRY({
+    copy_out(positions, g_filled.positions);
+    copy_out(normals, g_filled.normals);
+    copy_out(colors, g_filled.colors);
+    copy_out(indices, g_filled.indices);
+    g_filled = DirectBA::Mesh();
+  });
+}
 // DirectBA::SmoothMesh of host arrays in the same two steps: bsh_smooth_mesh (normals and indices may be null; boundary 0 fixed, 1 rim,
 // 2 free) keeps the new positions and normals for this thread; bsh_smoothed_copy copies them out (either pointer may be null) and
 // drops them.  Colours and indices are the caller's own.

@@ -932,6 +932,74 @@ void DirectBA::SmoothMesh(hipStream_t stream, const Mesh& mesh, const SmoothOpti
   out->normals = std::move(smoothed.normals);
 }
 
+DirectBA::DeviceMesh DirectBA::CleanMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                                 const u32* indices, const CleanOptions& options, CleanReport* report) {
+  DeviceMesh c = ResultMesh(vertices, triangles, normals, colors, true, true);
+  c.triangle_map.reset(new DeviceArray<u32>(triangles));
+  u32 counts[4] = {0, 0, 0, 0};
+  Check(bslam_clean_mesh(ctx_, stream, vertices, triangles, positions, normals, colors, indices, options.weld ? 1 : 0, options.remove_duplicates ? 1 : 0,
+                         options.remove_unreferenced ? 1 : 0, c.positions->address(), AddressOf(c.normals), AddressOf(c.colors), c.indices->address(),
+                         c.vertex_map->address(), c.triangle_map->address(), &c.vertices, &c.triangles, counts),
+        "bslam_clean_mesh");
+  if (report) *report = CleanReport{counts[0], counts[1], counts[2], counts[3]};
+  return c;
+}
+
+void DirectBA::CleanMesh(hipStream_t stream, const Mesh& mesh, const CleanOptions& options, Mesh* out, std::vector<u32>* vertex_map, std::vector<u32>* triangle_map,
+                         CleanReport* report) {
+  const DeviceMesh m = UploadMesh(stream, mesh, "CleanMesh", kMeshAll);
+  const DeviceMesh c = CleanMeshOnDevice(stream, m.vertices, m.triangles, m.positions->address(), AddressOf(m.normals), AddressOf(m.colors), m.indices->address(), options,
+                                         report);
+  if (triangle_map) {
+    triangle_map->resize(c.triangle_map->count());
+    c.triangle_map->Download(stream, triangle_map->data(), triangle_map->size());   // rides on the wait of DownloadMesh
+  }
+  DownloadMesh(stream, c, out, vertex_map);
+}
+
+void DirectBA::MeshTopology(hipStream_t stream, const Mesh& mesh, bslam_mesh_report* report, std::vector<u32>* edge_uses, std::vector<u32>* loop_of_slot) {
+  CheckMeshSizes(mesh, "MeshTopology", kMeshIndices);
+  MeshTopology(stream, mesh.vertex_count(), mesh.indices, report, edge_uses, loop_of_slot);
+}
+
+void DirectBA::MeshTopology(hipStream_t stream, size_t vertex_count, const std::vector<u32>& indices, bslam_mesh_report* report, std::vector<u32>* edge_uses,
+                            std::vector<u32>* loop_of_slot) {
+  if (indices.size() % 3 != 0 || indices.size() > 0x7fffffffull || 3 * static_cast<uint64_t>(vertex_count) > 0x7fffffffull)
+    throw std::invalid_argument("MeshTopology: indices must hold 3 entries per triangle, and the mesh must fit one device image");
+  DeviceMesh m = UploadMesh(stream, Mesh(), nullptr, kMeshIndices, &indices);   // the indices alone
+  m.vertices = static_cast<u32>(vertex_count);
+  const size_t slots = size_t{3} * m.triangles;
+  DeviceArray<u32> uses(edge_uses ? slots : 0), loops(loop_of_slot ? slots : 0);
+  Check(bslam_mesh_topology(ctx_, stream, m.vertices, m.triangles, m.indices->address(), report, edge_uses ? uses.address() : nullptr,
+                            loop_of_slot ? loops.address() : nullptr),
+        "bslam_mesh_topology");
+  if (edge_uses) { edge_uses->resize(slots); uses.Download(stream, edge_uses->data(), slots); }
+  if (loop_of_slot) { loop_of_slot->resize(slots); loops.Download(stream, loop_of_slot->data(), slots); }
+  Wait(stream);
+}
+
+DirectBA::DeviceMesh DirectBA::FillMeshHolesOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                                     const u32* indices, u32 max_hole_edges) {
+  u32 v = 0, t = 0, filled = 0;
+  Check(bslam_fill_mesh_holes(ctx_, stream, vertices, triangles, positions, normals, colors, indices, max_hole_edges, 0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, &v,
+                              &t, &filled),
+        "bslam_fill_mesh_holes");
+  DeviceMesh f = ResultMesh(v, t, normals, colors, true, false);
+  Check(bslam_fill_mesh_holes(ctx_, stream, vertices, triangles, positions, normals, colors, indices, max_hole_edges, v, t, f.positions->address(), AddressOf(f.normals),
+                              AddressOf(f.colors), f.indices->address(), nullptr, &f.vertices, &f.triangles, &f.filled_holes),
+        "bslam_fill_mesh_holes");
+  if (f.vertices != v || f.triangles != t || f.filled_holes != filled) throw std::runtime_error("FillMeshHoles: the mesh changed between the two calls");
+  return f;
+}
+
+u32 DirectBA::FillMeshHoles(hipStream_t stream, const Mesh& mesh, u32 max_hole_edges, Mesh* out) {
+  const DeviceMesh m = UploadMesh(stream, mesh, "FillMeshHoles", kMeshAll);
+  const DeviceMesh f = FillMeshHolesOnDevice(stream, m.vertices, m.triangles, m.positions->address(), AddressOf(m.normals), AddressOf(m.colors), m.indices->address(),
+                                             max_hole_edges);
+  DownloadMesh(stream, f, out, nullptr);
+  return f.filled_holes;
+}
+
 void DirectBA::RenderMesh(hipStream_t stream, const Mesh& mesh, const SE3f& global_T_camera, const PinholeCamera4f& camera, const MeshViewOptions& options,
                           ModelViews* views) {
   const int w = camera.width(), h = camera.height();

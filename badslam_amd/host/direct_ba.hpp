@@ -283,7 +283,9 @@ class DirectBA {
     std::unique_ptr<DeviceArray<float>> positions, normals;
     std::unique_ptr<DeviceArray<uchar4_t>> colors;
     std::unique_ptr<DeviceArray<u32>> indices, vertex_map;
+    std::unique_ptr<DeviceArray<u32>> triangle_map;   // of a cleaning: the output triangle of every input triangle
     u32 vertices = 0, triangles = 0, rounds = 0;
+    u32 filled_holes = 0;                             // of a hole filling
     DeviceMesh() = default;
     DeviceMesh(u32 v, u32 t) : positions(new DeviceArray<float>(size_t{3} * v)), normals(new DeviceArray<float>(size_t{3} * v)), colors(new DeviceArray<uchar4_t>(v)),
                                indices(new DeviceArray<u32>(size_t{3} * t)), vertices(v), triangles(t) {}
@@ -352,6 +354,34 @@ class DirectBA {
   // ... and on a caller's device arrays (4 byte aligned; normals may be null; see bslam_smooth_mesh).
   DeviceMesh SmoothMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const u32* indices,
                                 const SmoothOptions& options);
+  // Mesh repair (bslam_clean_mesh): with weld, vertices with equal coordinates become the one with the smallest id; triangles that repeat a
+  // vertex are dropped; with remove_duplicates, of the triangles on the same three vertices the first stays; with remove_unreferenced,
+  // vertices that no surviving triangle names are dropped (never those of a point cloud).  What stays keeps its order and its bits.
+  struct CleanOptions {
+    bool weld = true, remove_duplicates = true, remove_unreferenced = true;
+  };
+  struct CleanReport {
+    u32 welded_vertices = 0, unreferenced_vertices = 0, degenerate_triangles = 0, duplicate_triangles = 0;
+  };
+  // Host arrays: mesh.normals and mesh.colors may be empty; *out gets what the input has.  vertex_map and triangle_map (may be null)
+  // receive the output id of every input vertex and triangle, 0xffffffff where it was dropped; report may be null.
+  void CleanMesh(hipStream_t stream, const Mesh& mesh, const CleanOptions& options, Mesh* out, std::vector<u32>* vertex_map, std::vector<u32>* triangle_map,
+                 CleanReport* report);
+  // The same on device arrays (4 byte aligned; normals and colors may be null; see bslam_clean_mesh); the result stays on the device.
+  DeviceMesh CleanMeshOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors, const u32* indices,
+                               const CleanOptions& options, CleanReport* report);
+  // The census of the edges and boundary loops of mesh.indices (bslam_mesh_topology); edge_uses and loop_of_slot, one entry per
+  // triangle corner, may be null.  Triangles that repeat a vertex are refused: clean first.
+  void MeshTopology(hipStream_t stream, const Mesh& mesh, bslam_mesh_report* report, std::vector<u32>* edge_uses, std::vector<u32>* loop_of_slot);
+  // The same of index triples over vertex_count vertices, for a caller that has no positions at hand.
+  void MeshTopology(hipStream_t stream, size_t vertex_count, const std::vector<u32>& indices, bslam_mesh_report* report, std::vector<u32>* edge_uses,
+                    std::vector<u32>* loop_of_slot);
+  // Hole filling (bslam_fill_mesh_holes): every boundary loop of at most max_hole_edges (3 .. 4096) edges gets a vertex at the centroid of
+  // its vertices and a fan of triangles; the input comes first and unchanged.  Returns the number of holes filled.
+  u32 FillMeshHoles(hipStream_t stream, const Mesh& mesh, u32 max_hole_edges, Mesh* out);
+  // The same on device arrays; two calls, the first for the counts.  The result stays on the device.
+  DeviceMesh FillMeshHolesOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
+                                   const u32* indices, u32 max_hole_edges);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.

@@ -864,6 +864,90 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, u
  * steps is in none of them.  Zeros before such a call.  For tools/bench_smooth_mesh.py. */
 int bslam_smooth_stage_times(bslam_context* ctx, float* stage_ms5);
 
+/* Mesh repair: welding and removal of what a mesh should not hold, the census of its edges and boundary loops, and the closing of
+ * small holes (DESIGN.md 8 "Mesh repair", csrc/repair_kernels.hpp).  Everything is integer but the centroid of a hole, so nothing
+ * depends on the order of execution: two calls give identical bits.  A slot is 3 t + k: corner k of triangle t, and the directed
+ * half-edge from corner k to corner (k + 1) % 3 (the slot of "Mesh decimation").
+ * Clean; weld, remove_duplicates and remove_unreferenced are 0 or 1:
+ *   Representative.  With weld, two vertices are the same iff their three coordinates are equal as floats (-0.0f equals +0.0f; the bits
+ *   are compared otherwise); the representative rep(v) of v is the smallest vertex id among the vertices that are the same as v.  Its
+ *   position, normal and colour are the output's: nothing is averaged.  Without weld rep(v) = v.
+ *   Triangles.  Triangle t is looked at as (rep(i0), rep(i1), rep(i2)).  It is degenerate iff two of the three are equal, and is
+ *   dropped.  With remove_duplicates, two triangles that are not degenerate and have the same set of three representatives -- whatever
+ *   their orientation or rotation -- are duplicates: the one with the smallest triangle id stays, the others are dropped.  The
+ *   surviving triangles keep their corner order and their relative order.
+ *   Vertices.  Vertex v is kept iff rep(v) = v and (remove_unreferenced is 0, or T == 0 -- a point cloud keeps its points --, or a
+ *   surviving triangle names it).  Kept vertices keep their relative order and the bits of their attributes, so a clean mesh comes back
+ *   identical and the operation is idempotent.  With all three flags 0 the result is the input less its degenerate triangles.
+ *   vertex_map[v] = the new id of rep(v), triangle_map[t] = the new id of t; 0xffffffff where that was dropped.
+ *   counts4 = {V - the number of representatives, representatives that were not kept, degenerate triangles, duplicate triangles}.
+ * bslam_clean_mesh: the arrays are those of bslam_simplify_mesh (device; room for V vertices and T triangles; out_normals and
+ * out_colors exactly when their inputs are given), vertex_map uint32[V] and triangle_map uint32[T] may be null; the two counts and
+ * counts4 are returned on the host; nothing at or beyond the counts is written.  V == 0 is legal with T == 0.  Refused without a
+ * launch: null required arguments, a flag other than 0 or 1, an out_normals / out_colors that does not match its input, more than
+ * 2^32 - 256 vertices or triangles, misaligned (4 byte) pointers, an output that overlaps an input or another output.  Refused behind
+ * the launches that precede the scatter, by a device error bit, with BSLAM_ERR_INVALID_ARGUMENT and no output written: an index >= V
+ * (never dereferenced) and "a vertex is not finite" (checked with and without weld).  Weld: the stable radix sort twice, by the bits
+ * of z over 32 bits and then by y << 32 | x over 64, so the head of a run of equal keys is its smallest id; head flags, their scan,
+ * and two passes that hand the head to its run.  Duplicates: the same two-pass sort over the sorted triple (lo, mid, hi), by hi over
+ * `bits` bits and then by lo << bits | mid over 2 bits, bits = those of a vertex id.  Then flags, two scans, one read-back, one scatter.
+ * Topology, of the indices alone; a triangle that repeats an index is refused ("a triangle repeats an index": clean first):
+ *   Edges.  The undirected edge of a slot is the pair of its two ends; edge_uses[slot] = the number of slots with that edge.  An edge
+ *   with 1 use is a boundary edge, with 2 an interior edge, with 3 or more a non-manifold edge.  An interior edge whose two slots run
+ *   in the same direction is inconsistently oriented.  euler = referenced vertices - unique edges + T.
+ *   Loops.  A boundary slot is the slot of a boundary edge.  A vertex is passable iff exactly one boundary slot starts at it and
+ *   exactly one ends at it; any other vertex touched by a boundary slot is blocked.  next(h) is the boundary slot that starts where h
+ *   ends, defined iff that vertex is passable.  A loop is a cycle of next; its id is its smallest slot.  loop_of_slot[h] is that id
+ *   for the slots on a loop and 0xffffffff for every other slot: those of other edges, and boundary slots whose walk meets a blocked
+ *   vertex (open_boundary_slots counts the latter).  loops, longest_loop (in edges) and loop_edges (their sum over the loops).
+ * bslam_mesh_topology: indices uint32[3 T], edge_uses uint32[3 T] and loop_of_slot uint32[3 T] (either may be null) are device arrays;
+ * *report is written on the host.  V == 0 is legal with T == 0.  Refused without a launch: null ctx or report, more than 2^32 - 256
+ * vertices or slots, misaligned pointers, an output that overlaps the indices or the other output.  An index >= V and a repeated
+ * index are reported behind the key pass, before anything is decoded or written: *report and both outputs stay untouched.  One
+ * stable sort of (edge, slot), head flags and their scan, the run starts, a census pass, a scan of the boundary flags, a read-back of the number B of
+ * boundary slots, then ceil(log2 B) + 1 rounds of pointer jumping between two buffers (label = min(label, label[next]), open |=
+ * open[next], next = next[next]) whatever the loops look like, an integer count per label, and one read-back.
+ * Hole filling, 3 <= max_hole_edges <= 4096:
+ *   The topology of the input; every loop of n <= max_hole_edges edges is filled, in ascending loop id.  Its slots are visited from
+ *   its smallest slot h0 along next.  The new vertex: position, per axis, (float)(s / (double)n) with s the double sum of the origins
+ *   of the slots in that order, the first added to 0.0;  colour, if present, (S + n / 2) / n per channel in integers, alpha included
+ *   (the rounding of bslam_fuse_keyframes);  normal, if present, (float)(g / sqrt(gg)) per axis with g the double sum of the origins'
+ *   normals in that order and gg = (g.x g.x + g.y g.y) + g.z g.z, or (0, 0, 0) unless gg is finite and > 0.  Slot h = (a -> b) gives
+ *   the triangle (b, a, new vertex): counter-clockwise, consistent with the triangle across the boundary edge.
+ *   Output: the input, unchanged; then the new vertices in loop order; then the new triangles by (loop, place in the walk).
+ *   hole_of_triangle[i] = the ordinal of the loop of appended triangle i.  Larger loops and everything on a blocked vertex stay open.
+ * bslam_fill_mesh_holes: inputs as bslam_clean_mesh; out_positions float[3 vertex_capacity], out_normals, out_colors (exactly when
+ * their inputs are given), out_indices uint32[3 triangle_capacity], hole_of_triangle uint32[triangle_capacity - T] (may be null).
+ * *out_vertex_count = V + *filled_holes and *out_triangle_count on the host.  When out_positions or out_indices is null, or a count
+ * exceeds its capacity, only the counts are returned and nothing is written: call once for the counts and once with buffers
+ * (bslam_extract_mesh).  Refusals as bslam_clean_mesh and bslam_mesh_topology, and max_hole_edges outside [3, 4096].  One lane per
+ * loop walks it.
+ * All three: scratch lives in a context slab of its own that the first of these calls reserves; they synchronise `stream`.  Every
+ * rank of a surfel-sharded run holds the same mesh and computes the same result. */
+typedef struct bslam_mesh_report {
+  uint32_t referenced_vertices, unique_edges, boundary_edges, interior_edges, nonmanifold_edges, inconsistent_edges;
+  uint32_t blocked_vertices, loops, longest_loop, loop_edges, open_boundary_slots, reserved;
+  int64_t euler;
+} bslam_mesh_report;
+int bslam_clean_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                     const float* normals, const void* colors, const uint32_t* indices, int weld, int remove_duplicates,
+                     int remove_unreferenced, float* out_positions, float* out_normals, void* out_colors, uint32_t* out_indices,
+                     uint32_t* vertex_map, uint32_t* triangle_map, uint32_t* out_vertex_count, uint32_t* out_triangle_count,
+                     uint32_t* counts4);
+int bslam_mesh_topology(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const uint32_t* indices,
+                        bslam_mesh_report* report, uint32_t* edge_uses, uint32_t* loop_of_slot);
+int bslam_fill_mesh_holes(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                          const float* normals, const void* colors, const uint32_t* indices, uint32_t max_hole_edges,
+                          uint32_t vertex_capacity, uint32_t triangle_capacity, float* out_positions, float* out_normals,
+                          void* out_colors, uint32_t* out_indices, uint32_t* hole_of_triangle, uint32_t* out_vertex_count,
+                          uint32_t* out_triangle_count, uint32_t* filled_holes);
+/* The device time in milliseconds of the stages of the last of the three calls above on `ctx` that ran while bslam_profile_enable
+ * was on (HOST out), each between a pair of events on the call's stream, zero where a stage did not run.  bslam_clean_mesh: {vertex
+ * keys, weld sorts, representatives, triangle keys, triangle sorts, duplicates, flags and scans, scatter}.  bslam_mesh_topology: {keys,
+ * sort, census, loops, 0, 0, 0, 0}.  bslam_fill_mesh_holes: those four, then {scans of the holes, copy and fans, 0, 0}.  For
+ * tools/bench_mesh_repair.py. */
+int bslam_repair_stage_times(bslam_context* ctx, float* stage_ms8);
+
 /* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
  * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
  * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components

@@ -12,6 +12,7 @@ has a ground truth, prints the ATE RMSE.
                             [--mesh PATH] [--mesh-voxel-size M] [--mesh-truncation M] [--mesh-min-count N] [--mesh-min-component N]
                             [--mesh-smooth-iterations N] [--mesh-smooth-lambda L] [--mesh-smooth-mu M] [--mesh-smooth-boundary fixed|rim|free]
                             [--mesh-simplify-cell M] [--mesh-decimate-ratio R | --mesh-decimate-vertices N]
+                            [--mesh-fill-holes N] [--mesh-clean]
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
                             [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
@@ -60,6 +61,13 @@ measuring against the extracted one); the counts before and after are printed an
 quadric-error edge collapse (DirectBA.DecimateMesh) to R times its vertices, or to N vertices; default off, and at most one of the
 two.  Unlike clustering it spends the vertices where the surface bends and keeps creases and open boundaries.  The decimated mesh is
 what is written and scored; the counts before and after and the number of rounds are printed and reported.
+--mesh-fill-holes N: every hole of the mesh whose boundary has at most N (3 .. 4096) edges is closed by a vertex at the centroid of
+its boundary and a fan of triangles (DirectBA.FillHoles), after --mesh-min-component and before the smoothing; larger boundaries, such
+as the outer rim of an open scan, stay.  --mesh-clean: duplicate and degenerate triangles and the vertices only they name are removed
+(DirectBA.CleanMesh) after --mesh-simplify-cell, so that the decimation sees no doubled face, and after the decimation.  Both are
+off by default.  With either, the census of the mesh as written (DirectBA.MeshTopology: boundary, non-manifold and inconsistently
+oriented edges, boundary loops, Euler characteristic, components) is printed and reported as mesh_topology, with the counts before and
+after under mesh_hole_filling and mesh_cleaning.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 
@@ -200,7 +208,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
         surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
         mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
-        mesh_smooth_boundary="fixed"):
+        mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
         raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
@@ -210,6 +218,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if mesh_smooth_iterations < 0:
         raise ValueError("--mesh-smooth-iterations must be >= 0")
     smooth = mesh_smooth_iterations > 0
+    repair = mesh_fill_holes is not None or bool(mesh_clean)
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
@@ -256,9 +265,21 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
     if mesh or ground_truth_surface or surfel_mesh_distance:
-        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if smooth or mesh_simplify_cell or decimate else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
+        m, origin, dims, report = fuse_and_mesh(slam.ba(), None if smooth or mesh_simplify_cell or decimate or repair else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
                                                 mesh_min_component)
-        surface, smoothed, simplified, decimated = {}, None, None, None
+        surface, smoothed, simplified, decimated, filled, cleaned = {}, None, None, None, None, []
+
+        def clean(before, after_what):
+            c = slam.ba().CleanMesh(before)
+            cleaned.append(dict(c["report"], after=after_what, vertices_before=len(before["positions"]), triangles_before=len(before["triangles"]),
+                                vertices=len(c["positions"]), triangles=len(c["triangles"])))
+            return c
+
+        if mesh_fill_holes is not None:
+            before = m
+            m = slam.ba().FillHoles(before, int(mesh_fill_holes))
+            filled = {"max_hole_edges": int(mesh_fill_holes), "filled_holes": int(m["filled_holes"]), "vertices_before": len(before["positions"]),
+                      "triangles_before": len(before["triangles"]), "vertices": len(m["positions"]), "triangles": len(m["triangles"])}
         if smooth:
             m = slam.ba().SmoothMesh(m, iterations=int(mesh_smooth_iterations), lambda_=float(mesh_smooth_lambda), mu=float(mesh_smooth_mu), boundary=mesh_smooth_boundary)
             smoothed = {"iterations": int(mesh_smooth_iterations), "lambda": float(mesh_smooth_lambda), "mu": float(mesh_smooth_mu), "boundary": mesh_smooth_boundary}
@@ -267,13 +288,23 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             m = slam.ba().SimplifyMesh(extracted, float(mesh_simplify_cell))
             simplified = {"cell": float(mesh_simplify_cell), "vertices_before": len(extracted["positions"]), "triangles_before": len(extracted["triangles"]),
                           "vertices": len(m["positions"]), "triangles": len(m["triangles"])}
+            if mesh_clean:
+                m = clean(m, "simplification")
         if decimate:
             before = m
             m = slam.ba().DecimateMesh(before, target_vertices=mesh_decimate_vertices, ratio=mesh_decimate_ratio)
             decimated = {"target_vertices": mesh_decimate_vertices, "ratio": mesh_decimate_ratio, "vertices_before": len(before["positions"]),
                          "triangles_before": len(before["triangles"]), "vertices": len(m["positions"]), "triangles": len(m["triangles"]), "rounds": int(m["rounds"])}
-        if mesh and (smooth or mesh_simplify_cell or decimate):
+            if mesh_clean:
+                m = clean(m, "decimation")
+        if mesh and (smooth or mesh_simplify_cell or decimate or repair):
             dba.SaveMeshAsPLY(mesh, m)
+        if repair:
+            surface["mesh_topology"] = slam.ba().MeshTopology(m)
+            if filled:
+                surface["mesh_hole_filling"] = filled
+            if cleaned:
+                surface["mesh_cleaning"] = cleaned
         if ground_truth_surface:
             surface["ground_truth"] = str(ground_truth_surface)
             start = None
@@ -311,6 +342,10 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             result["mesh"]["simplification"] = simplified
         if decimated:
             result["mesh"]["decimation"] = decimated
+        if filled:
+            result["mesh"]["hole_filling"] = filled
+        if cleaned:
+            result["mesh"]["cleaning"] = cleaned
     if inspect:
         inspect(slam, result)
     if trajectory:
@@ -349,6 +384,8 @@ def arg_parser():
     ap.add_argument("--mesh-simplify-cell", type=float, default=None)
     ap.add_argument("--mesh-decimate-ratio", type=float, default=None)
     ap.add_argument("--mesh-decimate-vertices", type=int, default=None)
+    ap.add_argument("--mesh-fill-holes", type=int, default=None)
+    ap.add_argument("--mesh-clean", action="store_true")
     ap.add_argument("--point-cloud", default=None)
     ap.add_argument("--ground-truth-surface", default=None)
     ap.add_argument("--surface-max-distance", type=float, default=0.1)
@@ -372,7 +409,7 @@ def main():
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
             mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
             mesh_smooth_iterations=a.mesh_smooth_iterations, mesh_smooth_lambda=a.mesh_smooth_lambda, mesh_smooth_mu=a.mesh_smooth_mu,
-            mesh_smooth_boundary=a.mesh_smooth_boundary)
+            mesh_smooth_boundary=a.mesh_smooth_boundary, mesh_fill_holes=a.mesh_fill_holes, mesh_clean=a.mesh_clean)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -410,6 +447,18 @@ def main():
         if "mesh_decimation" in sf and "mesh" not in r:
             dc = sf["mesh_decimation"]
             print(f"mesh decimated in {dc['rounds']} rounds: {dc['vertices_before']} vertices, {dc['triangles_before']} triangles -> {dc['vertices']}, {dc['triangles']}")
+        if "mesh_hole_filling" in sf:
+            fh = sf["mesh_hole_filling"]
+            print(f"{fh['filled_holes']} holes of at most {fh['max_hole_edges']} edges filled: {fh['vertices_before']} vertices, {fh['triangles_before']} triangles -> "
+                  f"{fh['vertices']}, {fh['triangles']}")
+        for cl in sf.get("mesh_cleaning", []):
+            print(f"mesh cleaned after the {cl['after']}: {cl['duplicate_triangles']} duplicate and {cl['degenerate_triangles']} degenerate triangles, "
+                  f"{cl['welded_vertices']} welded and {cl['unreferenced_vertices']} unreferenced vertices removed -> {cl['vertices']} vertices, {cl['triangles']} triangles")
+        if "mesh_topology" in sf:
+            tp = sf["mesh_topology"]
+            print(f"mesh topology: {tp['components']} components, {tp['unique_edges']} edges ({tp['boundary_edges']} boundary, {tp['nonmanifold_edges']} non-manifold, "
+                  f"{tp['inconsistent_edges']} inconsistently oriented), {tp['loops']} boundary loops (longest {tp['longest_loop']}), {tp['blocked_vertices']} blocked "
+                  f"vertices, Euler characteristic {tp['euler']}; closed: {tp['closed']}, oriented: {tp['oriented']}")
         if "registration" in sf:
             reg = sf["registration"]
             print(f"registration to the ground truth: {reg['reason']} after {reg['iterations']} steps; ground_truth_T_mesh =")

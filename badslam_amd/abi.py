@@ -75,6 +75,19 @@ class MeshReport(C.Structure):
         return {name: int(getattr(self, name)) for name in MESH_REPORT_FIELDS + ("euler",)}
 
 
+ORIENT_REPORT_FIELDS = ("patches", "orientable_patches", "nonorientable_patches", "closed_patches", "seams", "disagreeing_seams_before", "disagreeing_seams_after",
+                        "flipped_triangles", "inverted_patches", "fallback_patches")
+ORIENT_MODES = {"majority": 0, "normals": 1, "volume": 2}
+
+
+class OrientReport(C.Structure):
+    """bslam_orient_report: the counts of bslam_orient_mesh."""
+    _fields_ = [(name, C.c_uint32) for name in ORIENT_REPORT_FIELDS]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name in ORIENT_REPORT_FIELDS}
+
+
 class SE3f(C.Structure):
     _fields_ = [("q", C.c_float * 4), ("t", C.c_float * 3)]
 
@@ -159,6 +172,8 @@ SIGNATURES = {
     "bslam_fill_mesh_holes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32), P(C.c_uint32)]),
     "bslam_repair_stage_times": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "bslam_orient_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                    P(OrientReport)]),
     "bslam_point_mesh_distance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float,
                                             C.c_uint64, C.c_void_p, C.c_void_p, P(C.c_uint64), P(C.c_uint64)]),
     "bslam_sample_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,

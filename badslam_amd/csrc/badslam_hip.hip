@@ -29,6 +29,7 @@
 #include "decimate_kernels.hpp"
 #include "smooth_kernels.hpp"
 #include "repair_kernels.hpp"
+#include "orient_kernels.hpp"
 #include "raycast_kernels.hpp"
 #include "render_mesh_kernels.hpp"
 #include "place_kernels.hpp"
@@ -1464,6 +1465,7 @@ int bslam_debug_pose_residuals(
 #include "decimate_abi.inc"
 #include "smooth_abi.inc"
 #include "repair_abi.inc"
+#include "orient_abi.inc"
 #include "distance_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"

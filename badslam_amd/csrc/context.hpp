@@ -227,7 +227,9 @@ struct bslam_context {
                              // representatives, ranks, flags | per triangle: flags, ranks | scan sums | the radix sort's scratch; bslam_mesh_topology and
                              // bslam_fill_mesh_holes: words | per slot: keys, sorted keys, slots, head flags, ranks, run starts, boundary flags and numbers | per vertex:
                              // flags, boundary counts, first boundary slot | per boundary slot: two buffers of next, label and open, loop lengths, fans | scan sums |
-                             // the sort's scratch; reserved by the first of these calls
+                             // the sort's scratch; bslam_orient_mesh: both word blocks | per slot: keys, sorted keys, slots, head flags, ranks, run starts, seam codes |
+                             // referenced flags [V] | per triangle: links, patches, the sums at the root, flags | scan sums | the sort's scratch; reserved by the
+                             // first of these calls
   // those calls while profiling is on: a pair of events around each of up to eight stages and the last call's times (bslam_repair_stage_times)
   bslam::StageEvents<16> repair_events;
   float repair_stage_ms[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};

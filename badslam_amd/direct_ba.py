@@ -95,6 +95,7 @@ def host_lib():
     L.bsh_clean_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.POINTER(C.c_int), u64p]
     L.bsh_cleaned_copy.argtypes = [f32p, f32p, u8p, u32p, u32p, u32p]
     L.bsh_mesh_topology.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, u32p, C.POINTER(abi.MeshReport), u32p, u32p]
+    L.bsh_orient_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, u32p, C.c_int, u32p, u8p, u32p, C.POINTER(abi.OrientReport)]
     L.bsh_fill_mesh_holes.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, C.c_uint32, u64p]
     L.bsh_filled_copy.argtypes = [f32p, f32p, u8p, u32p]
     L.bsh_smooth_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, u32p, C.c_uint32, C.c_float, C.c_float, C.c_uint32]
@@ -963,6 +964,36 @@ class DirectBA:
                                            _u32(out["triangles"])))
         if col is not None and channels == 3:
             out["colors"] = np.ascontiguousarray(out["colors"][:, :3])
+        return out
+
+    # --- mesh orientation (bslam_orient_mesh)
+    def OrientMesh(self, mesh, mode="majority", recompute_normals=False, report=False):
+        """`mesh` (the dict of ExtractMesh or LoadPLY; triangles that repeat a vertex are refused: CleanMesh first) with one winding
+        per patch.  A patch is a set of triangles connected over edges that exactly two triangles use; where it can be oriented at all,
+        its triangles are flipped -- (a, b, c) becomes (a, c, b) -- until no such edge is run the same way twice, and `mode` picks the
+        side: "majority" keeps the winding most of its triangles have (the fewest flips; a tie keeps that of its first triangle),
+        "normals" the one the mesh's vertex normals vote for, "volume" the one that encloses a positive volume (closed patches; an
+        open one, and any vote that does not decide, falls back to "majority").  A patch that cannot be oriented (a Moebius band) stays
+        as it is.  -> the dict of ExtractMesh with new triangles -- positions, normals and colors are the input's -- plus flipped (T,)
+        bool, patch_of_triangle (T,) u32, the smallest triangle id of every triangle's patch, and, with report=True, report: a dict of
+        patches, orientable_patches, nonorientable_patches, closed_patches, seams, disagreeing_seams_before, disagreeing_seams_after,
+        flipped_triangles, inverted_patches and fallback_patches.  recompute_normals=True replaces the normals by MeshNormals of the
+        result."""
+        if mode not in abi.ORIENT_MODES:
+            raise ValueError("OrientMesh: mode must be 'majority', 'normals' or 'volume'")
+        pos, nrm, col, tri, channels = self._mesh_arrays(mesh, "OrientMesh")
+        if mode == "normals" and nrm is None:
+            raise ValueError("OrientMesh: the mode 'normals' needs a mesh with normals")
+        counts = abi.OrientReport()
+        out = dict(positions=pos.copy(), normals=None if nrm is None else nrm.copy(), colors=None if col is None else np.ascontiguousarray(col[:, :channels]),
+                   triangles=np.zeros((len(tri), 3), np.uint32), flipped=np.zeros(len(tri), np.uint8), patch_of_triangle=np.zeros(len(tri), np.uint32))
+        self._check(self.L.bsh_orient_mesh(self._ba, self.stream, len(pos), _f(pos), None if nrm is None else _f(nrm), len(tri), _u32(tri), abi.ORIENT_MODES[mode],
+                                           _u32(out["triangles"]), _u8(out["flipped"]), _u32(out["patch_of_triangle"]), C.byref(counts)))
+        out["flipped"] = out["flipped"].astype(bool)
+        if recompute_normals:
+            out["normals"] = self.MeshNormals(out)["normals"]
+        if report:
+            out["report"] = counts.as_dict()
         return out
 
     # --- surface evaluation (bslam_point_mesh_distance)

@@ -415,6 +415,22 @@ int bsh_mesh_topology(void* ba, void* stream, uint64_t vertices, uint64_t triang
     copy_out(loop_of_slot, loops);
   });
 }
+// DirectBA::OrientMesh of host arrays (normals may be null unless mode is 1): out_indices (3 * triangles entries), flipped and
+// patch_of_triangle (one entry per triangle, either may be null) and *report (a bslam_orient_report, may be null).
+int bsh_orient_mesh(void* ba, void* stream, uint64_t vertices, const float* positions, const float* normals, uint64_t triangles, const uint32_t* indices, int mode,
+                    uint32_t* out_indices, uint8_t* flipped, uint32_t* patch_of_triangle, void* report) {
+  BSH_TRY({
+    if (mode < 0 || mode > 2) throw std::invalid_argument("OrientMesh: mode must be 0 (majority), 1 (normals) or 2 (volume)");
+    const DirectBA::Mesh mesh = mesh_from(vertices, positions, normals, nullptr, triangles, indices);
+    std::vector<uint32_t> oriented, patches;
+    std::vector<uint8_t> flips;
+    static_cast<DirectBA*>(ba)->OrientMesh(static_cast<hipStream_t>(stream), mesh, static_cast<DirectBA::OrientMode>(mode), &oriented, flipped ? &flips : nullptr,
+                                           patch_of_triangle ? &patches : nullptr, static_cast<bslam_orient_report*>(report));
+    copy_out(out_indices, oriented);
+    copy_out(flipped, flips);
+    copy_out(patch_of_triangle, patches);
+  });
+}
 // DirectBA::FillMeshHoles of host arrays in the same two steps: bsh_fill_mesh_holes keeps the result for this thread and reports
 // counts3 = {vertices, triangles, holes filled}; bsh_filled_copy copies it out (any pointer may be null) and drops it.
 static thread_local DirectBA::Mesh g_filled;

@@ -1000,6 +1000,24 @@ u32 DirectBA::FillMeshHoles(hipStream_t stream, const Mesh& mesh, u32 max_hole_e
   return f.filled_holes;
 }
 
+void DirectBA::OrientMesh(hipStream_t stream, const Mesh& mesh, OrientMode mode, std::vector<u32>* indices, std::vector<u8>* flipped, std::vector<u32>* patch_of_triangle,
+                          bslam_orient_report* report) {
+  if (mode == kOrientNormals && mesh.normals.empty() && !mesh.positions.empty()) throw std::invalid_argument("OrientMesh: the mode 'normals' needs a mesh with normals");
+  const DeviceMesh m = UploadMesh(stream, mesh, "OrientMesh", kMeshPositions | kMeshIndices | (mode == kOrientNormals ? kMeshNormals : 0u));
+  DeviceArray<u32> oriented(size_t{3} * m.triangles), patches(patch_of_triangle ? m.triangles : 0);
+  DeviceArray<u8> flips(flipped ? m.triangles : 0);
+  bslam_orient_report counts;
+  Check(bslam_orient_mesh(ctx_, stream, m.vertices, m.triangles, AddressOf(m.positions), AddressOf(m.normals), AddressOf(m.indices), mode, oriented.address(),
+                          flipped ? flips.address() : nullptr, patch_of_triangle ? patches.address() : nullptr, &counts),
+        "bslam_orient_mesh");
+  if (report) *report = counts;
+  indices->resize(size_t{3} * m.triangles);
+  oriented.Download(stream, indices->data(), indices->size());
+  if (flipped) { flipped->resize(m.triangles); flips.Download(stream, flipped->data(), flipped->size()); }
+  if (patch_of_triangle) { patch_of_triangle->resize(m.triangles); patches.Download(stream, patch_of_triangle->data(), patch_of_triangle->size()); }
+  Wait(stream);
+}
+
 void DirectBA::RenderMesh(hipStream_t stream, const Mesh& mesh, const SE3f& global_T_camera, const PinholeCamera4f& camera, const MeshViewOptions& options,
                           ModelViews* views) {
   const int w = camera.width(), h = camera.height();

@@ -382,6 +382,14 @@ class DirectBA {
   // The same on device arrays; two calls, the first for the counts.  The result stays on the device.
   DeviceMesh FillMeshHolesOnDevice(hipStream_t stream, u32 vertices, u32 triangles, const float* positions, const float* normals, const uchar4_t* colors,
                                    const u32* indices, u32 max_hole_edges);
+  // Mesh orientation (bslam_orient_mesh): every orientable patch -- triangles joined over edges that two triangles use -- gets one
+  // winding, and `mode` says which: the one most of its triangles have, the one the vertex normals vote for (mesh.normals is needed),
+  // or the one with a positive enclosed volume (closed patches; others fall back to the majority).  A patch that cannot be oriented
+  // stays as it is.  *indices gets the triangles in their order, a flipped one (a, b, c) as (a, c, b); flipped (0 / 1) and
+  // patch_of_triangle (the smallest triangle id of the patch) have one entry per triangle and may be null, and so may report.
+  enum OrientMode : int { kOrientMajority = 0, kOrientNormals = 1, kOrientVolume = 2 };
+  void OrientMesh(hipStream_t stream, const Mesh& mesh, OrientMode mode, std::vector<u32>* indices, std::vector<u8>* flipped, std::vector<u32>* patch_of_triangle,
+                  bslam_orient_report* report);
   // Surface evaluation (bslam_point_mesh_distance): the distance of every point to the nearest triangle of a mesh within
   // max_distance, +infinity and triangle 0xffffffff beyond.  cell_size 0: the grid cell starts at max_distance and doubles while
   // the call reports that the grid exceeds max_grid_entries (or its cap on the cells); the result names the cell that was used.

@@ -948,6 +948,54 @@ int bslam_fill_mesh_holes(bslam_context* ctx, void* stream, uint32_t vertex_coun
  * tools/bench_mesh_repair.py. */
 int bslam_repair_stage_times(bslam_context* ctx, float* stage_ms8);
 
+/* Mesh orientation: one winding per connected piece, and a rule for which side is out (DESIGN.md 8 "Mesh orientation",
+ * csrc/orient_kernels.hpp).  Slots and edges are those of "Mesh repair"; the same triangles are refused (an index >= V, a repeated
+ * index, a position that is not finite).
+ *   Seams.  A seam is an edge with exactly two uses.  It disagrees iff its two slots start at the same vertex (the test that
+ *   inconsistent_edges of bslam_mesh_topology counts), else it agrees.
+ *   Patches.  Two triangles are joined iff they share a seam; edges with one use or with three or more join nothing.  A patch is a
+ *   connected component of the triangles under joins; its id is its smallest triangle id.  A patch is closed iff every slot of every
+ *   triangle of it lies on a seam.
+ *   flip0.  A patch is orientable iff bits f[t] exist with f[a] ^ f[b] = disagrees(seam) for every seam (a, b) of it; flip0 is the one
+ *   such assignment with flip0[patch id] = 0.  A patch that is not orientable (a Moebius band) is returned unchanged and counted.
+ *   Side.  flipped[t] = flip0[t] ^ invert[patch of t] in an orientable patch and 0 in any other.  A flipped triangle (a, b, c) is
+ *   written as (a, c, b); triangle order and vertices do not change.  invert by `mode`:
+ *     0, majority: invert = 1 iff more triangles of the patch have flip0 = 1 than flip0 = 0 (a tie: 0).  The fewest triangles change.
+ *     1, normals: a triangle (i0, i1, i2), with i1 and i2 exchanged where flip0 = 1, votes by the sign of
+ *       (cr.x n.x + cr.y n.y) + cr.z n.z,  cr = cross(p1 - p0, p2 - p0),  n = (n0 + n1) + n2  per component,
+ *       all in float64 from the fp32 inputs, cross(u, v) = (u.y v.z - u.z v.y, u.z v.x - u.x v.z, u.x v.y - u.y v.x), nothing contracted;
+ *       a NaN votes for neither side.  invert = 1 iff the negative votes outnumber the positive ones; equal counts, zero included,
+ *       fall back to majority.
+ *     2, volume: c = the componentwise minimum of all V positions, D = the largest of the three extents max - min, both taken as
+ *       float64; e = the frexp exponent of D (D = m 2^e, 0.5 <= m < 1), k = 58 - 3 e - bit_length(T).  A triangle, exchanged as above,
+ *       adds q = llrint(ldexp((a.x cr.x + a.y cr.y) + a.z cr.z, k)), a = p0 - c, cr = cross(p1 - c, p2 - c), rounded to nearest even;
+ *       |q| < 6 * 2^(58 - bit_length(T)), so the int64 sum over a patch is exact (|sum| < 2^61) and has no order.  invert = 1 iff it is
+ *       negative.  A patch that is not closed, a sum of zero and D = 0 fall back to majority.
+ *   Report.  patches = orientable_patches + nonorientable_patches; closed_patches of either kind; seams and those that disagree in the
+ *   input and in the output (the latter lie in the patches that are not orientable); flipped_triangles; inverted_patches and
+ *   fallback_patches count orientable patches only (fallback_patches is 0 in mode 0).
+ * bslam_orient_mesh: positions float[3 V], normals float[3 V] (read in mode 1 alone, may be null otherwise), indices and out_indices
+ * uint32[3 T], flipped uint8[T] and patch_of_triangle uint32[T] (either may be null) are device arrays; *report is written on the
+ * host.  V == 0 is legal with T == 0, and T == 0 gives a report of zeros.  Refused without a launch: null ctx or report, a mode other
+ * than 0, 1, 2, mode 1 without normals, more than 2^32 - 256 vertices or slots, a null array that has elements, misaligned (4 byte,
+ * flipped included) pointers, an output that overlaps an input or another output -- out_indices == indices too: the call is not in
+ * place.  Refused behind the key pass by a device error bit, before anything is written: the three refusals named above.  The census's
+ * key pass, stable sort, head flags, scan and run starts; then one launch with a lane per sorted slot that joins the two triangles of
+ * every seam in a lock-free union-find over uint32[T] words parent << 1 | parity (the smaller root wins; a hook is a compare-and-swap
+ * of the losing root's word; path halving stores (grandparent, p1 ^ p2) as one word); a second launch over the seams that marks a patch
+ * whose two triangles meet their root with the wrong parity; a launch per triangle that writes patch and flip0 and adds the counts and
+ * the votes at the root, summed within the wave first; one over the roots that decides; one that writes.  Patch ids, flip0 of
+ * orientable patches and the orientable flag do not depend on which thread won which swap.  Scratch is the slab of "Mesh repair"; the
+ * call synchronises `stream`.  While profiling is on, bslam_repair_stage_times gives {position check, bounds and keys, sort, runs,
+ * union-find, conflict pass, patches and votes, decision and indices, 0}. */
+typedef struct bslam_orient_report {
+  uint32_t patches, orientable_patches, nonorientable_patches, closed_patches, seams, disagreeing_seams_before, disagreeing_seams_after;
+  uint32_t flipped_triangles, inverted_patches, fallback_patches;
+} bslam_orient_report;
+int bslam_orient_mesh(bslam_context* ctx, void* stream, uint32_t vertex_count, uint32_t triangle_count, const float* positions,
+                      const float* normals, const uint32_t* indices, int mode, uint32_t* out_indices, uint8_t* flipped,
+                      uint32_t* patch_of_triangle, bslam_orient_report* report);
+
 /* Surface evaluation: the distance from each of N points to the nearest triangle of an indexed mesh, bounded by a search radius
  * (DESIGN.md 8 "Surface evaluation", csrc/distance_kernels.hpp).  All arithmetic is fp32 and nothing is contracted implicitly;
  * `/` and sqrtf are correctly rounded; dot(a, b) = fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x)) and cross has unfused components

@@ -68,6 +68,12 @@ as the outer rim of an open scan, stay.  --mesh-clean: duplicate and degenerate 
 off by default.  With either, the census of the mesh as written (DirectBA.MeshTopology: boundary, non-manifold and inconsistently
 oriented edges, boundary loops, Euler characteristic, components) is printed and reported as mesh_topology, with the counts before and
 after under mesh_hole_filling and mesh_cleaning.
+--mesh-orient {majority,normals,volume}: the mesh gets one winding per connected patch (DirectBA.OrientMesh) right behind the extraction
+and before --mesh-fill-holes, whose walk along a boundary a flipped triangle would stop: majority keeps the side most triangles of a
+patch face, normals the side the vertex normals vote for, volume the side that encloses a positive volume (closed patches; others fall
+back to majority); the normals are recomputed from the oriented triangles.  Off by default.  The counts (patches, those that cannot be
+oriented, seams that disagreed before and after, flipped triangles, inverted and fallback patches) are printed and reported as
+mesh_orientation, and mesh_topology is reported as with the other two.
 A volume of more than 2^30 samples is refused: choose a larger voxel size.  --point-cloud PATH: the surfel cloud
 (DirectBA.ExportToPointCloud) as a binary PLY with colours and normals.
 
@@ -208,7 +214,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
         surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
         mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
-        mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False):
+        mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False, mesh_orient=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
         raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
@@ -218,7 +224,9 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if mesh_smooth_iterations < 0:
         raise ValueError("--mesh-smooth-iterations must be >= 0")
     smooth = mesh_smooth_iterations > 0
-    repair = mesh_fill_holes is not None or bool(mesh_clean)
+    if mesh_orient is not None and mesh_orient not in abi.ORIENT_MODES:
+        raise ValueError("--mesh-orient must be majority, normals or volume")
+    repair = mesh_fill_holes is not None or bool(mesh_clean) or mesh_orient is not None
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
@@ -267,7 +275,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if mesh or ground_truth_surface or surfel_mesh_distance:
         m, origin, dims, report = fuse_and_mesh(slam.ba(), None if smooth or mesh_simplify_cell or decimate or repair else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
                                                 mesh_min_component)
-        surface, smoothed, simplified, decimated, filled, cleaned = {}, None, None, None, None, []
+        surface, smoothed, simplified, decimated, filled, cleaned, oriented = {}, None, None, None, None, [], None
 
         def clean(before, after_what):
             c = slam.ba().CleanMesh(before)
@@ -275,6 +283,10 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
                                 vertices=len(c["positions"]), triangles=len(c["triangles"])))
             return c
 
+        if mesh_orient is not None:
+            o = slam.ba().OrientMesh(m, mode=mesh_orient, recompute_normals=True, report=True)
+            oriented = dict(o["report"], mode=mesh_orient)
+            m = {k: o[k] for k in ("positions", "normals", "colors", "triangles")}
         if mesh_fill_holes is not None:
             before = m
             m = slam.ba().FillHoles(before, int(mesh_fill_holes))
@@ -301,6 +313,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             dba.SaveMeshAsPLY(mesh, m)
         if repair:
             surface["mesh_topology"] = slam.ba().MeshTopology(m)
+            if oriented:
+                surface["mesh_orientation"] = oriented
             if filled:
                 surface["mesh_hole_filling"] = filled
             if cleaned:
@@ -342,6 +356,8 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
             result["mesh"]["simplification"] = simplified
         if decimated:
             result["mesh"]["decimation"] = decimated
+        if oriented:
+            result["mesh"]["orientation"] = oriented
         if filled:
             result["mesh"]["hole_filling"] = filled
         if cleaned:
@@ -386,6 +402,7 @@ def arg_parser():
     ap.add_argument("--mesh-decimate-vertices", type=int, default=None)
     ap.add_argument("--mesh-fill-holes", type=int, default=None)
     ap.add_argument("--mesh-clean", action="store_true")
+    ap.add_argument("--mesh-orient", choices=tuple(abi.ORIENT_MODES), default=None)
     ap.add_argument("--point-cloud", default=None)
     ap.add_argument("--ground-truth-surface", default=None)
     ap.add_argument("--surface-max-distance", type=float, default=0.1)
@@ -409,7 +426,7 @@ def main():
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
             mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
             mesh_smooth_iterations=a.mesh_smooth_iterations, mesh_smooth_lambda=a.mesh_smooth_lambda, mesh_smooth_mu=a.mesh_smooth_mu,
-            mesh_smooth_boundary=a.mesh_smooth_boundary, mesh_fill_holes=a.mesh_fill_holes, mesh_clean=a.mesh_clean)
+            mesh_smooth_boundary=a.mesh_smooth_boundary, mesh_fill_holes=a.mesh_fill_holes, mesh_clean=a.mesh_clean, mesh_orient=a.mesh_orient)
     if "ba_cost" in r:
         print(f"BA objective before the final BA {r['ba_cost'][0]:.6e}, after {r['ba_cost'][1]:.6e} ({r['ba_cost'][2]} residual pairs)")
     print(f"{r['frames']} frames, {r['keyframes']} keyframes, {r['surfels']} surfels -> {r['poses_file']}")
@@ -447,6 +464,11 @@ def main():
         if "mesh_decimation" in sf and "mesh" not in r:
             dc = sf["mesh_decimation"]
             print(f"mesh decimated in {dc['rounds']} rounds: {dc['vertices_before']} vertices, {dc['triangles_before']} triangles -> {dc['vertices']}, {dc['triangles']}")
+        if "mesh_orientation" in sf:
+            mo = sf["mesh_orientation"]
+            print(f"mesh oriented by {mo['mode']}: {mo['patches']} patches ({mo['nonorientable_patches']} not orientable, {mo['closed_patches']} closed), "
+                  f"{mo['disagreeing_seams_before']} of {mo['seams']} seams disagreed, {mo['disagreeing_seams_after']} do; {mo['flipped_triangles']} triangles flipped, "
+                  f"{mo['inverted_patches']} patches inverted, {mo['fallback_patches']} by the majority for want of a vote")
         if "mesh_hole_filling" in sf:
             fh = sf["mesh_hole_filling"]
             print(f"{fh['filled_holes']} holes of at most {fh['max_hole_edges']} edges filled: {fh['vertices_before']} vertices, {fh['triangles_before']} triangles -> "

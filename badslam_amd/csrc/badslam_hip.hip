@@ -23,6 +23,7 @@
 #include "fusion_kernels.hpp"
 #include "mesh_kernels.hpp"
 #include "distance_kernels.hpp"
+#include "bvh_kernels.hpp"
 #include "registration_kernels.hpp"
 #include "sampling_kernels.hpp"
 #include "simplify_kernels.hpp"
@@ -1467,6 +1468,7 @@ int bslam_debug_pose_residuals(
 #include "repair_abi.inc"
 #include "orient_abi.inc"
 #include "distance_abi.inc"
+#include "bvh_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"
 #include "raycast_abi.inc"

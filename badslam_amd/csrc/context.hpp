@@ -203,6 +203,13 @@ struct bslam_context {
     uint32_t cells = 0, valid = 0, triangles = 0;
     void *records = nullptr, *cell_count = nullptr, *cell_start = nullptr, *list = nullptr;
   } prepared;
+  bslam::Slab bvh;           // bslam_nearest_triangle: words | keys, sorted keys u64[T] | ids, sorted ids u32[T] | per node: parents, children, box keys |
+                             // per leaf: boxes | packed nodes | leaf records | the radix sort's scratch; reserved by its first call
+  struct BvhTree {           // the tree of the last call (bslam_debug_nearest_triangle_tree); the pointers lie inside that slab
+    uint32_t leaves = 0, height = 0;
+    void *words = nullptr, *sorted_ids = nullptr, *parent_internal = nullptr, *parent_leaf = nullptr, *box_min = nullptr, *box_max = nullptr;
+    void *leaf_lo = nullptr, *leaf_hi = nullptr, *nodes = nullptr, *records = nullptr;
+  } bvh_tree;
   bslam::Slab sampling;      // bslam_sample_mesh: words | counts u32[T] | offsets u32[T] | scan sums; reserved by its first call
   bslam::Slab simplify;      // bslam_simplify_mesh: words | keys, sorted keys u64[V] | ids, sorted ids, head flags, ranks, clusters [V] | keep flags, ranks [T] |
                              // scan sums | the radix sort's scratch; reserved by its first call

@@ -86,6 +86,7 @@ def host_lib():
     u64p = C.POINTER(C.c_uint64)
     L.bsh_point_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_float, C.c_uint64, f32p, u32p,
                                           f32p, u64p]
+    L.bsh_nearest_triangle.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, f32p, u32p, u32p]
     L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
     L.bsh_distance_copy.argtypes = [f32p, u32p]
     L.bsh_simplify_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, f32p, C.c_float, u64p]
@@ -1019,6 +1020,24 @@ class DirectBA:
                                                    0.0 if cell_size is None else float(cell_size), int(max_grid_entries), _f(distance), _u32(triangle),
                                                    C.byref(cell), grid))
         return self._distance_result(distance, triangle, cell, grid)
+
+    def NearestTriangle(self, points, mesh, max_distance=None):
+        """Distance of every point (n, 3) to the nearest triangle of `mesh` through a bounding-volume hierarchy
+        (bslam_nearest_triangle): any max_distance > 0, None for no radius at all -- every point then hits a mesh that has a valid
+        triangle.  dict of distance (n,) f32 (+inf beyond max_distance), triangle (n,) u32 (0xFFFFFFFF there), leaves (the
+        triangles with finite coordinates) and height (of the tree).  mesh: as in PointMeshDistance; without triangles every
+        vertex is the triangle (i, i, i)."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        if tri is None or len(tri) == 0:
+            tri = np.repeat(np.arange(len(pos), dtype=np.uint32)[:, None], 3, axis=1)
+        tri = np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        distance, triangle = np.zeros(len(pts), np.float32), np.zeros(len(pts), np.uint32)
+        tree = (C.c_uint32 * 2)()
+        self._check(self.L.bsh_nearest_triangle(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), _u32(tri),
+                                                float("inf") if max_distance is None else float(max_distance), _f(distance), _u32(triangle), tree))
+        return dict(distance=distance, triangle=triangle, leaves=int(tree[0]), height=int(tree[1]))
 
     def SurfelMeshDistance(self, max_distance, cell_size=None, max_grid_entries=1 << 28):
         """PointMeshDistance of the centres of the valid surfels (the positions of ExportToPointCloud, in its order) against the mesh

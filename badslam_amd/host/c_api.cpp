@@ -518,6 +518,20 @@ int bsh_point_mesh_distance(void* ba, void* stream, uint64_t point_count, const 
     grid_out(result, cell_used, grid2);
   });
 }
+// DirectBA::NearestTriangle of host arrays shaped as above; max_distance may be +infinity; tree2 = {leaves, height}.
+int bsh_nearest_triangle(void* ba, void* stream, uint64_t point_count, const float* points, uint64_t vertices, const float* positions, uint64_t triangles,
+                         const uint32_t* indices, float max_distance, float* distance, uint32_t* triangle, uint32_t* tree2) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::NearestTriangleResult result;
+    static_cast<DirectBA*>(ba)->NearestTriangle(static_cast<hipStream_t>(stream), points, point_count, mesh, max_distance, &result);
+    copy_out(distance, result.distance);
+    copy_out(triangle, result.triangle);
+    if (tree2) { tree2[0] = result.leaves; tree2[1] = result.height; }
+  });
+}
 // DirectBA::SurfelMeshDistance in two steps, like the mesh: the call keeps its result for this thread and reports *count (the
 // valid surfels), *cell_used and grid2; bsh_distance_copy copies distance and triangle out (`count` entries each) and drops it.
 static thread_local DirectBA::PointMeshResult g_distance;

@@ -687,6 +687,24 @@ void DirectBA::PointMeshDistance(hipStream_t stream, const float* points, size_t
   PointMeshDistanceOnDevice(stream, point_count, dev_points.address(), m.vertices, m.positions->address(), m.triangles, m.indices->address(), options, result);
 }
 
+void DirectBA::NearestTriangle(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, float max_distance, NearestTriangleResult* result) {
+  CheckMeshSizes(mesh, "NearestTriangle", kMeshPositions | kMeshIndices, point_count);
+  if (point_count > 0x7fffffffull) throw std::invalid_argument("NearestTriangle: too many points for one device image");
+  const u32 n = static_cast<u32>(point_count);
+  DeviceArray<float> dev_points(3 * point_count);
+  dev_points.Upload(stream, points, 3 * point_count);
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshIndices);   // its wait covers the points
+  result->distance.assign(n, 0.f);
+  result->triangle.assign(n, 0u);
+  DeviceArray<float> distance(n);
+  DeviceArray<u32> triangle(n);
+  Check(bslam_nearest_triangle(ctx_, stream, n, dev_points.address(), m.vertices, m.positions->address(), m.triangles, m.indices->address(), max_distance,
+                               distance.address(), triangle.address(), &result->leaves, &result->height), "bslam_nearest_triangle");
+  distance.Download(stream, result->distance.data(), n);
+  triangle.Download(stream, result->triangle.data(), n);
+  Wait(stream);
+}
+
 std::vector<float> DirectBA::ValidSurfelCentres(hipStream_t stream) const {
   std::vector<float> centres;
   const size_t n = surfels_size_;

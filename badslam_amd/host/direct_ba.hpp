@@ -410,6 +410,14 @@ class DirectBA {
   // The same on device arrays (4 byte aligned; see bslam_point_mesh_distance); the results are downloaded.
   void PointMeshDistanceOnDevice(hipStream_t stream, size_t point_count, const float* points, u32 vertices, const float* positions, u32 triangles,
                                  const u32* indices, const PointMeshOptions& options, PointMeshResult* result);
+  // Nearest triangle (bslam_nearest_triangle): the same distance through a bounding-volume hierarchy, for any max_distance > 0,
+  // +infinity included: no radius, every point hits a mesh that has a valid triangle.  leaves: the valid triangles; height: of the tree.
+  struct NearestTriangleResult {
+    std::vector<float> distance;
+    std::vector<u32> triangle;
+    u32 leaves = 0, height = 0;
+  };
+  void NearestTriangle(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, float max_distance, NearestTriangleResult* result);
   // The centres of the valid surfels (the points of ExportToPointCloud, in its order) against the mesh the last ExtractMesh
   // returned, which stays on the device for this: how far the surfels that bundle adjustment optimised lie from the surface the
   // volume produced -- a consistency figure that needs no ground truth.  Throws std::logic_error if no mesh was extracted.

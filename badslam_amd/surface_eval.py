@@ -21,7 +21,11 @@ The ground truth has to be given in the frame of the reconstruction, or evaluate
 needs a start within its search radius, for example the transform ate.align_rigid finds for the trajectory).  A ground truth without triangles is a point cloud (the form the
 ETH3D SLAM scans come in): every point then is its own degenerate triangle.
 
-distance_summary is pure NumPy; evaluate needs a DirectBA for the distance calls.
+evaluate(max_distance=None) measures without a search radius (DirectBA.NearestTriangle, bslam_nearest_triangle: a bounding-volume
+hierarchy in place of the grid), and deviation() uses the same call to say how far a mesh operator moved a surface: mean, rmse and
+maximum from a mesh to its reference and back, and the Hausdorff distance.
+
+distance_summary is pure NumPy; evaluate and deviation need a DirectBA for the distance calls.
 """
 import numpy as np
 
@@ -71,6 +75,9 @@ def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.0
     ground truth may be a point cloud (no or empty triangles).  -> dict of accuracy and completeness (distance_summary each),
     f_scores (a list per threshold), max_distance and the grids the two calls used.  Both are measured at the vertices unless
     sample_density is given: see the module's docstring.
+    max_distance None: no search radius.  Both directions run through DirectBA.NearestTriangle (a bounding-volume hierarchy, no grid):
+    every point hits, `beyond` is 0, the result has max_distance None and, in place of the grids, accuracy_tree and completeness_tree
+    (leaves, height).  cell_size is not used then.
     sample_density: each side that has triangles is replaced as a query point set by DirectBA.SampleMesh(side, density=sample_density,
     seed=sample_seed); the result then also has `sampling`: density, seed, reconstruction_samples and ground_truth_samples (the
     numbers of samples; None for a side without triangles, which keeps its vertices).
@@ -81,6 +88,8 @@ def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.0
     `before`, the accuracy and completeness summaries under `initial` alone.  The registration itself runs on the reconstruction's
     vertices; the sampling arguments apply to the evaluations before and after it."""
     sampled = {} if sample_density is None else dict(sample_density=sample_density, sample_seed=sample_seed)
+    if register and max_distance is None:
+        raise ValueError("evaluate: register=True needs a finite max_distance (the registration's search radius)")
     if register:
         start = np.eye(4) if initial is None else np.asarray(initial, np.float64).reshape(4, 4)
         before = evaluate(ba, dict(reconstruction, positions=transform_positions(reconstruction["positions"], start)), ground_truth, max_distance, thresholds, cell_size,
@@ -100,14 +109,52 @@ def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.0
         else:
             queries.append(side["positions"])
             counts.append(None)
-    acc = ba.PointMeshDistance(queries[0], ground_truth, max_distance, cell_size)
-    com = ba.PointMeshDistance(queries[1], reconstruction, max_distance, cell_size)
-    accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
-    grid = lambda r: dict(cell_size=r["cell_size"], grid_cells=r["grid_cells"], grid_entries=r["grid_entries"])
-    result = dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
-                  accuracy_grid=grid(acc), completeness_grid=grid(com))
+    if max_distance is None:   # no radius: the tree, and every point of a side hits whatever the other side holds
+        acc = ba.NearestTriangle(queries[0], ground_truth)
+        com = ba.NearestTriangle(queries[1], reconstruction)
+        accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
+        tree = lambda r: dict(leaves=r["leaves"], height=r["height"])
+        result = dict(max_distance=None, accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
+                      accuracy_tree=tree(acc), completeness_tree=tree(com))
+    else:
+        acc = ba.PointMeshDistance(queries[0], ground_truth, max_distance, cell_size)
+        com = ba.PointMeshDistance(queries[1], reconstruction, max_distance, cell_size)
+        accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
+        grid = lambda r: dict(cell_size=r["cell_size"], grid_cells=r["grid_cells"], grid_entries=r["grid_entries"])
+        result = dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
+                      accuracy_grid=grid(acc), completeness_grid=grid(com))
     if sample_density is not None:
         result["sampling"] = dict(density=float(sample_density), seed=int(sample_seed), reconstruction_samples=counts[0], ground_truth_samples=counts[1])
+    return result
+
+
+def _deviation_side(distance):
+    d = np.asarray(distance, np.float64).reshape(-1)
+    d = d[np.isfinite(d)]
+    nan = float("nan")
+    return dict(count=int(len(d)), mean=float(d.mean()) if len(d) else nan, rmse=float(np.sqrt(np.mean(d * d))) if len(d) else nan,
+                max=float(d.max()) if len(d) else nan)
+
+
+def deviation(ba, mesh, reference, sample_density=None, sample_seed=0):
+    """How far a mesh operator (SimplifyMesh, DecimateMesh, SmoothMesh, FillHoles ...) moved a surface: the distances from `mesh` to
+    `reference` and back, without a search radius (DirectBA.NearestTriangle), so that the points that moved most count in full.
+    Measured at the vertices, or -- sample_density given -- at DirectBA.SampleMesh samples of each side that has triangles.
+    -> dict of mesh_to_reference and reference_to_mesh (count, mean, rmse, max each), hausdorff (the larger of the two maxima) and,
+    with sample_density, sampling: density, seed, mesh_samples and reference_samples (None for a side without triangles).  A side without a point, or a target without a valid triangle, gives nan."""
+    queries, counts = [], []
+    for side in (mesh, reference):
+        if sample_density is not None and _has_triangles(side):
+            queries.append(ba.SampleMesh(side, density=sample_density, seed=sample_seed)["positions"])
+            counts.append(int(len(queries[-1])))
+        else:
+            queries.append(side["positions"])
+            counts.append(None)
+    forth = _deviation_side(ba.NearestTriangle(queries[0], reference)["distance"])
+    back = _deviation_side(ba.NearestTriangle(queries[1], mesh)["distance"])
+    result = dict(mesh_to_reference=forth, reference_to_mesh=back, hausdorff=float(np.fmax(forth["max"], back["max"])))
+    if sample_density is not None:
+        result["sampling"] = dict(density=float(sample_density), seed=int(sample_seed), mesh_samples=counts[0], reference_samples=counts[1])
     return result
 
 

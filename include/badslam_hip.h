@@ -1041,6 +1041,55 @@ int bslam_point_mesh_distance(bslam_context* ctx, void* stream, uint32_t point_c
                               float cell_size, uint64_t max_grid_entries, float* out_distance, uint32_t* out_triangle,
                               uint64_t* grid_cells, uint64_t* grid_entries);
 
+/* Nearest triangle: the distance from each of N points to the nearest triangle of an indexed mesh with any search radius,
+ * including none (DESIGN.md 8 "Nearest triangle", csrc/bvh_kernels.hpp): a bounding-volume hierarchy over the triangles in place
+ * of the grid, at a cost that does not depend on the radius.  Arithmetic, dot, cross, `/` and sqrtf are those of "Surface
+ * evaluation".  Point p, triangle t with vertices a, b, c = positions[indices[3 t + 0 .. 2]], R = max_distance.
+ * Validity:
+ *   An index >= vertex_count is never dereferenced: BSLAM_ERR_INVALID_ARGUMENT, outputs untouched.  A triangle with a coordinate
+ *   that is not finite is not part of the mesh for this call.  A point with a coordinate that is not finite is a miss.
+ * Box:
+ *   box(t) = (lo, hi), the component-wise fp32 minimum and maximum of a, b, c.
+ * Box distance:
+ *   on each axis e.a = max(lo.a - p.a, p.a - hi.a, 0) (two fp32 subtractions);  b2(p, box) = fmaf(e.z, e.z, fmaf(e.y, e.y, e.x * e.x)),
+ *   the nesting of dot.
+ * Pair:
+ *   d2(p, t) = max(pair(p, t), b2(p, box(t))), where pair is d2 of "Surface evaluation": three segments and the face term, a NaN
+ *   is no value (+infinity when nothing is a value).
+ * Result:
+ *   best = the smallest d2 over the valid triangles, triangle = the smallest t that attains it.  The point hits iff best is finite
+ *   and best <= fl(R * R); R = +INFINITY is legal and means no radius.  On a hit distance = sqrtf(best); else distance =
+ *   +INFINITY and triangle = 0xffffffff.
+ * Why the clamp by b2: the true distance to a triangle is never below the distance to its box, so the clamp only raises values
+ *   that rounding made too small -- and it makes pruning exact.  fp32 subtraction, max, the product of two non-negative numbers
+ *   and fmaf with non-negative addends are monotone under round-to-nearest; so for boxes A inside B, b2(p, B) <= b2(p, A) as
+ *   floats; so b2(p, box of a node) <= b2(p, box(t)) <= d2(p, t) for every triangle t below the node.  The traversal skips a
+ *   subtree if and only if b2(p, box of its node) > min(best so far, fl(R * R)), and enters it on equality, where a lower index
+ *   may tie: nothing that could be the result is ever skipped.  The result therefore depends on the rule alone -- not on the
+ *   shape of the tree, the width of the Morton code, the order of the traversal or the order in which atomics arrive -- and two
+ *   calls give identical bits.  Where no clamp is active at a minimum (the usual case) the result equals that of
+ *   bslam_point_mesh_distance at the same R bit for bit.
+ * bslam_nearest_triangle: arrays, alignment, overlap rules and the caps of 2^32 - 256 points or triangles as in
+ * bslam_point_mesh_distance.  Refused without a launch: a null context or out_distance, a max_distance that is not > 0 (a NaN
+ * included).  Refused behind the census: more than 2^31 valid triangles (a child reference keeps one bit for the leaf flag).
+ * N == 0 and T == 0 are legal; with T == 0, or without a valid triangle, every point misses.  *leaves (host, may be null)
+ * receives the number of valid triangles, the leaves of the tree, and *height (host, may be null) the number of edges from the
+ * root to the deepest leaf, at most 62 (30 key bits + 32 index bits: the bound the traversal stack is sized from); 0 for a
+ * single leaf.  Scratch and the tree live in a context slab that grows on demand and is released by bslam_destroy.  While
+ * profiling is on, bslam_debug_cull_stats counts the nodes the query fetched as `tested` and the triangles it evaluated as
+ * tested - culled (modulo 2^64).  Synchronises `stream`.
+ * bslam_debug_nearest_triangle_tree copies the tree of the last bslam_nearest_triangle call of the context to the host, for tests:
+ * *leaves = L, its leaves (0: there is none, nothing else is written).  If L > leaf_capacity nothing else is written either.
+ * Node 0 .. L - 2 are the internal nodes and node 0 is the root; node L - 1 + j is leaf j (with L == 1 node 0 is that leaf).
+ * parent uint32[2 L - 1] (0xffffffff for the root), children uint32[2 (L - 1)] (the two children of internal node i at 2 i and
+ * 2 i + 1), boxes float[6 (2 L - 1)] (lo.xyz, hi.xyz per node) and leaf_triangle uint32[L] are host arrays.  Children and the
+ * boxes of all nodes but the root are read from the nodes as the query fetches them.  Synchronises the device. */
+int bslam_nearest_triangle(bslam_context* ctx, void* stream, uint32_t point_count, const float* points, uint32_t vertex_count,
+                           const float* positions, uint32_t triangle_count, const uint32_t* indices, float max_distance,
+                           float* out_distance, uint32_t* out_triangle, uint32_t* leaves, uint32_t* height);
+int bslam_debug_nearest_triangle_tree(bslam_context* ctx, uint32_t leaf_capacity, uint32_t* parent, uint32_t* children, float* boxes,
+                                      uint32_t* leaf_triangle, uint32_t* leaves);
+
 /* Surface sampling: points drawn uniformly by area from an indexed mesh, so that what is measured at them does not depend on how
  * the mesh happens to be tessellated (DESIGN.md 8 "Surface sampling", csrc/sampling_kernels.hpp).  Integers are uint32 with
  * wrap-around; floats are fp32, nothing is contracted implicitly, and dot, cross, `/` and sqrtf are those of "Surface evaluation"

@@ -16,6 +16,7 @@ has a ground truth, prints the ATE RMSE.
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
                             [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
+                            [--mesh-deviation]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
 sees it and its camera is scaled to match (level 1 runs a 640x480 dataset at 320x240).  --median-filter-and-densify-iterations:
@@ -89,6 +90,11 @@ the transform and the figures before it are printed and reported with the rest.
 --surface-sample-spacing S: both figures are measured at points drawn uniformly by area, one per S x S metres on average, from each
 side that has triangles (DirectBA.SampleMesh; surface_eval.evaluate(sample_density=1 / S^2)) instead of at the vertices, so that they
 no longer depend on how either mesh is tessellated; the numbers of samples are printed and reported.
+--surface-max-distance inf: no search radius.  Both directions then run through a bounding-volume hierarchy (DirectBA.NearestTriangle;
+surface_eval.evaluate(max_distance=None)), every point hits and nothing is `beyond`; --register-surface needs a finite radius.
+--mesh-deviation: how far the --mesh-* operators moved the surface -- the mesh as written against the mesh as extracted, both ways and
+without a radius (surface_eval.deviation: mean, rmse and max per direction, the Hausdorff distance, and the operators that ran); at
+the vertices, or at samples when --surface-sample-spacing is given.
 --surface-report FILE.json: what was printed, as JSON.  Either option fuses with the --mesh-* options whether or not --mesh is given.
 """
 import argparse
@@ -213,7 +219,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         place_recognition=False, place_min_gap=10, mesh=None, mesh_voxel_size=0.01, mesh_truncation=None, mesh_min_count=1, point_cloud=None,
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
         surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
-        mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
+        mesh_deviation=False, mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
         mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False, mesh_orient=None):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
@@ -227,6 +233,11 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
     if mesh_orient is not None and mesh_orient not in abi.ORIENT_MODES:
         raise ValueError("--mesh-orient must be majority, normals or volume")
     repair = mesh_fill_holes is not None or bool(mesh_clean) or mesh_orient is not None
+    if not surface_max_distance > 0:
+        raise ValueError("--surface-max-distance must be > 0 (inf: no search radius)")
+    radius = None if np.isinf(surface_max_distance) else float(surface_max_distance)      # None: the tree of DirectBA.NearestTriangle, no grid
+    if register_surface and radius is None:
+        raise ValueError("--register-surface needs a finite --surface-max-distance: it is the registration's search radius")
     ds = dba.read_tum_dataset(dataset_dir, trajectory or "")
     frames = ds["frames"] if end_frame is None else ds["frames"][:end_frame]
     check_level_fits(ds["width"], ds["height"], pyramid_level_for_color)
@@ -272,10 +283,11 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         positions, colors, normals = slam.ba().ExportToPointCloud()
         dba.SavePointCloudAsPLY(point_cloud, positions, colors, normals)
         result["point_cloud"] = (str(point_cloud), len(positions))
-    if mesh or ground_truth_surface or surfel_mesh_distance:
+    if mesh or ground_truth_surface or surfel_mesh_distance or mesh_deviation:
         m, origin, dims, report = fuse_and_mesh(slam.ba(), None if smooth or mesh_simplify_cell or decimate or repair else mesh, mesh_voxel_size, mesh_truncation, mesh_min_count, fused,
                                                 mesh_min_component)
         surface, smoothed, simplified, decimated, filled, cleaned, oriented = {}, None, None, None, None, [], None
+        as_extracted = m
 
         def clean(before, after_what):
             c = slam.ba().CleanMesh(before)
@@ -326,13 +338,23 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
                 aligned = ate.ate_files(os.path.join(str(dataset_dir), trajectory), out)
                 start = np.eye(4)
                 start[:3, :3], start[:3, 3] = aligned["R"], aligned["t"]
-            surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), surface_max_distance, tuple(surface_thresholds),
+            surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), radius, tuple(surface_thresholds),
                                                  register=bool(register_surface), initial=start,
                                                  sample_density=None if surface_sample_spacing is None else 1.0 / (float(surface_sample_spacing) ** 2)))
         if surfel_mesh_distance:
-            surface["surfel_mesh_distance"] = surface_eval.distance_summary(slam.ba().SurfelMeshDistance(surface_max_distance)["distance"], tuple(surface_thresholds))
+            if radius is None:      # the centres of ExportToPointCloud, in its order, against the mesh as extracted
+                centre_distance = slam.ba().NearestTriangle(slam.ba().ExportToPointCloud()[0], as_extracted)["distance"]
+            else:
+                centre_distance = slam.ba().SurfelMeshDistance(radius)["distance"]
+            surface["surfel_mesh_distance"] = surface_eval.distance_summary(centre_distance, tuple(surface_thresholds))
+        if mesh_deviation:
+            operators = ([f"orient ({mesh_orient})"] if oriented else []) + (["fill holes"] if filled else []) + (["smooth"] if smoothed else []) + \
+                        (["simplify"] if simplified else []) + (["decimate"] if decimated else []) + (["clean"] if cleaned else [])
+            surface["mesh_deviation"] = dict(surface_eval.deviation(slam.ba(), m, as_extracted,
+                                                                    sample_density=None if surface_sample_spacing is None else 1.0 / (float(surface_sample_spacing) ** 2)),
+                                             operators=operators)
         if surface:
-            surface["max_distance"] = float(surface_max_distance)
+            surface["max_distance"] = radius
             if smoothed:
                 surface["mesh_smoothing"] = smoothed
             if simplified:
@@ -405,7 +427,8 @@ def arg_parser():
     ap.add_argument("--mesh-orient", choices=tuple(abi.ORIENT_MODES), default=None)
     ap.add_argument("--point-cloud", default=None)
     ap.add_argument("--ground-truth-surface", default=None)
-    ap.add_argument("--surface-max-distance", type=float, default=0.1)
+    ap.add_argument("--surface-max-distance", type=float, default=0.1)      # "inf": no search radius
+    ap.add_argument("--mesh-deviation", action="store_true")
     ap.add_argument("--surface-thresholds", type=lambda text: tuple(float(v) for v in text.split(",")), default=(0.01, 0.02, 0.05))
     ap.add_argument("--surfel-mesh-distance", action="store_true")
     ap.add_argument("--surface-report", default=None)
@@ -424,7 +447,7 @@ def main():
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
-            mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
+            mesh_deviation=a.mesh_deviation, mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
             mesh_smooth_iterations=a.mesh_smooth_iterations, mesh_smooth_lambda=a.mesh_smooth_lambda, mesh_smooth_mu=a.mesh_smooth_mu,
             mesh_smooth_boundary=a.mesh_smooth_boundary, mesh_fill_holes=a.mesh_fill_holes, mesh_clean=a.mesh_clean, mesh_orient=a.mesh_orient)
     if "ba_cost" in r:
@@ -493,12 +516,18 @@ def main():
             at = lambda n: "its vertices" if n is None else f"{n} samples"
             print(f"measured at {sm['density']:g} samples per square metre: the mesh at {at(sm['reconstruction_samples'])}, the ground truth at {at(sm['ground_truth_samples'])}")
         if "accuracy" in sf:
-            print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, within {sf['max_distance']:g} m)", sf["accuracy"]))
+            within = "no search radius" if sf["max_distance"] is None else f"within {sf['max_distance']:g} m"
+            print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, {within})", sf["accuracy"]))
             print(surface_eval.format_summary("completeness (ground truth -> mesh)", sf["completeness"]))
             for row in sf["f_scores"]:
                 print(f"  at {row['threshold']:g} m: precision {row['precision']:.4f}, recall {row['recall']:.4f}, F-score {row['f_score']:.4f}")
         if "surfel_mesh_distance" in sf:
             print(surface_eval.format_summary("surfel centres -> mesh", sf["surfel_mesh_distance"]))
+        if "mesh_deviation" in sf:
+            dv = sf["mesh_deviation"]
+            side = lambda s: f"mean {s['mean']:.5f}, rmse {s['rmse']:.5f}, max {s['max']:.5f} m over {s['count']} points"
+            print(f"mesh as written against the mesh as extracted (operators: {', '.join(dv['operators']) or 'none'}): written -> extracted {side(dv['mesh_to_reference'])}; "
+                  f"extracted -> written {side(dv['reference_to_mesh'])}; Hausdorff {dv['hausdorff']:.5f} m")
     if "ate" in r:
         print(f"ATE RMSE {r['ate']['rmse']:.6f} m over {r['ate']['pairs']} poses")
 

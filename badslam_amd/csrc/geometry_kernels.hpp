@@ -91,6 +91,12 @@ __global__ __launch_bounds__(256) void permute_surfel_rows_kernel(const uint32_t
 // the first associated active keyframe -- and the number of surfels set active to this block's two slots of `counters`
 // (counters[2 * blockIdx.x + {0, 1}]; no atomics: a single contended address would serialise 1e4..1e5 waves): what bench.py
 // credits this pass with.
+// One departure from the reference: it associates with SurfelProjectsToAssociatedPixel, whose `z <= 0` test a NaN position (a
+// merged or deleted surfel not yet compacted away) passes, so that such a surfel lands on pixel (0, 0) and may be set active;
+// project_and_associate refuses a NaN position, and the surfel stays inactive here.  That is safe only while every reader of
+// the flag refuses NaN positions as well (all BA kernels do, through project_with<false>) and compaction drops the surfel; a
+// reader that does not must not rely on this byte.  Pinned by tests/test_gpu_lifecycle_reference.py (the kernel) and
+// tests/test_lifecycle_cpu.py (the oracle, which follows the reference).
 template <bool kCount>
 __global__ __launch_bounds__(256) void activation_kernel(CamConsts c, const KfDev* __restrict__ kfs, int kf_count, Schedule sc, SurfelRowsRW s,
                                                          unsigned long long* __restrict__ counters) {

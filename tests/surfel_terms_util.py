@@ -519,9 +519,12 @@ class HardFixture:
 
 
 @functools.lru_cache(maxsize=None)
-def hard_fixture(case):
+def hard_fixture(case, size=DEPTH_SIZE, cell=CELL, n_surfels=N_SURFELS):
+    """size, cell, n_surfels: the variants of tests/lifecycle_util.py (another image size, cell size and surfel count over the same
+    scene, poses and groups); the defaults are the fixture every other module uses."""
     (cw, ch), color_cam, a, vary_cfactor = CASES[case]
-    w, h = DEPTH_SIZE
+    w, h = size
+    CELL, N_SURFELS = cell, n_surfels
     fx, fy, cx, cy = DEPTH_CAMERA
     fix = HardFixture()
     fix.case, fix.a = case, a
@@ -549,7 +552,10 @@ def hard_fixture(case):
         s = w / cw
         luma = np.clip(_luma(s * (cxs + 0.5), s * (cys + 0.5), 0.4 * k) + 0.5, 0, 255).astype(np.uint8)
         rgba = np.stack([np.full_like(luma, 0x55), 255 - luma, np.full_like(luma, 0xaa), luma], -1)
-        fix.keyframes.append({"depth": raw, "normals": encode_normal(normal).astype(np.uint16), "luma": luma, "rgba": np.ascontiguousarray(rgba)})
+        # squared point radii as half-float bits, another number at every pixel of every keyframe (the lifecycle reads them)
+        radius = 0.010 + 0.012 * _frac(0.37 * xs + 0.61 * ys + 0.29 * k)
+        fix.keyframes.append({"depth": raw, "normals": encode_normal(normal).astype(np.uint16), "luma": luma, "rgba": np.ascontiguousarray(rgba),
+                              "radius": (radius * radius).astype(np.float16).view(np.uint16)})
 
     i = np.arange(N_SURFELS)
     g1, g2, g3, g4 = (_frac((i + 1) * c) for c in (0.7548776662466927, 0.5698402909980532, 0.3819660112501051, 0.2360679774997897))

@@ -290,6 +290,7 @@ int bslam_update_cfactors_from_pcg_delta(bslam_context* ctx, void* stream_, cons
   hipLaunchKernelGGL(pcg_update_cfactors_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (uint8_t*)cfactor_buffer->address,
                      (uint32_t)cfactor_buffer->pitch, cfactor_buffer->width, cfactor_buffer->height, cfactor_unknown_start_index, pcg_delta);
   BSLAM_HIP_TRY(hipGetLastError());
+  ctx->records_signature.clear();   // cfactor content changed: cached records (bslam_set_keyframe_cache) were built from the old one
   return BSLAM_OK;
 }
 

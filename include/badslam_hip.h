@@ -184,7 +184,9 @@ int bslam_set_texture_mode(bslam_context* ctx, int mode);
  * reference's tests do, BS/test/test_geometry_optimization_geometric_residual.cc:124-139).
  * enable = 1: the caller promises to call bslam_invalidate_keyframe_cache() after changing the
  * CONTENT of any keyframe depth / normal image or of the cfactor image in place; records are then
- * re-used while buffer addresses, pitches, a, raw_to_float_depth and the cell size are unchanged. */
+ * re-used while buffer addresses, pitches, a, raw_to_float_depth and the cell size are unchanged.
+ * The library's own writers of the cfactor image, bslam_optimize_intrinsics (with depth intrinsics)
+ * and bslam_update_cfactors_from_pcg_delta, drop the records themselves. */
 int bslam_set_keyframe_cache(bslam_context* ctx, int enable);
 int bslam_invalidate_keyframe_cache(bslam_context* ctx);
 

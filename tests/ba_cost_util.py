@@ -75,3 +75,15 @@ def scene_objective(scene, mask=None, surfels_size=None, use_depth=None, use_des
         scene.surfels_size = saved
     return np.array(cost), np.array(counts)
 
+
+
+def oracle_terms(got_cost, want_cost, want_counts):
+    """[(keyframe, residual type, |device - oracle|, tolerance)] of a cost table against scene_objective's: 1e-4 relative, plus 1e-9
+    per pair for sums of near-zero terms (at the true poses a depth residual is a rounding error, formed with fused multiply-adds on
+    the device and without on the host)."""
+    out = []
+    for k in range(len(want_cost)):
+        for j in range(2):
+            tol = 1e-4 * abs(want_cost[k, j]) + 1e-9 * max(1, int(want_counts[k, j]))
+            out.append((k, j, abs(float(got_cost[k, j]) - want_cost[k, j]), tol))
+    return out

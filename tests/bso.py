@@ -196,6 +196,13 @@ def se3_to_np(a):
     return np.array(list(a.q) + list(a.t), np.float32)
 
 
+def pose_coeff_terms(H, b, H64, b64):
+    """[(|device - oracle|, tolerance)] for H and for b of one keyframe's Gauss-Newton coefficients against the float64 sums of
+    HostScene.accumulate_pose: 1e-4 of the largest entry, b's floor at 1e-3 of H's."""
+    return [(np.abs(np.asarray(H, np.float64) - H64).max(), 1e-4 * np.abs(H64).max()),
+            (np.abs(np.asarray(b, np.float64) - b64).max(), 1e-4 * max(np.abs(b64).max(), 1e-3 * np.abs(H64).max()))]
+
+
 class HostKeyframe:
     """Host mirror of vis::Keyframe's buffers (BS/keyframe.h:227-231)."""
 

@@ -114,6 +114,14 @@ def shared_close(got, sums, groups, what, tol=None):
     return worst
 
 
+def ulp_distance(a, b):
+    """Distance in representable fp32 values between two float32 arrays."""
+    def ordered(x):
+        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
+        return np.where(i < 0, -(i & 0x7fffffff), i)
+    return np.abs(ordered(a) - ordered(b))
+
+
 def rel_close(a, b, rel, what):
     """test_gpu_pcg.close: max |a - b| over the slice's largest |b| (for runs of like-scaled entries and for scalars)."""
     a, b = np.atleast_1d(np.asarray(a, np.float64)), np.atleast_1d(np.asarray(b, np.float64))

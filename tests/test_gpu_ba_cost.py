@@ -37,12 +37,8 @@ def ba_cost(ctx, dev, use_depth, use_desc, surfels_size=None, active=None, views
 
 def check_against_oracle(got_cost, got_counts, want_cost, want_counts):
     assert np.array_equal(got_counts.astype(np.int64), want_counts), (got_counts, want_counts)
-    # 1e-4 relative; plus 1e-9 per pair for sums of near-zero terms (at the true poses a depth residual is a rounding error, formed
-    # with fused multiply-adds on the device and without on the host)
-    for k in range(len(want_cost)):
-        for j in range(2):
-            tol = 1e-4 * abs(want_cost[k, j]) + 1e-9 * max(1, int(want_counts[k, j]))
-            assert abs(float(got_cost[k, j]) - want_cost[k, j]) <= tol, (k, j, got_cost[k, j], want_cost[k, j])
+    for k, j, err, tol in ba_cost_util.oracle_terms(got_cost, want_cost, want_counts):
+        assert err <= tol, (k, j, got_cost[k, j], want_cost[k, j])
 
 
 def perturb(scene, rng, t=0.006, r=0.003):

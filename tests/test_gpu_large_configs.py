@@ -14,6 +14,7 @@ import pytest
 
 import badslam_amd
 from badslam_amd import abi, synthetic
+from tests import bso
 
 pytestmark = pytest.mark.gpu
 P = C.POINTER
@@ -105,8 +106,7 @@ def test_configs2_photometric_300_keyframes_properties_and_oracle(oracle):
                                                 abi.TEX_FIXED_POINT_1_8, C.byref(count), C.byref(cost), bso.fptr(H), bso.fptr(b),
                                                 H64.ctypes.data_as(P(C.c_double)), b64.ctypes.data_as(P(C.c_double)), None)
         assert count.value == cnt[k], (k, count.value, cnt[k])
-        assert np.abs(full[k, :21] - H64).max() <= 1e-4 * np.abs(H64).max(), k
-        assert np.abs(full[k, 21:27] - b64).max() <= 1e-4 * max(np.abs(b64).max(), 1e-3 * np.abs(H64).max()), k
+        assert all(err <= tol for err, tol in bso.pose_coeff_terms(full[k, :21], full[k, 21:27], H64, b64)), k
 
 
 def oracle_coefficients(dev, k, surf, use_desc):
@@ -164,8 +164,7 @@ def test_trajectory_stack_300_keyframes_culling_properties_and_oracle(oracle):
     for k in (0, 149, 299):
         H64, b64, count = oracle_coefficients(dev, k, surf, True)
         assert count == cnt[k], (k, count, cnt[k])
-        assert np.abs(full[k, :21] - H64).max() <= 1e-4 * np.abs(H64).max(), k
-        assert np.abs(full[k, 21:27] - b64).max() <= 1e-4 * max(np.abs(b64).max(), 1e-3 * np.abs(H64).max()), k
+        assert all(err <= tol for err, tol in bso.pose_coeff_terms(full[k, :21], full[k, 21:27], H64, b64)), k
 
 
 def test_configs4_geometry_1000_keyframes_20m_surfels_properties():

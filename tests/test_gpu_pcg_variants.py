@@ -65,12 +65,7 @@ def case_scene(name):
     return scene, layout
 
 
-def ulp_distance(a, b):
-    """Distance in representable fp32 values between two float32 arrays."""
-    def ordered(x):
-        i = np.ascontiguousarray(x, np.float32).view(np.int32).astype(np.int64)
-        return np.where(i < 0, -(i & 0x7fffffff), i)
-    return np.abs(ordered(a) - ordered(b))
+ulp_distance = pp.ulp_distance   # (test_gpu_intrinsics_step imports it from here)
 
 
 def assert_same_run(first, second, groups, what):

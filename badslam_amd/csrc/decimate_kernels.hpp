@@ -92,10 +92,9 @@ __global__ __launch_bounds__(256) void decimate_keys_kernel(DecimateState s) {
   if (t >= s.triangles) return;
   const uint32_t i[3] = {s.tri[3 * (size_t)t], s.tri[3 * (size_t)t + 1], s.tri[3 * (size_t)t + 2]};
   for (int k = 0; k < 3; ++k) {
-    const uint32_t a = i[k], b = i[(k + 1) % 3], lo = a < b ? a : b, hi = a < b ? b : a;
     const size_t slot = 3 * (size_t)t + k;
-    s.edge_keys[slot] = ((unsigned long long)lo << s.bits) | hi;
-    s.vertex_keys[slot] = a;
+    s.edge_keys[slot] = mesh_edge_key(i[k], i[(k + 1) % 3], s.bits);
+    s.vertex_keys[slot] = i[k];
     s.ids[slot] = (uint32_t)slot;
   }
 }
@@ -112,8 +111,8 @@ __global__ __launch_bounds__(256) void decimate_heads_kernel(DecimateState s) {
   s.first[slot] = head ? 1 : 0;
   s.single[slot] = head && last ? 1 : 0;
   if (head && last) {
-    s.boundary[(uint32_t)(e >> s.bits)] = 1;                           // every writer writes 1
-    s.boundary[(uint32_t)(e & ((1ull << s.bits) - 1ull))] = 1;
+    s.boundary[mesh_edge_lo(e, s.bits)] = 1;   // every writer writes 1
+    s.boundary[mesh_edge_hi(e, s.bits)] = 1;
   }
   const unsigned long long v = s.sorted_vertices[i];
   if (i == 0 || s.sorted_vertices[i - 1] != v) s.fan_start[v] = i;
@@ -160,7 +159,7 @@ __global__ __launch_bounds__(256) void decimate_eval_kernel(DecimateState s, flo
   uint32_t choice = 0;
   if (s.head[i]) {
     const unsigned long long e = s.sorted_edges[i];
-    const uint32_t lo = (uint32_t)(e >> s.bits), hi = (uint32_t)(e & ((1ull << s.bits) - 1ull));
+    const uint32_t lo = mesh_edge_lo(e, s.bits), hi = mesh_edge_hi(e, s.bits);
     const uint32_t c = 1u + ((i + 1 < s.edges && s.sorted_edges[i + 1] == e) ? 1u : 0u) + ((i + 2 < s.edges && s.sorted_edges[i + 2] == e) ? 1u : 0u);   // 3: more than two
     const uint32_t lo_begin = s.fan_start[lo], lo_end = s.fan_end[lo], hi_begin = s.fan_start[hi], hi_end = s.fan_end[hi];
     bool ok = c <= 2u;
@@ -242,7 +241,7 @@ __global__ __launch_bounds__(256) void decimate_select_kernel(DecimateState s) {
   bool selected = false;
   if (key != kDecimateNoKey) {
     const unsigned long long e = s.sorted_edges[i];
-    const uint32_t lo = (uint32_t)(e >> s.bits), hi = (uint32_t)(e & ((1ull << s.bits) - 1ull));
+    const uint32_t lo = mesh_edge_lo(e, s.bits), hi = mesh_edge_hi(e, s.bits);
     selected = key == s.m2[lo] && key == s.m2[hi];
     if (selected) {
       atomicAdd(&s.words[kDecimateSelected], 1u);
@@ -271,7 +270,7 @@ __global__ __launch_bounds__(256) void decimate_apply_kernel(DecimateState s) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= s.edges || !s.selected[i]) return;
   const unsigned long long e = s.sorted_edges[i];
-  const uint32_t lo = (uint32_t)(e >> s.bits), hi = (uint32_t)(e & ((1ull << s.bits) - 1ull)), choice = s.choice[i];
+  const uint32_t lo = mesh_edge_lo(e, s.bits), hi = mesh_edge_hi(e, s.bits), choice = s.choice[i];
   for (int n = 0; n < 10; ++n) s.quadrics[10 * (size_t)lo + n] = s.quadrics[10 * (size_t)lo + n] + s.quadrics[10 * (size_t)hi + n];
   float* pl = s.positions + 3 * (size_t)lo;
   const float* ph = s.positions + 3 * (size_t)hi;

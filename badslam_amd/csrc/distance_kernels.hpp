@@ -53,8 +53,6 @@ __device__ __forceinline__ uint32_t pmd_key(float f) {   // unsigned order == fl
 }
 __host__ __device__ __forceinline__ float pmd_cell(float x, float origin, float inv_cell) { return floorf((x - origin) * inv_cell); }
 
-__device__ __forceinline__ bool pmd_finite(float v) { return (__float_as_uint(v) & 0x7f800000u) != 0x7f800000u; }
-
 // Vertices and dilated box of triangle t.  *bad is set for an index >= V, which is never dereferenced.
 __device__ __forceinline__ PmdTriangle pmd_load_triangle(uint32_t t, uint32_t vertices, const float* __restrict__ positions, const uint32_t* __restrict__ indices,
                                                          float R, bool* bad) {

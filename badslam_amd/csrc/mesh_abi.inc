@@ -1,6 +1,6 @@
 // mesh_abi.inc -- mesh component entry points of include/badslam_hip.h, and the host pieces the mesh operators behind it share
-// (simplify_abi.inc, decimate_abi.inc, smooth_abi.inc): span checks, the error word, the triangle remap, the radix sort.  Included by
-// badslam_hip.hip after lifecycle_abi.inc and fusion_abi.inc: device_scan, the fusion slab.
+// (simplify_abi.inc, decimate_abi.inc, smooth_abi.inc, repair_abi.inc, orient_abi.inc): span checks, the error word, the triangle remap,
+// the radix sort, the edge runs.  Included by badslam_hip.hip after lifecycle_abi.inc and fusion_abi.inc: device_scan, the fusion slab.
 
 namespace bslam {
 
@@ -50,6 +50,7 @@ static int mesh_error(uint32_t bits, const char* call) {
   if (bits & kMeshBadIndex) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a triangle names a vertex beyond vertex_count", call);
   if (bits & kMeshOverrun) return fail(BSLAM_ERR_INTERNAL, "%s: a union-find loop ran into its cap", call);
   if (bits & kMeshBadPosition) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a vertex is not finite", call);
+  if (bits & kMeshDegenerate) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a triangle repeats an index (bslam_clean_mesh drops such triangles)", call);
   return BSLAM_OK;
 }
 
@@ -104,6 +105,49 @@ static int mesh_sort(const char* call, void* temp, size_t temp_bytes, const unsi
   BSLAM_HIP_TRY(mesh_sort_pairs(nullptr, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
   if (need > temp_bytes) return fail(BSLAM_ERR_INTERNAL, "%s: a sort of %zu pairs needs %zu bytes of scratch where %zu were reserved", call, count, need, temp_bytes);
   BSLAM_HIP_TRY(mesh_sort_pairs(temp, &need, keys, sorted_keys, ids, sorted_ids, count, end_bit, stream));
+  return BSLAM_OK;
+}
+
+// The edge runs of mesh_kernels.hpp for the V >= 1 vertices and T triangles of `indices`: the scalars, and the arrays carved from `c`
+// (referenced is left null).  `error` is the error word of the call.
+static void edge_runs_layout(Carver& c, uint32_t V, uint32_t T, const uint32_t* indices, uint32_t* error, EdgeRuns* runs) {
+  const size_t ne = pad64(3 * (size_t)T);
+  runs->vertices = V; runs->triangles = T; runs->slots = 3 * T; runs->bits = vertex_id_bits(V); runs->indices = indices; runs->error = error;
+  runs->keys = c.take<unsigned long long>(ne, 64); runs->sorted_keys = c.take<unsigned long long>(ne, 64); runs->ids = c.take<uint32_t>(ne, 64);
+  runs->sorted_slots = c.take<uint32_t>(ne, 64); runs->head = c.take<uint8_t>(ne, 64); runs->rank = c.take<uint32_t>(ne, 64);
+  runs->start_of = c.take<uint32_t>(ne + 64, 64);
+}
+
+// Builds `runs` in the stages 0 .. 2 of `timer` (RepairTimer; a template parameter only because repair_abi.inc, which defines it, is
+// included behind this file).  The caller has opened stage 0 and may have launched kernels of its own there.  Here: the keys, the end of stage 0, the read-back of the error word -- nothing is decoded from the key of
+// a triangle that must not be looked at, and no output is written for a mesh that is refused --, the stable sort as stage 1 (the uses
+// of an edge stay in ascending slot) and, in stage 2, the heads, their scan, whose total goes to *unique_edges, a word on the device,
+// and the starts.  Stage 2 is left open for the caller to close.  Without triangles it returns behind the read-back.
+template <class Timer>
+static int build_edge_runs(bslam_context* ctx, hipStream_t stream, const char* call, const EdgeRuns& runs, uint32_t* tile_sums, uint8_t* sort_temp, size_t sort_bytes,
+                           Timer& timer, uint32_t* unique_edges) {
+  const dim3 block(256);
+  const size_t T = runs.triangles, E = runs.slots;
+  int rc;
+  if (T != 0) {
+    hipLaunchKernelGGL(edge_keys_kernel, flat_grid(T), block, 0, stream, runs);
+    BSLAM_HIP_TRY(hipGetLastError());
+  }
+  if ((rc = timer.end(0))) return rc;
+  const uint32_t* host = nullptr;
+  if ((rc = read_back(ctx, stream, (const uint32_t*)runs.error, 1, &host))) return rc;
+  if ((rc = mesh_error(host[0], call))) return rc;
+  if (T == 0) return BSLAM_OK;
+  if ((rc = timer.begin(1))) return rc;
+  if ((rc = mesh_sort(call, sort_temp, sort_bytes, runs.keys, runs.sorted_keys, runs.ids, runs.sorted_slots, E, 2 * runs.bits, stream))) return rc;
+  if ((rc = timer.end(1))) return rc;
+  if ((rc = timer.begin(2))) return rc;
+  hipLaunchKernelGGL(mesh_heads_kernel, flat_grid(E), block, 0, stream, runs.slots, (const unsigned long long*)runs.sorted_keys, (const uint32_t*)runs.sorted_slots,
+                     (const unsigned long long*)nullptr, runs.head);
+  BSLAM_HIP_TRY(hipGetLastError());
+  if ((rc = device_scan(stream, 0, runs.head, runs.slots, false, runs.rank, tile_sums, unique_edges))) return rc;
+  hipLaunchKernelGGL(edge_starts_kernel, flat_grid(E), block, 0, stream, runs);
+  BSLAM_HIP_TRY(hipGetLastError());
   return BSLAM_OK;
 }
 
@@ -177,18 +221,20 @@ int bslam_filter_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
          keep_vertex = c.take<uint8_t>(nv, 64); keep_triangle = c.take<uint8_t>(nt, 64); vertex_rank = c.take<uint32_t>(nv, 64);
          triangle_rank = c.take<uint32_t>(nt, 64); tile_sums = c.take<uint32_t>(tiles); words = c.take<uint32_t>(16);
        }))) return rc;
-  MeshFilter m;
-  m.vertices = vertex_count; m.triangles = triangle_count; m.vertex_blocks = flat_grid(V).x; m.min_vertices = min_vertices;
-  m.positions = positions; m.normals = normals; m.colors = (const uint32_t*)colors; m.indices = indices; m.sizes = sizes;
-  m.out_positions = out_positions; m.out_normals = out_normals; m.out_colors = (uint32_t*)out_colors; m.out_indices = out_indices;
-  const dim3 grid(m.vertex_blocks + flat_grid(T).x), block(256);   // < 2^25 blocks
+  MeshFilter f;
+  f.vertices = vertex_count; f.triangles = triangle_count; f.vertex_blocks = flat_grid(V).x; f.min_vertices = min_vertices; f.indices = indices; f.sizes = sizes;
+  const dim3 grid(f.vertex_blocks + flat_grid(T).x), block(256);   // < 2^25 blocks
   BSLAM_HIP_TRY(hipMemsetAsync(words, 0, 2 * sizeof(uint32_t), stream));
-  hipLaunchKernelGGL(mesh_keep_flags_kernel, grid, block, 0, stream, m, keep_vertex, keep_triangle, words);
+  hipLaunchKernelGGL(mesh_keep_flags_kernel, grid, block, 0, stream, f, keep_vertex, keep_triangle, words);
   BSLAM_HIP_TRY(hipGetLastError());
   if ((rc = device_scan(stream, 0, keep_vertex, vertex_count, true, vertex_rank, tile_sums, words + 2))) return rc;
   if ((rc = device_scan(stream, 0, keep_triangle, triangle_count, true, triangle_rank, tile_sums, words + 3))) return rc;
-  hipLaunchKernelGGL(mesh_scatter_kernel, grid, block, 0, stream, m, (const uint8_t*)keep_vertex, (const uint8_t*)keep_triangle, (const uint32_t*)vertex_rank,
-                     (const uint32_t*)triangle_rank);
+  MeshCompact m = {};   // rep and the maps stay null: every vertex its own, no maps
+  m.vertices = vertex_count; m.triangles = triangle_count; m.vertex_blocks = f.vertex_blocks;
+  m.positions = positions; m.normals = normals; m.colors = (const uint32_t*)colors; m.indices = indices;
+  m.keep_vertex = keep_vertex; m.keep_triangle = keep_triangle; m.vertex_rank = vertex_rank; m.triangle_rank = triangle_rank;
+  m.out_positions = out_positions; m.out_normals = out_normals; m.out_colors = (uint32_t*)out_colors; m.out_indices = out_indices;
+  hipLaunchKernelGGL(mesh_compact_kernel, grid, block, 0, stream, m);
   BSLAM_HIP_TRY(hipGetLastError());
   const uint32_t* host = nullptr;
   if ((rc = read_back(ctx, stream, (const uint32_t*)words, 4, &host))) return rc;

@@ -1,7 +1,8 @@
 // orient_kernels.hpp -- consistent winding of an indexed triangle mesh, for gfx950: a union-find over the triangles that carries a
-// parity bit, a conflict pass that finds the pieces that cannot be oriented, the per-patch votes for which side is out, and the pass
-// that writes the flipped triangles.  The edge runs come from the census of repair_kernels.hpp (topology_keys_kernel, the stable sort,
-// repair_heads_kernel, the scan and topology_starts_kernel).  The reference has no mesh.
+// parity bit (the kParity = true instantiation of mesh_kernels.hpp: link[t] = parent << 1 | parity, where parity is f[t] ^ f[parent]
+// of every assignment f that satisfies the seams joined so far), a conflict pass that finds the pieces that cannot be oriented, the
+// per-patch votes for which side is out, and the pass that writes the flipped triangles.  The edge runs are those of mesh_kernels.hpp
+// (EdgeRuns; build_edge_runs of mesh_abi.inc).  The reference has no mesh.
 //
 // The rule (include/badslam_hip.h "Mesh orientation", DESIGN.md 8 "Mesh orientation"): a seam is an edge with exactly two uses; it
 // disagrees iff its two slots start at the same vertex.  Triangles that share a seam are joined; a patch is a class of the transitive
@@ -14,7 +15,7 @@
 
 #include <cstdint>
 
-#include "repair_kernels.hpp"
+#include "mesh_kernels.hpp"
 
 namespace bslam {
 
@@ -28,12 +29,10 @@ constexpr int kOrientSeams = 0, kOrientDisagreeBefore = 1, kOrientDisagreeAfter 
 constexpr uint32_t kOrientConflict = 1u, kOrientOpen = 2u;
 
 struct OrientMesh {
-  uint32_t vertices, triangles, slots;
+  EdgeRuns runs;                                       // triangles, slots, indices, the runs; runs.error: the error word of the call
   int mode;
   int size_bits;                                       // the bit length of T
   const float* positions; const float* normals;        // normals: null unless mode 1
-  const uint32_t* indices;
-  const uint32_t* sorted_slots; const uint8_t* head; const uint32_t* rank; const uint32_t* start_of;   // the runs of the census
   uint32_t* link;                                      // [T] parent << 1 | parity to the parent; parent <= t
   uint8_t* seam;                                       // [E] by sorted position: 0, or 1 | disagrees << 1 at the head of a run of two
   uint8_t* open;                                       // [T] a slot of t lies on an edge with other than two uses
@@ -42,7 +41,6 @@ struct OrientMesh {
   long long* volume;                                   // [T] at the root
   uint8_t* invert;                                     // [T] at the root
   uint32_t* out_indices; uint8_t* flipped; uint32_t* patch_of_triangle;   // the caller's; the last two may be null
-  uint32_t* words;                                     // words[0]: the error word of the mesh calls
   uint32_t* counts;                                    // kOrientWords
 };
 
@@ -83,7 +81,7 @@ __global__ __launch_bounds__(256) void orient_bounds_kernel(uint32_t vertices, c
 // link[t] = t << 1: every triangle a root with parity 0; the per-triangle and per-root sums are cleared.
 __global__ __launch_bounds__(256) void orient_init_kernel(OrientMesh m) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= m.triangles) return;
+  if (t >= m.runs.triangles) return;
   m.link[t] = t << 1;
   m.open[t] = 0;
   m.state[t] = 0; m.size[t] = 0; m.ones[t] = 0; m.positive[t] = 0; m.negative[t] = 0;
@@ -91,120 +89,46 @@ __global__ __launch_bounds__(256) void orient_init_kernel(OrientMesh m) {
   m.invert[t] = 0;
 }
 
-// ---------------------------------------------------------------------------------------------
-// Parity union-find over link[T], the union-find of mesh_kernels.hpp with one more bit: link[t] = parent << 1 | parity, where parity
-// is f[t] ^ f[parent] of every assignment f that satisfies the seams joined so far.  parent <= t at all times, so a find walks
-// strictly downwards and the root of a finished patch is its smallest triangle whatever the schedule.  Every word always holds a true
-// (ancestor, parity to that ancestor) pair: a hook writes the parity that the seam demands between the two roots, and path halving
-// replaces (parent, p1) by (grandparent, p1 ^ p2) in one 32-bit store.  Links are only ever added, so the parity between two
-// connected triangles never changes, and a stale word is still a true pair.  As in mesh_find every access inside the union launch is
-// a relaxed atomic at agent scope.
-// ---------------------------------------------------------------------------------------------
-
-// Root of v with path halving; *parity ^= the parity from v to it.  At most `cap` steps; *overrun is set beyond.
-__device__ __forceinline__ uint32_t orient_find(uint32_t* link, uint32_t v, uint32_t* parity, uint32_t cap, bool* overrun) {
-  uint32_t w = parent_load(link + v);
-  for (uint32_t steps = 0; (w >> 1) != v; ++steps) {
-    if (steps >= cap) { *overrun = true; return v; }
-    const uint32_t p = w >> 1, wp = parent_load(link + p);
-    if ((wp >> 1) != p) parent_store(link + v, (wp & ~1u) | ((w ^ wp) & 1u));
-    *parity ^= w & 1u;
-    v = p;
-    w = wp;
-  }
-  return v;
-}
-
-// Joins the trees of a and b, which must differ by `rel` (f[a] ^ f[b]), for every lane of a wave whose `active` is set; all 64 lanes
-// call it together.  The rounds are those of mesh_unite_wave: find both roots and fold their parities into rel, which then is what the
-// two roots must differ by; the larger root is hooked under the smaller one with that parity by a compare-and-swap that expects the
-// root itself; of the lanes that hold the same larger root only the lowest swaps in a round.  A failed swap returns the word the
-// entry holds now, a true (ancestor, parity) pair of the failed root: the lane goes on from that ancestor with the parity folded in.
-// Two triangles found under one root are left alone, whatever rel says: the conflict pass looks at every seam again.
-__device__ __forceinline__ void orient_unite_wave(uint32_t* link, bool active, uint32_t a, uint32_t b, uint32_t rel, uint32_t triangles, bool* overrun) {
-  const uint32_t cap = triangles + 64u;
-  const int lane = (int)(threadIdx.x & 63u);
-  for (unsigned long long round = 0; __ballot(active) != 0; ++round) {   // wave-uniform
-    uint32_t hi = 0, lo = 0;
-    if (active) {
-      a = orient_find(link, a, &rel, cap, overrun);
-      b = orient_find(link, b, &rel, cap, overrun);
-      if (a == b || *overrun) active = false;
-      hi = a > b ? a : b;
-      lo = a > b ? b : a;
-    }
-    bool swaps = false;
-    for (unsigned long long pending = __ballot(active); pending != 0;) {   // wave-uniform: one pass per distinct hi
-      const int first = __builtin_ctzll(pending);
-      const uint32_t h = __shfl(hi, first, 64);
-      if (lane == first) swaps = true;
-      pending &= ~__ballot(active && hi == h);
-    }
-    if (swaps) {
-      uint32_t expected = hi << 1;
-      if (__hip_atomic_compare_exchange_strong(link + hi, &expected, (lo << 1) | rel, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
-        active = false;
-      } else {
-        a = expected >> 1;   // the parent the entry holds now, < hi
-        rel ^= expected & 1u;
-        b = lo;
-      }
-    }
-    if (active && round >= 64ull * cap) { *overrun = true; active = false; }
-  }
-}
-
 // By sorted position, one launch whatever the diameter: the triangles of a slot on an edge with other than two uses are open; the head
-// of a run of two is a seam, counted, kept in seam[] with its disagreement for the launches behind, and its two triangles are joined.
+// of a run of two is a seam, counted, kept in seam[] with its disagreement for the launches behind, and its two triangles are joined
+// with that disagreement as their relation.  Two triangles already under one root are left alone, whatever the seam says: the
+// conflict pass looks at every seam again.
 __global__ __launch_bounds__(256) void orient_union_kernel(OrientMesh m) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   bool is_seam = false;
   uint32_t a = 0, b = 0, d = 0;
-  if (i < m.slots) {   // lanes beyond the last slot stay: the wave votes as a whole
-    const uint32_t r = m.rank[i] - 1u, uses = m.start_of[r + 1] - m.start_of[r], slot = m.sorted_slots[i];
+  if (i < m.runs.slots) {   // lanes beyond the last slot stay: the wave votes as a whole
+    const uint32_t r = m.runs.rank[i] - 1u, uses = m.runs.start_of[r + 1] - m.runs.start_of[r], slot = m.runs.sorted_slots[i];
     if (uses != 2) m.open[slot / 3u] = 1;
-    is_seam = uses == 2 && m.head[i] != 0;
+    is_seam = uses == 2 && m.runs.head[i] != 0;
     if (is_seam) {
-      const uint32_t other = m.sorted_slots[i + 1];   // a run of two: i + 1 < E
+      const uint32_t other = m.runs.sorted_slots[i + 1];   // a run of two: i + 1 < E
       a = slot / 3u;
       b = other / 3u;
-      d = m.indices[slot] == m.indices[other] ? 1u : 0u;
+      d = m.runs.indices[slot] == m.runs.indices[other] ? 1u : 0u;
     }
     m.seam[i] = is_seam ? (uint8_t)(1u | (d << 1)) : (uint8_t)0;
   }
-  repair_count(&m.counts[kOrientSeams], is_seam);
-  repair_count(&m.counts[kOrientDisagreeBefore], is_seam && d != 0);
+  mesh_wave_count(&m.counts[kOrientSeams], is_seam);
+  mesh_wave_count(&m.counts[kOrientDisagreeBefore], is_seam && d != 0);
   bool overrun = false;
-  orient_unite_wave(m.link, is_seam, a, b, d, m.triangles, &overrun);
-  if (overrun) atomicOr(&m.words[0], kMeshOverrun);
-}
-
-// Root of v by plain loads, for the launches behind the union (the kernel boundary made every hook visible); *parity = the parity
-// from v to it.
-__device__ __forceinline__ uint32_t orient_root(const uint32_t* link, uint32_t v, uint32_t triangles, uint32_t* parity, bool* overrun) {
-  uint32_t w = link[v], p = 0;
-  for (uint32_t steps = 0; (w >> 1) != v; ++steps) {
-    if (steps >= triangles + 64u) { *overrun = true; break; }
-    p ^= w & 1u;
-    v = w >> 1;
-    w = link[v];
-  }
-  *parity = p;
-  return v;
+  uint32_t tries = 0, fails = 0;   // not reported
+  mesh_unite_wave<true>(m.link, is_seam, a, b, d, m.runs.triangles, &overrun, &tries, &fails);
+  if (overrun) atomicOr(m.runs.error, kMeshOverrun);
 }
 
 // By sorted position, behind the union: the two triangles of a seam have one root, and the patch cannot be oriented iff for one of
 // its seams their parities to it differ by other than the seam's disagreement -- whichever spanning forest the hooks built.
 __global__ __launch_bounds__(256) void orient_conflict_kernel(OrientMesh m) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m.slots) return;
+  if (i >= m.runs.slots) return;
   const uint32_t code = m.seam[i];
   if (code == 0) return;
   bool overrun = false;
   uint32_t pa = 0, pb = 0;
-  const uint32_t ra = orient_root(m.link, m.sorted_slots[i] / 3u, m.triangles, &pa, &overrun);
-  const uint32_t rb = orient_root(m.link, m.sorted_slots[i + 1] / 3u, m.triangles, &pb, &overrun);
-  if (overrun || ra != rb) { atomicOr(&m.words[0], kMeshOverrun); return; }
+  const uint32_t ra = mesh_root<true>(m.link, m.runs.sorted_slots[i] / 3u, m.runs.triangles, &pa, &overrun);
+  const uint32_t rb = mesh_root<true>(m.link, m.runs.sorted_slots[i + 1] / 3u, m.runs.triangles, &pb, &overrun);
+  if (overrun || ra != rb) { atomicOr(m.runs.error, kMeshOverrun); return; }
   if ((pa ^ pb) != (code >> 1) && !(m.state[ra] & kOrientConflict)) atomicOr(&m.state[ra], kOrientConflict);
 }
 
@@ -221,19 +145,19 @@ __device__ __forceinline__ double orient_dot(orient3 a, orient3 b) { return (a.x
 // that share a root add once; after four distinct roots the lanes that are left add for themselves (mesh_flatten_kernel).
 __global__ __launch_bounds__(256) void orient_flatten_kernel(OrientMesh m) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  bool live = t < m.triangles, overrun = false;
+  bool live = t < m.runs.triangles, overrun = false;
   uint32_t root = 0, par = 0;
   bool open = false, plus = false, minus = false;
   long long q = 0;
   if (live) {
-    root = orient_root(m.link, t, m.triangles, &par, &overrun);
-    if (overrun) { atomicOr(&m.words[0], kMeshOverrun); live = false; }
+    root = mesh_root<true>(m.link, t, m.runs.triangles, &par, &overrun);
+    if (overrun) { atomicOr(m.runs.error, kMeshOverrun); live = false; }
   }
   if (live) {
     m.patch[t] = root;
     m.flip0[t] = (uint8_t)par;
     open = m.open[t] != 0;
-    const uint32_t i0 = m.indices[3 * (size_t)t], i1 = m.indices[3 * (size_t)t + 1 + par], i2 = m.indices[3 * (size_t)t + 2 - par];
+    const uint32_t i0 = m.runs.indices[3 * (size_t)t], i1 = m.runs.indices[3 * (size_t)t + 1 + par], i2 = m.runs.indices[3 * (size_t)t + 2 - par];
     if (m.mode == kOrientNormals) {
       const orient3 p0 = orient_load(m.positions, i0), p1 = orient_load(m.positions, i1), p2 = orient_load(m.positions, i2);
       const orient3 n0 = orient_load(m.normals, i0), n1 = orient_load(m.normals, i1), n2 = orient_load(m.normals, i2);
@@ -289,7 +213,7 @@ __global__ __launch_bounds__(256) void orient_flatten_kernel(OrientMesh m) {
 // vote does not decide falls back to the majority.  With an extent of zero no volume was added, so every sum is zero.
 __global__ __launch_bounds__(256) void orient_decide_kernel(OrientMesh m) {
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool root = t < m.triangles && m.patch[t] == t;
+  const bool root = t < m.runs.triangles && m.patch[t] == t;
   bool orientable = false, closed = false, fallback = false, invert = false;
   if (root) {
     const uint32_t state = m.state[t], size = m.size[t], ones = m.ones[t];
@@ -310,12 +234,12 @@ __global__ __launch_bounds__(256) void orient_decide_kernel(OrientMesh m) {
       m.invert[t] = invert ? 1 : 0;
     }
   }
-  repair_count(&m.counts[kOrientPatches], root);
-  repair_count(&m.counts[kOrientOrientable], root && orientable);
-  repair_count(&m.counts[kOrientNonOrientable], root && !orientable);
-  repair_count(&m.counts[kOrientClosed], root && closed);
-  repair_count(&m.counts[kOrientFallback], fallback);
-  repair_count(&m.counts[kOrientInverted], invert);
+  mesh_wave_count(&m.counts[kOrientPatches], root);
+  mesh_wave_count(&m.counts[kOrientOrientable], root && orientable);
+  mesh_wave_count(&m.counts[kOrientNonOrientable], root && !orientable);
+  mesh_wave_count(&m.counts[kOrientClosed], root && closed);
+  mesh_wave_count(&m.counts[kOrientFallback], fallback);
+  mesh_wave_count(&m.counts[kOrientInverted], invert);
 }
 
 // Blocks [0, triangle_blocks) take a triangle per lane: flipped = flip0 ^ invert of its patch, or 0 where the patch cannot be oriented;
@@ -325,22 +249,22 @@ __global__ __launch_bounds__(256) void orient_write_kernel(OrientMesh m, uint32_
   if (blockIdx.x < triangle_blocks) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     bool flip = false;
-    if (t < m.triangles) {
+    if (t < m.runs.triangles) {
       const uint32_t root = m.patch[t];
       flip = !(m.state[root] & kOrientConflict) && (m.flip0[t] ^ m.invert[root]) != 0;
       const size_t at = 3 * (size_t)t;
-      const uint32_t a = m.indices[at], b = m.indices[at + 1], c = m.indices[at + 2];
+      const uint32_t a = m.runs.indices[at], b = m.runs.indices[at + 1], c = m.runs.indices[at + 2];
       m.out_indices[at] = a; m.out_indices[at + 1] = flip ? c : b; m.out_indices[at + 2] = flip ? b : c;
       if (m.flipped != nullptr) m.flipped[t] = flip ? 1 : 0;
       if (m.patch_of_triangle != nullptr) m.patch_of_triangle[t] = root;
     }
-    repair_count(&m.counts[kOrientFlipped], flip);
+    mesh_wave_count(&m.counts[kOrientFlipped], flip);
     return;
   }
   const uint32_t i = (blockIdx.x - triangle_blocks) * blockDim.x + threadIdx.x;
   bool disagrees = false;
-  if (i < m.slots && (m.seam[i] & 2u)) disagrees = (m.state[m.patch[m.sorted_slots[i] / 3u]] & kOrientConflict) != 0;
-  repair_count(&m.counts[kOrientDisagreeAfter], disagrees);
+  if (i < m.runs.slots && (m.seam[i] & 2u)) disagrees = (m.state[m.patch[m.runs.sorted_slots[i] / 3u]] & kOrientConflict) != 0;
+  mesh_wave_count(&m.counts[kOrientDisagreeAfter], disagrees);
 }
 
 }  // namespace bslam

@@ -1,6 +1,6 @@
 // repair_abi.inc -- bslam_clean_mesh, bslam_mesh_topology and bslam_fill_mesh_holes of include/badslam_hip.h (included by
 // badslam_hip.hip after mesh_abi.inc: check_attribute_pairs, mesh_array_spans, check_mesh_spans, mesh_error, empty_mesh, pad64,
-// vertex_id_bits, mesh_sort; device_scan, flat_grid, read_back, carve).
+// vertex_id_bits, mesh_sort, edge_runs_layout, build_edge_runs; device_scan, flat_grid, read_back, carve).
 
 namespace bslam {
 
@@ -23,19 +23,12 @@ struct RepairTimer {
   }
 };
 
-static int repair_error(uint32_t bits, const char* call) {
-  if (int rc = mesh_error(bits, call)) return rc;
-  if (bits & kRepairDegenerate) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: a triangle repeats an index (bslam_clean_mesh drops such triangles)", call);
-  return BSLAM_OK;
-}
-
-// The scratch of the topology pass for V vertices and T triangles, carved from `c`.
-static void topology_layout(Carver& c, size_t V, size_t T, RepairTopology* s, uint32_t** tile_sums, uint8_t** sort_temp, size_t sort_bytes) {
-  const size_t E = 3 * T, nv = pad64(V), ne = pad64(E), tiles = std::max(nv, ne) / kScanTile + 2;
+// The scratch of the topology pass for the V vertices and T triangles of `indices`, carved from `c`.
+static void topology_layout(Carver& c, uint32_t V, uint32_t T, const uint32_t* indices, RepairTopology* s, uint32_t** tile_sums, uint8_t** sort_temp, size_t sort_bytes) {
+  const size_t E = 3 * (size_t)T, nv = pad64(V), ne = pad64(E), tiles = std::max(nv, ne) / kScanTile + 2;
   s->words = c.take<uint32_t>(kRepairWords, 16);
-  s->keys = c.take<unsigned long long>(ne, 64); s->sorted_keys = c.take<unsigned long long>(ne, 64); s->ids = c.take<uint32_t>(ne, 64);
-  s->sorted_slots = c.take<uint32_t>(ne, 64); s->head = c.take<uint8_t>(ne, 64); s->rank = c.take<uint32_t>(ne, 64); s->start_of = c.take<uint32_t>(ne + 64, 64);
-  s->referenced = c.take<uint8_t>(nv, 64); s->starts = c.take<uint32_t>(nv, 64); s->ends = c.take<uint32_t>(nv, 64); s->start_slot = c.take<uint32_t>(nv, 64);
+  edge_runs_layout(c, V, T, indices, s->words + kRepairError, &s->runs);
+  s->runs.referenced = c.take<uint8_t>(nv, 64); s->starts = c.take<uint32_t>(nv, 64); s->ends = c.take<uint32_t>(nv, 64); s->start_slot = c.take<uint32_t>(nv, 64);
   s->boundary = c.take<uint8_t>(ne, 64); s->boundary_id = c.take<uint32_t>(ne, 64); s->loop_slot = c.take<uint32_t>(ne, 64);
   for (int b = 0; b < 2; ++b) { s->next[b] = c.take<uint32_t>(ne, 64); s->label[b] = c.take<uint32_t>(ne, 64); s->open[b] = c.take<uint8_t>(ne, 64); }
   s->loop_length = c.take<uint32_t>(ne, 64);
@@ -44,43 +37,26 @@ static void topology_layout(Carver& c, size_t V, size_t T, RepairTopology* s, ui
 }
 
 // The census and the loops of `s` (V >= 1; the words are zero but kRepairLongest, which is all ones).  Stages 0 .. 3: keys, sort, census,
-// loops.  With fill_flag the loops of at most max_hole_edges edges are flagged for bslam_fill_mesh_holes.  *boundary_slots and *buffer:
-// B, and the buffer that holds the final labels.  The stream is left running; the words hold the report.
+// loops; the first two and the runs of the third are build_edge_runs.  With fill_flag the loops of at most max_hole_edges edges are
+// flagged for bslam_fill_mesh_holes.  *boundary_slots and *buffer: B, and the buffer that holds the final labels.  The stream is left
+// running; the words hold the report.
 static int topology_pass(bslam_context* ctx, hipStream_t stream, const char* call, RepairTopology& s, uint32_t* tile_sums, uint8_t* sort_temp, size_t sort_bytes,
                          RepairTimer& timer, uint32_t max_hole_edges, uint8_t* fill_flag, uint32_t* fan, uint32_t* boundary_slots, int* buffer) {
   const dim3 block(256);
-  const size_t V = s.vertices, T = s.triangles, E = s.slots;
+  const size_t V = s.runs.vertices, T = s.runs.triangles, E = s.runs.slots;
   int rc;
   *boundary_slots = 0;
   *buffer = 0;
-  BSLAM_HIP_TRY(hipMemsetAsync(s.referenced, 0, V, stream));
+  BSLAM_HIP_TRY(hipMemsetAsync(s.runs.referenced, 0, V, stream));
   BSLAM_HIP_TRY(hipMemsetAsync(s.starts, 0, V * sizeof(uint32_t), stream));
   BSLAM_HIP_TRY(hipMemsetAsync(s.ends, 0, V * sizeof(uint32_t), stream));
   BSLAM_HIP_TRY(hipMemsetAsync(s.start_slot, 0xff, V * sizeof(uint32_t), stream));
   if (T != 0) {
     if ((rc = timer.begin(0))) return rc;
-    hipLaunchKernelGGL(topology_keys_kernel, flat_grid(T), block, 0, stream, s);
-    BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = timer.end(0))) return rc;
-    // nothing is decoded from the key of a triangle that must not be looked at, and no output is written for a mesh that is refused
-    const uint32_t* host = nullptr;
-    if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, 1, &host))) return rc;
-    if ((rc = repair_error(host[kRepairError], call))) return rc;
-    if (s.loop_of_slot != nullptr) BSLAM_HIP_TRY(hipMemsetAsync(s.loop_of_slot, 0xff, E * sizeof(uint32_t), stream));
-    if ((rc = timer.begin(1))) return rc;
-    // stable: the uses of an edge stay in ascending slot
-    if ((rc = mesh_sort(call, sort_temp, sort_bytes, s.keys, s.sorted_keys, s.ids, s.sorted_slots, E, 2 * s.bits, stream))) return rc;
-    if ((rc = timer.end(1))) return rc;
-    if ((rc = timer.begin(2))) return rc;
-    hipLaunchKernelGGL(repair_heads_kernel, flat_grid(E), block, 0, stream, s.slots, (const unsigned long long*)s.sorted_keys, (const uint32_t*)s.sorted_slots,
-                       (const unsigned long long*)nullptr, s.head);
-    BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = device_scan(stream, 0, s.head, s.slots, false, s.rank, tile_sums, s.words + kRepairEdges))) return rc;
-    hipLaunchKernelGGL(topology_starts_kernel, flat_grid(E), block, 0, stream, s);
-    BSLAM_HIP_TRY(hipGetLastError());
+    if ((rc = build_edge_runs(ctx, stream, call, s.runs, tile_sums, sort_temp, sort_bytes, timer, s.words + kRepairEdges))) return rc;
     hipLaunchKernelGGL(topology_census_kernel, flat_grid(E), block, 0, stream, s);
     BSLAM_HIP_TRY(hipGetLastError());
-    if ((rc = device_scan(stream, 0, s.boundary, s.slots, true, s.boundary_id, tile_sums, s.words + kRepairBoundarySlots))) return rc;
+    if ((rc = device_scan(stream, 0, s.boundary, s.runs.slots, true, s.boundary_id, tile_sums, s.words + kRepairBoundarySlots))) return rc;
   } else {
     if ((rc = timer.begin(2))) return rc;
   }
@@ -88,6 +64,8 @@ static int topology_pass(bslam_context* ctx, hipStream_t stream, const char* cal
   BSLAM_HIP_TRY(hipGetLastError());
   if ((rc = timer.end(2))) return rc;
   if (T == 0) return BSLAM_OK;
+  // 0xffffffff where no loop passes; like every output, not written for a mesh that is refused
+  if (s.loop_of_slot != nullptr) BSLAM_HIP_TRY(hipMemsetAsync(s.loop_of_slot, 0xff, E * sizeof(uint32_t), stream));
   // the rounds of the pointer jumping depend on the number of boundary slots alone
   const uint32_t* host = nullptr;
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, kRepairWords, &host))) return rc;
@@ -185,13 +163,13 @@ int bslam_clean_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, u
     // stage 1: the two stable sorts, by z and then by (y, x): a run is in ascending vertex id
     if ((rc = timer.begin(1))) return rc;
     if ((rc = mesh_sort(call, sort_temp, sort_bytes, key_first, sorted_keys, ids, ids_a, V, 32, stream))) return rc;
-    hipLaunchKernelGGL(repair_gather_kernel, flat_grid(V), block, 0, stream, vertex_count, (const unsigned long long*)key_second, (const uint32_t*)ids_a, gathered);
+    hipLaunchKernelGGL(mesh_gather_kernel, flat_grid(V), block, 0, stream, vertex_count, (const unsigned long long*)key_second, (const uint32_t*)ids_a, gathered);
     BSLAM_HIP_TRY(hipGetLastError());
     if ((rc = mesh_sort(call, sort_temp, sort_bytes, gathered, sorted_keys, ids_a, ids_b, V, 64, stream))) return rc;
     if ((rc = timer.end(1))) return rc;
     // stage 2: runs and representatives
     if ((rc = timer.begin(2))) return rc;
-    hipLaunchKernelGGL(repair_heads_kernel, flat_grid(V), block, 0, stream, vertex_count, (const unsigned long long*)sorted_keys, (const uint32_t*)ids_b,
+    hipLaunchKernelGGL(mesh_heads_kernel, flat_grid(V), block, 0, stream, vertex_count, (const unsigned long long*)sorted_keys, (const uint32_t*)ids_b,
                        (const unsigned long long*)key_first, head);
     BSLAM_HIP_TRY(hipGetLastError());
     if ((rc = device_scan(stream, 0, head, vertex_count, false, rank, tile_sums, words + kRepairUnique))) return rc;
@@ -214,13 +192,13 @@ int bslam_clean_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, u
     // stage 4: the two stable sorts, by hi and then by (lo, mid): a run is in ascending triangle id
     if ((rc = timer.begin(4))) return rc;
     if ((rc = mesh_sort(call, sort_temp, sort_bytes, key_first, sorted_keys, ids, ids_a, T, bits, stream))) return rc;
-    hipLaunchKernelGGL(repair_gather_kernel, flat_grid(T), block, 0, stream, triangle_count, (const unsigned long long*)key_second, (const uint32_t*)ids_a, gathered);
+    hipLaunchKernelGGL(mesh_gather_kernel, flat_grid(T), block, 0, stream, triangle_count, (const unsigned long long*)key_second, (const uint32_t*)ids_a, gathered);
     BSLAM_HIP_TRY(hipGetLastError());
     if ((rc = mesh_sort(call, sort_temp, sort_bytes, gathered, sorted_keys, ids_a, ids_b, T, 2 * bits, stream))) return rc;
     if ((rc = timer.end(4))) return rc;
     // stage 5: duplicates
     if ((rc = timer.begin(5))) return rc;
-    hipLaunchKernelGGL(repair_heads_kernel, flat_grid(T), block, 0, stream, triangle_count, (const unsigned long long*)sorted_keys, (const uint32_t*)ids_b,
+    hipLaunchKernelGGL(mesh_heads_kernel, flat_grid(T), block, 0, stream, triangle_count, (const unsigned long long*)sorted_keys, (const uint32_t*)ids_b,
                        (const unsigned long long*)key_first, head);
     BSLAM_HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(repair_duplicate_kernel, flat_grid(T), block, 0, stream, triangle_count, (const uint8_t*)head, (const uint32_t*)ids_b, keep, words);
@@ -247,13 +225,13 @@ int bslam_clean_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, u
                  degenerate = host[kRepairDegenerates], duplicate = host[kRepairDuplicates];
   // stage 7: scatter
   if ((rc = timer.begin(7))) return rc;
-  RepairClean m;
+  MeshCompact m;
   m.vertices = vertex_count; m.triangles = triangle_count; m.vertex_blocks = flat_grid(V).x;
   m.positions = positions; m.normals = normals; m.colors = (const uint32_t*)colors; m.indices = indices;
-  m.rep = rep; m.keep_vertex = keep_vertex; m.keep = keep; m.vertex_rank = vertex_rank; m.triangle_rank = triangle_rank;
+  m.keep_vertex = keep_vertex; m.keep_triangle = keep; m.vertex_rank = vertex_rank; m.triangle_rank = triangle_rank; m.rep = rep;
   m.out_positions = out_positions; m.out_normals = out_normals; m.out_colors = (uint32_t*)out_colors; m.out_indices = out_indices;
   m.vertex_map = vertex_map; m.triangle_map = triangle_map;
-  hipLaunchKernelGGL(repair_scatter_kernel, dim3(m.vertex_blocks + flat_grid(T).x), block, 0, stream, m);
+  hipLaunchKernelGGL(mesh_compact_kernel, dim3(m.vertex_blocks + flat_grid(T).x), block, 0, stream, m);
   BSLAM_HIP_TRY(hipGetLastError());
   if ((rc = timer.end(7))) return rc;
   BSLAM_HIP_TRY(hipStreamSynchronize(stream));
@@ -286,8 +264,7 @@ int bslam_mesh_topology(bslam_context* ctx, void* stream_, uint32_t vertex_count
   RepairTopology s = {};
   uint32_t* tile_sums;
   uint8_t* sort_temp;
-  if ((rc = carve(ctx->repair, [&](Carver& c) { topology_layout(c, V, T, &s, &tile_sums, &sort_temp, sort_bytes); }))) return rc;
-  s.vertices = vertex_count; s.triangles = triangle_count; s.slots = (uint32_t)E; s.bits = vertex_id_bits(V); s.indices = indices;
+  if ((rc = carve(ctx->repair, [&](Carver& c) { topology_layout(c, vertex_count, triangle_count, indices, &s, &tile_sums, &sort_temp, sort_bytes); }))) return rc;
   s.edge_uses = edge_uses; s.loop_of_slot = loop_of_slot;
   if ((rc = repair_clear_words(s.words, stream))) return rc;
   uint32_t B = 0;
@@ -296,7 +273,7 @@ int bslam_mesh_topology(bslam_context* ctx, void* stream_, uint32_t vertex_count
   const uint32_t* host = nullptr;
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, kRepairWords, &host))) return rc;
   if ((rc = timer.collect())) return rc;
-  if ((rc = repair_error(host[kRepairError], call))) return rc;
+  if ((rc = mesh_error(host[kRepairError], call))) return rc;
   topology_report(host, triangle_count, report);
   return BSLAM_OK;
 }
@@ -336,15 +313,12 @@ int bslam_fill_mesh_holes(bslam_context* ctx, void* stream_, uint32_t vertex_cou
   uint8_t *sort_temp, *fill_flag;
   const size_t ne = pad64(E);
   if ((rc = carve(ctx->repair, [&](Carver& c) {
-         topology_layout(c, V, T, &s, &tile_sums, &sort_temp, sort_bytes);
+         topology_layout(c, vertex_count, triangle_count, indices, &s, &tile_sums, &sort_temp, sort_bytes);
          fill_flag = c.take<uint8_t>(ne, 64); fan = c.take<uint32_t>(ne, 64); ordinal = c.take<uint32_t>(ne, 64); fan_offset = c.take<uint32_t>(ne, 64);
        }))) return rc;
-  s.vertices = vertex_count; s.triangles = triangle_count; s.slots = (uint32_t)E; s.bits = vertex_id_bits(V); s.indices = indices;
   if ((rc = repair_clear_words(s.words, stream))) return rc;
   const dim3 block(256);
-  // the position check of bslam_clean_mesh, alone
-  hipLaunchKernelGGL(repair_vertex_kernel, flat_grid(V), block, 0, stream, vertex_count, positions, 0, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                     (uint32_t*)nullptr, (uint32_t*)nullptr, s.words);
+  hipLaunchKernelGGL(mesh_check_positions_kernel, flat_grid(V), block, 0, stream, vertex_count, positions, s.words + kRepairError);
   BSLAM_HIP_TRY(hipGetLastError());
   uint32_t B = 0;
   int at = 0;
@@ -358,7 +332,7 @@ int bslam_fill_mesh_holes(bslam_context* ctx, void* stream_, uint32_t vertex_cou
   }
   const uint32_t* host = nullptr;
   if ((rc = read_back(ctx, stream, (const uint32_t*)s.words, kRepairWords, &host))) return rc;
-  if ((rc = repair_error(host[kRepairError], call))) return rc;
+  if ((rc = mesh_error(host[kRepairError], call))) return rc;
   const size_t filled = host[kRepairFilled], added = host[kRepairFanTriangles], V2 = V + filled, T2 = T + added;
   if (V2 > 0xffffff00ull || T2 > 0xffffff00ull) return fail(BSLAM_ERR_INVALID_ARGUMENT, "%s: the filled mesh has more than 2^32 - 256 vertices or triangles", call);
   if (buffers && V2 <= VC && T2 <= TC) {

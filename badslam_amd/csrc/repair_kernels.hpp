@@ -18,8 +18,6 @@
 
 namespace bslam {
 
-constexpr uint32_t kRepairDegenerate = 16u;   // a bit of the mesh error word: a triangle given to the census repeats an index
-constexpr uint32_t kRepairNone = 0xffffffffu;
 
 // Words of the small device block of a call (u32 units).
 constexpr int kRepairError = 0, kRepairUnique = 1, kRepairVertices = 2, kRepairTriangles = 3, kRepairDegenerates = 4, kRepairDuplicates = 5,
@@ -33,18 +31,12 @@ __device__ __forceinline__ uint32_t repair_bits(float x) {
   return b == 0x80000000u ? 0u : b;
 }
 
-// *word += the number of lanes of the wave that arrive with `flag` set: one atomic per wave.
-__device__ __forceinline__ void repair_count(uint32_t* word, bool flag) {
-  const unsigned long long votes = __ballot(flag);
-  if (flag && (threadIdx.x & 63u) == (uint32_t)__builtin_ctzll(votes)) atomicAdd(word, (uint32_t)__popcll(votes));
-}
-
 // ---------------------------------------------------------------------------------------------
 // Clean.  rep[v] is the representative of v: the smallest vertex id with the same three coordinates, or v without welding.
 // ---------------------------------------------------------------------------------------------
 
 // One vertex per lane: the error bit of a position that is not finite; with `weld` the keys of the two sorts -- z, then y << 32 | x --
-// and id[v] = v; without it rep[v] = v (rep may then be null: the check alone).
+// and id[v] = v; without it rep[v] = v.
 __global__ __launch_bounds__(256) void repair_vertex_kernel(uint32_t vertices, const float* __restrict__ positions, int weld, unsigned long long* __restrict__ key_z,
                                                             unsigned long long* __restrict__ key_yx, uint32_t* __restrict__ ids, uint32_t* __restrict__ rep,
                                                             uint32_t* __restrict__ words) {
@@ -56,27 +48,9 @@ __global__ __launch_bounds__(256) void repair_vertex_kernel(uint32_t vertices, c
     key_z[v] = repair_bits(z);
     key_yx[v] = ((unsigned long long)repair_bits(y) << 32) | repair_bits(x);
     ids[v] = v;
-  } else if (rep != nullptr) {
+  } else {
     rep[v] = v;
   }
-}
-
-// The keys of the second of two stable sorts, in the order the first one left: out[i] = key[ids[i]].
-__global__ __launch_bounds__(256) void repair_gather_kernel(uint32_t count, const unsigned long long* __restrict__ key, const uint32_t* __restrict__ ids,
-                                                            unsigned long long* __restrict__ out) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < count) out[i] = key[ids[i]];
-}
-
-// head[i] = 1 iff sorted position i starts a run of equal keys: the sorted key of the last sort and, where an earlier sort took part
-// of the key, that part of the element itself (first_key, by id; may be null).
-__global__ __launch_bounds__(256) void repair_heads_kernel(uint32_t count, const unsigned long long* __restrict__ sorted_keys, const uint32_t* __restrict__ ids,
-                                                           const unsigned long long* __restrict__ first_key, uint8_t* __restrict__ head) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= count) return;
-  bool h = i == 0 || sorted_keys[i] != sorted_keys[i - 1];
-  if (!h && first_key != nullptr) h = first_key[ids[i]] != first_key[ids[i - 1]];
-  head[i] = h ? 1 : 0;
 }
 
 // first[r] = the element at the head of run r (rank: the inclusive scan of head).  Both sorts are stable, so it is the run's smallest id.
@@ -107,7 +81,7 @@ __global__ __launch_bounds__(256) void repair_triangle_kernel(uint32_t vertices,
   else atomicOr(&words[kRepairError], kMeshBadIndex);
   const bool distinct = valid && a != b && a != c && b != c;
   keep[t] = distinct ? 1 : 0;
-  repair_count(&words[kRepairDegenerates], valid && !distinct);
+  mesh_wave_count(&words[kRepairDegenerates], valid && !distinct);
   if (!duplicates) return;
   const uint32_t lo = min(a, min(b, c)), hi = max(a, max(b, c)), mid = (a ^ b ^ c) ^ lo ^ hi;   // two equal corners cancel: mid is the third
   key_hi[t] = hi;
@@ -125,7 +99,7 @@ __global__ __launch_bounds__(256) void repair_duplicate_kernel(uint32_t triangle
     duplicate = keep[t] != 0;
     if (duplicate) keep[t] = 0;
   }
-  repair_count(&words[kRepairDuplicates], duplicate);
+  mesh_wave_count(&words[kRepairDuplicates], duplicate);
 }
 
 // referenced[rep[corner]] = 1 for the corners of the kept triangles (zero before; every writer writes 1).
@@ -143,65 +117,19 @@ __global__ __launch_bounds__(256) void repair_keep_vertex_kernel(uint32_t vertic
   if (v < vertices) keep_vertex[v] = (rep[v] == v && (all || referenced[v])) ? 1 : 0;
 }
 
-struct RepairClean {
-  uint32_t vertices, triangles, vertex_blocks;
-  const float* positions; const float* normals; const uint32_t* colors;   // normals, colors: may be null
-  const uint32_t* indices;
-  const uint32_t* rep; const uint8_t* keep_vertex; const uint8_t* keep; const uint32_t* vertex_rank; const uint32_t* triangle_rank;
-  float* out_positions; float* out_normals; uint32_t* out_colors; uint32_t* out_indices;
-  uint32_t* vertex_map; uint32_t* triangle_map;                           // may be null
-};
-
-// Blocks [0, vertex_blocks) take a vertex per lane, the others a triangle.  A kept vertex goes to its rank with the bits of its
-// attributes, a kept triangle to its rank with its corners through rep and the ranks, in their order; the maps get the new ids or
-// 0xffffffff.  Nothing at or beyond the kept counts is written.
-__global__ __launch_bounds__(256) void repair_scatter_kernel(RepairClean m) {
-  if (blockIdx.x < m.vertex_blocks) {
-    const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= m.vertices) return;
-    const uint32_t r = m.rep[v];
-    if (m.vertex_map != nullptr) m.vertex_map[v] = m.keep_vertex[r] ? m.vertex_rank[r] : kRepairNone;
-    if (!m.keep_vertex[v]) return;
-    const size_t from = 3 * (size_t)v, to = 3 * (size_t)m.vertex_rank[v];
-    const uint32_t* pos = (const uint32_t*)m.positions;
-    uint32_t* out_pos = (uint32_t*)m.out_positions;
-    out_pos[to] = pos[from]; out_pos[to + 1] = pos[from + 1]; out_pos[to + 2] = pos[from + 2];
-    if (m.normals != nullptr) {
-      const uint32_t* nrm = (const uint32_t*)m.normals;
-      uint32_t* out_nrm = (uint32_t*)m.out_normals;
-      out_nrm[to] = nrm[from]; out_nrm[to + 1] = nrm[from + 1]; out_nrm[to + 2] = nrm[from + 2];
-    }
-    if (m.colors != nullptr) m.out_colors[m.vertex_rank[v]] = m.colors[v];
-    return;
-  }
-  const uint32_t t = (blockIdx.x - m.vertex_blocks) * blockDim.x + threadIdx.x;
-  if (t >= m.triangles) return;
-  if (m.triangle_map != nullptr) m.triangle_map[t] = m.keep[t] ? m.triangle_rank[t] : kRepairNone;
-  if (!m.keep[t]) return;
-  const size_t from = 3 * (size_t)t, to = 3 * (size_t)m.triangle_rank[t];
-  for (int k = 0; k < 3; ++k) m.out_indices[to + k] = m.vertex_rank[m.rep[m.indices[from + k]]];
-}
-
 // ---------------------------------------------------------------------------------------------
-// Topology.  E = 3 T slots.  By sorted position i the undirected edges lie in runs; run r starts at start_of[r] and start_of[U] = E.
-// A boundary slot is the one slot of a run of one; they are numbered in ascending slot (boundary_id, the exclusive scan of their
-// flags), and the loop arrays are indexed by that number.
+// Topology, over the edge runs of mesh_kernels.hpp.  A boundary slot is the one slot of a run of one; they are numbered in ascending
+// slot (boundary_id, the exclusive scan of their flags), and the loop arrays are indexed by that number.
 // ---------------------------------------------------------------------------------------------
 struct RepairTopology {
-  uint32_t vertices, triangles, slots, bits;
-  const uint32_t* indices;
-  unsigned long long *keys, *sorted_keys;     // [E] lo << bits | hi
-  uint32_t *ids, *sorted_slots;               // [E]
-  uint8_t* head; uint32_t* rank;              // [E] by sorted position
-  uint32_t* start_of;                         // [E + 1]
-  uint8_t* referenced;                        // [V]
+  EdgeRuns runs;                              // vertices, triangles, slots, indices; referenced[V] is given
   uint32_t *starts, *ends, *start_slot;       // [V] boundary slots that start / end at v; the smallest that starts there
   uint8_t* boundary; uint32_t* boundary_id;   // [E] by slot
   uint32_t* loop_slot;                        // [B] the slot of a boundary slot's number
   uint32_t *next[2], *label[2]; uint8_t* open[2];   // [B] double buffered
   uint32_t* loop_length;                      // [B] by the number of the loop's smallest slot
   uint32_t* edge_uses; uint32_t* loop_of_slot;      // the caller's, may be null
-  uint32_t* words;
+  uint32_t* words;                            // runs.error = &words[kRepairError]
 };
 
 __device__ __forceinline__ uint32_t repair_slot_end(const uint32_t* __restrict__ indices, uint32_t slot) {
@@ -209,56 +137,30 @@ __device__ __forceinline__ uint32_t repair_slot_end(const uint32_t* __restrict__
   return indices[3 * (size_t)t + (k + 1u) % 3u];
 }
 
-// One triangle per lane: the three edge keys, id[slot] = slot, referenced[corner] = 1.  An index >= V and a repeated index raise
-// their error bits; the call reads the word back before anything is decoded from a key.
-__global__ __launch_bounds__(256) void topology_keys_kernel(RepairTopology s) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= s.triangles) return;
-  const uint32_t i[3] = {s.indices[3 * (size_t)t], s.indices[3 * (size_t)t + 1], s.indices[3 * (size_t)t + 2]};
-  const bool valid = i[0] < s.vertices && i[1] < s.vertices && i[2] < s.vertices;
-  if (!valid) atomicOr(&s.words[kRepairError], kMeshBadIndex);
-  else if (i[0] == i[1] || i[0] == i[2] || i[1] == i[2]) atomicOr(&s.words[kRepairError], kRepairDegenerate);
-  for (int k = 0; k < 3; ++k) {
-    const uint32_t a = i[k], b = i[(k + 1) % 3], lo = a < b ? a : b, hi = a < b ? b : a;
-    const size_t slot = 3 * (size_t)t + k;
-    s.keys[slot] = valid ? ((unsigned long long)lo << s.bits) | hi : ~0ull;
-    s.ids[slot] = (uint32_t)slot;
-    if (valid) s.referenced[a] = 1;
-  }
-}
-
-// start_of[r] = the sorted position at which run r starts, and start_of[U] = E.
-__global__ __launch_bounds__(256) void topology_starts_kernel(RepairTopology s) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= s.slots) return;
-  if (s.head[i]) s.start_of[s.rank[i] - 1u] = i;
-  if (i + 1 == s.slots) s.start_of[s.rank[i]] = s.slots;
-}
-
 // By sorted position: the uses of the slot's edge; at the head of a run the class of the edge, the orientation test of an interior
 // edge -- its two slots start at the same end iff they run the same way -- and for a boundary edge the flag of its slot, the counts
 // at its two ends and the smallest slot that starts at its origin.
 __global__ __launch_bounds__(256) void topology_census_kernel(RepairTopology s) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = i < s.slots;
+  const bool live = i < s.runs.slots;
   uint32_t uses = 0, slot = 0;
   bool head = false;
   if (live) {
-    const uint32_t r = s.rank[i] - 1u;
-    uses = s.start_of[r + 1] - s.start_of[r];
-    slot = s.sorted_slots[i];
-    head = s.head[i] != 0;
+    const uint32_t r = s.runs.rank[i] - 1u;
+    uses = s.runs.start_of[r + 1] - s.runs.start_of[r];
+    slot = s.runs.sorted_slots[i];
+    head = s.runs.head[i] != 0;
     if (s.edge_uses != nullptr) s.edge_uses[slot] = uses;
     s.boundary[slot] = uses == 1 ? 1 : 0;
   }
-  repair_count(&s.words[kRepairBoundary], head && uses == 1);
-  repair_count(&s.words[kRepairInterior], head && uses == 2);
-  repair_count(&s.words[kRepairNonManifold], head && uses >= 3);
+  mesh_wave_count(&s.words[kRepairBoundary], head && uses == 1);
+  mesh_wave_count(&s.words[kRepairInterior], head && uses == 2);
+  mesh_wave_count(&s.words[kRepairNonManifold], head && uses >= 3);
   bool same_way = false;
-  if (head && uses == 2) same_way = s.indices[slot] == s.indices[s.sorted_slots[i + 1]];
-  repair_count(&s.words[kRepairInconsistent], same_way);
+  if (head && uses == 2) same_way = s.runs.indices[slot] == s.runs.indices[s.runs.sorted_slots[i + 1]];
+  mesh_wave_count(&s.words[kRepairInconsistent], same_way);
   if (head && uses == 1) {
-    const uint32_t from = s.indices[slot], to = repair_slot_end(s.indices, slot);
+    const uint32_t from = s.runs.indices[slot], to = repair_slot_end(s.runs.indices, slot);
     atomicAdd(&s.starts[from], 1u);
     atomicAdd(&s.ends[to], 1u);
     atomicMin(&s.start_slot[from], slot);
@@ -269,17 +171,17 @@ __global__ __launch_bounds__(256) void topology_census_kernel(RepairTopology s) 
 // and one that ends there.
 __global__ __launch_bounds__(256) void topology_vertex_kernel(RepairTopology s) {
   const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-  const bool live = v < s.vertices;
-  repair_count(&s.words[kRepairReferenced], live && s.referenced[v]);
-  repair_count(&s.words[kRepairBlocked], live && s.starts[v] + s.ends[v] != 0 && !(s.starts[v] == 1 && s.ends[v] == 1));
+  const bool live = v < s.runs.vertices;
+  mesh_wave_count(&s.words[kRepairReferenced], live && s.runs.referenced[v]);
+  mesh_wave_count(&s.words[kRepairBlocked], live && s.starts[v] + s.ends[v] != 0 && !(s.starts[v] == 1 && s.ends[v] == 1));
 }
 
 // One slot per lane, boundary slots only: next = the number of the boundary slot that starts where this one ends if that vertex is
 // passable; else the walk ends here: next = itself and the slot is open.  label = the slot.
 __global__ __launch_bounds__(256) void topology_loop_init_kernel(RepairTopology s) {
   const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
-  if (slot >= s.slots || !s.boundary[slot]) return;
-  const uint32_t j = s.boundary_id[slot], to = repair_slot_end(s.indices, slot);
+  if (slot >= s.runs.slots || !s.boundary[slot]) return;
+  const uint32_t j = s.boundary_id[slot], to = repair_slot_end(s.runs.indices, slot);
   const bool passable = s.starts[to] == 1 && s.ends[to] == 1;
   s.loop_slot[j] = slot;
   s.next[0][j] = passable ? s.boundary_id[s.start_slot[to]] : j;
@@ -302,7 +204,7 @@ __global__ __launch_bounds__(256) void topology_jump_kernel(RepairTopology s, ui
 __global__ __launch_bounds__(256) void topology_loop_label_kernel(RepairTopology s, uint32_t count, int at) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = j < count, open = live && s.open[at][j] != 0;
-  repair_count(&s.words[kRepairOpenSlots], open);
+  mesh_wave_count(&s.words[kRepairOpenSlots], open);
   if (!live || open) return;
   const uint32_t label = s.label[at][j];
   if (s.loop_of_slot != nullptr) s.loop_of_slot[s.loop_slot[j]] = label;
@@ -316,7 +218,7 @@ __global__ __launch_bounds__(256) void topology_loop_stats_kernel(RepairTopology
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool first = j < count && !s.open[at][j] && s.label[at][j] == s.loop_slot[j];
   const uint32_t length = first ? s.loop_length[j] : 0u;
-  repair_count(&s.words[kRepairLoops], first);
+  mesh_wave_count(&s.words[kRepairLoops], first);
   if (first) {
     atomicAdd(&s.words[kRepairLoopEdges], length);
     atomicMin(&s.words[kRepairLongest], ~length);
@@ -348,8 +250,8 @@ __global__ __launch_bounds__(256) void repair_fill_kernel(RepairTopology s, Repa
   double px = 0.0, py = 0.0, pz = 0.0, nx = 0.0, ny = 0.0, nz = 0.0;
   uint32_t c0 = 0, c1 = 0, c2 = 0, c3 = 0;   // n <= 4096: 4096 * 255 fits
   uint32_t slot = s.loop_slot[j];
-  for (uint32_t k = 0; k < n && slot < s.slots; ++k) {
-    const uint32_t a = s.indices[slot], b = repair_slot_end(s.indices, slot);
+  for (uint32_t k = 0; k < n && slot < s.runs.slots; ++k) {
+    const uint32_t a = s.runs.indices[slot], b = repair_slot_end(s.runs.indices, slot);
     px = px + (double)f.positions[3 * (size_t)a]; py = py + (double)f.positions[3 * (size_t)a + 1]; pz = pz + (double)f.positions[3 * (size_t)a + 2];
     if (f.normals != nullptr) {
       nx = nx + (double)f.normals[3 * (size_t)a]; ny = ny + (double)f.normals[3 * (size_t)a + 1]; nz = nz + (double)f.normals[3 * (size_t)a + 2];

@@ -51,7 +51,7 @@ int bslam_smooth_mesh(bslam_context* ctx, void* stream_, uint32_t vertex_count, 
   const dim3 block(256);
   BSLAM_HIP_TRY(hipMemsetAsync(s.words, 0, kSmoothWords * sizeof(uint32_t), stream));
   if ((rc = ctx->smooth_events.mark(ctx->profiling, stream, 0))) return rc;
-  hipLaunchKernelGGL(smooth_check_kernel, flat_grid(V), block, 0, stream, vertex_count, positions, s.words);
+  hipLaunchKernelGGL(mesh_check_positions_kernel, flat_grid(V), block, 0, stream, vertex_count, positions, s.words + kSmoothError);
   BSLAM_HIP_TRY(hipGetLastError());
   if (T != 0) {
     hipLaunchKernelGGL(smooth_keys_kernel, flat_grid(T), block, 0, stream, s);

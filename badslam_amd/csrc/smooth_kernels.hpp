@@ -42,14 +42,6 @@ struct SmoothState {
 
 __device__ __forceinline__ unsigned long long smooth_dead_pair(uint32_t bits) { return ~0ull >> (64u - 2u * bits); }   // v == u == 2^bits - 1: no live pair
 
-// Raises the error bit for a position that is not finite.
-__global__ __launch_bounds__(256) void smooth_check_kernel(uint32_t vertices, const float* __restrict__ positions, uint32_t* __restrict__ words) {
-  const uint32_t v = blockIdx.x * blockDim.x + threadIdx.x;
-  if (v >= vertices) return;
-  const bool finite = pmd_finite(positions[3 * (size_t)v]) && pmd_finite(positions[3 * (size_t)v + 1]) && pmd_finite(positions[3 * (size_t)v + 2]);
-  if (!finite) atomicOr(&words[kSmoothError], kMeshBadPosition);
-}
-
 // The keys of the two sorts, one triangle per lane.  A triangle with an index >= V raises the error bit and, like one that repeats
 // an index, gets the keys that sort last, so that nothing behind this launch dereferences it.
 __global__ __launch_bounds__(256) void smooth_keys_kernel(SmoothState s) {

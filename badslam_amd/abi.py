@@ -179,6 +179,11 @@ SIGNATURES = {
     "bslam_nearest_triangle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p,
                                          C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
     "bslam_debug_nearest_triangle_tree": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32)]),
+    "bslam_mesh_rays": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_uint32), P(C.c_uint32)]),
+    "bslam_mesh_visibility": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_void_p, P(Camera4f), C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_void_p, P(C.c_uint32),
+                                        P(C.c_uint32)]),
     "bslam_sample_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p,
                                     C.c_void_p, P(C.c_uint64)]),
     "bslam_registration_prepare": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_uint64,

@@ -24,6 +24,7 @@
 #include "mesh_kernels.hpp"
 #include "distance_kernels.hpp"
 #include "bvh_kernels.hpp"
+#include "ray_kernels.hpp"
 #include "registration_kernels.hpp"
 #include "sampling_kernels.hpp"
 #include "simplify_kernels.hpp"
@@ -1469,6 +1470,7 @@ int bslam_debug_pose_residuals(
 #include "orient_abi.inc"
 #include "distance_abi.inc"
 #include "bvh_abi.inc"
+#include "ray_abi.inc"
 #include "sampling_abi.inc"
 #include "registration_abi.inc"
 #include "raycast_abi.inc"

@@ -210,6 +210,7 @@ struct bslam_context {
     void *words = nullptr, *sorted_ids = nullptr, *parent_internal = nullptr, *parent_leaf = nullptr, *box_min = nullptr, *box_max = nullptr;
     void *leaf_lo = nullptr, *leaf_hi = nullptr, *nodes = nullptr, *records = nullptr;
   } bvh_tree;
+  bslam::Slab ray_views;     // bslam_mesh_visibility: float4[4 K], the rows of camera_T_global and the centre of every view
   bslam::Slab sampling;      // bslam_sample_mesh: words | counts u32[T] | offsets u32[T] | scan sums; reserved by its first call
   bslam::Slab simplify;      // bslam_simplify_mesh: words | keys, sorted keys u64[V] | ids, sorted ids, head flags, ranks, clusters [V] | keep flags, ranks [T] |
                              // scan sums | the radix sort's scratch; reserved by its first call

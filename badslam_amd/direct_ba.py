@@ -87,6 +87,9 @@ def host_lib():
     L.bsh_point_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, C.c_float, C.c_uint64, f32p, u32p,
                                           f32p, u64p]
     L.bsh_nearest_triangle.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_float, f32p, u32p, u32p]
+    L.bsh_mesh_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_int, f32p, u32p, f32p, u8p, u8p, u32p]
+    L.bsh_mesh_visibility.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, C.c_uint64, f32p, C.c_uint64, u32p, C.c_uint64, f32p, f32p, f32p, C.c_int, C.c_int,
+                                      f32p, u32p, u32p, u32p]
     L.bsh_surfel_mesh_distance.argtypes = [C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_uint64, u64p, f32p, u64p]
     L.bsh_distance_copy.argtypes = [f32p, u32p]
     L.bsh_simplify_mesh.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, f32p, f32p, u8p, C.c_uint64, u32p, f32p, C.c_float, u64p]
@@ -152,6 +155,32 @@ def se3f_from7(p):
     for i in range(3):
         T.t[i] = float(p[4 + i])
     return T
+
+
+def pose_matrix(pose):
+    """global_T_camera as a 4 x 4 float64 matrix: of an abi.SE3f (unit quaternion x y z w and translation), or of anything that
+    already is 4 x 4."""
+    if isinstance(pose, abi.SE3f):
+        x, y, z, w = (float(v) for v in pose.q)
+        M = np.eye(4)
+        M[:3, :3] = [[1 - 2 * (y * y + z * z), 2 * (x * y - z * w), 2 * (x * z + y * w)],
+                     [2 * (x * y + z * w), 1 - 2 * (x * x + z * z), 2 * (y * z - x * w)],
+                     [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]]
+        M[:3, 3] = [float(v) for v in pose.t]
+        return M
+    return np.asarray(pose, np.float64).reshape(4, 4)
+
+
+def view_rows(poses):
+    """The views of MeshVisibility from global_T_camera poses (abi.SE3f or 4 x 4): (camera_T_global (K, 3, 4) f32 -- the inverse
+    R^T | -R^T t formed in float64 and rounded -- and centres (K, 3) f32, the translations rounded)."""
+    rows, centres = np.zeros((len(poses), 3, 4), np.float32), np.zeros((len(poses), 3), np.float32)
+    for k, pose in enumerate(poses):
+        M = pose_matrix(pose)
+        rows[k, :, :3] = M[:3, :3].T
+        rows[k, :, 3] = -(M[:3, :3].T @ M[:3, 3])
+        centres[k] = M[:3, 3]
+    return rows, centres
 
 
 # ---- loop closure (badslam_amd/host/pose_graph.hpp, loop_closure.hpp) ------------------------------------------
@@ -1038,6 +1067,59 @@ class DirectBA:
         self._check(self.L.bsh_nearest_triangle(self._ba, self.stream, len(pts), _f(pts), len(pos), _f(pos), len(tri), _u32(tri),
                                                 float("inf") if max_distance is None else float(max_distance), _f(distance), _u32(triangle), tree))
         return dict(distance=distance, triangle=triangle, leaves=int(tree[0]), height=int(tree[1]))
+
+    # --- mesh rays (bslam_mesh_rays, bslam_mesh_visibility)
+    def RayCastMesh(self, origins, directions, mesh, t_min=0.0, t_max=None, any_hit=False):
+        """What every ray origins[i] + t * directions[i] ((n, 3) each; directions need not be normalised, t is in their units) hits
+        on `mesh` (the dict of ExtractMesh or LoadPLY) for t in [t_min, t_max] -- scalars or (n,) arrays; t_max None: +inf.  Both
+        faces hit.  -> dict of t (n,) f32 (+inf: a miss), triangle (n,) u32 (0xFFFFFFFF), uv (n, 2) f32 (the hit is (1 - u - v) a +
+        u b + v c), front (n,) bool (the ray meets the counter-clockwise side), leaves and height of the tree; with any_hit=True a
+        dict of hit (n,) bool, leaves, height: whether anything is hit, which is cheaper and all an occlusion test needs.  The bits
+        are those of the rule in include/badslam_hip.h "Mesh rays": among equal t the lowest triangle."""
+        org = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+        dirs = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        if len(org) != len(dirs):
+            raise ValueError("RayCastMesh: one direction per origin")
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        n = len(org)
+        t_range = None
+        if np.ndim(t_min) != 0 or np.ndim(t_max) != 0 or float(t_min) != 0.0 or t_max is not None:
+            t_range = np.empty((n, 2), np.float32)
+            t_range[:, 0] = t_min
+            t_range[:, 1] = np.inf if t_max is None else t_max
+        tree = (C.c_uint32 * 2)()
+        if any_hit:
+            hit = np.zeros(n, np.uint8)
+            self._check(self.L.bsh_mesh_rays(self._ba, self.stream, n, _f(org), _f(dirs), None if t_range is None else _f(t_range), len(pos), _f(pos), len(tri),
+                                             _u32(tri), 1, None, None, None, None, _u8(hit), tree))
+            return dict(hit=hit.astype(bool), leaves=int(tree[0]), height=int(tree[1]))
+        t, triangle, uv, front = np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+        self._check(self.L.bsh_mesh_rays(self._ba, self.stream, n, _f(org), _f(dirs), None if t_range is None else _f(t_range), len(pos), _f(pos), len(tri),
+                                         _u32(tri), 0, _f(t), _u32(triangle), _f(uv), _u8(front), None, tree))
+        return dict(t=t, triangle=triangle, uv=uv, front=front.astype(bool), leaves=int(tree[0]), height=int(tree[1]))
+
+    def MeshVisibility(self, points, mesh, poses, camera=None, min_depth=0.05, max_depth=50.0, margin=0.02, normals=None):
+        """From how many of the views `poses` (global_T_camera each, as for RenderMesh: abi.SE3f, or 4 x 4 matrices) every point
+        (n, 3) is seen past `mesh`: inside the view's image (`camera`, abi.Camera4f, default the depth camera) at a depth in
+        [min_depth, max_depth], facing it if `normals` (n, 3) are given, and with nothing of the mesh on the segment from the
+        camera centre to the point short of `margin` before it.  -> dict of count (n,) u32, first (n,) u32 (the lowest view that
+        sees the point, 0xFFFFFFFF for none), leaves, height.  view_rows(poses) are the views the kernel is given."""
+        pts = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        nrm = None if normals is None else np.ascontiguousarray(normals, np.float32).reshape(-1, 3)
+        if nrm is not None and len(nrm) != len(pts):
+            raise ValueError("MeshVisibility: one normal per point")
+        pos = np.ascontiguousarray(mesh["positions"], np.float32).reshape(-1, 3)
+        tri = mesh.get("triangles")
+        tri = np.zeros((0, 3), np.uint32) if tri is None else np.ascontiguousarray(tri, np.uint32).reshape(-1, 3)
+        params, w, h = self._view_camera(camera)
+        rows, centres = view_rows(list(poses))
+        options = np.array([min_depth, max_depth, margin], np.float32)
+        count, first, tree = np.zeros(len(pts), np.uint32), np.zeros(len(pts), np.uint32), (C.c_uint32 * 2)()
+        self._check(self.L.bsh_mesh_visibility(self._ba, self.stream, len(pts), _f(pts), None if nrm is None else _f(nrm), len(pos), _f(pos), len(tri), _u32(tri),
+                                               len(rows), _f(rows), _f(centres), _f(params), w, h, _f(options), _u32(count), _u32(first), tree))
+        return dict(count=count, first=first, leaves=int(tree[0]), height=int(tree[1]))
 
     def SurfelMeshDistance(self, max_distance, cell_size=None, max_grid_entries=1 << 28):
         """PointMeshDistance of the centres of the valid surfels (the positions of ExportToPointCloud, in its order) against the mesh

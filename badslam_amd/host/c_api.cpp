@@ -532,6 +532,47 @@ int bsh_nearest_triangle(void* ba, void* stream, uint64_t point_count, const flo
     if (tree2) { tree2[0] = result.leaves; tree2[1] = result.height; }
   });
 }
+// DirectBA::RayCastMesh of host arrays: origins, directions 3 per ray, t_range 2 per ray or null; any_hit 0 fills t, triangle, uv (2 per
+// ray) and front, any_hit 1 fills hit; the arrays of the other mode are not touched; tree2 = {leaves, height}.
+int bsh_mesh_rays(void* ba, void* stream, uint64_t ray_count, const float* origins, const float* directions, const float* t_range, uint64_t vertices,
+                  const float* positions, uint64_t triangles, const uint32_t* indices, int any_hit, float* t, uint32_t* triangle, float* uv, uint8_t* front, uint8_t* hit,
+                  uint32_t* tree2) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    mesh.indices.assign(indices, indices + 3 * triangles);
+    DirectBA::RayCastResult result;
+    static_cast<DirectBA*>(ba)->RayCastMesh(static_cast<hipStream_t>(stream), origins, directions, t_range, ray_count, mesh, any_hit != 0, &result);
+    copy_out(t, result.t);
+    copy_out(triangle, result.triangle);
+    copy_out(uv, result.uv);
+    copy_out(front, result.front);
+    copy_out(hit, result.hit);
+    if (tree2) { tree2[0] = result.leaves; tree2[1] = result.height; }
+  });
+}
+// DirectBA::MeshVisibility of host arrays: points and (or null) normals 3 per point, camera_T_global 12 per view (row-major 3 x 4),
+// centres 3 per view, camera_params4 = fx fy cx cy, options3 = min_depth, max_depth, margin; count and first one per point.
+int bsh_mesh_visibility(void* ba, void* stream, uint64_t point_count, const float* points, const float* normals, uint64_t vertices, const float* positions,
+                        uint64_t triangles, const uint32_t* indices, uint64_t views, const float* camera_T_global, const float* centres, const float* camera_params4,
+                        int width, int height, const float* options3, uint32_t* count, uint32_t* first, uint32_t* tree2) {
+  BSH_TRY({
+    DirectBA::Mesh mesh;
+    mesh.positions.assign(positions, positions + 3 * vertices);
+    mesh.indices.assign(indices, indices + 3 * triangles);
+    std::vector<bslam_mat3x4> rows(views);
+    for (uint64_t k = 0; k < views; ++k) std::memcpy(rows[k].m, camera_T_global + 12 * k, sizeof(rows[k].m));
+    const std::vector<float> centre(centres, centres + 3 * views);
+    DirectBA::VisibilityOptions options;
+    options.min_depth = options3[0]; options.max_depth = options3[1]; options.margin = options3[2];
+    DirectBA::VisibilityResult result;
+    static_cast<DirectBA*>(ba)->MeshVisibility(static_cast<hipStream_t>(stream), points, normals, point_count, mesh, rows, centre, PinholeCamera4f(width, height, camera_params4),
+                                               options, &result);
+    copy_out(count, result.count);
+    copy_out(first, result.first);
+    if (tree2) { tree2[0] = result.leaves; tree2[1] = result.height; }
+  });
+}
 // DirectBA::SurfelMeshDistance in two steps, like the mesh: the call keeps its result for this thread and reports *count (the
 // valid surfels), *cell_used and grid2; bsh_distance_copy copies distance and triangle out (`count` entries each) and drops it.
 static thread_local DirectBA::PointMeshResult g_distance;

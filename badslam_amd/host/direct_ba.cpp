@@ -705,6 +705,76 @@ void DirectBA::NearestTriangle(hipStream_t stream, const float* points, size_t p
   Wait(stream);
 }
 
+void DirectBA::RayCastMesh(hipStream_t stream, const float* origins, const float* directions, const float* t_range, size_t ray_count, const Mesh& mesh, bool any_hit,
+                           RayCastResult* result) {
+  CheckMeshSizes(mesh, "RayCastMesh", kMeshPositions | kMeshIndices, ray_count);
+  const u32 n = static_cast<u32>(ray_count);
+  DeviceArray<float> dev_origins(3 * ray_count), dev_directions(3 * ray_count), dev_range(t_range ? 2 * ray_count : 0);
+  dev_origins.Upload(stream, origins, 3 * ray_count);
+  dev_directions.Upload(stream, directions, 3 * ray_count);
+  if (t_range) dev_range.Upload(stream, t_range, 2 * ray_count);
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshIndices);   // its wait covers the rays
+  *result = RayCastResult();
+  const float* range = t_range ? dev_range.address() : nullptr;
+  if (any_hit) {
+    DeviceArray<uint8_t> hit(n);
+    result->hit.assign(n, 0);
+    Check(bslam_mesh_rays(ctx_, stream, n, dev_origins.address(), dev_directions.address(), range, m.vertices, m.positions->address(), m.triangles, m.indices->address(),
+                          BSLAM_RAYS_ANY, nullptr, nullptr, nullptr, nullptr, hit.address(), &result->leaves, &result->height), "bslam_mesh_rays");
+    hit.Download(stream, result->hit.data(), n);
+  } else {
+    DeviceArray<float> t(n), uv(2 * ray_count);
+    DeviceArray<u32> triangle(n);
+    DeviceArray<uint8_t> front(n);
+    result->t.assign(n, 0.f);
+    result->uv.assign(2 * ray_count, 0.f);
+    result->triangle.assign(n, 0u);
+    result->front.assign(n, 0);
+    Check(bslam_mesh_rays(ctx_, stream, n, dev_origins.address(), dev_directions.address(), range, m.vertices, m.positions->address(), m.triangles, m.indices->address(),
+                          BSLAM_RAYS_CLOSEST, t.address(), triangle.address(), uv.address(), front.address(), nullptr, &result->leaves, &result->height), "bslam_mesh_rays");
+    t.Download(stream, result->t.data(), n);
+    uv.Download(stream, result->uv.data(), 2 * ray_count);
+    triangle.Download(stream, result->triangle.data(), n);
+    front.Download(stream, result->front.data(), n);
+  }
+  Wait(stream);
+}
+
+void DirectBA::MeshVisibility(hipStream_t stream, const float* points, const float* normals, size_t point_count, const Mesh& mesh,
+                              const std::vector<bslam_mat3x4>& camera_T_global, const std::vector<float>& centres, const PinholeCamera4f& camera,
+                              const VisibilityOptions& options, VisibilityResult* result) {
+  CheckMeshSizes(mesh, "MeshVisibility", kMeshPositions | kMeshIndices, point_count);
+  if (centres.size() != 3 * camera_T_global.size()) throw std::invalid_argument("MeshVisibility: one centre (3 floats) per view");
+  if (camera_T_global.size() > BSLAM_MESH_VISIBILITY_MAX_VIEWS) throw std::invalid_argument("MeshVisibility: too many views");
+  const u32 n = static_cast<u32>(point_count);
+  DeviceArray<float> dev_points(3 * point_count), dev_normals(normals ? 3 * point_count : 0);
+  dev_points.Upload(stream, points, 3 * point_count);
+  if (normals) dev_normals.Upload(stream, normals, 3 * point_count);
+  const DeviceMesh m = UploadMesh(stream, mesh, nullptr, kMeshPositions | kMeshIndices);   // its wait covers the points
+  *result = VisibilityResult();
+  result->count.assign(n, 0u);
+  result->first.assign(n, 0u);
+  DeviceArray<u32> count(n), first(n);
+  const bslam_camera4f cam = camera.pod();
+  Check(bslam_mesh_visibility(ctx_, stream, n, dev_points.address(), normals ? dev_normals.address() : nullptr, m.vertices, m.positions->address(), m.triangles,
+                              m.indices->address(), static_cast<u32>(camera_T_global.size()), camera_T_global.data(), centres.data(), &cam, options.min_depth,
+                              options.max_depth, options.margin, count.address(), first.address(), &result->leaves, &result->height), "bslam_mesh_visibility");
+  count.Download(stream, result->count.data(), n);
+  first.Download(stream, result->first.data(), n);
+  Wait(stream);
+}
+
+void DirectBA::MeshVisibility(hipStream_t stream, const float* points, const float* normals, size_t point_count, const Mesh& mesh, const std::vector<SE3f>& global_T_camera,
+                              const PinholeCamera4f& camera, const VisibilityOptions& options, VisibilityResult* result) {
+  std::vector<bslam_mat3x4> views;
+  std::vector<float> centres;
+  for (const SE3f& pose : global_T_camera) {
+    views.push_back(pose.Inverse().Matrix3x4());
+    centres.insert(centres.end(), {pose.tx, pose.ty, pose.tz});
+  }
+  MeshVisibility(stream, points, normals, point_count, mesh, views, centres, camera, options, result);
+}
+
 std::vector<float> DirectBA::ValidSurfelCentres(hipStream_t stream) const {
   std::vector<float> centres;
   const size_t n = surfels_size_;

@@ -418,6 +418,30 @@ class DirectBA {
     u32 leaves = 0, height = 0;
   };
   void NearestTriangle(hipStream_t stream, const float* points, size_t point_count, const Mesh& mesh, float max_distance, NearestTriangleResult* result);
+  // Mesh rays (bslam_mesh_rays): what each of ray_count rays (host arrays: origins and directions float[3 n], t_range float[2 n] or
+  // null for [0, +inf]) hits on `mesh`.  Closest hit fills t (+inf: a miss), triangle (0xffffffff), uv and front; any_hit fills hit alone.
+  struct RayCastResult {
+    std::vector<float> t, uv;
+    std::vector<u32> triangle;
+    std::vector<uint8_t> front, hit;
+    u32 leaves = 0, height = 0;
+  };
+  void RayCastMesh(hipStream_t stream, const float* origins, const float* directions, const float* t_range, size_t ray_count, const Mesh& mesh, bool any_hit,
+                   RayCastResult* result);
+  // Visible points (bslam_mesh_visibility): from how many of the views each point (host arrays: points and, or null, normals
+  // float[3 n]) is seen past `mesh`, and the lowest such view (0xffffffff: none).  A view is camera_T_global and its centre, the
+  // translation of global_T_camera; the second form derives both from global_T_camera poses as RenderMesh does.
+  struct VisibilityOptions {
+    float min_depth = 0.05f, max_depth = 50.f, margin = 0.02f;
+  };
+  struct VisibilityResult {
+    std::vector<u32> count, first;
+    u32 leaves = 0, height = 0;
+  };
+  void MeshVisibility(hipStream_t stream, const float* points, const float* normals, size_t point_count, const Mesh& mesh, const std::vector<bslam_mat3x4>& camera_T_global,
+                      const std::vector<float>& centres, const PinholeCamera4f& camera, const VisibilityOptions& options, VisibilityResult* result);
+  void MeshVisibility(hipStream_t stream, const float* points, const float* normals, size_t point_count, const Mesh& mesh, const std::vector<SE3f>& global_T_camera,
+                      const PinholeCamera4f& camera, const VisibilityOptions& options, VisibilityResult* result);
   // The centres of the valid surfels (the points of ExportToPointCloud, in its order) against the mesh the last ExtractMesh
   // returned, which stays on the device for this: how far the surfels that bundle adjustment optimised lie from the surface the
   // volume produced -- a consistency figure that needs no ground truth.  Throws std::logic_error if no mesh was extracted.

@@ -25,9 +25,17 @@ evaluate(max_distance=None) measures without a search radius (DirectBA.NearestTr
 hierarchy in place of the grid), and deviation() uses the same call to say how far a mesh operator moved a surface: mean, rmse and
 maximum from a mesh to its reference and back, and the Hausdorff distance.
 
+evaluate(visible_from=...) restricts completeness and recall to the part of the ground truth the sensor could have observed, as
+the published surface benchmarks do: an RGB-D run never sees the back of a cupboard or the room next door, and recall over the
+whole scan is dominated by such surface.  The completeness query points are tested against the ground-truth mesh from the given
+keyframe poses (DirectBA.MeshVisibility, bslam_mesh_visibility: inside a view's image and depth range, facing it, and not occluded),
+and only those seen from at least min_views views count.
+
 distance_summary is pure NumPy; evaluate and deviation need a DirectBA for the distance calls.
 """
 import numpy as np
+
+VISIBILITY_MARGIN = 0.02      # the default margin of DirectBA.MeshVisibility
 
 
 def _percentile(sorted_values, q):
@@ -70,7 +78,7 @@ def _has_triangles(mesh):
 
 
 def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.01, 0.02, 0.05), cell_size=None, register=False, initial=None,
-             sample_density=None, sample_seed=0):
+             sample_density=None, sample_seed=0, visible_from=None):
     """reconstruction, ground_truth: mesh dicts (positions (V, 3), triangles (T, 3); DirectBA.ExtractMesh, LoadPLY) in one frame; the
     ground truth may be a point cloud (no or empty triangles).  -> dict of accuracy and completeness (distance_summary each),
     f_scores (a list per threshold), max_distance and the grids the two calls used.  Both are measured at the vertices unless
@@ -86,46 +94,87 @@ def evaluate(ba, reconstruction, ground_truth, max_distance=0.1, thresholds=(0.0
     is applied to a copy of the reconstruction's positions (in float64, then rounded to float32), and that copy is evaluated.  The
     result then also has `registration`: target_T_source (4 x 4 as nested lists), iterations, converged, reason, history, and
     `before`, the accuracy and completeness summaries under `initial` alone.  The registration itself runs on the reconstruction's
-    vertices; the sampling arguments apply to the evaluations before and after it."""
+    vertices; the sampling arguments apply to the evaluations before and after it.
+    visible_from: a dict of `poses` (global_T_camera of the views, as for DirectBA.MeshVisibility, in the reconstruction's frame)
+    and optionally camera, min_depth, max_depth, margin (DirectBA.MeshVisibility's arguments and defaults) and min_views (1).  The
+    completeness query points -- vertices or samples of the ground truth, the samples with their normals -- are tested against the
+    ground-truth mesh, and `completeness` and the recall in f_scores are taken over the points seen from at least min_views views.
+    The result then also has completeness_all, the summary over all points, and `visibility`: views, points, visible_points,
+    visible_fraction, margin, min_views.  A ground truth without triangles is a ValueError.  With register=True the poses are moved
+    by the motion in force (`initial` for `before`, the one found for the result) before the test.  Accuracy is untouched."""
     sampled = {} if sample_density is None else dict(sample_density=sample_density, sample_seed=sample_seed)
+    if visible_from is not None:
+        if "poses" not in visible_from or set(visible_from) - {"poses", "camera", "min_depth", "max_depth", "margin", "min_views"}:
+            raise ValueError("evaluate: visible_from needs poses and may hold camera, min_depth, max_depth, margin and min_views")
+        if not _has_triangles(ground_truth):
+            raise ValueError("evaluate: visible_from needs a ground truth with triangles (occlusion is tested against its mesh)")
     if register and max_distance is None:
         raise ValueError("evaluate: register=True needs a finite max_distance (the registration's search radius)")
     if register:
         start = np.eye(4) if initial is None else np.asarray(initial, np.float64).reshape(4, 4)
+        moved_views = lambda T: {} if visible_from is None else dict(visible_from=dict(visible_from, poses=transform_poses(visible_from["poses"], T)))
         before = evaluate(ba, dict(reconstruction, positions=transform_positions(reconstruction["positions"], start)), ground_truth, max_distance, thresholds, cell_size,
-                          **sampled)
+                          **sampled, **moved_views(start))
         found = ba.RegisterPoints(reconstruction["positions"], ground_truth, max_distance, initial=start, cell_size=cell_size)
         moved = dict(reconstruction, positions=transform_positions(reconstruction["positions"], found["target_T_source"]))
-        result = evaluate(ba, moved, ground_truth, max_distance, thresholds, cell_size, **sampled)
+        result = evaluate(ba, moved, ground_truth, max_distance, thresholds, cell_size, **sampled, **moved_views(found["target_T_source"]))
         result["registration"] = dict(target_T_source=np.asarray(found["target_T_source"], np.float64).tolist(), iterations=found["iterations"],
                                       converged=found["converged"], reason=found["reason"], history=found["history"],
                                       before=dict(accuracy=before["accuracy"], completeness=before["completeness"]))
         return result
-    queries, counts = [], []
+    queries, counts, query_normals = [], [], None
     for side in (reconstruction, ground_truth):
         if sample_density is not None and _has_triangles(side):
-            queries.append(ba.SampleMesh(side, density=sample_density, seed=sample_seed)["positions"])
+            samples = ba.SampleMesh(side, density=sample_density, seed=sample_seed)
+            queries.append(samples["positions"])
             counts.append(int(len(queries[-1])))
+            query_normals = samples.get("normals")   # of the last side, the ground truth, when it was sampled
         else:
             queries.append(side["positions"])
             counts.append(None)
+            query_normals = None
+    visible = None
+    if visible_from is not None:
+        options = {k: visible_from[k] for k in ("camera", "min_depth", "max_depth", "margin") if k in visible_from}
+        min_views = int(visible_from.get("min_views", 1))
+        seen = ba.MeshVisibility(queries[1], ground_truth, visible_from["poses"], normals=query_normals, **options)
+        visible = np.asarray(seen["count"]) >= min_views
+        points = int(len(visible))
+        visibility = dict(views=int(len(visible_from["poses"])), points=points, visible_points=int(visible.sum()),
+                          visible_fraction=float(visible.sum() / points) if points else float("nan"), margin=float(visible_from.get("margin", VISIBILITY_MARGIN)),
+                          min_views=min_views)
     if max_distance is None:   # no radius: the tree, and every point of a side hits whatever the other side holds
         acc = ba.NearestTriangle(queries[0], ground_truth)
         com = ba.NearestTriangle(queries[1], reconstruction)
-        accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
+        accuracy, completeness = distance_summary(acc["distance"], thresholds), _completeness(com["distance"], thresholds, visible)
         tree = lambda r: dict(leaves=r["leaves"], height=r["height"])
         result = dict(max_distance=None, accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
                       accuracy_tree=tree(acc), completeness_tree=tree(com))
     else:
         acc = ba.PointMeshDistance(queries[0], ground_truth, max_distance, cell_size)
         com = ba.PointMeshDistance(queries[1], reconstruction, max_distance, cell_size)
-        accuracy, completeness = distance_summary(acc["distance"], thresholds), distance_summary(com["distance"], thresholds)
+        accuracy, completeness = distance_summary(acc["distance"], thresholds), _completeness(com["distance"], thresholds, visible)
         grid = lambda r: dict(cell_size=r["cell_size"], grid_cells=r["grid_cells"], grid_entries=r["grid_entries"])
         result = dict(max_distance=float(max_distance), accuracy=accuracy, completeness=completeness, f_scores=f_scores(accuracy, completeness),
                       accuracy_grid=grid(acc), completeness_grid=grid(com))
     if sample_density is not None:
         result["sampling"] = dict(density=float(sample_density), seed=int(sample_seed), reconstruction_samples=counts[0], ground_truth_samples=counts[1])
+    if visible is not None:
+        result["completeness_all"] = distance_summary(com["distance"], thresholds)
+        result["visibility"] = visibility
     return result
+
+
+def _completeness(distance, thresholds, visible):
+    """The summary of the completeness distances: of all points, or of those flagged visible."""
+    return distance_summary(distance if visible is None else np.asarray(distance).reshape(-1)[visible], thresholds)
+
+
+def transform_poses(poses, T):
+    """global_T_camera poses (abi.SE3f or 4 x 4) moved by T (4 x 4, new_T_global): 4 x 4 float64 matrices."""
+    from .direct_ba import pose_matrix
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return [T @ pose_matrix(pose) for pose in poses]
 
 
 def _deviation_side(distance):

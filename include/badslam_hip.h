@@ -1092,6 +1092,80 @@ int bslam_nearest_triangle(bslam_context* ctx, void* stream, uint32_t point_coun
 int bslam_debug_nearest_triangle_tree(bslam_context* ctx, uint32_t leaf_capacity, uint32_t* parent, uint32_t* children, float* boxes,
                                       uint32_t* leaf_triangle, uint32_t* leaves);
 
+/* Mesh rays: what a ray hits on an indexed mesh -- the closest hit, or whether there is any -- and from how many views a point is
+ * seen (DESIGN.md 8 "Mesh rays", csrc/ray_kernels.hpp), over the tree of "Nearest triangle".  Every value is fp32 in the order
+ * written; nothing is contracted; `/` and sqrtf are correctly rounded; dot is that of "Surface evaluation".  The result is a
+ * function of this rule alone, not of the tree's shape, the traversal order or the width of the Morton code: a brute-force
+ * restatement over all N x T pairs reproduces every bit.
+ * Ray:
+ *   origin o, direction d (not normalised: t is in units of d), interval [t_min, t_max].  A ray misses everything if one of its
+ *   six components is not finite, if d == (0, 0, 0), if a bound is a NaN or if t_min > t_max; infinite bounds are legal.
+ *   Triangles are valid as in "Nearest triangle" (nine finite coordinates) and an index >= vertex_count is handled as there.
+ * Per ray:
+ *   kz = the axis of the largest |d.a| (of equals the first of x, y, z), kx = kz + 1, ky = kz + 2 (mod 3), swapped if d[kz] < 0;
+ *   Sx = d[kx] / d[kz], Sy = d[ky] / d[kz], Sz = 1 / d[kz];  inv.a = 1 / d.a on each axis.
+ * Triangle test (Woop, Benthin, Wald 2013), vertices a, b, c:
+ *   A = a - o;  Ax = A[kx] - Sx * A[kz], Ay = A[ky] - Sy * A[kz], Az = Sz * A[kz];  B and C alike.
+ *   U = Cx * By - Cy * Bx,  V = Ax * Cy - Ay * Cx,  W = Bx * Ay - By * Ax: differences of two rounded products, so each changes
+ *   its sign exactly when its edge is taken the other way round.  If U, V or W is exactly 0, all three are formed again in float64
+ *   from the same six fp32 numbers (the products are then exact, the difference has the exact sign); the signs are read from
+ *   those and U, V, W are their roundings to fp32.  (A nonzero fp32 value already has the exact sign: rounding is monotone.)
+ *   The test accepts iff not (one of U, V, W is < 0 and one is > 0), and det = (U + V) + W is not 0, and
+ *   t_tri = ((U * Az + V * Bz) + W * Cz) / det is no NaN.  u = V / det, v = W / det: the hit point is (1 - u - v) a + u b + v c.
+ *   Both faces hit; front = det > 0: the ray meets the side from which a, b, c run counter-clockwise, the front of
+ *   bslam_render_mesh.  Two triangles that share an edge or a vertex evaluate the shared edge function from bit-identical
+ *   numbers, so no ray passes between them.
+ * Slab:
+ *   slab(ray, box) = (enter, exit).  On an axis with d.a == 0 the interval is (-inf, +inf) if lo.a <= o.a <= hi.a, else empty
+ *   (+inf, -inf): no 0 x inf is ever formed there, and an origin exactly on a box plane is inside.  On any other axis
+ *   t0 = (lo.a - o.a) * inv.a, t1 = (hi.a - o.a) * inv.a, and the interval is (min(t0, t1), max(t0, t1)) -- or (-inf, +inf) if
+ *   one of the two is a NaN, which only 0 x inf can give (d.a subnormal, the origin on the plane).  enter = the largest of the
+ *   three lower ends moved BSLAM_RAY_PAD_ULPS representable floats down, exit = the smallest of the upper ends moved as many up
+ *   (-0 counts as +0; an infinity is never passed).  The slab is empty iff enter > exit.  It is monotone under inclusion of boxes
+ *   as floats: for A inside B, enter(B) <= enter(A) and exit(A) <= exit(B).
+ * Pair:
+ *   hit(ray, t) iff the test accepts, slab(ray, box(t)) is not empty, and t_hit = min(max(t_tri, enter), exit) is finite and
+ *   t_min <= t_hit <= t_max.  The slab is part of the value: the clamp makes pruning exact as b2 does in "Nearest triangle", and
+ *   the padding keeps the slab from rejecting what the test accepts (axis-aligned triangles have boxes of zero thickness).
+ * Closest hit: the smallest t_hit, among bit-equal ones the lowest triangle.  Any hit: whether some valid triangle hits; no
+ *   triangle is returned, because which one is found first depends on the tree.
+ * Why pruning is exact: a subtree is skipped iff the slab of its node's box is empty, or enter > min(best so far, t_max), or
+ *   exit < t_min, and is entered on equality.  By monotonicity [enter, exit] of every triangle below lies inside the node's, and
+ *   t_hit lies inside the triangle's: nothing that could be the result, or tie with it, is ever skipped.
+ * bslam_mesh_rays: origins and directions float[3 N], t_range float[2 N] = (t_min, t_max) per ray or null for [0, +inf],
+ * positions, indices as in bslam_nearest_triangle -- all device arrays, 4 byte aligned (the two byte arrays too), no output
+ * overlapping anything, at most 2^32 - 256 rays or triangles.  mode BSLAM_RAYS_CLOSEST needs out_t float[N]; out_triangle
+ * uint32[N], out_uv float[2 N] and out_front uint8[N] may be null; out_hit must be null.  A miss gives t = +INFINITY, triangle
+ * 0xffffffff, uv = 0, front = 0.  mode BSLAM_RAYS_ANY needs out_hit uint8[N] (1 or 0) and every other output null.  N == 0 and
+ * T == 0 are legal.  Both calls build the tree as bslam_nearest_triangle does and leave it for
+ * bslam_debug_nearest_triangle_tree; *leaves and *height (host, may be null) as there.  While profiling is on,
+ * bslam_debug_cull_stats counts the nodes fetched as `tested` and the triangles evaluated as tested - culled.  Both synchronise
+ * `stream`.
+ * bslam_mesh_visibility: for N points (device float[3 N]; normals device float[3 N] or null) and K views (HOST arrays:
+ * camera_T_global[K] and centres float[3 K], the translation of each global_T_camera -- the kernel derives nothing in between),
+ * point p is seen from view k iff
+ *   L = camera_T_global[k] . p in the row expression of bslam_render_mesh, ((m0 x + m1 y) + m2 z) + m3, has
+ *   min_depth <= L.z <= max_depth, and px = fx * (L.x / L.z) + cx, py alike, have 0 <= px < width and 0 <= py < height;
+ *   and, if normals are given, dot(n, d) < 0 for d = p - centres[k];
+ *   and the ray o = centres[k], d, [0, 1 - margin / sqrtf(dot(d, d))] has no hit.  An interval that is empty, or a ray that is
+ *   not valid, hits nothing.
+ * out_count uint32[N] = the number of views that see p, out_first uint32[N] (may be null) = the lowest of them, 0xffffffff for
+ * none.  Refused without a launch: depth bounds or a margin that are not finite, min_depth > max_depth, margin < 0, a camera
+ * outside the limits of bslam_render_surfels, more than BSLAM_MESH_VISIBILITY_MAX_VIEWS views.  With K == 0 all counts are 0. */
+#define BSLAM_RAY_PAD_ULPS 4
+#define BSLAM_RAYS_CLOSEST 0
+#define BSLAM_RAYS_ANY 1
+#define BSLAM_MESH_VISIBILITY_MAX_VIEWS 65536u
+int bslam_mesh_rays(bslam_context* ctx, void* stream, uint32_t ray_count, const float* origins, const float* directions,
+                    const float* t_range, uint32_t vertex_count, const float* positions, uint32_t triangle_count,
+                    const uint32_t* indices, int mode, float* out_t, uint32_t* out_triangle, float* out_uv, uint8_t* out_front,
+                    uint8_t* out_hit, uint32_t* leaves, uint32_t* height);
+int bslam_mesh_visibility(bslam_context* ctx, void* stream, uint32_t point_count, const float* points, const float* normals,
+                          uint32_t vertex_count, const float* positions, uint32_t triangle_count, const uint32_t* indices,
+                          uint32_t view_count, const bslam_mat3x4* camera_T_global, const float* centres,
+                          const bslam_camera4f* camera, float min_depth, float max_depth, float margin, uint32_t* out_count,
+                          uint32_t* out_first, uint32_t* leaves, uint32_t* height);
+
 /* Surface sampling: points drawn uniformly by area from an indexed mesh, so that what is measured at them does not depend on how
  * the mesh happens to be tessellated (DESIGN.md 8 "Surface sampling", csrc/sampling_kernels.hpp).  Integers are uint32 with
  * wrap-around; floats are fp32, nothing is contracted implicitly, and dot, cross, `/` and sqrtf are those of "Surface evaluation"

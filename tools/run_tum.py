@@ -16,6 +16,7 @@ has a ground truth, prints the ATE RMSE.
                             [--point-cloud PATH]
                             [--ground-truth-surface FILE.ply] [--surface-max-distance M] [--surface-thresholds M,M,...]
                             [--surfel-mesh-distance] [--surface-report FILE.json] [--register-surface] [--surface-sample-spacing M]
+                            [--surface-visible-only] [--surface-visibility-margin M]
                             [--mesh-deviation]
 
 --pyramid-level-for-depth / --pyramid-level-for-color (0 ... 3): the stream is halved L times on the GPU before anything else
@@ -92,6 +93,11 @@ side that has triangles (DirectBA.SampleMesh; surface_eval.evaluate(sample_densi
 no longer depend on how either mesh is tessellated; the numbers of samples are printed and reported.
 --surface-max-distance inf: no search radius.  Both directions then run through a bounding-volume hierarchy (DirectBA.NearestTriangle;
 surface_eval.evaluate(max_distance=None)), every point hits and nothing is `beyond`; --register-surface needs a finite radius.
+--surface-visible-only: completeness and recall are taken over the part of the ground truth the run could have observed -- the points
+seen from at least one keyframe pose of the run, inside the depth camera's image, within --max-depth, facing the camera and not
+occluded by the ground-truth mesh itself (DirectBA.MeshVisibility; surface_eval.evaluate(visible_from=...)); the report then also
+holds completeness_all and visibility.  --surface-visibility-margin M: the segment to a point ends M metres before it, default 0.02.
+The ground truth has to be a mesh.
 --mesh-deviation: how far the --mesh-* operators moved the surface -- the mesh as written against the mesh as extracted, both ways and
 without a radius (surface_eval.deviation: mean, rmse and max per direction, the Hausdorff distance, and the operators that ran); at
 the vertices, or at samples when --surface-sample-spacing is given.
@@ -220,7 +226,7 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
         render_source="surfels", mesh_min_component=0, ground_truth_surface=None, surface_max_distance=0.1, surface_thresholds=(0.01, 0.02, 0.05),
         surfel_mesh_distance=False, surface_report=None, register_surface=False, surface_sample_spacing=None, mesh_simplify_cell=None,
         mesh_deviation=False, mesh_decimate_ratio=None, mesh_decimate_vertices=None, mesh_smooth_iterations=0, mesh_smooth_lambda=0.5, mesh_smooth_mu=-0.53,
-        mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False, mesh_orient=None):
+        mesh_smooth_boundary="fixed", mesh_fill_holes=None, mesh_clean=False, mesh_orient=None, surface_visible_only=False, surface_visibility_margin=0.02):
     """inspect: called with the BadSlam object and the result dict before the run returns, while the model is still alive."""
     if mesh_decimate_ratio is not None and mesh_decimate_vertices is not None:
         raise ValueError("give at most one of --mesh-decimate-ratio and --mesh-decimate-vertices")
@@ -338,9 +344,14 @@ def run(dataset_dir, trajectory=None, out=None, keyframe_interval=10, ba_iterati
                 aligned = ate.ate_files(os.path.join(str(dataset_dir), trajectory), out)
                 start = np.eye(4)
                 start[:3, :3], start[:3, 3] = aligned["R"], aligned["t"]
+            visible = {}
+            if surface_visible_only:    # completeness over what the keyframes could have observed: their poses, the depth camera, the run's depth range
+                ba = slam.ba()
+                kf_poses = [ba.keyframe_pose(k) for k in range(ba.keyframe_count()) if not ba.keyframe_is_deleted(k)]
+                visible = dict(visible_from=dict(poses=kf_poses, max_depth=float(max_depth), margin=float(surface_visibility_margin)))
             surface.update(surface_eval.evaluate(slam.ba(), m, dba.LoadPLY(ground_truth_surface), radius, tuple(surface_thresholds),
                                                  register=bool(register_surface), initial=start,
-                                                 sample_density=None if surface_sample_spacing is None else 1.0 / (float(surface_sample_spacing) ** 2)))
+                                                 sample_density=None if surface_sample_spacing is None else 1.0 / (float(surface_sample_spacing) ** 2), **visible))
         if surfel_mesh_distance:
             if radius is None:      # the centres of ExportToPointCloud, in its order, against the mesh as extracted
                 centre_distance = slam.ba().NearestTriangle(slam.ba().ExportToPointCloud()[0], as_extracted)["distance"]
@@ -434,6 +445,8 @@ def arg_parser():
     ap.add_argument("--surface-report", default=None)
     ap.add_argument("--register-surface", action="store_true")
     ap.add_argument("--surface-sample-spacing", type=float, default=None)
+    ap.add_argument("--surface-visible-only", action="store_true")
+    ap.add_argument("--surface-visibility-margin", type=float, default=0.02)
     return ap
 
 
@@ -447,6 +460,7 @@ def main():
             render_source=a.render_source, mesh_min_component=a.mesh_min_component, ground_truth_surface=a.ground_truth_surface,
             surface_max_distance=a.surface_max_distance, surface_thresholds=a.surface_thresholds, surfel_mesh_distance=a.surfel_mesh_distance,
             surface_report=a.surface_report, register_surface=a.register_surface, surface_sample_spacing=a.surface_sample_spacing,
+            surface_visible_only=a.surface_visible_only, surface_visibility_margin=a.surface_visibility_margin,
             mesh_deviation=a.mesh_deviation, mesh_simplify_cell=a.mesh_simplify_cell, mesh_decimate_ratio=a.mesh_decimate_ratio, mesh_decimate_vertices=a.mesh_decimate_vertices,
             mesh_smooth_iterations=a.mesh_smooth_iterations, mesh_smooth_lambda=a.mesh_smooth_lambda, mesh_smooth_mu=a.mesh_smooth_mu,
             mesh_smooth_boundary=a.mesh_smooth_boundary, mesh_fill_holes=a.mesh_fill_holes, mesh_clean=a.mesh_clean, mesh_orient=a.mesh_orient)
@@ -518,6 +532,11 @@ def main():
         if "accuracy" in sf:
             within = "no search radius" if sf["max_distance"] is None else f"within {sf['max_distance']:g} m"
             print(surface_eval.format_summary(f"accuracy (mesh -> {sf['ground_truth']}, {within})", sf["accuracy"]))
+            if "visibility" in sf:
+                vs = sf["visibility"]
+                print(f"visible from the {vs['views']} keyframes (margin {vs['margin']:g} m): {vs['visible_points']} of {vs['points']} ground-truth points "
+                      f"({100 * vs['visible_fraction']:.1f} %); completeness and recall are over these")
+                print(surface_eval.format_summary("completeness over all points", sf["completeness_all"]))
             print(surface_eval.format_summary("completeness (ground truth -> mesh)", sf["completeness"]))
             for row in sf["f_scores"]:
                 print(f"  at {row['threshold']:g} m: precision {row['precision']:.4f}, recall {row['recall']:.4f}, F-score {row['f_score']:.4f}")
